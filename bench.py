@@ -2,6 +2,13 @@
 """Headline benchmark: Gvoxel-projections/s of the TSDF depth-map fusion path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg1|NxM@WxH] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline, its roofline from the timed
+steps themselves and the brick-class histogram of the last step.  Everything that takes runs of its own -- scenes,
+roofline_valu, box_state, ablation, end_to_end, cell_to_point, coloration and cpu_baseline below, and the strong-scaling
+objects of N > 1 -- is measured only with --full (each still subject to its --no-* switch).  --dump-outputs DIR writes
+what the last timed step computed (dump_outputs) after the timed steps.
 
 A step = one pass of the hot path over one batch of synthetic input: zero the grid, fuse every HBM-resident depth map
 of this rank into it and, for N > 1, sum the f32 grids of the ranks over RCCL (the path's only exchange step; issued
@@ -266,6 +273,33 @@ def end_to_end_probe(scene, capi, grid, ray, views, host_dtype, grid_dtype, pcie
             "pcie_floor_s": floor, "seconds_over_floor": dt / floor, "seconds_of_calls": [round(t, 6) for t in times[1:]]}
 
 
+DUMP_SAMPLES = 1 << 21   # grid values kept by dump_outputs: 8 MB (f32) or 16 MB (f64) of values + 16 MB of indices
+DUMP_SEED = 2024
+
+
+def dump_outputs(dirname: str, grid) -> None:
+    """What a caller of the timed path receives -- the fused grid -- as .npy files that two builds can be compared by:
+      grid_sample.npy        the grid's values (its own dtype, f32 or f64) at DUMP_SAMPLES flat indices: one seeded index
+                             drawn in each of DUMP_SAMPLES equal strides of the flat grid, the same for every run of a grid
+                             size; every voxel when the grid has no more than DUMP_SAMPLES
+      grid_sample_index.npy  those flat indices ([z][y][x] order), f64
+      grid_summary.npy       f64 [voxels, sum, sum of |v|, min, max, non-zero voxels] over the WHOLE grid"""
+    flat = np.asarray(grid).reshape(-1)
+    n = flat.size
+    if n <= DUMP_SAMPLES:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        stride = n // DUMP_SAMPLES
+        rng = np.random.default_rng(DUMP_SEED)
+        idx = np.arange(DUMP_SAMPLES, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_SAMPLES, dtype=np.int64)
+    summary = np.array([n, np.sum(flat, dtype=np.float64), np.sum(np.abs(flat), dtype=np.float64), flat.min(), flat.max(),
+                        np.count_nonzero(flat)], dtype=np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "grid_sample.npy"), np.ascontiguousarray(flat[idx]))
+    np.save(os.path.join(dirname, "grid_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "grid_summary.npy"), summary)
+
+
 # ---- launching -------------------------------------------------------------------------------------------------
 def free_port() -> int:
     s = socket.socket()
@@ -346,7 +380,16 @@ def main():
     ap.add_argument("--coloration-vertices", type=int, default=2_000_000)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: box_state, ablation and roofline_valu, cell_to_point, scenes, end_to_end, "
+                         "coloration, cpu_baseline (N = 1) and the strong-scaling objects (N > 1); without it the run does only "
+                         "what the headline needs, as if every --no-* switch were given")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the grid the last step fused as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_ablation = args.no_coloration = args.no_end_to_end = args.no_scenes = True
+        args.no_strong = True
     global HOLE_FRACTION
     HOLE_FRACTION = args.hole_fraction
 
@@ -442,7 +485,9 @@ def main():
     ctx.clear_views()
     upload_first_call_ms = ctx.upload_kernel_ms()[1]
     t_up = time.perf_counter()
-    views = upload_scene(ctx, scene, args.scene, maps_per_gpu, W, H, spacing, keep_host=True)
+    # (a host copy of the views only for the measurements that fuse them again elsewhere)
+    keep_host = not (args.no_ablation and args.no_end_to_end and args.no_cpu_baseline)
+    views = upload_scene(ctx, scene, args.scene, maps_per_gpu, W, H, spacing, keep_host=keep_host)
     upload_s = time.perf_counter() - t_up
     upload_kernels_ms = ctx.upload_kernel_ms()[1] - upload_first_call_ms
     info = ctx.info()
@@ -473,9 +518,11 @@ def main():
 
     dt, kern_ms = timed(args.steps, args.warmup)
     main_ms = timed.main_ms  # the fusion kernel proper (what rocprofv3 lists as fuse_tile_kernel / fuse_kernel)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.download_grid(np_grid))
     # what this box's vector units sustain right now on bare fp64 FMAs: boxes of the same model differ (the same library
     # has measured 5.0 and 7.1 ms per fusion kernel within the hour), and the fusion kernel is bound by fp64 vector issue
-    fp64_now = capi.fp64_probe(local_rank, 20.0)
+    fp64_now = capi.fp64_probe(local_rank, 20.0) if args.full else None
     ms_per_step = dt / args.steps * 1e3
     value = n_vox * maps_per_gpu * args.steps / dt / 1e9
 
@@ -507,18 +554,20 @@ def main():
         del default_grid
 
     # the step right after the path: cell data -> point data of the fused grid, HBM-bound
-    ts = []
-    for _ in range(4):
-        step()                      # a context-owned grid keeps its point data until the grid changes: change it
-        ctx.cell_to_point()
-        ctx.synchronize()
-        ts.append(ctx.timings().last_cell_to_point_ms)
-    c2p_ms = float(np.median(ts[1:]))
-    n_pts = (cells[0] + 1) * (cells[1] + 1) * (cells[2] + 1)
-    c2p_bytes = float(grid_bytes * n_vox + 8 * n_pts)
-    cell_to_point = {"kernel": "dmi::cell_to_point_kernel", "kernel_ms": c2p_ms, "bound": "hbm",
-                     "algorithmic_bytes": c2p_bytes, "achieved": c2p_bytes / (c2p_ms * 1e-3) / 1e9,
-                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": c2p_bytes / (c2p_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+    cell_to_point = None
+    if args.full:
+        ts = []
+        for _ in range(4):
+            step()                      # a context-owned grid keeps its point data until the grid changes: change it
+            ctx.cell_to_point()
+            ctx.synchronize()
+            ts.append(ctx.timings().last_cell_to_point_ms)
+        c2p_ms = float(np.median(ts[1:]))
+        n_pts = (cells[0] + 1) * (cells[1] + 1) * (cells[2] + 1)
+        c2p_bytes = float(grid_bytes * n_vox + 8 * n_pts)
+        cell_to_point = {"kernel": "dmi::cell_to_point_kernel", "kernel_ms": c2p_ms, "bound": "hbm",
+                         "algorithmic_bytes": c2p_bytes, "achieved": c2p_bytes / (c2p_ms * 1e-3) / 1e9,
+                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": c2p_bytes / (c2p_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS}
 
     # the other scene kinds on the same context, timed like the headline (fewer steps): what the path does when the depth
     # tables change character -- every pixel valid (dense), 10 % invalid speckle (speckle), speckle + noise + holes (noisy)
@@ -634,14 +683,18 @@ def main():
         "view_paths": ctx.view_paths(),
         # what actually bounds the default path: instruction issue (issue_roofline below)
         "roofline_issue": issue_roofline(issue_counts, main_ms),
-        "box_state": {"fp64_vector_tflops_now": fp64_now, "peak": FP64_VECTOR_PEAK_TFLOPS,
-                      "note": "dmi_fp64_probe right after the timed steps: independent v_fma_f64 chains on every SIMD for 20 ms"},
     }
+    if not args.full:
+        del out["roofline_valu"]   # (its time is the ablation's: brick classes off)
+    if fp64_now is not None:
+        out["box_state"] = {"fp64_vector_tflops_now": fp64_now, "peak": FP64_VECTOR_PEAK_TFLOPS,
+                            "note": "dmi_fp64_probe right after the timed steps: independent v_fma_f64 chains on every SIMD for 20 ms"}
     if ablation:
         out["ablation"] = ablation
     if scenes:
         out["scenes"] = scenes
-    out["cell_to_point"] = cell_to_point
+    if cell_to_point is not None:
+        out["cell_to_point"] = cell_to_point
     if not args.no_end_to_end:
         pcie = capi.pcie_probe(local_rank)
         out["pcie_GBps"] = {"h2d": pcie[0], "d2h": pcie[1]}
@@ -773,11 +826,13 @@ def multi_gpu(args, capi, scene, dist, barrier, device_sync, max_over_ranks, wor
         timed.main_ms = (k1.total_fuse_main_kernel_ms - k0.total_fuse_main_kernel_ms) / max(1, steps)
         return dt, t.last_step_ms, t.last_fuse_kernel_ms
 
-    def measure(name, cells_, n_total, w, h, seed, steps, warmup, check: bool):
+    def measure(name, cells_, n_total, w, h, seed, steps, warmup, check: bool, dump: bool = False):
         g = scene.default_grid(cells_)
         m = create_agreed(g)
         upload(m, n_total, w, h, seed, shard_views=(args.partition == "views"))
         dt, step_ms, fuse_ms = timed(m, steps, warmup)
+        if dump and args.dump_outputs and rank == 0:   # rank 0's grid as dmi_multi_download_grid gives it to its caller
+            dump_outputs(args.dump_outputs, m.download_grid(np_grid)[0])
         info = m.info()
         li = m.local_info(0)
         views_rank0 = int(li.n_views)
@@ -815,7 +870,7 @@ def multi_gpu(args, capi, scene, dist, barrier, device_sync, max_over_ranks, wor
 
     # weak: every rank `maps_per_gpu` views of its own = the shares of one (N x maps)-camera scene
     weak, info = measure(f"{args.workload} x {n_ranks} (weak: {maps_per_gpu} views per GPU)", cells, maps_per_gpu * n_ranks, W, H,
-                         1000, args.steps, args.warmup, check=False)
+                         1000, args.steps, args.warmup, check=False, dump=True)
     strong = []
     if not args.no_strong:
         # the fixed problems: the same `maps_per_gpu` views as the 1-GPU run, and BASELINE.json's cfg4

@@ -27,7 +27,7 @@ def _line(cmd, env=None):
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_device_peer_copy():
     d = _line([sys.executable, "bench.py", "--gpus", "2", "--exchange", "peer_copy", "--share-device", "--workload", WORKLOAD,
-               "--steps", "2", "--warmup", "1"])
+               "--steps", "2", "--warmup", "1", "--full"])
     assert d["n_gpus"] == 2 and d["metric"] == "Gvoxel-projections/s" and d["value"] > 0
     assert d["config"]["ranks_share_device_0"] and d["config"]["rccl_ranks"] == 0 and d["config"]["processes"] == 1
     assert "fallback" not in d["config"]
@@ -49,7 +49,7 @@ def test_bench_two_processes_fall_back_to_z_slabs_on_one_device():
     s.close()
     d = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), "bench.py", "--gpus", "2", "--share-device", "--workload", WORKLOAD, "--steps", "2",
-               "--warmup", "1"], env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
+               "--warmup", "1", "--full"], env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert d["n_gpus"] == 2 and d["config"]["processes"] == 2 and d["value"] > 0
     assert "z-slab" in d["config"].get("fallback", ""), d["config"]
     assert d["config"]["parallelism"].startswith("z-slabs x2")

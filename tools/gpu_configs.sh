@@ -3,17 +3,18 @@
 # Usage: tools/gpu_configs.sh <tag>
 set -u
 TAG=${1:-r01}
-mkdir -p gpurun_out
+LOG=${LOG:-build/logs}   # where the logs and result lines go
+mkdir -p $LOG
 export TMPDIR=/tmp
-OUT=gpurun_out/configs_$TAG.jsonl
+OUT=$LOG/configs_$TAG.jsonl
 : > $OUT
 run() {  # name, extra args...
   local name=$1; shift
   echo "== $name $*" >&2
-  timeout -k 10 600 python bench.py --steps 5 --warmup 2 --no-ablation --no-coloration --no-end-to-end --no-scenes "$@" 2> gpurun_out/configs_$TAG.$name.err | tail -1 > gpurun_out/configs_$TAG.$name.json
+  timeout -k 10 600 python bench.py --full --steps 5 --warmup 2 --no-ablation --no-coloration --no-end-to-end --no-scenes "$@" 2> $LOG/configs_$TAG.$name.err | tail -1 > $LOG/configs_$TAG.$name.json
   local rc=$?
-  if [ -s gpurun_out/configs_$TAG.$name.json ]; then
-    python - "$name" gpurun_out/configs_$TAG.$name.json >> $OUT <<'PY'
+  if [ -s $LOG/configs_$TAG.$name.json ]; then
+    python - "$name" $LOG/configs_$TAG.$name.json >> $OUT <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))
 d["config_name"] = sys.argv[1]
