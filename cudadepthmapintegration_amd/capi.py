@@ -102,6 +102,7 @@ ABI_SYMBOLS = [
     "dmi_point_data_device_pointer", "dmi_color_create", "dmi_color_destroy", "dmi_color_add_views",
     "dmi_color_clear_views", "dmi_color_process", "dmi_color_get_kernel_ms", "dmi_get_mixed_reason_histogram", "dmi_get_window_pair_count", "dmi_get_view_paths", "dmi_get_upload_kernel_ms", "dmi_sizeof_info", "dmi_sizeof_timings",
     "dmi_color_set_scratch_budget", "dmi_color_set_vertex_reorder", "dmi_iso_active_cells",
+    "dmi_extract_isosurface", "dmi_download_isosurface", "dmi_get_isosurface_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -170,6 +171,10 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "dmi_iso_active_cells"):  # (an older build loaded for an A/B, tools/gpu_exp.py, lacks the newest entry points)
         L.dmi_iso_active_cells.argtypes = [vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64),
                                            ctypes.c_uint64]
+    if hasattr(L, "dmi_extract_isosurface"):
+        L.dmi_extract_isosurface.argtypes = [vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.dmi_download_isosurface.argtypes = [vp, dp, ctypes.POINTER(ctypes.c_int64)]
+        L.dmi_get_isosurface_kernel_ms.argtypes = [vp, dp]
     L.dmi_get_brick_class_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dmi_get_mixed_reason_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_get_window_pair_count"):  # (absent from an older prebuilt library loaded for an A/B timing, tools/gpu_exp.py)
@@ -443,6 +448,22 @@ class FusionContext:
             self._check(self._lib.dmi_iso_active_cells(self._h, float(iso), ctypes.byref(n),
                                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), out.size))
         return int(n.value), out
+
+    def extract_isosurface(self, iso: float):
+        """(vertices [n, 3] f64 world coordinates, triangles [m, 3] int64): marching cubes over the point data at `iso` on the
+        device (dmi_extract_isosurface + dmi_download_isosurface; Reconstruction/main.cxx:166-182)."""
+        nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.dmi_extract_isosurface(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
+        verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
+        tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
+        self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return verts[:int(nv.value)], tris[:int(nt.value)]
+
+    def isosurface_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last extract_isosurface (dmi_get_isosurface_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_isosurface_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
 
     def brick_class_histogram(self) -> dict:
         """(brick, view) pairs of the last fuse by proven class (diagnostic)."""
@@ -824,7 +845,7 @@ HOST_ABI_SYMBOLS = [
     "dmi_filter_get_fuse_kernel_ms", "dmi_filter_get_number_of_cells", "dmi_filter_get_output",
     "dmi_filter_last_error", "dmi_read_krtd_file", "dmi_extract_all_file_path", "dmi_k3_to_k4",
     "dmi_apply_depth_threshold", "dmi_read_depth_map", "dmi_read_depth_map_color", "dmi_mesh_coloration_from_lists",
-    "dmi_cli_read_arguments", "dmi_cli_main",
+    "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata",
 ]
 
 _host_bound = False
@@ -876,6 +897,8 @@ def load_host() -> ctypes.CDLL:
     L.dmi_mesh_coloration_from_lists.restype = ctypes.c_int
     L.dmi_mesh_coloration_from_lists.argtypes = [dp, i64, ctypes.c_char_p, ctypes.c_char_p, i32, ctypes.POINTER(ctypes.c_uint8),
                                                  ctypes.POINTER(ctypes.c_uint8), ip, ctypes.c_char_p, ctypes.c_size_t]
+    L.dmi_write_polydata.restype = ctypes.c_int
+    L.dmi_write_polydata.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64]
     _host_bound = True
     return L
 
@@ -977,7 +1000,7 @@ class CliOptionsC(ctypes.Structure):
                 ("grid_end", ctypes.c_double * 3), ("grid_matrix", ctypes.c_double * 16), ("ray_thick", ctypes.c_double),
                 ("ray_rho", ctypes.c_double), ("ray_eta", ctypes.c_double), ("ray_delta", ctypes.c_double),
                 ("thresh_best_cost", ctypes.c_double), ("contour", ctypes.c_double), ("verbose", ctypes.c_int32),
-                ("summary", ctypes.c_int32), ("force_cubic_voxel", ctypes.c_int32)]
+                ("summary", ctypes.c_int32), ("force_cubic_voxel", ctypes.c_int32), ("extract_mesh", ctypes.c_int32)]
 
 
 def cli_read_arguments(args):
@@ -992,6 +1015,16 @@ def cli_read_arguments(args):
     err = ctypes.create_string_buffer(1 << 15)
     ok = L.dmi_cli_read_arguments(len(args), argv, ctypes.byref(out), err, len(err))
     return (out if ok else None), err.value.decode()
+
+
+def write_polydata(path, points, triangles):
+    """dmi_write_polydata: points [n, 3] f64 and triangles [m, 3] int64 as a VTK XML PolyData (.vtp) file; no GPU needed."""
+    L = load_host()
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    ok = L.dmi_write_polydata(os.fsencode(path), _dp(p), p.shape[0], t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), t.shape[0])
+    if not ok:
+        raise OSError(f"dmi_write_polydata failed: {path}")
 
 
 def cli_binary() -> str:

@@ -130,6 +130,21 @@ struct dmi_context {
   hipEvent_t c2p_start = nullptr, c2p_stop = nullptr;
   bool c2p_pending = false;
 
+  // dmi_extract_isosurface (isosurface.hip): per-segment counts / bases and the scan's storage, kept while large enough;
+  // the mesh of the last call
+  uint32_t *d_mesh_counts = nullptr;
+  uint64_t *d_mesh_bases = nullptr;
+  size_t mesh_segments_capacity = 0;
+  void *d_mesh_scan_temp = nullptr;
+  uint64_t mesh_scan_temp_capacity = 0;
+  double *d_mesh_vertices = nullptr;
+  int64_t *d_mesh_triangles = nullptr;
+  uint64_t mesh_vertex_capacity = 0, mesh_triangle_capacity = 0;
+  uint64_t mesh_vertices = 0, mesh_triangles = 0;
+  bool mesh_valid = false;
+  hipEvent_t mesh_events[4] = {nullptr, nullptr, nullptr, nullptr};  // around the count pass + scans, and the write pass
+  double last_isosurface_kernel_ms = 0.0;
+
   void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
   double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
   size_t stage_capacity = 0;  // elements per staging buffer
@@ -1023,6 +1038,13 @@ void dmi_destroy(dmi_context *ctx) {
   if (ctx->d_points) (void)hipFree(ctx->d_points);
   if (ctx->c2p_start) (void)hipEventDestroy(ctx->c2p_start);
   if (ctx->c2p_stop) (void)hipEventDestroy(ctx->c2p_stop);
+  if (ctx->d_mesh_counts) (void)hipFree(ctx->d_mesh_counts);
+  if (ctx->d_mesh_bases) (void)hipFree(ctx->d_mesh_bases);
+  if (ctx->d_mesh_scan_temp) (void)hipFree(ctx->d_mesh_scan_temp);
+  if (ctx->d_mesh_vertices) (void)hipFree(ctx->d_mesh_vertices);
+  if (ctx->d_mesh_triangles) (void)hipFree(ctx->d_mesh_triangles);
+  for (hipEvent_t e : ctx->mesh_events)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->slab_events) (void)hipEventDestroy(e);
   if (ctx->download_stream) (void)hipStreamDestroy(ctx->download_stream);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1870,6 +1892,134 @@ int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t 
   rc = drain_c2p(ctx);
   if (rc != DMI_OK) return rc;
   return drain_events(ctx);
+  });
+}
+
+namespace {
+// grows a context-owned device buffer to hold `bytes`: the old contents are not kept
+int ensure_buffer(dmi_context *ctx, void **ptr, uint64_t *capacity, uint64_t bytes) {
+  if (*ptr && *capacity >= bytes) return DMI_OK;
+  if (*ptr) {
+    DMI_HIP(ctx, hipFree(*ptr));
+    ctx->device_bytes -= *capacity;
+    *ptr = nullptr;
+    *capacity = 0;
+  }
+  DMI_HIP(ctx, hipMalloc(ptr, (size_t)bytes));
+  ctx->device_bytes += bytes;
+  *capacity = bytes;
+  return DMI_OK;
+}
+}  // namespace
+
+int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_extract_isosurface", [&]() -> int {
+  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: null argument");
+  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: the iso-value is a NaN");
+  if (ctx->opt.z_first != 0)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: the context holds a z-slab (z_first != 0); its lattice is not the grid's");
+  *n_vertices = *n_triangles = 0;
+  ctx->mesh_valid = false;
+  const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
+  const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
+  if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: grid too large for one launch");
+  int rc = dmi_cell_to_point(ctx);  // the contour filter reads the point data (Reconstruction/main.cxx:151-173)
+  if (rc != DMI_OK) return rc;
+  dmi::MeshGeom g{};
+  g.nx = nx;
+  g.ny = ny;
+  g.nz = nz;
+  g.segs_per_row = (int)((nx + 1 + 255) / 256);
+  g.iso = iso;
+  for (int a = 0; a < 3; ++a) {
+    g.origin[a] = ctx->grid.origin[a];
+    g.spacing[a] = ctx->grid.spacing[a];
+  }
+  for (int e = 0; e < 12; ++e) g.m[e] = ctx->grid.grid_matrix[e];
+  uint64_t cap = ctx->mesh_segments_capacity;
+  if (cap < n_seg + 1) {
+    uint64_t c32 = cap * 2 * sizeof(uint32_t), c64 = cap * 2 * sizeof(uint64_t);
+    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_counts, &c32, (uint64_t)(n_seg + 1) * 2 * sizeof(uint32_t));
+    if (rc != DMI_OK) return rc;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_bases, &c64, (uint64_t)(n_seg + 1) * 2 * sizeof(uint64_t));
+    if (rc != DMI_OK) return rc;
+    ctx->mesh_segments_capacity = n_seg + 1;
+  }
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::launch_isosurface_count(nullptr, g, ctx->d_mesh_counts, ctx->d_mesh_bases, nullptr, &temp_bytes, ctx->stream));
+  rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_scan_temp, &ctx->mesh_scan_temp_capacity, std::max<uint64_t>(temp_bytes, 16));
+  if (rc != DMI_OK) return rc;
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  if (!ctx->mesh_events[0])
+    for (hipEvent_t &e : ctx->mesh_events) DMI_HIP(ctx, hipEventCreate(&e));
+  // the trailing zeros behind each count array: bases[n_seg] and bases[2 n_seg + 1] become the totals
+  DMI_HIP(ctx, hipMemsetAsync(ctx->d_mesh_counts + n_seg, 0, sizeof(uint32_t), ctx->stream));
+  DMI_HIP(ctx, hipMemsetAsync(ctx->d_mesh_counts + 2 * n_seg + 1, 0, sizeof(uint32_t), ctx->stream));
+  DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[0], ctx->stream));
+  DMI_HIP(ctx, dmi::launch_isosurface_count(ctx->d_points, g, ctx->d_mesh_counts, ctx->d_mesh_bases, ctx->d_mesh_scan_temp,
+                                            &temp_bytes, ctx->stream));
+  DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[1], ctx->stream));
+  uint64_t totals[2] = {0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&totals[0], ctx->d_mesh_bases + n_seg, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&totals[1], ctx->d_mesh_bases + 2 * n_seg + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // vertex and triangle ids are int64 (vtkIdType) and the buffers' byte sizes must fit a size_t: refused, never wrapped
+  const uint64_t id_limit = (uint64_t)std::numeric_limits<int64_t>::max() / 24;
+  if (totals[0] > id_limit || totals[1] > id_limit)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: mesh too large for int64 ids");
+  g.n_vertices = totals[0];
+  g.n_triangles = totals[1];
+  float ms_count = 0.f, ms_write = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms_count, ctx->mesh_events[0], ctx->mesh_events[1]));
+  if (totals[0] > 0) {
+    uint64_t vcap = ctx->mesh_vertex_capacity * 24, tcap = ctx->mesh_triangle_capacity * 24;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_vertices, &vcap, totals[0] * 24);
+    if (rc != DMI_OK) return rc;
+    ctx->mesh_vertex_capacity = vcap / 24;
+    if (totals[1] > 0) {
+      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_triangles, &tcap, totals[1] * 24);
+      if (rc != DMI_OK) return rc;
+      ctx->mesh_triangle_capacity = tcap / 24;
+    }
+    DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[2], ctx->stream));
+    DMI_HIP(ctx, dmi::launch_isosurface_write(ctx->d_points, g, ctx->d_mesh_bases, ctx->d_mesh_vertices, ctx->d_mesh_triangles,
+                                              ctx->stream));
+    DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[3], ctx->stream));
+    DMI_HIP(ctx, hipEventSynchronize(ctx->mesh_events[3]));
+    DMI_HIP(ctx, hipEventElapsedTime(&ms_write, ctx->mesh_events[2], ctx->mesh_events[3]));
+  }
+  ctx->last_isosurface_kernel_ms = (double)ms_count + (double)ms_write;
+  ctx->mesh_vertices = totals[0];
+  ctx->mesh_triangles = totals[1];
+  ctx->mesh_valid = true;
+  *n_vertices = totals[0];
+  *n_triangles = totals[1];
+  rc = drain_c2p(ctx);
+  if (rc != DMI_OK) return rc;
+  return drain_events(ctx);
+  });
+}
+
+int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangles) {
+  return guarded(ctx, "dmi_download_isosurface", [&]() -> int {
+  if (!ctx || !vertices || !triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: null argument");
+  if (!ctx->mesh_valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: no mesh (dmi_extract_isosurface has not succeeded)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (ctx->mesh_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(vertices, ctx->d_mesh_vertices, (size_t)ctx->mesh_vertices * 24, hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->mesh_triangles)
+    DMI_HIP(ctx, hipMemcpyAsync(triangles, ctx->d_mesh_triangles, (size_t)ctx->mesh_triangles * 24, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_kernel_ms: null argument");
+  *last = ctx->last_isosurface_kernel_ms;
+  return DMI_OK;
   });
 }
 

@@ -420,4 +420,21 @@ hipError_t launch_iso_count(const double *points, int nx, int ny, int nz, double
 hipError_t launch_iso_write(const double *points, int nx, int ny, int nz, double iso, const uint64_t *bases, int64_t *ids,
                             uint64_t capacity, hipStream_t stream);
 
+// Marching cubes over the point data (isosurface.hip): segments of 256 lattice points of one x-row.
+struct MeshGeom {
+  int nx, ny, nz, segs_per_row;
+  double iso;
+  double origin[3], spacing[3];
+  double m[12];                      // rows 0..2 of the grid matrix, row-major
+  uint64_t n_vertices, n_triangles;  // sizes of the write pass's output buffers
+};
+int isosurface_max_triangles_per_cell();
+size_t isosurface_segment_count(int nx, int ny, int nz);
+// counts / bases: 2 (segments + 1) entries, vertices then triangles; counts[segments] and counts[2 segments + 1] are zeros the
+// caller keeps there, so bases[segments] and bases[2 segments + 1] receive the totals
+hipError_t launch_isosurface_count(const double *points, const MeshGeom &g, uint32_t *counts, uint64_t *bases, void *scan_temp,
+                                   size_t *scan_temp_bytes, hipStream_t stream);
+hipError_t launch_isosurface_write(const double *points, const MeshGeom &g, const uint64_t *bases, double *verts, int64_t *tris,
+                                   hipStream_t stream);
+
 }  // namespace dmi

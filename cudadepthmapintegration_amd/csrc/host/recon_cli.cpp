@@ -88,12 +88,15 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
       {"--rayDelta", {Kind::kValue, "ray potential: reach around a surface, not below --rayThick (default 0.3)", into_double(&o->rayDelta)}},
       {"--threshBestCost", {Kind::kValue, "depths whose best cost exceeds this are dropped (default 0.14)", into_double(&o->threshBestCost)}},
       {"--gridEnd", {Kind::kMulti, "last corner of the grid (required)", into_vector(&o->gridEnd)}},
-      {"--contour", {Kind::kValue, "iso value (recorded only: this tool extracts no surface; default 1.0)", into_double(&o->contour)}},
-      {"--outputMeshFilename", {Kind::kValue, "mesh file name (.vtp, required by the reference's checks; not written)", into_string(&o->outputMeshFilename)}},
+      {"--contour", {Kind::kValue, "iso value (default 1.0; a surface is extracted only with --extractMesh)", into_double(&o->contour)}},
+      {"--outputMeshFilename", {Kind::kValue, "mesh file name (.vtp, required by the reference's checks; written only with --extractMesh)", into_string(&o->outputMeshFilename)}},
       {"--verbose", {Kind::kFlag, "print progress and the parameters", into_flag(&o->verbose)}},
       {"--summary", {Kind::kFlag, "write summary.txt into the data folder", into_flag(&o->summary)}},
       {"--forceCubicVoxel", {Kind::kFlag, "use the smallest of the three spacings on every axis", into_flag(&o->forceCubicVoxel)}},
       {"--device", {Kind::kMulti, "HIP device ordinal(s); several = one fusion over several GPUs (not in the reference)", into_vector(&o->devices)}},
+      {"--extractMesh", {Kind::kFlag, "extract the iso-surface at --contour on the GPU and write it to --outputMeshFilename: points and "
+                                      "triangles only, without the Normals and scalar arrays VTK's contour filter adds (not in the reference)",
+                         into_flag(&o->extractMesh)}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -326,6 +329,47 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
   return true;
 }
 
+bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
+                   std::string *error) {
+  if (nPoints < 0 || nTriangles < 0) {
+    *error = "WritePolyData: negative count";
+    return false;
+  }
+  std::ofstream out(path, std::ios::binary);
+  if (!out) {
+    *error = "WritePolyData: cannot open " + path;
+    return false;
+  }
+  const uint64_t point_bytes = (uint64_t)nPoints * 3 * sizeof(double), conn_bytes = (uint64_t)nTriangles * 3 * sizeof(int64_t),
+                 offset_bytes = (uint64_t)nTriangles * sizeof(int64_t);
+  out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
+         "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
+      << nPoints << "\" NumberOfVerts=\"0\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"" << nTriangles
+      << "\">\n      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" format=\"appended\" "
+         "offset=\"0\"/>\n      </Points>\n      <Polys>\n        <DataArray type=\"Int64\" Name=\"connectivity\" format=\"appended\" offset=\""
+      << sizeof(uint64_t) + point_bytes << "\"/>\n        <DataArray type=\"Int64\" Name=\"offsets\" format=\"appended\" offset=\""
+      << 2 * sizeof(uint64_t) + point_bytes + conn_bytes
+      << "\"/>\n      </Polys>\n    </Piece>\n  </PolyData>\n  <AppendedData encoding=\"raw\">\n   _";
+  out.write(reinterpret_cast<const char *>(&point_bytes), sizeof(point_bytes));
+  out.write(reinterpret_cast<const char *>(points), (std::streamsize)point_bytes);
+  out.write(reinterpret_cast<const char *>(&conn_bytes), sizeof(conn_bytes));
+  out.write(reinterpret_cast<const char *>(triangles), (std::streamsize)conn_bytes);
+  out.write(reinterpret_cast<const char *>(&offset_bytes), sizeof(offset_bytes));
+  std::vector<int64_t> offsets((size_t)std::min<int64_t>(nTriangles, int64_t(1) << 20));
+  for (int64_t done = 0; done < nTriangles;) {  // 3, 6, 9, ... in pieces
+    const int64_t n = std::min<int64_t>(nTriangles - done, (int64_t)offsets.size());
+    for (int64_t q = 0; q < n; ++q) offsets[(size_t)q] = 3 * (done + q + 1);
+    out.write(reinterpret_cast<const char *>(offsets.data()), (std::streamsize)(n * sizeof(int64_t)));
+    done += n;
+  }
+  out << "\n  </AppendedData>\n</VTKFile>\n";
+  if (!out) {
+    *error = "WritePolyData: write failed: " + path;
+    return false;
+  }
+  return true;
+}
+
 namespace {
 
 void describe(const Options &o, std::ostream &out, bool with_sketch) {
@@ -346,7 +390,8 @@ void describe(const Options &o, std::ostream &out, bool with_sketch) {
            "                          -delta  -thick  0  +thick  (distance behind the surface)\n";
   out << "  thickness  " << o.rayThick << " (about " << o.rayThick / mean_voxel << " voxels)\n  rho        " << o.rayRho
       << "\n  eta        " << o.rayEta << "\n  delta      " << o.rayDelta << " (about " << o.rayDelta / mean_voxel
-      << " voxels)\nother\n  contour value  " << o.contour << " (no surface is extracted by this tool)\n";
+      << " voxels)\nother\n  contour value  " << o.contour
+      << (o.extractMesh ? " (surface extracted: --extractMesh)\n" : " (no surface is extracted by this tool)\n");
 }
 
 }  // namespace
@@ -388,6 +433,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   say("** Transform cell data to point data...");
   const std::vector<double> &cells = filter.GetOutputScalars();
   std::vector<double> points((size_t)dims[0] * dims[1] * dims[2]);
+  std::vector<double> meshVertices;    // --extractMesh
+  std::vector<int64_t> meshTriangles;
+  double dummyVertex = 0.0;            // a valid pointer for an empty mesh
+  int64_t dummyTriangle = 0;
   {
     // vtkCellDataToPointData (rmain:151-155) on the GPU: the cell grid goes up once more, the point grid comes back
     dmi_grid_desc grid;
@@ -413,6 +462,20 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (rc == DMI_OK) rc = dmi_iso_active_cells(ctx, o.contour, &active, nullptr, 0);
     result->contourActiveCells = active;
     if (rc != DMI_OK) result->error = std::string("cell data -> point data: ") + dmi_last_error(ctx);
+    if (rc == DMI_OK && o.extractMesh) {
+      // vtkContourFilter + vtkTransformFilter (rmain:166-182) on the device; vtkXMLPolyDataWriter (rmain:184-187) below
+      uint64_t nv = 0, nt = 0;
+      rc = dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      if (rc == DMI_OK) {
+        meshVertices.resize((size_t)nv * 3);
+        meshTriangles.resize((size_t)nt * 3);
+        rc = dmi_download_isosurface(ctx, meshVertices.data() ? meshVertices.data() : &dummyVertex,
+                                     meshTriangles.data() ? meshTriangles.data() : &dummyTriangle);
+      }
+      if (rc != DMI_OK) result->error = std::string("iso-surface: ") + dmi_last_error(ctx);
+      result->meshVertices = nv;
+      result->meshTriangles = nt;
+    }
     if (ctx) dmi_destroy(ctx);
     if (rc != DMI_OK) return 1;
   }
@@ -421,10 +484,23 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     result->error = error;
     return 1;
   }
-  // Said whatever --verbose is: the reference writes a mesh here (rmain:166-187) and this tool does not.
-  log << "warning: " << o.outputMeshFilename << " is NOT written: the iso-surface (vtkContourFilter) is not part of this tool; "
-      << result->contourActiveCells << " of " << (long long)(dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1)
-      << " cells straddle the contour value " << o.contour << std::endl;
+  if (o.extractMesh) {
+    say("** Save mesh...");
+    if (!WritePolyData(o.outputMeshFilename, meshVertices.data(), (int64_t)result->meshVertices, meshTriangles.data(),
+                       (int64_t)result->meshTriangles, &error)) {
+      result->error = error;
+      return 1;
+    }
+    // said whatever --verbose is, like the warning below without the flag
+    log << "mesh: " << o.outputMeshFilename << ": " << result->meshVertices << " vertices, " << result->meshTriangles
+        << " triangles at the contour value " << o.contour << " (" << result->contourActiveCells << " of "
+        << (long long)(dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1) << " cells straddle it)" << std::endl;
+  } else {
+    // Said whatever --verbose is: the reference writes a mesh here (rmain:166-187) and this tool does not.
+    log << "warning: " << o.outputMeshFilename << " is NOT written: the iso-surface (vtkContourFilter) is not part of this tool; "
+        << result->contourActiveCells << " of " << (long long)(dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1)
+        << " cells straddle the contour value " << o.contour << std::endl;
+  }
   say("** Save volume...");
   if (!WriteStructuredGrid(o.outputGridFilename, dims, origin, spacing, matrix, cells.data(), ReconstructionFilter::OutputArrayName(),
                            &error)) {
@@ -439,7 +515,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     for (int i = 0; i < argc; ++i) out << " " << argv[i];
     out << "\noutput volume  " << o.outputGridFilename << "\n";
     describe(o, out, false);
-    out << "contour\n  cells straddling the value  " << result->contourActiveCells << " (no surface extracted)\n";
+    if (o.extractMesh)
+      out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
+          << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";
+    else
+      out << "contour\n  cells straddling the value  " << result->contourActiveCells << " (no surface extracted)\n";
     out << "time\n  reconstruction  " << result->reconstructionSeconds << " s\n  total           " << result->totalSeconds << " s\n";
   }
   say("---END---");

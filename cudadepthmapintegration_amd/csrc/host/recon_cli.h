@@ -3,11 +3,13 @@
 // grid's end point, the grid matrix from gridVecX/Y/Z (rmain:345-360), the filter run and the cell -> point pass
 // (rmain:110-155), and the outputs that need no VTK algorithm: the point-data volume as a compressed MetaImage
 // (rmain:157-161), the transformed volume as a .vts structured grid (rmain:189-198), the summary file (rmain:458-516).
-// NOT here: the iso-surface (vtkContourFilter, rmain:166-187) -- marching cubes is a different algorithm family and
-// SURVEY.md 8 keeps it out of this path; --outputMeshFilename is accepted and checked as the reference does, and
-// nothing is written to it.
+// The iso-surface (vtkContourFilter + vtkTransformFilter, rmain:166-187) only with --extractMesh, which the reference does
+// not have: dmi_extract_isosurface at --contour on the device, written to --outputMeshFilename as a .vtp of points and
+// triangles (no Normals, no scalar array).  Without the flag --outputMeshFilename is accepted and checked as the
+// reference does, and nothing is written to it.
 #pragma once
 
+#include <cstdint>
 #include <iosfwd>
 #include <string>
 #include <vector>
@@ -23,7 +25,7 @@ struct Options {
   std::vector<double> gridEnd;        // --gridEnd
   std::vector<double> gridVecX, gridVecY, gridVecZ;  // --gridVecX/Y/Z, defaults: the coordinate axes
   std::string outputGridFilename;     // --outputGridFilename (.vts)
-  std::string outputMeshFilename;     // --outputMeshFilename (.vtp; checked, not written)
+  std::string outputMeshFilename;     // --outputMeshFilename (.vtp; checked; written with --extractMesh only)
   std::string dataFolder;             // --dataFolder
   std::string depthMapFile = "vtiList.txt";  // --depthMapFile
   std::string krtFile = "kList.txt";         // --KRTFile
@@ -31,6 +33,7 @@ struct Options {
   double threshBestCost = 0.14;       // --threshBestCost
   double contour = 1.0;               // --contour (recorded in the summary; no contour is extracted here)
   bool verbose = false, summary = false, forceCubicVoxel = false;
+  bool extractMesh = false;           // not in the reference: write the iso-surface at --contour to --outputMeshFilename
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -47,14 +50,20 @@ struct RunResult {
   double reconstructionSeconds = 0.0, totalSeconds = 0.0;
   // cells of the point lattice whose corners straddle --contour (dmi_iso_active_cells): what a marching cubes would visit
   unsigned long long contourActiveCells = 0;
+  // --extractMesh: the size of the mesh written
+  unsigned long long meshVertices = 0, meshTriangles = 0;
   std::string error;  // empty on success
 };
-// rmain:97-213 without the contour: 0 on success.  `log` receives what --verbose prints.
+// rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);
 
 // writers (little-endian hosts)
 bool WriteMetaImage(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                     const double *pointScalars, std::string *error);
+// a triangle mesh as VTK XML PolyData (what vtkXMLPolyDataWriter writes, rmain:184-187): appended raw data, UInt64 headers,
+// Float64 Points, Polys with Int64 connectivity and offsets
+bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
+                   std::string *error);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

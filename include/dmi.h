@@ -42,7 +42,8 @@ extern "C" {
 
 #define DMI_ABI_VERSION 5 /* 3: dmi_info grew (pixels_without_depth); dmi_iso_active_cells, DMI_EXCHANGE_PEER_COPY, dmi_multi_peer_chunk
                            * 4: dmi_get_window_pair_count, dmi_get_upload_kernel_ms, dmi_sizeof_info / dmi_sizeof_timings
-                           * 5: dmi_get_view_paths */
+                           * 5: dmi_get_view_paths; later, additions only: dmi_extract_isosurface,
+                           *    dmi_download_isosurface, dmi_get_isosurface_kernel_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -224,6 +225,28 @@ int dmi_point_data_device_pointer(dmi_context *ctx, void **ptr);
  * ids (k*ny + j)*nx + i in ascending order -- the cells a host marching cubes has to visit, instead of all of them.  Runs
  * dmi_cell_to_point first if the grid changed.  Synchronises. */
 int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t *cell_ids, uint64_t capacity);
+
+/* Marching cubes over the point data at `iso` (the vtkContourFilter + vtkTransformFilter steps of
+ * Reconstruction/main.cxx:166-182), on the device.  Runs dmi_cell_to_point first if the grid changed.  The mesh stays on
+ * the device until the next call; *n_vertices / *n_triangles receive its size.  Synchronises.  (Added after round 5;
+ * dmi_abi_version() stays 5.)  Semantics, restated exactly and met bit for bit:
+ *   - a lattice point is inside when its value is >= iso; a NaN is outside (the test of dmi_iso_active_cells);
+ *   - one vertex per crossed lattice edge (exactly one inside endpoint), shared by every cell around the edge; the edge is
+ *     owned by its lower endpoint a; vertices are numbered by (a's linear id (k*(ny+1) + j)*(nx+1) + i, axis x < y < z);
+ *   - position, f64, every operation rounded: t = (iso - v_a) / (v_b - v_a), or 0 / 1 when a NaN endpoint leaves a / b
+ *     the inside one; corner c = origin + idx * spacing per axis; along the edge's axis d x_d = c_a[d] + t*(c_b[d] - c_a[d]),
+ *     the other two coordinates c_a's; world w_r = M[r][0]*x + M[r][1]*y + M[r][2]*z + M[r][3], left to right;
+ *   - triangles from a generated 256-case table (corner c = x + 2y + 4z; at most 5 per cell; closed, oriented from the
+ *     inside to the outside), by ascending cell id, then table order; degenerate ones (t = 0 or 1) are kept;
+ *   - the cells that emit triangles are exactly the dmi_iso_active_cells ids.
+ * An empty surface is a success (0 and 0).  DMI_ERR_INVALID_ARGUMENT for a NaN iso, null pointers and a context created
+ * with dmi_options.z_first != 0 (a z-slab's lattice has the wrong borders). */
+int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles);
+/* The mesh of the last dmi_extract_isosurface: vertices [n][3] f64 world coordinates, triangles [m][3] int64 vertex ids
+ * (vtkIdType).  DMI_ERR_INVALID_ARGUMENT before any successful extraction.  Synchronises. */
+int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangles);
+/* hipEvent time of the kernels of the last dmi_extract_isosurface (both passes and the scans between them). */
+int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last);
 
 /* Diagnostic: how many (8 x 8 x column brick, view) pairs of the last dmi_fuse were proven to be handled
  * uniformly.  out[0] mixed (per-voxel path), out[1] all voxels accumulate -eta*rho, out[2] all accumulate 0,
