@@ -103,6 +103,7 @@ ABI_SYMBOLS = [
     "dmi_color_clear_views", "dmi_color_process", "dmi_color_get_kernel_ms", "dmi_get_mixed_reason_histogram", "dmi_get_window_pair_count", "dmi_get_view_paths", "dmi_get_upload_kernel_ms", "dmi_sizeof_info", "dmi_sizeof_timings",
     "dmi_color_set_scratch_budget", "dmi_color_set_vertex_reorder", "dmi_iso_active_cells",
     "dmi_extract_isosurface", "dmi_download_isosurface", "dmi_get_isosurface_kernel_ms",
+    "dmi_extract_isosurface_normals", "dmi_download_isosurface_normals",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -175,6 +176,9 @@ def load() -> ctypes.CDLL:
         L.dmi_extract_isosurface.argtypes = [vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.dmi_download_isosurface.argtypes = [vp, dp, ctypes.POINTER(ctypes.c_int64)]
         L.dmi_get_isosurface_kernel_ms.argtypes = [vp, dp]
+    if hasattr(L, "dmi_extract_isosurface_normals"):
+        L.dmi_extract_isosurface_normals.argtypes = [vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.dmi_download_isosurface_normals.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     L.dmi_get_brick_class_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dmi_get_mixed_reason_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_get_window_pair_count"):  # (absent from an older prebuilt library loaded for an A/B timing, tools/gpu_exp.py)
@@ -459,8 +463,22 @@ class FusionContext:
         self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return verts[:int(nv.value)], tris[:int(nt.value)]
 
+    def extract_isosurface_with_normals(self, iso: float):
+        """(vertices [n, 3] f64, triangles [m, 3] int64, normals [n, 3] f32): extract_isosurface's mesh, bit for bit, and one
+        unit normal per vertex from the point data's gradient, in world coordinates (dmi_extract_isosurface_normals +
+        dmi_download_isosurface + dmi_download_isosurface_normals)."""
+        nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.dmi_extract_isosurface_normals(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
+        verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
+        tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
+        normals = np.empty((max(int(nv.value), 1), 3), dtype=np.float32)
+        self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        self._check(self._lib.dmi_download_isosurface_normals(self._h, normals.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return verts[:int(nv.value)], tris[:int(nt.value)], normals[:int(nv.value)]
+
     def isosurface_kernel_ms(self) -> float:
-        """hipEvent milliseconds of the kernels of the last extract_isosurface (dmi_get_isosurface_kernel_ms)."""
+        """hipEvent milliseconds of the kernels of the last extract_isosurface or extract_isosurface_with_normals
+        (dmi_get_isosurface_kernel_ms)."""
         a = ctypes.c_double(0)
         self._check(self._lib.dmi_get_isosurface_kernel_ms(self._h, ctypes.byref(a)))
         return float(a.value)
@@ -845,7 +863,7 @@ HOST_ABI_SYMBOLS = [
     "dmi_filter_get_fuse_kernel_ms", "dmi_filter_get_number_of_cells", "dmi_filter_get_output",
     "dmi_filter_last_error", "dmi_read_krtd_file", "dmi_extract_all_file_path", "dmi_k3_to_k4",
     "dmi_apply_depth_threshold", "dmi_read_depth_map", "dmi_read_depth_map_color", "dmi_mesh_coloration_from_lists",
-    "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata",
+    "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata", "dmi_write_polydata_with_normals",
 ]
 
 _host_bound = False
@@ -899,6 +917,9 @@ def load_host() -> ctypes.CDLL:
                                                  ctypes.POINTER(ctypes.c_uint8), ip, ctypes.c_char_p, ctypes.c_size_t]
     L.dmi_write_polydata.restype = ctypes.c_int
     L.dmi_write_polydata.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64]
+    L.dmi_write_polydata_with_normals.restype = ctypes.c_int
+    L.dmi_write_polydata_with_normals.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64,
+                                                  ctypes.POINTER(ctypes.c_float), ctypes.c_double]
     _host_bound = True
     return L
 
@@ -1000,7 +1021,8 @@ class CliOptionsC(ctypes.Structure):
                 ("grid_end", ctypes.c_double * 3), ("grid_matrix", ctypes.c_double * 16), ("ray_thick", ctypes.c_double),
                 ("ray_rho", ctypes.c_double), ("ray_eta", ctypes.c_double), ("ray_delta", ctypes.c_double),
                 ("thresh_best_cost", ctypes.c_double), ("contour", ctypes.c_double), ("verbose", ctypes.c_int32),
-                ("summary", ctypes.c_int32), ("force_cubic_voxel", ctypes.c_int32), ("extract_mesh", ctypes.c_int32)]
+                ("summary", ctypes.c_int32), ("force_cubic_voxel", ctypes.c_int32), ("extract_mesh", ctypes.c_int32),
+                ("mesh_normals", ctypes.c_int32)]
 
 
 def cli_read_arguments(args):
@@ -1025,6 +1047,21 @@ def write_polydata(path, points, triangles):
     ok = L.dmi_write_polydata(os.fsencode(path), _dp(p), p.shape[0], t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), t.shape[0])
     if not ok:
         raise OSError(f"dmi_write_polydata failed: {path}")
+
+
+def write_polydata_with_normals(path, points, triangles, normals, contour):
+    """dmi_write_polydata_with_normals: write_polydata's file plus the point arrays Normals ([n, 3] f32) and
+    reconstruction_scalar (f64, `contour` at every point); no GPU needed."""
+    L = load_host()
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    if n.shape != p.shape:
+        raise ValueError(f"normals {n.shape} do not match points {p.shape}")
+    ok = L.dmi_write_polydata_with_normals(os.fsencode(path), _dp(p), p.shape[0], t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                           t.shape[0], n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), float(contour))
+    if not ok:
+        raise OSError(f"dmi_write_polydata_with_normals failed: {path}")
 
 
 def cli_binary() -> str:

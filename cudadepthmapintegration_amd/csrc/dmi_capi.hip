@@ -142,6 +142,9 @@ struct dmi_context {
   uint64_t mesh_vertex_capacity = 0, mesh_triangle_capacity = 0;
   uint64_t mesh_vertices = 0, mesh_triangles = 0;
   bool mesh_valid = false;
+  float *d_mesh_normals = nullptr;      // dmi_extract_isosurface_normals: [n][3] f32, kept while large enough
+  uint64_t mesh_normal_capacity = 0;    // vertices
+  bool mesh_has_normals = false;        // the last successful extraction wrote them
   hipEvent_t mesh_events[4] = {nullptr, nullptr, nullptr, nullptr};  // around the count pass + scans, and the write pass
   double last_isosurface_kernel_ms = 0.0;
 
@@ -1043,6 +1046,7 @@ void dmi_destroy(dmi_context *ctx) {
   if (ctx->d_mesh_scan_temp) (void)hipFree(ctx->d_mesh_scan_temp);
   if (ctx->d_mesh_vertices) (void)hipFree(ctx->d_mesh_vertices);
   if (ctx->d_mesh_triangles) (void)hipFree(ctx->d_mesh_triangles);
+  if (ctx->d_mesh_normals) (void)hipFree(ctx->d_mesh_normals);
   for (hipEvent_t e : ctx->mesh_events)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->slab_events) (void)hipEventDestroy(e);
@@ -1896,6 +1900,17 @@ int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t 
 }
 
 namespace {
+// The normals' matrix: the cofactors of the grid matrix's upper-left 3 x 3 A, C[r][c] = A[r+1][c+1] A[r+2][c+2] -
+// A[r+1][c+2] A[r+2][c+1] (indices mod 3), negated when det A < 0: inverse(A)^T times |det A|, f64, row-major
+void normal_matrix(const double gm[16], double nm[9]) {
+  auto a = [&](int r, int c) { return gm[4 * (r % 3) + c % 3]; };
+  double cof[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) cof[3 * r + c] = a(r + 1, c + 1) * a(r + 2, c + 2) - a(r + 1, c + 2) * a(r + 2, c + 1);
+  const double det = a(0, 0) * cof[0] + a(0, 1) * cof[1] + a(0, 2) * cof[2];
+  for (int e = 0; e < 9; ++e) nm[e] = det < 0 ? -cof[e] : cof[e];
+}
+
 // grows a context-owned device buffer to hold `bytes`: the old contents are not kept
 int ensure_buffer(dmi_context *ctx, void **ptr, uint64_t *capacity, uint64_t bytes) {
   if (*ptr && *capacity >= bytes) return DMI_OK;
@@ -1912,17 +1927,20 @@ int ensure_buffer(dmi_context *ctx, void **ptr, uint64_t *capacity, uint64_t byt
 }
 }  // namespace
 
-int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
-  return guarded(ctx, "dmi_extract_isosurface", [&]() -> int {
-  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: null argument");
-  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: the iso-value is a NaN");
+namespace {
+// dmi_extract_isosurface, and with `normals` dmi_extract_isosurface_normals (`entry` names the call in the errors)
+int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, uint64_t *n_vertices, uint64_t *n_triangles,
+                       bool normals) {
+  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the iso-value is a NaN");
   if (ctx->opt.z_first != 0)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: the context holds a z-slab (z_first != 0); its lattice is not the grid's");
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the context holds a z-slab (z_first != 0); its lattice is not the grid's");
   *n_vertices = *n_triangles = 0;
   ctx->mesh_valid = false;
+  ctx->mesh_has_normals = false;
   const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
   const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
-  if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: grid too large for one launch");
+  if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": grid too large for one launch");
   int rc = dmi_cell_to_point(ctx);  // the contour filter reads the point data (Reconstruction/main.cxx:151-173)
   if (rc != DMI_OK) return rc;
   dmi::MeshGeom g{};
@@ -1966,7 +1984,7 @@ int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, u
   // vertex and triangle ids are int64 (vtkIdType) and the buffers' byte sizes must fit a size_t: refused, never wrapped
   const uint64_t id_limit = (uint64_t)std::numeric_limits<int64_t>::max() / 24;
   if (totals[0] > id_limit || totals[1] > id_limit)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_extract_isosurface: mesh too large for int64 ids");
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for int64 ids");
   g.n_vertices = totals[0];
   g.n_triangles = totals[1];
   float ms_count = 0.f, ms_write = 0.f;
@@ -1981,9 +1999,18 @@ int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, u
       if (rc != DMI_OK) return rc;
       ctx->mesh_triangle_capacity = tcap / 24;
     }
+    dmi::MeshNormals nrm{};
+    if (normals) {
+      uint64_t ncap = ctx->mesh_normal_capacity * 12;
+      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_normals, &ncap, totals[0] * 12);
+      if (rc != DMI_OK) return rc;
+      ctx->mesh_normal_capacity = ncap / 12;
+      normal_matrix(ctx->grid.grid_matrix, nrm.nm);
+      nrm.normals = ctx->d_mesh_normals;
+    }
     DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[2], ctx->stream));
     DMI_HIP(ctx, dmi::launch_isosurface_write(ctx->d_points, g, ctx->d_mesh_bases, ctx->d_mesh_vertices, ctx->d_mesh_triangles,
-                                              ctx->stream));
+                                              normals ? &nrm : nullptr, ctx->stream));
     DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[3], ctx->stream));
     DMI_HIP(ctx, hipEventSynchronize(ctx->mesh_events[3]));
     DMI_HIP(ctx, hipEventElapsedTime(&ms_write, ctx->mesh_events[2], ctx->mesh_events[3]));
@@ -1992,11 +2019,24 @@ int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, u
   ctx->mesh_vertices = totals[0];
   ctx->mesh_triangles = totals[1];
   ctx->mesh_valid = true;
+  ctx->mesh_has_normals = normals;
   *n_vertices = totals[0];
   *n_triangles = totals[1];
   rc = drain_c2p(ctx);
   if (rc != DMI_OK) return rc;
   return drain_events(ctx);
+}
+}  // namespace
+
+int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_extract_isosurface", [&]() -> int {
+    return extract_isosurface(ctx, "dmi_extract_isosurface", iso, n_vertices, n_triangles, false);
+  });
+}
+
+int dmi_extract_isosurface_normals(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_extract_isosurface_normals", [&]() -> int {
+    return extract_isosurface(ctx, "dmi_extract_isosurface_normals", iso, n_vertices, n_triangles, true);
   });
 }
 
@@ -2010,6 +2050,22 @@ int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangl
     DMI_HIP(ctx, hipMemcpyAsync(vertices, ctx->d_mesh_vertices, (size_t)ctx->mesh_vertices * 24, hipMemcpyDeviceToHost, ctx->stream));
   if (ctx->mesh_triangles)
     DMI_HIP(ctx, hipMemcpyAsync(triangles, ctx->d_mesh_triangles, (size_t)ctx->mesh_triangles * 24, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_download_isosurface_normals(dmi_context *ctx, float *normals) {
+  return guarded(ctx, "dmi_download_isosurface_normals", [&]() -> int {
+  if (!ctx || !normals) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: null argument");
+  if (!ctx->mesh_valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: no mesh (no extraction has succeeded)");
+  if (!ctx->mesh_has_normals)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_download_isosurface_normals: the last mesh has no normals (dmi_extract_isosurface, not dmi_extract_isosurface_normals)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (ctx->mesh_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(normals, ctx->d_mesh_normals, (size_t)ctx->mesh_vertices * 12, hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return DMI_OK;
   });

@@ -428,13 +428,20 @@ struct MeshGeom {
   double m[12];                      // rows 0..2 of the grid matrix, row-major
   uint64_t n_vertices, n_triangles;  // sizes of the write pass's output buffers
 };
+// the write pass with normals (dmi_extract_isosurface_normals): the cofactor matrix of the grid matrix's upper-left 3 x 3,
+// negated when its determinant is negative, row-major, and the [n_vertices][3] f32 output
+struct MeshNormals {
+  double nm[9];
+  float *normals;
+};
 int isosurface_max_triangles_per_cell();
 size_t isosurface_segment_count(int nx, int ny, int nz);
 // counts / bases: 2 (segments + 1) entries, vertices then triangles; counts[segments] and counts[2 segments + 1] are zeros the
 // caller keeps there, so bases[segments] and bases[2 segments + 1] receive the totals
 hipError_t launch_isosurface_count(const double *points, const MeshGeom &g, uint32_t *counts, uint64_t *bases, void *scan_temp,
                                    size_t *scan_temp_bytes, hipStream_t stream);
+// writes the vertices' normals too when `normals` is not null
 hipError_t launch_isosurface_write(const double *points, const MeshGeom &g, const uint64_t *bases, double *verts, int64_t *tris,
-                                   hipStream_t stream);
+                                   const MeshNormals *normals, hipStream_t stream);
 
 }  // namespace dmi

@@ -95,8 +95,13 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
       {"--forceCubicVoxel", {Kind::kFlag, "use the smallest of the three spacings on every axis", into_flag(&o->forceCubicVoxel)}},
       {"--device", {Kind::kMulti, "HIP device ordinal(s); several = one fusion over several GPUs (not in the reference)", into_vector(&o->devices)}},
       {"--extractMesh", {Kind::kFlag, "extract the iso-surface at --contour on the GPU and write it to --outputMeshFilename: points and "
-                                      "triangles only, without the Normals and scalar arrays VTK's contour filter adds (not in the reference)",
+                                      "triangles only, without the Normals and scalar arrays VTK's contour filter adds unless --meshNormals "
+                                      "is given (not in the reference)",
                          into_flag(&o->extractMesh)}},
+      {"--meshNormals", {Kind::kFlag, "with --extractMesh: compute the mesh's normals on the GPU and write them and the scalar array "
+                                      "reconstruction_scalar (the contour value) as point data, as VTK's contour filter does (not in the "
+                                      "reference)",
+                         into_flag(&o->meshNormals)}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -153,6 +158,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   }
   if (help) {
     err << HelpText();
+    return false;
+  }
+  if (o->meshNormals && !o->extractMesh) {
+    err << "Error : --meshNormals needs --extractMesh (the normals belong to the extracted mesh).\n" << HelpText();
     return false;
   }
   // rmain:257-262
@@ -330,7 +339,7 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 }
 
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
-                   std::string *error) {
+                   std::string *error, const float *normals, double contour) {
   if (nPoints < 0 || nTriangles < 0) {
     *error = "WritePolyData: negative count";
     return false;
@@ -342,10 +351,17 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
   }
   const uint64_t point_bytes = (uint64_t)nPoints * 3 * sizeof(double), conn_bytes = (uint64_t)nTriangles * 3 * sizeof(int64_t),
                  offset_bytes = (uint64_t)nTriangles * sizeof(int64_t);
+  const uint64_t normal_bytes = (uint64_t)nPoints * 3 * sizeof(float), scalar_bytes = (uint64_t)nPoints * sizeof(double);
+  const uint64_t normal_offset = 3 * sizeof(uint64_t) + point_bytes + conn_bytes + offset_bytes;  // behind the offsets
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
-      << nPoints << "\" NumberOfVerts=\"0\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"" << nTriangles
-      << "\">\n      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" format=\"appended\" "
+      << nPoints << "\" NumberOfVerts=\"0\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"" << nTriangles << "\">\n";
+  if (normals)  // vtkContourFilter's point data (ComputeNormals, ComputeScalars)
+    out << "      <PointData Normals=\"Normals\" Scalars=\"reconstruction_scalar\">\n        <DataArray type=\"Float32\" "
+           "Name=\"Normals\" NumberOfComponents=\"3\" format=\"appended\" offset=\""
+        << normal_offset << "\"/>\n        <DataArray type=\"Float64\" Name=\"reconstruction_scalar\" format=\"appended\" offset=\""
+        << normal_offset + sizeof(uint64_t) + normal_bytes << "\"/>\n      </PointData>\n";
+  out << "      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" format=\"appended\" "
          "offset=\"0\"/>\n      </Points>\n      <Polys>\n        <DataArray type=\"Int64\" Name=\"connectivity\" format=\"appended\" offset=\""
       << sizeof(uint64_t) + point_bytes << "\"/>\n        <DataArray type=\"Int64\" Name=\"offsets\" format=\"appended\" offset=\""
       << 2 * sizeof(uint64_t) + point_bytes + conn_bytes
@@ -361,6 +377,17 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
     for (int64_t q = 0; q < n; ++q) offsets[(size_t)q] = 3 * (done + q + 1);
     out.write(reinterpret_cast<const char *>(offsets.data()), (std::streamsize)(n * sizeof(int64_t)));
     done += n;
+  }
+  if (normals) {
+    out.write(reinterpret_cast<const char *>(&normal_bytes), sizeof(normal_bytes));
+    out.write(reinterpret_cast<const char *>(normals), (std::streamsize)normal_bytes);
+    out.write(reinterpret_cast<const char *>(&scalar_bytes), sizeof(scalar_bytes));
+    const std::vector<double> scalars((size_t)std::min<int64_t>(nPoints, int64_t(1) << 20), contour);
+    for (int64_t done = 0; done < nPoints;) {
+      const int64_t n = std::min<int64_t>(nPoints - done, (int64_t)scalars.size());
+      out.write(reinterpret_cast<const char *>(scalars.data()), (std::streamsize)(n * sizeof(double)));
+      done += n;
+    }
   }
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
@@ -435,8 +462,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   std::vector<double> points((size_t)dims[0] * dims[1] * dims[2]);
   std::vector<double> meshVertices;    // --extractMesh
   std::vector<int64_t> meshTriangles;
+  std::vector<float> meshNormals;      // --meshNormals
   double dummyVertex = 0.0;            // a valid pointer for an empty mesh
   int64_t dummyTriangle = 0;
+  float dummyNormal = 0.f;
   {
     // vtkCellDataToPointData (rmain:151-155) on the GPU: the cell grid goes up once more, the point grid comes back
     dmi_grid_desc grid;
@@ -465,12 +494,16 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (rc == DMI_OK && o.extractMesh) {
       // vtkContourFilter + vtkTransformFilter (rmain:166-182) on the device; vtkXMLPolyDataWriter (rmain:184-187) below
       uint64_t nv = 0, nt = 0;
-      rc = dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      rc = o.meshNormals ? dmi_extract_isosurface_normals(ctx, o.contour, &nv, &nt) : dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
       if (rc == DMI_OK) {
         meshVertices.resize((size_t)nv * 3);
         meshTriangles.resize((size_t)nt * 3);
         rc = dmi_download_isosurface(ctx, meshVertices.data() ? meshVertices.data() : &dummyVertex,
                                      meshTriangles.data() ? meshTriangles.data() : &dummyTriangle);
+      }
+      if (rc == DMI_OK && o.meshNormals) {
+        meshNormals.resize((size_t)nv * 3);
+        rc = dmi_download_isosurface_normals(ctx, meshNormals.data() ? meshNormals.data() : &dummyNormal);
       }
       if (rc != DMI_OK) result->error = std::string("iso-surface: ") + dmi_last_error(ctx);
       result->meshVertices = nv;
@@ -487,7 +520,7 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   if (o.extractMesh) {
     say("** Save mesh...");
     if (!WritePolyData(o.outputMeshFilename, meshVertices.data(), (int64_t)result->meshVertices, meshTriangles.data(),
-                       (int64_t)result->meshTriangles, &error)) {
+                       (int64_t)result->meshTriangles, &error, o.meshNormals ? (meshNormals.empty() ? &dummyNormal : meshNormals.data()) : nullptr, o.contour)) {
       result->error = error;
       return 1;
     }

@@ -5,8 +5,9 @@
 // (rmain:157-161), the transformed volume as a .vts structured grid (rmain:189-198), the summary file (rmain:458-516).
 // The iso-surface (vtkContourFilter + vtkTransformFilter, rmain:166-187) only with --extractMesh, which the reference does
 // not have: dmi_extract_isosurface at --contour on the device, written to --outputMeshFilename as a .vtp of points and
-// triangles (no Normals, no scalar array).  Without the flag --outputMeshFilename is accepted and checked as the
-// reference does, and nothing is written to it.
+// triangles; with --meshNormals as well (not in the reference either) dmi_extract_isosurface_normals, and the .vtp carries
+// the point arrays Normals and reconstruction_scalar that vtkContourFilter attaches.  Without --extractMesh
+// --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
 #include <cstdint>
@@ -34,6 +35,7 @@ struct Options {
   double contour = 1.0;               // --contour (recorded in the summary; no contour is extracted here)
   bool verbose = false, summary = false, forceCubicVoxel = false;
   bool extractMesh = false;           // not in the reference: write the iso-surface at --contour to --outputMeshFilename
+  bool meshNormals = false;           // not in the reference: ... with its Normals and scalar arrays (needs --extractMesh)
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -61,9 +63,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
 bool WriteMetaImage(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                     const double *pointScalars, std::string *error);
 // a triangle mesh as VTK XML PolyData (what vtkXMLPolyDataWriter writes, rmain:184-187): appended raw data, UInt64 headers,
-// Float64 Points, Polys with Int64 connectivity and offsets
+// Float64 Points, Polys with Int64 connectivity and offsets.  With `normals` ([nPoints][3] f32) also the point arrays of
+// vtkContourFilter: <PointData Normals="Normals" Scalars="reconstruction_scalar">, Float32 x 3 and Float64 `contour` at every
+// point, appended behind the offsets; without them the file is what it always was.
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
-                   std::string *error);
+                   std::string *error, const float *normals = nullptr, double contour = 0.0);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

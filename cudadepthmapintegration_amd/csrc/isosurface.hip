@@ -15,6 +15,10 @@
 // The triangles of a segment's cells name vertices of the rows (j, k), (j+1, k), (j, k+1), (j+1, k+1) and of one point
 // past the segment: the write pass rebuilds those rows' in-segment prefix counts in LDS and adds the scanned bases, so
 // no per-point index array exists (device scratch is O(segments)).
+// The write pass with normals (NORMALS) also writes each vertex's normal (tests/isosurface_normals_np.py):
+// the negated central-difference gradient at both endpoints of its edge, interpolated at t, through the cofactor matrix of
+// the grid matrix and normalised, f32.  The gradient's neighbours in rows j - 1 and k - 1 are not among the 8 rows in LDS:
+// every lattice value it needs is read from global memory, where L2 and the MALL serve the rows the workgroup just loaded.
 #include <rocprim/device/device_scan.hpp>
 
 #include "fusion_kernels.h"
@@ -84,11 +88,33 @@ __device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t x, uint64_t *w
 constexpr int kField = 12;  // bits per packed count: a segment has at most 257 * 3 vertices per row and 256 * 5 triangles
 constexpr uint64_t kFieldMask = (1u << kField) - 1;
 
-template <bool WRITE>
+// minus the gradient of the point data at lattice point (i, j, k), p = &P[i, j, k]: one-sided at the lattice's borders,
+// central inside, every operation rounded.  The contexts have cell_dims >= 1, so no axis has a single point.
+__device__ __forceinline__ void neg_gradient(const double *p, int i, int j, int k, const MeshGeom &g, int64_t prow, int64_t pplane,
+                                             double out[3]) {
+  const int q[3] = {i, j, k}, n[3] = {g.nx, g.ny, g.nz};
+  const int64_t stride[3] = {1, prow, pplane};
+  const double c = p[0];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const bool lo = q[e] == 0, hi = q[e] == n[e];
+    const double below = lo ? c : p[-stride[e]], above = hi ? c : p[stride[e]];
+    // (0.5 * (below - above)) inside, (below - above) at a border: 1.0 * x is x, bit for bit
+    out[e] = ((lo || hi ? 1.0 : 0.5) * (below - above)) / g.spacing[e];
+  }
+}
+
+// Normals: empty for the count pass and the plain write pass, whose kernel arguments and code stay what they were without
+// normals; one MeshNormals for the write pass that writes them (NORMALS).
+template <bool WRITE, typename... Normals>
 __global__ __launch_bounds__(kSeg) void isosurface_kernel(const double *__restrict__ points, MeshGeom g,
                                                           uint32_t *__restrict__ vcounts, uint32_t *__restrict__ tcounts,
                                                           const uint64_t *__restrict__ vbases, const uint64_t *__restrict__ tbases,
-                                                          double *__restrict__ verts, int64_t *__restrict__ tris) {
+                                                          double *__restrict__ verts, int64_t *__restrict__ tris, Normals... normals) {
+  constexpr bool NORMALS = sizeof...(Normals) != 0;
+  static_assert(sizeof...(Normals) <= 1, "one MeshNormals at most");
+  static_assert(WRITE || !NORMALS, "normals are written by the write pass");
+  const MeshNormals nrm{normals...};  // (unused without normals)
   constexpr int kRows = WRITE ? 8 : 4;  // the count pass needs the cells' corner rows and the own row's +y / +z only
   __shared__ uint8_t inb[kSeg + 2];     // bit r: point (i0 + q) of row r is inside
   __shared__ uint8_t msk[4][kSeg + 1];  // crossed edges (bit = axis) of the points of rows 0..3
@@ -176,6 +202,8 @@ __global__ __launch_bounds__(kSeg) void isosurface_kernel(const double *__restri
       const int64_t stride[3] = {1, prow, pplane};
       const double ca[3] = {g.origin[0] + idx[0] * g.spacing[0], g.origin[1] + idx[1] * g.spacing[1],
                             g.origin[2] + idx[2] * g.spacing[2]};
+      double ga[3];  // G(a), shared by the point's vertices
+      if constexpr (NORMALS) neg_gradient(p, i, j, k, g, prow, pplane, ga);
       unsigned before = 0;
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
@@ -191,6 +219,17 @@ __global__ __launch_bounds__(kSeg) void isosurface_kernel(const double *__restri
 #pragma unroll
           for (int r = 0; r < 3; ++r)
             verts[id * 3 + r] = g.m[4 * r + 0] * x[0] + g.m[4 * r + 1] * x[1] + g.m[4 * r + 2] * x[2] + g.m[4 * r + 3];
+          if constexpr (NORMALS) {
+            double gb[3], gv[3], w[3];
+            neg_gradient(p + stride[d], i + (d == 0), j + (d == 1), k + (d == 2), g, prow, pplane, gb);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) gv[r] = ga[r] + s * (gb[r] - ga[r]);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) w[r] = nrm.nm[3 * r + 0] * gv[0] + nrm.nm[3 * r + 1] * gv[1] + nrm.nm[3 * r + 2] * gv[2];
+            const double len = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) nrm.normals[id * 3 + r] = (float)(len != 0.0 ? w[r] / len : w[r]);  // a NaN len divides
+          }
         }
       }
     }
@@ -245,10 +284,14 @@ hipError_t launch_isosurface_count(const double *points, const MeshGeom &g, uint
 }
 
 hipError_t launch_isosurface_write(const double *points, const MeshGeom &g, const uint64_t *bases, double *verts, int64_t *tris,
-                                   hipStream_t stream) {
+                                   const MeshNormals *normals, hipStream_t stream) {
   const size_t n = isosurface_segment_count(g.nx, g.ny, g.nz);
-  hipLaunchKernelGGL((isosurface_kernel<true>), dim3((unsigned)n), dim3(kSeg), 0, stream, points, g, (uint32_t *)nullptr,
-                     (uint32_t *)nullptr, bases, bases + n + 1, verts, tris);
+  if (normals)
+    hipLaunchKernelGGL((isosurface_kernel<true, MeshNormals>), dim3((unsigned)n), dim3(kSeg), 0, stream, points, g, (uint32_t *)nullptr,
+                       (uint32_t *)nullptr, bases, bases + n + 1, verts, tris, *normals);
+  else
+    hipLaunchKernelGGL((isosurface_kernel<true>), dim3((unsigned)n), dim3(kSeg), 0, stream, points, g, (uint32_t *)nullptr,
+                       (uint32_t *)nullptr, bases, bases + n + 1, verts, tris);
   return hipGetLastError();
 }
 

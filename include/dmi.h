@@ -43,7 +43,8 @@ extern "C" {
 #define DMI_ABI_VERSION 5 /* 3: dmi_info grew (pixels_without_depth); dmi_iso_active_cells, DMI_EXCHANGE_PEER_COPY, dmi_multi_peer_chunk
                            * 4: dmi_get_window_pair_count, dmi_get_upload_kernel_ms, dmi_sizeof_info / dmi_sizeof_timings
                            * 5: dmi_get_view_paths; later, additions only: dmi_extract_isosurface,
-                           *    dmi_download_isosurface, dmi_get_isosurface_kernel_ms */
+                           *    dmi_download_isosurface, dmi_get_isosurface_kernel_ms; dmi_extract_isosurface_normals,
+                           *    dmi_download_isosurface_normals */
 
 typedef struct dmi_context dmi_context;
 
@@ -245,7 +246,23 @@ int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, u
 /* The mesh of the last dmi_extract_isosurface: vertices [n][3] f64 world coordinates, triangles [m][3] int64 vertex ids
  * (vtkIdType).  DMI_ERR_INVALID_ARGUMENT before any successful extraction.  Synchronises. */
 int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangles);
-/* hipEvent time of the kernels of the last dmi_extract_isosurface (both passes and the scans between them). */
+/* dmi_extract_isosurface with the checks, errors, vertices and triangles of that call, bit for bit, plus one normal per vertex
+ * ([n][3] f32, kept on the device; what vtkContourFilter's ComputeNormals and vtkTransformFilter make of it).  (Added after
+ * round 5; dmi_abi_version() stays 5.)  Definition, f64 and every operation rounded until the last step:
+ *   - minus the gradient at lattice point p, per axis e with p's index q, N cells on the axis and h = spacing[e]:
+ *     G_e = (P[p] - P[p+e]) / h at q == 0, (P[p-e] - P[p]) / h at q == N, (0.5 * (P[p-e] - P[p+e])) / h otherwise;
+ *   - a vertex on the edge (a, b = a + e_d) with its own t: g_r = G(a)_r + t * (G(b)_r - G(a)_r);
+ *   - Nm = the cofactors of the grid matrix's upper-left 3x3 A, C[r][c] = A[r+1][c+1]*A[r+2][c+2] - A[r+1][c+2]*A[r+2][c+1]
+ *     (indices mod 3), negated when det A = A[0][0]*C[0][0] + A[0][1]*C[0][1] + A[0][2]*C[0][2] < 0 (inverse(A)^T up to a
+ *     positive factor; the identity for the identity);
+ *   - w_r = Nm[r][0]*g_0 + Nm[r][1]*g_1 + Nm[r][2]*g_2, L = sqrt((w_0*w_0 + w_1*w_1) + w_2*w_2), n = w / L unless L == 0
+ *     (then n = w), each n_r rounded to f32 (nearest even).  The normals point from the inside (>= iso) to the outside. */
+int dmi_extract_isosurface_normals(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles);
+/* The normals [n][3] f32 of the last extraction.  DMI_ERR_INVALID_ARGUMENT for a null pointer, before any successful
+ * extraction, and when the last successful one was a plain dmi_extract_isosurface.  Synchronises. */
+int dmi_download_isosurface_normals(dmi_context *ctx, float *normals);
+/* hipEvent time of the kernels of the last dmi_extract_isosurface or dmi_extract_isosurface_normals (both passes and the scans
+ * between them). */
 int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last);
 
 /* Diagnostic: how many (8 x 8 x column brick, view) pairs of the last dmi_fuse were proven to be handled

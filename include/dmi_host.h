@@ -93,19 +93,27 @@ typedef struct dmi_cli_options {
   double ray_thick, ray_rho, ray_eta, ray_delta, thresh_best_cost, contour;
   int32_t verbose, summary, force_cubic_voxel;
   int32_t extract_mesh;       /* --extractMesh (not in the reference): write the iso-surface to --outputMeshFilename */
+  int32_t mesh_normals;       /* --meshNormals (not in the reference; only with --extractMesh): with its Normals and scalar */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
 /* The whole tool: ReadArguments, the filter, cell -> point data, meta_image_volume.mha (in the working directory, as the
  * reference), the .vts volume, the summary file.  Process exit code: 0 on success.  The iso-surface (rmain:166-187) only
- * with --extractMesh: dmi_extract_isosurface at --contour, written to --outputMeshFilename by dmi_write_polydata. */
+ * with --extractMesh: dmi_extract_isosurface at --contour, written to --outputMeshFilename by dmi_write_polydata; with
+ * --meshNormals too, dmi_extract_isosurface_normals and dmi_write_polydata_with_normals. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
  * the .vts writer (appended raw data, UInt64 headers, little-endian): Float64 Points [n_points][3], Polys with Int64
  * connectivity [n_triangles][3] and offsets 3, 6, 9, ...  No point or cell arrays (VTK's contour filter would add Normals
- * and the scalar).  1 on success, 0 when the file cannot be written or a count is negative. */
+ * and the scalar: dmi_write_polydata_with_normals).  1 on success, 0 when the file cannot be written or a count is negative. */
 int dmi_write_polydata(const char *path, const double *points, int64_t n_points, const int64_t *triangles, int64_t n_triangles);
+/* dmi_write_polydata's file plus the point data vtkContourFilter attaches: <PointData Normals="Normals"
+ * Scalars="reconstruction_scalar"> with Normals, Float32 x 3 ([n_points][3], dmi_download_isosurface_normals), and
+ * reconstruction_scalar, Float64, `contour` at every point; both in the appended raw block behind the offsets.  1 on success,
+ * 0 when the file cannot be written, a count is negative or a pointer is null while its count is not zero. */
+int dmi_write_polydata_with_normals(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
+                                    int64_t n_triangles, const float *normals, double contour);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """Kernel time of dmi_extract_isosurface on the cfg-3 speckle scene (512^3, 256 views of 1280 x 720, as bench.py --full builds
-it), next to the HBM floor of reading the point lattice.  Prints one JSON line.
+it), next to the HBM floor of reading the point lattice.  Prints one JSON line.  With --normals it times
+dmi_extract_isosurface_normals too, the two calls alternating in the same process (kernel_ms / normals_kernel_ms).
 
-    python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5]
+    python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals]
 """
 import argparse
 import json
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--iso", type=float, default=1.0)
     ap.add_argument("--views", type=int, default=256)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--normals", action="store_true", help="also time the call with normals, alternating with the plain one")
     a = ap.parse_args()
     grid = scene.default_grid(512)
     ray = scene.default_ray_potential(grid)
@@ -35,10 +37,15 @@ def main():
         ctx.cell_to_point()
         nv, nt = 0, 0
         verts, tris = ctx.extract_isosurface(a.iso)      # warm-up: buffers sized, code loaded
-        times = []
+        if a.normals:
+            ctx.extract_isosurface_with_normals(a.iso)
+        times, ntimes = [], []
         for _ in range(a.repeat):
             verts, tris = ctx.extract_isosurface(a.iso)
             times.append(ctx.isosurface_kernel_ms())
+            if a.normals:
+                ctx.extract_isosurface_with_normals(a.iso)
+                ntimes.append(ctx.isosurface_kernel_ms())
         nv, nt = len(verts), len(tris)
     n_points = 513 ** 3
     lattice = n_points * 8
@@ -46,6 +53,9 @@ def main():
            "lattice_bytes": lattice, "mesh_bytes": nv * 24 + nt * 24,
            "floor_ms_8tbps": lattice / HBM_TBPS / 1e9, "floor_ms_c2p_rate": lattice / C2P_TBPS / 1e9,
            "two_reads_floor_ms_8tbps": 2 * lattice / HBM_TBPS / 1e9}
+    if a.normals:
+        out.update({"normals_kernel_ms": ntimes, "normals_kernel_ms_min": min(ntimes), "normals_bytes": nv * 12,
+                    "normals_over_plain_min": min(ntimes) / min(times)})
     print(json.dumps(out))
 
 
