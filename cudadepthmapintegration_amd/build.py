@@ -19,10 +19,13 @@ CSRC = os.path.join(_HERE, "csrc")
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 LIB_PATH = os.path.join(CSRC, "libdmi_hip.so")
 
-SOURCES = ["fusion_kernels.hip", "fusion_tile.hip", "fusion_classify.hip", "coloration_kernels.hip", "grid_post.hip", "isosurface.hip", "dmi_capi.hip", "dmi_multi.hip", "host/recon_host.cpp", "host/vti_reader.cpp", "host/recon_cli.cpp", "host/dmi_host_capi.cpp"]
+SOURCES = ["fusion_kernels.hip", "fusion_tile.hip", "fusion_classify.hip", "coloration_kernels.hip", "grid_post.hip", "isosurface.hip", "dmi_capi.hip", "dmi_multi.hip", "host/recon_host.cpp", "host/vti_reader.cpp", "host/vtp_reader.cpp", "host/recon_cli.cpp", "host/color_cli.cpp", "host/dmi_host_capi.cpp"]
 HEADERS = ["fusion_kernels.h", "fusion_device.h", "fusion_tile_acc.inc", "isosurface_table.inc", os.path.join("host", "recon_host.h"),
-           os.path.join("host", "vti_reader.h"), os.path.join("host", "recon_cli.h"),
+           os.path.join("host", "vtk_xml_data.h"), os.path.join("host", "vti_reader.h"), os.path.join("host", "vtp_reader.h"),
+           os.path.join("host", "recon_cli.h"), os.path.join("host", "color_cli.h"),
            os.path.join("..", "..", "include", "dmi.h"), os.path.join("..", "..", "include", "dmi_host.h")]
+# the command-line tools: a few lines of main() each, linked against the library (build_cli, build_color_cli)
+CLI_MAINS = ["recon_cli_main.cpp", "color_cli_main.cpp"]
 
 # -ffp-contract=off: no FMA contraction anywhere on the result path (parity contract).
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function",
@@ -148,7 +151,7 @@ def source_digest(files=None) -> str:
     h = hashlib.sha256()
     h.update(" ".join(COMMON_FLAGS + HIP_FLAGS).encode())
     if files is None:
-        files = [os.path.join(CSRC, s) for s in _sources()] + _headers() + [os.path.join(CSRC, "host", "recon_cli_main.cpp")]
+        files = [os.path.join(CSRC, s) for s in _sources()] + _headers() + [os.path.join(CSRC, "host", m) for m in CLI_MAINS]
     for f in files:
         h.update(os.path.relpath(f, CSRC).encode())
         with open(f, "rb") as fh:
@@ -386,34 +389,47 @@ def build(force: bool = False, verbose: bool = False) -> str:
     with open(_digest_path(), "w") as fh:
         fh.write(digest + "\n")
     build_cli(verbose)
+    build_color_cli(verbose)
     _record("rebuilt: hipcc compiled the stale objects and linked the library")
     return LIB_PATH
 
 
 CLI_PATH = os.path.join(CSRC, "dmi_reconstruction")
+COLOR_CLI_PATH = os.path.join(CSRC, "dmi_coloration")
 
 
-def build_cli(verbose: bool = False) -> str:
-    """The reference's `Reconstruction` command line over the library (csrc/host/recon_cli_main.cpp): a few lines of
-    main() linked against the .so next to it (rpath $ORIGIN).  Only for the default library.  Built by build() right after
-    the library and on demand by capi.cli_binary(); up to date = its digest file names the library's source digest
-    (timestamps say nothing after a checkout or a copy).  Linked to a temporary and moved into place."""
+def _link_tool(main_src: str, exe: str, verbose: bool) -> str:
+    """One command-line tool over the library: csrc/host/<main_src>, a few lines of main(), linked against the .so next to it
+    (rpath $ORIGIN).  Only for the default library.  Up to date = its digest file names the library's source digest (timestamps
+    say nothing after a checkout or a copy).  Linked to a temporary and moved into place."""
     if os.path.basename(LIB_PATH) != "libdmi_hip.so" or LIB_OVERRIDE:
         return ""
-    src = os.path.join(CSRC, "host", "recon_cli_main.cpp")
+    src = os.path.join(CSRC, "host", main_src)
     digest = source_digest()
-    marker = CLI_PATH + ".digest"
-    if os.path.exists(CLI_PATH) and os.path.exists(marker):
+    marker = exe + ".digest"
+    if os.path.exists(exe) and os.path.exists(marker):
         with open(marker) as fh:
             if fh.read().strip() == digest:
-                return CLI_PATH
+                return exe
     os.makedirs(OBJ_DIR, exist_ok=True)
-    staged = os.path.join(OBJ_DIR, f"dmi_reconstruction.{os.getpid()}.tmp")
+    staged = os.path.join(OBJ_DIR, f"{os.path.basename(exe)}.{os.getpid()}.tmp")
     cmd = [hipcc_path()] + COMMON_FLAGS + [src, "-L" + CSRC, "-ldmi_hip", "-Wl,-rpath,$ORIGIN", "-o", staged]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    os.replace(staged, CLI_PATH)
+    os.replace(staged, exe)
     with open(marker, "w") as fh:
         fh.write(digest + "\n")
-    return CLI_PATH
+    return exe
+
+
+def build_cli(verbose: bool = False) -> str:
+    """The reference's `Reconstruction` command line (csrc/host/recon_cli_main.cpp).  Built by build() right after the library
+    and on demand by capi.cli_binary()."""
+    return _link_tool("recon_cli_main.cpp", CLI_PATH, verbose)
+
+
+def build_color_cli(verbose: bool = False) -> str:
+    """The reference's `Coloration` command line (csrc/host/color_cli_main.cpp).  Built by build() right after the library and
+    on demand by capi.coloration_cli_binary()."""
+    return _link_tool("color_cli_main.cpp", COLOR_CLI_PATH, verbose)

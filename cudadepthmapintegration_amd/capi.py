@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import os
 import sys
+from typing import NamedTuple
 
 import numpy as np
 
@@ -101,7 +102,8 @@ ABI_SYMBOLS = [
     "dmi_color_mesh", "dmi_color_last_error", "dmi_cell_to_point", "dmi_download_point_data_f64",
     "dmi_point_data_device_pointer", "dmi_color_create", "dmi_color_destroy", "dmi_color_add_views",
     "dmi_color_clear_views", "dmi_color_process", "dmi_color_get_kernel_ms", "dmi_get_mixed_reason_histogram", "dmi_get_window_pair_count", "dmi_get_view_paths", "dmi_get_upload_kernel_ms", "dmi_sizeof_info", "dmi_sizeof_timings",
-    "dmi_color_set_scratch_budget", "dmi_color_set_vertex_reorder", "dmi_iso_active_cells",
+    "dmi_color_set_scratch_budget", "dmi_color_set_vertex_reorder", "dmi_color_add_views_with_depth", "dmi_color_set_depth_test",
+    "dmi_iso_active_cells",
     "dmi_extract_isosurface", "dmi_download_isosurface", "dmi_get_isosurface_kernel_ms",
     "dmi_extract_isosurface_normals", "dmi_download_isosurface_normals",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
@@ -207,6 +209,8 @@ def load() -> ctypes.CDLL:
     L.dmi_color_get_kernel_ms.argtypes = [vp, dp]
     L.dmi_color_set_scratch_budget.argtypes = [vp, ctypes.c_uint64]
     L.dmi_color_set_vertex_reorder.argtypes = [vp, i32]
+    L.dmi_color_add_views_with_depth.argtypes = [vp, u8p, dp, dp, dp, i32, i32, i32]
+    L.dmi_color_set_depth_test.argtypes = [vp, i32, ctypes.c_double]
     L.dmi_color_last_error.argtypes = []
     L.dmi_color_last_error.restype = ctypes.c_char_p
     i64, i64p, i32p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
@@ -795,13 +799,26 @@ class ColorContext:
         except Exception:
             pass
 
-    def add_views(self, colors, K4, RT4):
+    def add_views(self, colors, K4, RT4, depths=None):
+        """Append views: colors [n, H, W, 3] u8 in vtk row order, K4 / RT4 [n, 4, 4].  depths [n, H, W] f64 (the "Depths"
+        arrays, vtk row order): kept resident for the depth test (set_depth_test); views added without them cannot take it."""
         col = np.ascontiguousarray(colors, dtype=np.uint8)
         n, H, W, _ = col.shape
         k = np.ascontiguousarray(K4, dtype=np.float64).reshape(n, 16)
         rt = np.ascontiguousarray(RT4, dtype=np.float64).reshape(n, 16)
-        self._check(self._lib.dmi_color_add_views(self._h, col.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _dp(k), _dp(rt),
-                                                  n, W, H))
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        if depths is None:
+            self._check(self._lib.dmi_color_add_views(self._h, col.ctypes.data_as(u8), _dp(k), _dp(rt), n, W, H))
+            return
+        d = np.ascontiguousarray(depths, dtype=np.float64)
+        if d.shape != (n, H, W):
+            raise ValueError(f"depths {d.shape} do not match the colour planes ({n}, {H}, {W})")
+        self._check(self._lib.dmi_color_add_views_with_depth(self._h, col.ctypes.data_as(u8), _dp(d), _dp(k), _dp(rt), n, W, H))
+
+    def set_depth_test(self, enable: bool, tolerance: float = 0.0):
+        """The visibility test (include/dmi.h, dmi_color_set_depth_test): a pair counts only if the vertex is in front of the
+        camera and its camera z is within `tolerance` of the view's depth at the pixel (> 0).  Off: the reference's colouring."""
+        self._check(self._lib.dmi_color_set_depth_test(self._h, 1 if enable else 0, float(tolerance)))
 
     def clear_views(self):
         self._check(self._lib.dmi_color_clear_views(self._h))
@@ -864,6 +881,8 @@ HOST_ABI_SYMBOLS = [
     "dmi_filter_last_error", "dmi_read_krtd_file", "dmi_extract_all_file_path", "dmi_k3_to_k4",
     "dmi_apply_depth_threshold", "dmi_read_depth_map", "dmi_read_depth_map_color", "dmi_mesh_coloration_from_lists",
     "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata", "dmi_write_polydata_with_normals",
+    "dmi_mesh_coloration_from_lists_with_depth", "dmi_read_polydata", "dmi_polydata_free", "dmi_polydata_counts",
+    "dmi_polydata_array", "dmi_polydata_designations", "dmi_color_cli_read_arguments", "dmi_color_cli_main",
 ]
 
 _host_bound = False
@@ -915,6 +934,21 @@ def load_host() -> ctypes.CDLL:
     L.dmi_mesh_coloration_from_lists.restype = ctypes.c_int
     L.dmi_mesh_coloration_from_lists.argtypes = [dp, i64, ctypes.c_char_p, ctypes.c_char_p, i32, ctypes.POINTER(ctypes.c_uint8),
                                                  ctypes.POINTER(ctypes.c_uint8), ip, ctypes.c_char_p, ctypes.c_size_t]
+    L.dmi_mesh_coloration_from_lists_with_depth.restype = ctypes.c_int
+    L.dmi_mesh_coloration_from_lists_with_depth.argtypes = [dp, i64, ctypes.c_char_p, ctypes.c_char_p, i32, ctypes.c_double,
+                                                            ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
+                                                            ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+    L.dmi_read_polydata.restype = ctypes.c_void_p
+    L.dmi_read_polydata.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+    L.dmi_polydata_free.restype = None
+    L.dmi_polydata_free.argtypes = [ctypes.c_void_p]
+    L.dmi_polydata_counts.restype = ctypes.c_int
+    L.dmi_polydata_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
+    L.dmi_polydata_array.restype = ctypes.c_int
+    L.dmi_polydata_array.argtypes = [ctypes.c_void_p, i32, i32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p),
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_void_p)]
+    L.dmi_polydata_designations.restype = ctypes.c_char_p
+    L.dmi_polydata_designations.argtypes = [ctypes.c_void_p, i32]
     L.dmi_write_polydata.restype = ctypes.c_int
     L.dmi_write_polydata.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64]
     L.dmi_write_polydata_with_normals.restype = ctypes.c_int
@@ -1136,8 +1170,9 @@ def read_depth_map_color(path):
     return c.reshape(dims[1], dims[0], 3)
 
 
-def mesh_coloration_from_lists(points, vti_list, krtd_list, device: int = 0):
-    """MeshColoration(mesh, vtiList, krtdList).ProcessColoration() through the host mirror (reads the .vti/.krtd files)."""
+def mesh_coloration_from_lists(points, vti_list, krtd_list, device: int = 0, depth_tolerance: float | None = None):
+    """MeshColoration(mesh, vtiList, krtdList).ProcessColoration() through the host mirror (reads the .vti/.krtd files).
+    depth_tolerance: with the depth test of dmi_color_set_depth_test (MeshColoration::SetDepthTolerance)."""
     L = load_host()
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     nv = pts.shape[0]
@@ -1146,9 +1181,92 @@ def mesh_coloration_from_lists(points, vti_list, krtd_list, device: int = 0):
     count = np.zeros(nv, dtype=np.int32)
     err = ctypes.create_string_buffer(512)
     u8 = ctypes.POINTER(ctypes.c_uint8)
-    ok = L.dmi_mesh_coloration_from_lists(_dp(pts), nv, os.fsencode(vti_list), os.fsencode(krtd_list), device,
-                                          mean.ctypes.data_as(u8), median.ctypes.data_as(u8),
-                                          count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), err, len(err))
+    outs = (mean.ctypes.data_as(u8), median.ctypes.data_as(u8), count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), err, len(err))
+    if depth_tolerance is None:
+        ok = L.dmi_mesh_coloration_from_lists(_dp(pts), nv, os.fsencode(vti_list), os.fsencode(krtd_list), device, *outs)
+    else:
+        ok = L.dmi_mesh_coloration_from_lists_with_depth(_dp(pts), nv, os.fsencode(vti_list), os.fsencode(krtd_list), device,
+                                                         float(depth_tolerance), *outs)
     if not ok:
         raise RuntimeError(err.value.decode())
     return mean, median, count
+
+
+# ---- the `Coloration` tool: .vtp in, coloured .vtp out (include/dmi_host.h) ----------------------------------------------------
+_VTK_DTYPES = {"Int8": np.int8, "UInt8": np.uint8, "Int16": np.int16, "UInt16": np.uint16, "Int32": np.int32, "UInt32": np.uint32,
+               "Int64": np.int64, "UInt64": np.uint64, "Float32": np.float32, "Float64": np.float64}
+
+
+class PolyDataFile(NamedTuple):
+    """What dmi_read_polydata reads from a .vtp: arrays in their stored types; a data array of one component is [n], else
+    [n, components]; designations are (key, value) pairs of <PointData ...> / <CellData ...>."""
+    points: np.ndarray
+    connectivity: np.ndarray
+    offsets: np.ndarray
+    point_data: dict
+    cell_data: dict
+    point_designations: list
+    cell_designations: list
+
+
+def read_polydata(path) -> PolyDataFile:
+    """VTK XML PolyData without VTK (csrc/host/vtp_reader.h); no GPU needed.  Raises ValueError with the reader's reason."""
+    L = load_host()
+    err = ctypes.create_string_buffer(4096)
+    h = L.dmi_read_polydata(os.fsencode(path), err, len(err))
+    if not h:
+        raise ValueError(err.value.decode())
+    try:
+        counts = (ctypes.c_int64 * 5)()
+        L.dmi_polydata_counts(h, counts)
+
+        def array(kind, index):
+            name, tname, comps, n, data = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_void_p()
+            if not L.dmi_polydata_array(h, kind, index, ctypes.byref(name), ctypes.byref(tname), ctypes.byref(comps), ctypes.byref(n),
+                                        ctypes.byref(data)):
+                raise ValueError(f"{path}: no array {kind}/{index}")
+            dt = np.dtype(_VTK_DTYPES[tname.value.decode()])
+            nbytes = n.value * comps.value * dt.itemsize
+            a = np.frombuffer(ctypes.string_at(data.value, nbytes) if nbytes else b"", dtype=dt).copy()
+            return name.value.decode(), (a.reshape(-1, comps.value) if comps.value != 1 else a)
+
+        def designations(cell):
+            text = L.dmi_polydata_designations(h, cell).decode()
+            return [tuple(line.split("=", 1)) for line in text.splitlines() if line]
+
+        return PolyDataFile(array(0, 0)[1], array(1, 0)[1], array(2, 0)[1],
+                            dict(array(3, i) for i in range(counts[3])), dict(array(4, i) for i in range(counts[4])),
+                            designations(0), designations(1))
+    finally:
+        L.dmi_polydata_free(h)
+
+
+class ColorCliOptionsC(ctypes.Structure):
+    _fields_ = [("input", ctypes.c_char * 4096), ("output", ctypes.c_char * 4096), ("krtd", ctypes.c_char * 4096),
+                ("vti", ctypes.c_char * 4096), ("verbose", ctypes.c_int32), ("device", ctypes.c_int32), ("depth_test", ctypes.c_int32),
+                ("depth_tolerance", ctypes.c_double)]
+
+
+def color_cli_read_arguments(args):
+    """ReadArguments of the `Coloration` tool (Coloration/main.cxx:105-135) on ["prog", "--flag", ...]:
+    (options or None, the text the tool would print)."""
+    L = load_host()
+    L.dmi_color_cli_read_arguments.restype = ctypes.c_int
+    L.dmi_color_cli_read_arguments.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ColorCliOptionsC),
+                                               ctypes.c_char_p, ctypes.c_size_t]
+    argv = (ctypes.c_char_p * len(args))(*[os.fsencode(a) for a in args])
+    out = ColorCliOptionsC()
+    err = ctypes.create_string_buffer(1 << 15)
+    ok = L.dmi_color_cli_read_arguments(len(args), argv, ctypes.byref(out), err, len(err))
+    return (out if ok else None), err.value.decode()
+
+
+def coloration_cli_binary() -> str:
+    """Path of the dmi_coloration executable next to the library (linked now if the build has not done so; see cli_binary)."""
+    from . import build as _build
+    try:
+        _build.build_color_cli()
+    except Exception:
+        if not os.path.exists(_build.COLOR_CLI_PATH):
+            raise
+    return _build.COLOR_CLI_PATH

@@ -16,6 +16,9 @@
 // lower nibbles the same way (more than 65 535 views: a bit-by-bit radix selection, eight reads).  Vertices are
 // processed in chunks that bound the scratch table.  Everything after the pixel selection is integer arithmetic, so the
 // three outputs are bit-identical to the reference's.
+//
+// Opt-in and not in the reference: the visibility test (dmi_color_set_depth_test, DESIGN.md 8b'): with resident depth planes a
+// pair counts only if the vertex's camera z is > 0 and within a tolerance of the view's depth (> 0) at the pixel.
 #include "../../include/dmi.h"
 #include "fusion_kernels.h"
 
@@ -115,6 +118,18 @@ __host__ __device__ inline int64_t color_plane_texels(int W, int H) {
 }
 __device__ __forceinline__ int64_t texel_index(int x, int y, int tiles_x) {
   return ((int64_t)(y >> kTexLogH) * tiles_x + (x >> kTexLogW)) * kTexTile + ((y & (kTexTileH - 1)) << kTexLogW) + (x & (kTexTileW - 1));
+}
+
+// [n][H][W] f64 depths in vtk point order -> [n] tiled f64 planes in the colour planes' layout (the same texel index serves
+// both gathers of a pair: dmi_color_add_views_with_depth)
+__global__ __launch_bounds__(256) void pack_depth_kernel(const double *__restrict__ src, double *__restrict__ dst, int W, int H,
+                                                         int64_t n_pixels_total) {
+  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n_pixels_total) return;
+  const int64_t npix = (int64_t)W * H;
+  const int64_t m = id / npix, r = id % npix;
+  const int y = (int)(r / W), x = (int)(r % W);
+  dst[m * color_plane_texels(W, H) + texel_index(x, y, (W + kTexTileW - 1) / kTexTileW)] = src[m * npix + (int64_t)(H - 1 - y) * W + x];
 }
 
 // [n][H][W][3] in vtk point order (row 0 = bottom, RD.cxx:106-108) -> [n] tiled RGBA planes, top row first
@@ -264,16 +279,34 @@ struct MedianSeed {
   uint32_t hi, rest01, rest23, rest45;
 };
 
+// The visibility test (dmi_color_set_depth_test): per view a tiled f64 depth plane, and the tolerance.  Passed
+// as a trailing parameter pack that is empty with the test off, so those instantiations are the plain pass instruction for
+// instruction.
+struct DepthTest {
+  const double *const *planes;  // [view] -> tiled plane (pack_depth_kernel)
+  double tol;
+};
+template <typename... T>
+__device__ __forceinline__ DepthTest depth_test_of(T... t) {
+  if constexpr (sizeof...(T) == 0) return DepthTest{nullptr, 0.0};
+  else return (t, ...);
+}
+
 // HIST: also fill, per lane, 16-bin histograms of the upper nibbles of the three channels in LDS (every lane owns a
 // column of counters: no barrier, no conflict) and leave the MedianSeed of the vertex: the first of the two passes of
 // the histogram medians costs no read of the scratch table.
-template <bool HIST, bool PIPE>
+// Depth (one DepthTest or nothing): a pair counts only if, besides the bounds test, the vertex's camera z cz (the reference's
+// TransformPoint row 2, every operation rounded) is > 0, the view's depth d at the pixel is > 0 and fabs(cz - d) <= tol.  The
+// depth is gathered in the same step as the texel and the test is made where the texel is consumed.
+template <bool HIST, bool PIPE, typename... Depth>
 __global__ __launch_bounds__(256) void project_color_kernel(const double *__restrict__ points, int64_t nv,
                                                             const uint32_t *__restrict__ perm,
                                                             const ColorView *__restrict__ views, int n, int W, int H,
                                                             uchar4 *__restrict__ scratch, uint8_t *__restrict__ mean,
                                                             int32_t *__restrict__ count, MedianSeed *__restrict__ seeds,
-                                                            const ViewMargin *__restrict__ margins) {
+                                                            const ViewMargin *__restrict__ margins, Depth... depth) {
+  constexpr bool DEPTH = sizeof...(Depth) > 0;
+  const DepthTest dt = depth_test_of(depth...);
   __shared__ uint32_t hist[HIST ? 3 * kHistWords * 256 : 1];  // [channel][word][lane]: 24 KB
   const int lane = threadIdx.x;
   const int tiles_x = (W + kTexTileW - 1) / kTexTileW;
@@ -289,7 +322,8 @@ __global__ __launch_bounds__(256) void project_color_kernel(const double *__rest
   if constexpr (HIST)
     for (int q = 0; q < 3 * kHistWords; ++q) hist[q * 256 + lane] = 0;
   // what happens to a view's texel once it has arrived: count, integer sums, histogram, the scratch table's entry
-  auto consume = [&](int mq, uchar4 c, bool ok) {
+  auto consume = [&](int mq, uchar4 c, bool ok, double d, double cz) {
+    if constexpr (DEPTH) ok = ok && d > 0.0 && __builtin_fabs(cz - d) <= dt.tol;  // (cz > 0 was part of ok; NaN: false)
     uchar4 out = make_uchar4(0, 0, 0, 0);
     if (ok) {
       out = make_uchar4(c.x, c.y, c.z, 1);
@@ -306,7 +340,7 @@ __global__ __launch_bounds__(256) void project_color_kernel(const double *__rest
     scratch[(int64_t)mq * nv + id] = out;
   };
   // the view's pixel for this vertex and the request for its texel
-  auto project = [&](int m, uchar4 &c, bool &ok) __attribute__((always_inline)) {
+  auto project = [&](int m, uchar4 &c, bool &ok, double &d, double &cz) __attribute__((always_inline)) {
     const ColorView *v = views + m;  // wave-uniform
     // The pixel only has to be the reference's pixel: the homogeneous coordinates come from the rows of K3*[R|T] (nine
     // FMAs instead of the reference's 33 operations), and the pixel they select is taken when it provably is the
@@ -332,8 +366,17 @@ __global__ __launch_bounds__(256) void project_color_kernel(const double *__rest
       is_pixel = by_dz.round_to_pixel(dx, dz, px) && by_dz.round_to_pixel(dy, dz, py);   // RD.cxx:177-181
     }
     ok = is_pixel && px >= 0 && py >= 0 && px < W && py < H;                             // MC.cxx:158-163
+    if constexpr (DEPTH) {
+      // the camera z of TransformPoint (RD.cxx:173), not the shortcut's az
+      cz = ((cload(&v->rt[8]) * x + cload(&v->rt[9]) * y) + cload(&v->rt[10]) * z) + cload(&v->rt[11]);
+      ok = ok && cz > 0.0;
+      d = 0.0;
+    }
     c = make_uchar4(0, 0, 0, 0);
-    if (ok) c = cload(&v->color)[texel_index(px, py, tiles_x)];     // RD.cxx:106-108 (row flip and tiling done at upload)
+    if (ok) {
+      c = cload(&v->color)[texel_index(px, py, tiles_x)];     // RD.cxx:106-108 (row flip and tiling done at upload)
+      if constexpr (DEPTH) d = cload(&dt.planes[m])[texel_index(px, py, tiles_x)];
+    }
   };
   if constexpr (PIPE) {
     // Vertices in the caller's order (a mesh: neighbours in neighbouring lanes): the loop software-pipelined.  View m's texel is
@@ -351,36 +394,42 @@ __global__ __launch_bounds__(256) void project_color_kernel(const double *__rest
     constexpr int K = DMI_COLOR_AHEAD;  // views between a texel's request and its use
     uchar4 slot_c[K];
     bool slot_ok[K];
+    double slot_d[K] = {}, slot_cz[K] = {};  // (the depth test's: the gathered depth and the camera z; unused without it)
     int m = 0;
     if (n >= K) {
 #pragma unroll
-      for (int q = 0; q < K; ++q) project(q, slot_c[q], slot_ok[q]);
+      for (int q = 0; q < K; ++q) project(q, slot_c[q], slot_ok[q], slot_d[q], slot_cz[q]);
       for (m = K; m + K <= n; m += K) {
 #pragma unroll
         for (int q = 0; q < K; ++q) {
           uchar4 c;
           bool ok;
-          project(m + q, c, ok);
-          consume(m + q - K, slot_c[q], slot_ok[q]);  // the view this slot held
+          double d = 0.0, cz = 0.0;
+          project(m + q, c, ok, d, cz);
+          consume(m + q - K, slot_c[q], slot_ok[q], slot_d[q], slot_cz[q]);  // the view this slot held
           slot_c[q] = c;
           slot_ok[q] = ok;
+          slot_d[q] = d;
+          slot_cz[q] = cz;
         }
       }
 #pragma unroll
-      for (int q = 0; q < K; ++q) consume(m - K + q, slot_c[q], slot_ok[q]);
+      for (int q = 0; q < K; ++q) consume(m - K + q, slot_c[q], slot_ok[q], slot_d[q], slot_cz[q]);
     }
     for (; m < n; ++m) {  // the views a whole round of K does not cover
       uchar4 c;
       bool ok;
-      project(m, c, ok);
-      consume(m, c, ok);
+      double d = 0.0, cz = 0.0;
+      project(m, c, ok, d, cz);
+      consume(m, c, ok, d, cz);
     }
   } else {
     for (int m = 0; m < n; ++m) {
       uchar4 c;
       bool ok;
-      project(m, c, ok);
-      consume(m, c, ok);
+      double d = 0.0, cz = 0.0;
+      project(m, c, ok, d, cz);
+      consume(m, c, ok, d, cz);
     }
   }
   count[vtx] = cnt;  // MC.cxx:186 (0 when no view sees the vertex, MC.cxx:130)
@@ -538,6 +587,7 @@ thread_local std::string g_color_error;
 
 struct ColorBatch {
   uchar4 *d_rgba = nullptr;
+  double *d_depth = nullptr;  // tiled f64 depth planes (dmi_color_add_views_with_depth), else null
   int32_t n = 0;
 };
 
@@ -551,6 +601,11 @@ struct dmi_color_context {
   std::vector<ColorView> h_views;
   ColorView *d_views = nullptr;
   size_t d_views_capacity = 0;
+  // the visibility test (dmi_color_set_depth_test): per view its depth plane or null, and the same on the device
+  std::vector<const double *> h_depth_planes;
+  const double **d_depth_planes = nullptr;
+  bool depth_test = false;
+  double depth_tol = 0.0;
   bool views_dirty = false;
   // per-chunk work buffers, grown on demand.  Round 5: the vertices, the three outputs, the chunk's magnitudes and margins exist
   // TWICE, and a chunk's copy in (h2d stream), kernels (stream) and copies out (d2h stream) overlap its neighbours'
@@ -666,8 +721,8 @@ void dmi_color_destroy(dmi_color_context *c) {
   (void)hipSetDevice(c->device);
   for (hipStream_t st : {c->h2d, c->stream, c->d2h})
     if (st) (void)hipStreamSynchronize(st);
-  for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba);
-  for (void *p : {(void *)c->d_views, (void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_scratch, (void *)c->d_mean[0], (void *)c->d_mean[1],
+  for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba), (void)hipFree(b.d_depth);
+  for (void *p : {(void *)c->d_views, (void *)c->d_depth_planes, (void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_scratch, (void *)c->d_mean[0], (void *)c->d_mean[1],
                   (void *)c->d_median[0], (void *)c->d_median[1], (void *)c->d_count[0], (void *)c->d_count[1], (void *)c->d_seeds, (void *)c->d_margins[0],
                   (void *)c->d_margins[1], (void *)c->d_pmax[0], (void *)c->d_pmax[1], (void *)c->d_stage, (void *)c->d_keys, (void *)c->d_keys_sorted,
                   (void *)c->d_index, (void *)c->d_perm, c->d_sort_temp, (void *)c->d_box})
@@ -745,6 +800,7 @@ int dmi_color_add_views(dmi_color_context *c, const uint8_t *colors, const doubl
         v.mag[4 * r + q] = mag;
       }
     c->h_views.push_back(v);
+    c->h_depth_planes.push_back(nullptr);
   }
   c->views_dirty = true;
   return DMI_OK;
@@ -756,11 +812,79 @@ int dmi_color_clear_views(dmi_color_context *c) {
   if (!c) return DMI_ERR_INVALID_ARGUMENT;
   DMI_COLOR_HIP(c, hipSetDevice(c->device));
   DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
-  for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba);
+  for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba), (void)hipFree(b.d_depth);
   c->batches.clear();
   c->h_views.clear();
+  c->h_depth_planes.clear();
   c->views_dirty = true;
   c->W = c->H = 0;
+  return DMI_OK;
+  });
+}
+
+int dmi_color_add_views_with_depth(dmi_color_context *c, const uint8_t *colors, const double *depths, const double *K4,
+                                   const double *RT4, int32_t n, int32_t width, int32_t height) {
+  return guarded(c, "dmi_color_add_views_with_depth", [&]() -> int {
+  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, "dmi_color_add_views_with_depth: null context");
+  if (!depths) return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_add_views_with_depth: null argument");
+  // the colour planes and camera records exactly as dmi_color_add_views (which checks everything else) ...
+  const int rc = dmi_color_add_views(c, colors, K4, RT4, n, width, height);
+  if (rc != DMI_OK) return rc;
+  // ... then the depth planes; on a failure the views just appended go again, so that the call adds all or nothing
+  auto undo = [&](double *planes, const std::string &msg) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(planes);
+    ColorBatch b = c->batches.back();
+    (void)hipFree(b.d_rgba);
+    c->batches.pop_back();
+    c->h_views.resize(c->h_views.size() - (size_t)n);
+    c->h_depth_planes.resize(c->h_depth_planes.size() - (size_t)n);
+    if (c->batches.empty()) c->W = c->H = 0;
+    c->views_dirty = true;
+    return cfail(c, DMI_ERR_DEVICE, "dmi_color_add_views_with_depth: " + msg);
+  };
+  const size_t npix = (size_t)width * height, plane = (size_t)color_plane_texels(width, height);
+  double *planes = nullptr;
+  hipError_t e = hipMalloc(&planes, plane * (size_t)n * sizeof(double));
+  if (e != hipSuccess) return undo(nullptr, std::string("hipMalloc(depth planes): ") + hipGetErrorString(e));
+  e = hipMemsetAsync(planes, 0, plane * (size_t)n * sizeof(double), c->stream);  // (the tiles' padding: never read)
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(256) << 20) / (npix * sizeof(double))), (size_t)n);
+  if (e == hipSuccess && c->stage_capacity < chunk * npix * sizeof(double)) {
+    e = hipStreamSynchronize(c->stream);
+    if (c->d_stage) (void)hipFree(c->d_stage);
+    c->d_stage = nullptr;
+    c->stage_capacity = 0;
+    if (e == hipSuccess) e = hipMalloc(&c->d_stage, chunk * npix * sizeof(double));
+    if (e == hipSuccess) c->stage_capacity = chunk * npix * sizeof(double);
+  }
+  for (size_t m0 = 0; e == hipSuccess && m0 < (size_t)n; m0 += chunk) {
+    const size_t cnt = std::min(chunk, (size_t)n - m0);
+    e = hipMemcpyAsync(c->d_stage, depths + m0 * npix, cnt * npix * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+      const int64_t total = (int64_t)(cnt * npix);
+      hipLaunchKernelGGL(pack_depth_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
+                         reinterpret_cast<const double *>(c->d_stage), planes + m0 * plane, width, height, total);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the stage buffer is reused by the next chunk
+  }
+  if (e != hipSuccess) return undo(planes, std::string("depth upload: ") + hipGetErrorString(e));
+  c->batches.back().d_depth = planes;
+  const size_t first = c->h_depth_planes.size() - (size_t)n;
+  for (int32_t m = 0; m < n; ++m) c->h_depth_planes[first + (size_t)m] = planes + (size_t)m * plane;
+  c->views_dirty = true;
+  return DMI_OK;
+  });
+}
+
+int dmi_color_set_depth_test(dmi_color_context *c, int32_t enable, double tolerance) {
+  return guarded(c, "dmi_color_set_depth_test", [&]() -> int {
+  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, "dmi_color_set_depth_test: null context");
+  if (!(tolerance >= 0.0 && tolerance <= 1.7976931348623157e308))  // NaN, negative, infinite
+    return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_set_depth_test: the tolerance must be finite and >= 0");
+  c->depth_test = enable != 0;
+  c->depth_tol = tolerance;
   return DMI_OK;
   });
 }
@@ -802,6 +926,11 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
     return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: null argument");
   const size_t n_views = c->h_views.size();
   if (n_views == 0) return cfail(c, DMI_ERR_STATE, "dmi_color_process: no views resident (MC.cxx:102-106)");
+  if (c->depth_test)
+    for (size_t m = 0; m < n_views; ++m)
+      if (!c->h_depth_planes[m])
+        return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: the depth test is on and view " + std::to_string(m) +
+                                                      " was added without depths (dmi_color_add_views_with_depth)");
   c->last_kernel_ms = 0.0;
   if (n_points == 0) return DMI_OK;
   DMI_COLOR_HIP(c, hipSetDevice(c->device));
@@ -810,6 +939,9 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
     c->d_views = nullptr;
     c->d_views_capacity = 0;
     DMI_COLOR_HIP(c, hipMalloc(&c->d_views, n_views * sizeof(ColorView)));
+    if (c->d_depth_planes) (void)hipFree(c->d_depth_planes);
+    c->d_depth_planes = nullptr;
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_depth_planes, n_views * sizeof(const double *)));
     for (int b = 0; b < 2; ++b) {
       if (c->d_margins[b]) (void)hipFree(c->d_margins[b]);
       c->d_margins[b] = nullptr;
@@ -821,6 +953,8 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
   }
   if (c->views_dirty) {
     DMI_COLOR_HIP(c, hipMemcpyAsync(c->d_views, c->h_views.data(), n_views * sizeof(ColorView), hipMemcpyHostToDevice, c->stream));
+    DMI_COLOR_HIP(c, hipMemcpyAsync(c->d_depth_planes, c->h_depth_planes.data(), n_views * sizeof(const double *), hipMemcpyHostToDevice,
+                                    c->stream));
     DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
     c->views_dirty = false;
   }
@@ -920,6 +1054,7 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
                                               0, 30, c->stream));
       perm = c->d_perm;
     }
+    const DepthTest depth{c->d_depth_planes, c->depth_tol};
     bool histogram_medians = n_views <= 65535;
 #ifdef DMI_TUNING
     if (getenv("DMI_COLOR_BITWISE_MEDIAN")) histogram_medians = false;  // A/B of the two median kernels
@@ -933,7 +1068,13 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
 #ifdef DMI_TUNING
       if (const char *env = getenv("DMI_DEBUG_COLOR_EXTRA_LDS")) extra_lds = (unsigned)strtoul(env, nullptr, 0);
 #endif
-      if (!perm && !coherent)
+      if (c->depth_test && !perm && !coherent)
+        hipLaunchKernelGGL((project_color_kernel<true, false, DepthTest>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm,
+                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b], depth);
+      else if (c->depth_test)
+        hipLaunchKernelGGL((project_color_kernel<true, true, DepthTest>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm,
+                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b], depth);
+      else if (!perm && !coherent)
         hipLaunchKernelGGL((project_color_kernel<true, false>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm, c->d_views,
                            (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b]);
       else
@@ -943,8 +1084,12 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
       hipLaunchKernelGGL(median_low_nibble_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scratch, nv, (int)n_views, perm,
                          c->d_count[b], c->d_seeds, c->d_median[b]);
     } else {
-      hipLaunchKernelGGL((project_color_kernel<false, false>), dim3(blocks), dim3(256), 0, c->stream, c->d_points[b], nv, perm, c->d_views,
-                         (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b]);
+      if (c->depth_test)
+        hipLaunchKernelGGL((project_color_kernel<false, false, DepthTest>), dim3(blocks), dim3(256), 0, c->stream, c->d_points[b], nv, perm,
+                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b], depth);
+      else
+        hipLaunchKernelGGL((project_color_kernel<false, false>), dim3(blocks), dim3(256), 0, c->stream, c->d_points[b], nv, perm, c->d_views,
+                           (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b]);
       DMI_COLOR_TRY(hipGetLastError());
       hipLaunchKernelGGL(median_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scratch, nv, (int)n_views, perm,
                          c->d_count[b], c->d_median[b]);

@@ -8,8 +8,10 @@
 #include <string>
 #include <vector>
 
+#include "color_cli.h"
 #include "recon_host.h"
 #include "recon_cli.h"
+#include "vtp_reader.h"
 
 using dmi::host::DepthImage;
 using dmi::host::ReconstructionData;
@@ -182,24 +184,136 @@ int dmi_read_depth_map_color(const char *path, int32_t dims[3], uint8_t *color, 
   });
 }
 
-int dmi_mesh_coloration_from_lists(const double *points, int64_t n_points, const char *vti_list, const char *krtd_list,
-                                   int32_t device, uint8_t *mean, uint8_t *median, int32_t *count, char *err, size_t errlen) {
-  return guarded<int>(0, [&]() -> int {
+namespace {
+void copy_text(const std::string &m, char *dst, size_t len) {
+  if (dst && len > 0) {
+    std::strncpy(dst, m.c_str(), len - 1);
+    dst[len - 1] = 0;
+  }
+}
+
+int mesh_coloration_from_lists(const double *points, int64_t n_points, const char *vti_list, const char *krtd_list, int32_t device,
+                               const double *depth_tolerance, uint8_t *mean, uint8_t *median, int32_t *count, char *err, size_t errlen) {
   auto fail = [&](const std::string &m) {
-    if (err && errlen > 0) {
-      std::strncpy(err, m.c_str(), errlen - 1);
-      err[errlen - 1] = 0;
-    }
+    copy_text(m, err, errlen);
     return 0;
   };
   if (!points || !vti_list || !krtd_list || !mean || !median || !count || n_points < 0) return fail("null argument");
   dmi::host::MeshColoration mc(points, n_points, vti_list, krtd_list);
   mc.SetDevice(device);
+  if (depth_tolerance) mc.SetDepthTolerance(*depth_tolerance);
   if (!mc.ProcessColoration()) return fail(mc.LastError());
   std::memcpy(mean, mc.GetMeanColoration().data(), (size_t)n_points * 3);
   std::memcpy(median, mc.GetMedianColoration().data(), (size_t)n_points * 3);
   for (int64_t i = 0; i < n_points; ++i) count[i] = mc.GetNbProjectedDepthMap()[(size_t)i];
   return 1;
+}
+}  // namespace
+
+int dmi_mesh_coloration_from_lists_with_depth(const double *points, int64_t n_points, const char *vti_list, const char *krtd_list,
+                                              int32_t device, double depth_tolerance, uint8_t *mean, uint8_t *median, int32_t *count,
+                                              char *err, size_t errlen) {
+  return guarded<int>(0, [&]() -> int {
+    return mesh_coloration_from_lists(points, n_points, vti_list, krtd_list, device, &depth_tolerance, mean, median, count, err, errlen);
+  });
+}
+
+struct dmi_polydata {
+  dmi::host::vtp::PolyData mesh;
+  std::string designations[2];
+};
+
+dmi_polydata *dmi_read_polydata(const char *path, char *err, size_t errlen) {
+  return guarded<dmi_polydata *>(nullptr, [&]() -> dmi_polydata * {
+    if (!path) {
+      copy_text("null path", err, errlen);
+      return nullptr;
+    }
+    std::unique_ptr<dmi_polydata> pd(new dmi_polydata());
+    std::string why;
+    if (!dmi::host::vtp::ReadPolyData(path, &pd->mesh, &why)) {
+      copy_text(why, err, errlen);
+      return nullptr;
+    }
+    for (int cell = 0; cell < 2; ++cell)
+      for (const auto &kv : cell ? pd->mesh.cell_designations : pd->mesh.point_designations)
+        pd->designations[cell] += kv.first + "=" + kv.second + "\n";
+    return pd.release();
+  });
+}
+
+void dmi_polydata_free(dmi_polydata *pd) { delete pd; }
+
+int dmi_polydata_counts(const dmi_polydata *pd, int64_t out[5]) {
+  if (!pd || !out) return 0;
+  out[0] = pd->mesh.n_points;
+  out[1] = pd->mesh.n_polys;
+  out[2] = pd->mesh.n_polys ? pd->mesh.OffsetAt(pd->mesh.n_polys - 1) : 0;
+  out[3] = (int64_t)pd->mesh.point_data.size();
+  out[4] = (int64_t)pd->mesh.cell_data.size();
+  return 1;
+}
+
+int dmi_polydata_array(const dmi_polydata *pd, int32_t kind, int32_t index, const char **name, const char **type, int32_t *components,
+                       int64_t *n_tuples, const void **data) {
+  if (!pd) return 0;
+  const dmi::host::vtp::PolyData &m = pd->mesh;
+  const dmi::host::vtp::Array *a = nullptr;
+  int64_t tuples = 0;
+  if (kind == 0) a = &m.points, tuples = m.n_points;
+  else if (kind == 1) a = &m.connectivity, tuples = m.n_polys ? m.OffsetAt(m.n_polys - 1) : 0;
+  else if (kind == 2) a = &m.offsets, tuples = m.n_polys;
+  else if (kind == 3 && index >= 0 && (size_t)index < m.point_data.size()) a = &m.point_data[(size_t)index], tuples = m.n_points;
+  else if (kind == 4 && index >= 0 && (size_t)index < m.cell_data.size()) a = &m.cell_data[(size_t)index], tuples = m.n_polys;
+  if (!a) return 0;
+  if (name) *name = a->name.c_str();
+  if (type) *type = a->type.c_str();
+  if (components) *components = a->components;
+  if (n_tuples) *n_tuples = tuples;
+  if (data) *data = a->bytes.data();
+  return 1;
+}
+
+const char *dmi_polydata_designations(const dmi_polydata *pd, int32_t cell) {
+  return pd ? pd->designations[cell ? 1 : 0].c_str() : "";
+}
+
+int dmi_color_cli_read_arguments(int32_t argc, const char *const *argv, dmi_color_cli_options *out, char *err, size_t errlen) {
+  return guarded<int>(0, [&]() -> int {
+  if (!argv || !out || argc < 0) return 0;
+  dmi::host::color_cli::Options o;
+  std::ostringstream text;
+  const bool ok = dmi::host::color_cli::ReadArguments(argc, argv, &o, text);
+  copy_text(text.str(), err, errlen);
+  if (!ok) return 0;
+  std::memset(out, 0, sizeof(*out));
+  copy_text(o.input, out->input, sizeof(out->input));
+  copy_text(o.output, out->output, sizeof(out->output));
+  copy_text(o.krtd, out->krtd, sizeof(out->krtd));
+  copy_text(o.vti, out->vti, sizeof(out->vti));
+  out->verbose = o.verbose;
+  out->device = o.device;
+  out->depth_test = o.depthTest;
+  out->depth_tolerance = o.depthTolerance;
+  return 1;
+  });
+}
+
+int dmi_color_cli_main(int32_t argc, const char *const *argv) {
+  return guarded<int>(1, [&]() -> int {
+  dmi::host::color_cli::Options o;
+  if (!dmi::host::color_cli::ReadArguments(argc, argv, &o, std::cerr)) return 1;  // EXIT_FAILURE, cmain:71-74
+  std::string error;
+  const int rc = dmi::host::color_cli::Run(o, std::cout, &error);
+  if (rc != 0) std::cerr << "dmi_coloration: " << error << std::endl;
+  return rc;
+  });
+}
+
+int dmi_mesh_coloration_from_lists(const double *points, int64_t n_points, const char *vti_list, const char *krtd_list,
+                                   int32_t device, uint8_t *mean, uint8_t *median, int32_t *count, char *err, size_t errlen) {
+  return guarded<int>(0, [&]() -> int {
+    return mesh_coloration_from_lists(points, n_points, vti_list, krtd_list, device, nullptr, mean, median, count, err, errlen);
   });
 }
 

@@ -801,7 +801,12 @@ bool MeshColoration::ProcessColoration() {
   }
   const int W = first->dims[0], H = first->dims[1];  // MC.cxx:111: dimensions of view 0
   const size_t npix = (size_t)W * H;
+  if (DepthTest && !(DepthTolerance >= 0.0 && std::isfinite(DepthTolerance))) {
+    Error = "MeshColoration: the depth tolerance must be finite and >= 0";
+    return false;
+  }
   std::vector<unsigned char> colors(npix * 3 * (size_t)nbDepthMap);
+  std::vector<double> depths(DepthTest ? npix * (size_t)nbDepthMap : 0);
   std::vector<double> K4(16 * (size_t)nbDepthMap), RT(16 * (size_t)nbDepthMap);
   for (int m = 0; m < nbDepthMap; ++m) {
     DepthImage *img = DataList[m]->GetDepthMap();
@@ -810,6 +815,14 @@ bool MeshColoration::ProcessColoration() {
       std::cerr << Error << std::endl;
       return false;
     }
+    if (DepthTest) {
+      if (img->depths.size() != npix) {  // (ReadDepthMap already requires a Float64 "Depths" array, RD.cxx:143-146)
+        Error = "MeshColoration: view " + std::to_string(m) + " has no 'Depths' array of the size of view 0 (the depth test needs it)";
+        std::cerr << Error << std::endl;
+        return false;
+      }
+      std::memcpy(&depths[(size_t)m * npix], img->depths.data(), npix * sizeof(double));
+    }
     std::memcpy(&colors[(size_t)m * npix * 3], img->color.data(), npix * 3);
     std::memcpy(&K4[16 * (size_t)m], DataList[m]->Get4MatrixK(), 16 * sizeof(double));
     std::memcpy(&RT[16 * (size_t)m], DataList[m]->GetMatrixTR(), 16 * sizeof(double));
@@ -817,8 +830,20 @@ bool MeshColoration::ProcessColoration() {
   Mean.assign((size_t)nv * 3, 0);   // MC.cxx:113-133: arrays start at 0
   Median.assign((size_t)nv * 3, 0);
   std::vector<int32_t> count((size_t)nv, 0);
-  const int rc = dmi_color_mesh(Points.data(), nv, colors.data(), K4.data(), RT.data(), nbDepthMap, W, H, Device, Mean.data(),
-                                Median.data(), count.data());
+  int rc = DMI_OK;
+  if (nv == 0) {
+    // no vertex: nothing to colour, no device needed
+  } else if (!DepthTest) {
+    rc = dmi_color_mesh(Points.data(), nv, colors.data(), K4.data(), RT.data(), nbDepthMap, W, H, Device, Mean.data(), Median.data(),
+                        count.data());
+  } else {
+    dmi_color_context *ctx = nullptr;
+    rc = dmi_color_create(Device, &ctx);
+    if (rc == DMI_OK) rc = dmi_color_add_views_with_depth(ctx, colors.data(), depths.data(), K4.data(), RT.data(), nbDepthMap, W, H);
+    if (rc == DMI_OK) rc = dmi_color_set_depth_test(ctx, 1, DepthTolerance);
+    if (rc == DMI_OK) rc = dmi_color_process(ctx, Points.data(), nv, Mean.data(), Median.data(), count.data());
+    if (ctx) dmi_color_destroy(ctx);  // (the message stays in dmi_color_last_error)
+  }
   if (rc != DMI_OK) {
     Error = dmi_color_last_error();
     return false;

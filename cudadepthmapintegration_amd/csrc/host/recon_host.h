@@ -237,7 +237,8 @@ class ReconstructionFilter {
 
 // ---- Coloration/MeshColoration ---------------------------------------------------------------------------
 // MC.h:42-61.  The mesh contributes only its points (MC.cxx:109-110); the output is the three point-data arrays
-// the reference adds to the mesh (MC.cxx:194-196).  ProcessColoration runs on the GPU (dmi_color_mesh).
+// the reference adds to the mesh (MC.cxx:194-196).  ProcessColoration runs on the GPU (dmi_color_mesh; with the depth test
+// the resident-view context: dmi_color_add_views_with_depth, dmi_color_set_depth_test).
 class MeshColoration {
  public:
   MeshColoration();
@@ -252,8 +253,18 @@ class MeshColoration {
   const std::vector<int> &GetNbProjectedDepthMap() const { return Count; }          // "NbProjectedDepthMap"
   const std::string &LastError() const { return Error; }
   void SetDevice(int d) { Device = d; }
+  // Not in the reference: the visibility test of dmi_color_set_depth_test (a pair counts only if the view's "Depths" value at
+  // the pixel is within `tolerance` of the vertex's camera z, both > 0); needs every view's "Depths" array.  A NaN, infinite or
+  // negative tolerance fails ProcessColoration.  ClearDepthTest: back to the reference's colouring.
+  void SetDepthTolerance(double tolerance) {
+    DepthTest = true;
+    DepthTolerance = tolerance;
+  }
+  void ClearDepthTest() { DepthTest = false; }
 
  private:
+  bool DepthTest = false;
+  double DepthTolerance = 0.0;
   std::vector<double> Points;
   bool HasInput = false;
   std::vector<ReconstructionData *> DataList;

@@ -1,4 +1,5 @@
-// vti_reader.cpp -- see vti_reader.h.  Host-only C++; zlib is the one codec used (vtkZLibDataCompressor).
+// vti_reader.cpp -- see vti_reader.h.  Host-only C++; zlib is the one codec used (vtkZLibDataCompressor).  Also the home of the
+// container decoding the .vtp reader shares (vtk_xml_data.h): this file still builds on its own, with zlib alone.
 #include "vti_reader.h"
 
 #include <zlib.h>
@@ -11,9 +12,12 @@
 #include <fstream>
 #include <sstream>
 
+#include "vtk_xml_data.h"
+
+// ---- the shared container decoding (vtk_xml_data.h) ----------------------------------------------------------------------
 namespace dmi {
 namespace host {
-namespace vti {
+namespace vtkxml {
 namespace {
 
 bool fail(std::string *err, const std::string &msg) {
@@ -92,12 +96,6 @@ void swap_elements(unsigned char *p, size_t n_elems, size_t size) {
   if (size < 2) return;
   for (size_t i = 0; i < n_elems; ++i) std::reverse(p + i * size, p + (i + 1) * size);
 }
-
-struct Format {
-  size_t header_word = 4;  // header_type UInt32 (the default of version 0.1 files) or UInt64
-  bool swap = false;       // file byte order differs from the host's
-  bool zlib = false;
-};
 
 uint64_t header_word(const unsigned char *p, const Format &f, size_t index) {
   unsigned char w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -219,6 +217,137 @@ bool decode_b64(const std::string &text, size_t pos, size_t end, const Format &f
 
 }  // namespace
 
+bool Fail(std::string *err, const std::string &msg) { return fail(err, msg); }
+bool Attr(const std::string &tag, const std::string &name, std::string *out) { return attr(tag, name, out); }
+size_t TypeSize(const std::string &type) { return type_size(type); }
+
+std::vector<std::pair<std::string, std::string>> Attributes(const std::string &tag) {
+  std::vector<std::pair<std::string, std::string>> out;
+  size_t p = tag.find_first_of(" \t\r\n");
+  while (p != std::string::npos && p < tag.size()) {
+    while (p < tag.size() && std::isspace((unsigned char)tag[p])) ++p;
+    const size_t eq = tag.find("=\"", p);
+    if (eq == std::string::npos) break;
+    const size_t close = tag.find('"', eq + 2);
+    if (close == std::string::npos) break;
+    out.emplace_back(tag.substr(p, eq - p), tag.substr(eq + 2, close - eq - 2));
+    p = close + 1;
+  }
+  return out;
+}
+
+bool ReadFormat(const std::string &vtag, const std::string &path, Format *fmt, std::string *err) {
+  std::string s;
+  if (attr(vtag, "header_type", &s)) {
+    if (s == "UInt64") fmt->header_word = 8;
+    else if (s != "UInt32") return fail(err, path + ": unsupported header_type " + s);
+  }
+  if (attr(vtag, "byte_order", &s)) fmt->swap = s == "BigEndian";
+  if (attr(vtag, "compressor", &s) && !s.empty()) {
+    if (s != "vtkZLibDataCompressor") return fail(err, path + ": unsupported compressor " + s + " (only vtkZLibDataCompressor)");
+    fmt->zlib = true;
+  }
+  return true;
+}
+
+bool FindAppended(const std::string &text, size_t from, const std::string &path, Appended *out, size_t *xml_end, std::string *err) {
+  const std::string::size_type app = text.find("<AppendedData", from);
+  if (app != std::string::npos) {
+    const std::string::size_type app_end = text.find('>', app);
+    if (app_end == std::string::npos) return fail(err, path + ": malformed <AppendedData>");
+    const std::string atag = text.substr(app, app_end - app);
+    std::string s;
+    if (attr(atag, "encoding", &s)) out->raw = s == "raw";
+    const std::string::size_type us = text.find('_', app_end);
+    if (us == std::string::npos) return fail(err, path + ": <AppendedData> without the '_' marker");
+    out->data = us + 1;
+  }
+  *xml_end = app != std::string::npos ? app : text.size();
+  return true;
+}
+
+bool DecodeDataArray(const std::string &text, const std::string &tag, bool self_closed, size_t p, size_t limit,
+                     const Appended &app, const Format &fmt, size_t n_tuples, const std::string &path, Array *a_out, size_t *next,
+                     std::string *err) {
+  Array &a = *a_out;
+  std::string s, format = "ascii";
+  attr(tag, "format", &format);
+  const size_t n_values = n_tuples * (size_t)a.components;
+  const size_t n_bytes = n_values * a.elem_size;
+  *next = p;
+  if (format == "appended") {
+    if (app.data == std::string::npos) return fail(err, path + ": appended array without <AppendedData>");
+    if (!attr(tag, "offset", &s)) return fail(err, path + ": appended array '" + a.name + "' without offset");
+    const unsigned long long off = std::strtoull(s.c_str(), nullptr, 10);
+    if (off > text.size() - app.data) return fail(err, path + ": offset of '" + a.name + "' is past the end of the file");
+    std::string why;
+    const bool ok = app.raw ? decode_raw(reinterpret_cast<const unsigned char *>(text.data()) + app.data + off,
+                                         text.size() - app.data - (size_t)off, fmt, n_bytes, &a.bytes, &why)
+                            : decode_b64(text, app.data + (size_t)off, text.size(), fmt, n_bytes, &a.bytes, &why);
+    if (!ok) return fail(err, path + ": array '" + a.name + "': " + why);
+  } else {
+    if (self_closed) return fail(err, path + ": inline array '" + a.name + "' has no content");
+    const std::string::size_type close = text.find("</DataArray>", p);
+    if (close == std::string::npos || close > limit) return fail(err, path + ": unterminated <DataArray>");
+    if (format == "binary") {
+      std::string why;
+      if (!decode_b64(text, p, close, fmt, n_bytes, &a.bytes, &why)) return fail(err, path + ": array '" + a.name + "': " + why);
+    } else if (format == "ascii") {
+      if (n_values > (close - p)) return fail(err, path + ": array '" + a.name + "' has fewer values than points");
+      a.bytes.resize(n_bytes);
+      const char *c = text.data() + p;
+      const char *const cend = text.data() + close;
+      const bool is_float = a.type == "Float32" || a.type == "Float64";
+      const bool is_signed = a.type[0] == 'I';
+      for (size_t i = 0; i < n_values; ++i) {
+        while (c < cend && std::isspace((unsigned char)*c)) ++c;
+        if (c >= cend) return fail(err, path + ": array '" + a.name + "' has fewer values than points");
+        char *nxt = nullptr;
+        unsigned char *dst = a.bytes.data() + i * a.elem_size;
+        if (is_float) {
+          const double v = std::strtod(c, &nxt);
+          if (a.elem_size == 8) std::memcpy(dst, &v, 8);
+          else { const float w = (float)v; std::memcpy(dst, &w, 4); }
+        } else if (is_signed) {
+          const long long v = std::strtoll(c, &nxt, 10);
+          std::memcpy(dst, &v, a.elem_size);  // little-endian host: the low bytes
+        } else {
+          const unsigned long long v = std::strtoull(c, &nxt, 10);
+          std::memcpy(dst, &v, a.elem_size);
+        }
+        if (nxt == c) return fail(err, path + ": array '" + a.name + "' holds something that is not a number");
+        c = nxt;
+      }
+      *next = close;
+      return true;  // text values have no byte order
+    } else {
+      return fail(err, path + ": array '" + a.name + "' has unknown format " + format);
+    }
+    *next = close;
+  }
+  if (a.bytes.size() != n_bytes)
+    return fail(err, path + ": array '" + a.name + "' holds " + std::to_string(a.bytes.size()) + " bytes, the extent needs " +
+                         std::to_string(n_bytes));
+  if (fmt.swap) swap_elements(a.bytes.data(), n_values, a.elem_size);
+  return true;
+}
+
+}  // namespace vtkxml
+}  // namespace host
+}  // namespace dmi
+
+// ---- ImageData -----------------------------------------------------------------------------------------------------------
+
+namespace dmi {
+namespace host {
+namespace vti {
+namespace {
+
+bool fail(std::string *err, const std::string &msg) { return vtkxml::Fail(err, msg); }
+bool attr(const std::string &tag, const std::string &name, std::string *out) { return vtkxml::Attr(tag, name, out); }
+
+}  // namespace
+
 namespace {
 bool read_image_data(const std::string &path, const std::vector<std::string> &wanted, Image *out, std::string *err);
 }
@@ -248,16 +377,8 @@ bool read_image_data(const std::string &path, const std::vector<std::string> &wa
   const std::string vtag = text.substr(vf, text.find('>', vf) - vf);
   std::string s;
   if (!attr(vtag, "type", &s) || s != "ImageData") return fail(err, path + ": VTKFile type is not ImageData");
-  Format fmt;
-  if (attr(vtag, "header_type", &s)) {
-    if (s == "UInt64") fmt.header_word = 8;
-    else if (s != "UInt32") return fail(err, path + ": unsupported header_type " + s);
-  }
-  if (attr(vtag, "byte_order", &s)) fmt.swap = s == "BigEndian";
-  if (attr(vtag, "compressor", &s) && !s.empty()) {
-    if (s != "vtkZLibDataCompressor") return fail(err, path + ": unsupported compressor " + s + " (only vtkZLibDataCompressor)");
-    fmt.zlib = true;
-  }
+  vtkxml::Format fmt;
+  if (!vtkxml::ReadFormat(vtag, path, &fmt, err)) return false;
 
   const std::string::size_type img = text.find("<ImageData", vf);
   if (img == std::string::npos) return fail(err, path + ": no <ImageData> element");
@@ -284,19 +405,9 @@ bool read_image_data(const std::string &path, const std::vector<std::string> &wa
   const size_t n_points = (size_t)out->dims(0) * out->dims(1) * out->dims(2);
 
   // appended data section (raw payloads can contain anything: never search inside it)
-  const std::string::size_type app = text.find("<AppendedData", img);
-  size_t app_data = std::string::npos;
-  bool app_raw = false;
-  if (app != std::string::npos) {
-    const std::string::size_type app_end = text.find('>', app);
-    if (app_end == std::string::npos) return fail(err, path + ": malformed <AppendedData>");
-    const std::string atag = text.substr(app, app_end - app);
-    if (attr(atag, "encoding", &s)) app_raw = s == "raw";
-    const std::string::size_type us = text.find('_', app_end);
-    if (us == std::string::npos) return fail(err, path + ": <AppendedData> without the '_' marker");
-    app_data = us + 1;
-  }
-  const size_t xml_end = app != std::string::npos ? app : text.size();
+  vtkxml::Appended app;
+  size_t xml_end = text.size();
+  if (!vtkxml::FindAppended(text, img, path, &app, &xml_end, err)) return false;
 
   std::string::size_type pd0 = text.find("<PointData", img), pd1 = std::string::npos;
   if (pd0 != std::string::npos && pd0 < xml_end) {
@@ -319,70 +430,11 @@ bool read_image_data(const std::string &path, const std::vector<std::string> &wa
     Array a;
     attr(tag, "Name", &a.name);
     if (!wanted.empty() && std::find(wanted.begin(), wanted.end(), a.name) == wanted.end()) continue;
-    std::string format = "ascii";
-    attr(tag, "format", &format);
-    if (!attr(tag, "type", &a.type) || (a.elem_size = type_size(a.type)) == 0)
+    if (!attr(tag, "type", &a.type) || (a.elem_size = vtkxml::TypeSize(a.type)) == 0)
       return fail(err, path + ": array '" + a.name + "' has an unknown type");
     if (attr(tag, "NumberOfComponents", &s)) a.components = std::atoi(s.c_str());
     if (a.components < 1 || a.components > 1024) return fail(err, path + ": array '" + a.name + "' has an impossible component count");
-    const size_t n_values = n_points * (size_t)a.components;
-    const size_t n_bytes = n_values * a.elem_size;
-
-    if (format == "appended") {
-      if (app_data == std::string::npos) return fail(err, path + ": appended array without <AppendedData>");
-      if (!attr(tag, "offset", &s)) return fail(err, path + ": appended array '" + a.name + "' without offset");
-      const unsigned long long off = std::strtoull(s.c_str(), nullptr, 10);
-      if (off > text.size() - app_data) return fail(err, path + ": offset of '" + a.name + "' is past the end of the file");
-      std::string why;
-      const bool ok = app_raw ? decode_raw(reinterpret_cast<const unsigned char *>(text.data()) + app_data + off,
-                                           text.size() - app_data - (size_t)off, fmt, n_bytes, &a.bytes, &why)
-                              : decode_b64(text, app_data + (size_t)off, text.size(), fmt, n_bytes, &a.bytes, &why);
-      if (!ok) return fail(err, path + ": array '" + a.name + "': " + why);
-    } else {
-      if (self_closed) return fail(err, path + ": inline array '" + a.name + "' has no content");
-      const std::string::size_type close = text.find("</DataArray>", p);
-      if (close == std::string::npos || close > pd1) return fail(err, path + ": unterminated <DataArray>");
-      if (format == "binary") {
-        std::string why;
-        if (!decode_b64(text, p, close, fmt, n_bytes, &a.bytes, &why)) return fail(err, path + ": array '" + a.name + "': " + why);
-      } else if (format == "ascii") {
-        if (n_values > (close - p)) return fail(err, path + ": array '" + a.name + "' has fewer values than points");
-        a.bytes.resize(n_bytes);
-        const char *c = text.data() + p;
-        const char *const cend = text.data() + close;
-        const bool is_float = a.type == "Float32" || a.type == "Float64";
-        const bool is_signed = a.type[0] == 'I';
-        for (size_t i = 0; i < n_values; ++i) {
-          while (c < cend && std::isspace((unsigned char)*c)) ++c;
-          if (c >= cend) return fail(err, path + ": array '" + a.name + "' has fewer values than points");
-          char *next = nullptr;
-          unsigned char *dst = a.bytes.data() + i * a.elem_size;
-          if (is_float) {
-            const double v = std::strtod(c, &next);
-            if (a.elem_size == 8) std::memcpy(dst, &v, 8);
-            else { const float w = (float)v; std::memcpy(dst, &w, 4); }
-          } else if (is_signed) {
-            const long long v = std::strtoll(c, &next, 10);
-            std::memcpy(dst, &v, a.elem_size);  // little-endian host: the low bytes
-          } else {
-            const unsigned long long v = std::strtoull(c, &next, 10);
-            std::memcpy(dst, &v, a.elem_size);
-          }
-          if (next == c) return fail(err, path + ": array '" + a.name + "' holds something that is not a number");
-          c = next;
-        }
-        p = close;
-        out->point_data.push_back(std::move(a));
-        continue;  // text values have no byte order
-      } else {
-        return fail(err, path + ": array '" + a.name + "' has unknown format " + format);
-      }
-      p = close;
-    }
-    if (a.bytes.size() != n_bytes)
-      return fail(err, path + ": array '" + a.name + "' holds " + std::to_string(a.bytes.size()) + " bytes, the extent needs " +
-                           std::to_string(n_bytes));
-    if (fmt.swap) swap_elements(a.bytes.data(), n_values, a.elem_size);
+    if (!vtkxml::DecodeDataArray(text, tag, self_closed, p, pd1, app, fmt, n_points, path, &a, &p, err)) return false;
     out->point_data.push_back(std::move(a));
   }
   return true;

@@ -13,23 +13,20 @@
 // the header is its own base64 unit when compressed and shares the unit with the data when not.
 // All of vtkXMLImageDataWriter's data modes (ascii, binary, appended raw / base64) with and without zlib,
 // either header width and either byte order are read.  LZ4 / LZMA compressors are not (no codec in the image).
+// The container decoding is shared with the PolyData reader (vtk_xml_data.h).
 #pragma once
 
 #include <cstdint>
 #include <string>
 #include <vector>
 
+#include "vtk_xml_data.h"
+
 namespace dmi {
 namespace host {
 namespace vti {
 
-struct Array {
-  std::string name;
-  std::string type;   // "Float64", "UInt8", ... as written in the file
-  int components = 1;
-  size_t elem_size = 0;
-  std::vector<unsigned char> bytes;  // host byte order, tuples * components * elem_size bytes
-};
+using Array = vtkxml::Array;  // name, type, components, bytes in host byte order
 
 struct Image {
   int extent[6] = {0, -1, 0, -1, 0, -1};

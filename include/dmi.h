@@ -353,6 +353,22 @@ int dmi_color_set_scratch_budget(dmi_color_context *ctx, uint64_t bytes);
 int dmi_color_set_vertex_reorder(dmi_color_context *ctx, int32_t enable);
 /* hipEvent time of the kernels (projection + median) of the last dmi_color_process, summed over its chunks */
 int dmi_color_get_kernel_ms(dmi_color_context *ctx, double *out);
+/* Opt-in visibility test (not in the reference, whose colouring has neither a z-sign nor a depth test, so occluders and
+ * views from behind blend into a vertex's colour).  (Added after round 5; dmi_abi_version() stays 5.)  Definition (DESIGN.md
+ * 8b), met bit for bit: for vertex p = (x, y, z) f64 and view m with W x H images,
+ *   - (px, py) is the pixel the plain pass selects, with the same bounds test;
+ *   - cz = ((RT[8]*x + RT[9]*y) + RT[10]*z) + RT[11], every operation rounded, no FMA (TransformPoint's camera z, RD.cxx:173);
+ *   - d = depths_m[(H-1-py)*W + px], the f64 "Depths" value in vtk point order (no best-cost threshold);
+ *   - with the test on and tolerance tol the pair counts iff the bounds test passes, cz > 0, d > 0 and fabs(cz - d) <= tol
+ *     (the difference rounded).  A comparison with a NaN is false: NaN, -1 and infinite depths reject the pair.
+ * Mean, median and count are then those of the pairs that count; a vertex without any is all zeros.
+ * dmi_color_add_views_with_depth appends views exactly as dmi_color_add_views and keeps their depth planes ([n][H][W] f64,
+ * vtk point order) resident; dmi_color_clear_views drops them.  dmi_color_set_depth_test: DMI_ERR_INVALID_ARGUMENT for a
+ * NaN, infinite or negative tolerance; while the test is on, dmi_color_process fails with DMI_ERR_INVALID_ARGUMENT if a
+ * resident view was added without depths.  Default off: every output is then the plain pass's. */
+int dmi_color_add_views_with_depth(dmi_color_context *ctx, const uint8_t *colors, const double *depths, const double *K4,
+                                   const double *RT4, int32_t n, int32_t width, int32_t height);
+int dmi_color_set_depth_test(dmi_color_context *ctx, int32_t enable, double tolerance);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

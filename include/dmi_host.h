@@ -115,6 +115,44 @@ int dmi_write_polydata(const char *path, const double *points, int64_t n_points,
 int dmi_write_polydata_with_normals(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
                                     int64_t n_triangles, const float *normals, double contour);
 
+/* dmi_mesh_coloration_from_lists with the visibility test of dmi_color_set_depth_test (dmi.h) at `depth_tolerance`
+ * (MeshColoration::SetDepthTolerance; needs the views' "Depths" arrays).  1 on success, 0 on error (message in err). */
+int dmi_mesh_coloration_from_lists_with_depth(const double *points, int64_t n_points, const char *vti_list, const char *krtd_list,
+                                              int32_t device, double depth_tolerance, uint8_t *mean, uint8_t *median, int32_t *count,
+                                              char *err, size_t errlen);
+
+/* ---- VTK XML PolyData without VTK (csrc/host/vtp_reader.h): what vtkXMLPolyDataReader gives the Coloration tool ----
+ * One piece; Points Float32 / Float64; Polys with Int32 / Int64 connectivity and offsets; every point- and cell-data array as
+ * stored (host byte order), with its section's designations.  Every data mode of the format (see dmi_read_depth_map).
+ * dmi_read_polydata: NULL on failure, the reason in err (truncated to errlen). */
+typedef struct dmi_polydata dmi_polydata;
+dmi_polydata *dmi_read_polydata(const char *path, char *err, size_t errlen);
+void dmi_polydata_free(dmi_polydata *pd);
+/* out[0] points, out[1] polys, out[2] connectivity length, out[3] point-data arrays, out[4] cell-data arrays.  1 on success. */
+int dmi_polydata_counts(const dmi_polydata *pd, int64_t out[5]);
+/* One array: kind 0 = Points, 1 = Polys connectivity, 2 = Polys offsets, 3 = point-data array `index`, 4 = cell-data array
+ * `index`.  Pointers into pd (valid until dmi_polydata_free); any out pointer may be NULL.  1 on success. */
+int dmi_polydata_array(const dmi_polydata *pd, int32_t kind, int32_t index, const char **name, const char **type, int32_t *components,
+                       int64_t *n_tuples, const void **data);
+/* the attributes of <PointData> (cell == 0) or <CellData> (cell != 0), "key=value" per line: Scalars=..., Normals=... */
+const char *dmi_polydata_designations(const dmi_polydata *pd, int32_t cell);
+
+/* ---- the `Coloration` command line (Coloration/main.cxx; csrc/host/color_cli.h) ----
+ * What ReadArguments (cmain:105-135) makes of a command line.  --device and --depthTolerance are not in the reference. */
+typedef struct dmi_color_cli_options {
+  char input[4096], output[4096], krtd[4096], vti[4096]; /* --input, --output, --krtd, --vti (NUL-terminated, truncated) */
+  int32_t verbose;
+  int32_t device;             /* --device (default 0) */
+  int32_t depth_test;         /* --depthTolerance given: the visibility test of dmi_color_set_depth_test */
+  double depth_tolerance;
+} dmi_color_cli_options;
+/* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
+int dmi_color_cli_read_arguments(int32_t argc, const char *const *argv, dmi_color_cli_options *out, char *err, size_t errlen);
+/* The whole tool: read --input, colour its points from the views of the two list files, write --output with the input's
+ * points, polys and arrays plus MeanColoration, MedianColoration and NbProjectedDepthMap.  Process exit code: 0 on success,
+ * 1 on any error -- including a failed colouring, after which the reference returns 0 and writes nothing (cmain:82-99). */
+int dmi_color_cli_main(int32_t argc, const char *const *argv);
+
 #ifdef __cplusplus
 }
 #endif
