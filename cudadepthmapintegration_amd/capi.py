@@ -18,6 +18,7 @@ from .scene import GridDesc, RayPotential, Views
 DMI_OK = 0
 DMI_F32, DMI_F64 = 0, 1
 DMI_DEPTH_AUTO, DMI_DEPTH_F32, DMI_DEPTH_F64 = 0, 1, 2
+DMI_COMPONENTS_MIN_TRIANGLES, DMI_COMPONENTS_LARGEST = 0, 1
 
 # kernel_variant bits (tuning knobs)
 VARIANT_EXACT_DIVISION = 1  # disable the checked-reciprocal fast path
@@ -106,6 +107,8 @@ ABI_SYMBOLS = [
     "dmi_iso_active_cells",
     "dmi_extract_isosurface", "dmi_download_isosurface", "dmi_get_isosurface_kernel_ms",
     "dmi_extract_isosurface_normals", "dmi_download_isosurface_normals",
+    "dmi_filter_isosurface_components", "dmi_download_isosurface_regions", "dmi_get_isosurface_filter_kernel_ms",
+    "dmi_get_isosurface_filter_pass_ms", "dmi_get_isosurface_filter_cas_retries",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -181,6 +184,13 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "dmi_extract_isosurface_normals"):
         L.dmi_extract_isosurface_normals.argtypes = [vp, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.dmi_download_isosurface_normals.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    if hasattr(L, "dmi_filter_isosurface_components"):
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.dmi_filter_isosurface_components.argtypes = [vp, ctypes.c_int, ctypes.c_uint64, u64p, u64p, u64p, u64p]
+        L.dmi_download_isosurface_regions.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+        L.dmi_get_isosurface_filter_kernel_ms.argtypes = [vp, dp]
+        L.dmi_get_isosurface_filter_pass_ms.argtypes = [vp, dp]
+        L.dmi_get_isosurface_filter_cas_retries.argtypes = [vp, u64p]
     L.dmi_get_brick_class_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dmi_get_mixed_reason_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_get_window_pair_count"):  # (absent from an older prebuilt library loaded for an A/B timing, tools/gpu_exp.py)
@@ -317,6 +327,7 @@ class FusionContext:
         self.grid = grid
         self.grid_dtype = grid_dtype
         self.n_voxels = grid.n_voxels
+        self._mesh_counts = None  # (vertices, triangles, kept components) of the context's mesh; None: no mesh (the C side's mesh_valid)
         rc = self._lib.dmi_create(ctypes.byref(g), ctypes.byref(r), ctypes.byref(o), ctypes.byref(self._h))
         if rc != DMI_OK:
             self._h = ctypes.c_void_p()
@@ -461,9 +472,11 @@ class FusionContext:
         """(vertices [n, 3] f64 world coordinates, triangles [m, 3] int64): marching cubes over the point data at `iso` on the
         device (dmi_extract_isosurface + dmi_download_isosurface; Reconstruction/main.cxx:166-182)."""
         nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._mesh_counts = None    # a failed extraction leaves no mesh
         self._check(self._lib.dmi_extract_isosurface(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
         verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
         tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
+        self._mesh_counts = (int(nv.value), int(nt.value), 0)
         self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return verts[:int(nv.value)], tris[:int(nt.value)]
 
@@ -472,13 +485,76 @@ class FusionContext:
         unit normal per vertex from the point data's gradient, in world coordinates (dmi_extract_isosurface_normals +
         dmi_download_isosurface + dmi_download_isosurface_normals)."""
         nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._mesh_counts = None    # a failed extraction leaves no mesh
         self._check(self._lib.dmi_extract_isosurface_normals(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
         verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
         tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
         normals = np.empty((max(int(nv.value), 1), 3), dtype=np.float32)
+        self._mesh_counts = (int(nv.value), int(nt.value), 0)
         self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         self._check(self._lib.dmi_download_isosurface_normals(self._h, normals.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
         return verts[:int(nv.value)], tris[:int(nt.value)], normals[:int(nv.value)]
+
+    def filter_isosurface_components(self, mode: str = "min_triangles", min_triangles: int = 0):
+        """(vertices, triangles, components found, components kept): label the connected components of the context's mesh -- the
+        last extraction's, or the last filter's since -- and keep those of at least `min_triangles` triangles
+        (mode="min_triangles") or the largest one (mode="largest"); the mesh is compacted on the device
+        (dmi_filter_isosurface_components).  download_isosurface* return the filtered mesh afterwards."""
+        m = {"min_triangles": DMI_COMPONENTS_MIN_TRIANGLES, "largest": DMI_COMPONENTS_LARGEST}[mode]
+        out = [ctypes.c_uint64(0) for _ in range(4)]
+        self._check(self._lib.dmi_filter_isosurface_components(self._h, m, int(min_triangles), *[ctypes.byref(x) for x in out]))
+        self._mesh_counts = (int(out[0].value), int(out[1].value), int(out[3].value))
+        return tuple(int(x.value) for x in out)
+
+    def _current_mesh_counts(self):
+        c = self._mesh_counts      # a refused filter changes neither the C side's mesh nor these
+        if c is None:
+            raise DmiError(1, "no mesh: extract_isosurface has not succeeded")
+        return c
+
+    def download_isosurface(self):
+        """(vertices [n, 3] f64, triangles [m, 3] int64) of the context's current mesh: the last extraction's, or the last
+        filter_isosurface_components' since (dmi_download_isosurface)."""
+        nv, nt, _ = self._current_mesh_counts()
+        verts = np.empty((max(nv, 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
+        tris = np.empty((max(nt, 1), 3), dtype=np.int64)
+        self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return verts[:nv], tris[:nt]
+
+    def download_isosurface_normals(self):
+        """normals [n, 3] f32 of the context's current mesh after filter_isosurface_components (the extraction had them)."""
+        nv, _, _ = self._current_mesh_counts()
+        normals = np.empty((max(nv, 1), 3), dtype=np.float32)
+        self._check(self._lib.dmi_download_isosurface_normals(self._h, normals.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return normals[:nv]
+
+    def download_isosurface_regions(self):
+        """(RegionId [n] int64: each vertex's component, RegionSize [k] int64: each kept component's triangles) of the last
+        filter_isosurface_components; components are numbered by ascending smallest vertex id (dmi_download_isosurface_regions)."""
+        nv, _, nk = self._current_mesh_counts()
+        rid = np.empty(max(nv, 1), dtype=np.int64)
+        rsz = np.empty(max(nk, 1), dtype=np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        self._check(self._lib.dmi_download_isosurface_regions(self._h, rid.ctypes.data_as(i64p), rsz.ctypes.data_as(i64p)))
+        return rid[:nv], rsz[:nk]
+
+    def isosurface_filter_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last filter_isosurface_components (dmi_get_isosurface_filter_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_isosurface_filter_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
+
+    def isosurface_filter_cas_retries(self) -> int:
+        """Compare-and-swaps of the last filter's hooking pass that lost a race (dmi_get_isosurface_filter_cas_retries)."""
+        a = ctypes.c_uint64(0)
+        self._check(self._lib.dmi_get_isosurface_filter_cas_retries(self._h, ctypes.byref(a)))
+        return int(a.value)
+
+    def isosurface_filter_pass_ms(self) -> dict:
+        """The same pass by pass (dmi_get_isosurface_filter_pass_ms)."""
+        a = (ctypes.c_double * 4)()
+        self._check(self._lib.dmi_get_isosurface_filter_pass_ms(self._h, a))
+        return dict(zip(("labels", "sizes", "scans", "compaction"), (float(x) for x in a)))
 
     def isosurface_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last extract_isosurface or extract_isosurface_with_normals
@@ -881,6 +957,7 @@ HOST_ABI_SYMBOLS = [
     "dmi_filter_last_error", "dmi_read_krtd_file", "dmi_extract_all_file_path", "dmi_k3_to_k4",
     "dmi_apply_depth_threshold", "dmi_read_depth_map", "dmi_read_depth_map_color", "dmi_mesh_coloration_from_lists",
     "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata", "dmi_write_polydata_with_normals",
+    "dmi_write_polydata_with_arrays",
     "dmi_mesh_coloration_from_lists_with_depth", "dmi_read_polydata", "dmi_polydata_free", "dmi_polydata_counts",
     "dmi_polydata_array", "dmi_polydata_designations", "dmi_color_cli_read_arguments", "dmi_color_cli_main",
 ]
@@ -954,6 +1031,9 @@ def load_host() -> ctypes.CDLL:
     L.dmi_write_polydata_with_normals.restype = ctypes.c_int
     L.dmi_write_polydata_with_normals.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64,
                                                   ctypes.POINTER(ctypes.c_float), ctypes.c_double]
+    L.dmi_write_polydata_with_arrays.restype = ctypes.c_int
+    L.dmi_write_polydata_with_arrays.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64,
+                                                 ctypes.POINTER(ctypes.c_float), ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
     _host_bound = True
     return L
 
@@ -1056,7 +1136,8 @@ class CliOptionsC(ctypes.Structure):
                 ("ray_rho", ctypes.c_double), ("ray_eta", ctypes.c_double), ("ray_delta", ctypes.c_double),
                 ("thresh_best_cost", ctypes.c_double), ("contour", ctypes.c_double), ("verbose", ctypes.c_int32),
                 ("summary", ctypes.c_int32), ("force_cubic_voxel", ctypes.c_int32), ("extract_mesh", ctypes.c_int32),
-                ("mesh_normals", ctypes.c_int32)]
+                ("mesh_normals", ctypes.c_int32), ("mesh_largest_component", ctypes.c_int32), ("mesh_region_ids", ctypes.c_int32),
+                ("mesh_min_component_triangles", ctypes.c_int64)]
 
 
 def cli_read_arguments(args):
@@ -1096,6 +1177,30 @@ def write_polydata_with_normals(path, points, triangles, normals, contour):
                                            t.shape[0], n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), float(contour))
     if not ok:
         raise OSError(f"dmi_write_polydata_with_normals failed: {path}")
+
+
+def write_polydata_with_arrays(path, points, triangles, normals=None, contour=0.0, region_ids=None):
+    """dmi_write_polydata_with_arrays: write_polydata's file (normals None) or write_polydata_with_normals' plus the point array
+    RegionId ([n] int64) when region_ids is given; no GPU needed."""
+    L = load_host()
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    n = r = None
+    if normals is not None:
+        n = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if n.shape != p.shape:
+            raise ValueError(f"normals {n.shape} do not match points {p.shape}")
+        n = np.concatenate([n.reshape(-1), np.zeros(1, np.float32)])     # never a null pointer, even for an empty mesh
+    if region_ids is not None:
+        r = np.ascontiguousarray(region_ids, dtype=np.int64).reshape(-1)
+        if r.shape[0] != p.shape[0]:
+            raise ValueError(f"region ids {r.shape} do not match points {p.shape}")
+        r = np.concatenate([r, np.zeros(1, np.int64)])
+    ok = L.dmi_write_polydata_with_arrays(os.fsencode(path), _dp(p), p.shape[0], t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                          t.shape[0], None if n is None else n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                          float(contour), None if r is None else r.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+    if not ok:
+        raise OSError(f"dmi_write_polydata_with_arrays failed: {path}")
 
 
 def cli_binary() -> str:

@@ -147,6 +147,26 @@ struct dmi_context {
   bool mesh_has_normals = false;        // the last successful extraction wrote them
   hipEvent_t mesh_events[4] = {nullptr, nullptr, nullptr, nullptr};  // around the count pass + scans, and the write pass
   double last_isosurface_kernel_ms = 0.0;
+  // dmi_filter_isosurface_components (isosurface_components.hip): the second set of mesh buffers the compaction writes (swapped
+  // with the first afterwards), the region arrays and the union-find's scratch, all kept while large enough
+  double *d_mesh_alt_vertices = nullptr;
+  int64_t *d_mesh_alt_triangles = nullptr;
+  float *d_mesh_alt_normals = nullptr;
+  uint64_t mesh_alt_vertex_capacity = 0, mesh_alt_triangle_capacity = 0, mesh_alt_normal_capacity = 0;
+  int64_t *d_mesh_region_id = nullptr, *d_mesh_region_size = nullptr;
+  uint64_t mesh_region_capacity = 0;       // vertices
+  uint32_t *d_comp_vertex_scratch = nullptr;  // parent, size, vmap, rmap: 4 arrays of (capacity + 1)
+  uint32_t *d_comp_triangle_scratch = nullptr;
+  uint64_t comp_vertex_capacity = 0, comp_triangle_capacity = 0;
+  unsigned long long *d_comp_counters = nullptr;
+  void *d_comp_scan_temp = nullptr;
+  uint64_t comp_scan_temp_capacity = 0;
+  hipEvent_t comp_events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool mesh_filtered = false;              // a filter has run since the last extraction: the region arrays are the mesh's
+  uint64_t mesh_regions = 0;               // kept components of that filter
+  double last_filter_kernel_ms = 0.0;
+  uint64_t last_filter_cas_retries = 0;     // compare-and-swaps of the last filter's hooking pass that lost a race
+  double last_filter_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // labels (init, hook, flatten), sizes (and largest), scans, compaction
 
   void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
   double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
@@ -1049,6 +1069,12 @@ void dmi_destroy(dmi_context *ctx) {
   if (ctx->d_mesh_normals) (void)hipFree(ctx->d_mesh_normals);
   for (hipEvent_t e : ctx->mesh_events)
     if (e) (void)hipEventDestroy(e);
+  for (void *p : {(void *)ctx->d_mesh_alt_vertices, (void *)ctx->d_mesh_alt_triangles, (void *)ctx->d_mesh_alt_normals,
+                  (void *)ctx->d_mesh_region_id, (void *)ctx->d_mesh_region_size, (void *)ctx->d_comp_vertex_scratch,
+                  (void *)ctx->d_comp_triangle_scratch, (void *)ctx->d_comp_counters, ctx->d_comp_scan_temp})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t e : ctx->comp_events)
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->slab_events) (void)hipEventDestroy(e);
   if (ctx->download_stream) (void)hipStreamDestroy(ctx->download_stream);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1938,6 +1964,7 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
   *n_vertices = *n_triangles = 0;
   ctx->mesh_valid = false;
   ctx->mesh_has_normals = false;
+  ctx->mesh_filtered = false;
   const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
   const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
   if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": grid too large for one launch");
@@ -2075,6 +2102,174 @@ int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last) {
   return guarded(ctx, "dmi_get_isosurface_kernel_ms", [&]() -> int {
   if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_kernel_ms: null argument");
   *last = ctx->last_isosurface_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
+                                     uint64_t *n_components, uint64_t *n_components_kept) {
+  return guarded(ctx, "dmi_filter_isosurface_components", [&]() -> int {
+  const std::string entry = "dmi_filter_isosurface_components";
+  if (!ctx || !n_vertices || !n_triangles || !n_components || !n_components_kept)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (mode != DMI_COMPONENTS_MIN_TRIANGLES && mode != DMI_COMPONENTS_LARGEST)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": unknown mode " + std::to_string(mode));
+  if (!ctx->mesh_valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  *n_vertices = *n_triangles = *n_components = *n_components_kept = 0;
+  const uint64_t nv = ctx->mesh_vertices, nt = ctx->mesh_triangles;
+  // labels and sizes are u32: refused, never wrapped (as the extraction refuses what its int64 ids cannot hold)
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit component labels");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (nv == 0) {  // an empty mesh stays empty
+    ctx->mesh_filtered = true;
+    ctx->mesh_regions = 0;
+    ctx->last_filter_kernel_ms = 0.0;
+    for (double &p : ctx->last_filter_pass_ms) p = 0.0;
+    ctx->last_filter_cas_retries = 0;
+    return DMI_OK;
+  }
+  const bool normals = ctx->mesh_has_normals;
+  int rc;
+  {
+    uint64_t cap = ctx->mesh_alt_vertex_capacity * 24;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_vertices, &cap, nv * 24);
+    if (rc != DMI_OK) return rc;
+    ctx->mesh_alt_vertex_capacity = cap / 24;
+    cap = ctx->mesh_alt_triangle_capacity * 24;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_triangles, &cap, std::max<uint64_t>(nt, 1) * 24);
+    if (rc != DMI_OK) return rc;
+    ctx->mesh_alt_triangle_capacity = cap / 24;
+    if (normals) {
+      cap = ctx->mesh_alt_normal_capacity * 12;
+      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_normals, &cap, nv * 12);
+      if (rc != DMI_OK) return rc;
+      ctx->mesh_alt_normal_capacity = cap / 12;
+    }
+    if (ctx->mesh_region_capacity < nv) {
+      uint64_t a = ctx->mesh_region_capacity * 8, b = a;
+      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_region_id, &a, nv * 8);
+      if (rc != DMI_OK) return rc;
+      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_region_size, &b, nv * 8);
+      if (rc != DMI_OK) return rc;
+      ctx->mesh_region_capacity = nv;
+    }
+    cap = ctx->comp_vertex_capacity ? (ctx->comp_vertex_capacity + 1) * 16 : 0;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_comp_vertex_scratch, &cap, (nv + 1) * 16);
+    if (rc != DMI_OK) return rc;
+    ctx->comp_vertex_capacity = cap / 16 - 1;
+    cap = ctx->comp_triangle_capacity ? (ctx->comp_triangle_capacity + 1) * 4 : 0;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_comp_triangle_scratch, &cap, (nt + 1) * 4);
+    if (rc != DMI_OK) return rc;
+    ctx->comp_triangle_capacity = cap / 4 - 1;
+    cap = ctx->d_comp_counters ? 24 : 0;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_comp_counters, &cap, 24);
+    if (rc != DMI_OK) return rc;
+  }
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::components_scan_temp_bytes(nv, nt, &temp_bytes));
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  rc = ensure_buffer(ctx, (void **)&ctx->d_comp_scan_temp, &ctx->comp_scan_temp_capacity, temp_bytes);
+  if (rc != DMI_OK) return rc;
+  if (!ctx->comp_events[0])
+    for (hipEvent_t &e : ctx->comp_events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::ComponentsMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = ctx->d_mesh_vertices;
+  m.normals = normals ? ctx->d_mesh_normals : nullptr;
+  m.triangles = ctx->d_mesh_triangles;
+  m.out_vertices = ctx->d_mesh_alt_vertices;
+  m.out_normals = ctx->d_mesh_alt_normals;
+  m.out_triangles = ctx->d_mesh_alt_triangles;
+  m.region_id = ctx->d_mesh_region_id;
+  m.region_size = ctx->d_mesh_region_size;
+  dmi::ComponentsScratch s{};
+  uint32_t *vs = ctx->d_comp_vertex_scratch;
+  s.parent = vs;
+  s.size = vs + (nv + 1);
+  s.vmap = vs + 2 * (nv + 1);
+  s.rmap = vs + 3 * (nv + 1);
+  s.tmap = ctx->d_comp_triangle_scratch;
+  s.counters = ctx->d_comp_counters;
+  s.scan_temp = ctx->d_comp_scan_temp;
+  s.scan_temp_bytes = temp_bytes;
+  // (a failure from here on leaves the context's mesh and its regions as they were: the buffers are swapped only at the end)
+  DMI_HIP(ctx, dmi::launch_isosurface_components(m, s, mode == DMI_COMPONENTS_LARGEST ? 1 : 0, min_triangles, ctx->comp_events, ctx->stream));
+  uint32_t kept[3] = {0, 0, 0};
+  unsigned long long counters[3] = {0, 0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[0], s.vmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[1], s.tmap + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[2], s.rmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(counters, s.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->comp_events[0], ctx->comp_events[4]));
+  ctx->last_filter_kernel_ms = (double)ms;
+  for (int p = 0; p < 4; ++p) {
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->comp_events[p], ctx->comp_events[p + 1]));
+    ctx->last_filter_pass_ms[p] = (double)ms;
+  }
+  // the compacted mesh becomes the context's mesh; the buffers it came from are the next filter's output
+  std::swap(ctx->d_mesh_vertices, ctx->d_mesh_alt_vertices);
+  std::swap(ctx->mesh_vertex_capacity, ctx->mesh_alt_vertex_capacity);
+  std::swap(ctx->d_mesh_triangles, ctx->d_mesh_alt_triangles);
+  std::swap(ctx->mesh_triangle_capacity, ctx->mesh_alt_triangle_capacity);
+  if (normals) {
+    std::swap(ctx->d_mesh_normals, ctx->d_mesh_alt_normals);
+    std::swap(ctx->mesh_normal_capacity, ctx->mesh_alt_normal_capacity);
+  }
+  ctx->mesh_vertices = kept[0];
+  ctx->mesh_triangles = kept[1];
+  ctx->mesh_regions = kept[2];
+  ctx->mesh_filtered = true;
+  ctx->last_filter_cas_retries = counters[2];
+  *n_vertices = kept[0];
+  *n_triangles = kept[1];
+  *n_components = counters[1];
+  *n_components_kept = kept[2];
+  return DMI_OK;
+  });
+}
+
+int dmi_download_isosurface_regions(dmi_context *ctx, int64_t *region_id, int64_t *region_size) {
+  return guarded(ctx, "dmi_download_isosurface_regions", [&]() -> int {
+  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: null argument");
+  if (!ctx->mesh_valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: no mesh (no extraction has succeeded)");
+  if (!ctx->mesh_filtered)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_download_isosurface_regions: no regions (dmi_filter_isosurface_components has not run since the last extraction)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (region_id && ctx->mesh_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(region_id, ctx->d_mesh_region_id, (size_t)ctx->mesh_vertices * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (region_size && ctx->mesh_regions)
+    DMI_HIP(ctx, hipMemcpyAsync(region_size, ctx->d_mesh_region_size, (size_t)ctx->mesh_regions * 8, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_filter_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_filter_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_kernel_ms: null argument");
+  *last = ctx->last_filter_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_filter_pass_ms(dmi_context *ctx, double out[4]) {
+  return guarded(ctx, "dmi_get_isosurface_filter_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_pass_ms: null argument");
+  for (int p = 0; p < 4; ++p) out[p] = ctx->last_filter_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last) {
+  return guarded(ctx, "dmi_get_isosurface_filter_cas_retries", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_cas_retries: null argument");
+  *last = ctx->last_filter_cas_retries;
   return DMI_OK;
   });
 }

@@ -444,4 +444,28 @@ hipError_t launch_isosurface_count(const double *points, const MeshGeom &g, uint
 hipError_t launch_isosurface_write(const double *points, const MeshGeom &g, const uint64_t *bases, double *verts, int64_t *tris,
                                    const MeshNormals *normals, hipStream_t stream);
 
+// Connected components of that mesh (isosurface_components.hip): the mesh to filter and the buffers of the result.
+struct ComponentsMesh {
+  uint64_t n_vertices, n_triangles;  // both below 2^32 (u32 labels and sizes), n_vertices >= 1
+  const double *vertices;            // [n_vertices][3]
+  const float *normals;              // [n_vertices][3], or null: the mesh has none
+  const int64_t *triangles;          // [n_triangles][3]
+  double *out_vertices;              // room for the whole mesh each: how much stays is known only afterwards
+  float *out_normals;
+  int64_t *out_triangles;
+  int64_t *region_id;                // [n_vertices]
+  int64_t *region_size;              // [n_vertices]: one per kept component
+};
+struct ComponentsScratch {
+  uint32_t *parent, *size;           // [n_vertices]: after the call, every vertex's label and every label's triangle count
+  uint32_t *vmap, *rmap;             // [n_vertices + 1]: kept vertices / kept components before; the totals at [n_vertices]
+  uint32_t *tmap;                    // [n_triangles + 1]
+  unsigned long long *counters;      // [3]: the largest component's key (size << 32 | ~label), the components found, retried swaps
+  void *scan_temp;
+  size_t scan_temp_bytes;
+};
+hipError_t components_scan_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
+hipError_t launch_isosurface_components(const ComponentsMesh &m, const ComponentsScratch &s, int largest, uint64_t min_triangles,
+                                        hipEvent_t *events, hipStream_t stream);
+
 }  // namespace dmi

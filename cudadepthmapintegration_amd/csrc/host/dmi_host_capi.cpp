@@ -341,6 +341,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->verbose = o.verbose; out->summary = o.summary; out->force_cubic_voxel = o.forceCubicVoxel;
   out->extract_mesh = o.extractMesh;
   out->mesh_normals = o.meshNormals;
+  out->mesh_largest_component = o.meshLargestComponent;
+  out->mesh_region_ids = o.meshRegionIds;
+  out->mesh_min_component_triangles = o.meshMinComponentTriangles;
   return 1;
   });
 }
@@ -360,6 +363,15 @@ int dmi_write_polydata_with_normals(const char *path, const double *points, int6
   std::string error;
   const float none = 0.f;  // an empty mesh still carries the (empty) point arrays
   return dmi::host::cli::WritePolyData(path, points, n_points, triangles, n_triangles, &error, normals ? normals : &none, contour) ? 1 : 0;
+  });
+}
+
+int dmi_write_polydata_with_arrays(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
+                                   int64_t n_triangles, const float *normals, double contour, const int64_t *region_id) {
+  return guarded<int>(0, [&]() -> int {
+  if (!path || n_points < 0 || n_triangles < 0 || (n_points > 0 && !points) || (n_triangles > 0 && !triangles)) return 0;
+  std::string error;
+  return dmi::host::cli::WritePolyData(path, points, n_points, triangles, n_triangles, &error, normals, contour, region_id) ? 1 : 0;
   });
 }
 

@@ -62,6 +62,20 @@ std::function<bool(const std::vector<std::string> &)> into_string(std::string *d
   };
 }
 
+// a non-negative integer: digits only ("-3", "+3", "3.5" and "" are errors)
+std::function<bool(const std::vector<std::string> &)> into_count(long long *dst) {
+  return [dst](const std::vector<std::string> &values) {
+    if (values.size() != 1 || values[0].empty() || values[0].size() > 18) return false;
+    long long n = 0;
+    for (const char c : values[0]) {
+      if (c < '0' || c > '9') return false;
+      n = 10 * n + (c - '0');
+    }
+    *dst = n;
+    return true;
+  };
+}
+
 std::function<bool(const std::vector<std::string> &)> into_flag(bool *dst) {
   return [dst](const std::vector<std::string> &) {
     *dst = true;
@@ -102,6 +116,16 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                       "reconstruction_scalar (the contour value) as point data, as VTK's contour filter does (not in the "
                                       "reference)",
                          into_flag(&o->meshNormals)}},
+      {"--meshMinComponentTriangles", {Kind::kValue, "with --extractMesh: drop every connected component of the mesh that has fewer "
+                                                     "than this many triangles, on the GPU (a non-negative integer; 0 drops "
+                                                     "nothing; not in the reference)",
+                                       into_count(&o->meshMinComponentTriangles)}},
+      {"--meshLargestComponent", {Kind::kFlag, "with --extractMesh: keep only the connected component with the most triangles, on the GPU "
+                                               "(after --meshMinComponentTriangles when both are given; not in the reference)",
+                                  into_flag(&o->meshLargestComponent)}},
+      {"--meshRegionIds", {Kind::kFlag, "with --extractMesh: write the point array RegionId, the number of each vertex's connected component "
+                                        "(components numbered by their smallest vertex id; not in the reference)",
+                           into_flag(&o->meshRegionIds)}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -162,6 +186,18 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   }
   if (o->meshNormals && !o->extractMesh) {
     err << "Error : --meshNormals needs --extractMesh (the normals belong to the extracted mesh).\n" << HelpText();
+    return false;
+  }
+  if (o->meshMinComponentTriangles >= 0 && !o->extractMesh) {
+    err << "Error : --meshMinComponentTriangles needs --extractMesh (the components belong to the extracted mesh).\n" << HelpText();
+    return false;
+  }
+  if (o->meshLargestComponent && !o->extractMesh) {
+    err << "Error : --meshLargestComponent needs --extractMesh (the components belong to the extracted mesh).\n" << HelpText();
+    return false;
+  }
+  if (o->meshRegionIds && !o->extractMesh) {
+    err << "Error : --meshRegionIds needs --extractMesh (the region ids belong to the extracted mesh).\n" << HelpText();
     return false;
   }
   // rmain:257-262
@@ -339,7 +375,7 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 }
 
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
-                   std::string *error, const float *normals, double contour) {
+                   std::string *error, const float *normals, double contour, const int64_t *regionIds) {
   if (nPoints < 0 || nTriangles < 0) {
     *error = "WritePolyData: negative count";
     return false;
@@ -353,6 +389,8 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
                  offset_bytes = (uint64_t)nTriangles * sizeof(int64_t);
   const uint64_t normal_bytes = (uint64_t)nPoints * 3 * sizeof(float), scalar_bytes = (uint64_t)nPoints * sizeof(double);
   const uint64_t normal_offset = 3 * sizeof(uint64_t) + point_bytes + conn_bytes + offset_bytes;  // behind the offsets
+  const uint64_t region_bytes = (uint64_t)nPoints * sizeof(int64_t);
+  const uint64_t region_offset = normal_offset + (normals ? 2 * sizeof(uint64_t) + normal_bytes + scalar_bytes : 0);
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
       << nPoints << "\" NumberOfVerts=\"0\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"" << nTriangles << "\">\n";
@@ -360,7 +398,12 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
     out << "      <PointData Normals=\"Normals\" Scalars=\"reconstruction_scalar\">\n        <DataArray type=\"Float32\" "
            "Name=\"Normals\" NumberOfComponents=\"3\" format=\"appended\" offset=\""
         << normal_offset << "\"/>\n        <DataArray type=\"Float64\" Name=\"reconstruction_scalar\" format=\"appended\" offset=\""
-        << normal_offset + sizeof(uint64_t) + normal_bytes << "\"/>\n      </PointData>\n";
+        << normal_offset + sizeof(uint64_t) + normal_bytes << "\"/>\n";
+  else if (regionIds)
+    out << "      <PointData Scalars=\"RegionId\">\n";
+  if (regionIds)  // vtkPolyDataConnectivityFilter's (ColorRegionsOn)
+    out << "        <DataArray type=\"Int64\" Name=\"RegionId\" format=\"appended\" offset=\"" << region_offset << "\"/>\n";
+  if (normals || regionIds) out << "      </PointData>\n";
   out << "      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" format=\"appended\" "
          "offset=\"0\"/>\n      </Points>\n      <Polys>\n        <DataArray type=\"Int64\" Name=\"connectivity\" format=\"appended\" offset=\""
       << sizeof(uint64_t) + point_bytes << "\"/>\n        <DataArray type=\"Int64\" Name=\"offsets\" format=\"appended\" offset=\""
@@ -388,6 +431,10 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
       out.write(reinterpret_cast<const char *>(scalars.data()), (std::streamsize)(n * sizeof(double)));
       done += n;
     }
+  }
+  if (regionIds) {
+    out.write(reinterpret_cast<const char *>(&region_bytes), sizeof(region_bytes));
+    out.write(reinterpret_cast<const char *>(regionIds), (std::streamsize)region_bytes);
   }
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
@@ -463,9 +510,12 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   std::vector<double> meshVertices;    // --extractMesh
   std::vector<int64_t> meshTriangles;
   std::vector<float> meshNormals;      // --meshNormals
+  std::vector<int64_t> meshRegionIds;  // --meshRegionIds
+  const bool filterMesh = o.meshMinComponentTriangles >= 0 || o.meshLargestComponent || o.meshRegionIds;
   double dummyVertex = 0.0;            // a valid pointer for an empty mesh
   int64_t dummyTriangle = 0;
   float dummyNormal = 0.f;
+  int64_t dummyRegion = 0;
   {
     // vtkCellDataToPointData (rmain:151-155) on the GPU: the cell grid goes up once more, the point grid comes back
     dmi_grid_desc grid;
@@ -495,6 +545,22 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       // vtkContourFilter + vtkTransformFilter (rmain:166-182) on the device; vtkXMLPolyDataWriter (rmain:184-187) below
       uint64_t nv = 0, nt = 0;
       rc = o.meshNormals ? dmi_extract_isosurface_normals(ctx, o.contour, &nv, &nt) : dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      result->meshVerticesExtracted = nv;
+      result->meshTrianglesExtracted = nt;
+      if (rc == DMI_OK && filterMesh) {
+        // vtkPolyDataConnectivityFilter's part, on the device before anything is downloaded: by size, then the largest; with
+        // --meshRegionIds alone everything is kept and only labelled
+        uint64_t found = 0, kept = 0, found2 = 0;
+        if (o.meshMinComponentTriangles >= 0 || !o.meshLargestComponent)
+          rc = dmi_filter_isosurface_components(ctx, DMI_COMPONENTS_MIN_TRIANGLES, (uint64_t)std::max(o.meshMinComponentTriangles, 0LL),
+                                                &nv, &nt, &found, &kept);
+        if (rc == DMI_OK && o.meshLargestComponent) {
+          const bool first = o.meshMinComponentTriangles < 0;
+          rc = dmi_filter_isosurface_components(ctx, DMI_COMPONENTS_LARGEST, 0, &nv, &nt, first ? &found : &found2, &kept);
+        }
+        result->meshComponents = found;
+        result->meshComponentsKept = kept;
+      }
       if (rc == DMI_OK) {
         meshVertices.resize((size_t)nv * 3);
         meshTriangles.resize((size_t)nt * 3);
@@ -504,6 +570,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       if (rc == DMI_OK && o.meshNormals) {
         meshNormals.resize((size_t)nv * 3);
         rc = dmi_download_isosurface_normals(ctx, meshNormals.data() ? meshNormals.data() : &dummyNormal);
+      }
+      if (rc == DMI_OK && o.meshRegionIds) {
+        meshRegionIds.resize((size_t)nv);
+        rc = dmi_download_isosurface_regions(ctx, meshRegionIds.data() ? meshRegionIds.data() : &dummyRegion, nullptr);
       }
       if (rc != DMI_OK) result->error = std::string("iso-surface: ") + dmi_last_error(ctx);
       result->meshVertices = nv;
@@ -520,7 +590,8 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   if (o.extractMesh) {
     say("** Save mesh...");
     if (!WritePolyData(o.outputMeshFilename, meshVertices.data(), (int64_t)result->meshVertices, meshTriangles.data(),
-                       (int64_t)result->meshTriangles, &error, o.meshNormals ? (meshNormals.empty() ? &dummyNormal : meshNormals.data()) : nullptr, o.contour)) {
+                       (int64_t)result->meshTriangles, &error, o.meshNormals ? (meshNormals.empty() ? &dummyNormal : meshNormals.data()) : nullptr, o.contour,
+                       o.meshRegionIds ? (meshRegionIds.empty() ? &dummyRegion : meshRegionIds.data()) : nullptr)) {
       result->error = error;
       return 1;
     }
@@ -528,6 +599,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     log << "mesh: " << o.outputMeshFilename << ": " << result->meshVertices << " vertices, " << result->meshTriangles
         << " triangles at the contour value " << o.contour << " (" << result->contourActiveCells << " of "
         << (long long)(dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1) << " cells straddle it)" << std::endl;
+    if (filterMesh)
+      log << "mesh components: " << result->meshComponents << " found, " << result->meshComponentsKept << " kept; "
+          << result->meshVerticesExtracted << " vertices, " << result->meshTrianglesExtracted << " triangles before, "
+          << result->meshVertices << " vertices, " << result->meshTriangles << " triangles after" << std::endl;
   } else {
     // Said whatever --verbose is: the reference writes a mesh here (rmain:166-187) and this tool does not.
     log << "warning: " << o.outputMeshFilename << " is NOT written: the iso-surface (vtkContourFilter) is not part of this tool; "
@@ -551,7 +626,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
           << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";
-    else
+    if (filterMesh)  // (only with --extractMesh)
+      out << "  mesh components found  " << result->meshComponents << "\n  mesh components kept  " << result->meshComponentsKept
+          << "\n  mesh vertices before the component filter  " << result->meshVerticesExtracted
+          << "\n  mesh triangles before the component filter  " << result->meshTrianglesExtracted << "\n";
+    if (!o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << " (no surface extracted)\n";
     out << "time\n  reconstruction  " << result->reconstructionSeconds << " s\n  total           " << result->totalSeconds << " s\n";
   }

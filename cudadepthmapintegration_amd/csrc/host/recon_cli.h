@@ -6,7 +6,10 @@
 // The iso-surface (vtkContourFilter + vtkTransformFilter, rmain:166-187) only with --extractMesh, which the reference does
 // not have: dmi_extract_isosurface at --contour on the device, written to --outputMeshFilename as a .vtp of points and
 // triangles; with --meshNormals as well (not in the reference either) dmi_extract_isosurface_normals, and the .vtp carries
-// the point arrays Normals and reconstruction_scalar that vtkContourFilter attaches.  Without --extractMesh
+// the point arrays Normals and reconstruction_scalar that vtkContourFilter attaches.  --meshMinComponentTriangles N and
+// --meshLargestComponent (not in the reference: what a vtkPolyDataConnectivityFilter behind the contour would do) drop connected
+// components of that mesh on the device before it is downloaded (dmi_filter_isosurface_components: by size, then the largest),
+// and --meshRegionIds writes the point array RegionId (Int64: the kept components numbered by ascending label).  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
@@ -36,6 +39,10 @@ struct Options {
   bool verbose = false, summary = false, forceCubicVoxel = false;
   bool extractMesh = false;           // not in the reference: write the iso-surface at --contour to --outputMeshFilename
   bool meshNormals = false;           // not in the reference: ... with its Normals and scalar arrays (needs --extractMesh)
+  // not in the reference (all need --extractMesh): drop the mesh's connected components of fewer than N triangles (-1: flag not
+  // given), keep only the largest one (after the former), write the point array RegionId
+  long long meshMinComponentTriangles = -1;
+  bool meshLargestComponent = false, meshRegionIds = false;
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -54,6 +61,9 @@ struct RunResult {
   unsigned long long contourActiveCells = 0;
   // --extractMesh: the size of the mesh written
   unsigned long long meshVertices = 0, meshTriangles = 0;
+  // with a component flag: the mesh as extracted, and the connected components found in it and kept (meshVertices /
+  // meshTriangles are then the filtered mesh's)
+  unsigned long long meshVerticesExtracted = 0, meshTrianglesExtracted = 0, meshComponents = 0, meshComponentsKept = 0;
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
@@ -65,9 +75,10 @@ bool WriteMetaImage(const std::string &path, const int pointDims[3], const doubl
 // a triangle mesh as VTK XML PolyData (what vtkXMLPolyDataWriter writes, rmain:184-187): appended raw data, UInt64 headers,
 // Float64 Points, Polys with Int64 connectivity and offsets.  With `normals` ([nPoints][3] f32) also the point arrays of
 // vtkContourFilter: <PointData Normals="Normals" Scalars="reconstruction_scalar">, Float32 x 3 and Float64 `contour` at every
-// point, appended behind the offsets; without them the file is what it always was.
+// point, appended behind the offsets; without them the file is what it always was.  With `regionIds` ([nPoints] int64) the
+// point array RegionId (Int64, one component) behind those; alone it is the section's Scalars.
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
-                   std::string *error, const float *normals = nullptr, double contour = 0.0);
+                   std::string *error, const float *normals = nullptr, double contour = 0.0, const int64_t *regionIds = nullptr);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

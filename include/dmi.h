@@ -44,7 +44,9 @@ extern "C" {
                            * 4: dmi_get_window_pair_count, dmi_get_upload_kernel_ms, dmi_sizeof_info / dmi_sizeof_timings
                            * 5: dmi_get_view_paths; later, additions only: dmi_extract_isosurface,
                            *    dmi_download_isosurface, dmi_get_isosurface_kernel_ms; dmi_extract_isosurface_normals,
-                           *    dmi_download_isosurface_normals */
+                           *    dmi_download_isosurface_normals; dmi_filter_isosurface_components, dmi_download_isosurface_regions,
+                           *    dmi_get_isosurface_filter_kernel_ms, dmi_get_isosurface_filter_pass_ms,
+                           *    dmi_get_isosurface_filter_cas_retries */
 
 typedef struct dmi_context dmi_context;
 
@@ -264,6 +266,42 @@ int dmi_download_isosurface_normals(dmi_context *ctx, float *normals);
 /* hipEvent time of the kernels of the last dmi_extract_isosurface or dmi_extract_isosurface_normals (both passes and the scans
  * between them). */
 int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last);
+
+/* What vtkPolyDataConnectivityFilter does after the reference's contour, on the device: label the connected components of the
+ * context's mesh, keep some of them and compact the mesh (additions to ABI 5; csrc/isosurface_components.hip).  The input is
+ * the mesh the context holds: that of the last successful extraction (with or without normals), or of the last filter since --
+ * V vertices, T triangles [T][3] of vertex ids.  Definition (all results are integers or copied bits):
+ *   - connectivity is by vertex ID, never by position: two vertices are adjacent when one triangle names both, a component is
+ *     a class of the transitive closure.  Vertices that coincide in position (t = 0 or 1) but have different ids are joined
+ *     only through the degenerate triangles that name them, which the extraction keeps.  A vertex no triangle names is a
+ *     component of its own with 0 triangles (a marching-cubes mesh has none);
+ *   - the LABEL of a component is its smallest vertex id, its SIZE the number of triangles whose vertices lie in it, degenerate
+ *     ones included;
+ *   - mode DMI_COMPONENTS_MIN_TRIANGLES keeps every component with size >= min_triangles (0 keeps everything: labels only);
+ *     mode DMI_COMPONENTS_LARGEST keeps the one component of greatest size, ties going to the smallest label (min_triangles is
+ *     ignored); an empty mesh stays empty;
+ *   - the new mesh: the surviving vertices in ascending old id, renumbered 0, 1, 2, ...; the surviving triangles in their
+ *     original order with their ids remapped; positions, and normals when the extraction had them, are the original bits;
+ *   - the kept components are numbered 0, 1, 2, ... by ascending label: RegionId[v] (one per surviving vertex) is its
+ *     component's number and RegionSize[r] (one per kept component) its size.
+ * Returns the new mesh's sizes, the components found and the components kept.  A mesh filtered to nothing is a success (0, 0),
+ * as an empty extraction is.  The filter is idempotent for the same arguments.  Afterwards dmi_download_isosurface and
+ * dmi_download_isosurface_normals return the filtered mesh; the next extraction replaces it.
+ * DMI_ERR_INVALID_ARGUMENT: a null pointer, an unknown mode, no successful extraction yet, or a mesh of 2^32 or more vertices
+ * or triangles (labels and sizes are 32-bit on the device: refused, never wrapped).  Synchronises once, to read the counts. */
+enum { DMI_COMPONENTS_MIN_TRIANGLES = 0, DMI_COMPONENTS_LARGEST = 1 };
+int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
+                                     uint64_t *n_components, uint64_t *n_components_kept);
+/* RegionId [n_vertices] and RegionSize [n_components_kept] of the last filter, int64; either pointer may be null (not wanted).
+ * DMI_ERR_INVALID_ARGUMENT before any successful extraction and when no filter has run since the last one.  Synchronises. */
+int dmi_download_isosurface_regions(dmi_context *ctx, int64_t *region_id, int64_t *region_size);
+/* hipEvent time of all kernels of the last dmi_filter_isosurface_components (separate from dmi_get_isosurface_kernel_ms), and
+ * pass by pass: out[0] labels (initialisation, hooking, flattening), out[1] sizes (and the maximum for LARGEST), out[2] the three
+ * scans, out[3] the compaction. */
+int dmi_get_isosurface_filter_kernel_ms(dmi_context *ctx, double *last);
+int dmi_get_isosurface_filter_pass_ms(dmi_context *ctx, double out[4]);
+/* Diagnostic: how many compare-and-swaps of the last filter's hooking pass lost a race and were retried (0 = no contention). */
+int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last);
 
 /* Diagnostic: how many (8 x 8 x column brick, view) pairs of the last dmi_fuse were proven to be handled
  * uniformly.  out[0] mixed (per-voxel path), out[1] all voxels accumulate -eta*rho, out[2] all accumulate 0,

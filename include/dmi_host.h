@@ -94,13 +94,19 @@ typedef struct dmi_cli_options {
   int32_t verbose, summary, force_cubic_voxel;
   int32_t extract_mesh;       /* --extractMesh (not in the reference): write the iso-surface to --outputMeshFilename */
   int32_t mesh_normals;       /* --meshNormals (not in the reference; only with --extractMesh): with its Normals and scalar */
+  /* not in the reference, only with --extractMesh (dmi_filter_isosurface_components, dmi.h): */
+  int32_t mesh_largest_component;        /* --meshLargestComponent: keep the connected component with the most triangles */
+  int32_t mesh_region_ids;               /* --meshRegionIds: write the point array RegionId */
+  int64_t mesh_min_component_triangles;  /* --meshMinComponentTriangles N: drop components of fewer triangles; -1: not given */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
 /* The whole tool: ReadArguments, the filter, cell -> point data, meta_image_volume.mha (in the working directory, as the
  * reference), the .vts volume, the summary file.  Process exit code: 0 on success.  The iso-surface (rmain:166-187) only
  * with --extractMesh: dmi_extract_isosurface at --contour, written to --outputMeshFilename by dmi_write_polydata; with
- * --meshNormals too, dmi_extract_isosurface_normals and dmi_write_polydata_with_normals. */
+ * --meshNormals too, dmi_extract_isosurface_normals and dmi_write_polydata_with_normals.  With --meshMinComponentTriangles
+ * and / or --meshLargestComponent the mesh goes through dmi_filter_isosurface_components first (by size, then the largest), and
+ * with --meshRegionIds the file is dmi_write_polydata_with_arrays' with RegionId. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
@@ -114,6 +120,13 @@ int dmi_write_polydata(const char *path, const double *points, int64_t n_points,
  * 0 when the file cannot be written, a count is negative or a pointer is null while its count is not zero. */
 int dmi_write_polydata_with_normals(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
                                     int64_t n_triangles, const float *normals, double contour);
+
+/* Either file with the point array RegionId (Int64, one component: region_id[n_points], dmi_download_isosurface_regions)
+ * appended behind everything else.  normals == NULL: dmi_write_polydata's file plus <PointData Scalars="RegionId">; otherwise
+ * dmi_write_polydata_with_normals' with RegionId as the third array of its <PointData>.  region_id == NULL: exactly the file of
+ * dmi_write_polydata (normals == NULL) or dmi_write_polydata_with_normals.  1 on success; 0 as those two. */
+int dmi_write_polydata_with_arrays(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
+                                   int64_t n_triangles, const float *normals, double contour, const int64_t *region_id);
 
 /* dmi_mesh_coloration_from_lists with the visibility test of dmi_color_set_depth_test (dmi.h) at `depth_tolerance`
  * (MeshColoration::SetDepthTolerance; needs the views' "Depths" arrays).  1 on success, 0 on error (message in err). */

@@ -1,8 +1,13 @@
 """Kernel time of dmi_extract_isosurface on the cfg-3 speckle scene (512^3, 256 views of 1280 x 720, as bench.py --full builds
 it), next to the HBM floor of reading the point lattice.  Prints one JSON line.  With --normals it times
-dmi_extract_isosurface_normals too, the two calls alternating in the same process (kernel_ms / normals_kernel_ms).
+dmi_extract_isosurface_normals too, the two calls alternating in the same process (kernel_ms / normals_kernel_ms).  With
+--components it times dmi_filter_isosurface_components beside the extraction (each filter follows a fresh extraction with
+normals, the calls alternating): MIN(0), MIN at --min-triangles and LARGEST, pass by pass, with the mesh's component count and
+size histogram, a floor derived from the bytes the filter must move, and the host alternative (download + the numpy restatement
+of tests/isosurface_components_np.py, imported from there) for orientation.  --grid N runs the whole tool on an N^3 grid (a quick
+run; the records in profiles/ are of the default 512).
 
-    python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals]
+    python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
 """
 import argparse
 import json
@@ -18,14 +23,73 @@ HBM_TBPS = 8.0        # MI355X peak
 C2P_TBPS = 4.7        # what the cell -> point pass achieves (profiles/NOTEBOOK.md)
 
 
+def components_record(ctx, a):
+    """The --components record of the context's grid at a.iso (a.repeat rounds after a warm-up round, a.min_triangles the mid
+    threshold).  In every round each of the three filters follows a fresh extraction with normals, whose own kernel time is taken
+    in the same breath: the ratios compare calls that alternate in one process."""
+    import time
+
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))   # the host alternative IS the tests' numpy restatement
+    import isosurface_components_np as C
+    rec = {"min_triangles_mid": a.min_triangles}
+    cases = {"min0": ("min_triangles", 0), "mid": ("min_triangles", a.min_triangles), "largest": ("largest", 0)}
+    for k in cases:
+        rec[k] = {"kernel_ms": [], "pass_ms": [], "extraction_kernel_ms": [], "cas_retries": []}
+    for r in range(a.repeat + 1):                       # round 0 is the warm-up: buffers sized, code loaded
+        for k, (mode, n) in cases.items():
+            ctx.extract_isosurface_with_normals(a.iso)
+            ex = ctx.isosurface_kernel_ms()
+            counts = ctx.filter_isosurface_components(mode, n)
+            if r:
+                rec[k]["extraction_kernel_ms"].append(ex)
+                rec[k]["kernel_ms"].append(ctx.isosurface_filter_kernel_ms())
+                rec[k]["pass_ms"].append(ctx.isosurface_filter_pass_ms())
+                rec[k]["cas_retries"].append(ctx.isosurface_filter_cas_retries())
+            rec[k]["counts"] = dict(zip(("vertices", "triangles", "components", "components_kept"), counts))
+    # the size histogram, from the labels-only filter's RegionSize
+    verts, tris, normals = ctx.extract_isosurface_with_normals(a.iso)
+    nv, nt = len(verts), len(tris)
+    ctx.filter_isosurface_components("min_triangles", 0)
+    _, rsz = ctx.download_isosurface_regions()
+    edges = [0, 1, 2, 4, 8, 16, 32, 64, 128, 256, 1024, 4096, 1 << 14, 1 << 16, 1 << 20, 1 << 62]
+    hist = np.histogram(rsz, bins=edges)[0]
+    rec["size_histogram"] = {f"[{lo},{hi})": int(c) for lo, hi, c in zip(edges[:-1], edges[1:], hist)}
+    rec["largest_sizes"] = [int(x) for x in np.sort(rsz)[::-1][:5]]
+    # The floor: triangles read twice and written once (3 x 24 B), positions and normals read and written once (2 x 36 B per
+    # vertex), labels / sizes / maps written and read once each (16 B per vertex), RegionId written (8 B per vertex).
+    rec["floor_bytes"] = nt * 72 + nv * (72 + 16 + 8)
+    rec["floor_ms_c2p_rate"] = rec["floor_bytes"] / C2P_TBPS / 1e9
+    for k in cases:
+        rec[k]["kernel_ms_min"] = min(rec[k]["kernel_ms"])
+        rec[k]["extraction_kernel_ms_min"] = min(rec[k]["extraction_kernel_ms"])
+        rec[k]["over_extraction"] = rec[k]["kernel_ms_min"] / rec[k]["extraction_kernel_ms_min"]
+        rec[k]["over_floor_c2p_rate"] = rec[k]["kernel_ms_min"] / rec["floor_ms_c2p_rate"]
+    # the host alternative, for orientation: download the unfiltered mesh, label it with the numpy restatement
+    ctx.extract_isosurface_with_normals(a.iso)
+    ctx.filter_isosurface_components("min_triangles", 0)        # keeps everything: the download below is the whole mesh
+    t0 = time.perf_counter()
+    ctx.download_isosurface()
+    ctx.download_isosurface_normals()
+    t1 = time.perf_counter()
+    want = C.filter_mesh(verts, tris, normals, C.LARGEST)
+    t2 = time.perf_counter()
+    rec["host_download_s"], rec["host_numpy_largest_s"] = t1 - t0, t2 - t1
+    rec["host_matches_gpu"] = want["counts"] == tuple(rec["largest"]["counts"].values())
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iso", type=float, default=1.0)
     ap.add_argument("--views", type=int, default=256)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--normals", action="store_true", help="also time the call with normals, alternating with the plain one")
+    ap.add_argument("--components", action="store_true", help="also time the connected-components filter after the extraction")
+    ap.add_argument("--min-triangles", type=int, default=100, help="the mid threshold of --components")
+    ap.add_argument("--grid", type=int, default=512, help="cells per axis (512: the cfg-3 grid)")
     a = ap.parse_args()
-    grid = scene.default_grid(512)
+    grid = scene.default_grid(a.grid)
     ray = scene.default_ray_potential(grid)
     spacing = float(max(grid.spacing))
     with capi.FusionContext(grid, ray) as ctx:
@@ -47,7 +111,8 @@ def main():
                 ctx.extract_isosurface_with_normals(a.iso)
                 ntimes.append(ctx.isosurface_kernel_ms())
         nv, nt = len(verts), len(tris)
-    n_points = 513 ** 3
+        comp = components_record(ctx, a) if a.components else None
+    n_points = (a.grid + 1) ** 3
     lattice = n_points * 8
     out = {"iso": a.iso, "views": a.views, "vertices": nv, "triangles": nt, "kernel_ms": times, "kernel_ms_min": min(times),
            "lattice_bytes": lattice, "mesh_bytes": nv * 24 + nt * 24,
@@ -56,6 +121,8 @@ def main():
     if a.normals:
         out.update({"normals_kernel_ms": ntimes, "normals_kernel_ms_min": min(ntimes), "normals_bytes": nv * 12,
                     "normals_over_plain_min": min(ntimes) / min(times)})
+    if comp is not None:
+        out["components"] = comp
     print(json.dumps(out))
 
 
