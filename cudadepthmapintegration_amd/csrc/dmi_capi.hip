@@ -167,6 +167,20 @@ struct dmi_context {
   double last_filter_kernel_ms = 0.0;
   uint64_t last_filter_cas_retries = 0;     // compare-and-swaps of the last filter's hooking pass that lost a race
   double last_filter_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // labels (init, hook, flatten), sizes (and largest), scans, compaction
+  // dmi_smooth_isosurface (isosurface_smooth.hip): the steps go from the mesh into d_mesh_alt_vertices and d_smooth_vertices in
+  // turn (the last one written is swapped with the mesh's afterwards), the normals into d_mesh_alt_normals; the adjacency's scratch,
+  // all kept while large enough
+  double *d_smooth_vertices = nullptr;
+  uint64_t smooth_vertex_capacity = 0;     // vertices
+  uint64_t *d_smooth_keys = nullptr;       // two arrays of 6 triangles' keys
+  uint64_t smooth_keys_capacity = 0;       // bytes
+  void *d_smooth_vertex_scratch = nullptr;  // the fixed bits, then row starts, valences and offsets: 3 arrays of (vertices + 1)
+  uint64_t smooth_vertex_scratch_capacity = 0;  // bytes
+  void *d_smooth_temp = nullptr;
+  uint64_t smooth_temp_capacity = 0;
+  hipEvent_t smooth_events[4] = {nullptr, nullptr, nullptr, nullptr};
+  double last_smooth_kernel_ms = 0.0;
+  double last_smooth_pass_ms[3] = {0.0, 0.0, 0.0};  // adjacency (and incidence), steps, normals
 
   void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
   double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
@@ -1074,6 +1088,10 @@ void dmi_destroy(dmi_context *ctx) {
                   (void *)ctx->d_comp_triangle_scratch, (void *)ctx->d_comp_counters, ctx->d_comp_scan_temp})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : ctx->comp_events)
+    if (e) (void)hipEventDestroy(e);
+  for (void *p : {(void *)ctx->d_smooth_vertices, (void *)ctx->d_smooth_keys, ctx->d_smooth_vertex_scratch, ctx->d_smooth_temp})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t e : ctx->smooth_events)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->slab_events) (void)hipEventDestroy(e);
   if (ctx->download_stream) (void)hipStreamDestroy(ctx->download_stream);
@@ -2270,6 +2288,117 @@ int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last) {
   return guarded(ctx, "dmi_get_isosurface_filter_cas_retries", [&]() -> int {
   if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_cas_retries: null argument");
   *last = ctx->last_filter_cas_retries;
+  return DMI_OK;
+  });
+}
+
+int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, double mu) {
+  return guarded(ctx, "dmi_smooth_isosurface", [&]() -> int {
+  const std::string entry = "dmi_smooth_isosurface";
+  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (iterations < 0 || iterations > 1000)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": iterations " + std::to_string(iterations) + " is not in [0, 1000]");
+  if (!(lambda > 0.0 && lambda <= 1.0)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": lambda is not in (0, 1]");
+  if (!(mu <= 0.0) || mu - mu != 0.0) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mu is not a finite number <= 0");
+  if (!ctx->mesh_valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const uint64_t nv = ctx->mesh_vertices, nt = ctx->mesh_triangles;
+  // ids are u32 on the device, and so are the offsets into the 6 T directed edges: refused, never wrapped
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  if (6 * nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit adjacency offsets (6 x triangles >= 2^32)");
+  if (iterations == 0 || nv == 0) {  // nothing to do: the mesh, its normals included, stays as it is
+    ctx->last_smooth_kernel_ms = 0.0;
+    for (double &p : ctx->last_smooth_pass_ms) p = 0.0;
+    return DMI_OK;
+  }
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  const bool normals = ctx->mesh_has_normals;
+  const uint64_t fixed_words = (nv + 63) / 64;
+  int rc;
+  {
+    uint64_t cap = ctx->mesh_alt_vertex_capacity * 24;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_vertices, &cap, nv * 24);
+    if (rc != DMI_OK) return rc;
+    ctx->mesh_alt_vertex_capacity = cap / 24;
+    cap = ctx->smooth_vertex_capacity * 24;
+    rc = ensure_buffer(ctx, (void **)&ctx->d_smooth_vertices, &cap, nv * 24);
+    if (rc != DMI_OK) return rc;
+    ctx->smooth_vertex_capacity = cap / 24;
+    if (normals) {
+      cap = ctx->mesh_alt_normal_capacity * 12;
+      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_normals, &cap, nv * 12);
+      if (rc != DMI_OK) return rc;
+      ctx->mesh_alt_normal_capacity = cap / 12;
+    }
+    rc = ensure_buffer(ctx, (void **)&ctx->d_smooth_keys, &ctx->smooth_keys_capacity, 2 * std::max<uint64_t>(6 * nt, 2) * 8);
+    if (rc != DMI_OK) return rc;
+    rc = ensure_buffer(ctx, &ctx->d_smooth_vertex_scratch, &ctx->smooth_vertex_scratch_capacity, fixed_words * 8 + 3 * (nv + 1) * 4);
+    if (rc != DMI_OK) return rc;
+  }
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::smooth_temp_bytes(nv, nt, &temp_bytes));
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  rc = ensure_buffer(ctx, &ctx->d_smooth_temp, &ctx->smooth_temp_capacity, temp_bytes);
+  if (rc != DMI_OK) return rc;
+  if (!ctx->smooth_events[0])
+    for (hipEvent_t &e : ctx->smooth_events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::SmoothMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = ctx->d_mesh_vertices;
+  m.triangles = ctx->d_mesh_triangles;
+  m.normals_out = normals ? ctx->d_mesh_alt_normals : nullptr;
+  dmi::SmoothScratch s{};
+  s.keys[0] = ctx->d_smooth_keys;
+  s.keys[1] = ctx->d_smooth_keys + std::max<uint64_t>(6 * nt, 2);
+  s.fixed = (unsigned long long *)ctx->d_smooth_vertex_scratch;
+  s.row_start = (uint32_t *)(s.fixed + fixed_words);
+  s.valence = s.row_start + (nv + 1);
+  s.offsets = s.valence + (nv + 1);
+  s.positions[0] = ctx->d_mesh_alt_vertices;
+  s.positions[1] = ctx->d_smooth_vertices;
+  s.temp = ctx->d_smooth_temp;
+  s.temp_bytes = temp_bytes;
+  // (a failure from here on leaves the context's mesh as it was: no kernel writes it, and the buffers are swapped only at the end)
+  double *result = nullptr;
+  DMI_HIP(ctx, dmi::launch_isosurface_smooth(m, s, iterations, lambda, mu, &result, ctx->smooth_events, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->smooth_events[0], ctx->smooth_events[3]));
+  ctx->last_smooth_kernel_ms = (double)ms;
+  for (int p = 0; p < 3; ++p) {
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->smooth_events[p], ctx->smooth_events[p + 1]));
+    ctx->last_smooth_pass_ms[p] = (double)ms;
+  }
+  // the smoothed positions become the context's; the buffer they replace is the next call's scratch
+  if (result == ctx->d_mesh_alt_vertices) {
+    std::swap(ctx->d_mesh_vertices, ctx->d_mesh_alt_vertices);
+    std::swap(ctx->mesh_vertex_capacity, ctx->mesh_alt_vertex_capacity);
+  } else {
+    std::swap(ctx->d_mesh_vertices, ctx->d_smooth_vertices);
+    std::swap(ctx->mesh_vertex_capacity, ctx->smooth_vertex_capacity);
+  }
+  if (normals) {
+    std::swap(ctx->d_mesh_normals, ctx->d_mesh_alt_normals);
+    std::swap(ctx->mesh_normal_capacity, ctx->mesh_alt_normal_capacity);
+  }
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_smooth_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_kernel_ms: null argument");
+  *last = ctx->last_smooth_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]) {
+  return guarded(ctx, "dmi_get_isosurface_smooth_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_pass_ms: null argument");
+  for (int p = 0; p < 3; ++p) out[p] = ctx->last_smooth_pass_ms[p];
   return DMI_OK;
   });
 }

@@ -468,4 +468,24 @@ hipError_t components_scan_temp_bytes(uint64_t n_vertices, uint64_t n_triangles,
 hipError_t launch_isosurface_components(const ComponentsMesh &m, const ComponentsScratch &s, int largest, uint64_t min_triangles,
                                         hipEvent_t *events, hipStream_t stream);
 
+// Taubin smoothing of that mesh (isosurface_smooth.hip): the mesh to smooth (read only) and where its new normals go.
+struct SmoothMesh {
+  uint64_t n_vertices, n_triangles;  // n_vertices >= 1 and below 2^32, 6 n_triangles below 2^32 (u32 ids and CSR offsets)
+  const double *vertices;            // [n_vertices][3]
+  const int64_t *triangles;          // [n_triangles][3]
+  float *normals_out;                // [n_vertices][3]: the geometric normals of the result, or null: none wanted
+};
+struct SmoothScratch {
+  uint64_t *keys[2];                 // [6 n_triangles] each: the edge keys and their sort; afterwards the neighbour ids and the incidence
+  uint32_t *row_start;               // [n_vertices + 1]
+  uint32_t *valence, *offsets;       // [n_vertices + 1]: the CSR offsets, the total at [n_vertices]
+  unsigned long long *fixed;         // [(n_vertices + 63) / 64]: one bit per vertex
+  double *positions[2];              // [n_vertices][3] each: the steps' two buffers
+  void *temp;                        // rocPRIM's
+  size_t temp_bytes;
+};
+hipError_t smooth_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
+hipError_t launch_isosurface_smooth(const SmoothMesh &m, const SmoothScratch &s, int iterations, double lambda, double mu,
+                                    double **result, hipEvent_t *events, hipStream_t stream);
+
 }  // namespace dmi

@@ -344,6 +344,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_largest_component = o.meshLargestComponent;
   out->mesh_region_ids = o.meshRegionIds;
   out->mesh_min_component_triangles = o.meshMinComponentTriangles;
+  out->mesh_smooth_iterations = o.meshSmoothIterations;
+  out->mesh_smooth_lambda = o.meshSmoothLambda;
+  out->mesh_smooth_mu = o.meshSmoothMu;
   return 1;
   });
 }

@@ -76,6 +76,17 @@ std::function<bool(const std::vector<std::string> &)> into_count(long long *dst)
   };
 }
 
+// a number the predicate accepts (a NaN, an infinity or a value out of range is an error like a word); *given notes the flag
+std::function<bool(const std::vector<std::string> &)> into_checked_double(double *dst, bool *given, bool (*ok)(double)) {
+  return [dst, given, ok](const std::vector<std::string> &values) {
+    double x = 0.0;
+    if (values.size() != 1 || !parse_number(values[0], &x) || !std::isfinite(x) || !ok(x)) return false;
+    *dst = x;
+    *given = true;
+    return true;
+  };
+}
+
 std::function<bool(const std::vector<std::string> &)> into_flag(bool *dst) {
   return [dst](const std::vector<std::string> &) {
     *dst = true;
@@ -126,6 +137,23 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
       {"--meshRegionIds", {Kind::kFlag, "with --extractMesh: write the point array RegionId, the number of each vertex's connected component "
                                         "(components numbered by their smallest vertex id; not in the reference)",
                            into_flag(&o->meshRegionIds)}},
+      {"--meshSmoothIterations", {Kind::kValue, "with --extractMesh: smooth the mesh on the GPU, after the component flags, with this "
+                                                "many Taubin iterations (a step with --meshSmoothLambda, then one with --meshSmoothMu; "
+                                                "vertices on the mesh's boundary stay; an integer in 0..1000, default 0 = off); with "
+                                                "--meshNormals the Normals written are then the smoothed mesh's geometric normals, not the "
+                                                "field's gradient (not in the reference)",
+                                  [o](const std::vector<std::string> &values) {
+                                    long long n = 0;
+                                    if (!into_count(&n)(values) || n > 1000) return false;
+                                    o->meshSmoothIterations = n;
+                                    o->meshSmoothIterationsGiven = true;
+                                    return true;
+                                  }}},
+      {"--meshSmoothLambda", {Kind::kValue, "with --extractMesh: the smoothing's positive factor, in (0, 1] (default 0.5; not in the reference)",
+                              into_checked_double(&o->meshSmoothLambda, &o->meshSmoothLambdaGiven, [](double x) { return x > 0.0 && x <= 1.0; })}},
+      {"--meshSmoothMu", {Kind::kValue, "with --extractMesh: the smoothing's negative factor, <= 0 (default -0.53; 0 = plain Laplacian "
+                                        "smoothing; not in the reference)",
+                          into_checked_double(&o->meshSmoothMu, &o->meshSmoothMuGiven, [](double x) { return x <= 0.0; })}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -200,6 +228,12 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     err << "Error : --meshRegionIds needs --extractMesh (the region ids belong to the extracted mesh).\n" << HelpText();
     return false;
   }
+  for (const auto &flag : {std::make_pair("--meshSmoothIterations", o->meshSmoothIterationsGiven),
+                           std::make_pair("--meshSmoothLambda", o->meshSmoothLambdaGiven), std::make_pair("--meshSmoothMu", o->meshSmoothMuGiven)})
+    if (flag.second && !o->extractMesh) {
+      err << "Error : " << flag.first << " needs --extractMesh (the smoothing belongs to the extracted mesh).\n" << HelpText();
+      return false;
+    }
   // rmain:257-262
   if (!o->gridSpacing.empty() && !o->gridDims.empty()) {
     err << "Error : Spacing and dimensions can't be both set\n" << HelpText();
@@ -561,6 +595,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
         result->meshComponents = found;
         result->meshComponentsKept = kept;
       }
+      if (rc == DMI_OK && o.meshSmoothIterations > 0) {  // on the mesh the component flags left, before anything is downloaded
+        rc = dmi_smooth_isosurface(ctx, (int32_t)o.meshSmoothIterations, o.meshSmoothLambda, o.meshSmoothMu);
+        if (rc == DMI_OK) rc = dmi_get_isosurface_smooth_kernel_ms(ctx, &result->meshSmoothKernelMs);
+      }
       if (rc == DMI_OK) {
         meshVertices.resize((size_t)nv * 3);
         meshTriangles.resize((size_t)nt * 3);
@@ -603,6 +641,9 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       log << "mesh components: " << result->meshComponents << " found, " << result->meshComponentsKept << " kept; "
           << result->meshVerticesExtracted << " vertices, " << result->meshTrianglesExtracted << " triangles before, "
           << result->meshVertices << " vertices, " << result->meshTriangles << " triangles after" << std::endl;
+    if (o.meshSmoothIterations > 0)
+      log << "mesh smoothing: " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
+          << "; " << result->meshSmoothKernelMs << " ms of GPU kernels" << std::endl;
   } else {
     // Said whatever --verbose is: the reference writes a mesh here (rmain:166-187) and this tool does not.
     log << "warning: " << o.outputMeshFilename << " is NOT written: the iso-surface (vtkContourFilter) is not part of this tool; "
@@ -630,6 +671,9 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       out << "  mesh components found  " << result->meshComponents << "\n  mesh components kept  " << result->meshComponentsKept
           << "\n  mesh vertices before the component filter  " << result->meshVerticesExtracted
           << "\n  mesh triangles before the component filter  " << result->meshTrianglesExtracted << "\n";
+    if (o.meshSmoothIterations > 0)  // (only with --extractMesh)
+      out << "  mesh smoothing  " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
+          << ", " << result->meshSmoothKernelMs << " ms of GPU kernels\n";
     if (!o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << " (no surface extracted)\n";
     out << "time\n  reconstruction  " << result->reconstructionSeconds << " s\n  total           " << result->totalSeconds << " s\n";

@@ -9,7 +9,10 @@
 // the point arrays Normals and reconstruction_scalar that vtkContourFilter attaches.  --meshMinComponentTriangles N and
 // --meshLargestComponent (not in the reference: what a vtkPolyDataConnectivityFilter behind the contour would do) drop connected
 // components of that mesh on the device before it is downloaded (dmi_filter_isosurface_components: by size, then the largest),
-// and --meshRegionIds writes the point array RegionId (Int64: the kept components numbered by ascending label).  Without --extractMesh
+// and --meshRegionIds writes the point array RegionId (Int64: the kept components numbered by ascending label).
+// --meshSmoothIterations N with --meshSmoothLambda / --meshSmoothMu (not in the reference: what a smoothing filter behind those
+// would do) runs dmi_smooth_isosurface on the device after the component flags; with --meshNormals the Normals written are then
+// the smoothed mesh's geometric ones.  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
@@ -43,6 +46,11 @@ struct Options {
   // given), keep only the largest one (after the former), write the point array RegionId
   long long meshMinComponentTriangles = -1;
   bool meshLargestComponent = false, meshRegionIds = false;
+  // not in the reference (all need --extractMesh): Taubin smoothing of the mesh on the GPU after the component flags, N iterations
+  // of a step with lambda and one with mu (0 iterations: off)
+  long long meshSmoothIterations = 0;
+  double meshSmoothLambda = 0.5, meshSmoothMu = -0.53;
+  bool meshSmoothIterationsGiven = false, meshSmoothLambdaGiven = false, meshSmoothMuGiven = false;
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -64,6 +72,7 @@ struct RunResult {
   // with a component flag: the mesh as extracted, and the connected components found in it and kept (meshVertices /
   // meshTriangles are then the filtered mesh's)
   unsigned long long meshVerticesExtracted = 0, meshTrianglesExtracted = 0, meshComponents = 0, meshComponentsKept = 0;
+  double meshSmoothKernelMs = 0.0;  // --meshSmoothIterations: hipEvent time of the smoothing's kernels
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.

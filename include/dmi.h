@@ -46,7 +46,8 @@ extern "C" {
                            *    dmi_download_isosurface, dmi_get_isosurface_kernel_ms; dmi_extract_isosurface_normals,
                            *    dmi_download_isosurface_normals; dmi_filter_isosurface_components, dmi_download_isosurface_regions,
                            *    dmi_get_isosurface_filter_kernel_ms, dmi_get_isosurface_filter_pass_ms,
-                           *    dmi_get_isosurface_filter_cas_retries */
+                           *    dmi_get_isosurface_filter_cas_retries; dmi_smooth_isosurface, dmi_get_isosurface_smooth_kernel_ms,
+                           *    dmi_get_isosurface_smooth_pass_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -302,6 +303,43 @@ int dmi_get_isosurface_filter_kernel_ms(dmi_context *ctx, double *last);
 int dmi_get_isosurface_filter_pass_ms(dmi_context *ctx, double out[4]);
 /* Diagnostic: how many compare-and-swaps of the last filter's hooking pass lost a race and were retried (0 = no contention). */
 int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last);
+
+/* Taubin lambda|mu smoothing of the context's mesh on the device: what a smoothing filter placed behind the contour and the
+ * connectivity filter does (vtkSmoothPolyDataFilter without boundary and feature-edge smoothing; only the intent is shared, not
+ * the numbers).  Additions to ABI 5; csrc/isosurface_smooth.hip.  The input is the mesh the context holds: V vertices (f64 world
+ * positions p) and T triangles of vertex ids -- the last extraction's or the last component filter's.  The triangles, their
+ * order, the vertex ids, RegionId and RegionSize are not touched.  Definition, met bit for bit:
+ *   - neighbours are by vertex ID, never by position (as in the components filter): N(v) is the set of distinct ids u != v that
+ *     share a triangle with v, in ascending id.  Vertices that coincide in position (t = 0 or 1) stay separate vertices;
+ *   - an undirected edge {a, b}, a != b, named by exactly one triangle is a BOUNDARY edge (where the surface leaves the grid; a
+ *     triangle that names an edge twice, (a, b, a), is one triangle).  Both endpoints of a boundary edge are FIXED: a fixed
+ *     vertex never moves, but it is a neighbour like any other.  A vertex with an empty N(v) never moves;
+ *   - one STEP with factor f: for every vertex that is not fixed and has k = |N(v)| >= 1, with neighbours n_0 < n_1 < ...,
+ *     s_d = ((p[n_0][d] + p[n_1][d]) + p[n_2][d]) + ... added left to right, m_d = s_d / (double)k,
+ *     p'[v][d] = p[v][d] + f * (m_d - p[v][d]); f64, every operation rounded, no FMA; every vertex reads the positions of the
+ *     PREVIOUS step (Jacobi); non-finite coordinates propagate as the arithmetic makes them;
+ *   - one ITERATION: a step with lambda, then, if mu != 0, a step with mu (mu == 0: plain Laplacian smoothing); `iterations` of
+ *     them are run;
+ *   - NORMALS: if the mesh carries normals (dmi_extract_isosurface_normals) and iterations > 0, they are replaced by geometric
+ *     normals of the smoothed mesh (the gradient normals describe the unsmoothed field).  For vertex v, over the triangles
+ *     (a, b, c), as stored, that name it (each once), in ascending triangle index: e = p[b] - p[a], g = p[c] - p[a],
+ *     x = (e_1*g_2 - e_2*g_1, e_2*g_0 - e_0*g_2, e_0*g_1 - e_1*g_0) (the area-weighted cross product; it points from the inside
+ *     to the outside, as the gradient normals do); w = the x added left to right ((0, 0, 0) without a triangle);
+ *     L = sqrt((w_0*w_0 + w_1*w_1) + w_2*w_2); n = w / L when L != 0 (a NaN L included), else n = w; each n_r rounded to f32
+ *     (nearest even).
+ * iterations in [0, 1000]; lambda finite and in (0, 1]; mu finite and <= 0.  iterations == 0 is a success that changes nothing,
+ * normals included; an empty mesh is a success.  DMI_ERR_INVALID_ARGUMENT for anything else, for a null context, before any
+ * successful extraction, and for a mesh of 2^32 or more vertices or triangles (ids are 32-bit on the device, as in the filter;
+ * the offsets into the 6 T directed edges too: 6 T >= 2^32 is refused as well).  A call that fails leaves the context's mesh as
+ * it was.  Afterwards dmi_download_isosurface and dmi_download_isosurface_normals return the smoothed mesh,
+ * dmi_download_isosurface_regions still works if a filter had run, a later dmi_filter_isosurface_components takes the smoothed
+ * mesh as its input, and the next extraction replaces it.  Synchronises once, at its end. */
+int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, double mu);
+/* hipEvent time of all kernels of the last dmi_smooth_isosurface, and pass by pass: out[0] the adjacency (edge keys, sort, CSR,
+ * fixed bits, and the triangle incidence of the normals), out[1] all steps, out[2] the normals.  Zeros after a call that had
+ * nothing to do. */
+int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last);
+int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]);
 
 /* Diagnostic: how many (8 x 8 x column brick, view) pairs of the last dmi_fuse were proven to be handled
  * uniformly.  out[0] mixed (per-voxel path), out[1] all voxels accumulate -eta*rho, out[2] all accumulate 0,

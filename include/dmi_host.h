@@ -98,6 +98,10 @@ typedef struct dmi_cli_options {
   int32_t mesh_largest_component;        /* --meshLargestComponent: keep the connected component with the most triangles */
   int32_t mesh_region_ids;               /* --meshRegionIds: write the point array RegionId */
   int64_t mesh_min_component_triangles;  /* --meshMinComponentTriangles N: drop components of fewer triangles; -1: not given */
+  /* not in the reference, only with --extractMesh (dmi_smooth_isosurface, dmi.h); appended to the struct: */
+  int64_t mesh_smooth_iterations;        /* --meshSmoothIterations N: Taubin iterations after the component flags; 0: off */
+  double mesh_smooth_lambda;             /* --meshSmoothLambda (default 0.5) */
+  double mesh_smooth_mu;                 /* --meshSmoothMu (default -0.53) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -106,7 +110,8 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * with --extractMesh: dmi_extract_isosurface at --contour, written to --outputMeshFilename by dmi_write_polydata; with
  * --meshNormals too, dmi_extract_isosurface_normals and dmi_write_polydata_with_normals.  With --meshMinComponentTriangles
  * and / or --meshLargestComponent the mesh goes through dmi_filter_isosurface_components first (by size, then the largest), and
- * with --meshRegionIds the file is dmi_write_polydata_with_arrays' with RegionId. */
+ * with --meshRegionIds the file is dmi_write_polydata_with_arrays' with RegionId.  With --meshSmoothIterations N the mesh goes
+ * through dmi_smooth_isosurface after those (the Normals of --meshNormals are then the smoothed mesh's geometric ones). */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of

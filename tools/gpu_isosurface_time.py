@@ -4,10 +4,14 @@ dmi_extract_isosurface_normals too, the two calls alternating in the same proces
 --components it times dmi_filter_isosurface_components beside the extraction (each filter follows a fresh extraction with
 normals, the calls alternating): MIN(0), MIN at --min-triangles and LARGEST, pass by pass, with the mesh's component count and
 size histogram, a floor derived from the bytes the filter must move, and the host alternative (download + the numpy restatement
-of tests/isosurface_components_np.py, imported from there) for orientation.  --grid N runs the whole tool on an N^3 grid (a quick
+of tests/isosurface_components_np.py, imported from there) for orientation.  With --smooth N it times dmi_smooth_isosurface
+(N iterations) in the same alternating style, once on the raw mesh and once after MIN(--min-triangles): pass by pass, one step
+against the bytes it must move, the scratch it needs, and the numpy restatement (tests/isosurface_smooth_np.py) on the raw
+mesh for orientation.  --grid N runs the whole tool on an N^3 grid (a quick
 run; the records in profiles/ are of the default 512).
 
     python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
+                                         [--smooth 10 [--smooth-lambda 0.5] [--smooth-mu -0.53]]
 """
 import argparse
 import json
@@ -79,6 +83,61 @@ def components_record(ctx, a):
     return rec
 
 
+def smooth_record(ctx, a):
+    """The --smooth record of the context's grid at a.iso: a.smooth iterations with a.smooth_lambda / a.smooth_mu, a.repeat rounds
+    after a warm-up round.  In every round each smoothing follows a fresh extraction with normals ("raw"), or that and the
+    MIN(a.min_triangles) filter ("min"); the extraction's own kernel time is taken in the same breath."""
+    import time
+
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))   # the host alternative IS the tests' numpy restatement
+    import isosurface_smooth_np as S
+    steps = a.smooth * (2 if a.smooth_mu != 0 else 1)
+    rec = {"iterations": a.smooth, "lambda": a.smooth_lambda, "mu": a.smooth_mu, "steps": steps, "min_triangles": a.min_triangles}
+    for k in ("raw", "min"):
+        rec[k] = {"kernel_ms": [], "pass_ms": [], "extraction_kernel_ms": []}
+    for r in range(a.repeat + 1):                       # round 0 is the warm-up: buffers sized, code loaded
+        for k in ("raw", "min"):
+            ctx.extract_isosurface_with_normals(a.iso)
+            ex = ctx.isosurface_kernel_ms()
+            if k == "min":
+                ctx.filter_isosurface_components("min_triangles", a.min_triangles)
+            if r == 0:                                  # the mesh that is smoothed, for the counts and the host's run
+                verts, tris = ctx.download_isosurface()
+                normals = ctx.download_isosurface_normals()
+                rec[k]["vertices"], rec[k]["triangles"] = len(verts), len(tris)
+                if k == "raw":
+                    raw = (verts, tris, normals)
+                rec[k]["neighbour_entries"] = int(S.adjacency(len(verts), tris)[1].sum())
+            ctx.smooth_isosurface(a.smooth, a.smooth_lambda, a.smooth_mu)
+            if r:
+                rec[k]["extraction_kernel_ms"].append(ex)
+                rec[k]["kernel_ms"].append(ctx.isosurface_smooth_kernel_ms())
+                rec[k]["pass_ms"].append(ctx.isosurface_smooth_pass_ms())
+            if k == "raw" and r == a.repeat:
+                got = (ctx.download_isosurface()[0], ctx.download_isosurface_normals())
+    for k in ("raw", "min"):
+        nv, nt, ne = rec[k]["vertices"], rec[k]["triangles"], rec[k]["neighbour_entries"]
+        rec[k]["kernel_ms_min"] = min(rec[k]["kernel_ms"])
+        rec[k]["extraction_kernel_ms_min"] = min(rec[k]["extraction_kernel_ms"])
+        rec[k]["over_extraction"] = rec[k]["kernel_ms_min"] / rec[k]["extraction_kernel_ms_min"]
+        for p in ("adjacency", "steps", "normals"):
+            rec[k][p + "_ms_min"] = min(q[p] for q in rec[k]["pass_ms"])
+        rec[k]["step_ms"] = rec[k]["steps_ms_min"] / steps
+        # one step's floor: positions read and written once (2 x 24 B per vertex), the CSR read once (offsets and neighbour ids)
+        rec[k]["step_floor_bytes"] = 48 * nv + 4 * (nv + 1) + 4 * ne
+        rec[k]["step_floor_ms_c2p_rate"] = rec[k]["step_floor_bytes"] / C2P_TBPS / 1e9
+        rec[k]["step_over_floor_c2p_rate"] = rec[k]["step_ms"] / rec[k]["step_floor_ms_c2p_rate"]
+        # the scratch of the call (DESIGN.md 8f), rocPRIM's own storage aside: two key arrays of 6 T, the fixed bits and three
+        # u32 arrays per vertex, and the two step buffers (one of them is the component filter's second vertex buffer)
+        rec[k]["scratch_bytes"] = 2 * max(6 * nt, 2) * 8 + (nv + 63) // 64 * 8 + 12 * (nv + 1) + 48 * nv
+    t0 = time.perf_counter()
+    want = S.smooth(raw[0], raw[1], a.smooth, a.smooth_lambda, a.smooth_mu, raw[2])
+    rec["host_numpy_s"] = time.perf_counter() - t0
+    rec["host_matches_gpu"] = want[0].tobytes() == got[0].tobytes() and want[1].tobytes() == got[1].tobytes()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iso", type=float, default=1.0)
@@ -87,6 +146,9 @@ def main():
     ap.add_argument("--normals", action="store_true", help="also time the call with normals, alternating with the plain one")
     ap.add_argument("--components", action="store_true", help="also time the connected-components filter after the extraction")
     ap.add_argument("--min-triangles", type=int, default=100, help="the mid threshold of --components")
+    ap.add_argument("--smooth", type=int, default=0, help="also time the Taubin smoothing with this many iterations (0: not)")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5)
+    ap.add_argument("--smooth-mu", type=float, default=-0.53)
     ap.add_argument("--grid", type=int, default=512, help="cells per axis (512: the cfg-3 grid)")
     a = ap.parse_args()
     grid = scene.default_grid(a.grid)
@@ -112,6 +174,7 @@ def main():
                 ntimes.append(ctx.isosurface_kernel_ms())
         nv, nt = len(verts), len(tris)
         comp = components_record(ctx, a) if a.components else None
+        smooth = smooth_record(ctx, a) if a.smooth > 0 else None
     n_points = (a.grid + 1) ** 3
     lattice = n_points * 8
     out = {"iso": a.iso, "views": a.views, "vertices": nv, "triangles": nt, "kernel_ms": times, "kernel_ms_min": min(times),
@@ -123,6 +186,8 @@ def main():
                     "normals_over_plain_min": min(ntimes) / min(times)})
     if comp is not None:
         out["components"] = comp
+    if smooth is not None:
+        out["smooth"] = smooth
     print(json.dumps(out))
 
 
