@@ -1,24 +1,28 @@
 // dmi_capi.hip -- implementation of the C ABI declared in include/dmi.h.
 //
+// Creation, destruction, views, fusion, grid transfer and the diagnostics; the point data and the mesh entry points are in
+// dmi_capi_mesh.hip, the context both files work on in dmi_context.h.
 // Host-side driver of the fusion path: what CudaInitialize (cu:269-298) and ProcessDepthMap
 // (cu:302-386) do in the reference, minus the disk I/O and the VTK types.  No global state: everything
 // lives in the context (the reference keeps __constant__ symbols and ch_gridDims, cu:55-64).
-#include "../../include/dmi.h"
-#include "fusion_kernels.h"
+#include "dmi_context.h"
 
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <limits>
-#include <new>
-#include <string>
-#include <vector>
 
+using dmi::Batch;
+using dmi::drain_c2p;
+using dmi::drain_events;
+using dmi::EventPair;
+using dmi::fail;
+using dmi::flush_zero_fill;
 using dmi::FuseArgs;
 using dmi::FuseConfig;
+using dmi::guarded;
 using dmi::MapRec;
 using dmi::TileArgs;
 using dmi::TileMapRec;
@@ -27,175 +31,14 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct Batch {
-  void *d_depth = nullptr;             // n * W * H values of the context's current storage type
-  dmi::DepthTile *d_pyramid = nullptr;  // n min/max pyramids (fusion_classify.hip), then the n validity maps
-  size_t valid_offset = 0;              // byte offset of the validity maps within d_pyramid
-  size_t bits_offset = 0;               // ... and of the validity bits (TileMapRec::vbits) behind them
-  size_t aux_bytes = 0;                 // size of the d_pyramid allocation
-  int32_t n = 0;
-  unsigned long long holes = 0;         // pixels without a depth among the n * W * H (counted while the validity maps are built)
-  unsigned long long mingled_strips = 0;  // 8-pixel strips (a column of a tile row) with both a hole and a depth
-};
-
-struct EventPair {
-  hipEvent_t start = nullptr, stop = nullptr;
-  hipEvent_t mid = nullptr;  // recorded just before the fusion kernel proper (after cz table, classification, ordering)
-  bool has_mid = false;
-};
-
 constexpr double kMagnitudeLimit = 1e60;  // see DESIGN.md "K specialisation": keeps every product finite
+
+size_t grid_elem(const dmi_context *c) { return c->opt.grid_dtype == DMI_F64 ? 8 : 4; }
+size_t depth_elem(const dmi_context *c) { return c->depth_f64 ? 8 : 4; }
 
 }  // namespace
 
-struct dmi_context {
-  dmi_grid_desc grid{};
-  dmi_ray_potential ray{};
-  dmi_options opt{};
-  int64_t n_voxels = 0;
-
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  // dmi_add_views copies, converts and builds pyramids on a stream of its own and waits for that stream only: a fuse
-  // still running on `stream` overlaps the upload of the next views (FusionDriver::ProcessDepthMap pipelines on this)
-  hipStream_t upload_stream = nullptr;
-  hipStream_t download_stream = nullptr;  // dmi_fuse_range_download: the slabs' copies to the host
-  std::vector<hipEvent_t> slab_events;    // ... and what each waits for
-
-  void *d_grid = nullptr;
-  bool own_grid = false;
-  std::vector<uint8_t> layer_is_zero;  // per cell layer: known to hold +0.0 everywhere (reset, not fused since)
-  bool zero_fill_pending = false;  // reset requested, memset deferred: the next fuse overwrites every voxel
-  // No voxel of the (context-owned) grid is -0.0: true after a reset and preserved by every fusion -- a sum that is not -0.0 never
-  // becomes one (x + y is -0.0 only when both are; a non-zero f64 sum does not round to zero) -- so the +0.0 adds of voxels far
-  // behind every surface stay unobservable from one dmi_fuse_range to the next, not only in the first (round 4: the chunked
-  // fusion of the drop-in filter ran its later chunks at half speed).  False once the caller has uploaded a grid, and for a
-  // caller-owned grid (whoever owns it may write anything between two calls).
-  bool grid_free_of_negative_zero = false;
-  uint32_t *d_voxel_hits = nullptr;
-  unsigned long long *d_map_hits = nullptr;
-  size_t map_hits_capacity = 0;
-
-  int32_t W = 0, H = 0;
-  bool depth_f64 = false;
-  bool finite_bounded = true;  // grid descriptor magnitudes allow the K shortcuts
-  int k_mode = dmi::K_PINHOLE;          // the least structured K among the resident views (dmi_info)
-  std::vector<uint8_t> view_k_mode;     // per view: dmi::KMode of its K
-  std::vector<uint8_t> view_tile_ok;    // per view: meets the tiled kernel's per-view preconditions (make_tile_rec)
-  std::vector<Batch> batches;
-  std::vector<MapRec> h_maps;
-  MapRec *d_maps = nullptr;
-  size_t d_maps_capacity = 0;
-  bool maps_dirty = false;
-
-  // tiled kernel (fusion_tile.hip): per-map records, the r22*wz(k) table, a device copy of FuseArgs
-  std::vector<TileMapRec> h_tile_maps;
-  TileMapRec *d_tile_maps = nullptr;
-  std::vector<dmi::WinRec> h_win_recs;  // per view: what the window form of the FREE column reads (one line each)
-  dmi::WinRec *d_win_recs = nullptr;
-  std::vector<dmi::FootRec> h_foot_recs;  // per view: the brick's corners relative to its first voxel (window_origin_kernel)
-  dmi::FootRec *d_foot_recs = nullptr;
-  double *d_cz_table = nullptr;
-  size_t cz_table_capacity = 0;  // doubles
-  FuseArgs *d_fuse_args = nullptr;
-  double max_tile_err = 0.0;     // largest TileMapRec::err among the resident views
-  bool last_fuse_tiled = false;
-  bool last_fuse_classes = false;
-  int64_t last_class_bricks = 0;  // wave bricks of the last fuse
-  int32_t last_bricks_z = 0, last_tk = 0;
-  const dmi::WinPair *last_win_origin = nullptr;  // the last tiled launch's pair table (nullptr: it had no windows)
-  int32_t last_class_pitch = 0, last_first = 0, last_count = 0;
-  dmi::PyramidDesc pyramid{};    // geometry of every view's depth min/max pyramid
-  uint8_t *d_zero_row = nullptr;  // one row of BRICK_MIXED bytes: the class table of a fuse without classes
-  size_t zero_row_capacity = 0;
-  uint8_t *d_classes = nullptr;  // brick classes [wave bricks][class_pitch], then the coarse table [boxes][class_pitch]
-  size_t coarse_offset = 0;      // byte offset of the coarse table within d_classes (last fuse)
-  size_t classes_capacity = 0;   // bytes
-  int32_t *d_queue_heads = nullptr;          // TileArgs::queue_heads (128 ints)
-  unsigned long long *d_wg_times = nullptr;  // tuning builds: TileArgs::wg_times of the last tiled fuse
-  size_t wg_times_blocks = 0;
-  // slot enumeration of the tiled kernel (TileArgs::sb_perm), one table per slab geometry seen (the z-slabs of a
-  // multi-GPU fusion come round again every step)
-  struct SlotPerm {
-    int32_t super_x, super_y, super_z, zmajor;
-    int32_t *d_perm;
-  };
-  std::vector<SlotPerm> slot_perms;
-  uint8_t *d_order_level = nullptr;  // workgroup order: scratch levels, order[], count
-  int32_t *d_order = nullptr;
-  size_t order_capacity = 0;     // slots
-
-  double *d_points = nullptr;     // vtkCellDataToPointData of the grid, (nx+1)(ny+1)(nz+1) f64 (grid_post.hip)
-  bool points_valid = false;      // d_points matches the grid's current contents
-  hipEvent_t c2p_start = nullptr, c2p_stop = nullptr;
-  bool c2p_pending = false;
-
-  // dmi_extract_isosurface (isosurface.hip): per-segment counts / bases and the scan's storage, kept while large enough;
-  // the mesh of the last call
-  uint32_t *d_mesh_counts = nullptr;
-  uint64_t *d_mesh_bases = nullptr;
-  size_t mesh_segments_capacity = 0;
-  void *d_mesh_scan_temp = nullptr;
-  uint64_t mesh_scan_temp_capacity = 0;
-  double *d_mesh_vertices = nullptr;
-  int64_t *d_mesh_triangles = nullptr;
-  uint64_t mesh_vertex_capacity = 0, mesh_triangle_capacity = 0;
-  uint64_t mesh_vertices = 0, mesh_triangles = 0;
-  bool mesh_valid = false;
-  float *d_mesh_normals = nullptr;      // dmi_extract_isosurface_normals: [n][3] f32, kept while large enough
-  uint64_t mesh_normal_capacity = 0;    // vertices
-  bool mesh_has_normals = false;        // the last successful extraction wrote them
-  hipEvent_t mesh_events[4] = {nullptr, nullptr, nullptr, nullptr};  // around the count pass + scans, and the write pass
-  double last_isosurface_kernel_ms = 0.0;
-  // dmi_filter_isosurface_components (isosurface_components.hip): the second set of mesh buffers the compaction writes (swapped
-  // with the first afterwards), the region arrays and the union-find's scratch, all kept while large enough
-  double *d_mesh_alt_vertices = nullptr;
-  int64_t *d_mesh_alt_triangles = nullptr;
-  float *d_mesh_alt_normals = nullptr;
-  uint64_t mesh_alt_vertex_capacity = 0, mesh_alt_triangle_capacity = 0, mesh_alt_normal_capacity = 0;
-  int64_t *d_mesh_region_id = nullptr, *d_mesh_region_size = nullptr;
-  uint64_t mesh_region_capacity = 0;       // vertices
-  uint32_t *d_comp_vertex_scratch = nullptr;  // parent, size, vmap, rmap: 4 arrays of (capacity + 1)
-  uint32_t *d_comp_triangle_scratch = nullptr;
-  uint64_t comp_vertex_capacity = 0, comp_triangle_capacity = 0;
-  unsigned long long *d_comp_counters = nullptr;
-  void *d_comp_scan_temp = nullptr;
-  uint64_t comp_scan_temp_capacity = 0;
-  hipEvent_t comp_events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool mesh_filtered = false;              // a filter has run since the last extraction: the region arrays are the mesh's
-  uint64_t mesh_regions = 0;               // kept components of that filter
-  double last_filter_kernel_ms = 0.0;
-  uint64_t last_filter_cas_retries = 0;     // compare-and-swaps of the last filter's hooking pass that lost a race
-  double last_filter_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // labels (init, hook, flatten), sizes (and largest), scans, compaction
-  // dmi_smooth_isosurface (isosurface_smooth.hip): the steps go from the mesh into d_mesh_alt_vertices and d_smooth_vertices in
-  // turn (the last one written is swapped with the mesh's afterwards), the normals into d_mesh_alt_normals; the adjacency's scratch,
-  // all kept while large enough
-  double *d_smooth_vertices = nullptr;
-  uint64_t smooth_vertex_capacity = 0;     // vertices
-  uint64_t *d_smooth_keys = nullptr;       // two arrays of 6 triangles' keys
-  uint64_t smooth_keys_capacity = 0;       // bytes
-  void *d_smooth_vertex_scratch = nullptr;  // the fixed bits, then row starts, valences and offsets: 3 arrays of (vertices + 1)
-  uint64_t smooth_vertex_scratch_capacity = 0;  // bytes
-  void *d_smooth_temp = nullptr;
-  uint64_t smooth_temp_capacity = 0;
-  hipEvent_t smooth_events[4] = {nullptr, nullptr, nullptr, nullptr};
-  double last_smooth_kernel_ms = 0.0;
-  double last_smooth_pass_ms[3] = {0.0, 0.0, 0.0};  // adjacency (and incidence), steps, normals
-
-  void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
-  double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
-  size_t stage_capacity = 0;  // elements per staging buffer
-  unsigned long long *d_lossy = nullptr;
-  hipEvent_t up_start = nullptr, up_stop = nullptr;  // around the upload pass's kernels (dmi_get_upload_kernel_ms)
-  double last_upload_kernel_ms = 0.0, total_upload_kernel_ms = 0.0;
-
-  std::vector<EventPair> pending, pool;
-  dmi_timings timings{};
-  uint64_t device_bytes = 0;
-  std::string err;
-};
-
-namespace {
+namespace dmi {  // the helpers dmi_context.h declares
 
 int fail(dmi_context *ctx, int code, const std::string &msg) {
   if (ctx)
@@ -203,52 +46,6 @@ int fail(dmi_context *ctx, int code, const std::string &msg) {
   else
     g_create_error = msg;
   return code;
-}
-
-// No C++ exception may cross the C ABI (the caller may be C, or C++ built with another runtime): every entry point
-// that can allocate on the host runs its body through this.
-template <typename Body>
-int guarded(dmi_context *ctx, const char *entry, Body &&body) noexcept {
-  try {
-    return body();
-  } catch (const std::bad_alloc &) {
-    try {
-      return fail(ctx, DMI_ERR_OUT_OF_MEMORY, std::string(entry) + ": host allocation failed");
-    } catch (...) {
-      return DMI_ERR_OUT_OF_MEMORY;
-    }
-  } catch (const std::exception &e) {
-    try {
-      return fail(ctx, DMI_ERR_STATE, std::string(entry) + ": " + e.what());
-    } catch (...) {
-      return DMI_ERR_STATE;
-    }
-  } catch (...) {
-    return DMI_ERR_STATE;
-  }
-}
-
-#define DMI_HIP(ctx, call)                                                                              \
-  do {                                                                                                  \
-    hipError_t e_ = (call);                                                                             \
-    if (e_ != hipSuccess) {                                                                             \
-      (void)hipGetLastError();                                                                          \
-      return fail(ctx, e_ == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE,              \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                                   \
-    }                                                                                                   \
-  } while (0)
-
-size_t grid_elem(const dmi_context *c) { return c->opt.grid_dtype == DMI_F64 ? 8 : 4; }
-size_t depth_elem(const dmi_context *c) { return c->depth_f64 ? 8 : 4; }
-
-bool bounded(double v) { return std::isfinite(v) && std::fabs(v) <= kMagnitudeLimit; }
-
-int classify_k(const double *K, const double *RT) {
-  for (int i = 0; i < 12; ++i)
-    if (!bounded(K[i]) || !bounded(RT[i])) return dmi::K_GENERAL;
-  const bool pinhole = K[3] == 0 && K[7] == 0 && K[11] == 0 && K[4] == 0 && K[8] == 0 && K[9] == 0 && K[10] == 1;
-  if (!pinhole) return dmi::K_GENERAL;
-  return K[1] == 0 ? dmi::K_PINHOLE : dmi::K_PINHOLE_SKEW;
 }
 
 int drain_events(dmi_context *ctx) {
@@ -267,6 +64,49 @@ int drain_events(dmi_context *ctx) {
   }
   ctx->pending.clear();
   return DMI_OK;
+}
+
+int flush_zero_fill(dmi_context *ctx) {
+  if (ctx->zero_fill_pending) {
+    DMI_HIP(ctx, hipMemsetAsync(ctx->d_grid, 0, ctx->n_voxels * grid_elem(ctx), ctx->stream));
+    ctx->zero_fill_pending = false;
+  }
+  return DMI_OK;
+}
+
+int ensure_buffer(dmi_context *ctx, DeviceBuffer &buffer, uint64_t bytes) {
+  if (buffer.ptr && buffer.capacity >= bytes) return DMI_OK;
+  if (buffer.ptr) {
+    DMI_HIP(ctx, hipFree(buffer.ptr));
+    ctx->device_bytes -= buffer.capacity;
+    buffer = DeviceBuffer{};
+  }
+  DMI_HIP(ctx, hipMalloc(&buffer.ptr, (size_t)bytes));
+  ctx->device_bytes += bytes;
+  buffer.capacity = bytes;
+  return DMI_OK;
+}
+
+int ensure_buffers(dmi_context *ctx, std::initializer_list<BufferNeed> needs) {
+  for (const BufferNeed &need : needs) {
+    const int rc = need.bytes ? ensure_buffer(ctx, *need.buffer, need.bytes) : DMI_OK;
+    if (rc != DMI_OK) return rc;
+  }
+  return DMI_OK;
+}
+
+}  // namespace dmi
+
+namespace {
+
+bool bounded(double v) { return std::isfinite(v) && std::fabs(v) <= kMagnitudeLimit; }
+
+int classify_k(const double *K, const double *RT) {
+  for (int i = 0; i < 12; ++i)
+    if (!bounded(K[i]) || !bounded(RT[i])) return dmi::K_GENERAL;
+  const bool pinhole = K[3] == 0 && K[7] == 0 && K[11] == 0 && K[4] == 0 && K[8] == 0 && K[9] == 0 && K[10] == 1;
+  if (!pinhole) return dmi::K_GENERAL;
+  return K[1] == 0 ? dmi::K_PINHOLE : dmi::K_PINHOLE_SKEW;
 }
 
 int ensure_stage(dmi_context *ctx, size_t elems, bool need_cost) {
@@ -837,14 +677,6 @@ int download_converted(dmi_context *ctx, HostT *dst) {
   return DMI_OK;
 }
 
-int flush_zero_fill(dmi_context *ctx) {
-  if (ctx->zero_fill_pending) {
-    DMI_HIP(ctx, hipMemsetAsync(ctx->d_grid, 0, ctx->n_voxels * grid_elem(ctx), ctx->stream));
-    ctx->zero_fill_pending = false;
-  }
-  return DMI_OK;
-}
-
 int sync_maps(dmi_context *ctx) {
   const size_t n = ctx->h_maps.size();
   if (ctx->d_maps_capacity < n) {
@@ -1072,27 +904,11 @@ void dmi_destroy(dmi_context *ctx) {
   if (ctx->d_stage_cost) (void)hipFree(ctx->d_stage_cost);
   if (ctx->d_convert) (void)hipFree(ctx->d_convert);
   if (ctx->d_lossy) (void)hipFree(ctx->d_lossy);
-  if (ctx->d_points) (void)hipFree(ctx->d_points);
-  if (ctx->c2p_start) (void)hipEventDestroy(ctx->c2p_start);
-  if (ctx->c2p_stop) (void)hipEventDestroy(ctx->c2p_stop);
-  if (ctx->d_mesh_counts) (void)hipFree(ctx->d_mesh_counts);
-  if (ctx->d_mesh_bases) (void)hipFree(ctx->d_mesh_bases);
-  if (ctx->d_mesh_scan_temp) (void)hipFree(ctx->d_mesh_scan_temp);
-  if (ctx->d_mesh_vertices) (void)hipFree(ctx->d_mesh_vertices);
-  if (ctx->d_mesh_triangles) (void)hipFree(ctx->d_mesh_triangles);
-  if (ctx->d_mesh_normals) (void)hipFree(ctx->d_mesh_normals);
-  for (hipEvent_t e : ctx->mesh_events)
-    if (e) (void)hipEventDestroy(e);
-  for (void *p : {(void *)ctx->d_mesh_alt_vertices, (void *)ctx->d_mesh_alt_triangles, (void *)ctx->d_mesh_alt_normals,
-                  (void *)ctx->d_mesh_region_id, (void *)ctx->d_mesh_region_size, (void *)ctx->d_comp_vertex_scratch,
-                  (void *)ctx->d_comp_triangle_scratch, (void *)ctx->d_comp_counters, ctx->d_comp_scan_temp})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ctx->comp_events)
-    if (e) (void)hipEventDestroy(e);
-  for (void *p : {(void *)ctx->d_smooth_vertices, (void *)ctx->d_smooth_keys, ctx->d_smooth_vertex_scratch, ctx->d_smooth_temp})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : ctx->smooth_events)
-    if (e) (void)hipEventDestroy(e);
+  ctx->c2p.release();
+  ctx->mesh.release();
+  ctx->extraction.release();
+  ctx->components.release();
+  ctx->smoothing.release();
   for (hipEvent_t e : ctx->slab_events) (void)hipEventDestroy(e);
   if (ctx->download_stream) (void)hipStreamDestroy(ctx->download_stream);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -1154,7 +970,7 @@ int dmi_reset_grid(dmi_context *ctx) {
     DMI_HIP(ctx, hipMemsetAsync(ctx->d_map_hits, 0, ctx->map_hits_capacity * sizeof(unsigned long long), ctx->stream));
   ctx->layer_is_zero.assign((size_t)ctx->grid.cell_dims[2], 1);
   ctx->grid_free_of_negative_zero = ctx->own_grid;
-  ctx->points_valid = false;
+  ctx->c2p.valid = false;
   return DMI_OK;
   });
 }
@@ -1173,7 +989,7 @@ int dmi_upload_grid(dmi_context *ctx, const double *grid) {
   }
   ctx->layer_is_zero.assign((size_t)ctx->grid.cell_dims[2], 0);
   ctx->grid_free_of_negative_zero = false;
-  ctx->points_valid = false;
+  ctx->c2p.valid = false;
   return DMI_OK;
   });
 }
@@ -1648,7 +1464,7 @@ int fuse_run(dmi_context *ctx, int32_t first, int32_t count, int32_t z_first, in
   // held (zeros after a reset): later fuses read the grid, which is correct either way
   for (int32_t z = z_first; z < z_first + z_count; ++z) ctx->layer_is_zero[(size_t)z] = 0;
   ctx->zero_fill_pending = false;
-  ctx->points_valid = false;
+  ctx->c2p.valid = false;
   if (ctx->pending.size() >= 256) return drain_events(ctx);
   return DMI_OK;
 }
@@ -1829,579 +1645,6 @@ int grid_pointer_for_sums(dmi_context *ctx, void **ptr) {
 }
 }  // namespace dmi
 }  // extern "C++"
-
-namespace {
-int64_t n_points(const dmi_context *c) {
-  return (int64_t)(c->grid.cell_dims[0] + 1) * (c->grid.cell_dims[1] + 1) * (c->grid.cell_dims[2] + 1);
-}
-int drain_c2p(dmi_context *ctx) {
-  if (!ctx->c2p_pending) return DMI_OK;
-  DMI_HIP(ctx, hipEventSynchronize(ctx->c2p_stop));
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->c2p_start, ctx->c2p_stop));
-  ctx->timings.last_cell_to_point_ms = ms;
-  ctx->c2p_pending = false;
-  return DMI_OK;
-}
-}  // namespace
-
-int dmi_cell_to_point(dmi_context *ctx) {
-  return guarded(ctx, "dmi_cell_to_point", [&]() -> int {
-  if (!ctx) return DMI_ERR_INVALID_ARGUMENT;
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  // an external grid can be changed by its owner (e.g. an all-reduce) without the context knowing: always recompute
-  if (ctx->points_valid && ctx->own_grid) return DMI_OK;
-  int rc = flush_zero_fill(ctx);
-  if (rc != DMI_OK) return rc;
-  rc = drain_c2p(ctx);
-  if (rc != DMI_OK) return rc;
-  if (!ctx->d_points) {
-    DMI_HIP(ctx, hipMalloc(&ctx->d_points, (size_t)n_points(ctx) * 8));
-    ctx->device_bytes += (uint64_t)n_points(ctx) * 8;
-  }
-  if (!ctx->c2p_start) {
-    DMI_HIP(ctx, hipEventCreate(&ctx->c2p_start));
-    DMI_HIP(ctx, hipEventCreate(&ctx->c2p_stop));
-  }
-  DMI_HIP(ctx, hipEventRecord(ctx->c2p_start, ctx->stream));
-  DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, ctx->d_points,
-                                         ctx->grid.cell_dims[0], ctx->grid.cell_dims[1], ctx->grid.cell_dims[2], ctx->stream));
-  DMI_HIP(ctx, hipEventRecord(ctx->c2p_stop, ctx->stream));
-  ctx->c2p_pending = true;
-  ctx->points_valid = true;
-  return DMI_OK;
-  });
-}
-
-int dmi_download_point_data_f64(dmi_context *ctx, double *out) {
-  return guarded(ctx, "dmi_download_point_data_f64", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_point_data_f64: null argument");
-  int rc = dmi_cell_to_point(ctx);
-  if (rc != DMI_OK) return rc;
-  DMI_HIP(ctx, hipMemcpyAsync(out, ctx->d_points, (size_t)n_points(ctx) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  rc = drain_c2p(ctx);
-  if (rc != DMI_OK) return rc;
-  return drain_events(ctx);
-  });
-}
-
-int dmi_point_data_device_pointer(dmi_context *ctx, void **ptr) {
-  return guarded(ctx, "dmi_point_data_device_pointer", [&]() -> int {
-  if (!ctx || !ptr) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_point_data_device_pointer: null argument");
-  int rc = dmi_cell_to_point(ctx);
-  if (rc != DMI_OK) return rc;
-  *ptr = ctx->d_points;
-  return DMI_OK;
-  });
-}
-
-int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t *cell_ids, uint64_t capacity) {
-  return guarded(ctx, "dmi_iso_active_cells", [&]() -> int {
-  if (!ctx || !count) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_iso_active_cells: null argument");
-  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_iso_active_cells: the iso-value is a NaN");
-  *count = 0;
-  int rc = dmi_cell_to_point(ctx);  // the contour filter reads the point data (Reconstruction/main.cxx:151-173)
-  if (rc != DMI_OK) return rc;
-  const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
-  const size_t n_blocks = dmi::iso_block_count(nx, ny, nz);
-  if (n_blocks >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_iso_active_cells: grid too large for one launch");
-  // scratch for this call: per-block counts (+ a trailing zero), their prefix sums, the scan's own storage, the ids
-  struct Scratch {
-    uint32_t *counts = nullptr;
-    uint64_t *bases = nullptr;
-    void *temp = nullptr;
-    int64_t *ids = nullptr;
-    ~Scratch() {
-      (void)hipFree(counts);
-      (void)hipFree(bases);
-      (void)hipFree(temp);
-      (void)hipFree(ids);
-    }
-  } sc;
-  size_t temp_bytes = 0;
-  DMI_HIP(ctx, dmi::launch_iso_count(nullptr, nx, ny, nz, iso, nullptr, nullptr, nullptr, &temp_bytes, ctx->stream));
-  DMI_HIP(ctx, hipMalloc(&sc.counts, (n_blocks + 1) * sizeof(uint32_t)));
-  DMI_HIP(ctx, hipMalloc(&sc.bases, (n_blocks + 1) * sizeof(uint64_t)));
-  DMI_HIP(ctx, hipMalloc(&sc.temp, std::max<size_t>(temp_bytes, 16)));
-  DMI_HIP(ctx, hipMemsetAsync(sc.counts + n_blocks, 0, sizeof(uint32_t), ctx->stream));
-  DMI_HIP(ctx, dmi::launch_iso_count(ctx->d_points, nx, ny, nz, iso, sc.counts, sc.bases, sc.temp, &temp_bytes, ctx->stream));
-  uint64_t total = 0;
-  DMI_HIP(ctx, hipMemcpyAsync(&total, sc.bases + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *count = total;
-  const uint64_t n_out = std::min<uint64_t>(total, cell_ids ? capacity : 0);
-  if (n_out > 0) {
-    DMI_HIP(ctx, hipMalloc(&sc.ids, (size_t)n_out * sizeof(int64_t)));
-    DMI_HIP(ctx, dmi::launch_iso_write(ctx->d_points, nx, ny, nz, iso, sc.bases, sc.ids, n_out, ctx->stream));
-    DMI_HIP(ctx, hipMemcpyAsync(cell_ids, sc.ids, (size_t)n_out * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  rc = drain_c2p(ctx);
-  if (rc != DMI_OK) return rc;
-  return drain_events(ctx);
-  });
-}
-
-namespace {
-// The normals' matrix: the cofactors of the grid matrix's upper-left 3 x 3 A, C[r][c] = A[r+1][c+1] A[r+2][c+2] -
-// A[r+1][c+2] A[r+2][c+1] (indices mod 3), negated when det A < 0: inverse(A)^T times |det A|, f64, row-major
-void normal_matrix(const double gm[16], double nm[9]) {
-  auto a = [&](int r, int c) { return gm[4 * (r % 3) + c % 3]; };
-  double cof[9];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) cof[3 * r + c] = a(r + 1, c + 1) * a(r + 2, c + 2) - a(r + 1, c + 2) * a(r + 2, c + 1);
-  const double det = a(0, 0) * cof[0] + a(0, 1) * cof[1] + a(0, 2) * cof[2];
-  for (int e = 0; e < 9; ++e) nm[e] = det < 0 ? -cof[e] : cof[e];
-}
-
-// grows a context-owned device buffer to hold `bytes`: the old contents are not kept
-int ensure_buffer(dmi_context *ctx, void **ptr, uint64_t *capacity, uint64_t bytes) {
-  if (*ptr && *capacity >= bytes) return DMI_OK;
-  if (*ptr) {
-    DMI_HIP(ctx, hipFree(*ptr));
-    ctx->device_bytes -= *capacity;
-    *ptr = nullptr;
-    *capacity = 0;
-  }
-  DMI_HIP(ctx, hipMalloc(ptr, (size_t)bytes));
-  ctx->device_bytes += bytes;
-  *capacity = bytes;
-  return DMI_OK;
-}
-}  // namespace
-
-namespace {
-// dmi_extract_isosurface, and with `normals` dmi_extract_isosurface_normals (`entry` names the call in the errors)
-int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, uint64_t *n_vertices, uint64_t *n_triangles,
-                       bool normals) {
-  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
-  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the iso-value is a NaN");
-  if (ctx->opt.z_first != 0)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the context holds a z-slab (z_first != 0); its lattice is not the grid's");
-  *n_vertices = *n_triangles = 0;
-  ctx->mesh_valid = false;
-  ctx->mesh_has_normals = false;
-  ctx->mesh_filtered = false;
-  const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
-  const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
-  if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": grid too large for one launch");
-  int rc = dmi_cell_to_point(ctx);  // the contour filter reads the point data (Reconstruction/main.cxx:151-173)
-  if (rc != DMI_OK) return rc;
-  dmi::MeshGeom g{};
-  g.nx = nx;
-  g.ny = ny;
-  g.nz = nz;
-  g.segs_per_row = (int)((nx + 1 + 255) / 256);
-  g.iso = iso;
-  for (int a = 0; a < 3; ++a) {
-    g.origin[a] = ctx->grid.origin[a];
-    g.spacing[a] = ctx->grid.spacing[a];
-  }
-  for (int e = 0; e < 12; ++e) g.m[e] = ctx->grid.grid_matrix[e];
-  uint64_t cap = ctx->mesh_segments_capacity;
-  if (cap < n_seg + 1) {
-    uint64_t c32 = cap * 2 * sizeof(uint32_t), c64 = cap * 2 * sizeof(uint64_t);
-    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_counts, &c32, (uint64_t)(n_seg + 1) * 2 * sizeof(uint32_t));
-    if (rc != DMI_OK) return rc;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_bases, &c64, (uint64_t)(n_seg + 1) * 2 * sizeof(uint64_t));
-    if (rc != DMI_OK) return rc;
-    ctx->mesh_segments_capacity = n_seg + 1;
-  }
-  size_t temp_bytes = 0;
-  DMI_HIP(ctx, dmi::launch_isosurface_count(nullptr, g, ctx->d_mesh_counts, ctx->d_mesh_bases, nullptr, &temp_bytes, ctx->stream));
-  rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_scan_temp, &ctx->mesh_scan_temp_capacity, std::max<uint64_t>(temp_bytes, 16));
-  if (rc != DMI_OK) return rc;
-  temp_bytes = std::max<size_t>(temp_bytes, 16);
-  if (!ctx->mesh_events[0])
-    for (hipEvent_t &e : ctx->mesh_events) DMI_HIP(ctx, hipEventCreate(&e));
-  // the trailing zeros behind each count array: bases[n_seg] and bases[2 n_seg + 1] become the totals
-  DMI_HIP(ctx, hipMemsetAsync(ctx->d_mesh_counts + n_seg, 0, sizeof(uint32_t), ctx->stream));
-  DMI_HIP(ctx, hipMemsetAsync(ctx->d_mesh_counts + 2 * n_seg + 1, 0, sizeof(uint32_t), ctx->stream));
-  DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[0], ctx->stream));
-  DMI_HIP(ctx, dmi::launch_isosurface_count(ctx->d_points, g, ctx->d_mesh_counts, ctx->d_mesh_bases, ctx->d_mesh_scan_temp,
-                                            &temp_bytes, ctx->stream));
-  DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[1], ctx->stream));
-  uint64_t totals[2] = {0, 0};
-  DMI_HIP(ctx, hipMemcpyAsync(&totals[0], ctx->d_mesh_bases + n_seg, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipMemcpyAsync(&totals[1], ctx->d_mesh_bases + 2 * n_seg + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  // vertex and triangle ids are int64 (vtkIdType) and the buffers' byte sizes must fit a size_t: refused, never wrapped
-  const uint64_t id_limit = (uint64_t)std::numeric_limits<int64_t>::max() / 24;
-  if (totals[0] > id_limit || totals[1] > id_limit)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for int64 ids");
-  g.n_vertices = totals[0];
-  g.n_triangles = totals[1];
-  float ms_count = 0.f, ms_write = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms_count, ctx->mesh_events[0], ctx->mesh_events[1]));
-  if (totals[0] > 0) {
-    uint64_t vcap = ctx->mesh_vertex_capacity * 24, tcap = ctx->mesh_triangle_capacity * 24;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_vertices, &vcap, totals[0] * 24);
-    if (rc != DMI_OK) return rc;
-    ctx->mesh_vertex_capacity = vcap / 24;
-    if (totals[1] > 0) {
-      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_triangles, &tcap, totals[1] * 24);
-      if (rc != DMI_OK) return rc;
-      ctx->mesh_triangle_capacity = tcap / 24;
-    }
-    dmi::MeshNormals nrm{};
-    if (normals) {
-      uint64_t ncap = ctx->mesh_normal_capacity * 12;
-      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_normals, &ncap, totals[0] * 12);
-      if (rc != DMI_OK) return rc;
-      ctx->mesh_normal_capacity = ncap / 12;
-      normal_matrix(ctx->grid.grid_matrix, nrm.nm);
-      nrm.normals = ctx->d_mesh_normals;
-    }
-    DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[2], ctx->stream));
-    DMI_HIP(ctx, dmi::launch_isosurface_write(ctx->d_points, g, ctx->d_mesh_bases, ctx->d_mesh_vertices, ctx->d_mesh_triangles,
-                                              normals ? &nrm : nullptr, ctx->stream));
-    DMI_HIP(ctx, hipEventRecord(ctx->mesh_events[3], ctx->stream));
-    DMI_HIP(ctx, hipEventSynchronize(ctx->mesh_events[3]));
-    DMI_HIP(ctx, hipEventElapsedTime(&ms_write, ctx->mesh_events[2], ctx->mesh_events[3]));
-  }
-  ctx->last_isosurface_kernel_ms = (double)ms_count + (double)ms_write;
-  ctx->mesh_vertices = totals[0];
-  ctx->mesh_triangles = totals[1];
-  ctx->mesh_valid = true;
-  ctx->mesh_has_normals = normals;
-  *n_vertices = totals[0];
-  *n_triangles = totals[1];
-  rc = drain_c2p(ctx);
-  if (rc != DMI_OK) return rc;
-  return drain_events(ctx);
-}
-}  // namespace
-
-int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
-  return guarded(ctx, "dmi_extract_isosurface", [&]() -> int {
-    return extract_isosurface(ctx, "dmi_extract_isosurface", iso, n_vertices, n_triangles, false);
-  });
-}
-
-int dmi_extract_isosurface_normals(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
-  return guarded(ctx, "dmi_extract_isosurface_normals", [&]() -> int {
-    return extract_isosurface(ctx, "dmi_extract_isosurface_normals", iso, n_vertices, n_triangles, true);
-  });
-}
-
-int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangles) {
-  return guarded(ctx, "dmi_download_isosurface", [&]() -> int {
-  if (!ctx || !vertices || !triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: null argument");
-  if (!ctx->mesh_valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: no mesh (dmi_extract_isosurface has not succeeded)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (ctx->mesh_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(vertices, ctx->d_mesh_vertices, (size_t)ctx->mesh_vertices * 24, hipMemcpyDeviceToHost, ctx->stream));
-  if (ctx->mesh_triangles)
-    DMI_HIP(ctx, hipMemcpyAsync(triangles, ctx->d_mesh_triangles, (size_t)ctx->mesh_triangles * 24, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
-  });
-}
-
-int dmi_download_isosurface_normals(dmi_context *ctx, float *normals) {
-  return guarded(ctx, "dmi_download_isosurface_normals", [&]() -> int {
-  if (!ctx || !normals) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: null argument");
-  if (!ctx->mesh_valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: no mesh (no extraction has succeeded)");
-  if (!ctx->mesh_has_normals)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
-                "dmi_download_isosurface_normals: the last mesh has no normals (dmi_extract_isosurface, not dmi_extract_isosurface_normals)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (ctx->mesh_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(normals, ctx->d_mesh_normals, (size_t)ctx->mesh_vertices * 12, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
-  });
-}
-
-int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_kernel_ms: null argument");
-  *last = ctx->last_isosurface_kernel_ms;
-  return DMI_OK;
-  });
-}
-
-int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
-                                     uint64_t *n_components, uint64_t *n_components_kept) {
-  return guarded(ctx, "dmi_filter_isosurface_components", [&]() -> int {
-  const std::string entry = "dmi_filter_isosurface_components";
-  if (!ctx || !n_vertices || !n_triangles || !n_components || !n_components_kept)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
-  if (mode != DMI_COMPONENTS_MIN_TRIANGLES && mode != DMI_COMPONENTS_LARGEST)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": unknown mode " + std::to_string(mode));
-  if (!ctx->mesh_valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
-  *n_vertices = *n_triangles = *n_components = *n_components_kept = 0;
-  const uint64_t nv = ctx->mesh_vertices, nt = ctx->mesh_triangles;
-  // labels and sizes are u32: refused, never wrapped (as the extraction refuses what its int64 ids cannot hold)
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit component labels");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (nv == 0) {  // an empty mesh stays empty
-    ctx->mesh_filtered = true;
-    ctx->mesh_regions = 0;
-    ctx->last_filter_kernel_ms = 0.0;
-    for (double &p : ctx->last_filter_pass_ms) p = 0.0;
-    ctx->last_filter_cas_retries = 0;
-    return DMI_OK;
-  }
-  const bool normals = ctx->mesh_has_normals;
-  int rc;
-  {
-    uint64_t cap = ctx->mesh_alt_vertex_capacity * 24;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_vertices, &cap, nv * 24);
-    if (rc != DMI_OK) return rc;
-    ctx->mesh_alt_vertex_capacity = cap / 24;
-    cap = ctx->mesh_alt_triangle_capacity * 24;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_triangles, &cap, std::max<uint64_t>(nt, 1) * 24);
-    if (rc != DMI_OK) return rc;
-    ctx->mesh_alt_triangle_capacity = cap / 24;
-    if (normals) {
-      cap = ctx->mesh_alt_normal_capacity * 12;
-      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_normals, &cap, nv * 12);
-      if (rc != DMI_OK) return rc;
-      ctx->mesh_alt_normal_capacity = cap / 12;
-    }
-    if (ctx->mesh_region_capacity < nv) {
-      uint64_t a = ctx->mesh_region_capacity * 8, b = a;
-      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_region_id, &a, nv * 8);
-      if (rc != DMI_OK) return rc;
-      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_region_size, &b, nv * 8);
-      if (rc != DMI_OK) return rc;
-      ctx->mesh_region_capacity = nv;
-    }
-    cap = ctx->comp_vertex_capacity ? (ctx->comp_vertex_capacity + 1) * 16 : 0;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_comp_vertex_scratch, &cap, (nv + 1) * 16);
-    if (rc != DMI_OK) return rc;
-    ctx->comp_vertex_capacity = cap / 16 - 1;
-    cap = ctx->comp_triangle_capacity ? (ctx->comp_triangle_capacity + 1) * 4 : 0;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_comp_triangle_scratch, &cap, (nt + 1) * 4);
-    if (rc != DMI_OK) return rc;
-    ctx->comp_triangle_capacity = cap / 4 - 1;
-    cap = ctx->d_comp_counters ? 24 : 0;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_comp_counters, &cap, 24);
-    if (rc != DMI_OK) return rc;
-  }
-  size_t temp_bytes = 0;
-  DMI_HIP(ctx, dmi::components_scan_temp_bytes(nv, nt, &temp_bytes));
-  temp_bytes = std::max<size_t>(temp_bytes, 16);
-  rc = ensure_buffer(ctx, (void **)&ctx->d_comp_scan_temp, &ctx->comp_scan_temp_capacity, temp_bytes);
-  if (rc != DMI_OK) return rc;
-  if (!ctx->comp_events[0])
-    for (hipEvent_t &e : ctx->comp_events) DMI_HIP(ctx, hipEventCreate(&e));
-  dmi::ComponentsMesh m{};
-  m.n_vertices = nv;
-  m.n_triangles = nt;
-  m.vertices = ctx->d_mesh_vertices;
-  m.normals = normals ? ctx->d_mesh_normals : nullptr;
-  m.triangles = ctx->d_mesh_triangles;
-  m.out_vertices = ctx->d_mesh_alt_vertices;
-  m.out_normals = ctx->d_mesh_alt_normals;
-  m.out_triangles = ctx->d_mesh_alt_triangles;
-  m.region_id = ctx->d_mesh_region_id;
-  m.region_size = ctx->d_mesh_region_size;
-  dmi::ComponentsScratch s{};
-  uint32_t *vs = ctx->d_comp_vertex_scratch;
-  s.parent = vs;
-  s.size = vs + (nv + 1);
-  s.vmap = vs + 2 * (nv + 1);
-  s.rmap = vs + 3 * (nv + 1);
-  s.tmap = ctx->d_comp_triangle_scratch;
-  s.counters = ctx->d_comp_counters;
-  s.scan_temp = ctx->d_comp_scan_temp;
-  s.scan_temp_bytes = temp_bytes;
-  // (a failure from here on leaves the context's mesh and its regions as they were: the buffers are swapped only at the end)
-  DMI_HIP(ctx, dmi::launch_isosurface_components(m, s, mode == DMI_COMPONENTS_LARGEST ? 1 : 0, min_triangles, ctx->comp_events, ctx->stream));
-  uint32_t kept[3] = {0, 0, 0};
-  unsigned long long counters[3] = {0, 0, 0};
-  DMI_HIP(ctx, hipMemcpyAsync(&kept[0], s.vmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipMemcpyAsync(&kept[1], s.tmap + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipMemcpyAsync(&kept[2], s.rmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipMemcpyAsync(counters, s.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->comp_events[0], ctx->comp_events[4]));
-  ctx->last_filter_kernel_ms = (double)ms;
-  for (int p = 0; p < 4; ++p) {
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->comp_events[p], ctx->comp_events[p + 1]));
-    ctx->last_filter_pass_ms[p] = (double)ms;
-  }
-  // the compacted mesh becomes the context's mesh; the buffers it came from are the next filter's output
-  std::swap(ctx->d_mesh_vertices, ctx->d_mesh_alt_vertices);
-  std::swap(ctx->mesh_vertex_capacity, ctx->mesh_alt_vertex_capacity);
-  std::swap(ctx->d_mesh_triangles, ctx->d_mesh_alt_triangles);
-  std::swap(ctx->mesh_triangle_capacity, ctx->mesh_alt_triangle_capacity);
-  if (normals) {
-    std::swap(ctx->d_mesh_normals, ctx->d_mesh_alt_normals);
-    std::swap(ctx->mesh_normal_capacity, ctx->mesh_alt_normal_capacity);
-  }
-  ctx->mesh_vertices = kept[0];
-  ctx->mesh_triangles = kept[1];
-  ctx->mesh_regions = kept[2];
-  ctx->mesh_filtered = true;
-  ctx->last_filter_cas_retries = counters[2];
-  *n_vertices = kept[0];
-  *n_triangles = kept[1];
-  *n_components = counters[1];
-  *n_components_kept = kept[2];
-  return DMI_OK;
-  });
-}
-
-int dmi_download_isosurface_regions(dmi_context *ctx, int64_t *region_id, int64_t *region_size) {
-  return guarded(ctx, "dmi_download_isosurface_regions", [&]() -> int {
-  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: null argument");
-  if (!ctx->mesh_valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: no mesh (no extraction has succeeded)");
-  if (!ctx->mesh_filtered)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
-                "dmi_download_isosurface_regions: no regions (dmi_filter_isosurface_components has not run since the last extraction)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (region_id && ctx->mesh_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(region_id, ctx->d_mesh_region_id, (size_t)ctx->mesh_vertices * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (region_size && ctx->mesh_regions)
-    DMI_HIP(ctx, hipMemcpyAsync(region_size, ctx->d_mesh_region_size, (size_t)ctx->mesh_regions * 8, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
-  });
-}
-
-int dmi_get_isosurface_filter_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_filter_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_kernel_ms: null argument");
-  *last = ctx->last_filter_kernel_ms;
-  return DMI_OK;
-  });
-}
-
-int dmi_get_isosurface_filter_pass_ms(dmi_context *ctx, double out[4]) {
-  return guarded(ctx, "dmi_get_isosurface_filter_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_pass_ms: null argument");
-  for (int p = 0; p < 4; ++p) out[p] = ctx->last_filter_pass_ms[p];
-  return DMI_OK;
-  });
-}
-
-int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last) {
-  return guarded(ctx, "dmi_get_isosurface_filter_cas_retries", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_cas_retries: null argument");
-  *last = ctx->last_filter_cas_retries;
-  return DMI_OK;
-  });
-}
-
-int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, double mu) {
-  return guarded(ctx, "dmi_smooth_isosurface", [&]() -> int {
-  const std::string entry = "dmi_smooth_isosurface";
-  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
-  if (iterations < 0 || iterations > 1000)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": iterations " + std::to_string(iterations) + " is not in [0, 1000]");
-  if (!(lambda > 0.0 && lambda <= 1.0)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": lambda is not in (0, 1]");
-  if (!(mu <= 0.0) || mu - mu != 0.0) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mu is not a finite number <= 0");
-  if (!ctx->mesh_valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
-  const uint64_t nv = ctx->mesh_vertices, nt = ctx->mesh_triangles;
-  // ids are u32 on the device, and so are the offsets into the 6 T directed edges: refused, never wrapped
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
-  if (6 * nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit adjacency offsets (6 x triangles >= 2^32)");
-  if (iterations == 0 || nv == 0) {  // nothing to do: the mesh, its normals included, stays as it is
-    ctx->last_smooth_kernel_ms = 0.0;
-    for (double &p : ctx->last_smooth_pass_ms) p = 0.0;
-    return DMI_OK;
-  }
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  const bool normals = ctx->mesh_has_normals;
-  const uint64_t fixed_words = (nv + 63) / 64;
-  int rc;
-  {
-    uint64_t cap = ctx->mesh_alt_vertex_capacity * 24;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_vertices, &cap, nv * 24);
-    if (rc != DMI_OK) return rc;
-    ctx->mesh_alt_vertex_capacity = cap / 24;
-    cap = ctx->smooth_vertex_capacity * 24;
-    rc = ensure_buffer(ctx, (void **)&ctx->d_smooth_vertices, &cap, nv * 24);
-    if (rc != DMI_OK) return rc;
-    ctx->smooth_vertex_capacity = cap / 24;
-    if (normals) {
-      cap = ctx->mesh_alt_normal_capacity * 12;
-      rc = ensure_buffer(ctx, (void **)&ctx->d_mesh_alt_normals, &cap, nv * 12);
-      if (rc != DMI_OK) return rc;
-      ctx->mesh_alt_normal_capacity = cap / 12;
-    }
-    rc = ensure_buffer(ctx, (void **)&ctx->d_smooth_keys, &ctx->smooth_keys_capacity, 2 * std::max<uint64_t>(6 * nt, 2) * 8);
-    if (rc != DMI_OK) return rc;
-    rc = ensure_buffer(ctx, &ctx->d_smooth_vertex_scratch, &ctx->smooth_vertex_scratch_capacity, fixed_words * 8 + 3 * (nv + 1) * 4);
-    if (rc != DMI_OK) return rc;
-  }
-  size_t temp_bytes = 0;
-  DMI_HIP(ctx, dmi::smooth_temp_bytes(nv, nt, &temp_bytes));
-  temp_bytes = std::max<size_t>(temp_bytes, 16);
-  rc = ensure_buffer(ctx, &ctx->d_smooth_temp, &ctx->smooth_temp_capacity, temp_bytes);
-  if (rc != DMI_OK) return rc;
-  if (!ctx->smooth_events[0])
-    for (hipEvent_t &e : ctx->smooth_events) DMI_HIP(ctx, hipEventCreate(&e));
-  dmi::SmoothMesh m{};
-  m.n_vertices = nv;
-  m.n_triangles = nt;
-  m.vertices = ctx->d_mesh_vertices;
-  m.triangles = ctx->d_mesh_triangles;
-  m.normals_out = normals ? ctx->d_mesh_alt_normals : nullptr;
-  dmi::SmoothScratch s{};
-  s.keys[0] = ctx->d_smooth_keys;
-  s.keys[1] = ctx->d_smooth_keys + std::max<uint64_t>(6 * nt, 2);
-  s.fixed = (unsigned long long *)ctx->d_smooth_vertex_scratch;
-  s.row_start = (uint32_t *)(s.fixed + fixed_words);
-  s.valence = s.row_start + (nv + 1);
-  s.offsets = s.valence + (nv + 1);
-  s.positions[0] = ctx->d_mesh_alt_vertices;
-  s.positions[1] = ctx->d_smooth_vertices;
-  s.temp = ctx->d_smooth_temp;
-  s.temp_bytes = temp_bytes;
-  // (a failure from here on leaves the context's mesh as it was: no kernel writes it, and the buffers are swapped only at the end)
-  double *result = nullptr;
-  DMI_HIP(ctx, dmi::launch_isosurface_smooth(m, s, iterations, lambda, mu, &result, ctx->smooth_events, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->smooth_events[0], ctx->smooth_events[3]));
-  ctx->last_smooth_kernel_ms = (double)ms;
-  for (int p = 0; p < 3; ++p) {
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->smooth_events[p], ctx->smooth_events[p + 1]));
-    ctx->last_smooth_pass_ms[p] = (double)ms;
-  }
-  // the smoothed positions become the context's; the buffer they replace is the next call's scratch
-  if (result == ctx->d_mesh_alt_vertices) {
-    std::swap(ctx->d_mesh_vertices, ctx->d_mesh_alt_vertices);
-    std::swap(ctx->mesh_vertex_capacity, ctx->mesh_alt_vertex_capacity);
-  } else {
-    std::swap(ctx->d_mesh_vertices, ctx->d_smooth_vertices);
-    std::swap(ctx->mesh_vertex_capacity, ctx->smooth_vertex_capacity);
-  }
-  if (normals) {
-    std::swap(ctx->d_mesh_normals, ctx->d_mesh_alt_normals);
-    std::swap(ctx->mesh_normal_capacity, ctx->mesh_alt_normal_capacity);
-  }
-  return DMI_OK;
-  });
-}
-
-int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_smooth_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_kernel_ms: null argument");
-  *last = ctx->last_smooth_kernel_ms;
-  return DMI_OK;
-  });
-}
-
-int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]) {
-  return guarded(ctx, "dmi_get_isosurface_smooth_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_pass_ms: null argument");
-  for (int p = 0; p < 3; ++p) out[p] = ctx->last_smooth_pass_ms[p];
-  return DMI_OK;
-  });
-}
 
 int dmi_get_brick_class_histogram(dmi_context *ctx, uint64_t out[4]) {
   return guarded(ctx, "dmi_get_brick_class_histogram", [&]() -> int {

@@ -1,0 +1,508 @@
+// dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
+// (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
+// filter, the smoother and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
+#include "dmi_context.h"
+
+#include <algorithm>
+#include <limits>
+
+using dmi::drain_c2p;
+using dmi::drain_events;
+using dmi::ensure_buffer;
+using dmi::ensure_buffers;
+using dmi::fail;
+using dmi::flush_zero_fill;
+using dmi::guarded;
+
+namespace {
+// bytes per vertex (3 f64), per triangle (3 int64 ids) and per normal (3 f32) of the mesh buffers
+constexpr uint64_t kVertexBytes = 3 * sizeof(double), kTriangleBytes = 3 * sizeof(int64_t), kNormalBytes = 3 * sizeof(float);
+
+int64_t n_points(const dmi_context *c) {
+  return (int64_t)(c->grid.cell_dims[0] + 1) * (c->grid.cell_dims[1] + 1) * (c->grid.cell_dims[2] + 1);
+}
+}  // namespace
+
+int dmi::drain_c2p(dmi_context *ctx) {
+  if (!ctx->c2p.pending) return DMI_OK;
+  DMI_HIP(ctx, hipEventSynchronize(ctx->c2p.events[1]));
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->c2p.events[0], ctx->c2p.events[1]));
+  ctx->timings.last_cell_to_point_ms = ms;
+  ctx->c2p.pending = false;
+  return DMI_OK;
+}
+
+extern "C" {
+
+int dmi_cell_to_point(dmi_context *ctx) {
+  return guarded(ctx, "dmi_cell_to_point", [&]() -> int {
+  if (!ctx) return DMI_ERR_INVALID_ARGUMENT;
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  // an external grid can be changed by its owner (e.g. an all-reduce) without the context knowing: always recompute
+  if (ctx->c2p.valid && ctx->own_grid) return DMI_OK;
+  int rc = flush_zero_fill(ctx);
+  if (rc != DMI_OK) return rc;
+  rc = drain_c2p(ctx);
+  if (rc != DMI_OK) return rc;
+  rc = ensure_buffer(ctx, ctx->c2p.points, (uint64_t)n_points(ctx) * 8);
+  if (rc != DMI_OK) return rc;
+  if (!ctx->c2p.events[0])
+    for (hipEvent_t &e : ctx->c2p.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[0], ctx->stream));
+  DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, ctx->c2p.points.as<double>(),
+                                         ctx->grid.cell_dims[0], ctx->grid.cell_dims[1], ctx->grid.cell_dims[2], ctx->stream));
+  DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[1], ctx->stream));
+  ctx->c2p.pending = true;
+  ctx->c2p.valid = true;
+  return DMI_OK;
+  });
+}
+
+int dmi_download_point_data_f64(dmi_context *ctx, double *out) {
+  return guarded(ctx, "dmi_download_point_data_f64", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_point_data_f64: null argument");
+  int rc = dmi_cell_to_point(ctx);
+  if (rc != DMI_OK) return rc;
+  DMI_HIP(ctx, hipMemcpyAsync(out, ctx->c2p.points.ptr, (size_t)n_points(ctx) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  rc = drain_c2p(ctx);
+  if (rc != DMI_OK) return rc;
+  return drain_events(ctx);
+  });
+}
+
+int dmi_point_data_device_pointer(dmi_context *ctx, void **ptr) {
+  return guarded(ctx, "dmi_point_data_device_pointer", [&]() -> int {
+  if (!ctx || !ptr) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_point_data_device_pointer: null argument");
+  int rc = dmi_cell_to_point(ctx);
+  if (rc != DMI_OK) return rc;
+  *ptr = ctx->c2p.points.ptr;
+  return DMI_OK;
+  });
+}
+
+int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t *cell_ids, uint64_t capacity) {
+  return guarded(ctx, "dmi_iso_active_cells", [&]() -> int {
+  if (!ctx || !count) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_iso_active_cells: null argument");
+  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_iso_active_cells: the iso-value is a NaN");
+  *count = 0;
+  int rc = dmi_cell_to_point(ctx);  // the contour filter reads the point data (Reconstruction/main.cxx:151-173)
+  if (rc != DMI_OK) return rc;
+  const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
+  const size_t n_blocks = dmi::iso_block_count(nx, ny, nz);
+  if (n_blocks >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_iso_active_cells: grid too large for one launch");
+  // scratch for this call: per-block counts (+ a trailing zero), their prefix sums, the scan's own storage, the ids
+  struct Scratch {
+    uint32_t *counts = nullptr;
+    uint64_t *bases = nullptr;
+    void *temp = nullptr;
+    int64_t *ids = nullptr;
+    ~Scratch() {
+      (void)hipFree(counts);
+      (void)hipFree(bases);
+      (void)hipFree(temp);
+      (void)hipFree(ids);
+    }
+  } sc;
+  const double *points = ctx->c2p.points.as<double>();
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::launch_iso_count(nullptr, nx, ny, nz, iso, nullptr, nullptr, nullptr, &temp_bytes, ctx->stream));
+  DMI_HIP(ctx, hipMalloc(&sc.counts, (n_blocks + 1) * sizeof(uint32_t)));
+  DMI_HIP(ctx, hipMalloc(&sc.bases, (n_blocks + 1) * sizeof(uint64_t)));
+  DMI_HIP(ctx, hipMalloc(&sc.temp, std::max<size_t>(temp_bytes, 16)));
+  DMI_HIP(ctx, hipMemsetAsync(sc.counts + n_blocks, 0, sizeof(uint32_t), ctx->stream));
+  DMI_HIP(ctx, dmi::launch_iso_count(points, nx, ny, nz, iso, sc.counts, sc.bases, sc.temp, &temp_bytes, ctx->stream));
+  uint64_t total = 0;
+  DMI_HIP(ctx, hipMemcpyAsync(&total, sc.bases + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *count = total;
+  const uint64_t n_out = std::min<uint64_t>(total, cell_ids ? capacity : 0);
+  if (n_out > 0) {
+    DMI_HIP(ctx, hipMalloc(&sc.ids, (size_t)n_out * sizeof(int64_t)));
+    DMI_HIP(ctx, dmi::launch_iso_write(points, nx, ny, nz, iso, sc.bases, sc.ids, n_out, ctx->stream));
+    DMI_HIP(ctx, hipMemcpyAsync(cell_ids, sc.ids, (size_t)n_out * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  rc = drain_c2p(ctx);
+  if (rc != DMI_OK) return rc;
+  return drain_events(ctx);
+  });
+}
+
+namespace {
+// The normals' matrix: the cofactors of the grid matrix's upper-left 3 x 3 A, C[r][c] = A[r+1][c+1] A[r+2][c+2] -
+// A[r+1][c+2] A[r+2][c+1] (indices mod 3), negated when det A < 0: inverse(A)^T times |det A|, f64, row-major
+void normal_matrix(const double gm[16], double nm[9]) {
+  auto a = [&](int r, int c) { return gm[4 * (r % 3) + c % 3]; };
+  double cof[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) cof[3 * r + c] = a(r + 1, c + 1) * a(r + 2, c + 2) - a(r + 1, c + 2) * a(r + 2, c + 1);
+  const double det = a(0, 0) * cof[0] + a(0, 1) * cof[1] + a(0, 2) * cof[2];
+  for (int e = 0; e < 9; ++e) nm[e] = det < 0 ? -cof[e] : cof[e];
+}
+
+// dmi_extract_isosurface, and with `normals` dmi_extract_isosurface_normals (`entry` names the call in the errors)
+int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, uint64_t *n_vertices, uint64_t *n_triangles,
+                       bool normals) {
+  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (iso != iso) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the iso-value is a NaN");
+  if (ctx->opt.z_first != 0)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the context holds a z-slab (z_first != 0); its lattice is not the grid's");
+  *n_vertices = *n_triangles = 0;
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Extraction &ex = ctx->extraction;
+  mesh.valid = false;
+  mesh.has_normals = false;
+  mesh.filtered = false;
+  const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
+  const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
+  if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": grid too large for one launch");
+  int rc = dmi_cell_to_point(ctx);  // the contour filter reads the point data (Reconstruction/main.cxx:151-173)
+  if (rc != DMI_OK) return rc;
+  dmi::MeshGeom g{};
+  g.nx = nx;
+  g.ny = ny;
+  g.nz = nz;
+  g.segs_per_row = (int)((nx + 1 + 255) / 256);
+  g.iso = iso;
+  for (int a = 0; a < 3; ++a) {
+    g.origin[a] = ctx->grid.origin[a];
+    g.spacing[a] = ctx->grid.spacing[a];
+  }
+  for (int e = 0; e < 12; ++e) g.m[e] = ctx->grid.grid_matrix[e];
+  // two count arrays and two base arrays (vertices, triangles) of n_seg entries and a trailing total each
+  rc = ensure_buffers(ctx, {{&ex.counts, (uint64_t)(n_seg + 1) * 2 * sizeof(uint32_t)}, {&ex.bases, (uint64_t)(n_seg + 1) * 2 * sizeof(uint64_t)}});
+  if (rc != DMI_OK) return rc;
+  uint32_t *counts = ex.counts.as<uint32_t>();
+  uint64_t *bases = ex.bases.as<uint64_t>();
+  const double *points = ctx->c2p.points.as<double>();
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::launch_isosurface_count(nullptr, g, counts, bases, nullptr, &temp_bytes, ctx->stream));
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  rc = ensure_buffer(ctx, ex.scan_temp, temp_bytes);
+  if (rc != DMI_OK) return rc;
+  if (!ex.events[0])
+    for (hipEvent_t &e : ex.events) DMI_HIP(ctx, hipEventCreate(&e));
+  // the trailing zeros behind each count array: bases[n_seg] and bases[2 n_seg + 1] become the totals
+  DMI_HIP(ctx, hipMemsetAsync(counts + n_seg, 0, sizeof(uint32_t), ctx->stream));
+  DMI_HIP(ctx, hipMemsetAsync(counts + 2 * n_seg + 1, 0, sizeof(uint32_t), ctx->stream));
+  DMI_HIP(ctx, hipEventRecord(ex.events[0], ctx->stream));
+  DMI_HIP(ctx, dmi::launch_isosurface_count(points, g, counts, bases, ex.scan_temp.ptr, &temp_bytes, ctx->stream));
+  DMI_HIP(ctx, hipEventRecord(ex.events[1], ctx->stream));
+  uint64_t totals[2] = {0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&totals[0], bases + n_seg, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&totals[1], bases + 2 * n_seg + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // vertex and triangle ids are int64 (vtkIdType) and the buffers' byte sizes must fit a size_t: refused, never wrapped
+  const uint64_t id_limit = (uint64_t)std::numeric_limits<int64_t>::max() / kVertexBytes;
+  if (totals[0] > id_limit || totals[1] > id_limit)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for int64 ids");
+  g.n_vertices = totals[0];
+  g.n_triangles = totals[1];
+  float ms_count = 0.f, ms_write = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms_count, ex.events[0], ex.events[1]));
+  if (totals[0] > 0) {
+    rc = ensure_buffers(ctx, {{&mesh.vertices, totals[0] * kVertexBytes}, {&mesh.triangles, totals[1] * kTriangleBytes},
+                              {&mesh.normals, normals ? totals[0] * kNormalBytes : 0}});
+    if (rc != DMI_OK) return rc;
+    dmi::MeshNormals nrm{};
+    if (normals) {
+      normal_matrix(ctx->grid.grid_matrix, nrm.nm);
+      nrm.normals = mesh.normals.as<float>();
+    }
+    DMI_HIP(ctx, hipEventRecord(ex.events[2], ctx->stream));
+    DMI_HIP(ctx, dmi::launch_isosurface_write(points, g, bases, mesh.vertices.as<double>(), mesh.triangles.as<int64_t>(),
+                                              normals ? &nrm : nullptr, ctx->stream));
+    DMI_HIP(ctx, hipEventRecord(ex.events[3], ctx->stream));
+    DMI_HIP(ctx, hipEventSynchronize(ex.events[3]));
+    DMI_HIP(ctx, hipEventElapsedTime(&ms_write, ex.events[2], ex.events[3]));
+  }
+  ex.last_kernel_ms = (double)ms_count + (double)ms_write;
+  mesh.n_vertices = totals[0];
+  mesh.n_triangles = totals[1];
+  mesh.valid = true;
+  mesh.has_normals = normals;
+  *n_vertices = totals[0];
+  *n_triangles = totals[1];
+  rc = drain_c2p(ctx);
+  if (rc != DMI_OK) return rc;
+  return drain_events(ctx);
+}
+}  // namespace
+
+int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_extract_isosurface", [&]() -> int {
+    return extract_isosurface(ctx, "dmi_extract_isosurface", iso, n_vertices, n_triangles, false);
+  });
+}
+
+int dmi_extract_isosurface_normals(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_extract_isosurface_normals", [&]() -> int {
+    return extract_isosurface(ctx, "dmi_extract_isosurface_normals", iso, n_vertices, n_triangles, true);
+  });
+}
+
+int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangles) {
+  return guarded(ctx, "dmi_download_isosurface", [&]() -> int {
+  if (!ctx || !vertices || !triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: null argument");
+  const dmi_context::Mesh &mesh = ctx->mesh;
+  if (!mesh.valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: no mesh (dmi_extract_isosurface has not succeeded)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (mesh.n_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(vertices, mesh.vertices.ptr, (size_t)(mesh.n_vertices * kVertexBytes), hipMemcpyDeviceToHost, ctx->stream));
+  if (mesh.n_triangles)
+    DMI_HIP(ctx, hipMemcpyAsync(triangles, mesh.triangles.ptr, (size_t)(mesh.n_triangles * kTriangleBytes), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_download_isosurface_normals(dmi_context *ctx, float *normals) {
+  return guarded(ctx, "dmi_download_isosurface_normals", [&]() -> int {
+  if (!ctx || !normals) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: null argument");
+  const dmi_context::Mesh &mesh = ctx->mesh;
+  if (!mesh.valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: no mesh (no extraction has succeeded)");
+  if (!mesh.has_normals)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_download_isosurface_normals: the last mesh has no normals (dmi_extract_isosurface, not dmi_extract_isosurface_normals)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (mesh.n_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(normals, mesh.normals.ptr, (size_t)(mesh.n_vertices * kNormalBytes), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_kernel_ms: null argument");
+  *last = ctx->extraction.last_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
+                                     uint64_t *n_components, uint64_t *n_components_kept) {
+  return guarded(ctx, "dmi_filter_isosurface_components", [&]() -> int {
+  const std::string entry = "dmi_filter_isosurface_components";
+  if (!ctx || !n_vertices || !n_triangles || !n_components || !n_components_kept)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (mode != DMI_COMPONENTS_MIN_TRIANGLES && mode != DMI_COMPONENTS_LARGEST)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": unknown mode " + std::to_string(mode));
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Components &comp = ctx->components;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  *n_vertices = *n_triangles = *n_components = *n_components_kept = 0;
+  const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
+  // labels and sizes are u32: refused, never wrapped (as the extraction refuses what its int64 ids cannot hold)
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit component labels");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (nv == 0) {  // an empty mesh stays empty
+    mesh.filtered = true;
+    mesh.regions = 0;
+    comp.last_kernel_ms = 0.0;
+    for (double &p : comp.last_pass_ms) p = 0.0;
+    comp.last_cas_retries = 0;
+    return DMI_OK;
+  }
+  const bool normals = mesh.has_normals;
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::components_scan_temp_bytes(nv, nt, &temp_bytes));
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  // the compaction's output, the region arrays, the union-find's scratch (vertex_scratch: 4 u32 arrays of nv + 1) and the scans'
+  int rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&mesh.alt_triangles, std::max<uint64_t>(nt, 1) * kTriangleBytes},
+                                {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&mesh.region_id, nv * 8}, {&mesh.region_size, nv * 8},
+                                {&comp.vertex_scratch, (nv + 1) * 16}, {&comp.triangle_scratch, (nt + 1) * 4}, {&comp.counters, 24},
+                                {&comp.scan_temp, temp_bytes}});
+  if (rc != DMI_OK) return rc;
+  if (!comp.events[0])
+    for (hipEvent_t &e : comp.events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::ComponentsMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = mesh.vertices.as<double>();
+  m.normals = normals ? mesh.normals.as<float>() : nullptr;
+  m.triangles = mesh.triangles.as<int64_t>();
+  m.out_vertices = mesh.alt_vertices.as<double>();
+  m.out_normals = mesh.alt_normals.as<float>();
+  m.out_triangles = mesh.alt_triangles.as<int64_t>();
+  m.region_id = mesh.region_id.as<int64_t>();
+  m.region_size = mesh.region_size.as<int64_t>();
+  dmi::ComponentsScratch s{};
+  uint32_t *vs = comp.vertex_scratch.as<uint32_t>();
+  s.parent = vs;
+  s.size = vs + (nv + 1);
+  s.vmap = vs + 2 * (nv + 1);
+  s.rmap = vs + 3 * (nv + 1);
+  s.tmap = comp.triangle_scratch.as<uint32_t>();
+  s.counters = comp.counters.as<unsigned long long>();
+  s.scan_temp = comp.scan_temp.ptr;
+  s.scan_temp_bytes = temp_bytes;
+  // (a failure from here on leaves the context's mesh and its regions as they were: the buffers are swapped only at the end)
+  DMI_HIP(ctx, dmi::launch_isosurface_components(m, s, mode == DMI_COMPONENTS_LARGEST ? 1 : 0, min_triangles, comp.events, ctx->stream));
+  uint32_t kept[3] = {0, 0, 0};
+  unsigned long long counters[3] = {0, 0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[0], s.vmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[1], s.tmap + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[2], s.rmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(counters, s.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, comp.events[0], comp.events[4]));
+  comp.last_kernel_ms = (double)ms;
+  for (int p = 0; p < 4; ++p) {
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, comp.events[p], comp.events[p + 1]));
+    comp.last_pass_ms[p] = (double)ms;
+  }
+  // the compacted mesh becomes the context's mesh; the buffers it came from are the next filter's output
+  std::swap(mesh.vertices, mesh.alt_vertices);
+  std::swap(mesh.triangles, mesh.alt_triangles);
+  if (normals) std::swap(mesh.normals, mesh.alt_normals);
+  mesh.n_vertices = kept[0];
+  mesh.n_triangles = kept[1];
+  mesh.regions = kept[2];
+  mesh.filtered = true;
+  comp.last_cas_retries = counters[2];
+  *n_vertices = kept[0];
+  *n_triangles = kept[1];
+  *n_components = counters[1];
+  *n_components_kept = kept[2];
+  return DMI_OK;
+  });
+}
+
+int dmi_download_isosurface_regions(dmi_context *ctx, int64_t *region_id, int64_t *region_size) {
+  return guarded(ctx, "dmi_download_isosurface_regions", [&]() -> int {
+  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: null argument");
+  const dmi_context::Mesh &mesh = ctx->mesh;
+  if (!mesh.valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: no mesh (no extraction has succeeded)");
+  if (!mesh.filtered)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_download_isosurface_regions: no regions (dmi_filter_isosurface_components has not run since the last extraction)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (region_id && mesh.n_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(region_id, mesh.region_id.ptr, (size_t)mesh.n_vertices * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (region_size && mesh.regions)
+    DMI_HIP(ctx, hipMemcpyAsync(region_size, mesh.region_size.ptr, (size_t)mesh.regions * 8, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_filter_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_filter_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_kernel_ms: null argument");
+  *last = ctx->components.last_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_filter_pass_ms(dmi_context *ctx, double out[4]) {
+  return guarded(ctx, "dmi_get_isosurface_filter_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_pass_ms: null argument");
+  for (int p = 0; p < 4; ++p) out[p] = ctx->components.last_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last) {
+  return guarded(ctx, "dmi_get_isosurface_filter_cas_retries", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_cas_retries: null argument");
+  *last = ctx->components.last_cas_retries;
+  return DMI_OK;
+  });
+}
+
+int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, double mu) {
+  return guarded(ctx, "dmi_smooth_isosurface", [&]() -> int {
+  const std::string entry = "dmi_smooth_isosurface";
+  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (iterations < 0 || iterations > 1000)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": iterations " + std::to_string(iterations) + " is not in [0, 1000]");
+  if (!(lambda > 0.0 && lambda <= 1.0)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": lambda is not in (0, 1]");
+  if (!(mu <= 0.0) || mu - mu != 0.0) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mu is not a finite number <= 0");
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Smoothing &sm = ctx->smoothing;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
+  // ids are u32 on the device, and so are the offsets into the 6 T directed edges: refused, never wrapped
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  if (6 * nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit adjacency offsets (6 x triangles >= 2^32)");
+  if (iterations == 0 || nv == 0) {  // nothing to do: the mesh, its normals included, stays as it is
+    sm.last_kernel_ms = 0.0;
+    for (double &p : sm.last_pass_ms) p = 0.0;
+    return DMI_OK;
+  }
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  const bool normals = mesh.has_normals;
+  const uint64_t fixed_words = (nv + 63) / 64, n_keys = std::max<uint64_t>(6 * nt, 2);
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::smooth_temp_bytes(nv, nt, &temp_bytes));
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  // the two position buffers of the steps, the new normals, two key arrays, the per-vertex scratch (fixed bits, then 3 u32 arrays
+  // of nv + 1) and the sort's and scans' own storage
+  int rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&sm.vertices, nv * kVertexBytes},
+                                {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&sm.keys, 2 * n_keys * 8},
+                                {&sm.vertex_scratch, fixed_words * 8 + 3 * (nv + 1) * 4}, {&sm.temp, temp_bytes}});
+  if (rc != DMI_OK) return rc;
+  if (!sm.events[0])
+    for (hipEvent_t &e : sm.events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::SmoothMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = mesh.vertices.as<double>();
+  m.triangles = mesh.triangles.as<int64_t>();
+  m.normals_out = normals ? mesh.alt_normals.as<float>() : nullptr;
+  dmi::SmoothScratch s{};
+  s.keys[0] = sm.keys.as<uint64_t>();
+  s.keys[1] = s.keys[0] + n_keys;
+  s.fixed = sm.vertex_scratch.as<unsigned long long>();
+  s.row_start = (uint32_t *)(s.fixed + fixed_words);
+  s.valence = s.row_start + (nv + 1);
+  s.offsets = s.valence + (nv + 1);
+  s.positions[0] = mesh.alt_vertices.as<double>();
+  s.positions[1] = sm.vertices.as<double>();
+  s.temp = sm.temp.ptr;
+  s.temp_bytes = temp_bytes;
+  // (a failure from here on leaves the context's mesh as it was: no kernel writes it, and the buffers are swapped only at the end)
+  double *result = nullptr;
+  DMI_HIP(ctx, dmi::launch_isosurface_smooth(m, s, iterations, lambda, mu, &result, sm.events, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, sm.events[0], sm.events[3]));
+  sm.last_kernel_ms = (double)ms;
+  for (int p = 0; p < 3; ++p) {
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, sm.events[p], sm.events[p + 1]));
+    sm.last_pass_ms[p] = (double)ms;
+  }
+  // the smoothed positions become the context's; the buffer they replace is the next call's scratch
+  std::swap(mesh.vertices, result == mesh.alt_vertices.ptr ? mesh.alt_vertices : sm.vertices);
+  if (normals) std::swap(mesh.normals, mesh.alt_normals);
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_smooth_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_kernel_ms: null argument");
+  *last = ctx->smoothing.last_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]) {
+  return guarded(ctx, "dmi_get_isosurface_smooth_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_pass_ms: null argument");
+  for (int p = 0; p < 3; ++p) out[p] = ctx->smoothing.last_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,246 @@
+// dmi_context.h -- the context behind the C ABI of include/dmi.h, and the helpers its translation units share (dmi_capi.hip:
+// creation, destruction, views, fusion, grid transfer, diagnostics; dmi_capi_mesh.hip: point data and the iso-surface).
+// Private: never installed.
+#pragma once
+#include "../../include/dmi.h"
+#include "fusion_kernels.h"
+
+#include <exception>
+#include <initializer_list>
+#include <new>
+#include <string>
+#include <vector>
+
+namespace dmi {
+
+struct Batch {
+  void *d_depth = nullptr;             // n * W * H values of the context's current storage type
+  DepthTile *d_pyramid = nullptr;  // n min/max pyramids (fusion_classify.hip), then the n validity maps
+  size_t valid_offset = 0;              // byte offset of the validity maps within d_pyramid
+  size_t bits_offset = 0;               // ... and of the validity bits (TileMapRec::vbits) behind them
+  size_t aux_bytes = 0;                 // size of the d_pyramid allocation
+  int32_t n = 0;
+  unsigned long long holes = 0;         // pixels without a depth among the n * W * H (counted while the validity maps are built)
+  unsigned long long mingled_strips = 0;  // 8-pixel strips (a column of a tile row) with both a hole and a depth
+};
+
+struct EventPair {
+  hipEvent_t start = nullptr, stop = nullptr;
+  hipEvent_t mid = nullptr;  // recorded just before the fusion kernel proper (after cz table, classification, ordering)
+  bool has_mid = false;
+};
+
+// A grow-only device allocation of the context: the pointer and its capacity travel together (one std::swap exchanges two
+// buffers whole).  Grown by ensure_buffer, freed by its group's release(); owns nothing by itself.
+struct DeviceBuffer {
+  void *ptr = nullptr;
+  uint64_t capacity = 0;  // bytes
+  template <typename T>
+  T *as() const { return static_cast<T *>(ptr); }
+};
+
+// what every group's release() is made of (dmi_destroy has selected the device)
+inline void free_buffers(std::initializer_list<DeviceBuffer *> buffers) {
+  for (DeviceBuffer *b : buffers) {
+    if (b->ptr) (void)hipFree(b->ptr);
+    *b = DeviceBuffer{};
+  }
+}
+template <size_t N>
+void destroy_events(hipEvent_t (&events)[N]) {
+  for (hipEvent_t &e : events) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+}
+}  // namespace dmi
+
+struct dmi_context {
+  dmi_grid_desc grid{};
+  dmi_ray_potential ray{};
+  dmi_options opt{};
+  int64_t n_voxels = 0;
+
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  // dmi_add_views copies, converts and builds pyramids on a stream of its own and waits for that stream only: a fuse
+  // still running on `stream` overlaps the upload of the next views (FusionDriver::ProcessDepthMap pipelines on this)
+  hipStream_t upload_stream = nullptr;
+  hipStream_t download_stream = nullptr;  // dmi_fuse_range_download: the slabs' copies to the host
+  std::vector<hipEvent_t> slab_events;    // ... and what each waits for
+
+  void *d_grid = nullptr;
+  bool own_grid = false;
+  std::vector<uint8_t> layer_is_zero;  // per cell layer: known to hold +0.0 everywhere (reset, not fused since)
+  bool zero_fill_pending = false;  // reset requested, memset deferred: the next fuse overwrites every voxel
+  // No voxel of the (context-owned) grid is -0.0: true after a reset and preserved by every fusion -- a sum that is not -0.0 never
+  // becomes one (x + y is -0.0 only when both are; a non-zero f64 sum does not round to zero) -- so the +0.0 adds of voxels far
+  // behind every surface stay unobservable from one dmi_fuse_range to the next, not only in the first (round 4: the chunked
+  // fusion of the drop-in filter ran its later chunks at half speed).  False once the caller has uploaded a grid, and for a
+  // caller-owned grid (whoever owns it may write anything between two calls).
+  bool grid_free_of_negative_zero = false;
+  uint32_t *d_voxel_hits = nullptr;
+  unsigned long long *d_map_hits = nullptr;
+  size_t map_hits_capacity = 0;
+
+  int32_t W = 0, H = 0;
+  bool depth_f64 = false;
+  bool finite_bounded = true;  // grid descriptor magnitudes allow the K shortcuts
+  int k_mode = dmi::K_PINHOLE;          // the least structured K among the resident views (dmi_info)
+  std::vector<uint8_t> view_k_mode;     // per view: dmi::KMode of its K
+  std::vector<uint8_t> view_tile_ok;    // per view: meets the tiled kernel's per-view preconditions (make_tile_rec)
+  std::vector<dmi::Batch> batches;
+  std::vector<dmi::MapRec> h_maps;
+  dmi::MapRec *d_maps = nullptr;
+  size_t d_maps_capacity = 0;
+  bool maps_dirty = false;
+
+  // tiled kernel (fusion_tile.hip): per-map records, the r22*wz(k) table, a device copy of FuseArgs
+  std::vector<dmi::TileMapRec> h_tile_maps;
+  dmi::TileMapRec *d_tile_maps = nullptr;
+  std::vector<dmi::WinRec> h_win_recs;  // per view: what the window form of the FREE column reads (one line each)
+  dmi::WinRec *d_win_recs = nullptr;
+  std::vector<dmi::FootRec> h_foot_recs;  // per view: the brick's corners relative to its first voxel (window_origin_kernel)
+  dmi::FootRec *d_foot_recs = nullptr;
+  double *d_cz_table = nullptr;
+  size_t cz_table_capacity = 0;  // doubles
+  dmi::FuseArgs *d_fuse_args = nullptr;
+  double max_tile_err = 0.0;     // largest TileMapRec::err among the resident views
+  bool last_fuse_tiled = false;
+  bool last_fuse_classes = false;
+  int64_t last_class_bricks = 0;  // wave bricks of the last fuse
+  int32_t last_bricks_z = 0, last_tk = 0;
+  const dmi::WinPair *last_win_origin = nullptr;  // the last tiled launch's pair table (nullptr: it had no windows)
+  int32_t last_class_pitch = 0, last_first = 0, last_count = 0;
+  dmi::PyramidDesc pyramid{};    // geometry of every view's depth min/max pyramid
+  uint8_t *d_zero_row = nullptr;  // one row of BRICK_MIXED bytes: the class table of a fuse without classes
+  size_t zero_row_capacity = 0;
+  uint8_t *d_classes = nullptr;  // brick classes [wave bricks][class_pitch], then the coarse table [boxes][class_pitch]
+  size_t coarse_offset = 0;      // byte offset of the coarse table within d_classes (last fuse)
+  size_t classes_capacity = 0;   // bytes
+  int32_t *d_queue_heads = nullptr;          // TileArgs::queue_heads (128 ints)
+  unsigned long long *d_wg_times = nullptr;  // tuning builds: TileArgs::wg_times of the last tiled fuse
+  size_t wg_times_blocks = 0;
+  // slot enumeration of the tiled kernel (TileArgs::sb_perm), one table per slab geometry seen (the z-slabs of a
+  // multi-GPU fusion come round again every step)
+  struct SlotPerm {
+    int32_t super_x, super_y, super_z, zmajor;
+    int32_t *d_perm;
+  };
+  std::vector<SlotPerm> slot_perms;
+  uint8_t *d_order_level = nullptr;  // workgroup order: scratch levels, order[], count
+  int32_t *d_order = nullptr;
+  size_t order_capacity = 0;     // slots
+
+  // ---- post-processing (dmi_capi_mesh.hip): every buffer is kept while large enough, every capacity is in bytes ----
+  struct CellToPoint {
+    dmi::DeviceBuffer points;  // vtkCellDataToPointData of the grid, (nx+1)(ny+1)(nz+1) f64 (grid_post.hip)
+    bool valid = false;        // points matches the grid's current contents
+    hipEvent_t events[2] = {nullptr, nullptr};  // start, stop
+    bool pending = false;
+    void release() { dmi::free_buffers({&points}); dmi::destroy_events(events); }
+  } c2p;
+  // The mesh of the last extraction, as the filter and the smoother have left it.  The filter compacts into the alternates and the
+  // smoother steps through alt_vertices and smoothing.vertices (normals into alt_normals); whichever holds the result is then swapped
+  // with the mesh's own buffer.
+  struct Mesh {
+    dmi::DeviceBuffer vertices, triangles, normals;  // [n][3] f64, [n][3] int64, [n][3] f32
+    dmi::DeviceBuffer alt_vertices, alt_triangles, alt_normals;
+    dmi::DeviceBuffer region_id, region_size;  // int64 per vertex / per kept component, of the last filter
+    uint64_t n_vertices = 0, n_triangles = 0;
+    uint64_t regions = 0;      // kept components of that filter
+    bool valid = false;
+    bool has_normals = false;  // the last successful extraction wrote them
+    bool filtered = false;     // a filter has run since the last extraction: the region arrays are the mesh's
+    void release() {
+      dmi::free_buffers({&vertices, &triangles, &normals, &alt_vertices, &alt_triangles, &alt_normals, &region_id, &region_size});
+    }
+  } mesh;
+  struct Extraction {  // dmi_extract_isosurface (isosurface.hip)
+    dmi::DeviceBuffer counts, bases, scan_temp;  // per-segment counts (u32) and bases (u64), two arrays of (segments + 1) each
+    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};  // around the count pass + scans, and the write pass
+    double last_kernel_ms = 0.0;
+    void release() { dmi::free_buffers({&counts, &bases, &scan_temp}); dmi::destroy_events(events); }
+  } extraction;
+  struct Components {  // dmi_filter_isosurface_components (isosurface_components.hip)
+    dmi::DeviceBuffer vertex_scratch;  // parent, size, vmap, rmap: 4 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer triangle_scratch, counters, scan_temp;
+    hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double last_kernel_ms = 0.0;
+    uint64_t last_cas_retries = 0;  // compare-and-swaps of the last filter's hooking pass that lost a race
+    double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // labels (init, hook, flatten), sizes (and largest), scans, compaction
+    void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &counters, &scan_temp}); dmi::destroy_events(events); }
+  } components;
+  struct Smoothing {  // dmi_smooth_isosurface (isosurface_smooth.hip)
+    dmi::DeviceBuffer vertices;        // the second position buffer of the steps
+    dmi::DeviceBuffer keys;            // two u64 arrays of 6 triangles' keys
+    dmi::DeviceBuffer vertex_scratch;  // the fixed bits, then row starts, valences and offsets: 3 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer temp;
+    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
+    double last_kernel_ms = 0.0;
+    double last_pass_ms[3] = {0.0, 0.0, 0.0};  // adjacency (and incidence), steps, normals
+    void release() { dmi::free_buffers({&vertices, &keys, &vertex_scratch, &temp}); dmi::destroy_events(events); }
+  } smoothing;
+
+  void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
+  double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
+  size_t stage_capacity = 0;  // elements per staging buffer
+  unsigned long long *d_lossy = nullptr;
+  hipEvent_t up_start = nullptr, up_stop = nullptr;  // around the upload pass's kernels (dmi_get_upload_kernel_ms)
+  double last_upload_kernel_ms = 0.0, total_upload_kernel_ms = 0.0;
+
+  std::vector<dmi::EventPair> pending, pool;
+  dmi_timings timings{};
+  uint64_t device_bytes = 0;
+  std::string err;
+};
+
+namespace dmi {
+
+int fail(dmi_context *ctx, int code, const std::string &msg);  // records msg (ctx == nullptr: for dmi_last_error(nullptr))
+int drain_events(dmi_context *ctx);                            // the pending fusions' timings
+int drain_c2p(dmi_context *ctx);                               // ... and the pending cell-to-point pass's
+int flush_zero_fill(dmi_context *ctx);
+// Grows a context-owned device buffer to hold `bytes`: kept when its capacity suffices, else freed and allocated at exactly
+// `bytes` (device_bytes follows); the old contents are not kept.
+int ensure_buffer(dmi_context *ctx, DeviceBuffer &buffer, uint64_t bytes);
+struct BufferNeed {
+  DeviceBuffer *buffer;
+  uint64_t bytes;  // 0: not needed by this call, left as it is
+};
+int ensure_buffers(dmi_context *ctx, std::initializer_list<BufferNeed> needs);  // in order, up to the first failure
+
+// No C++ exception may cross the C ABI (the caller may be C, or C++ built with another runtime): every entry point
+// that can allocate on the host runs its body through this.
+template <typename Body>
+int guarded(dmi_context *ctx, const char *entry, Body &&body) noexcept {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    try {
+      return fail(ctx, DMI_ERR_OUT_OF_MEMORY, std::string(entry) + ": host allocation failed");
+    } catch (...) {
+      return DMI_ERR_OUT_OF_MEMORY;
+    }
+  } catch (const std::exception &e) {
+    try {
+      return fail(ctx, DMI_ERR_STATE, std::string(entry) + ": " + e.what());
+    } catch (...) {
+      return DMI_ERR_STATE;
+    }
+  } catch (...) {
+    return DMI_ERR_STATE;
+  }
+}
+
+}  // namespace dmi
+
+#define DMI_HIP(ctx, call)                                                                              \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess) {                                                                             \
+      (void)hipGetLastError();                                                                          \
+      return dmi::fail(ctx, e_ == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE,         \
+                  std::string(#call) + ": " + hipGetErrorString(e_));                                   \
+    }                                                                                                   \
+  } while (0)

@@ -364,6 +364,81 @@ def test_gpu_smoothing_life_cycle_determinism_and_errors():
         assert ctx.download_isosurface()[0].shape == (0, 3)
 
 
+def _filter_smooth_download(ctx, iso, normals, n_min):
+    """The context's grid through extract -> filter -> smooth(3, 0.5, -0.53) -> download.  n_min None: the filter keeps the largest
+    component; else it keeps those of >= n_min triangles, and a second filter after the smoothing keeps the largest.  Returns the
+    unfiltered extraction (v0, t0, n0) and the final mesh (v, t, n, region ids, region sizes); n0 and n are None without normals."""
+    if normals:
+        v0, t0, n0 = ctx.extract_isosurface_with_normals(iso)
+    else:
+        (v0, t0), n0 = ctx.extract_isosurface(iso), None
+    if n_min is None:
+        ctx.filter_isosurface_components(C.LARGEST)
+        ctx.smooth_isosurface(3, 0.5, -0.53)
+    else:
+        ctx.filter_isosurface_components(C.MIN_TRIANGLES, n_min)
+        ctx.smooth_isosurface(3, 0.5, -0.53)
+        ctx.filter_isosurface_components(C.LARGEST)
+    v, t = ctx.download_isosurface()
+    n = ctx.download_isosurface_normals() if normals else None
+    return (v0, t0, n0), (v, t, n) + tuple(ctx.download_isosurface_regions())
+
+
+def _filter_smooth_restated(v0, t0, n0, n_min):
+    """What _filter_smooth_download returns second, from the CPU restatements applied to the unfiltered extraction."""
+    if n_min is None:
+        kept = C.filter_mesh(v0, t0, n0, C.LARGEST)
+        v, n = S.smooth(kept["vertices"], kept["triangles"], 3, 0.5, -0.53, kept["normals"])
+        return v, kept["triangles"], n, kept["region_id"], kept["region_size"]
+    kept = C.filter_mesh(v0, t0, n0, C.MIN_TRIANGLES, n_min)
+    v, n = S.smooth(kept["vertices"], kept["triangles"], 3, 0.5, -0.53, kept["normals"])
+    big = C.filter_mesh(v, kept["triangles"], n, C.LARGEST)
+    return big["vertices"], big["triangles"], big["normals"], big["region_id"], big["region_size"]
+
+
+def _same_mesh(got, want):
+    return all((g is None and w is None) or _same_bits(g, w) for g, w in zip(got, want)) and len(got) == len(want)
+
+
+@pytest.mark.gpu
+def test_gpu_mesh_buffers_grow_across_swaps_and_reach_a_steady_state():
+    """One context of 24 x 20 x 16 cells takes a small mesh S with normals, a large one L without normals, L with normals (the
+    normals' buffers grow while the vertex buffers, swapped by the filter and the smoother, are already large) and S again, each
+    filtered and smoothed.  Every download is, bit for bit, what a fresh context gives for that field and what the restatements make of
+    the unfiltered extraction; a second round of the four leaves info().device_bytes where the first left it."""
+    x, y, z = _lattice(24, 20, 16)
+    blob = lambda c, r: r - np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2)
+    small = _cell_field(np.maximum(blob((9.3, 9.8, 8.1), 3.3), blob((19.2, 6.4, 5.7), 1.7)))      # two spheres: LARGEST drops one
+    large = np.random.default_rng(17).uniform(-1.5, 2.5, size=(16, 20, 24))                          # a soup of many components
+    # (cells, iso, normals) of the four steps; n_min of the large field from a fresh context's extraction
+    with _context(large) as ctx:
+        v0, t0 = ctx.extract_isosurface(1.0)
+    size = C.components(len(v0), t0)[1]
+    n_min = int(np.median(size[size > 0])) + 1
+    steps = [(small, 0.0, True, None), (large, 1.0, False, n_min), (large, 1.0, True, n_min), (small, 0.0, True, None)]
+    want = []
+    for cells, iso, normals, n_min_ in steps[:3]:
+        with _context(cells) as ctx:
+            raw, fresh = _filter_smooth_download(ctx, iso, normals, n_min_)
+        assert _same_mesh(fresh, _filter_smooth_restated(*raw, n_min_))
+        want.append((raw, fresh))
+    want.append(want[0])
+    n_small, n_large = len(want[0][0][1]), len(want[1][0][1])
+    print(f"S: {n_small} triangles ({len(want[0][1][1])} kept), L: {n_large} triangles ({len(want[1][1][1])} kept), n_min {n_min}")
+    assert 100 < n_small < 1000 and n_large > 4 * n_small and len(want[0][1][1]) < n_small
+    assert _same_bits(want[1][0][0], want[2][0][0]) and _same_bits(want[1][1][0], want[2][1][0])   # normals or not: the same positions
+    device_bytes = []
+    with _context(small) as ctx:
+        for _ in range(2):
+            for (cells, iso, normals, n_min_), (raw, final) in zip(steps, want):
+                ctx.upload_grid(cells)
+                got_raw, got = _filter_smooth_download(ctx, iso, normals, n_min_)
+                assert _same_mesh(got_raw, raw) and _same_mesh(got, final), (iso, normals)
+            device_bytes.append(int(ctx.info().device_bytes))
+    print(f"device_bytes after round one {device_bytes[0]}, after round two {device_bytes[1]}")
+    assert device_bytes[0] == device_bytes[1] > 0
+
+
 @pytest.mark.gpu
 def test_gpu_timing_tool_smooth_record():
     """tools/gpu_isosurface_time.py --smooth: its record of a small fused scene is complete and agrees with the restatement."""
