@@ -102,8 +102,7 @@ def color_mesh_np(points, colors, K4, RT4):
                 u, v = np.float64(d[0]) / np.float64(d[2]), np.float64(d[1]) / np.float64(d[2])
             if not (np.isfinite(u) and np.isfinite(v)):
                 continue
-            ru = np.sign(u) * np.floor(np.abs(u) + 0.5)     # std::round: half away from zero
-            rv = np.sign(v) * np.floor(np.abs(v) + 0.5)
+            ru, rv = float(_round_half_away(u)), float(_round_half_away(v))   # std::round (|u| + 0.5 would round 0.49999999999999994 up)
             if not (abs(ru) < 2.0 ** 31 and abs(rv) < 2.0 ** 31):
                 continue
             px, py = int(ru), int(rv)
