@@ -110,6 +110,7 @@ ABI_SYMBOLS = [
     "dmi_filter_isosurface_components", "dmi_download_isosurface_regions", "dmi_get_isosurface_filter_kernel_ms",
     "dmi_get_isosurface_filter_pass_ms", "dmi_get_isosurface_filter_cas_retries",
     "dmi_smooth_isosurface", "dmi_get_isosurface_smooth_kernel_ms", "dmi_get_isosurface_smooth_pass_ms",
+    "dmi_decimate_isosurface", "dmi_get_isosurface_decimate_kernel_ms", "dmi_get_isosurface_decimate_pass_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -196,6 +197,10 @@ def load() -> ctypes.CDLL:
         L.dmi_smooth_isosurface.argtypes = [vp, i32, dbl, dbl]
         L.dmi_get_isosurface_smooth_kernel_ms.argtypes = [vp, dp]
         L.dmi_get_isosurface_smooth_pass_ms.argtypes = [vp, dp]
+    if hasattr(L, "dmi_decimate_isosurface"):
+        L.dmi_decimate_isosurface.argtypes = [vp, dbl, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.dmi_get_isosurface_decimate_kernel_ms.argtypes = [vp, dp]
+        L.dmi_get_isosurface_decimate_pass_ms.argtypes = [vp, dp]
     L.dmi_get_brick_class_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dmi_get_mixed_reason_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_get_window_pair_count"):  # (absent from an older prebuilt library loaded for an A/B timing, tools/gpu_exp.py)
@@ -578,6 +583,28 @@ class FusionContext:
         a = (ctypes.c_double * 3)()
         self._check(self._lib.dmi_get_isosurface_smooth_pass_ms(self._h, a))
         return dict(zip(("adjacency", "steps", "normals"), (float(x) for x in a)))
+
+    def decimate_isosurface(self, cell_size: float):
+        """(vertices, triangles) left after vertex clustering of the context's mesh on the device with cubic cells of `cell_size`
+        world units: every cluster becomes the mean of its members, collapsed and duplicate triangles and unreferenced vertices
+        go; normals, if the mesh has them, become the decimated mesh's geometric ones; the regions of an earlier filter are
+        dropped (dmi_decimate_isosurface).  download_isosurface* return the decimated mesh afterwards."""
+        nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.dmi_decimate_isosurface(self._h, float(cell_size), ctypes.byref(nv), ctypes.byref(nt)))
+        self._mesh_counts = (int(nv.value), int(nt.value), 0)
+        return int(nv.value), int(nt.value)
+
+    def isosurface_decimate_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last decimate_isosurface (dmi_get_isosurface_decimate_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_isosurface_decimate_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
+
+    def isosurface_decimate_pass_ms(self) -> dict:
+        """The same pass by pass (dmi_get_isosurface_decimate_pass_ms)."""
+        a = (ctypes.c_double * 4)()
+        self._check(self._lib.dmi_get_isosurface_decimate_pass_ms(self._h, a))
+        return dict(zip(("clustering", "representatives", "triangles", "normals"), (float(x) for x in a)))
 
     def isosurface_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last extract_isosurface or extract_isosurface_with_normals
@@ -1161,7 +1188,8 @@ class CliOptionsC(ctypes.Structure):
                 ("summary", ctypes.c_int32), ("force_cubic_voxel", ctypes.c_int32), ("extract_mesh", ctypes.c_int32),
                 ("mesh_normals", ctypes.c_int32), ("mesh_largest_component", ctypes.c_int32), ("mesh_region_ids", ctypes.c_int32),
                 ("mesh_min_component_triangles", ctypes.c_int64), ("mesh_smooth_iterations", ctypes.c_int64),
-                ("mesh_smooth_lambda", ctypes.c_double), ("mesh_smooth_mu", ctypes.c_double)]
+                ("mesh_smooth_lambda", ctypes.c_double), ("mesh_smooth_mu", ctypes.c_double),
+                ("mesh_decimate_cell_size", ctypes.c_double)]
 
 
 def cli_read_arguments(args):

@@ -1,9 +1,11 @@
 // dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
 // (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
-// filter, the smoother and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
+// filter, the smoother, the decimation and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
 #include "dmi_context.h"
 
 #include <algorithm>
+#include <cmath>
+#include <cstdio>
 #include <limits>
 
 using dmi::drain_c2p;
@@ -501,6 +503,179 @@ int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]) {
   return guarded(ctx, "dmi_get_isosurface_smooth_pass_ms", [&]() -> int {
   if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_pass_ms: null argument");
   for (int p = 0; p < 3; ++p) out[p] = ctx->smoothing.last_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
+namespace {
+// the events of the last decimation become its times (its normals, enqueued behind the call's last synchronisation, may still run)
+int drain_decimation(dmi_context *ctx) {
+  dmi_context::Decimation &dc = ctx->decimation;
+  if (!dc.pending) return DMI_OK;
+  DMI_HIP(ctx, hipEventSynchronize(dc.events[dc.pending_normals ? 7 : 5]));
+  auto elapsed = [&](int a, int b, double *out) -> hipError_t {
+    float ms = 0.f;
+    const hipError_t e = hipEventElapsedTime(&ms, dc.events[a], dc.events[b]);
+    *out = (double)ms;
+    return e;
+  };
+  double bounds = 0.0, ranks = 0.0, triangles = 0.0, representatives = 0.0, normals = 0.0;
+  DMI_HIP(ctx, elapsed(0, 1, &bounds));
+  DMI_HIP(ctx, elapsed(2, 3, &ranks));
+  DMI_HIP(ctx, elapsed(3, 4, &triangles));
+  DMI_HIP(ctx, elapsed(4, 5, &representatives));
+  if (dc.pending_normals) DMI_HIP(ctx, elapsed(6, 7, &normals));
+  dc.last_pass_ms[0] = bounds + ranks;
+  dc.last_pass_ms[1] = representatives;
+  dc.last_pass_ms[2] = triangles;
+  dc.last_pass_ms[3] = normals;
+  dc.last_kernel_ms = ((dc.last_pass_ms[0] + dc.last_pass_ms[1]) + dc.last_pass_ms[2]) + dc.last_pass_ms[3];
+  dc.pending = false;
+  return DMI_OK;
+}
+
+// the bins of one axis: floor((hi - lo) / h) + 1, or 0 when that is more than 2^21 (an infinite quotient included)
+uint64_t decimate_bins(double lo, double hi, double h) {
+  const double q = std::floor((hi - lo) / h);
+  return q < 2097152.0 ? (uint64_t)q + 1 : 0;
+}
+}  // namespace
+
+int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_decimate_isosurface", [&]() -> int {
+  const std::string entry = "dmi_decimate_isosurface";
+  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": cell_size is not a finite number > 0");
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Decimation &dc = ctx->decimation;
+  dmi_context::Smoothing &sm = ctx->smoothing;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
+  // ids are u32 on the device: refused, never wrapped
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  int rc = drain_decimation(ctx);  // (the events are about to be recorded again)
+  if (rc != DMI_OK) return rc;
+  *n_vertices = *n_triangles = 0;
+  if (nv == 0) {  // an empty mesh stays empty (it has no triangles either)
+    mesh.filtered = false;
+    dc.last_kernel_ms = 0.0;
+    for (double &p : dc.last_pass_ms) p = 0.0;
+    return DMI_OK;
+  }
+  const bool normals = mesh.has_normals;
+  size_t temp_bytes = 0, normals_temp_bytes = 0;
+  DMI_HIP(ctx, dmi::decimate_temp_bytes(nv, nt, &temp_bytes));
+  if (normals) DMI_HIP(ctx, dmi::smooth_temp_bytes(nv, nt, &normals_temp_bytes));  // (the decimated mesh is no larger)
+  temp_bytes = std::max<size_t>(std::max(temp_bytes, normals_temp_bytes), 16);
+  // the result's buffers (the component filter's alternates), the vertex keys, then the triangle keys and values, then the
+  // incidence of the normals (the smoother's key arrays), the per-vertex and per-triangle u32 arrays, rocPRIM's own storage
+  const uint64_t n_keys = std::max<uint64_t>(std::max(nv, 2 * nt), normals ? 3 * nt : 0);
+  rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&mesh.alt_triangles, std::max<uint64_t>(nt, 1) * kTriangleBytes},
+                            {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&sm.keys, 2 * n_keys * 8},
+                            {&dc.vertex_scratch, 8 * (nv + 1) * 4}, {&dc.triangle_scratch, 2 * (nt + 1) * 4}, {&dc.bounds, 64},
+                            {&sm.temp, temp_bytes}});
+  if (rc != DMI_OK) return rc;
+  if (!dc.events[0])
+    for (hipEvent_t &e : dc.events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::DecimateMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = mesh.vertices.as<double>();
+  m.triangles = mesh.triangles.as<int64_t>();
+  m.out_vertices = mesh.alt_vertices.as<double>();
+  m.out_triangles = mesh.alt_triangles.as<int64_t>();
+  dmi::DecimateScratch s{};
+  s.bounds = dc.bounds.as<unsigned long long>();
+  s.keys[0] = sm.keys.as<uint64_t>();
+  s.keys[1] = s.keys[0] + n_keys;
+  uint32_t *vs = dc.vertex_scratch.as<uint32_t>();
+  s.ids[0] = vs;
+  s.ids[1] = vs + (nv + 1);
+  s.head = vs + 2 * (nv + 1);
+  s.rank = vs + 3 * (nv + 1);
+  s.cluster_of = vs + 4 * (nv + 1);
+  s.start = vs + 5 * (nv + 1);
+  s.mark = vs + 6 * (nv + 1);
+  s.cmap = vs + 7 * (nv + 1);
+  s.keep = dc.triangle_scratch.as<uint32_t>();
+  s.tmap = s.keep + (nt + 1);
+  s.temp = sm.temp.ptr;
+  s.temp_bytes = temp_bytes;
+  // (a failure from here on leaves the context's mesh, its normals and its regions as they were: no kernel writes them, and the
+  // buffers are swapped only at the end)
+  DMI_HIP(ctx, dmi::launch_decimate_bounds(m, s, dc.events, ctx->stream));
+  unsigned long long bounds[7] = {0, 0, 0, 0, 0, 0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(bounds, s.bounds, sizeof(bounds), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the first of two: the bins, or the refusal
+  if (bounds[6]) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the mesh has a non-finite vertex coordinate");
+  dmi::DecimateGrid g{};
+  g.h = cell_size;
+  double extent = 0.0;
+  bool too_many = false;
+  for (int d = 0; d < 3; ++d) {
+    g.lo[d] = dmi::decimate_decode_bound(bounds[d]);
+    const double hi = dmi::decimate_decode_bound(bounds[3 + d]);
+    g.n[d] = decimate_bins(g.lo[d], hi, cell_size);
+    too_many |= g.n[d] == 0;
+    extent = std::max(extent, hi - g.lo[d]);
+  }
+  if (too_many) {
+    // the smallest cell size whose quotient, as rounded, stays below 2^21 on the longest axis
+    double least = extent / 2097152.0;
+    while (!(std::floor(extent / least) < 2097152.0)) least = std::nextafter(least, std::numeric_limits<double>::infinity());
+    char text[64];
+    std::snprintf(text, sizeof(text), "%.17g", least);
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                entry + ": more than 2^21 bins on an axis; the smallest acceptable cell size for this mesh is " + text);
+  }
+  DMI_HIP(ctx, dmi::launch_isosurface_decimate(m, g, s, dc.events + 2, ctx->stream));
+  uint32_t kept[2] = {0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[0], s.cmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&kept[1], s.tmap + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the second: the counts
+  const bool new_normals = normals && kept[0] > 0;
+  if (new_normals) {  // the smoother's incidence build and kernel on the result; the triangle keys are no longer needed
+    uint64_t *const keys[2] = {s.keys[0], s.keys[1]};
+    DMI_HIP(ctx, hipEventRecord(dc.events[6], ctx->stream));
+    DMI_HIP(ctx, dmi::launch_isosurface_geometric_normals(m.out_vertices, m.out_triangles, kept[0], kept[1], keys, s.head, s.temp, temp_bytes,
+                                                          mesh.alt_normals.as<float>(), ctx->stream));
+    DMI_HIP(ctx, hipEventRecord(dc.events[7], ctx->stream));
+  }
+  dc.pending = true;
+  dc.pending_normals = new_normals;
+  // the decimated mesh becomes the context's; the buffers it came from are the next call's output
+  std::swap(mesh.vertices, mesh.alt_vertices);
+  std::swap(mesh.triangles, mesh.alt_triangles);
+  if (normals) std::swap(mesh.normals, mesh.alt_normals);
+  mesh.n_vertices = kept[0];
+  mesh.n_triangles = kept[1];
+  mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
+  mesh.regions = 0;
+  *n_vertices = kept[0];
+  *n_triangles = kept[1];
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_decimate_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_decimate_kernel_ms: null argument");
+  const int rc = drain_decimation(ctx);
+  if (rc != DMI_OK) return rc;
+  *last = ctx->decimation.last_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]) {
+  return guarded(ctx, "dmi_get_isosurface_decimate_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_decimate_pass_ms: null argument");
+  const int rc = drain_decimation(ctx);
+  if (rc != DMI_OK) return rc;
+  for (int p = 0; p < 4; ++p) out[p] = ctx->decimation.last_pass_ms[p];
   return DMI_OK;
   });
 }

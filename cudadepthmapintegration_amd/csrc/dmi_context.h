@@ -140,9 +140,9 @@ struct dmi_context {
     bool pending = false;
     void release() { dmi::free_buffers({&points}); dmi::destroy_events(events); }
   } c2p;
-  // The mesh of the last extraction, as the filter and the smoother have left it.  The filter compacts into the alternates and the
-  // smoother steps through alt_vertices and smoothing.vertices (normals into alt_normals); whichever holds the result is then swapped
-  // with the mesh's own buffer.
+  // The mesh of the last extraction, as the filter, the smoother and the decimation have left it.  The filter and the decimation
+  // write into the alternates and the smoother steps through alt_vertices and smoothing.vertices (normals into alt_normals);
+  // whichever holds the result is then swapped with the mesh's own buffer.
   struct Mesh {
     dmi::DeviceBuffer vertices, triangles, normals;  // [n][3] f64, [n][3] int64, [n][3] f32
     dmi::DeviceBuffer alt_vertices, alt_triangles, alt_normals;
@@ -151,7 +151,7 @@ struct dmi_context {
     uint64_t regions = 0;      // kept components of that filter
     bool valid = false;
     bool has_normals = false;  // the last successful extraction wrote them
-    bool filtered = false;     // a filter has run since the last extraction: the region arrays are the mesh's
+    bool filtered = false;     // a filter has run since the last extraction or decimation: the region arrays are the mesh's
     void release() {
       dmi::free_buffers({&vertices, &triangles, &normals, &alt_vertices, &alt_triangles, &alt_normals, &region_id, &region_size});
     }
@@ -181,6 +181,18 @@ struct dmi_context {
     double last_pass_ms[3] = {0.0, 0.0, 0.0};  // adjacency (and incidence), steps, normals
     void release() { dmi::free_buffers({&vertices, &keys, &vertex_scratch, &temp}); dmi::destroy_events(events); }
   } smoothing;
+  struct Decimation {  // dmi_decimate_isosurface (isosurface_decimate.hip); it also uses smoothing.keys and smoothing.temp
+    dmi::DeviceBuffer vertex_scratch;    // sorted ids (2), head, rank, cluster, start, mark, map: 8 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer triangle_scratch;  // keep, map: 2 u32 arrays of (triangles + 1)
+    dmi::DeviceBuffer bounds;            // 8 u64
+    // around the bounds pass; before the keys, after the ranks, the triangles, the representatives; around the normals
+    hipEvent_t events[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool pending = false;         // the events of the last call have not been read yet (its normals may still run)
+    bool pending_normals = false;
+    double last_kernel_ms = 0.0;
+    double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // clustering, representatives, triangles, normals
+    void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); dmi::destroy_events(events); }
+  } decimation;
 
   void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
   double *d_stage_depth = nullptr, *d_stage_cost = nullptr;

@@ -487,5 +487,43 @@ struct SmoothScratch {
 hipError_t smooth_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
 hipError_t launch_isosurface_smooth(const SmoothMesh &m, const SmoothScratch &s, int iterations, double lambda, double mu,
                                     double **result, hipEvent_t *events, hipStream_t stream);
+// The smoother's geometric normals of any mesh (n_vertices >= 1 and below 2^32, n_triangles below 2^32; the decimation's too): the
+// vertex -> triangle incidence is built in keys[0] / keys[1] ([3 n_triangles] each) and row_start ([n_vertices + 1]); temp holds
+// smooth_temp_bytes(n_vertices, n_triangles).  Triangles naming an id >= n_vertices are skipped.
+hipError_t launch_isosurface_geometric_normals(const double *vertices, const int64_t *triangles, uint64_t n_vertices, uint64_t n_triangles,
+                                               uint64_t *const keys[2], uint32_t *row_start, void *temp, size_t temp_bytes,
+                                               float *normals_out, hipStream_t stream);
+
+// Vertex clustering of that mesh (isosurface_decimate.hip).  Nothing of the input mesh is written.
+struct DecimateMesh {
+  uint64_t n_vertices, n_triangles;  // n_vertices >= 1, both below 2^32 (u32 ids on the device)
+  const double *vertices;            // [n_vertices][3]
+  const int64_t *triangles;          // [n_triangles][3]
+  double *out_vertices;              // room for the whole mesh each: how much stays is known only afterwards
+  int64_t *out_triangles;
+};
+struct DecimateGrid {                // the bins, from the bounds the first pass found
+  double lo[3], h;
+  uint64_t n[3];                     // bins per axis, each <= 2^21
+};
+struct DecimateScratch {
+  unsigned long long *bounds;        // [8]: lo[3] and hi[3] as order-preserving integers, the non-finite flag, unused
+  uint64_t *keys[2];                 // [max(n_vertices, 2 n_triangles)] each: the vertex keys, then the triangle keys and values
+  uint32_t *ids[2];                  // [n_vertices] each: the vertex ids sorted with their keys
+  uint32_t *head, *rank;             // [n_vertices + 1]: first of a cluster, and the inclusive scan of that
+  uint32_t *cluster_of, *start;      // [n_vertices + 1]: a vertex's cluster; a cluster's first sorted position
+  uint32_t *mark, *cmap;             // [n_vertices + 1]: cluster named by a surviving triangle; output vertices before it
+  uint32_t *keep, *tmap;             // [n_triangles + 1]: triangle survives; surviving triangles before it
+  void *temp;                        // rocPRIM's
+  size_t temp_bytes;
+};
+hipError_t decimate_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
+// the bounds pass: s.bounds receives the six bounds (decimate_decode_bound) and the flag; `events`: 2, recorded around it
+hipError_t launch_decimate_bounds(const DecimateMesh &m, const DecimateScratch &s, hipEvent_t *events, hipStream_t stream);
+double decimate_decode_bound(unsigned long long ordered);
+// everything else: `events`: 4, recorded before the keys, after the ranks, after the triangles and after the representatives.
+// Afterwards s.cmap[n_vertices] and s.tmap[n_triangles] hold the output's sizes.
+hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, hipEvent_t *events,
+                                      hipStream_t stream);
 
 }  // namespace dmi

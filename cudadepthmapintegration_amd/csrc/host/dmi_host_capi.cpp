@@ -347,6 +347,7 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_smooth_iterations = o.meshSmoothIterations;
   out->mesh_smooth_lambda = o.meshSmoothLambda;
   out->mesh_smooth_mu = o.meshSmoothMu;
+  out->mesh_decimate_cell_size = o.meshDecimateCellSize;
   return 1;
   });
 }

@@ -154,6 +154,13 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
       {"--meshSmoothMu", {Kind::kValue, "with --extractMesh: the smoothing's negative factor, <= 0 (default -0.53; 0 = plain Laplacian "
                                         "smoothing; not in the reference)",
                           into_checked_double(&o->meshSmoothMu, &o->meshSmoothMuGiven, [](double x) { return x <= 0.0; })}},
+      {"--meshDecimateCellSize", {Kind::kValue, "with --extractMesh: decimate the mesh on the GPU by vertex clustering, after the component "
+                                                "flags and the smoothing: the vertices of one cubic cell of this size (world units, "
+                                                "finite and > 0) become their mean, collapsed and duplicate triangles go; a tiny value "
+                                                "only welds coincident vertices; with --meshNormals the Normals written are then the "
+                                                "decimated mesh's geometric normals, with --meshRegionIds the components are labelled again "
+                                                "on the decimated mesh (default 0 = off; not in the reference)",
+                                  into_checked_double(&o->meshDecimateCellSize, &o->meshDecimateCellSizeGiven, [](double x) { return x > 0.0; })}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -234,6 +241,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
       err << "Error : " << flag.first << " needs --extractMesh (the smoothing belongs to the extracted mesh).\n" << HelpText();
       return false;
     }
+  if (o->meshDecimateCellSizeGiven && !o->extractMesh) {
+    err << "Error : --meshDecimateCellSize needs --extractMesh (the decimation belongs to the extracted mesh).\n" << HelpText();
+    return false;
+  }
   // rmain:257-262
   if (!o->gridSpacing.empty() && !o->gridDims.empty()) {
     err << "Error : Spacing and dimensions can't be both set\n" << HelpText();
@@ -599,6 +610,16 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
         rc = dmi_smooth_isosurface(ctx, (int32_t)o.meshSmoothIterations, o.meshSmoothLambda, o.meshSmoothMu);
         if (rc == DMI_OK) rc = dmi_get_isosurface_smooth_kernel_ms(ctx, &result->meshSmoothKernelMs);
       }
+      if (rc == DMI_OK && o.meshDecimateCellSize > 0) {  // last: on the mesh the component flags and the smoothing left
+        result->meshVerticesBeforeDecimation = nv;
+        result->meshTrianglesBeforeDecimation = nt;
+        rc = dmi_decimate_isosurface(ctx, o.meshDecimateCellSize, &nv, &nt);
+        if (rc == DMI_OK) rc = dmi_get_isosurface_decimate_kernel_ms(ctx, &result->meshDecimateKernelMs);
+        if (rc == DMI_OK && o.meshRegionIds) {  // a cluster may have joined components: RegionId is labelled anew, nothing dropped
+          uint64_t found = 0, kept = 0;
+          rc = dmi_filter_isosurface_components(ctx, DMI_COMPONENTS_MIN_TRIANGLES, 0, &nv, &nt, &found, &kept);
+        }
+      }
       if (rc == DMI_OK) {
         meshVertices.resize((size_t)nv * 3);
         meshTriangles.resize((size_t)nt * 3);
@@ -644,6 +665,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (o.meshSmoothIterations > 0)
       log << "mesh smoothing: " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
           << "; " << result->meshSmoothKernelMs << " ms of GPU kernels" << std::endl;
+    if (o.meshDecimateCellSize > 0)
+      log << "mesh decimation: cell size " << o.meshDecimateCellSize << "; " << result->meshVerticesBeforeDecimation << " vertices, "
+          << result->meshTrianglesBeforeDecimation << " triangles before, " << result->meshVertices << " vertices, "
+          << result->meshTriangles << " triangles after; " << result->meshDecimateKernelMs << " ms of GPU kernels" << std::endl;
   } else {
     // Said whatever --verbose is: the reference writes a mesh here (rmain:166-187) and this tool does not.
     log << "warning: " << o.outputMeshFilename << " is NOT written: the iso-surface (vtkContourFilter) is not part of this tool; "
@@ -674,6 +699,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (o.meshSmoothIterations > 0)  // (only with --extractMesh)
       out << "  mesh smoothing  " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
           << ", " << result->meshSmoothKernelMs << " ms of GPU kernels\n";
+    if (o.meshDecimateCellSize > 0)  // (only with --extractMesh)
+      out << "  mesh decimation  cell size " << o.meshDecimateCellSize << ", " << result->meshVerticesBeforeDecimation << " vertices, "
+          << result->meshTrianglesBeforeDecimation << " triangles before, " << result->meshVertices << " vertices, "
+          << result->meshTriangles << " triangles after, " << result->meshDecimateKernelMs << " ms of GPU kernels\n";
     if (!o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << " (no surface extracted)\n";
     out << "time\n  reconstruction  " << result->reconstructionSeconds << " s\n  total           " << result->totalSeconds << " s\n";

@@ -12,7 +12,9 @@
 // and --meshRegionIds writes the point array RegionId (Int64: the kept components numbered by ascending label).
 // --meshSmoothIterations N with --meshSmoothLambda / --meshSmoothMu (not in the reference: what a smoothing filter behind those
 // would do) runs dmi_smooth_isosurface on the device after the component flags; with --meshNormals the Normals written are then
-// the smoothed mesh's geometric ones.  Without --extractMesh
+// the smoothed mesh's geometric ones.  --meshDecimateCellSize v (not in the reference: what a vtkQuadricClustering or a
+// vtkCleanPolyData behind those would do) runs dmi_decimate_isosurface last, before the downloads; with --meshRegionIds the
+// labelling then runs again on the decimated mesh.  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
@@ -51,6 +53,9 @@ struct Options {
   long long meshSmoothIterations = 0;
   double meshSmoothLambda = 0.5, meshSmoothMu = -0.53;
   bool meshSmoothIterationsGiven = false, meshSmoothLambdaGiven = false, meshSmoothMuGiven = false;
+  // not in the reference (needs --extractMesh): vertex clustering on the GPU after the smoothing, cells of this size (0: off)
+  double meshDecimateCellSize = 0.0;
+  bool meshDecimateCellSizeGiven = false;
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -73,6 +78,9 @@ struct RunResult {
   // meshTriangles are then the filtered mesh's)
   unsigned long long meshVerticesExtracted = 0, meshTrianglesExtracted = 0, meshComponents = 0, meshComponentsKept = 0;
   double meshSmoothKernelMs = 0.0;  // --meshSmoothIterations: hipEvent time of the smoothing's kernels
+  // --meshDecimateCellSize: the mesh that went into the decimation and the hipEvent time of its kernels
+  unsigned long long meshVerticesBeforeDecimation = 0, meshTrianglesBeforeDecimation = 0;
+  double meshDecimateKernelMs = 0.0;
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.

@@ -235,6 +235,24 @@ hipError_t sort_keys(void *temp, size_t *temp_bytes, uint64_t *a, uint64_t *b, u
   return e;
 }
 
+// The vertex -> triangle incidence of the normals: the 3 T keys (v << Bt | t) written to inc_a and sorted into inc_a or inc_b
+// (*incidence), row v's triangles ascending in t, and row_start[v], v in [0, V], its rows
+hipError_t build_incidence(const int64_t *tris, uint64_t nv, uint64_t nt, uint64_t *inc_a, uint64_t *inc_b, uint32_t *row_start, void *temp,
+                           size_t temp_bytes, const uint64_t **incidence, hipStream_t stream) {
+  const int id_bits = bits_for(nv), triangle_bits = bits_for(nt);
+  hipError_t e = hipSuccess;
+  uint64_t *inc_sorted = inc_a;
+  if (nt) {
+    hipLaunchKernelGGL(smooth_incidence_keys_kernel, dim3(blocks(nt)), dim3(kBlock), 0, stream, tris, nt, nv, id_bits, triangle_bits, inc_a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t bytes = temp_bytes;
+    if ((e = sort_keys(temp, &bytes, inc_a, inc_b, 3 * nt, id_bits + triangle_bits, &inc_sorted, stream)) != hipSuccess) return e;
+  }
+  *incidence = inc_sorted;
+  hipLaunchKernelGGL(smooth_row_start_kernel, dim3(blocks(nv + 1)), dim3(kBlock), 0, stream, inc_sorted, (uint32_t)(3 * nt), nv, triangle_bits, row_start);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // the storage rocPRIM asks for: the largest of the two sorts' and the scan's
@@ -283,18 +301,8 @@ hipError_t launch_isosurface_smooth(const SmoothMesh &m, const SmoothScratch &s,
   // the incidence of the normals: its 3 T keys in the second half of the spare buffer, sorted into it or into the first half of
   // the buffer that held the sorted edge keys (read for the last time by the fill kernel above)
   const uint64_t *incidence = nullptr;
-  if (m.normals_out) {
-    uint64_t *inc_a = spare + 3 * nt, *inc_b = sorted, *inc_sorted = inc_a;
-    if (nt) {
-      hipLaunchKernelGGL(smooth_incidence_keys_kernel, dim3(blocks(nt)), dim3(kBlock), 0, stream, m.triangles, nt, nv, id_bits, triangle_bits, inc_a);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      bytes = s.temp_bytes;
-      if ((e = sort_keys(s.temp, &bytes, inc_a, inc_b, 3 * nt, id_bits + triangle_bits, &inc_sorted, stream)) != hipSuccess) return e;
-    }
-    incidence = inc_sorted;
-    hipLaunchKernelGGL(smooth_row_start_kernel, dim3(blocks(nv + 1)), dim3(kBlock), 0, stream, incidence, (uint32_t)(3 * nt), nv, triangle_bits, s.row_start);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
+  if (m.normals_out && (e = build_incidence(m.triangles, nv, nt, spare + 3 * nt, sorted, s.row_start, s.temp, s.temp_bytes, &incidence, stream)) != hipSuccess)
+    return e;
   if ((e = mark(1)) != hipSuccess) return e;
   const double *in = m.vertices;
   int next = 0;
@@ -313,6 +321,17 @@ hipError_t launch_isosurface_smooth(const SmoothMesh &m, const SmoothScratch &s,
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return mark(3);
+}
+
+hipError_t launch_isosurface_geometric_normals(const double *vertices, const int64_t *triangles, uint64_t n_vertices, uint64_t n_triangles,
+                                               uint64_t *const keys[2], uint32_t *row_start, void *temp, size_t temp_bytes,
+                                               float *normals_out, hipStream_t stream) {
+  const uint64_t *incidence = nullptr;
+  const hipError_t e = build_incidence(triangles, n_vertices, n_triangles, keys[0], keys[1], row_start, temp, temp_bytes, &incidence, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(smooth_normals_kernel, dim3(blocks(n_vertices)), dim3(kBlock), 0, stream, vertices, triangles, incidence, row_start, n_vertices,
+                     bits_for(n_triangles), normals_out);
+  return hipGetLastError();
 }
 
 }  // namespace dmi

@@ -47,7 +47,8 @@ extern "C" {
                            *    dmi_download_isosurface_normals; dmi_filter_isosurface_components, dmi_download_isosurface_regions,
                            *    dmi_get_isosurface_filter_kernel_ms, dmi_get_isosurface_filter_pass_ms,
                            *    dmi_get_isosurface_filter_cas_retries; dmi_smooth_isosurface, dmi_get_isosurface_smooth_kernel_ms,
-                           *    dmi_get_isosurface_smooth_pass_ms */
+                           *    dmi_get_isosurface_smooth_pass_ms; dmi_decimate_isosurface, dmi_get_isosurface_decimate_kernel_ms,
+                           *    dmi_get_isosurface_decimate_pass_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -340,6 +341,48 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
  * nothing to do. */
 int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last);
 int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]);
+
+/* Decimation of the context's mesh on the device by vertex clustering (Rossignac-Borrel): what a vtkQuadricClustering or, with a
+ * tiny cell, a vtkCleanPolyData placed behind the contour does (only the intent is shared, not the numbers).  Additions to ABI 5;
+ * csrc/isosurface_decimate.hip.  The input is the mesh the context holds: V vertices (f64 world positions p) and T triangles of
+ * vertex ids -- the last extraction's, the last component filter's or the last smoothing's.  Definition, met bit
+ * for bit:
+ *   - BOUNDS: lo_d and hi_d are the minimum and the maximum of p[v][d] over all V vertices (exact, independent of order);
+ *   - a non-finite coordinate anywhere refuses the call;
+ *   - BINS, with h = cell_size: b_d(v) = floor((p[v][d] - lo_d) / h) in f64, the subtraction and the division each rounded, no
+ *     reciprocal; n_d = b_d evaluated at hi_d, plus 1; any n_d > 2^21 refuses the call (the key (b_2*n_1 + b_1)*n_0 + b_0 stays
+ *     within 63 bits);
+ *   - a CLUSTER is the set of all input vertices with the same (b_0, b_1, b_2), whether a triangle names them or not; clusters
+ *     are ordered by ascending (b_2, b_1, b_0);
+ *   - the REPRESENTATIVE of a cluster with k members of ascending old id m_0 < m_1 < ...:
+ *     s_d = ((p[m_0][d] + p[m_1][d]) + p[m_2][d]) + ... added left to right, r_d = s_d / (double)k; f64, no FMA (a cluster of
+ *     one keeps its vertex's bits);
+ *   - TRIANGLES: each id is replaced by its cluster; a triangle with two equal new ids is DEGENERATE and dropped; two
+ *     non-degenerate triangles whose new ids are the same SET (any order, either orientation) are DUPLICATES, and of each such
+ *     group only the one with the lowest original index survives; the survivors keep their original relative order and their
+ *     stored vertex order (orientation is kept); a triangle that names an id >= V is dropped (the filter and the smoother skip
+ *     such triangles in the same way);
+ *   - VERTICES: only clusters named by at least one surviving triangle are output, numbered 0, 1, 2, ... in cluster order, and
+ *     the triangles carry these numbers: the output has no unreferenced vertex, no degenerate and no duplicate triangle;
+ *   - NORMALS: if the mesh carries normals they are replaced by the geometric normals of the decimated mesh, dmi_smooth_isosurface's
+ *     definition word for word (the area-weighted cross products of the incident triangles in ascending triangle index, their
+ *     sum normalised unless its length is 0, rounded to f32) and its kernel; a mesh without normals stays without;
+ *   - REGIONS: RegionId and RegionSize of an earlier filter no longer describe this mesh (a cluster may join components): after
+ *     a successful decimation dmi_download_isosurface_regions is refused, exactly as after a fresh extraction, until a filter
+ *     runs again.  A later filter or smoothing takes the decimated mesh as its input; the next extraction replaces it.
+ * Returns the new mesh's sizes.  An empty mesh is a success (0, 0); a mesh whose every triangle collapses (cell_size exceeds the
+ * bounding box) is a success that leaves 0 vertices and 0 triangles.  DMI_ERR_INVALID_ARGUMENT: a null context or null count
+ * pointers; a cell_size that is NaN, infinite or <= 0; no successful extraction yet; a non-finite vertex coordinate; any
+ * n_d > 2^21 (the message names the smallest acceptable cell size); V or T >= 2^32.  A call that fails leaves the context's mesh,
+ * normals and regions exactly as they were: no kernel writes the mesh's own buffers, the result is built in the alternates and
+ * swapped in last.  Synchronises twice: once to learn the bounds (and to refuse), once for the counts; the normals are enqueued
+ * behind the second and nothing waits for them. */
+int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vertices, uint64_t *n_triangles);
+/* hipEvent time of all kernels of the last dmi_decimate_isosurface (the sum of its passes), and pass by pass: out[0] clustering
+ * (bounds, keys, sort, ranks), out[1] representatives, out[2] triangles (remap, degenerate and duplicate removal, vertex and
+ * triangle compaction), out[3] normals.  Zeros after a call that had nothing to do.  Waits for the last call's normals. */
+int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last);
+int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]);
 
 /* Diagnostic: how many (8 x 8 x column brick, view) pairs of the last dmi_fuse were proven to be handled
  * uniformly.  out[0] mixed (per-voxel path), out[1] all voxels accumulate -eta*rho, out[2] all accumulate 0,

@@ -102,6 +102,8 @@ typedef struct dmi_cli_options {
   int64_t mesh_smooth_iterations;        /* --meshSmoothIterations N: Taubin iterations after the component flags; 0: off */
   double mesh_smooth_lambda;             /* --meshSmoothLambda (default 0.5) */
   double mesh_smooth_mu;                 /* --meshSmoothMu (default -0.53) */
+  /* not in the reference, only with --extractMesh (dmi_decimate_isosurface, dmi.h); appended to the struct: */
+  double mesh_decimate_cell_size;        /* --meshDecimateCellSize v: vertex clustering after the smoothing, world units; 0: off */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -111,7 +113,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * --meshNormals too, dmi_extract_isosurface_normals and dmi_write_polydata_with_normals.  With --meshMinComponentTriangles
  * and / or --meshLargestComponent the mesh goes through dmi_filter_isosurface_components first (by size, then the largest), and
  * with --meshRegionIds the file is dmi_write_polydata_with_arrays' with RegionId.  With --meshSmoothIterations N the mesh goes
- * through dmi_smooth_isosurface after those (the Normals of --meshNormals are then the smoothed mesh's geometric ones). */
+ * through dmi_smooth_isosurface after those (the Normals of --meshNormals are then the smoothed mesh's geometric ones).  With
+ * --meshDecimateCellSize v it goes through dmi_decimate_isosurface last (Normals: the decimated mesh's geometric ones; RegionId:
+ * from the labelling run again on the decimated mesh). */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of

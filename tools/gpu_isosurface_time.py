@@ -7,11 +7,15 @@ size histogram, a floor derived from the bytes the filter must move, and the hos
 of tests/isosurface_components_np.py, imported from there) for orientation.  With --smooth N it times dmi_smooth_isosurface
 (N iterations) in the same alternating style, once on the raw mesh and once after MIN(--min-triangles): pass by pass, one step
 against the bytes it must move, the scratch it needs, and the numpy restatement (tests/isosurface_smooth_np.py) on the raw
-mesh for orientation.  --grid N runs the whole tool on an N^3 grid (a quick
+mesh for orientation.  With --decimate H (grid spacings; several may be given; a tiny H that the mesh's 2^21 bins refuse
+becomes the smallest size it accepts: the weld) it times dmi_decimate_isosurface after a fresh extraction with normals, pass by
+pass, with the counts before and after and the bytes each pass must move; --decimate-check compares with the numpy restatement
+(tests/isosurface_decimate_np.py).  --grid N runs the whole tool on an N^3 grid (a quick
 run; the records in profiles/ are of the default 512).
 
     python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
                                          [--smooth 10 [--smooth-lambda 0.5] [--smooth-mu -0.53]]
+                                         [--decimate 2 [--decimate 4 ...] [--decimate-check]]
 """
 import argparse
 import json
@@ -138,6 +142,51 @@ def smooth_record(ctx, a):
     return rec
 
 
+def decimate_record(ctx, a):
+    """The --decimate record of the context's grid at a.iso: vertex clustering with cells of a.decimate grid spacings, a.repeat
+    rounds after a warm-up round.  In every round the decimation follows a fresh extraction with normals whose own kernel time is
+    taken in the same breath.  With a.decimate_check the numpy restatement runs on the raw mesh and is compared bit for bit."""
+    import time
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))   # the host alternative IS the tests' numpy restatement
+    import isosurface_decimate_np as D
+    h = a.decimate * float(min(scene.default_grid(a.grid).spacing))
+    rec = {"cell_size_spacings": a.decimate, "cell_size": h, "kernel_ms": [], "pass_ms": [], "extraction_kernel_ms": []}
+    for r in range(a.repeat + 1):                       # round 0 is the warm-up: buffers sized, code loaded
+        raw = ctx.extract_isosurface_with_normals(a.iso)
+        ex = ctx.isosurface_kernel_ms()
+        if r == 0 and a.decimate < 1e-3:                # a weld: the smallest size this mesh accepts, if the one asked for is refused
+            h = rec["cell_size"] = max(h, D.min_cell_size(raw[0]))
+        rec["vertices"], rec["triangles"] = len(raw[0]), len(raw[1])
+        rec["vertices_after"], rec["triangles_after"] = ctx.decimate_isosurface(h)
+        if r:
+            rec["extraction_kernel_ms"].append(ex)
+            rec["kernel_ms"].append(ctx.isosurface_decimate_kernel_ms())
+            rec["pass_ms"].append(ctx.isosurface_decimate_pass_ms())
+    nv, nt, nv2, nt2 = rec["vertices"], rec["triangles"], rec["vertices_after"], rec["triangles_after"]
+    rec["kernel_ms_min"] = min(rec["kernel_ms"])
+    rec["extraction_kernel_ms_min"] = min(rec["extraction_kernel_ms"])
+    rec["over_extraction"] = rec["kernel_ms_min"] / rec["extraction_kernel_ms_min"]
+    for p in ("clustering", "representatives", "triangles", "normals"):
+        rec[p + "_ms_min"] = min(q[p] for q in rec["pass_ms"])
+    # what each pass must move at least: positions read twice (bounds, keys) and key, id and cluster written once; triangles read
+    # twice (keys, compaction), key and value written once, survivors written; positions and ids read, representatives written;
+    # output triangles and positions read, normals written
+    floors = {"clustering": 2 * 24 * nv + 16 * nv, "triangles": 2 * 24 * nt + 16 * nt + 24 * nt2,
+              "representatives": 28 * nv + 24 * nv2, "normals": 24 * nt2 + 24 * nv2 + 12 * nv2}
+    rec["floor_bytes"] = floors
+    rec["floor_ms_c2p_rate"] = {k: v / C2P_TBPS / 1e9 for k, v in floors.items()}
+    # the scratch of the call (DESIGN.md 8f), rocPRIM's own storage aside
+    rec["scratch_bytes"] = 2 * max(nv, 2 * nt, 3 * nt) * 8 + 32 * (nv + 1) + 8 * (nt + 1)
+    if a.decimate_check:
+        got = ctx.download_isosurface() + (ctx.download_isosurface_normals(),)
+        t0 = time.perf_counter()
+        want = D.decimate(raw[0], raw[1], h, raw[2])
+        rec["host_numpy_s"] = time.perf_counter() - t0
+        rec["host_matches_gpu"] = all(w.tobytes() == g.tobytes() for w, g in zip(want, got))
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iso", type=float, default=1.0)
@@ -149,6 +198,9 @@ def main():
     ap.add_argument("--smooth", type=int, default=0, help="also time the Taubin smoothing with this many iterations (0: not)")
     ap.add_argument("--smooth-lambda", type=float, default=0.5)
     ap.add_argument("--smooth-mu", type=float, default=-0.53)
+    ap.add_argument("--decimate", type=float, action="append", default=[],
+                    help="also time the vertex clustering with cells of this many grid spacings (may be given several times)")
+    ap.add_argument("--decimate-check", action="store_true", help="... and compare each with the numpy restatement, bit for bit")
     ap.add_argument("--grid", type=int, default=512, help="cells per axis (512: the cfg-3 grid)")
     a = ap.parse_args()
     grid = scene.default_grid(a.grid)
@@ -175,6 +227,9 @@ def main():
         nv, nt = len(verts), len(tris)
         comp = components_record(ctx, a) if a.components else None
         smooth = smooth_record(ctx, a) if a.smooth > 0 else None
+        decimate = []
+        for h in a.decimate:
+            decimate.append(decimate_record(ctx, argparse.Namespace(**{**vars(a), "decimate": h})))
     n_points = (a.grid + 1) ** 3
     lattice = n_points * 8
     out = {"iso": a.iso, "views": a.views, "vertices": nv, "triangles": nt, "kernel_ms": times, "kernel_ms_min": min(times),
@@ -188,6 +243,8 @@ def main():
         out["components"] = comp
     if smooth is not None:
         out["smooth"] = smooth
+    if decimate:
+        out["decimate"] = decimate
     print(json.dumps(out))
 
 
