@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "dmi_get_isosurface_filter_pass_ms", "dmi_get_isosurface_filter_cas_retries",
     "dmi_smooth_isosurface", "dmi_get_isosurface_smooth_kernel_ms", "dmi_get_isosurface_smooth_pass_ms",
     "dmi_decimate_isosurface", "dmi_get_isosurface_decimate_kernel_ms", "dmi_get_isosurface_decimate_pass_ms",
+    "dmi_color_process_isosurface", "dmi_download_isosurface_colors", "dmi_get_isosurface_color_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -232,6 +233,9 @@ def load() -> ctypes.CDLL:
     L.dmi_color_add_views_with_depth.argtypes = [vp, u8p, dp, dp, dp, i32, i32, i32]
     L.dmi_color_set_depth_test.argtypes = [vp, i32, ctypes.c_double]
     L.dmi_color_last_error.argtypes = []
+    L.dmi_color_process_isosurface.argtypes = [vp, vp, i32, dbl, ctypes.POINTER(ctypes.c_uint64)]
+    L.dmi_download_isosurface_colors.argtypes = [vp, u8p, u8p, ctypes.POINTER(ctypes.c_int32)]
+    L.dmi_get_isosurface_color_kernel_ms.argtypes = [vp, dp]
     L.dmi_color_last_error.restype = ctypes.c_char_p
     i64, i64p, i32p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
@@ -605,6 +609,35 @@ class FusionContext:
         a = (ctypes.c_double * 4)()
         self._check(self._lib.dmi_get_isosurface_decimate_pass_ms(self._h, a))
         return dict(zip(("clustering", "representatives", "triangles", "normals"), (float(x) for x in a)))
+
+    def color_isosurface(self, color_ctx: "ColorContext", fused_depth_tolerance: float | None = None) -> int:
+        """Colour the context's mesh where it is, with the views resident in `color_ctx`; returns the number of vertices.  The
+        three arrays stay on the device until download_isosurface_colors.  fused_depth_tolerance None: what
+        color_ctx.process(<the downloaded vertices>) returns, bit for bit.  A number: the visibility test with the depths this
+        context fused (thresholded by the best cost), view m of `color_ctx` being view m of this context
+        (dmi_color_process_isosurface).  Any later change of the mesh drops the colours."""
+        nv = ctypes.c_uint64(0)
+        fused = fused_depth_tolerance is not None
+        self._check(self._lib.dmi_color_process_isosurface(color_ctx._h, self._h, 1 if fused else 0,
+                                                           float(fused_depth_tolerance) if fused else 0.0, ctypes.byref(nv)))
+        return int(nv.value)
+
+    def download_isosurface_colors(self):
+        """(mean [n, 3] u8, median [n, 3] u8, count [n] i32) of the last color_isosurface (dmi_download_isosurface_colors)."""
+        nv, _, _ = self._current_mesh_counts()
+        mean = np.zeros((max(nv, 1), 3), dtype=np.uint8)    # never a null pointer: null means "not wanted"
+        median = np.zeros((max(nv, 1), 3), dtype=np.uint8)
+        count = np.zeros(max(nv, 1), dtype=np.int32)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.dmi_download_isosurface_colors(self._h, mean.ctypes.data_as(u8), median.ctypes.data_as(u8),
+                                                             count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return mean[:nv], median[:nv], count[:nv]
+
+    def isosurface_color_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last color_isosurface (dmi_get_isosurface_color_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_isosurface_color_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
 
     def isosurface_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last extract_isosurface or extract_isosurface_with_normals
@@ -1007,7 +1040,7 @@ HOST_ABI_SYMBOLS = [
     "dmi_filter_last_error", "dmi_read_krtd_file", "dmi_extract_all_file_path", "dmi_k3_to_k4",
     "dmi_apply_depth_threshold", "dmi_read_depth_map", "dmi_read_depth_map_color", "dmi_mesh_coloration_from_lists",
     "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata", "dmi_write_polydata_with_normals",
-    "dmi_write_polydata_with_arrays",
+    "dmi_write_polydata_with_arrays", "dmi_write_polydata_with_colors",
     "dmi_mesh_coloration_from_lists_with_depth", "dmi_read_polydata", "dmi_polydata_free", "dmi_polydata_counts",
     "dmi_polydata_array", "dmi_polydata_designations", "dmi_color_cli_read_arguments", "dmi_color_cli_main",
 ]
@@ -1084,6 +1117,9 @@ def load_host() -> ctypes.CDLL:
     L.dmi_write_polydata_with_arrays.restype = ctypes.c_int
     L.dmi_write_polydata_with_arrays.argtypes = [ctypes.c_char_p, dp, i64, ctypes.POINTER(ctypes.c_int64), i64,
                                                  ctypes.POINTER(ctypes.c_float), ctypes.c_double, ctypes.POINTER(ctypes.c_int64)]
+    L.dmi_write_polydata_with_colors.restype = ctypes.c_int
+    L.dmi_write_polydata_with_colors.argtypes = L.dmi_write_polydata_with_arrays.argtypes + [
+        ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)]
     _host_bound = True
     return L
 
@@ -1189,7 +1225,8 @@ class CliOptionsC(ctypes.Structure):
                 ("mesh_normals", ctypes.c_int32), ("mesh_largest_component", ctypes.c_int32), ("mesh_region_ids", ctypes.c_int32),
                 ("mesh_min_component_triangles", ctypes.c_int64), ("mesh_smooth_iterations", ctypes.c_int64),
                 ("mesh_smooth_lambda", ctypes.c_double), ("mesh_smooth_mu", ctypes.c_double),
-                ("mesh_decimate_cell_size", ctypes.c_double)]
+                ("mesh_decimate_cell_size", ctypes.c_double), ("mesh_coloration", ctypes.c_int32),
+                ("mesh_coloration_fused", ctypes.c_int32), ("mesh_coloration_depth_tolerance", ctypes.c_double)]
 
 
 def cli_read_arguments(args):
@@ -1231,9 +1268,10 @@ def write_polydata_with_normals(path, points, triangles, normals, contour):
         raise OSError(f"dmi_write_polydata_with_normals failed: {path}")
 
 
-def write_polydata_with_arrays(path, points, triangles, normals=None, contour=0.0, region_ids=None):
+def write_polydata_with_arrays(path, points, triangles, normals=None, contour=0.0, region_ids=None, colors=None):
     """dmi_write_polydata_with_arrays: write_polydata's file (normals None) or write_polydata_with_normals' plus the point array
-    RegionId ([n] int64) when region_ids is given; no GPU needed."""
+    RegionId ([n] int64) when region_ids is given; with colors = (mean [n, 3] u8, median [n, 3] u8, count [n] i32) the arrays
+    MeanColoration, MedianColoration and NbProjectedDepthMap behind those (dmi_write_polydata_with_colors); no GPU needed."""
     L = load_host()
     p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     t = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
@@ -1248,9 +1286,20 @@ def write_polydata_with_arrays(path, points, triangles, normals=None, contour=0.
         if r.shape[0] != p.shape[0]:
             raise ValueError(f"region ids {r.shape} do not match points {p.shape}")
         r = np.concatenate([r, np.zeros(1, np.int64)])
-    ok = L.dmi_write_polydata_with_arrays(os.fsencode(path), _dp(p), p.shape[0], t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                          t.shape[0], None if n is None else n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                          float(contour), None if r is None else r.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+    args = [os.fsencode(path), _dp(p), p.shape[0], t.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            t.shape[0], None if n is None else n.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            float(contour), None if r is None else r.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))]
+    if colors is not None:
+        mean = np.concatenate([np.ascontiguousarray(colors[0], dtype=np.uint8).reshape(-1, 3), np.zeros((1, 3), np.uint8)])
+        median = np.concatenate([np.ascontiguousarray(colors[1], dtype=np.uint8).reshape(-1, 3), np.zeros((1, 3), np.uint8)])
+        count = np.concatenate([np.ascontiguousarray(colors[2], dtype=np.int32).reshape(-1), np.zeros(1, np.int32)])
+        if not (mean.shape[0] == median.shape[0] == count.shape[0] == p.shape[0] + 1):
+            raise ValueError("colors do not match points")
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        ok = L.dmi_write_polydata_with_colors(*args, mean.ctypes.data_as(u8), median.ctypes.data_as(u8),
+                                              count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+    else:
+        ok = L.dmi_write_polydata_with_arrays(*args)
     if not ok:
         raise OSError(f"dmi_write_polydata_with_arrays failed: {path}")
 

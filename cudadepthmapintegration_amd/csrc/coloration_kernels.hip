@@ -19,7 +19,12 @@
 //
 // Opt-in and not in the reference: the visibility test (dmi_color_set_depth_test, DESIGN.md 8b'): with resident depth planes a
 // pair counts only if the vertex's camera z is > 0 and within a tolerance of the view's depth (> 0) at the pixel.
+//
+// The vertices may also be on the device already (dmi::color_device_vertices, for dmi_color_process_isosurface: the mesh of a
+// fusion context): the same chunk body with a chunk being an offset into the caller's device arrays, and the depth
+// of the visibility test optionally read from the fusion context's own tables (FusedDepth).
 #include "../../include/dmi.h"
+#include "dmi_context.h"
 #include "fusion_kernels.h"
 
 #include <stdlib.h>
@@ -285,9 +290,23 @@ struct MedianSeed {
 struct DepthTest {
   const double *const *planes;  // [view] -> tiled plane (pack_depth_kernel)
   double tol;
+  __device__ __forceinline__ double depth_at(int m, int px, int py, int tiles_x, int) const {
+    return cload(&planes[m])[texel_index(px, py, tiles_x)];
+  }
+};
+// The same test with the depth taken from a fusion context's resident tables (dmi_color_process_isosurface): per view
+// a plain [H][W] table of T = float or double, top image row first (what dmi_add_views* left: thresholded, flipped, narrowed when
+// the store is f32), widened to f64 where it is compared.
+template <typename T>
+struct FusedDepth {
+  const T *const *tables;  // [view] -> that view's table inside its Batch::d_depth
+  double tol;
+  __device__ __forceinline__ double depth_at(int m, int px, int py, int, int W) const {
+    return (double)cload(&tables[m])[(int64_t)py * W + px];
+  }
 };
 template <typename... T>
-__device__ __forceinline__ DepthTest depth_test_of(T... t) {
+__device__ __forceinline__ auto depth_test_of(T... t) {
   if constexpr (sizeof...(T) == 0) return DepthTest{nullptr, 0.0};
   else return (t, ...);
 }
@@ -295,9 +314,9 @@ __device__ __forceinline__ DepthTest depth_test_of(T... t) {
 // HIST: also fill, per lane, 16-bin histograms of the upper nibbles of the three channels in LDS (every lane owns a
 // column of counters: no barrier, no conflict) and leave the MedianSeed of the vertex: the first of the two passes of
 // the histogram medians costs no read of the scratch table.
-// Depth (one DepthTest or nothing): a pair counts only if, besides the bounds test, the vertex's camera z cz (the reference's
-// TransformPoint row 2, every operation rounded) is > 0, the view's depth d at the pixel is > 0 and fabs(cz - d) <= tol.  The
-// depth is gathered in the same step as the texel and the test is made where the texel is consumed.
+// Depth (one DepthTest, one FusedDepth<float / double> or nothing): a pair counts only if, besides the bounds test, the vertex's
+// camera z cz (the reference's TransformPoint row 2, every operation rounded) is > 0, the view's depth d at the pixel is > 0 and
+// fabs(cz - d) <= tol.  The depth is gathered in the same step as the texel and the test is made where the texel is consumed.
 template <bool HIST, bool PIPE, typename... Depth>
 __global__ __launch_bounds__(256) void project_color_kernel(const double *__restrict__ points, int64_t nv,
                                                             const uint32_t *__restrict__ perm,
@@ -306,7 +325,7 @@ __global__ __launch_bounds__(256) void project_color_kernel(const double *__rest
                                                             int32_t *__restrict__ count, MedianSeed *__restrict__ seeds,
                                                             const ViewMargin *__restrict__ margins, Depth... depth) {
   constexpr bool DEPTH = sizeof...(Depth) > 0;
-  const DepthTest dt = depth_test_of(depth...);
+  const auto dt = depth_test_of(depth...);
   __shared__ uint32_t hist[HIST ? 3 * kHistWords * 256 : 1];  // [channel][word][lane]: 24 KB
   const int lane = threadIdx.x;
   const int tiles_x = (W + kTexTileW - 1) / kTexTileW;
@@ -375,7 +394,7 @@ __global__ __launch_bounds__(256) void project_color_kernel(const double *__rest
     c = make_uchar4(0, 0, 0, 0);
     if (ok) {
       c = cload(&v->color)[texel_index(px, py, tiles_x)];     // RD.cxx:106-108 (row flip and tiling done at upload)
-      if constexpr (DEPTH) d = cload(&dt.planes[m])[texel_index(px, py, tiles_x)];
+      if constexpr (DEPTH) d = dt.depth_at(m, px, py, tiles_x, W);
     }
   };
   if constexpr (PIPE) {
@@ -604,6 +623,11 @@ struct dmi_color_context {
   // the visibility test (dmi_color_set_depth_test): per view its depth plane or null, and the same on the device
   std::vector<const double *> h_depth_planes;
   const double **d_depth_planes = nullptr;
+  // the fused form of the test (dmi::color_device_vertices): per view its table in the fusion context, for the call being made
+  std::vector<const void *> h_fused_tables;
+  const void **d_fused_tables = nullptr;
+  size_t fused_tables_capacity = 0;  // views
+  double *d_sample = nullptr;  // the in-place form's sample of vertices (coherence_sample_kernel)
   bool depth_test = false;
   double depth_tol = 0.0;
   bool views_dirty = false;
@@ -627,6 +651,7 @@ struct dmi_color_context {
   size_t sort_temp_bytes = 0;
   unsigned long long *d_box = nullptr;
   size_t chunk_capacity = 0, scratch_capacity = 0;
+  size_t staging_capacity = 0;  // vertices each of d_points / d_mean / d_median / d_count holds (the staged form only)
   uint8_t *d_stage = nullptr;
   size_t stage_capacity = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -722,7 +747,7 @@ void dmi_color_destroy(dmi_color_context *c) {
   for (hipStream_t st : {c->h2d, c->stream, c->d2h})
     if (st) (void)hipStreamSynchronize(st);
   for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba), (void)hipFree(b.d_depth);
-  for (void *p : {(void *)c->d_views, (void *)c->d_depth_planes, (void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_scratch, (void *)c->d_mean[0], (void *)c->d_mean[1],
+  for (void *p : {(void *)c->d_views, (void *)c->d_depth_planes, (void *)c->d_fused_tables, (void *)c->d_sample, (void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_scratch, (void *)c->d_mean[0], (void *)c->d_mean[1],
                   (void *)c->d_median[0], (void *)c->d_median[1], (void *)c->d_count[0], (void *)c->d_count[1], (void *)c->d_seeds, (void *)c->d_margins[0],
                   (void *)c->d_margins[1], (void *)c->d_pmax[0], (void *)c->d_pmax[1], (void *)c->d_stage, (void *)c->d_keys, (void *)c->d_keys_sorted,
                   (void *)c->d_index, (void *)c->d_perm, c->d_sort_temp, (void *)c->d_box})
@@ -889,47 +914,136 @@ int dmi_color_set_depth_test(dmi_color_context *c, int32_t enable, double tolera
   });
 }
 
+}  // extern "C"
+
 namespace {
 // Are consecutive vertices neighbours in space, as a mesh's are?  A sample of up to 512 consecutive pairs against the same
 // number of pairs half the array apart: coherent when the median step is under a tenth of the median far distance.  What the
 // answer chooses is a loop form of the projection kernel (below), never a result.
-bool vertices_in_coherent_order(const double *p, int64_t n) {
-  if (n < 64) return true;
-  const int64_t samples = std::min<int64_t>(512, n / 2);
+int64_t coherence_samples(int64_t n) { return std::min<int64_t>(512, n / 2); }
+// sample t of `samples` reads the rows i, i + 1 and (i + n / 2) % n with i = coherence_row(t, n, samples)
+__host__ __device__ inline int64_t coherence_row(int64_t t, int64_t n, int64_t samples) { return t * ((n - 1) / samples); }
+// rows: [samples][3][3], the three rows of every sample
+bool sample_in_coherent_order(const double *rows, int64_t samples) {
   std::vector<double> near_d, far_d;
   near_d.reserve((size_t)samples);
   far_d.reserve((size_t)samples);
-  auto dist2 = [&](int64_t a, int64_t b) {
+  auto dist2 = [&](const double *a, const double *b) {
     double s2 = 0.0;
     for (int q = 0; q < 3; ++q) {
-      const double d = p[3 * a + q] - p[3 * b + q];
+      const double d = a[q] - b[q];
       s2 += d * d;
     }
     return std::isfinite(s2) ? s2 : 1.0e300;  // (a NaN / inf vertex: far from everything -- no NaN reaches the partial sort)
   };
   for (int64_t t = 0; t < samples; ++t) {
-    const int64_t i = t * ((n - 1) / samples);
-    near_d.push_back(dist2(i, i + 1));
-    far_d.push_back(dist2(i, (i + n / 2) % n));
+    near_d.push_back(dist2(rows + 9 * t, rows + 9 * t + 3));
+    far_d.push_back(dist2(rows + 9 * t, rows + 9 * t + 6));
   }
   std::nth_element(near_d.begin(), near_d.begin() + near_d.size() / 2, near_d.end());
   std::nth_element(far_d.begin(), far_d.begin() + far_d.size() / 2, far_d.end());
   return near_d[near_d.size() / 2] < 0.01 * far_d[far_d.size() / 2];  // squared distances: a tenth of the distance
 }
-}  // namespace
+bool vertices_in_coherent_order(const double *p, int64_t n) {
+  if (n < 64) return true;
+  const int64_t samples = coherence_samples(n);
+  std::vector<double> rows((size_t)samples * 9);
+  for (int64_t t = 0; t < samples; ++t) {
+    const int64_t i = coherence_row(t, n, samples);
+    const int64_t from[3] = {i, i + 1, (i + n / 2) % n};
+    for (int r = 0; r < 3; ++r)
+      for (int q = 0; q < 3; ++q) rows[(size_t)(9 * t + 3 * r + q)] = p[3 * from[r] + q];
+  }
+  return sample_in_coherent_order(rows.data(), samples);
+}
+// the same sample of vertices that are on the device: rows[t] as above (dmi::color_device_vertices brings them to the host)
+__global__ __launch_bounds__(256) void coherence_sample_kernel(const double *__restrict__ points, int64_t n, int64_t samples,
+                                                               double *__restrict__ rows) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= samples) return;
+  const int64_t i = coherence_row(t, n, samples);
+  const int64_t from[3] = {i, i + 1, (i + n / 2) % n};
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 3; ++q) rows[9 * t + 3 * r + q] = points[3 * from[r] + q];
+}
 
-int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_points, uint8_t *mean, uint8_t *median,
-                      int32_t *count) {
-  return guarded(c, "dmi_color_process", [&]() -> int {
-  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: null context");
-  if (n_points < 0 || (n_points > 0 && (!points || !mean || !median || !count)))
-    return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: null argument");
+// One colouring call: where the vertices are and where the results go.  dmi_color_process stages the caller's host arrays chunk
+// by chunk through the context's double buffers; dmi::color_device_vertices reads and writes device arrays in place, a chunk being
+// an offset into them.  Both run the one chunk body below.
+struct ColorJob {
+  const char *entry = "";
+  int64_t n = 0;
+  const double *h_points = nullptr;  // staged form
+  uint8_t *h_mean = nullptr, *h_median = nullptr;
+  int32_t *h_count = nullptr;
+  const double *d_points = nullptr;  // in-place form
+  uint8_t *d_mean = nullptr, *d_median = nullptr;
+  int32_t *d_count = nullptr;
+  hipEvent_t after = nullptr;                // in place: the context's stream waits for it before anything reads the vertices
+  const void *const *fused_tables = nullptr;  // host array [views] of FusedDepth tables, or null: the context's own settings
+  bool fused_f64 = false;
+  double fused_tol = 0.0;
+  bool in_place() const { return d_points != nullptr; }
+};
+
+// (an allocation that fails leaves the capacities at zero: the next call allocates again)
+int ensure_work_buffers(dmi_color_context *c, size_t chunk, size_t n_views, bool staged) {
+  if (c->chunk_capacity < chunk || c->scratch_capacity < chunk * n_views) {
+    for (hipStream_t st : {c->h2d, c->stream, c->d2h}) DMI_COLOR_HIP(c, hipStreamSynchronize(st));
+    for (void *p : {(void *)c->d_scratch, (void *)c->d_seeds, (void *)c->d_keys, (void *)c->d_keys_sorted, (void *)c->d_index, (void *)c->d_perm,
+                    c->d_sort_temp})
+      if (p) (void)hipFree(p);
+    c->d_scratch = nullptr;
+    c->d_seeds = nullptr;
+    c->d_keys = c->d_keys_sorted = c->d_index = c->d_perm = nullptr;
+    c->d_sort_temp = nullptr;
+    c->sort_temp_bytes = 0;
+    c->chunk_capacity = c->scratch_capacity = 0;
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_scratch, chunk * n_views * sizeof(uchar4)));
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_seeds, chunk * sizeof(MedianSeed)));
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_keys, chunk * 4));
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_keys_sorted, chunk * 4));
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_index, chunk * 4));
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_perm, chunk * 4));
+    if (!c->d_box) DMI_COLOR_HIP(c, hipMalloc(&c->d_box, 6 * sizeof(unsigned long long)));
+    // rocPRIM tells how much temporary storage a sort of `chunk` pairs needs when called without any
+    DMI_COLOR_HIP(c, rocprim::radix_sort_pairs(nullptr, c->sort_temp_bytes, c->d_keys, c->d_keys_sorted, c->d_index, c->d_perm, chunk, 0,
+                                              30, c->stream));
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_sort_temp, std::max<size_t>(c->sort_temp_bytes, 16)));
+    c->chunk_capacity = chunk;
+    c->scratch_capacity = chunk * n_views;
+  }
+  // the double buffers of the staged form: the in-place form never allocates them
+  if (staged && c->staging_capacity < chunk) {
+    for (hipStream_t st : {c->h2d, c->stream, c->d2h}) DMI_COLOR_HIP(c, hipStreamSynchronize(st));
+    for (void *p : {(void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_mean[0], (void *)c->d_mean[1], (void *)c->d_median[0],
+                    (void *)c->d_median[1], (void *)c->d_count[0], (void *)c->d_count[1]})
+      if (p) (void)hipFree(p);
+    c->staging_capacity = 0;
+    for (int b = 0; b < 2; ++b) {
+      c->d_points[b] = nullptr; c->d_mean[b] = nullptr; c->d_median[b] = nullptr; c->d_count[b] = nullptr;
+      DMI_COLOR_HIP(c, hipMalloc(&c->d_points[b], chunk * 24));
+      DMI_COLOR_HIP(c, hipMalloc(&c->d_mean[b], chunk * 3));
+      DMI_COLOR_HIP(c, hipMalloc(&c->d_median[b], chunk * 3));
+      DMI_COLOR_HIP(c, hipMalloc(&c->d_count[b], chunk * 4));
+    }
+    c->staging_capacity = chunk;
+  }
+  return DMI_OK;
+}
+
+// What both forms of a colouring call run (the callers have checked their own arguments).
+int process_vertices(dmi_color_context *c, const ColorJob &job) {
+  const std::string entry = job.entry;
+  const int64_t n_points = job.n;
   const size_t n_views = c->h_views.size();
-  if (n_views == 0) return cfail(c, DMI_ERR_STATE, "dmi_color_process: no views resident (MC.cxx:102-106)");
-  if (c->depth_test)
+  if (n_views == 0) return cfail(c, DMI_ERR_STATE, entry + ": no views resident (MC.cxx:102-106)");
+  const bool fused = job.fused_tables != nullptr;
+  const bool own_test = c->depth_test && !fused;
+  if (own_test)
     for (size_t m = 0; m < n_views; ++m)
       if (!c->h_depth_planes[m])
-        return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: the depth test is on and view " + std::to_string(m) +
+        return cfail(c, DMI_ERR_INVALID_ARGUMENT, entry + ": the depth test is on and view " + std::to_string(m) +
                                                       " was added without depths (dmi_color_add_views_with_depth)");
   c->last_kernel_ms = 0.0;
   if (n_points == 0) return DMI_OK;
@@ -958,7 +1072,6 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
     DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
     c->views_dirty = false;
   }
-  const bool coherent = !c->reorder && vertices_in_coherent_order(points, n_points);
   // vertices per chunk: the scratch table [view][vertex] stays within its budget -- and a call of many vertices is cut into at
   // least four chunks, so that a chunk's copy in, its kernels and its copies out run beside its neighbours' (with the caller's
   // arrays in pinned memory, dmi_alloc_pinned, the copies are DMA transfers; from pageable memory they still are correct)
@@ -966,50 +1079,53 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
   size_t chunk = std::max<size_t>(256, budget / (n_views * sizeof(uchar4)) / 256 * 256);
   chunk = std::min<size_t>(chunk, ((size_t)n_points + 255) / 256 * 256);
   if ((size_t)n_points >= (size_t(1) << 18)) chunk = std::min<size_t>(chunk, std::max<size_t>(size_t(1) << 16, (((size_t)n_points + 3) / 4 + 255) / 256 * 256));
-  if (c->chunk_capacity < chunk || c->scratch_capacity < chunk * n_views) {
-    for (hipStream_t st : {c->h2d, c->stream, c->d2h}) DMI_COLOR_HIP(c, hipStreamSynchronize(st));
-    for (void *p : {(void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_scratch, (void *)c->d_mean[0], (void *)c->d_mean[1], (void *)c->d_median[0],
-                    (void *)c->d_median[1], (void *)c->d_count[0], (void *)c->d_count[1], (void *)c->d_seeds, (void *)c->d_keys, (void *)c->d_keys_sorted,
-                    (void *)c->d_index, (void *)c->d_perm, c->d_sort_temp})
-      if (p) (void)hipFree(p);
-    c->d_scratch = nullptr;
-    c->d_seeds = nullptr;
-    c->d_keys = c->d_keys_sorted = c->d_index = c->d_perm = nullptr;
-    c->d_sort_temp = nullptr;
-    c->sort_temp_bytes = 0;
-    c->chunk_capacity = c->scratch_capacity = 0;
-    for (int b = 0; b < 2; ++b) {
-      c->d_points[b] = nullptr; c->d_mean[b] = nullptr; c->d_median[b] = nullptr; c->d_count[b] = nullptr;
-      DMI_COLOR_HIP(c, hipMalloc(&c->d_points[b], chunk * 24));
-      DMI_COLOR_HIP(c, hipMalloc(&c->d_mean[b], chunk * 3));
-      DMI_COLOR_HIP(c, hipMalloc(&c->d_median[b], chunk * 3));
-      DMI_COLOR_HIP(c, hipMalloc(&c->d_count[b], chunk * 4));
-    }
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_scratch, chunk * n_views * sizeof(uchar4)));
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_seeds, chunk * sizeof(MedianSeed)));
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_keys, chunk * 4));
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_keys_sorted, chunk * 4));
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_index, chunk * 4));
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_perm, chunk * 4));
-    if (!c->d_box) DMI_COLOR_HIP(c, hipMalloc(&c->d_box, 6 * sizeof(unsigned long long)));
-    // rocPRIM tells how much temporary storage a sort of `chunk` pairs needs when called without any
-    DMI_COLOR_HIP(c, rocprim::radix_sort_pairs(nullptr, c->sort_temp_bytes, c->d_keys, c->d_keys_sorted, c->d_index, c->d_perm, chunk, 0,
-                                              30, c->stream));
-    DMI_COLOR_HIP(c, hipMalloc(&c->d_sort_temp, std::max<size_t>(c->sort_temp_bytes, 16)));
-    c->chunk_capacity = chunk;
-    c->scratch_capacity = chunk * n_views;
+  {
+    const int rc = ensure_work_buffers(c, chunk, n_views, !job.in_place());
+    if (rc != DMI_OK) return rc;
   }
   // On a failure past the first queued copy nothing may still be writing the caller's arrays when the call returns
   auto bail = [&](hipError_t he, const char *what) {
     for (hipStream_t st : {c->h2d, c->stream, c->d2h}) (void)hipStreamSynchronize(st);
     (void)hipGetLastError();
-    return cfail(c, DMI_ERR_DEVICE, std::string("dmi_color_process: ") + what + ": " + hipGetErrorString(he));
+    return cfail(c, DMI_ERR_DEVICE, entry + ": " + what + ": " + hipGetErrorString(he));
   };
 #define DMI_COLOR_TRY(call)                         \
   do {                                              \
     const hipError_t he_ = (call);                  \
     if (he_ != hipSuccess) return bail(he_, #call); \
   } while (0)
+  bool coherent = false;
+  if (job.in_place()) {
+    // the vertices are as whatever is queued on their owner's stream leaves them
+    if (job.after) DMI_COLOR_TRY(hipStreamWaitEvent(c->stream, job.after, 0));
+    if (fused) {
+      if (c->fused_tables_capacity < n_views) {  // (only the fused form ever allocates it)
+        if (c->d_fused_tables) (void)hipFree(c->d_fused_tables);
+        c->d_fused_tables = nullptr;
+        c->fused_tables_capacity = 0;
+        DMI_COLOR_TRY(hipMalloc(&c->d_fused_tables, n_views * sizeof(const void *)));
+        c->fused_tables_capacity = n_views;
+      }
+      c->h_fused_tables.assign(job.fused_tables, job.fused_tables + n_views);
+      DMI_COLOR_TRY(hipMemcpyAsync(c->d_fused_tables, c->h_fused_tables.data(), n_views * sizeof(const void *), hipMemcpyHostToDevice, c->stream));
+    }
+    // the order-of-work decision of the staged form from the same sample, brought to the host (36 KB at the most)
+    coherent = !c->reorder;
+    if (coherent && n_points >= 64) {
+      const int64_t samples = coherence_samples(n_points);
+      if (!c->d_sample) DMI_COLOR_TRY(hipMalloc(&c->d_sample, 512 * 9 * sizeof(double)));
+      double *rows = c->d_sample;
+      std::vector<double> h_rows((size_t)samples * 9);
+      hipLaunchKernelGGL(coherence_sample_kernel, dim3((unsigned)((samples + 255) / 256)), dim3(256), 0, c->stream, job.d_points, n_points, samples, rows);
+      DMI_COLOR_TRY(hipGetLastError());
+      DMI_COLOR_TRY(hipMemcpyAsync(h_rows.data(), rows, h_rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      DMI_COLOR_TRY(hipStreamSynchronize(c->stream));
+      coherent = sample_in_coherent_order(h_rows.data(), samples);
+    }
+    DMI_COLOR_TRY(hipEventRecord(c->ev0, c->stream));
+  } else {
+    coherent = !c->reorder && vertices_in_coherent_order(job.h_points, n_points);
+  }
   bool timed[2] = {false, false};
   auto collect = [&](int b) {  // the kernel time of the chunk that last used buffer set b (its kernels are known to have ended)
     if (!timed[b]) return;
@@ -1022,22 +1138,29 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
     const int b = (int)(index & 1);
     const int64_t nv = std::min<int64_t>((int64_t)chunk, n_points - v0);
     const unsigned blocks = (unsigned)((nv + 255) / 256);
-    // copy in, once the kernels of the chunk before last have read this buffer set
-    if (index >= 2) {
-      DMI_COLOR_TRY(hipStreamWaitEvent(c->h2d, c->kdone[b], 0));
-      DMI_COLOR_TRY(hipEventSynchronize(c->kdone[b]));  // (the host reads that chunk's kernel time before the events are re-recorded)
-      collect(b);
+    // this chunk's vertices and outputs: an offset into the device arrays, or buffer set b
+    const double *points = job.in_place() ? job.d_points + 3 * v0 : c->d_points[b];
+    uint8_t *mean = job.in_place() ? job.d_mean + 3 * v0 : c->d_mean[b];
+    uint8_t *median = job.in_place() ? job.d_median + 3 * v0 : c->d_median[b];
+    int32_t *count = job.in_place() ? job.d_count + v0 : c->d_count[b];
+    if (!job.in_place()) {
+      // copy in, once the kernels of the chunk before last have read this buffer set
+      if (index >= 2) {
+        DMI_COLOR_TRY(hipStreamWaitEvent(c->h2d, c->kdone[b], 0));
+        DMI_COLOR_TRY(hipEventSynchronize(c->kdone[b]));  // (the host reads that chunk's kernel time before the events are re-recorded)
+        collect(b);
+      }
+      DMI_COLOR_TRY(hipMemcpyAsync(c->d_points[b], job.h_points + 3 * v0, (size_t)nv * 24, hipMemcpyHostToDevice, c->h2d));
+      DMI_COLOR_TRY(hipEventRecord(c->up[b], c->h2d));
+      // kernels, once the vertices are there and the outputs of the chunk before last have left this buffer set
+      DMI_COLOR_TRY(hipStreamWaitEvent(c->stream, c->up[b], 0));
+      if (index >= 2) DMI_COLOR_TRY(hipStreamWaitEvent(c->stream, c->down[b], 0));
+      DMI_COLOR_TRY(hipEventRecord(c->k0[b], c->stream));
     }
-    DMI_COLOR_TRY(hipMemcpyAsync(c->d_points[b], points + 3 * v0, (size_t)nv * 24, hipMemcpyHostToDevice, c->h2d));
-    DMI_COLOR_TRY(hipEventRecord(c->up[b], c->h2d));
-    // kernels, once the vertices are there and the outputs of the chunk before last have left this buffer set
-    DMI_COLOR_TRY(hipStreamWaitEvent(c->stream, c->up[b], 0));
-    if (index >= 2) DMI_COLOR_TRY(hipStreamWaitEvent(c->stream, c->down[b], 0));
-    DMI_COLOR_TRY(hipEventRecord(c->k0[b], c->stream));
     // the chunk's largest coordinate magnitudes bound the error of the pixel selection's shortcut (ViewMargin); a coordinate
     // that is not finite makes the margins infinite: every pair then takes the reference's expression
     DMI_COLOR_TRY(hipMemsetAsync(c->d_pmax[b], 0, 4 * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(chunk_magnitude_kernel, dim3(std::min<unsigned>(blocks, 512u)), dim3(256), 0, c->stream, c->d_points[b], nv, c->d_pmax[b]);
+    hipLaunchKernelGGL(chunk_magnitude_kernel, dim3(std::min<unsigned>(blocks, 512u)), dim3(256), 0, c->stream, points, nv, c->d_pmax[b]);
     hipLaunchKernelGGL(view_margins_kernel, dim3((unsigned)((n_views + 255) / 256)), dim3(256), 0, c->stream, c->d_views, (int)n_views, c->d_pmax[b],
                        c->d_margins[b]);
     DMI_COLOR_TRY(hipGetLastError());
@@ -1046,69 +1169,94 @@ int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_poin
       // the order of work: along a Z-order curve of the chunk's bounding box (see bbox_kernel)
       static const unsigned long long kEmptyBox[6] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull};
       DMI_COLOR_TRY(hipMemcpyAsync(c->d_box, kEmptyBox, sizeof(kEmptyBox), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(bbox_kernel, dim3(std::min<unsigned>(blocks, 256u)), dim3(256), 0, c->stream, c->d_points[b], nv, c->d_box);
-      hipLaunchKernelGGL(morton_key_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_points[b], nv, c->d_box, c->d_keys, c->d_index);
+      hipLaunchKernelGGL(bbox_kernel, dim3(std::min<unsigned>(blocks, 256u)), dim3(256), 0, c->stream, points, nv, c->d_box);
+      hipLaunchKernelGGL(morton_key_kernel, dim3(blocks), dim3(256), 0, c->stream, points, nv, c->d_box, c->d_keys, c->d_index);
       DMI_COLOR_TRY(hipGetLastError());
       size_t temp = c->sort_temp_bytes;
       DMI_COLOR_TRY(rocprim::radix_sort_pairs(c->d_sort_temp, temp, c->d_keys, c->d_keys_sorted, c->d_index, c->d_perm, (size_t)nv,
                                               0, 30, c->stream));
       perm = c->d_perm;
     }
-    const DepthTest depth{c->d_depth_planes, c->depth_tol};
     bool histogram_medians = n_views <= 65535;
+    // (tuning builds: extra dynamic LDS per workgroup, i.e. FEWER resident waves -- what keeping a vertex's values in LDS
+    // instead of the scratch table would cost the view loop: tools/gpu_coloration_occupancy.sh)
+    unsigned extra_lds = 0;
 #ifdef DMI_TUNING
     if (getenv("DMI_COLOR_BITWISE_MEDIAN")) histogram_medians = false;  // A/B of the two median kernels
+    if (const char *env = getenv("DMI_DEBUG_COLOR_EXTRA_LDS")) extra_lds = (unsigned)strtoul(env, nullptr, 0);
 #endif
-    if (histogram_medians) {
-      // (vertices in a coherent order -- the caller's, a mesh's, or the Z-order pass's -- take the pipelined view loop, scattered
-      // ones the plain one)
-      // (tuning builds: extra dynamic LDS per workgroup, i.e. FEWER resident waves -- what keeping a vertex's values in LDS
-      // instead of the scratch table would cost the view loop: tools/gpu_coloration_occupancy.sh)
-      unsigned extra_lds = 0;
-#ifdef DMI_TUNING
-      if (const char *env = getenv("DMI_DEBUG_COLOR_EXTRA_LDS")) extra_lds = (unsigned)strtoul(env, nullptr, 0);
-#endif
-      if (c->depth_test && !perm && !coherent)
-        hipLaunchKernelGGL((project_color_kernel<true, false, DepthTest>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm,
-                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b], depth);
-      else if (c->depth_test)
-        hipLaunchKernelGGL((project_color_kernel<true, true, DepthTest>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm,
-                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b], depth);
-      else if (!perm && !coherent)
-        hipLaunchKernelGGL((project_color_kernel<true, false>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm, c->d_views,
-                           (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b]);
+    // The projection pass with the call's depth policy (none, the context's own planes, a fusion context's tables).  With
+    // histogram medians, vertices in a coherent order -- the caller's, a mesh's, or the Z-order pass's -- take the pipelined view
+    // loop, scattered ones the plain one.
+    auto project = [&](auto... policy) {
+      if (histogram_medians && !perm && !coherent)
+        hipLaunchKernelGGL((project_color_kernel<true, false, decltype(policy)...>), dim3(blocks), dim3(256), extra_lds, c->stream, points, nv, perm,
+                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, mean, count, c->d_seeds, c->d_margins[b], policy...);
+      else if (histogram_medians)
+        hipLaunchKernelGGL((project_color_kernel<true, true, decltype(policy)...>), dim3(blocks), dim3(256), extra_lds, c->stream, points, nv, perm,
+                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, mean, count, c->d_seeds, c->d_margins[b], policy...);
       else
-        hipLaunchKernelGGL((project_color_kernel<true, true>), dim3(blocks), dim3(256), extra_lds, c->stream, c->d_points[b], nv, perm, c->d_views,
-                           (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b]);
-      DMI_COLOR_TRY(hipGetLastError());
-      hipLaunchKernelGGL(median_low_nibble_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scratch, nv, (int)n_views, perm,
-                         c->d_count[b], c->d_seeds, c->d_median[b]);
-    } else {
-      if (c->depth_test)
-        hipLaunchKernelGGL((project_color_kernel<false, false, DepthTest>), dim3(blocks), dim3(256), 0, c->stream, c->d_points[b], nv, perm,
-                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b], depth);
-      else
-        hipLaunchKernelGGL((project_color_kernel<false, false>), dim3(blocks), dim3(256), 0, c->stream, c->d_points[b], nv, perm, c->d_views,
-                           (int)n_views, c->W, c->H, c->d_scratch, c->d_mean[b], c->d_count[b], c->d_seeds, c->d_margins[b]);
-      DMI_COLOR_TRY(hipGetLastError());
-      hipLaunchKernelGGL(median_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scratch, nv, (int)n_views, perm,
-                         c->d_count[b], c->d_median[b]);
-    }
+        hipLaunchKernelGGL((project_color_kernel<false, false, decltype(policy)...>), dim3(blocks), dim3(256), 0, c->stream, points, nv, perm,
+                           c->d_views, (int)n_views, c->W, c->H, c->d_scratch, mean, count, c->d_seeds, c->d_margins[b], policy...);
+    };
+    if (fused && job.fused_f64)
+      project(FusedDepth<double>{reinterpret_cast<const double *const *>(c->d_fused_tables), job.fused_tol});
+    else if (fused)
+      project(FusedDepth<float>{reinterpret_cast<const float *const *>(c->d_fused_tables), job.fused_tol});
+    else if (own_test)
+      project(DepthTest{c->d_depth_planes, c->depth_tol});
+    else
+      project();
     DMI_COLOR_TRY(hipGetLastError());
+    if (histogram_medians)
+      hipLaunchKernelGGL(median_low_nibble_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scratch, nv, (int)n_views, perm, count,
+                         c->d_seeds, median);
+    else
+      hipLaunchKernelGGL(median_kernel, dim3(blocks), dim3(256), 0, c->stream, c->d_scratch, nv, (int)n_views, perm, count, median);
+    DMI_COLOR_TRY(hipGetLastError());
+    if (job.in_place()) continue;
     DMI_COLOR_TRY(hipEventRecord(c->kdone[b], c->stream));
     timed[b] = true;
     // copies out
     DMI_COLOR_TRY(hipStreamWaitEvent(c->d2h, c->kdone[b], 0));
-    DMI_COLOR_TRY(hipMemcpyAsync(mean + 3 * v0, c->d_mean[b], (size_t)nv * 3, hipMemcpyDeviceToHost, c->d2h));
-    DMI_COLOR_TRY(hipMemcpyAsync(median + 3 * v0, c->d_median[b], (size_t)nv * 3, hipMemcpyDeviceToHost, c->d2h));
-    DMI_COLOR_TRY(hipMemcpyAsync(count + v0, c->d_count[b], (size_t)nv * 4, hipMemcpyDeviceToHost, c->d2h));
+    DMI_COLOR_TRY(hipMemcpyAsync(job.h_mean + 3 * v0, c->d_mean[b], (size_t)nv * 3, hipMemcpyDeviceToHost, c->d2h));
+    DMI_COLOR_TRY(hipMemcpyAsync(job.h_median + 3 * v0, c->d_median[b], (size_t)nv * 3, hipMemcpyDeviceToHost, c->d2h));
+    DMI_COLOR_TRY(hipMemcpyAsync(job.h_count + v0, c->d_count[b], (size_t)nv * 4, hipMemcpyDeviceToHost, c->d2h));
     DMI_COLOR_TRY(hipEventRecord(c->down[b], c->d2h));
   }
-  for (hipStream_t st : {c->h2d, c->stream, c->d2h}) DMI_COLOR_TRY(hipStreamSynchronize(st));
-  collect(0);
-  collect(1);
+  if (job.in_place()) {
+    // nothing but the chunks' kernels is on the stream between the two events: their span is the kernel time
+    DMI_COLOR_TRY(hipEventRecord(c->ev1, c->stream));
+    DMI_COLOR_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    DMI_COLOR_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_kernel_ms = (double)ms;
+  } else {
+    for (hipStream_t st : {c->h2d, c->stream, c->d2h}) DMI_COLOR_TRY(hipStreamSynchronize(st));
+    collect(0);
+    collect(1);
+  }
 #undef DMI_COLOR_TRY
   return DMI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dmi_color_process(dmi_color_context *c, const double *points, int64_t n_points, uint8_t *mean, uint8_t *median,
+                      int32_t *count) {
+  return guarded(c, "dmi_color_process", [&]() -> int {
+  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: null context");
+  if (n_points < 0 || (n_points > 0 && (!points || !mean || !median || !count)))
+    return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_process: null argument");
+  ColorJob job;
+  job.entry = "dmi_color_process";
+  job.n = n_points;
+  job.h_points = points;
+  job.h_mean = mean;
+  job.h_median = median;
+  job.h_count = count;
+  return process_vertices(c, job);
   });
 }
 
@@ -1155,3 +1303,27 @@ int dmi_color_mesh(const double *points, int64_t n_points, const uint8_t *colors
 }
 
 }  // extern "C"
+
+// ---- the in-place form, for the translation unit that owns the mesh (dmi_capi_mesh.hip; declared in dmi_context.h) ----
+dmi::ColorContextShape dmi::color_context_shape(const dmi_color_context *c) {
+  return ColorContextShape{c->device, c->W, c->H, (int64_t)c->h_views.size(), c->depth_test};
+}
+
+int dmi::color_device_vertices(dmi_color_context *c, const DeviceColoring &work, double *kernel_ms) {
+  return ::guarded(c, "dmi_color_process_isosurface", [&]() -> int {
+    ColorJob job;
+    job.entry = "dmi_color_process_isosurface";
+    job.n = work.n;
+    job.d_points = work.points;
+    job.d_mean = work.mean;
+    job.d_median = work.median;
+    job.d_count = work.count;
+    job.after = work.after;
+    job.fused_tables = work.fused_tables;
+    job.fused_f64 = work.fused_f64;
+    job.fused_tol = work.fused_tol;
+    const int rc = process_vertices(c, job);
+    if (rc == DMI_OK && kernel_ms) *kernel_ms = c->last_kernel_ms;
+    return rc;
+  });
+}

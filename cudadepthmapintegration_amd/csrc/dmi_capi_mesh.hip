@@ -1,6 +1,6 @@
 // dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
 // (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
-// filter, the smoother, the decimation and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
+// filter, the smoother, the decimation, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
 #include "dmi_context.h"
 
 #include <algorithm>
@@ -225,6 +225,7 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
   mesh.n_triangles = totals[1];
   mesh.valid = true;
   mesh.has_normals = normals;
+  mesh.colored = false;  // the colours of an earlier mesh are not this one's
   *n_vertices = totals[0];
   *n_triangles = totals[1];
   rc = drain_c2p(ctx);
@@ -305,6 +306,7 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
   if (nv == 0) {  // an empty mesh stays empty
     mesh.filtered = true;
+    mesh.colored = false;
     mesh.regions = 0;
     comp.last_kernel_ms = 0.0;
     for (double &p : comp.last_pass_ms) p = 0.0;
@@ -368,6 +370,7 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   mesh.n_triangles = kept[1];
   mesh.regions = kept[2];
   mesh.filtered = true;
+  mesh.colored = false;  // the colours were the unfiltered mesh's
   comp.last_cas_retries = counters[2];
   *n_vertices = kept[0];
   *n_triangles = kept[1];
@@ -440,6 +443,7 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   if (iterations == 0 || nv == 0) {  // nothing to do: the mesh, its normals included, stays as it is
     sm.last_kernel_ms = 0.0;
     for (double &p : sm.last_pass_ms) p = 0.0;
+    if (iterations > 0) mesh.colored = false;
     return DMI_OK;
   }
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
@@ -487,6 +491,7 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   // the smoothed positions become the context's; the buffer they replace is the next call's scratch
   std::swap(mesh.vertices, result == mesh.alt_vertices.ptr ? mesh.alt_vertices : sm.vertices);
   if (normals) std::swap(mesh.normals, mesh.alt_normals);
+  mesh.colored = false;  // the colours were those of the positions before
   return DMI_OK;
   });
 }
@@ -561,6 +566,7 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   *n_vertices = *n_triangles = 0;
   if (nv == 0) {  // an empty mesh stays empty (it has no triangles either)
     mesh.filtered = false;
+    mesh.colored = false;
     dc.last_kernel_ms = 0.0;
     for (double &p : dc.last_pass_ms) p = 0.0;
     return DMI_OK;
@@ -654,6 +660,7 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   mesh.n_triangles = kept[1];
   mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
   mesh.regions = 0;
+  mesh.colored = false;   // ... nor are the colours
   *n_vertices = kept[0];
   *n_triangles = kept[1];
   return DMI_OK;
@@ -676,6 +683,96 @@ int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]) {
   const int rc = drain_decimation(ctx);
   if (rc != DMI_OK) return rc;
   for (int p = 0; p < 4; ++p) out[p] = ctx->decimation.last_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
+int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t fused_depth_test, double tolerance, uint64_t *n_vertices) {
+  return guarded(ctx, "dmi_color_process_isosurface", [&]() -> int {
+  const std::string entry = "dmi_color_process_isosurface";
+  if (!c || !ctx || !n_vertices) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Coloration &col = ctx->coloration;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const dmi::ColorContextShape views = dmi::color_context_shape(c);
+  if (views.device != ctx->opt.device)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the colour context is on device " + std::to_string(views.device) + ", the mesh on device " +
+                                                   std::to_string(ctx->opt.device));
+  const bool fused = fused_depth_test != 0;
+  if (fused) {
+    if (!(tolerance >= 0.0 && tolerance <= 1.7976931348623157e308))  // NaN, negative, infinite
+      return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the tolerance must be finite and >= 0");
+    if (views.depth_test)
+      return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the colour context's own depth test is on (dmi_color_set_depth_test); one test at a time");
+    if (views.n_views > 0 && ((int64_t)ctx->h_maps.size() != views.n_views || ctx->W != views.W || ctx->H != views.H))
+      return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                  entry + ": the fused test needs the same views in both contexts: " + std::to_string(ctx->h_maps.size()) + " of " +
+                      std::to_string(ctx->W) + " x " + std::to_string(ctx->H) + " here, " + std::to_string(views.n_views) + " of " +
+                      std::to_string(views.W) + " x " + std::to_string(views.H) + " in the colour context");
+  }
+  if (views.n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident in the colour context (MC.cxx:102-106)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  const uint64_t nv = mesh.n_vertices;
+  if (nv > 0) {
+    // the results are built in the alternates and swapped in last: a call that fails leaves the previous colours in place
+    int rc = ensure_buffers(ctx, {{&mesh.alt_color_mean, nv * 3}, {&mesh.alt_color_median, nv * 3}, {&mesh.alt_color_count, nv * 4}});
+    if (rc != DMI_OK) return rc;
+    if (!col.events[0])
+      for (hipEvent_t &e : col.events) DMI_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    // whatever is still queued on this context's stream (a decimation's normals) comes first
+    DMI_HIP(ctx, hipEventRecord(col.events[0], ctx->stream));
+    std::vector<const void *> tables;
+    if (fused)
+      for (const dmi::MapRec &r : ctx->h_maps) tables.push_back(r.depth);
+    dmi::DeviceColoring work{};
+    work.points = mesh.vertices.as<double>();
+    work.n = (int64_t)nv;
+    work.mean = mesh.alt_color_mean.as<uint8_t>();
+    work.median = mesh.alt_color_median.as<uint8_t>();
+    work.count = mesh.alt_color_count.as<int32_t>();
+    work.after = col.events[0];
+    work.fused_tables = fused ? tables.data() : nullptr;
+    work.fused_f64 = ctx->depth_f64;
+    work.fused_tol = tolerance;
+    double ms = 0.0;
+    rc = dmi::color_device_vertices(c, work, &ms);
+    if (rc != DMI_OK) return fail(ctx, rc, dmi_color_last_error());
+    col.last_kernel_ms = ms;
+    std::swap(mesh.color_mean, mesh.alt_color_mean);
+    std::swap(mesh.color_median, mesh.alt_color_median);
+    std::swap(mesh.color_count, mesh.alt_color_count);
+  } else {
+    col.last_kernel_ms = 0.0;  // an empty mesh has empty colours
+  }
+  mesh.colored = true;
+  *n_vertices = nv;
+  return DMI_OK;
+  });
+}
+
+int dmi_download_isosurface_colors(dmi_context *ctx, uint8_t *mean, uint8_t *median, int32_t *count) {
+  return guarded(ctx, "dmi_download_isosurface_colors", [&]() -> int {
+  if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_colors: null argument");
+  const dmi_context::Mesh &mesh = ctx->mesh;
+  if (!mesh.valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_colors: no mesh (no extraction has succeeded)");
+  if (!mesh.colored)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_download_isosurface_colors: no colours (dmi_color_process_isosurface has not run since the mesh last changed)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  const size_t nv = (size_t)mesh.n_vertices;
+  if (mean && nv) DMI_HIP(ctx, hipMemcpyAsync(mean, mesh.color_mean.ptr, nv * 3, hipMemcpyDeviceToHost, ctx->stream));
+  if (median && nv) DMI_HIP(ctx, hipMemcpyAsync(median, mesh.color_median.ptr, nv * 3, hipMemcpyDeviceToHost, ctx->stream));
+  if (count && nv) DMI_HIP(ctx, hipMemcpyAsync(count, mesh.color_count.ptr, nv * 4, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_color_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_color_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_color_kernel_ms: null argument");
+  *last = ctx->coloration.last_kernel_ms;
   return DMI_OK;
   });
 }

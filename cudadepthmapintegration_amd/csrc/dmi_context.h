@@ -152,8 +152,13 @@ struct dmi_context {
     bool valid = false;
     bool has_normals = false;  // the last successful extraction wrote them
     bool filtered = false;     // a filter has run since the last extraction or decimation: the region arrays are the mesh's
+    // dmi_color_process_isosurface's results, [n][3] u8, [n][3] u8, [n] int32; written into the alternates and swapped in last
+    dmi::DeviceBuffer color_mean, color_median, color_count;
+    dmi::DeviceBuffer alt_color_mean, alt_color_median, alt_color_count;
+    bool colored = false;      // the colour arrays describe this mesh (dropped by whatever changes it)
     void release() {
-      dmi::free_buffers({&vertices, &triangles, &normals, &alt_vertices, &alt_triangles, &alt_normals, &region_id, &region_size});
+      dmi::free_buffers({&vertices, &triangles, &normals, &alt_vertices, &alt_triangles, &alt_normals, &region_id, &region_size,
+                         &color_mean, &color_median, &color_count, &alt_color_mean, &alt_color_median, &alt_color_count});
     }
   } mesh;
   struct Extraction {  // dmi_extract_isosurface (isosurface.hip)
@@ -193,6 +198,12 @@ struct dmi_context {
     double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // clustering, representatives, triangles, normals
     void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); dmi::destroy_events(events); }
   } decimation;
+
+  struct Coloration {  // dmi_color_process_isosurface (coloration_kernels.hip through dmi::color_device_vertices)
+    hipEvent_t events[1] = {nullptr};  // what the colour context's stream waits for: the end of this context's queued work
+    double last_kernel_ms = 0.0;
+    void release() { dmi::destroy_events(events); }
+  } coloration;
 
   void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
   double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
@@ -244,6 +255,30 @@ int guarded(dmi_context *ctx, const char *entry, Body &&body) noexcept {
     return DMI_ERR_STATE;
   }
 }
+
+
+// The colouring of vertices that are on the device already (coloration_kernels.hip, where dmi_color_context is private): the
+// chunk body of dmi_color_process with a chunk being an offset into `points` and into the outputs, no copy in and none out.
+struct ColorContextShape {
+  int32_t device, W, H;
+  int64_t n_views;
+  bool depth_test;  // dmi_color_set_depth_test is on
+};
+ColorContextShape color_context_shape(const dmi_color_context *c);
+struct DeviceColoring {
+  const double *points;  // [n][3], device
+  int64_t n;
+  uint8_t *mean, *median;  // [n][3], device
+  int32_t *count;          // [n], device
+  hipEvent_t after;        // the colour context's stream waits for it before it reads the vertices
+  // the fused depth test: per view (host array) the view's [H][W] table in a fusion context's store, top row first, f64 or f32;
+  // null: the colour context's own settings decide
+  const void *const *fused_tables;
+  bool fused_f64;
+  double fused_tol;
+};
+// Synchronises once at its end (and once for the order-of-work sample).  A failure's message is dmi_color_last_error()'s.
+int color_device_vertices(dmi_color_context *c, const DeviceColoring &work, double *kernel_ms);
 
 }  // namespace dmi
 

@@ -348,6 +348,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_smooth_lambda = o.meshSmoothLambda;
   out->mesh_smooth_mu = o.meshSmoothMu;
   out->mesh_decimate_cell_size = o.meshDecimateCellSize;
+  out->mesh_coloration = o.meshColoration ? 1 : 0;
+  out->mesh_coloration_fused = o.meshColorationDepthToleranceGiven ? 1 : 0;
+  out->mesh_coloration_depth_tolerance = o.meshColorationDepthTolerance;
   return 1;
   });
 }
@@ -376,6 +379,17 @@ int dmi_write_polydata_with_arrays(const char *path, const double *points, int64
   if (!path || n_points < 0 || n_triangles < 0 || (n_points > 0 && !points) || (n_triangles > 0 && !triangles)) return 0;
   std::string error;
   return dmi::host::cli::WritePolyData(path, points, n_points, triangles, n_triangles, &error, normals, contour, region_id) ? 1 : 0;
+  });
+}
+
+int dmi_write_polydata_with_colors(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
+                                   int64_t n_triangles, const float *normals, double contour, const int64_t *region_id,
+                                   const uint8_t *mean, const uint8_t *median, const int32_t *count) {
+  return guarded<int>(0, [&]() -> int {
+  if (!path || n_points < 0 || n_triangles < 0 || (n_points > 0 && !points) || (n_triangles > 0 && !triangles)) return 0;
+  if ((mean || median || count) && !(mean && median && count)) return 0;  // all three or none
+  std::string error;
+  return dmi::host::cli::WritePolyData(path, points, n_points, triangles, n_triangles, &error, normals, contour, region_id, mean, median, count) ? 1 : 0;
   });
 }
 

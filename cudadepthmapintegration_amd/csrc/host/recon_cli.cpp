@@ -161,6 +161,18 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                 "decimated mesh's geometric normals, with --meshRegionIds the components are labelled again "
                                                 "on the decimated mesh (default 0 = off; not in the reference)",
                                   into_checked_double(&o->meshDecimateCellSize, &o->meshDecimateCellSizeGiven, [](double x) { return x > 0.0; })}},
+      {"--meshColoration", {Kind::kFlag, "with --extractMesh, on one GPU: colour the mesh on the GPU where it is, last of all, from the "
+                                         "Color arrays of the depth-map files (UInt8 x 3, read in the same pass as the depths), and "
+                                         "write the point arrays MeanColoration, MedianColoration and NbProjectedDepthMap as the "
+                                         "Coloration tool does (not in the reference)",
+                            into_flag(&o->meshColoration)}},
+      {"--meshColorationDepthTolerance", {Kind::kValue, "with --meshColoration: a view colours a vertex only if the vertex lies in "
+                                                        "front of the camera and within this distance (finite, >= 0) of the depth "
+                                                        "the fusion kept at its pixel, i.e. after --threshBestCost; without the "
+                                                        "flag every view whose image holds the vertex counts, as in the reference "
+                                                        "(not in the reference)",
+                                          into_checked_double(&o->meshColorationDepthTolerance, &o->meshColorationDepthToleranceGiven,
+                                                              [](double x) { return x >= 0.0; })}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -243,6 +255,18 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     }
   if (o->meshDecimateCellSizeGiven && !o->extractMesh) {
     err << "Error : --meshDecimateCellSize needs --extractMesh (the decimation belongs to the extracted mesh).\n" << HelpText();
+    return false;
+  }
+  if (o->meshColoration && !o->extractMesh) {
+    err << "Error : --meshColoration needs --extractMesh (the colours belong to the extracted mesh).\n" << HelpText();
+    return false;
+  }
+  if (o->meshColorationDepthToleranceGiven && !o->meshColoration) {
+    err << "Error : --meshColorationDepthTolerance needs --meshColoration.\n" << HelpText();
+    return false;
+  }
+  if (o->meshColoration && o->devices.size() > 1) {
+    err << "Error : --meshColoration takes one --device (the mesh of a fusion over several GPUs is not coloured).\n" << HelpText();
     return false;
   }
   // rmain:257-262
@@ -420,7 +444,9 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 }
 
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
-                   std::string *error, const float *normals, double contour, const int64_t *regionIds) {
+                   std::string *error, const float *normals, double contour, const int64_t *regionIds, const uint8_t *mean,
+                   const uint8_t *median, const int32_t *count) {
+  const bool colors = mean && median && count;
   if (nPoints < 0 || nTriangles < 0) {
     *error = "WritePolyData: negative count";
     return false;
@@ -436,6 +462,8 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
   const uint64_t normal_offset = 3 * sizeof(uint64_t) + point_bytes + conn_bytes + offset_bytes;  // behind the offsets
   const uint64_t region_bytes = (uint64_t)nPoints * sizeof(int64_t);
   const uint64_t region_offset = normal_offset + (normals ? 2 * sizeof(uint64_t) + normal_bytes + scalar_bytes : 0);
+  const uint64_t rgb_bytes = (uint64_t)nPoints * 3, count_bytes = (uint64_t)nPoints * sizeof(int32_t);
+  const uint64_t color_offset = region_offset + (regionIds ? sizeof(uint64_t) + region_bytes : 0);  // behind every other array
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
       << nPoints << "\" NumberOfVerts=\"0\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"" << nTriangles << "\">\n";
@@ -446,9 +474,16 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
         << normal_offset + sizeof(uint64_t) + normal_bytes << "\"/>\n";
   else if (regionIds)
     out << "      <PointData Scalars=\"RegionId\">\n";
+  else if (colors)
+    out << "      <PointData>\n";
   if (regionIds)  // vtkPolyDataConnectivityFilter's (ColorRegionsOn)
     out << "        <DataArray type=\"Int64\" Name=\"RegionId\" format=\"appended\" offset=\"" << region_offset << "\"/>\n";
-  if (normals || regionIds) out << "      </PointData>\n";
+  if (colors)  // the Coloration tool's three (MC.cxx:194-196)
+    out << "        <DataArray type=\"UInt8\" Name=\"MeanColoration\" NumberOfComponents=\"3\" format=\"appended\" offset=\"" << color_offset
+        << "\"/>\n        <DataArray type=\"UInt8\" Name=\"MedianColoration\" NumberOfComponents=\"3\" format=\"appended\" offset=\""
+        << color_offset + sizeof(uint64_t) + rgb_bytes << "\"/>\n        <DataArray type=\"Int32\" Name=\"NbProjectedDepthMap\" format=\"appended\" offset=\""
+        << color_offset + 2 * (sizeof(uint64_t) + rgb_bytes) << "\"/>\n";
+  if (normals || regionIds || colors) out << "      </PointData>\n";
   out << "      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" format=\"appended\" "
          "offset=\"0\"/>\n      </Points>\n      <Polys>\n        <DataArray type=\"Int64\" Name=\"connectivity\" format=\"appended\" offset=\""
       << sizeof(uint64_t) + point_bytes << "\"/>\n        <DataArray type=\"Int64\" Name=\"offsets\" format=\"appended\" offset=\""
@@ -480,6 +515,14 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
   if (regionIds) {
     out.write(reinterpret_cast<const char *>(&region_bytes), sizeof(region_bytes));
     out.write(reinterpret_cast<const char *>(regionIds), (std::streamsize)region_bytes);
+  }
+  if (colors) {
+    out.write(reinterpret_cast<const char *>(&rgb_bytes), sizeof(rgb_bytes));
+    out.write(reinterpret_cast<const char *>(mean), (std::streamsize)rgb_bytes);
+    out.write(reinterpret_cast<const char *>(&rgb_bytes), sizeof(rgb_bytes));
+    out.write(reinterpret_cast<const char *>(median), (std::streamsize)rgb_bytes);
+    out.write(reinterpret_cast<const char *>(&count_bytes), sizeof(count_bytes));
+    out.write(reinterpret_cast<const char *>(count), (std::streamsize)count_bytes);
   }
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
@@ -542,6 +585,22 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   filter.SetGridMatrix(matrix);
   if (o.devices.size() == 1) filter.SetDevice(o.devices[0]);
   if (o.devices.size() > 1) filter.SetDevices(o.devices);
+  // --meshColoration: the driver hands every chunk's Color planes to this context while it reads the files, and keeps its fusion
+  // context (the views' thresholded depths stay resident for the fused visibility test; the mesh is extracted in it)
+  struct ColorContextHolder {
+    dmi_color_context *c = nullptr;
+    ~ColorContextHolder() {
+      if (c) dmi_color_destroy(c);
+    }
+  } coloring;
+  if (o.meshColoration) {
+    if (dmi_color_create(o.devices.empty() ? 0 : o.devices[0], &coloring.c) != DMI_OK) {
+      result->error = std::string("--meshColoration: ") + dmi_color_last_error();
+      return 1;
+    }
+    filter.SetColorSink(coloring.c);
+    filter.SetKeepContext(true);
+  }
   if (!filter.Update()) {
     result->error = filter.LastError().empty() ? "the reconstruction filter refused its parameters" : filter.LastError();
     return 1;
@@ -561,6 +620,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   int64_t dummyTriangle = 0;
   float dummyNormal = 0.f;
   int64_t dummyRegion = 0;
+  std::vector<uint8_t> meshMean, meshMedian;  // --meshColoration
+  std::vector<int32_t> meshCount;
+  uint8_t dummyRgb[3] = {0, 0, 0};
+  int32_t dummyCount = 0;
   {
     // vtkCellDataToPointData (rmain:151-155) on the GPU: the cell grid goes up once more, the point grid comes back
     dmi_grid_desc grid;
@@ -576,8 +639,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     dmi_default_options(&opt);
     opt.device = o.devices.empty() ? 0 : o.devices[0];
     opt.grid_dtype = DMI_F64;
-    dmi_context *ctx = nullptr;
-    int rc = dmi_create(&grid, &ray, &opt, &ctx);
+    // (with --meshColoration: the context that fused, its views resident; the grid goes up the same way, so that every array
+    // written is what it is without the flag)
+    dmi_context *ctx = o.meshColoration ? filter.TakeContext() : nullptr;  // (destroyed below like a fresh one)
+    int rc = ctx ? DMI_OK : dmi_create(&grid, &ray, &opt, &ctx);
     if (rc == DMI_OK) rc = dmi_upload_grid(ctx, cells.data());
     if (rc == DMI_OK) rc = dmi_cell_to_point(ctx);
     if (rc == DMI_OK) rc = dmi_download_point_data_f64(ctx, points.data());
@@ -620,6 +685,19 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
           rc = dmi_filter_isosurface_components(ctx, DMI_COMPONENTS_MIN_TRIANGLES, 0, &nv, &nt, &found, &kept);
         }
       }
+      if (rc == DMI_OK && o.meshColoration) {  // last of all: the mesh as it will be written, where it is
+        uint64_t colored = 0;
+        rc = dmi_color_process_isosurface(coloring.c, ctx, o.meshColorationDepthToleranceGiven ? 1 : 0, o.meshColorationDepthTolerance, &colored);
+        if (rc == DMI_OK) rc = dmi_get_isosurface_color_kernel_ms(ctx, &result->meshColorationKernelMs);
+        if (rc == DMI_OK) {
+          meshMean.resize((size_t)nv * 3);
+          meshMedian.resize((size_t)nv * 3);
+          meshCount.resize((size_t)nv);
+          rc = dmi_download_isosurface_colors(ctx, meshMean.data(), meshMedian.data(), meshCount.data());
+        }
+        dmi_info info;
+        if (rc == DMI_OK && dmi_get_info(ctx, &info) == DMI_OK) result->meshColorationViews = (unsigned long long)info.n_views;
+      }
       if (rc == DMI_OK) {
         meshVertices.resize((size_t)nv * 3);
         meshTriangles.resize((size_t)nt * 3);
@@ -650,7 +728,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     say("** Save mesh...");
     if (!WritePolyData(o.outputMeshFilename, meshVertices.data(), (int64_t)result->meshVertices, meshTriangles.data(),
                        (int64_t)result->meshTriangles, &error, o.meshNormals ? (meshNormals.empty() ? &dummyNormal : meshNormals.data()) : nullptr, o.contour,
-                       o.meshRegionIds ? (meshRegionIds.empty() ? &dummyRegion : meshRegionIds.data()) : nullptr)) {
+                       o.meshRegionIds ? (meshRegionIds.empty() ? &dummyRegion : meshRegionIds.data()) : nullptr,
+                       o.meshColoration ? (meshMean.empty() ? dummyRgb : meshMean.data()) : nullptr,
+                       o.meshColoration ? (meshMedian.empty() ? dummyRgb : meshMedian.data()) : nullptr,
+                       o.meshColoration ? (meshCount.empty() ? &dummyCount : meshCount.data()) : nullptr)) {
       result->error = error;
       return 1;
     }
@@ -669,6 +750,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       log << "mesh decimation: cell size " << o.meshDecimateCellSize << "; " << result->meshVerticesBeforeDecimation << " vertices, "
           << result->meshTrianglesBeforeDecimation << " triangles before, " << result->meshVertices << " vertices, "
           << result->meshTriangles << " triangles after; " << result->meshDecimateKernelMs << " ms of GPU kernels" << std::endl;
+    if (o.meshColoration) {
+      log << "mesh coloration: " << result->meshVertices << " vertices, " << result->meshColorationViews << " views, depth tolerance ";
+      if (o.meshColorationDepthToleranceGiven) log << o.meshColorationDepthTolerance; else log << "none";
+      log << "; " << result->meshColorationKernelMs << " ms of GPU kernels" << std::endl;
+    }
   } else {
     // Said whatever --verbose is: the reference writes a mesh here (rmain:166-187) and this tool does not.
     log << "warning: " << o.outputMeshFilename << " is NOT written: the iso-surface (vtkContourFilter) is not part of this tool; "
@@ -703,6 +789,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       out << "  mesh decimation  cell size " << o.meshDecimateCellSize << ", " << result->meshVerticesBeforeDecimation << " vertices, "
           << result->meshTrianglesBeforeDecimation << " triangles before, " << result->meshVertices << " vertices, "
           << result->meshTriangles << " triangles after, " << result->meshDecimateKernelMs << " ms of GPU kernels\n";
+    if (o.meshColoration) {  // (only with --extractMesh)
+      out << "  mesh coloration  " << result->meshVertices << " vertices, " << result->meshColorationViews << " views, depth tolerance ";
+      if (o.meshColorationDepthToleranceGiven) out << o.meshColorationDepthTolerance; else out << "none";
+      out << ", " << result->meshColorationKernelMs << " ms of GPU kernels\n";
+    }
     if (!o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << " (no surface extracted)\n";
     out << "time\n  reconstruction  " << result->reconstructionSeconds << " s\n  total           " << result->totalSeconds << " s\n";

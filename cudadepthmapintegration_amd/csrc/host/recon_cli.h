@@ -56,6 +56,12 @@ struct Options {
   // not in the reference (needs --extractMesh): vertex clustering on the GPU after the smoothing, cells of this size (0: off)
   double meshDecimateCellSize = 0.0;
   bool meshDecimateCellSizeGiven = false;
+  // not in the reference (needs --extractMesh): colour the final mesh on the GPU where it is (dmi_color_process_isosurface) from the
+  // views' Color arrays and write MeanColoration, MedianColoration and NbProjectedDepthMap; with a tolerance, the visibility test
+  // against the depths the fusion kept
+  bool meshColoration = false;
+  double meshColorationDepthTolerance = 0.0;
+  bool meshColorationDepthToleranceGiven = false;
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -81,6 +87,9 @@ struct RunResult {
   // --meshDecimateCellSize: the mesh that went into the decimation and the hipEvent time of its kernels
   unsigned long long meshVerticesBeforeDecimation = 0, meshTrianglesBeforeDecimation = 0;
   double meshDecimateKernelMs = 0.0;
+  // --meshColoration: the views that coloured the mesh and the hipEvent time of the colouring's kernels
+  unsigned long long meshColorationViews = 0;
+  double meshColorationKernelMs = 0.0;
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
@@ -93,9 +102,12 @@ bool WriteMetaImage(const std::string &path, const int pointDims[3], const doubl
 // Float64 Points, Polys with Int64 connectivity and offsets.  With `normals` ([nPoints][3] f32) also the point arrays of
 // vtkContourFilter: <PointData Normals="Normals" Scalars="reconstruction_scalar">, Float32 x 3 and Float64 `contour` at every
 // point, appended behind the offsets; without them the file is what it always was.  With `regionIds` ([nPoints] int64) the
-// point array RegionId (Int64, one component) behind those; alone it is the section's Scalars.
+// point array RegionId (Int64, one component) behind those; alone it is the section's Scalars.  With `mean` ([nPoints][3] u8),
+// `median` ([nPoints][3] u8) and `count` ([nPoints] int32), all three or none, the arrays MeanColoration, MedianColoration and
+// NbProjectedDepthMap of the Coloration tool behind every other array.
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
-                   std::string *error, const float *normals = nullptr, double contour = 0.0, const int64_t *regionIds = nullptr);
+                   std::string *error, const float *normals = nullptr, double contour = 0.0, const int64_t *regionIds = nullptr,
+                   const uint8_t *mean = nullptr, const uint8_t *median = nullptr, const int32_t *count = nullptr);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

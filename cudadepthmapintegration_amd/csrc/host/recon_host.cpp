@@ -276,7 +276,9 @@ FusionDriver::FusionDriver() {
   std::memset(&Ray, 0, sizeof(Ray));
   DepthDims[0] = DepthDims[1] = 0;
 }
-FusionDriver::~FusionDriver() {}
+FusionDriver::~FusionDriver() {
+  if (KeptContext) dmi_destroy(KeptContext);
+}
 
 void FusionDriver::CudaInitialize(const double i_gridMatrix[16], const int h_gridDims[3], const double h_gridOrig[3],
                                   const double h_gridSpacing[3], double h_rayPThick, double h_rayPRho, double h_rayPEta,
@@ -309,6 +311,7 @@ struct Chunk {
   double *depth = nullptr, *cost = nullptr;  // pinned (dmi_alloc_pinned)
   std::vector<double> K4, RT;
   std::vector<char> has_cost;
+  std::vector<unsigned char> color;  // [n][H][W][3] "Color" planes, only with a colour sink
   size_t first = 0, count = 0;
   bool filled = false;  // guarded by Feed::lock
   bool failed = false;
@@ -348,6 +351,12 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
   }
   const size_t npix = (size_t)W * H;
   const bool multi = !Devices.empty();
+  if (multi && (ColorSink || KeepContext)) {
+    Error = "ProcessDepthMap: a colour sink and a kept context need a single GPU";
+    return false;
+  }
+  if (KeptContext) dmi_destroy(KeptContext);
+  KeptContext = nullptr;
 
   // cu:323-327: the accumulator starts from io_scalar.  +0.0 everywhere (all bits zero)?  The filter knows (RequestData
   // has just filled the array, filt.cxx:133); other callers' arrays are scanned, eight bytes at a time.
@@ -428,6 +437,7 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
     c.K4.resize(chunk * 16);
     c.RT.resize(chunk * 16);
     c.has_cost.resize(chunk);
+    if (ColorSink) c.color.resize(chunk * npix * 3);
   }
   auto free_chunks = [&]() {
     for (Chunk &c : feed.slot) {
@@ -451,6 +461,7 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
       c.failed = false;
       for (size_t v = 0; v < c.count && !c.failed; ++v) {
         bool has_cost = false;
+        FillColor = ColorSink ? c.color.data() + v * npix * 3 : nullptr;  // (one thread fills at a time)
         try {
           if (!fill(c.first + v, c.depth + v * npix, c.cost + v * npix, &has_cost, &c.K4[v * 16], &c.RT[v * 16], &c.error)) c.failed = true;
         } catch (const std::exception &e) {
@@ -516,6 +527,12 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
       } else if (rc == DMI_OK) {
         rc = dmi_fuse_range(ctx, (int32_t)c.first, (int32_t)c.count);
       }
+      // the same chunk's colour planes, while that fusion runs
+      if (rc == DMI_OK && ColorSink && dmi_color_add_views(ColorSink, c.color.data(), c.K4.data(), c.RT.data(), (int32_t)c.count, W, H) != DMI_OK) {
+        Error = std::string("dmi_color_add_views: ") + dmi_color_last_error();
+        ok = false;
+        break;
+      }
     }
     if (rc != DMI_OK) {
       Error = std::string(multi ? "dmi_multi_add_views: " : "dmi_add_views / dmi_fuse_range: ") + last_error();
@@ -558,6 +575,10 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
     }
     dmi_timings t;
     if (dmi_get_timings(ctx, &t) == DMI_OK) FuseKernelMs = t.total_fuse_kernel_ms;
+    if (KeepContext) {
+      KeptContext = ctx;
+      ctx = nullptr;
+    }
   }
   destroy();
   return true;
@@ -580,6 +601,13 @@ bool FusionDriver::ProcessDepthMap(const std::vector<ReconstructionData *> &view
     std::memcpy(depth, img->depths.data(), npix * 8);
     *has_cost = img->best_cost.size() == npix;
     if (*has_cost) std::memcpy(cost, img->best_cost.data(), npix * 8);
+    if (FillColor) {
+      if (img->color.size() != npix * 3) {
+        *error = "ProcessDepthMap: view " + std::to_string(index) + " has no UInt8 x 3 'Color' array of the views' size";
+        return false;
+      }
+      std::memcpy(FillColor, img->color.data(), npix * 3);
+    }
     std::memcpy(K4, d->Get4MatrixK(), 16 * 8);  // cu:352
     std::memcpy(RT, d->GetMatrixTR(), 16 * 8);  // cu:353
     return true;
@@ -618,6 +646,13 @@ bool FusionDriver::ProcessDepthMap(const std::vector<std::string> &vtiList, cons
     std::memcpy(depth, img->depths.data(), npix * 8);
     *has_cost = img->best_cost.size() == npix;
     if (*has_cost) std::memcpy(cost, img->best_cost.data(), npix * 8);
+    if (FillColor) {
+      if (img->color.size() != npix * 3) {
+        *error = "ProcessDepthMap: depth map " + vtiList[index] + " has no UInt8 x 3 'Color' array of the views' size (--meshColoration needs it)";
+        return false;
+      }
+      std::memcpy(FillColor, img->color.data(), npix * 3);
+    }
     std::memcpy(K4, data.Get4MatrixK(), 16 * 8);
     std::memcpy(RT, data.GetMatrixTR(), 16 * 8);
     return true;
@@ -636,7 +671,9 @@ ReconstructionFilter::ReconstructionFilter() {
   InDims[0] = InDims[1] = InDims[2] = 0;
   for (int a = 0; a < 3; ++a) InOrigin[a] = InSpacing[a] = 0;
 }
-ReconstructionFilter::~ReconstructionFilter() {}
+ReconstructionFilter::~ReconstructionFilter() {
+  if (KeptContext) dmi_destroy(KeptContext);
+}
 
 void ReconstructionFilter::SetFilePathKRTD(const char *path) {
   HasKRTD = path != nullptr;
@@ -715,6 +752,10 @@ int ReconstructionFilter::Compute(int gridDims[3], double gridOrig[3], double gr
   driver.SetKernelVariant(KernelVariant);
   driver.SetHostChunkBytes(HostChunkBytes);
   driver.SetFillOnCallingThread(FillOnCallingThread);
+  driver.SetColorSink(ColorSink);
+  driver.SetKeepContext(KeepContext);
+  if (KeptContext) dmi_destroy(KeptContext);
+  KeptContext = nullptr;
   driver.SetInitialGridIsZero(true);  // RequestData zero-filled outScalar just before (filt.cxx:133)
   bool result;
   if (!Views.empty()) {
@@ -747,6 +788,7 @@ int ReconstructionFilter::Compute(int gridDims[3], double gridOrig[3], double gr
     result = driver.ProcessDepthMap(vtiList, krtdList, ThresholdBestCost, outScalar->data());  // filt.cxx:175-176
   }
   FuseKernelMs = driver.LastFuseKernelMs();
+  KeptContext = driver.TakeContext();
   if (!result) {
     Error = driver.LastError();
     return -1;

@@ -139,6 +139,18 @@ class FusionDriver {
   void SetHostChunkBytes(size_t bytes) { HostChunkBytes = bytes < 1 ? 1 : bytes; }
   // the next ProcessDepthMap's io_scalar is known to hold +0.0 everywhere: skips the scan and the upload (cu:323-327)
   void SetInitialGridIsZero(bool yes) { InitialGridIsZero = yes; }
+  // Not in the reference.  With a sink, every chunk's "Color" planes go to it with the chunk's K and RT (dmi_color_add_views)
+  // right after the chunk's depths went to the fusion context: every file is read once.  A view without a UInt8 x 3 Color array
+  // of the views' size fails the call with the file's name.  Single GPU only.
+  void SetColorSink(dmi_color_context *sink) { ColorSink = sink; }
+  // Keep the (single-GPU) fusion context of a successful ProcessDepthMap instead of destroying it: its views stay resident and
+  // its grid is the fused one.  TakeContext hands it over (the caller destroys it); the destructor destroys one nobody took.
+  void SetKeepContext(bool keep) { KeepContext = keep; }
+  dmi_context *TakeContext() {
+    dmi_context *c = KeptContext;
+    KeptContext = nullptr;
+    return c;
+  }
   const std::string &LastError() const { return Error; }
   double LastFuseKernelMs() const { return FuseKernelMs; }
   int64_t NumberOfCells() const;
@@ -160,6 +172,10 @@ class FusionDriver {
   size_t HostChunkBytes = size_t(256) << 20;
   double FuseKernelMs = 0.0;
   std::string Error;
+  dmi_color_context *ColorSink = nullptr;
+  bool KeepContext = false;
+  dmi_context *KeptContext = nullptr;
+  unsigned char *FillColor = nullptr;  // where the view being filled puts its colour plane (null: not wanted)
 };
 
 // ---- Reconstruction/vtkCudaReconstructionFilter ------------------------------------------------------
@@ -206,6 +222,15 @@ class ReconstructionFilter {
   void SetFillOnCallingThread(bool yes) { FillOnCallingThread = yes; }               // FusionDriver::SetFillOnCallingThread
   void SetKernelVariant(int v) { KernelVariant = v; }
   double GetFuseKernelMs() const { return FuseKernelMs; }
+  // Not in the reference (the CLI's --meshColoration): see FusionDriver::SetColorSink / SetKeepContext; TakeContext hands over
+  // the fusion context of the last Update (views resident, grid fused), or null; the caller destroys it
+  void SetColorSink(dmi_color_context *sink) { ColorSink = sink; }
+  void SetKeepContext(bool keep) { KeepContext = keep; }
+  dmi_context *TakeContext() {
+    dmi_context *c = KeptContext;
+    KeptContext = nullptr;
+    return c;
+  }
 
  protected:
   int RequestData();
@@ -226,6 +251,9 @@ class ReconstructionFilter {
   std::vector<double> OutScalar;
   std::string Error;
   int Device = 0, KernelVariant = 0;
+  dmi_color_context *ColorSink = nullptr;
+  bool KeepContext = false;
+  dmi_context *KeptContext = nullptr;
   std::vector<int> Devices;
   // several GPUs: z-slabs by default -- the reference's f64 grid, bit-identical to one GPU, no exchange; the north star's
   // depth-map shards + f32 all-reduce (DMI_PARTITION_VIEWS: tolerance include/dmi.h states) are an explicit choice

@@ -48,7 +48,8 @@ extern "C" {
                            *    dmi_get_isosurface_filter_kernel_ms, dmi_get_isosurface_filter_pass_ms,
                            *    dmi_get_isosurface_filter_cas_retries; dmi_smooth_isosurface, dmi_get_isosurface_smooth_kernel_ms,
                            *    dmi_get_isosurface_smooth_pass_ms; dmi_decimate_isosurface, dmi_get_isosurface_decimate_kernel_ms,
-                           *    dmi_get_isosurface_decimate_pass_ms */
+                           *    dmi_get_isosurface_decimate_pass_ms; dmi_color_process_isosurface, dmi_download_isosurface_colors,
+                           *    dmi_get_isosurface_color_kernel_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -488,6 +489,42 @@ int dmi_color_get_kernel_ms(dmi_color_context *ctx, double *out);
 int dmi_color_add_views_with_depth(dmi_color_context *ctx, const uint8_t *colors, const double *depths, const double *K4,
                                    const double *RT4, int32_t n, int32_t width, int32_t height);
 int dmi_color_set_depth_test(dmi_color_context *ctx, int32_t enable, double tolerance);
+
+/* ---- Coloration of the device mesh (added after round 5, dmi_abi_version() stays 5) ----
+ * dmi_color_process_isosurface colours the mesh `ctx` holds -- the last extraction's, or what the filter, the smoother or the
+ * decimation left -- with the views resident in `c`, reading the vertices ([V][3] f64) where they are: no vertex is copied to
+ * the device and no result to the host.  It waits for whatever is still queued on the context's stream (a decimation's normals)
+ * before it starts, brings a sample of at most 1536 vertices to the host to choose the order of work as dmi_color_process does
+ * (a choice that changes no result bit) and synchronises once at its end.  The three results stay on the device, owned by `ctx`
+ * and counted in its device_bytes: mean [V][3] u8, median [V][3] u8, count [V] i32; dmi_download_isosurface_colors copies them
+ * out (any of its three pointers may be null: not wanted; it synchronises).  *n_vertices receives V.
+ * LIFE CYCLE: a successful extraction, dmi_filter_isosurface_components, dmi_smooth_isosurface with iterations > 0 or
+ * dmi_decimate_isosurface drops the colours, because they no longer describe the mesh; dmi_download_isosurface_colors is then
+ * refused with DMI_ERR_INVALID_ARGUMENT, as it is before any colouring.  A call that fails leaves mesh, normals, regions and
+ * colours as they were, a colouring that fails included (the results are built in alternates and swapped in last).
+ * fused_depth_test == 0: bit for bit what dmi_color_process(c, <the downloaded vertices>, ...) returns with c's current
+ *   settings (its own depth test and planes, dmi_color_set_vertex_reorder, dmi_color_set_scratch_budget), in the same chunks.
+ * fused_depth_test != 0: the visibility test of dmi_color_set_depth_test with the depth taken from the FUSION context instead of
+ *   from planes of `c` (none are needed: at 256 views of 720p that is 1.9 GB of HBM and of upload less).  For vertex p and view m
+ *   the pair counts iff the bounds test passes, cz > 0, d > 0 and fabs(cz - d) <= tolerance, with cz and the pixel (px, py)
+ *   exactly as there and d = view m's resident fusion depth at image pixel (px, py) widened to f64: what dmi_add_views* was given
+ *   at vtk index (H-1-py)*W + px, REPLACED BY -1 WHERE ITS BEST COST EXCEEDED THE THRESHOLD (RD.cxx:138-167).  Under
+ *   DMI_DEPTH_AUTO and DMI_DEPTH_F64 that is the thresholded f64 depth bit for bit; under a forced DMI_DEPTH_F32 it is the
+ *   stored value, i.e. the depth rounded to f32.  NaN, -1 and infinite depths reject the pair.  Unlike the own-planes test (and
+ *   --depthTolerance of dmi_coloration), whose planes are the unthresholded "Depths", a pixel that the best-cost threshold
+ *   removed no longer vouches for a vertex: the fusion did not believe that depth, and neither does the colouring.
+ *   VIEWS CORRESPOND BY INDEX: view m of `c` must be view m of `ctx` (same K, [R|T], image).  That is the caller's contract; only
+ *   the view counts and the image sizes are compared.
+ * DMI_ERR_INVALID_ARGUMENT: null c, ctx or n_vertices; no successful extraction yet; c and ctx on different devices; with the
+ * fused test a NaN, infinite or negative tolerance, c's own depth test switched on, or ctx's view count, width or height not
+ * equal to c's.  DMI_ERR_STATE: no views in c, as in dmi_color_process.  An empty mesh is a success with *n_vertices = 0: empty
+ * colours then exist and download as nothing.  Errors are reported through dmi_last_error(ctx). */
+int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t fused_depth_test, double tolerance,
+                                 uint64_t *n_vertices);
+int dmi_download_isosurface_colors(dmi_context *ctx, uint8_t *mean, uint8_t *median, int32_t *count);
+/* hipEvent time of the kernels of the last dmi_color_process_isosurface (the span of its chunks' kernels: nothing else runs
+ * between them); zero after an empty mesh */
+int dmi_get_isosurface_color_kernel_ms(dmi_context *ctx, double *last);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

@@ -104,6 +104,10 @@ typedef struct dmi_cli_options {
   double mesh_smooth_mu;                 /* --meshSmoothMu (default -0.53) */
   /* not in the reference, only with --extractMesh (dmi_decimate_isosurface, dmi.h); appended to the struct: */
   double mesh_decimate_cell_size;        /* --meshDecimateCellSize v: vertex clustering after the smoothing, world units; 0: off */
+  /* not in the reference, only with --extractMesh (dmi_color_process_isosurface, dmi.h); appended to the struct: */
+  int32_t mesh_coloration;               /* --meshColoration: colour the final mesh on the device and write the three arrays */
+  int32_t mesh_coloration_fused;         /* --meshColorationDepthTolerance was given: the fused visibility test */
+  double mesh_coloration_depth_tolerance; /* ... its tolerance (finite, >= 0) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -115,7 +119,11 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * with --meshRegionIds the file is dmi_write_polydata_with_arrays' with RegionId.  With --meshSmoothIterations N the mesh goes
  * through dmi_smooth_isosurface after those (the Normals of --meshNormals are then the smoothed mesh's geometric ones).  With
  * --meshDecimateCellSize v it goes through dmi_decimate_isosurface last (Normals: the decimated mesh's geometric ones; RegionId:
- * from the labelling run again on the decimated mesh). */
+ * from the labelling run again on the decimated mesh).  With --meshColoration (one device) the views' Color arrays go to a
+ * dmi_color_context in the same pass that reads the depths, the mesh is extracted in the context that fused (its views stay
+ * resident) and coloured last by dmi_color_process_isosurface -- with --meshColorationDepthTolerance T the fused visibility
+ * test -- and the file is dmi_write_polydata_with_colors'.  A view without a UInt8 x 3 Color array of the views' size ends the
+ * run non-zero with the file's name. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
@@ -136,6 +144,14 @@ int dmi_write_polydata_with_normals(const char *path, const double *points, int6
  * dmi_write_polydata (normals == NULL) or dmi_write_polydata_with_normals.  1 on success; 0 as those two. */
 int dmi_write_polydata_with_arrays(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
                                    int64_t n_triangles, const float *normals, double contour, const int64_t *region_id);
+
+/* dmi_write_polydata_with_arrays' file with the Coloration tool's point arrays MeanColoration (UInt8 x 3), MedianColoration
+ * (UInt8 x 3) and NbProjectedDepthMap (Int32) appended behind every array it writes: mean, median [n_points][3], count [n_points]
+ * (dmi_download_isosurface_colors), all three or none (none: exactly dmi_write_polydata_with_arrays' file).  A function of its
+ * own because the older one's signature is part of the ABI.  1 on success; 0 as those. */
+int dmi_write_polydata_with_colors(const char *path, const double *points, int64_t n_points, const int64_t *triangles,
+                                   int64_t n_triangles, const float *normals, double contour, const int64_t *region_id,
+                                   const uint8_t *mean, const uint8_t *median, const int32_t *count);
 
 /* dmi_mesh_coloration_from_lists with the visibility test of dmi_color_set_depth_test (dmi.h) at `depth_tolerance`
  * (MeshColoration::SetDepthTolerance; needs the views' "Depths" arrays).  1 on success, 0 on error (message in err). */

@@ -10,7 +10,9 @@ against the bytes it must move, the scratch it needs, and the numpy restatement 
 mesh for orientation.  With --decimate H (grid spacings; several may be given; a tiny H that the mesh's 2^21 bins refuse
 becomes the smallest size it accepts: the weld) it times dmi_decimate_isosurface after a fresh extraction with normals, pass by
 pass, with the counts before and after and the bytes each pass must move; --decimate-check compares with the numpy restatement
-(tests/isosurface_decimate_np.py).  --grid N runs the whole tool on an N^3 grid (a quick
+(tests/isosurface_decimate_np.py).  With --color it times the coloration of the device mesh
+(dmi_color_process_isosurface) against dmi_color_process, the fused depth test against the own-planes test, and both again after a
+decimation (color_record).  --grid N runs the whole tool on an N^3 grid (a quick
 run; the records in profiles/ are of the default 512).
 
     python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
@@ -187,6 +189,66 @@ def decimate_record(ctx, a):
     return rec
 
 
+def color_record(ctx, a, spacing):
+    """The --color record: the mesh of the context's grid at a.iso coloured from the scene's first a.color_views views, the calls
+    alternating in one process, a.repeat times each.  The mesh is extracted in a second context that holds those views (the fused
+    test wants the same views on both sides) and a copy of the grid.  (i) dmi_color_process on the downloaded vertices against the
+    in-place call: kernel and call wall time; (ii) the fused test against the own-planes test and the plain pass (the plain pass is (i)'s in-place call): kernel time, and
+    the HBM the fused form does not allocate; (iii) the same after a decimation at a.color_decimate grid spacings."""
+    import time
+
+    import numpy as np
+    n = a.color_views
+    tol = 2.0 * spacing
+    grid = scene.default_grid(a.grid)
+    cells = ctx.download_grid()
+    rec = {"views": n, "tolerance": tol, "meshes": []}
+    with capi.FusionContext(grid, scene.default_ray_potential(grid)) as fc, capi.ColorContext() as plain, capi.ColorContext() as own:
+        for c0 in range(0, n, 32):
+            v, thr = scene.make_scene_views("speckle", 256, 1280, 720, seed=1000, view_range=(c0, min(n, c0 + 32)), noise_sigma=spacing)
+            colors = scene.make_colors(v.n, 1280, 720, seed=2000 + c0)
+            fc.add_views(v, threshold=thr)
+            plain.add_views(colors, v.K4, v.RT4)
+            own.add_views(colors, v.K4, v.RT4, depths=v.depth)
+        own.set_depth_test(True, tol)
+        rec["own_planes_bytes_not_allocated"] = n * ((1280 + 7) // 8) * ((720 + 3) // 4) * 32 * 8
+        fc.upload_grid(cells)
+        del cells
+        verts, _ = fc.extract_isosurface(a.iso)
+        for label in ("raw", "decimated"):
+            if label == "decimated":
+                fc.decimate_isosurface(a.color_decimate * float(min(grid.spacing)))
+                verts, _ = fc.download_isosurface()
+            m = {"mesh": label, "vertices": len(verts), "copy_bytes": len(verts) * 34, "copying": {"kernel_ms": [], "wall_ms": []},
+                 "in_place": {"kernel_ms": [], "wall_ms": []}, "fused_kernel_ms": [], "own_planes_kernel_ms": []}
+            if label == "decimated":
+                m["cell_size_spacings"] = a.color_decimate
+            for r in range(a.repeat + 1):                   # the first round warms up: buffers sized, code loaded
+                t0 = time.perf_counter()
+                want = plain.process(verts)
+                t1 = time.perf_counter()
+                k_copying = plain.kernel_ms()               # (the in-place call below overwrites it)
+                fc.color_isosurface(plain)
+                t2 = time.perf_counter()
+                got = fc.download_isosurface_colors() if r == 0 else None
+                k_in_place = fc.isosurface_color_kernel_ms()
+                own.process(verts)
+                k_own = own.kernel_ms()
+                fc.color_isosurface(plain, fused_depth_tolerance=tol)
+                k_fused = fc.isosurface_color_kernel_ms()
+                if r == 0:
+                    m["in_place_equals_copying"] = all(np.array_equal(x, y) for x, y in zip(got, want))
+                    continue
+                m["copying"]["kernel_ms"].append(k_copying)
+                m["copying"]["wall_ms"].append(1e3 * (t1 - t0))
+                m["in_place"]["kernel_ms"].append(k_in_place)
+                m["in_place"]["wall_ms"].append(1e3 * (t2 - t1))
+                m["own_planes_kernel_ms"].append(k_own)
+                m["fused_kernel_ms"].append(k_fused)
+            rec["meshes"].append(m)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iso", type=float, default=1.0)
@@ -201,6 +263,9 @@ def main():
     ap.add_argument("--decimate", type=float, action="append", default=[],
                     help="also time the vertex clustering with cells of this many grid spacings (may be given several times)")
     ap.add_argument("--decimate-check", action="store_true", help="... and compare each with the numpy restatement, bit for bit")
+    ap.add_argument("--color", action="store_true", help="also time the coloration of the device mesh against dmi_color_process")
+    ap.add_argument("--color-views", type=int, default=64, help="... from the scene's first this many views")
+    ap.add_argument("--color-decimate", type=float, default=2.0, help="... and again after a decimation at this many grid spacings")
     ap.add_argument("--grid", type=int, default=512, help="cells per axis (512: the cfg-3 grid)")
     a = ap.parse_args()
     grid = scene.default_grid(a.grid)
@@ -230,6 +295,7 @@ def main():
         decimate = []
         for h in a.decimate:
             decimate.append(decimate_record(ctx, argparse.Namespace(**{**vars(a), "decimate": h})))
+        color = color_record(ctx, a, spacing) if a.color else None
     n_points = (a.grid + 1) ** 3
     lattice = n_points * 8
     out = {"iso": a.iso, "views": a.views, "vertices": nv, "triangles": nt, "kernel_ms": times, "kernel_ms_min": min(times),
@@ -245,6 +311,8 @@ def main():
         out["smooth"] = smooth
     if decimate:
         out["decimate"] = decimate
+    if color is not None:
+        out["color"] = color
     print(json.dumps(out))
 
 
