@@ -170,6 +170,18 @@ struct ordered {
     asm volatile("v_rcp_f32 %0, %1" : "=v"(r) : "v"(x));
     return r;
   }
+  // The two links of a Newton step r' = r * (2 - z' * r) from a neighbouring voxel's reciprocal r to that of z' (the window
+  // column): 2.7 + 2.3 issue cycles where v_rcp_f32 takes 8.9 (tools/microbench/issue_rates.hip)
+  static __device__ __forceinline__ float two_minus(float z, float r) {
+    float d;
+    asm volatile("v_fma_f32 %0, -%1, %2, 2.0" : "=v"(d) : "v"(z), "v"(r));
+    return d;
+  }
+  static __device__ __forceinline__ float mul(float a, float b) {
+    float d;
+    asm volatile("v_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+  }
   static __device__ __forceinline__ f32x2 pk_fma_lo_s(f32x2 a, f32x2 b, unsigned long long c_bits) {
     f32x2 d;
     asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "v"(b), "s"(c_bits));
@@ -747,6 +759,16 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         uint32_t undecided = 0, und_kk = 0;  // per lane / wave-uniform: bit kk = voxel kk is redone after the column
         uint32_t window = 0;                 // this lane's row of the window
         constexpr int WG = 4;                // voxels per group
+        // Only the column's FIRST reciprocal is a v_rcp_f32: c.z is affine along the column, so one Newton step from the reciprocal of
+        // the voxel below, r' = r * (2 - z' * r), gives the next with a relative error of (dz / z)^2 -- a candidate as good as any
+        // (the verification is what the result rests on).  One value is carried from group to group.
+        // -DDMI_T1_RCP_EVERY_VOXEL: a v_rcp_f32 per voxel, as before (same results: an A/B switch for tools/gpu_exp.py).
+#ifdef DMI_T1_RCP_EVERY_VOXEL
+        constexpr bool kNewton = false;
+#else
+        constexpr bool kNewton = true;
+#endif
+        [[maybe_unused]] f32x2 r_below;      // (low half) the reciprocal of the last voxel of the group before
         // A group's look-ups are issued after its candidates and consumed after the NEXT group's candidates: neither the
         // window's loads nor a look-up's trip through the LDS crossbar is waited for
         uint32_t pw[WG], pc[WG];             // the previous group's words and columns
@@ -777,6 +799,36 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
           // whether the statement was a transcendental or wrote half a register) -- six per voxel when a chain runs on its own
           mask_t m_und[WG];
           constexpr int IL = DMI_T1_CHAINS;  // voxels whose chains alternate
+          if constexpr (kNewton) {
+            // The group's four chains by hand: the reciprocals hang on one another (voxel u's on voxel u - 1's), so the chains are
+            // staggered by two links instead of running side by side -- still one instruction at least between a producer and its reader
+            static_assert(WG == 4, "the link order below is written for groups of four");
+            f32x2 h[WG], cth[WG], r[WG], rpm[WG], rp[WG], t[WG];
+            float tw[WG], mx[WG];
+            auto kbits = [](int kk) __attribute__((always_inline)) { return (unsigned long long)(unsigned)__float_as_int((float)kk); };
+            auto lz = [&](int u) __attribute__((always_inline)) { cth[u] = g0 + u > 0 ? ordered::pk_fma_s(kbits(g0 + u), DC, C0) : C0; };
+            auto lh = [&](int u) __attribute__((always_inline)) { h[u] = g0 + u > 0 ? ordered::pk_fma_s(kbits(g0 + u), DH, H0) : H0; };
+            auto l2 = [&](int u) __attribute__((always_inline)) {
+              if (g0 + u > 0) tw[u] = ordered::two_minus(cth[u].x, u > 0 ? r[u > 0 ? u - 1 : 0].x : r_below.x);
+            };
+            auto lr = [&](int u) __attribute__((always_inline)) {
+              r[u].x = g0 + u > 0 ? ordered::mul(u > 0 ? r[u > 0 ? u - 1 : 0].x : r_below.x, tw[u]) : ordered::rcp(cth[u].x);
+            };
+            auto lq = [&](int u) __attribute__((always_inline)) { rpm[u] = ordered::pk_fma_lo_s(h[u], r[u], M2); };
+            auto lp = [&](int u) __attribute__((always_inline)) { rp[u] = ordered::pk_sub_s(rpm[u], M2); };
+            auto lt = [&](int u) __attribute__((always_inline)) { t[u] = ordered::pk_fnma_lo(rp[u], cth[u], h[u]); };
+            auto lm = [&](int u) __attribute__((always_inline)) { mx[u] = ordered::max_abs(t[u].x, t[u].y); };
+            lz(0), lz(1), lz(2), lz(3);
+            l2(0), lh(0), lr(0), lh(1), l2(1), lh(2), lr(1), lq(0), l2(2), lp(0), lr(2), lq(1), l2(3), lt(0), lr(3), lh(3);
+            lp(1), lq(2), lm(0), lq(3), lt(1), lp(2), lm(1), lp(3), lt(2), lt(3), lm(2), lm(3);
+            r_below = r[WG - 1];
+  #pragma unroll
+            for (int u = 0; u < WG; ++u) {
+              m_und[u] = ballot(!(mx[u] < cth[u].y));  // (a NaN is not accepted)
+              wg[u] = (unsigned)__float_as_int(__builtin_fmaf(rp[u].y, 4.0f, magic_v));  // (see the other form below)
+              cg[u] = (uint32_t)__float_as_int(rpm[u].x);
+            }
+          } else {
   #pragma unroll
           for (int q0 = 0; q0 < WG; q0 += IL) {
             f32x2 h[IL], cth[IL], rr[IL], rpm[IL], rp[IL], t[IL];
@@ -811,6 +863,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
               wg[q0 + u] = (unsigned)__float_as_int(__builtin_fmaf(rp[u].y, 4.0f, magic_v));
               cg[q0 + u] = (uint32_t)__float_as_int(rpm[u].x);
             }
+          }
           }
           mask_t m_und_any = m_und[0];
   #pragma unroll
