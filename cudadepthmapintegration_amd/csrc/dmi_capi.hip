@@ -373,11 +373,13 @@ void make_centred_rows(const dmi_context *ctx, const MapRec &r, const double P[4
     }
     // |hw_ref - model| <= cerr + Xmax * nl2: the centred numerator within cerr of the affine model anchored at the brick's first
     // voxel (the budget of 4d.1 covers the anchor's FMA chain and seven steps each way: < 100 of its 512 ulp), the reference's
-    // c.z within nl2 of ITS model (two computed values, 8 ulp(M[2]) each, rotated grids twice that), times the window's origin
-    const double xmax = (double)(std::max(ctx->W, ctx->H) / 2 + dmi::kValidMargin + 1);
+    // c.z within nl2 of ITS model (two computed values, 8 ulp(M[2]) each, rotated grids twice that), times the window's anchor
+    // pixel Xc: its first pixel (|.| <= xpix) plus (kWinAnchorX, kWinAnchorY)
+    const double xpix = (double)(std::max(ctx->W, ctx->H) / 2 + dmi::kValidMargin + 1);
+    const double xmax = xpix + (double)std::max(dmi::kWinAnchorX, dmi::kWinAnchorY);
     const double nl2 = 2.0 * nl;
-    const double pwin = (dmi::kWindowRows - 0.5) * dmi::kWinCzRatio + 3.0;  // bounds an accepted candidate: |P| < |h| / z + 1/2
-    // the steps as the kernel forms them, fl32(d32 - X0 * c32): each within 2^-23 (|d| + |X0 c|) of the real one; a lane takes up
+    const double pwin = (dmi::kWinReach + 0.5) * dmi::kWinCzRatio + 3.0;  // bounds an accepted candidate: |P| < |h| / z + 1/2
+    // the steps as the kernel forms them, fl32(d32 - Xc * c32): each within 2^-23 (|d| + |Xc c|) of the real one; a lane takes up
     // to 7 along i and j and kMaxColumn - 1 along k
     const double steps[3] = {7.0, 7.0, (double)(kMaxColumn - 1)};
     double e_step = 0.0;
@@ -411,7 +413,7 @@ void make_centred_rows(const dmi_context *ctx, const MapRec &r, const double P[4
           dst[2] = (float)((ni * c[0] + nj * c[1]) + nk * c[2]);
         }
       }
-      foot->ferr = float_not_below(cerr + xmax * nl2);
+      foot->ferr = float_not_below(cerr + xpix * nl2);  // (times a pixel's |u''|, not an anchor's)
     }
   }
   if (per_lane) {
@@ -1406,10 +1408,11 @@ int fuse_run(dmi_context *ctx, int32_t first, int32_t count, int32_t z_first, in
           DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
           (void)hipFree(ctx->d_wg_times);
         }
-        DMI_HIP(ctx, hipMalloc(&ctx->d_wg_times, blocks * 3 * sizeof(unsigned long long)));
-        ctx->wg_times_blocks = blocks;
+        // (+ 2: the launch's window pairs and their redone wave-voxels, dmi_debug_window_counts)
+        DMI_HIP(ctx, hipMalloc(&ctx->d_wg_times, (blocks * 3 + 2) * sizeof(unsigned long long)));
       }
-      DMI_HIP(ctx, hipMemsetAsync(ctx->d_wg_times, 0, blocks * 3 * sizeof(unsigned long long), ctx->stream));
+      ctx->wg_times_blocks = blocks;  // of THIS launch (a smaller one after a larger reuses the buffer; a larger one reallocates)
+      DMI_HIP(ctx, hipMemsetAsync(ctx->d_wg_times, 0, (blocks * 3 + 2) * sizeof(unsigned long long), ctx->stream));
       t.wg_times = ctx->d_wg_times;
       t.wg_times_n = (int64_t)blocks;
     }
@@ -1826,6 +1829,16 @@ extern "C" int dmi_debug_wg_times(dmi_context *ctx, unsigned long long *out, int
   if (!ctx->d_wg_times || !out || capacity < 3 * (int64_t)ctx->wg_times_blocks) return DMI_OK;
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return DMI_ERR_DEVICE;
   if (hipMemcpy(out, ctx->d_wg_times, ctx->wg_times_blocks * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
+    return DMI_ERR_DEVICE;
+  return DMI_OK;
+}
+// ... and the two counters behind it: out[0] = window pairs executed (per wave), out[1] = wave-voxels redone after a window column
+extern "C" int dmi_debug_window_counts(dmi_context *ctx, unsigned long long *out) {
+  if (!ctx || !out) return DMI_ERR_INVALID_ARGUMENT;
+  out[0] = out[1] = 0;
+  if (!ctx->d_wg_times) return DMI_OK;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return DMI_ERR_DEVICE;
+  if (hipMemcpy(out, ctx->d_wg_times + 3 * ctx->wg_times_blocks, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess)
     return DMI_ERR_DEVICE;
   return DMI_OK;
 }

@@ -719,7 +719,7 @@ __global__ __launch_bounds__(256) void classify_kernel(const TileArgs a, const M
 // in [rx0, rx1] x [ry0, ry1], inside the image or its margin.  Where that rectangle fits a window of kWindowCols x kWindowRows
 // pixels, the view has a window record (WinRec::e_abs finite) and c.z varies by less than kWinCzRatio over the brick, the pair's
 // WinPair is written and its class byte marked; every other pair keeps the gathering column.  WinPair (round 5): the window's
-// first pixel and, in fp64 rounded once to fp32, the window-relative numerators hw = h'' - X0 * c.z and c.z at the brick's
+// first pixel and, in fp64 rounded once to fp32, the window-relative numerators hw = h'' - Xc * c.z (Xc: the window's centre) and c.z at the brick's
 // voxel (0, 0, 0) -- h'' by the FMA chain over the centred rows (TileMapRec::cpx ...) at that voxel's computed world position,
 // c.z in the reference's order (cu:90-92, cu:172), exactly as the fusion kernel's fp64 tier forms them.
 // A wave is 64 consecutive bricks and walks over kOriginViews views, four class bytes per load; the view is
@@ -830,9 +830,9 @@ __global__ __launch_bounds__(256) void window_origin_kernel(const TileArgs a, co
             if (x0 >= -kValidMargin && y0 >= -kValidMargin && x1 < a.W + kValidMargin && y1 < a.H + kValidMargin &&
                 x1 - x0 < kWindowCols && y1 - y0 < kWindowRows) {
               wp.origin = (uint32_t)(x0 + kValidMargin) | ((uint32_t)(y0 + kValidMargin) << 16);
-              // the window's first pixel counted from the image centre (integers: exact)
-              wp.ax = (float)(hxa - (double)(x0 - cxc) * cza);
-              wp.ay = (float)(hya - (double)(y0 - cyc) * cza);
+              // the anchor pixel Xc -- the window's centre (kWinAnchorX, kWinAnchorY) -- counted from the image centre (integers: exact)
+              wp.ax = (float)(hxa - (double)(x0 + kWinAnchorX - cxc) * cza);
+              wp.ay = (float)(hya - (double)(y0 + kWinAnchorY - cyc) * cza);
               wp.acz = z0;
             }
           }

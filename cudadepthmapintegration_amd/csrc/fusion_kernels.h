@@ -144,9 +144,9 @@ static_assert(sizeof(TileMapRec) == 368, "TileMapRec layout");
 // What the window form of the FREE column needs of a view (round 5): ONE 64-byte line, all fp32, fetched with one scalar load per
 // (brick, view) -- the 368-byte TileMapRec took five or six dependent batches of them, which with four waves per SIMD was what
 // the column waited for.  The centred numerators hx'', hy'' (TileMapRec::cpx ...) and c.z are affine in the voxel's indices; the
-// column works in coordinates relative to the WINDOW's first pixel X0 = (x0'', y0''), hw = h'' - X0 * c.z, whose value at the
-// brick's first voxel window_origin_kernel has formed in fp64 (WinPair): |hw| <= (window size + 1) * c.z, so every fp32 rounding
-// on the way costs 2^-24 of some sixty c.z instead of 2^-24 of up to W/2 c.z.  d*: steps of (hx'', hy'') per
+// column works in coordinates relative to the WINDOW's centre Xc = first pixel + (kWinAnchorX, kWinAnchorY), hw = h'' - Xc * c.z,
+// whose value at the brick's first voxel window_origin_kernel has formed in fp64 (WinPair): |hw| <= (half a window + 1/2) * c.z, so
+// every fp32 rounding on the way costs 2^-24 of some thirty c.z instead of 2^-24 of up to W/2 c.z.  d*: steps of (hx'', hy'') per
 // voxel along i, j, k; c*: (step of c.z, c1 times it) -- the second half steps the acceptance threshold c1 * c.z - e_abs.
 struct alignas(64) WinRec {
   const uint32_t *vbits;  // TileMapRec::vbits
@@ -165,7 +165,19 @@ struct alignas(64) FootRec {
   float ferr, pad[15];
 };
 static_assert(sizeof(FootRec) == 320, "FootRec layout");
-constexpr float kWinC1 = 0.5f - 0x1p-14f;  // what is left of 1/2 after every c.z-proportional rounding of the window column (4e.6)
+// The window column counts its coordinates from the window's CENTRE, first pixel + (kWinAnchorX, kWinAnchorY): |hw| <= (half the
+// window + 1/2) * c.z, half of what the corner gave, and so are the c.z-proportional roundings that c1 has to absorb (4e.6).
+// -DDMI_WIN_CORNER_ANCHOR counts from the first pixel again, with the wider band that needs (same results: an A/B switch for
+// tools/gpu_exp.py, tools/exp_list_window_centre.txt).
+#ifdef DMI_WIN_CORNER_ANCHOR
+constexpr int kWinAnchorX = 0, kWinAnchorY = 0;
+constexpr float kWinC1 = 0.5f - 0x1p-14f;
+#else
+constexpr int kWinAnchorX = kWindowCols / 2, kWinAnchorY = kWindowRows / 2;
+constexpr float kWinC1 = 0.5f - 0x1p-15f;  // what is left of 1/2 after every c.z-proportional rounding of the window column (4e.6)
+#endif
+// an accepted candidate's magnitude stays below (this + 1/2) * kWinCzRatio + 3 (make_centred_rows)
+constexpr int kWinReach = kWinAnchorY ? kWindowRows - kWinAnchorY : kWindowRows - 1;
 // the brick's c.z may vary by this factor at most for the pair to get a window (bounds |hw| by the threshold's own c.z)
 constexpr double kWinCzRatio = 1.25;
 // Per windowed (brick, view) pair, TileArgs::win_origin[brick * class_pitch + view]: the window's first pixel (padded-image

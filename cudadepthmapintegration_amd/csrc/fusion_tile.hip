@@ -491,6 +491,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
   if (kb->wg_times) wg_t0 = __builtin_amdgcn_s_memrealtime();
   unsigned dbg_cols = 0, dbg_redo = 0;  // views with a column of their own / voxels redone after their column
   unsigned dbg_win = 0, dbg_win_early = 0;  // window pairs / those before the brick's first view of another column
+  unsigned dbg_win_redo = 0;                // voxels redone after a WINDOW column (dbg_redo counts every column's)
 #endif
   const int wbx = bx * WX + (w % WX), wby = by * WY + (w / WX);    // this wave's brick (8 x 8 x TK voxels)
   if ((wbx >= kb->wbricks_x) | (wby >= kb->wbricks_y)) DMI_NEXT_BRICK     // wave entirely outside the grid
@@ -653,9 +654,9 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
     // the 32 x 64 pixels that start at (x0, y0) = TileArgs::win_origin[brick][view] (padded-image coordinates).  Lane r fetches
     // row y0 + r of the view's validity bits (two dwords from one or two 128-byte tiles, funnel-shifted to start at x0): two
     // coalesced loads per (brick, view), in flight while the column is set up.  A voxel asks the lane that holds its row with
-    // ds_bpermute_b32.  The candidate is formed WITH the window's origin: rpm = fl32(h'' * rcp + (1.5 * 2^23 - origin)) is an
-    // integer-valued float whose low mantissa bits are the pixel's column / row within the window (v_bfe_u32 and
-    // ds_bpermute_b32 read only those bits), and P = rpm - (1.5 * 2^23 - origin), exact, is the candidate that the verification
+    // ds_bpermute_b32.  The candidate is formed in window-relative coordinates: rpm = fl32(hw * rcp + (1.5 * 2^23 + anchor)) is an
+    // integer-valued float whose low mantissa bits are the pixel's column / row within the window (v_bfe_i32 and
+    // ds_bpermute_b32 read only those bits), and P = rpm - (1.5 * 2^23 + anchor), exact, is the candidate that the verification
     // of tier 1 accepts or not (4d.3: any candidate will do).  What it does not accept is redone after the column, in fp64
     // (tier 2), then with the reference's expression.  The whole view is handled here, apart from the other columns, so that
     // nothing of it stays live across them.
@@ -711,12 +712,13 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
 #endif
         // the window's first pixel counted from the image centre
         const int x0c = x0p - kw->win_cx, y0c = y0p - kw->win_cy;
-        // ---- set-up, all fp32: the window-relative numerators hw = h'' - X0 * c.z, c.z and the acceptance
+        // ---- set-up, all fp32: the window-relative numerators hw = h'' - Xc * c.z, c.z and the acceptance
         // threshold are affine in (lane.x, lane.y, kk); their values at the brick's first voxel come with the pair (A2, acz), the
-        // steps with the view: Bw = d - X0 * c per axis, then two packed FMAs along i and j
+        // steps with the view: Bw = d - Xc * c per axis, then two packed FMAs along i and j.  Xc is the window's CENTRE, its first
+        // pixel plus (kWinAnchorX, kWinAnchorY) (scalar adds): |hw| <= (half a window + 1/2) * c.z
         f32x2 O, LJ;
-        O.x = (float)x0c;
-        O.y = (float)y0c;
+        O.x = (float)(x0c + kWinAnchorX);
+        O.y = (float)(y0c + kWinAnchorY);
         LJ.x = (float)(lane & 7);
         LJ.y = (float)(lane >> 3);
         auto pair_of = [&](int q) __attribute__((always_inline)) { return (unsigned long long)R[q] | ((unsigned long long)R[q + 1] << 32); };
@@ -736,9 +738,11 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         CA.y = __builtin_fmaf(acz, __uint_as_float(R[15]), -__uint_as_float(R[14]));
         const f32x2 C0 = pk_fma_hi0_sv(LJ, pair_of(10), pk_fma_lo0_sv(LJ, pair_of(8), CA));
         const f32x2 DC = vec_of(12);
-        unsigned long long M2 = 0x4B4000004B400000ull;  // (1.5 * 2^23, 1.5 * 2^23)
+        // (1.5 * 2^23 + kWinAnchorX, 1.5 * 2^23 + kWinAnchorY): rpm's low bits are the candidate's column / row within the window,
+        // P' + anchor >= 0, and rp = rpm - M2 is the centre-relative candidate P' that the verification reads
+        unsigned long long M2 = (0x4B400000ull + (unsigned)kWinAnchorX) | ((0x4B400000ull + (unsigned)kWinAnchorY) << 32);
         asm volatile("" : "+s"(M2));  // a register pair for the column's life (as a constant its high half was rebuilt for every other voxel)
-        float magic_v = 0x1.8p23f;  // ... in a vector register (a scalar operand would make the FMA above a slower encoding)
+        float magic_v = 0x1.8p23f + (float)(4 * kWinAnchorY);  // ... plus 4 * the anchor's row (the row address below), in a vector register (a scalar operand would make the FMA above a slower encoding)
         asm volatile("" : "+v"(magic_v));
         // fp64 values at the column's first voxel for the redo below: the centred h.x, h.y (TileMapRec::cpx ...) and the exact
         // c.z (cu:92, cu:172), as every tier-1 column starts from them
@@ -825,7 +829,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
   #pragma unroll
             for (int u = 0; u < WG; ++u) {
               m_und[u] = ballot(!(mx[u] < cth[u].y));  // (a NaN is not accepted)
-              wg[u] = (unsigned)__float_as_int(__builtin_fmaf(rp[u].y, 4.0f, magic_v));  // (see the other form below)
+              wg[u] = (unsigned)__float_as_int(__builtin_fmaf(rp[u].y, 4.0f, magic_v));  // 4 * (P'.y + kWinAnchorY) (see the other form below)
               cg[u] = (uint32_t)__float_as_int(rpm[u].x);
             }
           } else {
@@ -898,6 +902,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         while (und_kk) {  // wave-uniform
 #ifdef DMI_TUNING
           ++dbg_redo;
+          ++dbg_win_redo;
 #endif
           const int kk = __builtin_ctz(und_kk);
           und_kk &= und_kk - 1;
@@ -1486,6 +1491,13 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
                             ((unsigned long long)(dbg_win & 0x3ffu) << 42) | ((unsigned long long)(dbg_win_early & 0x3ffu) << 52) |
                             ((unsigned long long)(dbg_redo > 3 ? 3 : dbg_redo) << 62);
     }
+  }
+  // the launch's window pairs and the wave-voxels redone after their columns, exactly: two 64-bit counters behind the records
+  // (one lane per wave adds: a brick's waves run the same views, so the pairs count once per wave as the redo does)
+  if (KC(wg_times) && lane == 0 && (dbg_win | dbg_win_redo)) {
+    unsigned long long *wc = KC(wg_times) + 3 * (size_t)KC(wg_times_n);
+    atomicAdd(wc, (unsigned long long)dbg_win);
+    atomicAdd(wc + 1, (unsigned long long)dbg_win_redo);
   }
 #endif
   if (n_uniform > 0) {  // no view had work of its own: every voxel of the brick holds the same sum
