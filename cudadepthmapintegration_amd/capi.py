@@ -93,6 +93,8 @@ class MultiTimingsC(ctypes.Structure):
 DMI_PARTITION_VIEWS, DMI_PARTITION_Z_SLABS = 0, 1
 DMI_EXCHANGE_ALL_REDUCE, DMI_EXCHANGE_REDUCE_SCATTER, DMI_EXCHANGE_PEER_COPY = 0, 1, 2
 DMI_UNIQUE_ID_BYTES = 128
+# the rasteriser's compile-time shape (csrc/mesh_depth_render.h: kRenderViewGroup, kRenderLaneCap), for tests that aim at its edges
+RENDER_VIEW_GROUP, RENDER_LANE_CAP = 16, 64
 
 # every symbol include/dmi.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
@@ -112,6 +114,8 @@ ABI_SYMBOLS = [
     "dmi_smooth_isosurface", "dmi_get_isosurface_smooth_kernel_ms", "dmi_get_isosurface_smooth_pass_ms",
     "dmi_decimate_isosurface", "dmi_get_isosurface_decimate_kernel_ms", "dmi_get_isosurface_decimate_pass_ms",
     "dmi_color_process_isosurface", "dmi_download_isosurface_colors", "dmi_get_isosurface_color_kernel_ms",
+    "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
+    "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -237,6 +241,13 @@ def load() -> ctypes.CDLL:
     L.dmi_download_isosurface_colors.argtypes = [vp, u8p, u8p, ctypes.POINTER(ctypes.c_int32)]
     L.dmi_get_isosurface_color_kernel_ms.argtypes = [vp, dp]
     L.dmi_color_last_error.restype = ctypes.c_char_p
+    L.dmi_color_render_depths.argtypes = [vp, dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64]
+    L.dmi_color_render_isosurface_depths.argtypes = [vp, vp]
+    L.dmi_color_download_depths.argtypes = [vp, i32, i32, dp]
+    L.dmi_color_get_render_kernel_ms.argtypes = [vp, dp]
+    L.dmi_color_set_render_queue_capacity.argtypes = [vp, ctypes.c_uint64]
+    L.dmi_color_get_render_pass_ms.argtypes = [vp, dp]
+    L.dmi_color_get_render_queued_pairs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     i64, i64p, i32p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
@@ -633,6 +644,11 @@ class FusionContext:
                                                              count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return mean[:nv], median[:nv], count[:nv]
 
+    def render_isosurface_depths(self, color_ctx: "ColorContext") -> None:
+        """Render the context's mesh, where it is, into the depth planes of every view resident in `color_ctx`: bit for bit what
+        color_ctx.render_depths(*download_isosurface()) leaves (dmi_color_render_isosurface_depths; DESIGN.md 8b'')."""
+        self._check(self._lib.dmi_color_render_isosurface_depths(color_ctx._h, self._h))
+
     def isosurface_color_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last color_isosurface (dmi_get_isosurface_color_kernel_ms)."""
         a = ctypes.c_double(0)
@@ -932,6 +948,7 @@ class ColorContext:
     def __init__(self, device: int = 0):
         self._lib = load()
         self._h = ctypes.c_void_p()
+        self._n_views, self._W, self._H = 0, 0, 0
         rc = self._lib.dmi_color_create(device, ctypes.byref(self._h))
         if rc != DMI_OK:
             self._h = ctypes.c_void_p()
@@ -968,11 +985,13 @@ class ColorContext:
         u8 = ctypes.POINTER(ctypes.c_uint8)
         if depths is None:
             self._check(self._lib.dmi_color_add_views(self._h, col.ctypes.data_as(u8), _dp(k), _dp(rt), n, W, H))
+            self._n_views, self._W, self._H = self._n_views + n, W, H
             return
         d = np.ascontiguousarray(depths, dtype=np.float64)
         if d.shape != (n, H, W):
             raise ValueError(f"depths {d.shape} do not match the colour planes ({n}, {H}, {W})")
         self._check(self._lib.dmi_color_add_views_with_depth(self._h, col.ctypes.data_as(u8), _dp(d), _dp(k), _dp(rt), n, W, H))
+        self._n_views, self._W, self._H = self._n_views + n, W, H
 
     def set_depth_test(self, enable: bool, tolerance: float = 0.0):
         """The visibility test (include/dmi.h, dmi_color_set_depth_test): a pair counts only if the vertex is in front of the
@@ -981,6 +1000,7 @@ class ColorContext:
 
     def clear_views(self):
         self._check(self._lib.dmi_color_clear_views(self._h))
+        self._n_views, self._W, self._H = 0, 0, 0
 
     def process(self, points, out=None):
         """(mean [n, 3] u8, median [n, 3] u8, count [n] i32) of the vertices `points` [n, 3] f64.  out: the three arrays to fill
@@ -1001,6 +1021,47 @@ class ColorContext:
         self._check(self._lib.dmi_color_process(self._h, _dp(pts), nv, mean.ctypes.data_as(u8), median.ctypes.data_as(u8),
                                                 count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
         return mean, median, count
+
+    def render_depths(self, points, triangles):
+        """Render the triangle mesh (points [n, 3] f64, triangles [t, 3] ids) into the depth plane of every resident view: the
+        z-buffer the visibility test then compares against (dmi_color_render_depths; DESIGN.md 8b'').  Views added without
+        depths get a plane, uploaded planes are replaced."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        tri = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+        self._check(self._lib.dmi_color_render_depths(self._h, _dp(pts), pts.shape[0], tri.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                      tri.shape[0]))
+
+    def download_depths(self, first: int = 0, count: int | None = None):
+        """The depth planes of views [first, first + count) as [count, H, W] f64 in vtk row order -- what add_views(depths=...)
+        takes --, -1 where nothing was rendered (dmi_color_download_depths).  count None: all views from `first` on."""
+        n, W, H = self._n_views, self._W, self._H  # (kept by add_views / clear_views: the C ABI has no query for them)
+        if count is None:
+            count = max(n - int(first), 0)
+        out = np.zeros((max(int(count), 1), H, W), dtype=np.float64)
+        self._check(self._lib.dmi_color_download_depths(self._h, int(first), int(count), _dp(out)))
+        return out[:int(count)]
+
+    def render_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last render_depths / render_isosurface_depths."""
+        v = ctypes.c_double(0)
+        self._check(self._lib.dmi_color_get_render_kernel_ms(self._h, ctypes.byref(v)))
+        return float(v.value)
+
+    def render_pass_ms(self) -> dict:
+        """The same pass by pass: the fill, the small passes, the large passes (dmi_color_get_render_pass_ms)."""
+        a = (ctypes.c_double * 3)()
+        self._check(self._lib.dmi_color_get_render_pass_ms(self._h, a))
+        return dict(zip(("init", "small", "large"), (float(x) for x in a)))
+
+    def render_queued_pairs(self) -> int:
+        """(triangle, view) pairs the last rendering's large passes took (dmi_color_get_render_queued_pairs)."""
+        v = ctypes.c_uint64(0)
+        self._check(self._lib.dmi_color_get_render_queued_pairs(self._h, ctypes.byref(v)))
+        return int(v.value)
+
+    def set_render_queue_capacity(self, n: int):
+        """Entries the rasteriser's queue of large (triangle, view) pairs starts with (it grows on demand; same result)."""
+        self._check(self._lib.dmi_color_set_render_queue_capacity(self._h, int(n)))
 
     def set_scratch_budget(self, n_bytes: int):
         """Bound the device scratch of one vertex chunk (more, smaller chunks; same result)."""
@@ -1041,7 +1102,7 @@ HOST_ABI_SYMBOLS = [
     "dmi_apply_depth_threshold", "dmi_read_depth_map", "dmi_read_depth_map_color", "dmi_mesh_coloration_from_lists",
     "dmi_cli_read_arguments", "dmi_cli_main", "dmi_write_polydata", "dmi_write_polydata_with_normals",
     "dmi_write_polydata_with_arrays", "dmi_write_polydata_with_colors",
-    "dmi_mesh_coloration_from_lists_with_depth", "dmi_read_polydata", "dmi_polydata_free", "dmi_polydata_counts",
+    "dmi_mesh_coloration_from_lists_with_depth", "dmi_mesh_coloration_from_lists_with_mesh_depth", "dmi_read_polydata", "dmi_polydata_free", "dmi_polydata_counts",
     "dmi_polydata_array", "dmi_polydata_designations", "dmi_color_cli_read_arguments", "dmi_color_cli_main",
 ]
 
@@ -1098,6 +1159,11 @@ def load_host() -> ctypes.CDLL:
     L.dmi_mesh_coloration_from_lists_with_depth.argtypes = [dp, i64, ctypes.c_char_p, ctypes.c_char_p, i32, ctypes.c_double,
                                                             ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8),
                                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_char_p, ctypes.c_size_t]
+    L.dmi_mesh_coloration_from_lists_with_mesh_depth.restype = ctypes.c_int
+    L.dmi_mesh_coloration_from_lists_with_mesh_depth.argtypes = [dp, i64, ctypes.POINTER(ctypes.c_int64), i64, ctypes.c_char_p, ctypes.c_char_p,
+                                                                 i32, ctypes.c_double, ctypes.POINTER(ctypes.c_uint8),
+                                                                 ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32), dp,
+                                                                 ctypes.c_char_p, ctypes.c_size_t]
     L.dmi_read_polydata.restype = ctypes.c_void_p
     L.dmi_read_polydata.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     L.dmi_polydata_free.restype = None
@@ -1226,7 +1292,8 @@ class CliOptionsC(ctypes.Structure):
                 ("mesh_min_component_triangles", ctypes.c_int64), ("mesh_smooth_iterations", ctypes.c_int64),
                 ("mesh_smooth_lambda", ctypes.c_double), ("mesh_smooth_mu", ctypes.c_double),
                 ("mesh_decimate_cell_size", ctypes.c_double), ("mesh_coloration", ctypes.c_int32),
-                ("mesh_coloration_fused", ctypes.c_int32), ("mesh_coloration_depth_tolerance", ctypes.c_double)]
+                ("mesh_coloration_fused", ctypes.c_int32), ("mesh_coloration_depth_tolerance", ctypes.c_double),
+                ("mesh_coloration_depth_from_mesh", ctypes.c_int32)]
 
 
 def cli_read_arguments(args):
@@ -1376,9 +1443,11 @@ def read_depth_map_color(path):
     return c.reshape(dims[1], dims[0], 3)
 
 
-def mesh_coloration_from_lists(points, vti_list, krtd_list, device: int = 0, depth_tolerance: float | None = None):
+def mesh_coloration_from_lists(points, vti_list, krtd_list, device: int = 0, depth_tolerance: float | None = None, triangles=None):
     """MeshColoration(mesh, vtiList, krtdList).ProcessColoration() through the host mirror (reads the .vti/.krtd files).
-    depth_tolerance: with the depth test of dmi_color_set_depth_test (MeshColoration::SetDepthTolerance)."""
+    depth_tolerance: with the depth test of dmi_color_set_depth_test (MeshColoration::SetDepthTolerance).  triangles [t, 3] ids
+    (needs depth_tolerance): the test compares against the mesh's own rendered depth and the files need no "Depths" arrays
+    (dmi_mesh_coloration_from_lists_with_mesh_depth)."""
     L = load_host()
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
     nv = pts.shape[0]
@@ -1388,7 +1457,14 @@ def mesh_coloration_from_lists(points, vti_list, krtd_list, device: int = 0, dep
     err = ctypes.create_string_buffer(512)
     u8 = ctypes.POINTER(ctypes.c_uint8)
     outs = (mean.ctypes.data_as(u8), median.ctypes.data_as(u8), count.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), err, len(err))
-    if depth_tolerance is None:
+    if triangles is not None:
+        if depth_tolerance is None:
+            raise ValueError("triangles (the mesh's own depth) need a depth_tolerance")
+        tri = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+        ok = L.dmi_mesh_coloration_from_lists_with_mesh_depth(_dp(pts), nv, tri.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), tri.shape[0],
+                                                              os.fsencode(vti_list), os.fsencode(krtd_list), device, float(depth_tolerance),
+                                                              outs[0], outs[1], outs[2], None, err, len(err))
+    elif depth_tolerance is None:
         ok = L.dmi_mesh_coloration_from_lists(_dp(pts), nv, os.fsencode(vti_list), os.fsencode(krtd_list), device, *outs)
     else:
         ok = L.dmi_mesh_coloration_from_lists_with_depth(_dp(pts), nv, os.fsencode(vti_list), os.fsencode(krtd_list), device,
@@ -1450,7 +1526,7 @@ def read_polydata(path) -> PolyDataFile:
 class ColorCliOptionsC(ctypes.Structure):
     _fields_ = [("input", ctypes.c_char * 4096), ("output", ctypes.c_char * 4096), ("krtd", ctypes.c_char * 4096),
                 ("vti", ctypes.c_char * 4096), ("verbose", ctypes.c_int32), ("device", ctypes.c_int32), ("depth_test", ctypes.c_int32),
-                ("depth_tolerance", ctypes.c_double)]
+                ("depth_tolerance", ctypes.c_double), ("depth_from_mesh", ctypes.c_int32)]
 
 
 def color_cli_read_arguments(args):

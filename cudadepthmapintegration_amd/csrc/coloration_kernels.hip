@@ -26,6 +26,7 @@
 #include "../../include/dmi.h"
 #include "dmi_context.h"
 #include "fusion_kernels.h"
+#include "mesh_depth_render.h"
 
 #include <stdlib.h>
 
@@ -112,18 +113,8 @@ struct FastQuotient {
 // ((y >> 2) * tiles_x + (x >> 3)) * 32 + (y & 3) * 8 + (x & 7)).  The vertices of a wave are neighbours on the surface, their
 // pixels a patch of a few pixels each way: in rows of texels such a patch touches a line per image row, in tiles about half as
 // many (profiles/r17t_*).
-#ifndef DMI_TEX_TILE_LOG_W
-#define DMI_TEX_TILE_LOG_W 3
-#define DMI_TEX_TILE_LOG_H 2
-#endif
-constexpr int kTexLogW = DMI_TEX_TILE_LOG_W, kTexLogH = DMI_TEX_TILE_LOG_H;
-constexpr int kTexTileW = 1 << kTexLogW, kTexTileH = 1 << kTexLogH, kTexTile = kTexTileW * kTexTileH;
-__host__ __device__ inline int64_t color_plane_texels(int W, int H) {
-  return (int64_t)((W + kTexTileW - 1) / kTexTileW) * ((H + kTexTileH - 1) / kTexTileH) * kTexTile;
-}
-__device__ __forceinline__ int64_t texel_index(int x, int y, int tiles_x) {
-  return ((int64_t)(y >> kTexLogH) * tiles_x + (x >> kTexLogW)) * kTexTile + ((y & (kTexTileH - 1)) << kTexLogW) + (x & (kTexTileW - 1));
-}
+// (the layout itself: mesh_depth_render.h, shared with the rasteriser that fills depth planes)
+using dmi::kTexLogW, dmi::kTexLogH, dmi::kTexTileW, dmi::kTexTileH, dmi::kTexTile, dmi::color_plane_texels, dmi::texel_index;
 
 // [n][H][W] f64 depths in vtk point order -> [n] tiled f64 planes in the colour planes' layout (the same texel index serves
 // both gathers of a pair: dmi_color_add_views_with_depth)
@@ -657,6 +648,21 @@ struct dmi_color_context {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_kernel_ms = 0.0;
   bool reorder = false;  // take the vertices of a chunk along a Z-order curve (dmi_color_set_vertex_reorder)
+  // the rasteriser (dmi_color_render_depths, mesh_depth_render.hip): the planes of the last rendering -- ONE allocation for all
+  // views, which then owns every entry of h_depth_planes --, the cameras as it reads them, its queue of large pairs and the
+  // counters of a call (one per view group, then the id check's flag)
+  double *d_rendered = nullptr;
+  dmi::RenderView *d_render_views = nullptr;
+  size_t render_views_capacity = 0;
+  dmi::RenderPair *d_render_queue = nullptr;
+  size_t render_queue_allocated = 0;          // entries
+  uint32_t render_queue_capacity = 1u << 20;  // entries a call starts with (dmi_color_set_render_queue_capacity)
+  uint32_t *d_render_counters = nullptr;
+  size_t render_counters_capacity = 0;
+  double last_render_ms = 0.0;
+  double last_render_pass_ms[3] = {0.0, 0.0, 0.0};  // the fill, the small passes, the large passes (dmi_color_get_render_pass_ms)
+  uint64_t last_render_queued = 0;                  // (triangle, view) pairs the large passes took
+  std::vector<hipEvent_t> render_events;            // two around the fill, three per view group (before, between, after)
   size_t scratch_budget = size_t(1) << 30;  // bytes of [view][vertex] scratch per chunk (dmi_color_set_scratch_budget)
   std::string err;
 };
@@ -747,6 +753,9 @@ void dmi_color_destroy(dmi_color_context *c) {
   for (hipStream_t st : {c->h2d, c->stream, c->d2h})
     if (st) (void)hipStreamSynchronize(st);
   for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba), (void)hipFree(b.d_depth);
+  for (void *p : {(void *)c->d_rendered, (void *)c->d_render_views, (void *)c->d_render_queue, (void *)c->d_render_counters})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t ev : c->render_events) (void)hipEventDestroy(ev);
   for (void *p : {(void *)c->d_views, (void *)c->d_depth_planes, (void *)c->d_fused_tables, (void *)c->d_sample, (void *)c->d_points[0], (void *)c->d_points[1], (void *)c->d_scratch, (void *)c->d_mean[0], (void *)c->d_mean[1],
                   (void *)c->d_median[0], (void *)c->d_median[1], (void *)c->d_count[0], (void *)c->d_count[1], (void *)c->d_seeds, (void *)c->d_margins[0],
                   (void *)c->d_margins[1], (void *)c->d_pmax[0], (void *)c->d_pmax[1], (void *)c->d_stage, (void *)c->d_keys, (void *)c->d_keys_sorted,
@@ -838,6 +847,8 @@ int dmi_color_clear_views(dmi_color_context *c) {
   DMI_COLOR_HIP(c, hipSetDevice(c->device));
   DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
   for (ColorBatch &b : c->batches) (void)hipFree(b.d_rgba), (void)hipFree(b.d_depth);
+  if (c->d_rendered) (void)hipFree(c->d_rendered);  // (the rendered planes go with the views they were rendered for)
+  c->d_rendered = nullptr;
   c->batches.clear();
   c->h_views.clear();
   c->h_depth_planes.clear();
@@ -1299,6 +1310,265 @@ int dmi_color_mesh(const double *points, int64_t n_points, const uint8_t *colors
   if (rc == DMI_OK) rc = dmi_color_process(c, points, n_points, mean, median, count);
   dmi_color_destroy(c);  // g_color_error keeps the message
   return rc;
+  });
+}
+
+}  // extern "C"
+
+// ---- rendered depth planes (mesh_depth_render.hip; DESIGN.md 8b'') -------------------------------------------------------------
+namespace {
+// A mesh that is on the device, rendered into NEW planes for every resident view; they replace the old ones (uploaded or rendered)
+// only when everything has succeeded.  `after`: an event of the mesh's owner that the context's stream waits for first.
+int render_device_mesh(dmi_color_context *c, const std::string &entry, const dmi::RenderMesh &mesh, hipEvent_t after) {
+  const size_t n_views = c->h_views.size();
+  if (n_views == 0) return cfail(c, DMI_ERR_STATE, entry + ": no views resident");
+  DMI_COLOR_HIP(c, hipSetDevice(c->device));
+  const size_t plane = (size_t)color_plane_texels(c->W, c->H);
+  const size_t n_groups = (n_views + dmi::kRenderViewGroup - 1) / dmi::kRenderViewGroup;
+  if (c->render_views_capacity < n_views) {
+    DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_render_views) (void)hipFree(c->d_render_views);
+    c->d_render_views = nullptr;
+    c->render_views_capacity = 0;
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_render_views, n_views * sizeof(dmi::RenderView)));
+    c->render_views_capacity = n_views;
+  }
+  if (c->render_counters_capacity < n_groups + 1) {
+    DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_render_counters) (void)hipFree(c->d_render_counters);
+    c->d_render_counters = nullptr;
+    c->render_counters_capacity = 0;
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_render_counters, (n_groups + 1) * sizeof(uint32_t)));
+    c->render_counters_capacity = n_groups + 1;
+  }
+  auto ensure_queue = [&](size_t entries) -> hipError_t {
+    if (c->render_queue_allocated >= entries) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (c->d_render_queue) (void)hipFree(c->d_render_queue);
+    c->d_render_queue = nullptr;
+    c->render_queue_allocated = 0;
+    if (e == hipSuccess) e = hipMalloc(&c->d_render_queue, entries * sizeof(dmi::RenderPair));
+    if (e == hipSuccess) c->render_queue_allocated = entries;
+    return e;
+  };
+  uint32_t capacity = c->render_queue_capacity;
+  DMI_COLOR_HIP(c, ensure_queue(capacity));
+  while (c->render_events.size() < 2 + 3 * n_groups) {
+    hipEvent_t ev = nullptr;
+    DMI_COLOR_HIP(c, hipEventCreate(&ev));
+    c->render_events.push_back(ev);
+  }
+  hipEvent_t *const pass_events = c->render_events.data();
+  std::vector<dmi::RenderView> cameras(n_views);
+  for (size_t m = 0; m < n_views; ++m) {
+    for (int i = 0; i < 12; ++i) cameras[m].rt[i] = c->h_views[m].rt[i];
+    for (int i = 0; i < 9; ++i) cameras[m].k[i] = c->h_views[m].k[i];
+  }
+  double *planes = nullptr;
+  DMI_COLOR_HIP(c, hipMalloc(&planes, plane * n_views * sizeof(double)));
+  // from here on a failure frees the new planes and leaves the context's as they were
+  auto bail = [&](int code, const std::string &msg) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(planes);
+    return cfail(c, code, entry + ": " + msg);
+  };
+#define DMI_RENDER_TRY(call)                                                                                             \
+  do {                                                                                                                   \
+    const hipError_t he_ = (call);                                                                                       \
+    if (he_ != hipSuccess)                                                                                               \
+      return bail(he_ == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(he_)); \
+  } while (0)
+  if (after) DMI_RENDER_TRY(hipStreamWaitEvent(c->stream, after, 0));
+  DMI_RENDER_TRY(hipMemcpyAsync(c->d_render_views, cameras.data(), n_views * sizeof(dmi::RenderView), hipMemcpyHostToDevice, c->stream));
+  // the ids, on the device, before anything is rendered
+  uint32_t *flag = c->d_render_counters + n_groups;
+  uint32_t h_flag = 0;
+  DMI_RENDER_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+  DMI_RENDER_TRY(dmi::launch_render_check_ids(mesh, flag, c->stream));
+  DMI_RENDER_TRY(hipMemcpyAsync(&h_flag, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  DMI_RENDER_TRY(hipStreamSynchronize(c->stream));
+  if (h_flag) return bail(DMI_ERR_INVALID_ARGUMENT, "a triangle names a point outside [0, " + std::to_string(mesh.n_points) + ")");
+  std::vector<uint32_t> wanted(n_groups, 0);
+  double total_ms = 0.0, pass_ms[3] = {0.0, 0.0, 0.0};
+  auto add_span = [&](double &sum, hipEvent_t from, hipEvent_t to) -> hipError_t {
+    float span = 0.f;
+    const hipError_t e = hipEventElapsedTime(&span, from, to);
+    if (e == hipSuccess) sum += (double)span;
+    return e;
+  };
+  bool first_round = true;
+  std::vector<size_t> todo(n_groups);
+  for (size_t g = 0; g < n_groups; ++g) todo[g] = g;
+  while (!todo.empty()) {
+    DMI_RENDER_TRY(hipEventRecord(c->ev0, c->stream));
+    if (first_round) {
+      DMI_RENDER_TRY(hipEventRecord(pass_events[0], c->stream));
+      DMI_RENDER_TRY(dmi::launch_render_init(planes, (int64_t)(plane * n_views), c->stream));
+      DMI_RENDER_TRY(hipEventRecord(pass_events[1], c->stream));
+    }
+    for (size_t g : todo) {
+      const int m0 = (int)(g * dmi::kRenderViewGroup), gn = (int)std::min<size_t>(dmi::kRenderViewGroup, n_views - (size_t)m0);
+      DMI_RENDER_TRY(hipEventRecord(pass_events[2 + 3 * g], c->stream));
+      DMI_RENDER_TRY(dmi::launch_render_group(mesh, c->d_render_views, m0, gn, c->W, c->H, planes, c->d_render_queue, capacity,
+                                              c->d_render_counters + g, pass_events[3 + 3 * g], c->stream));
+      DMI_RENDER_TRY(hipEventRecord(pass_events[4 + 3 * g], c->stream));
+    }
+    DMI_RENDER_TRY(hipEventRecord(c->ev1, c->stream));
+    DMI_RENDER_TRY(hipMemcpyAsync(wanted.data(), c->d_render_counters, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    DMI_RENDER_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    DMI_RENDER_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    total_ms += (double)ms;
+    if (first_round) DMI_RENDER_TRY(add_span(pass_ms[0], pass_events[0], pass_events[1]));
+    for (size_t g : todo) {  // (a group that runs again counts again: that is what the call spent)
+      DMI_RENDER_TRY(add_span(pass_ms[1], pass_events[2 + 3 * g], pass_events[3 + 3 * g]));
+      DMI_RENDER_TRY(add_span(pass_ms[2], pass_events[3 + 3 * g], pass_events[4 + 3 * g]));
+    }
+    first_round = false;
+    // a group that wanted more entries than the queue had lost pairs: the queue grows to what was counted and the group runs
+    // again (a minimum over a superset of what is already in the planes: the same bits as one complete run)
+    uint32_t most = 0;
+    std::vector<size_t> again;
+    for (size_t g : todo)
+      if (wanted[g] > capacity) again.push_back(g), most = std::max(most, wanted[g]);
+    todo.swap(again);
+    if (!todo.empty()) {
+      DMI_RENDER_TRY(ensure_queue(most));
+      capacity = most;
+    }
+  }
+#undef DMI_RENDER_TRY
+  // the new planes become the context's: every view has one, the batches' uploaded planes and the last rendering's go
+  for (ColorBatch &b : c->batches) {
+    if (b.d_depth) (void)hipFree(b.d_depth);
+    b.d_depth = nullptr;
+  }
+  if (c->d_rendered) (void)hipFree(c->d_rendered);
+  c->d_rendered = planes;
+  for (size_t m = 0; m < n_views; ++m) c->h_depth_planes[m] = planes + m * plane;
+  c->views_dirty = true;
+  c->last_render_ms = total_ms;
+  for (int q = 0; q < 3; ++q) c->last_render_pass_ms[q] = pass_ms[q];
+  c->last_render_queued = 0;
+  for (uint32_t w : wanted) c->last_render_queued += w;  // (every group's last run had room for all it wanted)
+  return DMI_OK;
+}
+}  // namespace
+
+int dmi::color_render_device_mesh(dmi_color_context *c, const double *points, int64_t n_points, const int64_t *triangles, int64_t n_triangles,
+                                  hipEvent_t after) {
+  return ::guarded(c, "dmi_color_render_isosurface_depths", [&]() -> int {
+    return render_device_mesh(c, "dmi_color_render_isosurface_depths", dmi::RenderMesh{points, triangles, n_points, n_triangles}, after);
+  });
+}
+
+extern "C" {
+
+int dmi_color_render_depths(dmi_color_context *c, const double *points, int64_t n_points, const int64_t *triangles, int64_t n_triangles) {
+  return guarded(c, "dmi_color_render_depths", [&]() -> int {
+  const std::string entry = "dmi_color_render_depths";
+  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + ": null context");
+  if (n_points < 0 || n_triangles < 0 || (n_points > 0 && !points) || (n_triangles > 0 && !triangles))
+    return cfail(c, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument or negative count");
+  if (c->h_views.empty()) return cfail(c, DMI_ERR_STATE, entry + ": no views resident");
+  DMI_COLOR_HIP(c, hipSetDevice(c->device));
+  double *d_points = nullptr;
+  int64_t *d_triangles = nullptr;
+  auto release = [&]() {
+    (void)hipStreamSynchronize(c->stream);
+    if (d_points) (void)hipFree(d_points);
+    if (d_triangles) (void)hipFree(d_triangles);
+  };
+  // the whole mesh has to be resident (a triangle may name any point); it goes up in pieces of at most 64 MiB
+  auto upload = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
+    const size_t piece = size_t(64) << 20;
+    for (size_t off = 0; off < bytes; off += piece) {
+      const hipError_t e = hipMemcpyAsync(static_cast<char *>(dst) + off, static_cast<const char *>(src) + off, std::min(piece, bytes - off),
+                                          hipMemcpyHostToDevice, c->stream);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
+  hipError_t e = hipMalloc(&d_points, std::max<size_t>((size_t)n_points * 24, 8));
+  if (e == hipSuccess) e = hipMalloc(&d_triangles, std::max<size_t>((size_t)n_triangles * 24, 8));
+  if (e == hipSuccess) e = upload(d_points, points, (size_t)n_points * 24);
+  if (e == hipSuccess) e = upload(d_triangles, triangles, (size_t)n_triangles * 24);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    release();
+    return cfail(c, e == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE, entry + ": mesh upload: " + hipGetErrorString(e));
+  }
+  const int rc = render_device_mesh(c, entry, dmi::RenderMesh{d_points, d_triangles, n_points, n_triangles}, nullptr);
+  release();
+  return rc;
+  });
+}
+
+int dmi_color_download_depths(dmi_color_context *c, int32_t first, int32_t count, double *out) {
+  return guarded(c, "dmi_color_download_depths", [&]() -> int {
+  const std::string entry = "dmi_color_download_depths";
+  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + ": null context");
+  if (first < 0 || count < 0 || (size_t)first + (size_t)count > c->h_views.size() || (count > 0 && !out))
+    return cfail(c, DMI_ERR_INVALID_ARGUMENT, entry + ": views [" + std::to_string(first) + ", " + std::to_string((int64_t)first + count) + ") of " +
+                                                  std::to_string(c->h_views.size()) + " resident, or a null argument");
+  for (int32_t m = first; m < first + count; ++m)
+    if (!c->h_depth_planes[(size_t)m])
+      return cfail(c, DMI_ERR_INVALID_ARGUMENT, entry + ": view " + std::to_string(m) + " has no depth plane (dmi_color_add_views_with_depth, dmi_color_render_depths)");
+  if (count == 0) return DMI_OK;
+  DMI_COLOR_HIP(c, hipSetDevice(c->device));
+  const size_t npix = (size_t)c->W * c->H;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(256) << 20) / (npix * sizeof(double))), (size_t)count);
+  if (c->stage_capacity < chunk * npix * sizeof(double)) {
+    DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->d_stage) (void)hipFree(c->d_stage);
+    c->d_stage = nullptr;
+    c->stage_capacity = 0;
+    DMI_COLOR_HIP(c, hipMalloc(&c->d_stage, chunk * npix * sizeof(double)));
+    c->stage_capacity = chunk * npix * sizeof(double);
+  }
+  double *stage = reinterpret_cast<double *>(c->d_stage);
+  for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+    const size_t cnt = std::min(chunk, (size_t)count - m0);
+    for (size_t q = 0; q < cnt; ++q)
+      DMI_COLOR_HIP(c, dmi::launch_unpack_depth(c->h_depth_planes[(size_t)first + m0 + q], stage + q * npix, c->W, c->H, c->stream));
+    DMI_COLOR_HIP(c, hipMemcpyAsync(out + m0 * npix, stage, cnt * npix * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    DMI_COLOR_HIP(c, hipStreamSynchronize(c->stream));  // the stage buffer is reused by the next chunk
+  }
+  return DMI_OK;
+  });
+}
+
+int dmi_color_set_render_queue_capacity(dmi_color_context *c, uint64_t entries) {
+  return guarded(c, "dmi_color_set_render_queue_capacity", [&]() -> int {
+  if (!c) return cfail(nullptr, DMI_ERR_INVALID_ARGUMENT, "dmi_color_set_render_queue_capacity: null context");
+  if (entries < 1 || entries > 0x7fffffffull) return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_set_render_queue_capacity: 1 to 2^31 - 1 entries");
+  c->render_queue_capacity = (uint32_t)entries;
+  return DMI_OK;
+  });
+}
+
+int dmi_color_get_render_pass_ms(dmi_color_context *c, double out[3]) {
+  return guarded(c, "dmi_color_get_render_pass_ms", [&]() -> int {
+  if (!c || !out) return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_get_render_pass_ms: null argument");
+  for (int q = 0; q < 3; ++q) out[q] = c->last_render_pass_ms[q];
+  return DMI_OK;
+  });
+}
+
+int dmi_color_get_render_queued_pairs(dmi_color_context *c, uint64_t *out) {
+  return guarded(c, "dmi_color_get_render_queued_pairs", [&]() -> int {
+  if (!c || !out) return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_get_render_queued_pairs: null argument");
+  *out = c->last_render_queued;
+  return DMI_OK;
+  });
+}
+
+int dmi_color_get_render_kernel_ms(dmi_color_context *c, double *last) {
+  return guarded(c, "dmi_color_get_render_kernel_ms", [&]() -> int {
+  if (!c || !last) return cfail(c, DMI_ERR_INVALID_ARGUMENT, "dmi_color_get_render_kernel_ms: null argument");
+  *last = c->last_render_ms;
+  return DMI_OK;
   });
 }
 

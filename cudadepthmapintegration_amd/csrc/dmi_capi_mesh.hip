@@ -750,6 +750,30 @@ int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t
   });
 }
 
+int dmi_color_render_isosurface_depths(dmi_color_context *c, dmi_context *ctx) {
+  return guarded(ctx, "dmi_color_render_isosurface_depths", [&]() -> int {
+  const std::string entry = "dmi_color_render_isosurface_depths";
+  if (!c || !ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Coloration &col = ctx->coloration;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const dmi::ColorContextShape views = dmi::color_context_shape(c);
+  if (views.device != ctx->opt.device)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the colour context is on device " + std::to_string(views.device) + ", the mesh on device " +
+                                                   std::to_string(ctx->opt.device));
+  if (views.n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident in the colour context");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (!col.events[0])
+    for (hipEvent_t &e : col.events) DMI_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  // whatever is still queued on this context's stream (a decimation's normals) comes first
+  DMI_HIP(ctx, hipEventRecord(col.events[0], ctx->stream));
+  const int rc = dmi::color_render_device_mesh(c, mesh.vertices.as<double>(), (int64_t)mesh.n_vertices, mesh.triangles.as<int64_t>(),
+                                               (int64_t)mesh.n_triangles, col.events[0]);
+  if (rc != DMI_OK) return fail(ctx, rc, dmi_color_last_error());
+  return DMI_OK;
+  });
+}
+
 int dmi_download_isosurface_colors(dmi_context *ctx, uint8_t *mean, uint8_t *median, int32_t *count) {
   return guarded(ctx, "dmi_download_isosurface_colors", [&]() -> int {
   if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_colors: null argument");

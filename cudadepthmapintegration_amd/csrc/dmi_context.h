@@ -279,6 +279,10 @@ struct DeviceColoring {
 };
 // Synchronises once at its end (and once for the order-of-work sample).  A failure's message is dmi_color_last_error()'s.
 int color_device_vertices(dmi_color_context *c, const DeviceColoring &work, double *kernel_ms);
+// The rasteriser of dmi_color_render_depths on a mesh that is on the device already (dmi_color_render_isosurface_depths): points
+// [n][3] f64, triangles [n][3] int64; the colour context's stream waits for `after` first.  Synchronises.
+int color_render_device_mesh(dmi_color_context *c, const double *points, int64_t n_points, const int64_t *triangles, int64_t n_triangles,
+                             hipEvent_t after);
 
 }  // namespace dmi
 

@@ -5,10 +5,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <ostream>
 #include <sstream>
 #include <vector>
 
+#include "fan_triangulate.h"
 #include "recon_host.h"
 
 namespace dmi {
@@ -36,6 +38,12 @@ const Flag kFlags[] = {
      "(optional, not in the reference) turn on the visibility test: a view adds its pixel to a vertex only if the vertex is in "
      "front of the camera and its camera z is within this distance of the view's 'Depths' value there (finite, >= 0). "
      "Without it the three arrays are the reference's"},
+    {"--depthFromMesh", false,
+     "(optional, not in the reference; needs --depthTolerance) the visibility test compares against the input mesh's own depth, "
+     "rendered into every view on the GPU, instead of the views' 'Depths' arrays (which are then not read and need not exist: "
+     "a .vti file with a 'Color' array alone will do): no holes, no noise, "
+     "and a mesh from anywhere can be tested.  Polygons of more than three corners are fan-triangulated from their first corner "
+     "for the rendering only; a triangle that crosses a camera's plane does not occlude (no near-plane clipping)"},
 };
 
 }  // namespace
@@ -61,7 +69,7 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
       return false;
     }
     if (!hit->takes_value) {
-      (flag == "--help" ? help : o->verbose) = true;
+      (flag == "--help" ? help : flag == "--depthFromMesh" ? o->depthFromMesh : o->verbose) = true;
       continue;
     }
     if (i + 1 >= argc) {
@@ -102,6 +110,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   }
   if (o->input.empty() || o->output.empty() || o->krtd.empty() || o->vti.empty()) {  // cmain:126-132
     err << "Missing arguments..." << std::endl << HelpText();
+    return false;
+  }
+  if (o->depthFromMesh && !o->depthTest) {
+    err << "Error : --depthFromMesh needs --depthTolerance (the rendered depth is what the visibility test compares against)\n" << HelpText();
     return false;
   }
   return true;
@@ -204,7 +216,20 @@ int Run(const Options &o, std::ostream &log, std::string *error) {
       points[i] = (double)f;
     }
   }
-  MeshColoration coloration(points.data(), (int64_t)np, o.vti, o.krtd);  // cmain:79
+  // --depthFromMesh: the polys as triangles, for the rendering only (the written polys are the input's); the views' files are then
+  // read for their Color arrays alone and need no Depths
+  std::vector<int64_t> triangles;
+  if (o.depthFromMesh) {
+    std::vector<int64_t> connectivity((size_t)(mesh.n_polys ? mesh.OffsetAt(mesh.n_polys - 1) : 0)), offsets((size_t)mesh.n_polys);
+    for (size_t i = 0; i < connectivity.size(); ++i) connectivity[i] = mesh.ConnectivityAt((int64_t)i);
+    for (size_t i = 0; i < offsets.size(); ++i) offsets[i] = mesh.OffsetAt((int64_t)i);
+    triangles = FanTriangulate(connectivity.data(), (int64_t)connectivity.size(), offsets.data(), mesh.n_polys);
+    say("** Depth of the visibility test: the input mesh, rendered (" + std::to_string(triangles.size() / 3) + " triangles)");
+  }
+  std::unique_ptr<MeshColoration> owner(o.depthFromMesh
+                                            ? new MeshColoration(points.data(), (int64_t)np, triangles.data(), (int64_t)triangles.size() / 3, o.vti, o.krtd)
+                                            : new MeshColoration(points.data(), (int64_t)np, o.vti, o.krtd));  // cmain:79
+  MeshColoration &coloration = *owner;
   coloration.SetDevice(o.device);
   if (o.depthTest) coloration.SetDepthTolerance(o.depthTolerance);
   if (!coloration.ProcessColoration()) {  // cmain:80, 96-99

@@ -1,8 +1,9 @@
 // color_cli.h -- the command line of the reference's `Coloration` tool (Coloration/main.cxx, "cmain") on top of the host
 // mirror: the same flags and checks (cmain:105-135), the mesh read from a .vtp (vtkXMLPolyDataReader, cmain:75-77: here
 // vtp_reader.h), MeshColoration over the two list files (cmain:79-80), and the mesh written back with its three new point
-// arrays (vtkXMLPolyDataWriter, cmain:85-88).  Not in the reference: --device, and --depthTolerance, which turns on the
-// visibility test of dmi_color_set_depth_test.  One deliberate deviation: when the colouring fails the reference still returns
+// arrays (vtkXMLPolyDataWriter, cmain:85-88).  Not in the reference: --device, --depthTolerance, which turns on the
+// visibility test of dmi_color_set_depth_test, and --depthFromMesh, which gives that test the input mesh's own rendered depth
+// (dmi_color_render_depths) instead of the views' "Depths" arrays.  One deliberate deviation: when the colouring fails the reference still returns
 // EXIT_SUCCESS, writes nothing and says so only under --verbose (cmain:82-99); this tool returns 1 and prints the error.
 #pragma once
 
@@ -25,6 +26,7 @@ struct Options {
   int device = 0;                // --device (not in the reference)
   bool depthTest = false;        // --depthTolerance given (not in the reference)
   double depthTolerance = 0.0;
+  bool depthFromMesh = false;    // --depthFromMesh: the test's depth is the input mesh's own, rendered (not in the reference)
 };
 
 // cmain:105-135.  false: do not run (an error or --help; the text went to `err`).

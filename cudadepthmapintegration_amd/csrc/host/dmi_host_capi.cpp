@@ -218,6 +218,29 @@ int dmi_mesh_coloration_from_lists_with_depth(const double *points, int64_t n_po
   });
 }
 
+int dmi_mesh_coloration_from_lists_with_mesh_depth(const double *points, int64_t n_points, const int64_t *triangles, int64_t n_triangles,
+                                                   const char *vti_list, const char *krtd_list, int32_t device, double depth_tolerance,
+                                                   uint8_t *mean, uint8_t *median, int32_t *count, double *render_kernel_ms, char *err,
+                                                   size_t errlen) {
+  return guarded<int>(0, [&]() -> int {
+    auto fail = [&](const std::string &m) {
+      copy_text(m, err, errlen);
+      return 0;
+    };
+    if (!points || !vti_list || !krtd_list || !mean || !median || !count || n_points < 0 || n_triangles < 0 || (n_triangles > 0 && !triangles))
+      return fail("null argument");
+    dmi::host::MeshColoration mc(points, n_points, triangles, n_triangles, vti_list, krtd_list);
+    mc.SetDevice(device);
+    mc.SetDepthTolerance(depth_tolerance);
+    if (!mc.ProcessColoration()) return fail(mc.LastError());
+    std::memcpy(mean, mc.GetMeanColoration().data(), (size_t)n_points * 3);
+    std::memcpy(median, mc.GetMedianColoration().data(), (size_t)n_points * 3);
+    for (int64_t i = 0; i < n_points; ++i) count[i] = mc.GetNbProjectedDepthMap()[(size_t)i];
+    if (render_kernel_ms) *render_kernel_ms = mc.GetRenderKernelMs();
+    return 1;
+  });
+}
+
 struct dmi_polydata {
   dmi::host::vtp::PolyData mesh;
   std::string designations[2];
@@ -295,6 +318,7 @@ int dmi_color_cli_read_arguments(int32_t argc, const char *const *argv, dmi_colo
   out->device = o.device;
   out->depth_test = o.depthTest;
   out->depth_tolerance = o.depthTolerance;
+  out->depth_from_mesh = o.depthFromMesh ? 1 : 0;
   return 1;
   });
 }
@@ -351,6 +375,7 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_coloration = o.meshColoration ? 1 : 0;
   out->mesh_coloration_fused = o.meshColorationDepthToleranceGiven ? 1 : 0;
   out->mesh_coloration_depth_tolerance = o.meshColorationDepthTolerance;
+  out->mesh_coloration_depth_from_mesh = o.meshColorationDepthFromMesh ? 1 : 0;
   return 1;
   });
 }

@@ -173,6 +173,12 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                         "(not in the reference)",
                                           into_checked_double(&o->meshColorationDepthTolerance, &o->meshColorationDepthToleranceGiven,
                                                               [](double x) { return x >= 0.0; })}},
+      {"--meshColorationDepthFromMesh", {Kind::kFlag, "with --meshColoration and --meshColorationDepthTolerance: the depth that "
+                                                     "tolerance is measured against is the final mesh's own -- rendered into every "
+                                                     "view on the GPU after the last mesh operation -- instead of the depth the "
+                                                     "fusion kept: no holes, and still the surface after smoothing or decimation. "
+                                                     "A triangle that crosses a camera's plane does not occlude (not in the reference)",
+                                         into_flag(&o->meshColorationDepthFromMesh)}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -263,6 +269,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   }
   if (o->meshColorationDepthToleranceGiven && !o->meshColoration) {
     err << "Error : --meshColorationDepthTolerance needs --meshColoration.\n" << HelpText();
+    return false;
+  }
+  if (o->meshColorationDepthFromMesh && !(o->meshColoration && o->meshColorationDepthToleranceGiven)) {
+    err << "Error : --meshColorationDepthFromMesh needs --meshColoration and --meshColorationDepthTolerance.\n" << HelpText();
     return false;
   }
   if (o->meshColoration && o->devices.size() > 1) {
@@ -687,7 +697,16 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       }
       if (rc == DMI_OK && o.meshColoration) {  // last of all: the mesh as it will be written, where it is
         uint64_t colored = 0;
-        rc = dmi_color_process_isosurface(coloring.c, ctx, o.meshColorationDepthToleranceGiven ? 1 : 0, o.meshColorationDepthTolerance, &colored);
+        if (o.meshColorationDepthFromMesh) {
+          // the mesh's own z-buffer in the colour context's planes, then the colour context's own test against them
+          rc = dmi_color_render_isosurface_depths(coloring.c, ctx);
+          // (neither of the next two can fail on a context that has just rendered and a tolerance the parser has checked)
+          if (rc == DMI_OK) rc = dmi_color_get_render_kernel_ms(coloring.c, &result->meshColorationRenderKernelMs);
+          if (rc == DMI_OK) rc = dmi_color_set_depth_test(coloring.c, 1, o.meshColorationDepthTolerance);
+          if (rc == DMI_OK) rc = dmi_color_process_isosurface(coloring.c, ctx, 0, 0.0, &colored);
+        } else {
+          rc = dmi_color_process_isosurface(coloring.c, ctx, o.meshColorationDepthToleranceGiven ? 1 : 0, o.meshColorationDepthTolerance, &colored);
+        }
         if (rc == DMI_OK) rc = dmi_get_isosurface_color_kernel_ms(ctx, &result->meshColorationKernelMs);
         if (rc == DMI_OK) {
           meshMean.resize((size_t)nv * 3);
@@ -753,6 +772,7 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (o.meshColoration) {
       log << "mesh coloration: " << result->meshVertices << " vertices, " << result->meshColorationViews << " views, depth tolerance ";
       if (o.meshColorationDepthToleranceGiven) log << o.meshColorationDepthTolerance; else log << "none";
+      if (o.meshColorationDepthFromMesh) log << " against the mesh's own rendered depth (" << result->meshColorationRenderKernelMs << " ms of GPU kernels to render)";
       log << "; " << result->meshColorationKernelMs << " ms of GPU kernels" << std::endl;
     }
   } else {
@@ -792,6 +812,7 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (o.meshColoration) {  // (only with --extractMesh)
       out << "  mesh coloration  " << result->meshVertices << " vertices, " << result->meshColorationViews << " views, depth tolerance ";
       if (o.meshColorationDepthToleranceGiven) out << o.meshColorationDepthTolerance; else out << "none";
+      if (o.meshColorationDepthFromMesh) out << " against the mesh's own rendered depth (" << result->meshColorationRenderKernelMs << " ms of GPU kernels to render)";
       out << ", " << result->meshColorationKernelMs << " ms of GPU kernels\n";
     }
     if (!o.extractMesh)

@@ -62,6 +62,7 @@ struct Options {
   bool meshColoration = false;
   double meshColorationDepthTolerance = 0.0;
   bool meshColorationDepthToleranceGiven = false;
+  bool meshColorationDepthFromMesh = false;  // the tolerance is measured against the final mesh's own rendered depth
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -90,6 +91,7 @@ struct RunResult {
   // --meshColoration: the views that coloured the mesh and the hipEvent time of the colouring's kernels
   unsigned long long meshColorationViews = 0;
   double meshColorationKernelMs = 0.0;
+  double meshColorationRenderKernelMs = 0.0;  // --meshColorationDepthFromMesh: the rendering's kernels
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.

@@ -165,8 +165,11 @@ ReconstructionData::ReconstructionData() {
 }
 
 ReconstructionData::ReconstructionData(const std::string &depthPath, const std::string &matrixPath)
+    : ReconstructionData(depthPath, matrixPath, false) {}
+
+ReconstructionData::ReconstructionData(const std::string &depthPath, const std::string &matrixPath, bool depthsOptional)
     : ReconstructionData() {
-  HasDepthMap = ReadDepthMap(depthPath, &DepthMap);  // RD.cxx:60-61
+  HasDepthMap = ReadDepthMap(depthPath, &DepthMap, depthsOptional);  // RD.cxx:60-61
   double K[9], RT[16];
   std::memset(K, 0, sizeof(K));
   std::memset(RT, 0, sizeof(RT));
@@ -232,7 +235,9 @@ void ReconstructionData::ApplyDepthThresholdFilter(double thresholdBestCost) {
     if (DepthMap.best_cost[i] > thresholdBestCost) DepthMap.depths[i] = -1;  // RD.cxx:159-166
 }
 
-bool ReconstructionData::ReadDepthMap(const std::string &path, DepthImage *out) {
+bool ReconstructionData::ReadDepthMap(const std::string &path, DepthImage *out) { return ReadDepthMap(path, out, false); }
+
+bool ReconstructionData::ReadDepthMap(const std::string &path, DepthImage *out, bool depthsOptional) {
   // RD.cxx:223-229 (vtkXMLImageDataReader) through the VTK-free reader; the arrays are then taken by name and
   // type exactly as the reference does: "Depths" and "Best Cost Values" must be vtkDoubleArrays (SafeDownCast,
   // RD.cxx:143-146, cu:249-250), "Color" a vtkUnsignedCharArray with 3 components (RD.cxx:94-95).
@@ -265,7 +270,7 @@ bool ReconstructionData::ReadDepthMap(const std::string &path, DepthImage *out) 
     dst->resize(n);
     std::memcpy(dst->data(), a.bytes.data(), n * sizeof(double));
   }
-  return !out->depths.empty();
+  return depthsOptional || !out->depths.empty();
 }
 
 // ====================================================================================================
@@ -803,6 +808,17 @@ MeshColoration::MeshColoration() {}
 
 MeshColoration::MeshColoration(const double *meshPoints, int64_t nbMeshPoint, const std::string &vti, const std::string &krtd) {
   SetInput(meshPoints, nbMeshPoint);
+  ReadViews(vti, krtd, false);
+}
+
+MeshColoration::MeshColoration(const double *meshPoints, int64_t nbMeshPoint, const int64_t *triangles, int64_t nbTriangles, const std::string &vti,
+                               const std::string &krtd) {
+  SetInput(meshPoints, nbMeshPoint);
+  SetDepthFromMesh(triangles, nbTriangles);
+  ReadViews(vti, krtd, true);
+}
+
+void MeshColoration::ReadViews(const std::string &vti, const std::string &krtd, bool depthsOptional) {
   const std::vector<std::string> vtiList = help::ExtractAllFilePath(vti.c_str());
   const std::vector<std::string> krtdList = help::ExtractAllFilePath(krtd.c_str());
   if (krtdList.size() < vtiList.size()) {  // MC.cxx:59-63
@@ -810,7 +826,7 @@ MeshColoration::MeshColoration(const double *meshPoints, int64_t nbMeshPoint, co
     return;
   }
   for (size_t id = 0; id < vtiList.size(); id++) {  // MC.cxx:67-71
-    ReconstructionData *data = new ReconstructionData(vtiList[id], krtdList[id]);
+    ReconstructionData *data = new ReconstructionData(vtiList[id], krtdList[id], depthsOptional);
     Owned.push_back(data);
     DataList.push_back(data);
   }
@@ -848,7 +864,8 @@ bool MeshColoration::ProcessColoration() {
     return false;
   }
   std::vector<unsigned char> colors(npix * 3 * (size_t)nbDepthMap);
-  std::vector<double> depths(DepthTest ? npix * (size_t)nbDepthMap : 0);
+  const bool uploadDepths = DepthTest && !DepthFromMesh;  // (a rendered depth replaces the "Depths" arrays: they are not read)
+  std::vector<double> depths(uploadDepths ? npix * (size_t)nbDepthMap : 0);
   std::vector<double> K4(16 * (size_t)nbDepthMap), RT(16 * (size_t)nbDepthMap);
   for (int m = 0; m < nbDepthMap; ++m) {
     DepthImage *img = DataList[m]->GetDepthMap();
@@ -857,7 +874,7 @@ bool MeshColoration::ProcessColoration() {
       std::cerr << Error << std::endl;
       return false;
     }
-    if (DepthTest) {
+    if (uploadDepths) {
       if (img->depths.size() != npix) {  // (ReadDepthMap already requires a Float64 "Depths" array, RD.cxx:143-146)
         Error = "MeshColoration: view " + std::to_string(m) + " has no 'Depths' array of the size of view 0 (the depth test needs it)";
         std::cerr << Error << std::endl;
@@ -881,7 +898,12 @@ bool MeshColoration::ProcessColoration() {
   } else {
     dmi_color_context *ctx = nullptr;
     rc = dmi_color_create(Device, &ctx);
-    if (rc == DMI_OK) rc = dmi_color_add_views_with_depth(ctx, colors.data(), depths.data(), K4.data(), RT.data(), nbDepthMap, W, H);
+    if (rc == DMI_OK && uploadDepths) rc = dmi_color_add_views_with_depth(ctx, colors.data(), depths.data(), K4.data(), RT.data(), nbDepthMap, W, H);
+    if (rc == DMI_OK && !uploadDepths) {
+      rc = dmi_color_add_views(ctx, colors.data(), K4.data(), RT.data(), nbDepthMap, W, H);
+      if (rc == DMI_OK) rc = dmi_color_render_depths(ctx, Points.data(), nv, Triangles.data(), (int64_t)Triangles.size() / 3);
+      if (rc == DMI_OK) rc = dmi_color_get_render_kernel_ms(ctx, &RenderKernelMs);
+    }
     if (rc == DMI_OK) rc = dmi_color_set_depth_test(ctx, 1, DepthTolerance);
     if (rc == DMI_OK) rc = dmi_color_process(ctx, Points.data(), nv, Mean.data(), Median.data(), count.data());
     if (ctx) dmi_color_destroy(ctx);  // (the message stays in dmi_color_last_error)

@@ -49,6 +49,9 @@ class ReconstructionData {
   ReconstructionData();
   // RD.cxx:55-78.  matrixPath is a .krtd file; depthPath a .vti file (see ReadDepthMap for what is read).
   ReconstructionData(const std::string &depthPath, const std::string &matrixPath);
+  // Not in the reference: the same for a colouring that renders its own depth (MeshColoration::SetDepthFromMesh): a file without a
+  // "Depths" array is then an image too (its "Color" array is what is wanted).
+  ReconstructionData(const std::string &depthPath, const std::string &matrixPath, bool depthsOptional);
 
   int *GetDepthMapDimensions();  // {W, H, 1}
   DepthImage *GetDepthMap();     // RD.cxx:118-121
@@ -73,6 +76,8 @@ class ReconstructionData {
   // <ImageData WholeExtent=...> with point-data arrays "Depths" / "Best Cost Values" of type Float64 in
   // format="ascii" (other encodings need VTK: returns false).  See INTEGRATION.md.
   static bool ReadDepthMap(const std::string &path, DepthImage *out);
+  // depthsOptional: a file without "Depths" is read all the same (out->depths stays empty)
+  static bool ReadDepthMap(const std::string &path, DepthImage *out, bool depthsOptional);
 
  private:
   DepthImage DepthMap;
@@ -272,6 +277,10 @@ class MeshColoration {
   MeshColoration();
   // MC.cxx:52-72: reads every view named by the two list files (needs "Color" arrays in the .vti files)
   MeshColoration(const double *meshPoints, int64_t nbMeshPoint, const std::string &vtiList, const std::string &krtdList);
+  // Not in the reference: the same, with these triangles ([n][3] ids into the points) as SetDepthFromMesh: the views' .vti files
+  // then need no "Depths" array at all (the files are read here, so the reader has to know now)
+  MeshColoration(const double *meshPoints, int64_t nbMeshPoint, const int64_t *triangles, int64_t nbTriangles, const std::string &vtiList,
+                 const std::string &krtdList);
   ~MeshColoration();
   void SetInput(const double *meshPoints, int64_t nbMeshPoint);  // MC.cxx:85-91 (vtkPolyData points, [n][3])
   void AddView(ReconstructionData *data);                        // in-memory alternative to the list files; not owned
@@ -289,10 +298,22 @@ class MeshColoration {
     DepthTolerance = tolerance;
   }
   void ClearDepthTest() { DepthTest = false; }
+  // Not in the reference: with the depth test on, the depth it compares against is THIS mesh's own -- the input points and these
+  // triangles ([n][3] ids into them) rendered into every view (dmi_color_render_depths) -- and the views' "Depths" arrays are not
+  // read.  ClearDepthFromMesh: back to the "Depths" arrays.
+  void SetDepthFromMesh(const int64_t *triangles, int64_t nbTriangles) {
+    DepthFromMesh = true;
+    Triangles.assign(triangles, triangles + 3 * nbTriangles);
+  }
+  void ClearDepthFromMesh() { DepthFromMesh = false; }
+  double GetRenderKernelMs() const { return RenderKernelMs; }  // of the last ProcessColoration that rendered
 
  private:
   bool DepthTest = false;
   double DepthTolerance = 0.0;
+  bool DepthFromMesh = false;
+  std::vector<int64_t> Triangles;
+  double RenderKernelMs = 0.0;
   std::vector<double> Points;
   bool HasInput = false;
   std::vector<ReconstructionData *> DataList;
@@ -301,6 +322,7 @@ class MeshColoration {
   std::vector<int> Count;
   std::string Error;
   int Device = 0;
+  void ReadViews(const std::string &vtiList, const std::string &krtdList, bool depthsOptional);
 };
 
 }  // namespace host

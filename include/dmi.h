@@ -526,6 +526,55 @@ int dmi_download_isosurface_colors(dmi_context *ctx, uint8_t *mean, uint8_t *med
  * between them); zero after an empty mesh */
 int dmi_get_isosurface_color_kernel_ms(dmi_context *ctx, double *last);
 
+/* ---- Rendered depth planes: the mesh's own z-buffer as coloration visibility (DESIGN.md 8b''; added after round 5,
+ * dmi_abi_version() stays 5) ----
+ * The depth planes the visibility test compares against can be RENDERED from the mesh that is being coloured instead of taken from
+ * the depth maps: no holes, no noise, valid after smoothing or decimation, and available for a mesh that has no depth maps at all.
+ * dmi_color_render_depths rasterises a triangle mesh (points [n_points][3] f64, triangles [n_triangles][3] ids, host arrays,
+ * uploaded in pieces) into EVERY view resident in `c` and leaves each view with a tiled f64 depth plane of its own: a view added
+ * without depths gets one, the planes of dmi_color_add_views_with_depth are replaced.  dmi_color_clear_views drops them.  The
+ * consumer is unchanged: render, dmi_color_set_depth_test(c, 1, tol), then dmi_color_process or
+ * dmi_color_process_isosurface(c, ctx, 0, ...).
+ * Definition, met bit for bit (all arithmetic f64, every operation rounded, no FMA).  For view m (W x H, K, [R|T]) and a triangle
+ * with vertices p_0, p_1, p_2:
+ *   - (cx, cy, cz) and (dx, dy, dz) of each vertex as in the colouring (TransformPoint left to right, then the 3x3 K without
+ *     translation); u = dx/dz, v = dy/dz.  The triangle is skipped for this view unless all three vertices have cz > 0, dz > 0
+ *     and finite u, v.  THERE IS NO NEAR-PLANE CLIPPING: a triangle that crosses the camera plane does not occlude.
+ *   - pixel (x, y) has its centre at integer coordinates (the colouring's round(u)); candidates are
+ *     x in [max(0, ceil(min u)), min(W-1, floor(max u))], likewise y.
+ *   - e0 = (u2-u1)*(y-v1) - (v2-v1)*(x-u1), e1 = (u0-u2)*(y-v2) - (v0-v2)*(x-u2), e2 = (u1-u0)*(y-v0) - (v1-v0)*(x-u0); the pixel is
+ *     covered iff all three are >= 0 or all three are <= 0, and s = (e0+e1)+e2 != 0: both windings occlude, edges are inclusive,
+ *     zero-area triangles cover nothing.
+ *   - q = (e0/cz0 + e1/cz1) + e2/cz2, d = s/q, kept iff finite and > 0: the perspective-correct camera z, exact for a K whose last
+ *     row is (0, 0, 1) (all that SetMatrixK produces); for a general K it is an approximation.
+ *   - the plane holds the MINIMUM of d over the covering triangles and +inf where nothing covers (+inf fails the test's
+ *     fabs(cz - d) <= tol).  A minimum does not depend on order: the same bits from run to run, in whatever order the triangles
+ *     come.
+ * COST: the planes are 8 bytes per pixel and view, 1.9 GB at 256 views of 1280 x 720 (twice that while a rendering replaces an
+ * earlier one: the new planes are built beside the old and swapped in last).
+ * Errors: an id outside [0, n_points) -> DMI_ERR_INVALID_ARGUMENT, checked on the device before anything is rendered; no views ->
+ * DMI_ERR_STATE; a call that fails leaves the planes as they were.  n_triangles == 0 is a success that leaves every plane empty.
+ * dmi_color_render_isosurface_depths does the same from the mesh `ctx` holds, where it is (no copy), bit for bit what
+ * dmi_color_render_depths gives on the downloaded mesh; refusals as dmi_color_process_isosurface (no extraction yet, different
+ * devices: DMI_ERR_INVALID_ARGUMENT; no views: DMI_ERR_STATE), reported through dmi_last_error(ctx).
+ * dmi_color_download_depths: the planes of views [first, first + count) as out [count][H][W] f64 in vtk point order -- the layout
+ * dmi_color_add_views_with_depth takes --, -1 where the plane is +inf; DMI_ERR_INVALID_ARGUMENT when a view of the range has no
+ * plane.  dmi_color_get_render_kernel_ms: the hipEvent span of the last rendering's kernels.
+ * dmi_color_set_render_queue_capacity: triangles whose pixel range in a view is large are queued for a pass of their own; a
+ * rendering that needs more entries than the queue starts with (default 1 Mi, at least 1) grows it and renders the views
+ * concerned again.  As with the scratch budget, a smaller value never changes a bit. */
+int dmi_color_render_depths(dmi_color_context *c, const double *points, int64_t n_points, const int64_t *triangles,
+                            int64_t n_triangles);
+int dmi_color_render_isosurface_depths(dmi_color_context *c, dmi_context *ctx);
+int dmi_color_download_depths(dmi_color_context *c, int32_t first, int32_t count, double *out);
+int dmi_color_get_render_kernel_ms(dmi_color_context *c, double *last);
+/* The same rendering pass by pass (hipEvents between the kernels): out[0] the fill with +inf, out[1] the small passes (one lane
+ * per triangle), out[2] the large passes (one wave per queued pair), each summed over the view groups -- a group that ran again
+ * after a queue overflow counts both times.  And how many (triangle, view) pairs the large passes took. */
+int dmi_color_get_render_pass_ms(dmi_color_context *c, double out[3]);
+int dmi_color_get_render_queued_pairs(dmi_color_context *c, uint64_t *out);
+int dmi_color_set_render_queue_capacity(dmi_color_context *c, uint64_t entries);
+
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default
  * stream, cu:302-386); the seam where this plugs in is the pair of driver calls at

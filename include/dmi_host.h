@@ -106,8 +106,10 @@ typedef struct dmi_cli_options {
   double mesh_decimate_cell_size;        /* --meshDecimateCellSize v: vertex clustering after the smoothing, world units; 0: off */
   /* not in the reference, only with --extractMesh (dmi_color_process_isosurface, dmi.h); appended to the struct: */
   int32_t mesh_coloration;               /* --meshColoration: colour the final mesh on the device and write the three arrays */
-  int32_t mesh_coloration_fused;         /* --meshColorationDepthTolerance was given: the fused visibility test */
+  int32_t mesh_coloration_fused;         /* --meshColorationDepthTolerance was given: the visibility test */
   double mesh_coloration_depth_tolerance; /* ... its tolerance (finite, >= 0) */
+  /* (dmi_color_render_isosurface_depths, dmi.h); appended to the struct: */
+  int32_t mesh_coloration_depth_from_mesh; /* --meshColorationDepthFromMesh: that test against the mesh's own rendered depth */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -158,6 +160,14 @@ int dmi_write_polydata_with_colors(const char *path, const double *points, int64
 int dmi_mesh_coloration_from_lists_with_depth(const double *points, int64_t n_points, const char *vti_list, const char *krtd_list,
                                               int32_t device, double depth_tolerance, uint8_t *mean, uint8_t *median, int32_t *count,
                                               char *err, size_t errlen);
+/* The same test against the MESH'S OWN depth: points and triangles ([n_triangles][3] ids into the points) are rendered into every
+ * view (dmi_color_render_depths, dmi.h; MeshColoration::SetDepthFromMesh) and the views' "Depths" arrays are neither read nor
+ * needed -- a .vti file with a "Color" array alone will do.  render_kernel_ms (nullable) receives the rendering's kernel time.
+ * 1 on success, 0 on error (message in err). */
+int dmi_mesh_coloration_from_lists_with_mesh_depth(const double *points, int64_t n_points, const int64_t *triangles, int64_t n_triangles,
+                                                   const char *vti_list, const char *krtd_list, int32_t device, double depth_tolerance,
+                                                   uint8_t *mean, uint8_t *median, int32_t *count, double *render_kernel_ms, char *err,
+                                                   size_t errlen);
 
 /* ---- VTK XML PolyData without VTK (csrc/host/vtp_reader.h): what vtkXMLPolyDataReader gives the Coloration tool ----
  * One piece; Points Float32 / Float64; Polys with Int32 / Int64 connectivity and offsets; every point- and cell-data array as
@@ -176,13 +186,15 @@ int dmi_polydata_array(const dmi_polydata *pd, int32_t kind, int32_t index, cons
 const char *dmi_polydata_designations(const dmi_polydata *pd, int32_t cell);
 
 /* ---- the `Coloration` command line (Coloration/main.cxx; csrc/host/color_cli.h) ----
- * What ReadArguments (cmain:105-135) makes of a command line.  --device and --depthTolerance are not in the reference. */
+ * What ReadArguments (cmain:105-135) makes of a command line.  --device, --depthTolerance and --depthFromMesh are not in the
+ * reference. */
 typedef struct dmi_color_cli_options {
   char input[4096], output[4096], krtd[4096], vti[4096]; /* --input, --output, --krtd, --vti (NUL-terminated, truncated) */
   int32_t verbose;
   int32_t device;             /* --device (default 0) */
   int32_t depth_test;         /* --depthTolerance given: the visibility test of dmi_color_set_depth_test */
   double depth_tolerance;
+  int32_t depth_from_mesh;    /* --depthFromMesh: that test against the input mesh's own rendered depth (appended to the struct) */
 } dmi_color_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_color_cli_read_arguments(int32_t argc, const char *const *argv, dmi_color_cli_options *out, char *err, size_t errlen);

@@ -12,7 +12,9 @@ becomes the smallest size it accepts: the weld) it times dmi_decimate_isosurface
 pass, with the counts before and after and the bytes each pass must move; --decimate-check compares with the numpy restatement
 (tests/isosurface_decimate_np.py).  With --color it times the coloration of the device mesh
 (dmi_color_process_isosurface) against dmi_color_process, the fused depth test against the own-planes test, and both again after a
-decimation (color_record).  --grid N runs the whole tool on an N^3 grid (a quick
+decimation (color_record).  With --render-depths it times the z-buffer rasteriser (dmi_color_render_isosurface_depths) on the
+mesh, pass by pass, with the count of queued pairs, and the colouring with rendered planes next to the colouring with fused depths
+(render_record).  --grid N runs the whole tool on an N^3 grid (a quick
 run; the records in profiles/ are of the default 512).
 
     python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
@@ -249,6 +251,61 @@ def color_record(ctx, a, spacing):
     return rec
 
 
+FP64_VECTOR_TFLOPS = 78.6   # MI355X peak fp64 vector rate (FMA = 2)
+
+
+def render_record(ctx, a, spacing):
+    """The --render-depths record: the mesh of the context's grid at a.iso rendered into the scene's first a.render_views views
+    (dmi_color_render_isosurface_depths), a.repeat times after a warm-up call: the kernels' span, the fill, the small and the large
+    passes, the queued (triangle, view) pairs; then, alternating, the colouring with the rendered planes (the colour context's own
+    test) and with the fused depths, both in place at a tolerance of two voxels.  Floors: the projections on the fp64 vector rate
+    (three vertices of 33 operations and two divisions each, counted at 30 operations a division), the fill at the HBM rate."""
+    n = a.render_views
+    tol = 2.0 * spacing
+    grid = scene.default_grid(a.grid)
+    cells = ctx.download_grid()
+    rec = {"views": n, "tolerance": tol, "kernel_ms": [], "pass_ms": [], "queued_pairs": None, "color_rendered_kernel_ms": [],
+           "color_fused_kernel_ms": [], "queue_capacity": a.render_queue}
+    with capi.FusionContext(grid, scene.default_ray_potential(grid)) as fc, capi.ColorContext() as c:
+        for c0 in range(0, n, 32):
+            v, thr = scene.make_scene_views("speckle", 256, 1280, 720, seed=1000, view_range=(c0, min(n, c0 + 32)), noise_sigma=spacing)
+            fc.add_views(v, threshold=thr)
+            c.add_views(scene.make_colors(v.n, 1280, 720, seed=2000 + c0), v.K4, v.RT4)
+        fc.upload_grid(cells)
+        del cells
+        verts, tris = fc.extract_isosurface(a.iso)
+        rec["vertices"], rec["triangles"] = len(verts), len(tris)
+        if a.render_queue:
+            c.set_render_queue_capacity(a.render_queue)
+        for r in range(a.repeat + 1):                       # the first round warms up: buffers sized, code loaded
+            fc.render_isosurface_depths(c)
+            k, p, q = c.render_kernel_ms(), c.render_pass_ms(), c.render_queued_pairs()
+            c.set_depth_test(True, tol)
+            fc.color_isosurface(c)
+            k_rendered = fc.isosurface_color_kernel_ms()
+            c.set_depth_test(False)
+            fc.color_isosurface(c, fused_depth_tolerance=tol)
+            k_fused = fc.isosurface_color_kernel_ms()
+            if r == 0:
+                continue
+            rec["kernel_ms"].append(k)
+            rec["pass_ms"].append(p)
+            rec["queued_pairs"] = q
+            rec["color_rendered_kernel_ms"].append(k_rendered)
+            rec["color_fused_kernel_ms"].append(k_fused)
+    rec["kernel_ms_min"] = min(rec["kernel_ms"])
+    for p in ("init", "small", "large"):
+        rec[p + "_ms_min"] = min(x[p] for x in rec["pass_ms"])
+    rec["color_rendered_kernel_ms_min"] = min(rec["color_rendered_kernel_ms"])
+    rec["color_fused_kernel_ms_min"] = min(rec["color_fused_kernel_ms"])
+    pairs = rec["triangles"] * n
+    rec["projections"] = pairs
+    rec["projection_floor_ms_fp64_vector"] = pairs * 3 * (33 + 2 * 30) / (FP64_VECTOR_TFLOPS * 1e12) * 1e3
+    rec["plane_bytes"] = n * ((1280 + 7) // 8) * ((720 + 3) // 4) * 32 * 8
+    rec["init_floor_ms_8tbps"] = rec["plane_bytes"] / HBM_TBPS / 1e9
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iso", type=float, default=1.0)
@@ -266,6 +323,9 @@ def main():
     ap.add_argument("--color", action="store_true", help="also time the coloration of the device mesh against dmi_color_process")
     ap.add_argument("--color-views", type=int, default=64, help="... from the scene's first this many views")
     ap.add_argument("--color-decimate", type=float, default=2.0, help="... and again after a decimation at this many grid spacings")
+    ap.add_argument("--render-depths", action="store_true", help="also time the rendering of the mesh's own depth planes and the colouring with them")
+    ap.add_argument("--render-views", type=int, default=256, help="... into the scene's first this many views")
+    ap.add_argument("--render-queue", type=int, default=0, help="... with this queue capacity (0: the default)")
     ap.add_argument("--grid", type=int, default=512, help="cells per axis (512: the cfg-3 grid)")
     a = ap.parse_args()
     grid = scene.default_grid(a.grid)
@@ -296,6 +356,7 @@ def main():
         for h in a.decimate:
             decimate.append(decimate_record(ctx, argparse.Namespace(**{**vars(a), "decimate": h})))
         color = color_record(ctx, a, spacing) if a.color else None
+        render = render_record(ctx, a, spacing) if a.render_depths else None
     n_points = (a.grid + 1) ** 3
     lattice = n_points * 8
     out = {"iso": a.iso, "views": a.views, "vertices": nv, "triangles": nt, "kernel_ms": times, "kernel_ms_min": min(times),
@@ -313,6 +374,8 @@ def main():
         out["decimate"] = decimate
     if color is not None:
         out["color"] = color
+    if render is not None:
+        out["render_depths"] = render
     print(json.dumps(out))
 
 
