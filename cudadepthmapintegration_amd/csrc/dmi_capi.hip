@@ -75,16 +75,13 @@ int flush_zero_fill(dmi_context *ctx) {
 }
 
 int ensure_buffer(dmi_context *ctx, DeviceBuffer &buffer, uint64_t bytes) {
-  if (buffer.ptr && buffer.capacity >= bytes) return DMI_OK;
-  if (buffer.ptr) {
-    DMI_HIP(ctx, hipFree(buffer.ptr));
-    ctx->device_bytes -= buffer.capacity;
-    buffer = DeviceBuffer{};
-  }
-  DMI_HIP(ctx, hipMalloc(&buffer.ptr, (size_t)bytes));
-  ctx->device_bytes += bytes;
-  buffer.capacity = bytes;
-  return DMI_OK;
+  const uint64_t before = buffer.capacity;
+  const hipError_t grown = grow_buffer(buffer, bytes);
+  ctx->device_bytes += buffer.capacity - before;  // (what was freed has left even when the allocation failed)
+  if (grown == hipSuccess) return DMI_OK;
+  (void)hipGetLastError();
+  return fail(ctx, grown == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE,
+              std::string("hipMalloc(&buffer.ptr, (size_t)bytes): ") + hipGetErrorString(grown));  // (the message as it always read)
 }
 
 int ensure_buffers(dmi_context *ctx, std::initializer_list<BufferNeed> needs) {

@@ -1,6 +1,7 @@
 // dmi_context.h -- the context behind the C ABI of include/dmi.h, and the helpers its translation units share (dmi_capi.hip:
-// creation, destruction, views, fusion, grid transfer, diagnostics; dmi_capi_mesh.hip: point data and the iso-surface).
-// Private: never installed.
+// creation, destruction, views, fusion, grid transfer, diagnostics; dmi_capi_mesh.hip: point data and the iso-surface).  The
+// colour context (dmi_color_context.h, dmi_capi_color.hip) is built from the same DeviceBuffer, growth rule, release() parts
+// and exception guard.  Private: never installed.
 #pragma once
 #include "../../include/dmi.h"
 #include "fusion_kernels.h"
@@ -31,7 +32,7 @@ struct EventPair {
 };
 
 // A grow-only device allocation of the context: the pointer and its capacity travel together (one std::swap exchanges two
-// buffers whole).  Grown by ensure_buffer, freed by its group's release(); owns nothing by itself.
+// buffers whole).  Grown by grow_buffer (ensure_buffer), freed by its group's release(); owns nothing by itself.
 struct DeviceBuffer {
   void *ptr = nullptr;
   uint64_t capacity = 0;  // bytes
@@ -39,7 +40,19 @@ struct DeviceBuffer {
   T *as() const { return static_cast<T *>(ptr); }
 };
 
-// what every group's release() is made of (dmi_destroy has selected the device)
+inline bool holds(const DeviceBuffer &buffer, uint64_t bytes) { return buffer.ptr && buffer.capacity >= bytes; }
+// The growth rule of every context: a buffer that holds `bytes` is kept, any other is freed and allocated at exactly `bytes`; the
+// old contents are not kept.  A failure leaves it empty with capacity 0, so that the next call allocates again.
+inline hipError_t grow_buffer(DeviceBuffer &buffer, uint64_t bytes) {
+  if (holds(buffer, bytes)) return hipSuccess;
+  hipError_t e = buffer.ptr ? hipFree(buffer.ptr) : hipSuccess;
+  buffer = DeviceBuffer{};
+  if (e == hipSuccess) e = hipMalloc(&buffer.ptr, (size_t)bytes);
+  if (e == hipSuccess) buffer.capacity = bytes; else buffer.ptr = nullptr;
+  return e;
+}
+
+// what every group's release() is made of (the caller has selected the device)
 inline void free_buffers(std::initializer_list<DeviceBuffer *> buffers) {
   for (DeviceBuffer *b : buffers) {
     if (b->ptr) (void)hipFree(b->ptr);
@@ -199,7 +212,7 @@ struct dmi_context {
     void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); dmi::destroy_events(events); }
   } decimation;
 
-  struct Coloration {  // dmi_color_process_isosurface (coloration_kernels.hip through dmi::color_device_vertices)
+  struct Coloration {  // dmi_color_process_isosurface (dmi_capi_color.hip through dmi::color_device_vertices)
     hipEvent_t events[1] = {nullptr};  // what the colour context's stream waits for: the end of this context's queued work
     double last_kernel_ms = 0.0;
     void release() { dmi::destroy_events(events); }
@@ -224,8 +237,7 @@ int fail(dmi_context *ctx, int code, const std::string &msg);  // records msg (c
 int drain_events(dmi_context *ctx);                            // the pending fusions' timings
 int drain_c2p(dmi_context *ctx);                               // ... and the pending cell-to-point pass's
 int flush_zero_fill(dmi_context *ctx);
-// Grows a context-owned device buffer to hold `bytes`: kept when its capacity suffices, else freed and allocated at exactly
-// `bytes` (device_bytes follows); the old contents are not kept.
+// grow_buffer for a buffer of this context: device_bytes follows, a failure is recorded
 int ensure_buffer(dmi_context *ctx, DeviceBuffer &buffer, uint64_t bytes);
 struct BufferNeed {
   DeviceBuffer *buffer;
@@ -234,30 +246,34 @@ struct BufferNeed {
 int ensure_buffers(dmi_context *ctx, std::initializer_list<BufferNeed> needs);  // in order, up to the first failure
 
 // No C++ exception may cross the C ABI (the caller may be C, or C++ built with another runtime): every entry point
-// that can allocate on the host runs its body through this.
-template <typename Body>
-int guarded(dmi_context *ctx, const char *entry, Body &&body) noexcept {
+// that can allocate on the host runs its body through this.  `fail` is the context type's failure sink (dmi::fail, or the
+// colour context's).
+template <typename Ctx, typename Body>
+int guarded_by(int (*fail)(Ctx *, int, const std::string &), Ctx *ctx, const char *entry, Body &&body) noexcept {
+  auto report = [&](int code, const char *what) noexcept {
+    try {
+      return fail(ctx, code, std::string(entry) + ": " + what);
+    } catch (...) {
+      return code;
+    }
+  };
   try {
     return body();
   } catch (const std::bad_alloc &) {
-    try {
-      return fail(ctx, DMI_ERR_OUT_OF_MEMORY, std::string(entry) + ": host allocation failed");
-    } catch (...) {
-      return DMI_ERR_OUT_OF_MEMORY;
-    }
+    return report(DMI_ERR_OUT_OF_MEMORY, "host allocation failed");
   } catch (const std::exception &e) {
-    try {
-      return fail(ctx, DMI_ERR_STATE, std::string(entry) + ": " + e.what());
-    } catch (...) {
-      return DMI_ERR_STATE;
-    }
+    return report(DMI_ERR_STATE, e.what());
   } catch (...) {
-    return DMI_ERR_STATE;
+    return report(DMI_ERR_STATE, "unexpected C++ exception");
   }
+}
+template <typename Body>
+int guarded(dmi_context *ctx, const char *entry, Body &&body) noexcept {
+  return guarded_by(&fail, ctx, entry, static_cast<Body &&>(body));
 }
 
 
-// The colouring of vertices that are on the device already (coloration_kernels.hip, where dmi_color_context is private): the
+// The colouring of vertices that are on the device already (dmi_capi_color.hip, where dmi_color_context is private): the
 // chunk body of dmi_color_process with a chunk being an offset into `points` and into the outputs, no copy in and none out.
 struct ColorContextShape {
   int32_t device, W, H;

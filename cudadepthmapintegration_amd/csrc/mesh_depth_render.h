@@ -1,5 +1,5 @@
-// mesh_depth_render.h -- what coloration_kernels.hip (the owner of dmi_color_context) sees of the z-buffer rasteriser in
-// mesh_depth_render.hip, and the texel layout both share.  Private: never installed.
+// mesh_depth_render.h -- what dmi_capi_color.hip (the owner of dmi_color_context) sees of the z-buffer rasteriser in
+// mesh_depth_render.hip, and the texel layout that the rasteriser and coloration_kernels.hip share.  Private: never installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-"""The coloration pass at its edges (csrc/coloration_kernels.hip): pixel ties where the shortcut of the pixel selection runs
+"""The coloration pass at its edges (kernels: csrc/coloration_kernels.hip; context and host driver: csrc/dmi_capi_color.hip): pixel ties where the shortcut of the pixel selection runs
 and where it must not, medians of multisets the test names, both median kernels at 65 535 / 65 536 views, tiled planes with
 partial tiles checked texel by texel, and the view counts around the rounds of the pipelined view loop.  Scenes and
 expectations: tests/coloration_cases.py.  Every output is an integer: every comparison is np.array_equal."""
