@@ -114,6 +114,8 @@ ABI_SYMBOLS = [
     "dmi_smooth_isosurface", "dmi_get_isosurface_smooth_kernel_ms", "dmi_get_isosurface_smooth_pass_ms",
     "dmi_decimate_isosurface", "dmi_get_isosurface_decimate_kernel_ms", "dmi_get_isosurface_decimate_pass_ms",
     "dmi_color_process_isosurface", "dmi_download_isosurface_colors", "dmi_get_isosurface_color_kernel_ms",
+    "dmi_filter_isosurface_support", "dmi_download_isosurface_support", "dmi_get_isosurface_support_kernel_ms",
+    "dmi_get_isosurface_support_pass_ms",
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
@@ -206,6 +208,11 @@ def load() -> ctypes.CDLL:
         L.dmi_decimate_isosurface.argtypes = [vp, dbl, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.dmi_get_isosurface_decimate_kernel_ms.argtypes = [vp, dp]
         L.dmi_get_isosurface_decimate_pass_ms.argtypes = [vp, dp]
+    if hasattr(L, "dmi_filter_isosurface_support"):
+        L.dmi_filter_isosurface_support.argtypes = [vp, i32, dbl, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.dmi_download_isosurface_support.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
+        L.dmi_get_isosurface_support_kernel_ms.argtypes = [vp, dp]
+        L.dmi_get_isosurface_support_pass_ms.argtypes = [vp, dp]
     L.dmi_get_brick_class_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dmi_get_mixed_reason_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_get_window_pair_count"):  # (absent from an older prebuilt library loaded for an A/B timing, tools/gpu_exp.py)
@@ -620,6 +627,40 @@ class FusionContext:
         a = (ctypes.c_double * 4)()
         self._check(self._lib.dmi_get_isosurface_decimate_pass_ms(self._h, a))
         return dict(zip(("clustering", "representatives", "triangles", "normals"), (float(x) for x in a)))
+
+    def filter_isosurface_support(self, min_views: int, tolerance: float, facing: bool = True):
+        """(vertices, triangles) left after the trim of the context's mesh by view support on the device: every vertex is given the
+        number of resident views that saw it -- in front of the camera, inside the image, within `tolerance` of the depth the
+        fusion kept at its pixel and, with `facing`, with its normal towards the camera -- and only the triangles whose three
+        vertices have at least `min_views` such views stay, with the vertices they name.  min_views 0: the counts only
+        (dmi_filter_isosurface_support).  download_isosurface* return the trimmed mesh afterwards."""
+        nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._lib.dmi_filter_isosurface_support(self._h, int(min_views), float(tolerance), 1 if facing else 0,
+                                                            ctypes.byref(nv), ctypes.byref(nt)))
+        old = self._mesh_counts
+        if old is None or (int(nv.value), int(nt.value)) != old[:2]:   # something went: the regions of an earlier filter too
+            self._mesh_counts = (int(nv.value), int(nt.value), 0)
+        return int(nv.value), int(nt.value)
+
+    def download_isosurface_support(self):
+        """support [n] int32: the supporting views of every vertex of the mesh as the last filter_isosurface_support left it
+        (dmi_download_isosurface_support)."""
+        nv, _, _ = self._current_mesh_counts()
+        support = np.zeros(max(nv, 1), dtype=np.int32)    # never a null pointer, even for an empty mesh
+        self._check(self._lib.dmi_download_isosurface_support(self._h, support.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return support[:nv]
+
+    def isosurface_support_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last filter_isosurface_support (dmi_get_isosurface_support_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_isosurface_support_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
+
+    def isosurface_support_pass_ms(self) -> dict:
+        """The same pass by pass (dmi_get_isosurface_support_pass_ms)."""
+        a = (ctypes.c_double * 3)()
+        self._check(self._lib.dmi_get_isosurface_support_pass_ms(self._h, a))
+        return dict(zip(("counts", "scans", "compaction"), (float(x) for x in a)))
 
     def color_isosurface(self, color_ctx: "ColorContext", fused_depth_tolerance: float | None = None) -> int:
         """Colour the context's mesh where it is, with the views resident in `color_ctx`; returns the number of vertices.  The

@@ -26,65 +26,18 @@
 // This file: the device code and its launches (coloration_kernels.h).  The context, the C ABI and the host drivers: dmi_capi_color.hip.
 #include "coloration_kernels.h"
 #include "mesh_depth_render.h"
+#include "rounded_quotient.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace {
 
-using dmi::ColorView, dmi::ViewMargin, dmi::MedianSeed;
+using dmi::ColorView, dmi::ViewMargin, dmi::MedianSeed, dmi::FastQuotient, dmi::to_pixel;
 
 template <typename T>
 __device__ __forceinline__ T cload(const T *p) {  // wave-uniform address -> scalar load
   return *reinterpret_cast<const T __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(p));
 }
-
-__device__ __forceinline__ bool to_pixel(double u, int &p) {  // round half away from zero; NaN/inf/|x| >= 2^31 outside
-  const double r = round(u);
-  if (!(r > -2147483648.0 && r < 2147483648.0)) return false;
-  p = (int)r;
-  return true;
-}
-
-// std::round(num / den) as an int (RD.cxx:177-181) without the correctly rounded division, when that provably changes
-// nothing: r = 1/den from the hardware seed and two Newton steps, its residual 1 - den*r CHECKED to be below 2^-40, so
-// ua = num*r is within |Q| * 2^-39 of the real quotient Q and within 2^-21 of the reference's q = fl(num/den) as long as
-// |ua| < 2^16; if ua is further than 2^-20 from every half-integer, q lies on the same side of the same half-integers
-// and rounds -- half away from zero or not, no tie is near -- to the integer nearest to ua.  Everything else (a pixel
-// coordinate beyond 65 536, a near-tie, a zero / tiny / NaN denominator) takes the division.  Two quotients share r.
-struct FastQuotient {
-  double r;
-  bool usable;
-  __device__ __forceinline__ explicit FastQuotient(double den) {
-    double x = __builtin_amdgcn_rcp(den);
-    x = __builtin_fma(__builtin_fma(-den, x, 1.0), x, x);
-    x = __builtin_fma(__builtin_fma(-den, x, 1.0), x, x);
-    r = x;
-    usable = __builtin_fabs(__builtin_fma(-den, x, 1.0)) < 0x1p-40;  // NaN: false
-  }
-  __device__ __forceinline__ bool round_to_pixel(double num, double den, int &p) const {
-    const double ua = num * r;
-    const double fl = __builtin_floor(ua), fr = ua - fl;  // fr in [0, 1), exact
-    if (usable && __builtin_fabs(ua) < 65536.0 && __builtin_fabs(fr - 0.5) > 0x1p-20) {
-      p = (int)fl + (fr > 0.5 ? 1 : 0);
-      return true;
-    }
-    return to_pixel(num / den, p);
-  }
-  // The same for a numerator and a denominator that are only NEAR the reference's (each within the bounds behind
-  // `margin` = (E_num + 65537 E_den)): |num/den - num_ref/den_ref| <= (E_num + |u| E_den) / |den| with |u| < 2^16, so
-  // ua is within margin * |r| + 2^-21 of the reference's quotient; accepted iff further than that + 2^-21 from every
-  // half-integer.  false = not decided (the caller takes the reference's own expression).
-  __device__ __forceinline__ bool round_to_pixel_near(double num, double margin, int &p) const {
-    const double ua = num * r;
-    const double fl = __builtin_floor(ua), fr = ua - fl;
-    const double reach = __builtin_fma(margin, __builtin_fabs(r), 0x1p-20);
-    if (usable && __builtin_fabs(ua) < 65536.0 && __builtin_fabs(fr - 0.5) > reach) {  // a NaN margin or r: not taken
-      p = (int)fl + (fr > 0.5 ? 1 : 0);
-      return true;
-    }
-    return false;
-  }
-};
 
 // A colour plane in HBM: RGBA texels, top image row first, in TILES of 8 x 4 texels = one 128-byte line (texel (x, y) at
 // ((y >> 2) * tiles_x + (x >> 3)) * 32 + (y & 3) * 8 + (x & 7)).  The vertices of a wave are neighbours on the surface, their

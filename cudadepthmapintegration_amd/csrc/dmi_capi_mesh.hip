@@ -1,6 +1,6 @@
 // dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
 // (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
-// filter, the smoother, the decimation, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
+// filter, the smoother, the decimation, the support trim, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
 #include "dmi_context.h"
 
 #include <algorithm>
@@ -157,6 +157,7 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
   mesh.valid = false;
   mesh.has_normals = false;
   mesh.filtered = false;
+  ctx->support.valid = false;  // the counts of an earlier mesh are not this one's
   const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
   const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
   if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": grid too large for one launch");
@@ -307,6 +308,7 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   if (nv == 0) {  // an empty mesh stays empty
     mesh.filtered = true;
     mesh.colored = false;
+    ctx->support.valid = false;
     mesh.regions = 0;
     comp.last_kernel_ms = 0.0;
     for (double &p : comp.last_pass_ms) p = 0.0;
@@ -371,6 +373,7 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   mesh.regions = kept[2];
   mesh.filtered = true;
   mesh.colored = false;  // the colours were the unfiltered mesh's
+  ctx->support.valid = false;  // ... and so were the support counts
   comp.last_cas_retries = counters[2];
   *n_vertices = kept[0];
   *n_triangles = kept[1];
@@ -444,6 +447,7 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
     sm.last_kernel_ms = 0.0;
     for (double &p : sm.last_pass_ms) p = 0.0;
     if (iterations > 0) mesh.colored = false;
+    if (iterations > 0) ctx->support.valid = false;
     return DMI_OK;
   }
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
@@ -492,6 +496,7 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   std::swap(mesh.vertices, result == mesh.alt_vertices.ptr ? mesh.alt_vertices : sm.vertices);
   if (normals) std::swap(mesh.normals, mesh.alt_normals);
   mesh.colored = false;  // the colours were those of the positions before
+  ctx->support.valid = false;  // ... and so were the support counts
   return DMI_OK;
   });
 }
@@ -567,6 +572,7 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   if (nv == 0) {  // an empty mesh stays empty (it has no triangles either)
     mesh.filtered = false;
     mesh.colored = false;
+    ctx->support.valid = false;
     dc.last_kernel_ms = 0.0;
     for (double &p : dc.last_pass_ms) p = 0.0;
     return DMI_OK;
@@ -661,6 +667,7 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
   mesh.regions = 0;
   mesh.colored = false;   // ... nor are the colours
+  ctx->support.valid = false;  // ... nor the support counts
   *n_vertices = kept[0];
   *n_triangles = kept[1];
   return DMI_OK;
@@ -683,6 +690,154 @@ int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]) {
   const int rc = drain_decimation(ctx);
   if (rc != DMI_OK) return rc;
   for (int p = 0; p < 4; ++p) out[p] = ctx->decimation.last_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
+int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double tolerance, int32_t require_facing, uint64_t *n_vertices,
+                                  uint64_t *n_triangles) {
+  return guarded(ctx, "dmi_filter_isosurface_support", [&]() -> int {
+  const std::string entry = "dmi_filter_isosurface_support";
+  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (min_views < 0) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": min_views " + std::to_string(min_views) + " is negative");
+  if (!(tolerance >= 0.0 && tolerance <= 1.7976931348623157e308))  // NaN, negative, infinite
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the tolerance must be finite and >= 0");
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Support &sup = ctx->support;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const bool facing = require_facing != 0;
+  if (facing && !mesh.has_normals)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": require_facing needs the mesh's normals (dmi_extract_isosurface_normals)");
+  const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
+  // the maps of the compaction are u32: refused, never wrapped
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  const size_t n_views = ctx->h_maps.size();
+  if (n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident (call dmi_add_views first)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (nv == 0) {  // an empty mesh stays empty, and its counts are empty
+    sup.valid = true;
+    sup.last_kernel_ms = 0.0;
+    for (double &p : sup.last_pass_ms) p = 0.0;
+    *n_vertices = 0;
+    *n_triangles = nt;
+    return DMI_OK;
+  }
+  const bool trim = min_views > 0;  // 0: the counts only
+  const bool normals = mesh.has_normals;
+  size_t temp_bytes = 0;
+  if (trim) {
+    DMI_HIP(ctx, dmi::support_scan_temp_bytes(nv, nt, &temp_bytes));
+    temp_bytes = std::max<size_t>(temp_bytes, 16);
+  }
+  // the counts and the views' records; for a trim also the result's buffers (the component filter's alternates), the compacted
+  // counts, the per-vertex and per-triangle u32 arrays and the scans' own storage
+  int rc = ensure_buffers(ctx, {{&sup.work, nv * 4}, {&sup.maps, (uint64_t)n_views * sizeof(dmi::MapRec)},
+                                {&mesh.alt_vertices, trim ? nv * kVertexBytes : 0},
+                                {&mesh.alt_triangles, trim ? std::max<uint64_t>(nt, 1) * kTriangleBytes : 0},
+                                {&mesh.alt_normals, trim && normals ? nv * kNormalBytes : 0}, {&sup.compacted, trim ? nv * 4 : 0},
+                                {&sup.vertex_scratch, trim ? 2 * (nv + 1) * 4 : 0}, {&sup.triangle_scratch, trim ? (nt + 1) * 4 : 0},
+                                {&sup.scan_temp, trim ? temp_bytes : 0}});
+  if (rc != DMI_OK) return rc;
+  if (!sup.events[0])
+    for (hipEvent_t &e : sup.events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::SupportMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = mesh.vertices.as<double>();
+  m.normals = normals ? mesh.normals.as<float>() : nullptr;
+  m.triangles = mesh.triangles.as<int64_t>();
+  m.out_vertices = mesh.alt_vertices.as<double>();
+  m.out_normals = mesh.alt_normals.as<float>();
+  m.out_triangles = mesh.alt_triangles.as<int64_t>();
+  dmi::SupportViews views{};
+  views.maps = sup.maps.as<dmi::MapRec>();
+  views.n_views = (int)n_views;
+  views.W = ctx->W;
+  views.H = ctx->H;
+  views.depth_is_f64 = ctx->depth_f64 ? 1 : 0;
+  dmi::SupportScratch s{};
+  s.support = sup.work.as<int32_t>();
+  s.out_support = sup.compacted.as<int32_t>();
+  s.mark = sup.vertex_scratch.as<uint32_t>();
+  s.vmap = trim ? s.mark + (nv + 1) : nullptr;
+  s.tmap = sup.triangle_scratch.as<uint32_t>();
+  s.scan_temp = sup.scan_temp.ptr;
+  s.scan_temp_bytes = temp_bytes;
+  // (a failure from here on leaves the context's mesh, its normals, regions, colours and counts as they were: no kernel writes
+  // them, and the buffers are swapped only at the end)
+  // The records as they are now (h_maps is pageable: the copy is complete for the host when the call returns).  Not ctx->d_maps:
+  // that array is brought up to date only by a fusion (sync_maps in dmi_capi.hip, with the tiled kernel's records and the hit
+  // counters), so it lags behind views added since, and bringing it up to date from here would tie this call to the fusion's
+  // bookkeeping; 208 B a view per call is the price.
+  DMI_HIP(ctx, hipMemcpyAsync(sup.maps.ptr, ctx->h_maps.data(), n_views * sizeof(dmi::MapRec), hipMemcpyHostToDevice, ctx->stream));
+  DMI_HIP(ctx, dmi::launch_isosurface_support_counts(m, views, tolerance, facing ? 1 : 0, s, sup.events, ctx->stream));
+  uint32_t kept[2] = {(uint32_t)nv, (uint32_t)nt};
+  if (trim) {
+    DMI_HIP(ctx, dmi::launch_isosurface_support_filter(m, min_views, s, sup.events, ctx->stream));
+    DMI_HIP(ctx, hipMemcpyAsync(&kept[0], s.vmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    DMI_HIP(ctx, hipMemcpyAsync(&kept[1], s.tmap + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int n_passes = trim ? 3 : 1;
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, sup.events[0], sup.events[n_passes]));
+  sup.last_kernel_ms = (double)ms;
+  for (int p = 0; p < 3; ++p) {
+    ms = 0.f;
+    if (p < n_passes) DMI_HIP(ctx, hipEventElapsedTime(&ms, sup.events[p], sup.events[p + 1]));
+    sup.last_pass_ms[p] = (double)ms;
+  }
+  if (kept[0] != nv || kept[1] != nt) {
+    // the compacted mesh becomes the context's; the buffers it came from are the next call's output
+    std::swap(mesh.vertices, mesh.alt_vertices);
+    std::swap(mesh.triangles, mesh.alt_triangles);
+    if (normals) std::swap(mesh.normals, mesh.alt_normals);
+    std::swap(sup.counts, sup.compacted);
+    mesh.n_vertices = kept[0];
+    mesh.n_triangles = kept[1];
+    mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
+    mesh.regions = 0;
+    mesh.colored = false;   // ... nor are the colours
+  } else {
+    std::swap(sup.counts, sup.work);  // nothing went: the mesh, its regions and its colours stay
+  }
+  sup.valid = true;
+  *n_vertices = kept[0];
+  *n_triangles = kept[1];
+  return DMI_OK;
+  });
+}
+
+int dmi_download_isosurface_support(dmi_context *ctx, int32_t *support) {
+  return guarded(ctx, "dmi_download_isosurface_support", [&]() -> int {
+  if (!ctx || !support) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_support: null argument");
+  const dmi_context::Mesh &mesh = ctx->mesh;
+  if (!mesh.valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_support: no mesh (no extraction has succeeded)");
+  if (!ctx->support.valid)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_download_isosurface_support: no counts (dmi_filter_isosurface_support has not run since the mesh last changed)");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  if (mesh.n_vertices)
+    DMI_HIP(ctx, hipMemcpyAsync(support, ctx->support.counts.ptr, (size_t)mesh.n_vertices * 4, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_support_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_support_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_support_kernel_ms: null argument");
+  *last = ctx->support.last_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_support_pass_ms(dmi_context *ctx, double out[3]) {
+  return guarded(ctx, "dmi_get_isosurface_support_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_support_pass_ms: null argument");
+  for (int p = 0; p < 3; ++p) out[p] = ctx->support.last_pass_ms[p];
   return DMI_OK;
   });
 }

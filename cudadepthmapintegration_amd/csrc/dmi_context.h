@@ -153,7 +153,7 @@ struct dmi_context {
     bool pending = false;
     void release() { dmi::free_buffers({&points}); dmi::destroy_events(events); }
   } c2p;
-  // The mesh of the last extraction, as the filter, the smoother and the decimation have left it.  The filter and the decimation
+  // The mesh of the last extraction, as the support trim, the filter, the smoother and the decimation have left it.  The filter and the decimation
   // write into the alternates and the smoother steps through alt_vertices and smoothing.vertices (normals into alt_normals);
   // whichever holds the result is then swapped with the mesh's own buffer.
   struct Mesh {
@@ -211,6 +211,23 @@ struct dmi_context {
     double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // clustering, representatives, triangles, normals
     void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); dmi::destroy_events(events); }
   } decimation;
+
+  struct Support {  // dmi_filter_isosurface_support (isosurface_support.hip)
+    dmi::DeviceBuffer counts;          // [n] int32: the supporting views of every vertex of the mesh, as the last call left it
+    dmi::DeviceBuffer work, compacted; // the call's own counts, and those of its compacted mesh: whichever holds the result is
+                                       // swapped with `counts` last
+    dmi::DeviceBuffer maps;            // the resident views' MapRecs as the call found them
+    dmi::DeviceBuffer vertex_scratch;  // mark, vmap: 2 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer triangle_scratch, scan_temp;
+    bool valid = false;                // `counts` describes this mesh (dropped by whatever changes it)
+    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
+    double last_kernel_ms = 0.0;
+    double last_pass_ms[3] = {0.0, 0.0, 0.0};  // counts, marks and scans, compaction
+    void release() {
+      dmi::free_buffers({&counts, &work, &compacted, &maps, &vertex_scratch, &triangle_scratch, &scan_temp});
+      dmi::destroy_events(events);
+    }
+  } support;
 
   struct Coloration {  // dmi_color_process_isosurface (dmi_capi_color.hip through dmi::color_device_vertices)
     hipEvent_t events[1] = {nullptr};  // what the colour context's stream waits for: the end of this context's queued work

@@ -538,4 +538,35 @@ double decimate_decode_bound(unsigned long long ordered);
 hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, hipEvent_t *events,
                                       hipStream_t stream);
 
+// The trim of that mesh by view support (isosurface_support.hip).  Nothing of the input mesh is written.
+struct SupportMesh {
+  uint64_t n_vertices, n_triangles;  // n_vertices >= 1, both below 2^32 (u32 maps on the device)
+  const double *vertices;            // [n_vertices][3]
+  const float *normals;              // [n_vertices][3], or null: the mesh has none
+  const int64_t *triangles;          // [n_triangles][3]
+  double *out_vertices;              // room for the whole mesh each: how much stays is known only afterwards
+  float *out_normals;
+  int64_t *out_triangles;
+};
+struct SupportViews {
+  const MapRec *maps;                // [n_views], device: K, [R|T] and the depth table the fusion kept of every resident view
+  int n_views, W, H;
+  int depth_is_f64;
+};
+struct SupportScratch {
+  int32_t *support;                  // [n_vertices]: the counts of the input mesh
+  int32_t *out_support;              // [n_vertices]: ... of the compacted one
+  uint32_t *mark, *vmap;             // [n_vertices + 1]: named by a surviving triangle; surviving vertices before it
+  uint32_t *tmap;                    // [n_triangles + 1]: surviving triangles before it
+  void *scan_temp;                   // rocPRIM's
+  size_t scan_temp_bytes;
+};
+hipError_t support_scan_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
+// `events`: 4 (or null); the counts run between [0] and [1], the filter's marks and scans between [1] and [2], its compaction
+// between [2] and [3].  After the filter s.vmap[n_vertices] and s.tmap[n_triangles] hold the output's sizes.
+hipError_t launch_isosurface_support_counts(const SupportMesh &m, const SupportViews &views, double tolerance, int require_facing,
+                                            const SupportScratch &s, hipEvent_t *events, hipStream_t stream);
+hipError_t launch_isosurface_support_filter(const SupportMesh &m, int32_t min_views, const SupportScratch &s, hipEvent_t *events,
+                                            hipStream_t stream);
+
 }  // namespace dmi

@@ -179,6 +179,28 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                      "fusion kept: no holes, and still the surface after smoothing or decimation. "
                                                      "A triangle that crosses a camera's plane does not occlude (not in the reference)",
                                          into_flag(&o->meshColorationDepthFromMesh)}},
+      {"--meshMinSupportViews", {Kind::kValue, "with --extractMesh, on one GPU: trim the mesh by view support on the GPU, right after "
+                                               "the extraction and before the component flags (which then remove the fragments it "
+                                               "leaves): a view supports a vertex that lies in front of its camera, inside its image, "
+                                               "within --meshSupportDepthTolerance of the depth the fusion kept at its pixel (after "
+                                               "--threshBestCost) and whose normal points towards the camera; only the triangles whose "
+                                               "three vertices have at least this many supporting views stay, with the vertices they "
+                                               "name (a non-negative integer; 0 drops nothing; needs --meshSupportDepthTolerance; not "
+                                               "in the reference)",
+                                 into_count(&o->meshMinSupportViews)}},
+      {"--meshSupportDepthTolerance", {Kind::kValue, "the depth tolerance of --meshMinSupportViews and --meshSupportArray (world units, "
+                                                     "finite, >= 0; required with either; not in the reference)",
+                                       into_checked_double(&o->meshSupportDepthTolerance, &o->meshSupportDepthToleranceGiven,
+                                                           [](double x) { return x >= 0.0; })}},
+      {"--meshSupportNoFacing", {Kind::kFlag, "with --meshMinSupportViews or --meshSupportArray: a view supports a vertex whichever way "
+                                              "its normal points (without the flag the normals are computed for the test even when "
+                                              "--meshNormals is not given, and then not written; not in the reference)",
+                                 into_flag(&o->meshSupportNoFacing)}},
+      {"--meshSupportArray", {Kind::kFlag, "with --extractMesh, on one GPU: write the point array NbSupportingViews (Int32), the number of "
+                                           "supporting views of every vertex of the mesh as written, counted after every other mesh "
+                                           "operation (needs --meshSupportDepthTolerance, works without --meshMinSupportViews; not in "
+                                           "the reference)",
+                              into_flag(&o->meshSupportArray)}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -279,6 +301,27 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     err << "Error : --meshColoration takes one --device (the mesh of a fusion over several GPUs is not coloured).\n" << HelpText();
     return false;
   }
+  for (const auto &flag : {std::make_pair("--meshMinSupportViews", o->meshMinSupportViews >= 0), std::make_pair("--meshSupportArray", o->meshSupportArray)}) {
+    if (!flag.second) continue;
+    if (!o->extractMesh) {
+      err << "Error : " << flag.first << " needs --extractMesh (the support belongs to the extracted mesh).\n" << HelpText();
+      return false;
+    }
+    if (!o->meshSupportDepthToleranceGiven) {
+      err << "Error : " << flag.first << " needs --meshSupportDepthTolerance.\n" << HelpText();
+      return false;
+    }
+    if (o->devices.size() > 1) {
+      err << "Error : " << flag.first << " takes one --device (the mesh of a fusion over several GPUs is not trimmed).\n" << HelpText();
+      return false;
+    }
+  }
+  for (const auto &flag : {std::make_pair("--meshSupportDepthTolerance", o->meshSupportDepthToleranceGiven),
+                           std::make_pair("--meshSupportNoFacing", o->meshSupportNoFacing)})
+    if (flag.second && o->meshMinSupportViews < 0 && !o->meshSupportArray) {
+      err << "Error : " << flag.first << " needs --meshMinSupportViews or --meshSupportArray.\n" << HelpText();
+      return false;
+    }
   // rmain:257-262
   if (!o->gridSpacing.empty() && !o->gridDims.empty()) {
     err << "Error : Spacing and dimensions can't be both set\n" << HelpText();
@@ -455,7 +498,7 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
                    std::string *error, const float *normals, double contour, const int64_t *regionIds, const uint8_t *mean,
-                   const uint8_t *median, const int32_t *count) {
+                   const uint8_t *median, const int32_t *count, const int32_t *support) {
   const bool colors = mean && median && count;
   if (nPoints < 0 || nTriangles < 0) {
     *error = "WritePolyData: negative count";
@@ -473,7 +516,8 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
   const uint64_t region_bytes = (uint64_t)nPoints * sizeof(int64_t);
   const uint64_t region_offset = normal_offset + (normals ? 2 * sizeof(uint64_t) + normal_bytes + scalar_bytes : 0);
   const uint64_t rgb_bytes = (uint64_t)nPoints * 3, count_bytes = (uint64_t)nPoints * sizeof(int32_t);
-  const uint64_t color_offset = region_offset + (regionIds ? sizeof(uint64_t) + region_bytes : 0);  // behind every other array
+  const uint64_t support_offset = region_offset + (regionIds ? sizeof(uint64_t) + region_bytes : 0);
+  const uint64_t color_offset = support_offset + (support ? sizeof(uint64_t) + count_bytes : 0);  // behind every other array
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
       << nPoints << "\" NumberOfVerts=\"0\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"" << nTriangles << "\">\n";
@@ -484,16 +528,18 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
         << normal_offset + sizeof(uint64_t) + normal_bytes << "\"/>\n";
   else if (regionIds)
     out << "      <PointData Scalars=\"RegionId\">\n";
-  else if (colors)
+  else if (colors || support)
     out << "      <PointData>\n";
   if (regionIds)  // vtkPolyDataConnectivityFilter's (ColorRegionsOn)
     out << "        <DataArray type=\"Int64\" Name=\"RegionId\" format=\"appended\" offset=\"" << region_offset << "\"/>\n";
+  if (support)
+    out << "        <DataArray type=\"Int32\" Name=\"NbSupportingViews\" format=\"appended\" offset=\"" << support_offset << "\"/>\n";
   if (colors)  // the Coloration tool's three (MC.cxx:194-196)
     out << "        <DataArray type=\"UInt8\" Name=\"MeanColoration\" NumberOfComponents=\"3\" format=\"appended\" offset=\"" << color_offset
         << "\"/>\n        <DataArray type=\"UInt8\" Name=\"MedianColoration\" NumberOfComponents=\"3\" format=\"appended\" offset=\""
         << color_offset + sizeof(uint64_t) + rgb_bytes << "\"/>\n        <DataArray type=\"Int32\" Name=\"NbProjectedDepthMap\" format=\"appended\" offset=\""
         << color_offset + 2 * (sizeof(uint64_t) + rgb_bytes) << "\"/>\n";
-  if (normals || regionIds || colors) out << "      </PointData>\n";
+  if (normals || regionIds || colors || support) out << "      </PointData>\n";
   out << "      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" format=\"appended\" "
          "offset=\"0\"/>\n      </Points>\n      <Polys>\n        <DataArray type=\"Int64\" Name=\"connectivity\" format=\"appended\" offset=\""
       << sizeof(uint64_t) + point_bytes << "\"/>\n        <DataArray type=\"Int64\" Name=\"offsets\" format=\"appended\" offset=\""
@@ -525,6 +571,10 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
   if (regionIds) {
     out.write(reinterpret_cast<const char *>(&region_bytes), sizeof(region_bytes));
     out.write(reinterpret_cast<const char *>(regionIds), (std::streamsize)region_bytes);
+  }
+  if (support) {
+    out.write(reinterpret_cast<const char *>(&count_bytes), sizeof(count_bytes));
+    out.write(reinterpret_cast<const char *>(support), (std::streamsize)count_bytes);
   }
   if (colors) {
     out.write(reinterpret_cast<const char *>(&rgb_bytes), sizeof(rgb_bytes));
@@ -611,6 +661,10 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     filter.SetColorSink(coloring.c);
     filter.SetKeepContext(true);
   }
+  // the support trim and the support array read the depths the fusion kept: the same context, its views resident
+  const bool supportMesh = o.meshMinSupportViews >= 0 || o.meshSupportArray;
+  const bool supportFacing = supportMesh && !o.meshSupportNoFacing;
+  if (supportMesh) filter.SetKeepContext(true);
   if (!filter.Update()) {
     result->error = filter.LastError().empty() ? "the reconstruction filter refused its parameters" : filter.LastError();
     return 1;
@@ -634,6 +688,7 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   std::vector<int32_t> meshCount;
   uint8_t dummyRgb[3] = {0, 0, 0};
   int32_t dummyCount = 0;
+  std::vector<int32_t> meshSupport;  // --meshSupportArray
   {
     // vtkCellDataToPointData (rmain:151-155) on the GPU: the cell grid goes up once more, the point grid comes back
     dmi_grid_desc grid;
@@ -651,7 +706,7 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     opt.grid_dtype = DMI_F64;
     // (with --meshColoration: the context that fused, its views resident; the grid goes up the same way, so that every array
     // written is what it is without the flag)
-    dmi_context *ctx = o.meshColoration ? filter.TakeContext() : nullptr;  // (destroyed below like a fresh one)
+    dmi_context *ctx = o.meshColoration || supportMesh ? filter.TakeContext() : nullptr;  // (destroyed below like a fresh one)
     int rc = ctx ? DMI_OK : dmi_create(&grid, &ray, &opt, &ctx);
     if (rc == DMI_OK) rc = dmi_upload_grid(ctx, cells.data());
     if (rc == DMI_OK) rc = dmi_cell_to_point(ctx);
@@ -664,7 +719,19 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (rc == DMI_OK && o.extractMesh) {
       // vtkContourFilter + vtkTransformFilter (rmain:166-182) on the device; vtkXMLPolyDataWriter (rmain:184-187) below
       uint64_t nv = 0, nt = 0;
-      rc = o.meshNormals ? dmi_extract_isosurface_normals(ctx, o.contour, &nv, &nt) : dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      // (the facing test needs the normals whether they are written or not)
+      rc = o.meshNormals || supportFacing ? dmi_extract_isosurface_normals(ctx, o.contour, &nv, &nt) : dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      if (rc == DMI_OK && o.meshMinSupportViews > 0) {  // first: the fragments it leaves are the component flags' to remove
+        result->meshVerticesBeforeSupport = nv;
+        result->meshTrianglesBeforeSupport = nt;
+        rc = dmi_filter_isosurface_support(ctx, (int32_t)std::min(o.meshMinSupportViews, 0x7fffffffLL), o.meshSupportDepthTolerance,
+                                           supportFacing ? 1 : 0, &nv, &nt);
+        if (rc == DMI_OK) rc = dmi_get_isosurface_support_kernel_ms(ctx, &result->meshSupportKernelMs);
+      }
+      if (supportMesh) {
+        dmi_info info;
+        if (rc == DMI_OK && dmi_get_info(ctx, &info) == DMI_OK) result->meshSupportViews = (unsigned long long)info.n_views;
+      }
       result->meshVerticesExtracted = nv;
       result->meshTrianglesExtracted = nt;
       if (rc == DMI_OK && filterMesh) {
@@ -693,6 +760,14 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
         if (rc == DMI_OK && o.meshRegionIds) {  // a cluster may have joined components: RegionId is labelled anew, nothing dropped
           uint64_t found = 0, kept = 0;
           rc = dmi_filter_isosurface_components(ctx, DMI_COMPONENTS_MIN_TRIANGLES, 0, &nv, &nt, &found, &kept);
+        }
+      }
+      if (rc == DMI_OK && o.meshSupportArray) {  // the counts of the mesh as it will be written: nothing changes it from here on
+        uint64_t same_nv = 0, same_nt = 0;
+        rc = dmi_filter_isosurface_support(ctx, 0, o.meshSupportDepthTolerance, supportFacing ? 1 : 0, &same_nv, &same_nt);
+        if (rc == DMI_OK) {
+          meshSupport.resize((size_t)nv);
+          rc = dmi_download_isosurface_support(ctx, meshSupport.data() ? meshSupport.data() : &dummyCount);
         }
       }
       if (rc == DMI_OK && o.meshColoration) {  // last of all: the mesh as it will be written, where it is
@@ -750,7 +825,8 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
                        o.meshRegionIds ? (meshRegionIds.empty() ? &dummyRegion : meshRegionIds.data()) : nullptr,
                        o.meshColoration ? (meshMean.empty() ? dummyRgb : meshMean.data()) : nullptr,
                        o.meshColoration ? (meshMedian.empty() ? dummyRgb : meshMedian.data()) : nullptr,
-                       o.meshColoration ? (meshCount.empty() ? &dummyCount : meshCount.data()) : nullptr)) {
+                       o.meshColoration ? (meshCount.empty() ? &dummyCount : meshCount.data()) : nullptr,
+                       o.meshSupportArray ? (meshSupport.empty() ? &dummyCount : meshSupport.data()) : nullptr)) {
       result->error = error;
       return 1;
     }
@@ -758,6 +834,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     log << "mesh: " << o.outputMeshFilename << ": " << result->meshVertices << " vertices, " << result->meshTriangles
         << " triangles at the contour value " << o.contour << " (" << result->contourActiveCells << " of "
         << (long long)(dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1) << " cells straddle it)" << std::endl;
+    if (o.meshMinSupportViews > 0)
+      log << "mesh support: at least " << o.meshMinSupportViews << " of " << result->meshSupportViews << " views, depth tolerance "
+          << o.meshSupportDepthTolerance << (supportFacing ? ", facing" : ", any facing") << "; " << result->meshVerticesBeforeSupport
+          << " vertices, " << result->meshTrianglesBeforeSupport << " triangles before, " << result->meshVerticesExtracted << " vertices, "
+          << result->meshTrianglesExtracted << " triangles after; " << result->meshSupportKernelMs << " ms of GPU kernels" << std::endl;
     if (filterMesh)
       log << "mesh components: " << result->meshComponents << " found, " << result->meshComponentsKept << " kept; "
           << result->meshVerticesExtracted << " vertices, " << result->meshTrianglesExtracted << " triangles before, "
@@ -798,6 +879,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     if (o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
           << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";
+    if (o.meshMinSupportViews > 0)  // (only with --extractMesh)
+      out << "  mesh support  at least " << o.meshMinSupportViews << " of " << result->meshSupportViews << " views, depth tolerance "
+          << o.meshSupportDepthTolerance << (supportFacing ? ", facing" : ", any facing") << ", " << result->meshVerticesBeforeSupport
+          << " vertices, " << result->meshTrianglesBeforeSupport << " triangles before, " << result->meshVerticesExtracted << " vertices, "
+          << result->meshTrianglesExtracted << " triangles after, " << result->meshSupportKernelMs << " ms of GPU kernels\n";
     if (filterMesh)  // (only with --extractMesh)
       out << "  mesh components found  " << result->meshComponents << "\n  mesh components kept  " << result->meshComponentsKept
           << "\n  mesh vertices before the component filter  " << result->meshVerticesExtracted

@@ -14,7 +14,9 @@
 // would do) runs dmi_smooth_isosurface on the device after the component flags; with --meshNormals the Normals written are then
 // the smoothed mesh's geometric ones.  --meshDecimateCellSize v (not in the reference: what a vtkQuadricClustering or a
 // vtkCleanPolyData behind those would do) runs dmi_decimate_isosurface last, before the downloads; with --meshRegionIds the
-// labelling then runs again on the decimated mesh.  Without --extractMesh
+// labelling then runs again on the decimated mesh.  --meshMinSupportViews N with --meshSupportDepthTolerance T (not in the reference:
+// the trim by observation support of every TSDF pipeline) runs dmi_filter_isosurface_support right after the extraction, before the
+// component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
@@ -63,6 +65,13 @@ struct Options {
   double meshColorationDepthTolerance = 0.0;
   bool meshColorationDepthToleranceGiven = false;
   bool meshColorationDepthFromMesh = false;  // the tolerance is measured against the final mesh's own rendered depth
+  // not in the reference (all need --extractMesh and one GPU): trim the mesh by view support on the GPU right after the extraction
+  // (dmi_filter_isosurface_support: -1 = flag not given), with this depth tolerance and, unless --meshSupportNoFacing, the facing
+  // test; --meshSupportArray writes the counts of the final mesh as the point array NbSupportingViews
+  long long meshMinSupportViews = -1;
+  double meshSupportDepthTolerance = 0.0;
+  bool meshSupportDepthToleranceGiven = false;
+  bool meshSupportNoFacing = false, meshSupportArray = false;
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
 };
@@ -81,7 +90,7 @@ struct RunResult {
   unsigned long long contourActiveCells = 0;
   // --extractMesh: the size of the mesh written
   unsigned long long meshVertices = 0, meshTriangles = 0;
-  // with a component flag: the mesh as extracted, and the connected components found in it and kept (meshVertices /
+  // with a component flag: the mesh as extracted (as --meshMinSupportViews left it), and the connected components found in it and kept (meshVertices /
   // meshTriangles are then the filtered mesh's)
   unsigned long long meshVerticesExtracted = 0, meshTrianglesExtracted = 0, meshComponents = 0, meshComponentsKept = 0;
   double meshSmoothKernelMs = 0.0;  // --meshSmoothIterations: hipEvent time of the smoothing's kernels
@@ -92,6 +101,9 @@ struct RunResult {
   unsigned long long meshColorationViews = 0;
   double meshColorationKernelMs = 0.0;
   double meshColorationRenderKernelMs = 0.0;  // --meshColorationDepthFromMesh: the rendering's kernels
+  // --meshMinSupportViews: the mesh that went into the trim, the views that were asked and the hipEvent time of its kernels
+  unsigned long long meshVerticesBeforeSupport = 0, meshTrianglesBeforeSupport = 0, meshSupportViews = 0;
+  double meshSupportKernelMs = 0.0;
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
@@ -106,10 +118,12 @@ bool WriteMetaImage(const std::string &path, const int pointDims[3], const doubl
 // point, appended behind the offsets; without them the file is what it always was.  With `regionIds` ([nPoints] int64) the
 // point array RegionId (Int64, one component) behind those; alone it is the section's Scalars.  With `mean` ([nPoints][3] u8),
 // `median` ([nPoints][3] u8) and `count` ([nPoints] int32), all three or none, the arrays MeanColoration, MedianColoration and
-// NbProjectedDepthMap of the Coloration tool behind every other array.
+// NbProjectedDepthMap of the Coloration tool behind every other array.  With `support` ([nPoints] int32) the point array
+// NbSupportingViews (Int32, one component) behind RegionId and before those three.
 bool WritePolyData(const std::string &path, const double *points, int64_t nPoints, const int64_t *triangles, int64_t nTriangles,
                    std::string *error, const float *normals = nullptr, double contour = 0.0, const int64_t *regionIds = nullptr,
-                   const uint8_t *mean = nullptr, const uint8_t *median = nullptr, const int32_t *count = nullptr);
+                   const uint8_t *mean = nullptr, const uint8_t *median = nullptr, const int32_t *count = nullptr,
+                   const int32_t *support = nullptr);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

@@ -49,7 +49,8 @@ extern "C" {
                            *    dmi_get_isosurface_filter_cas_retries; dmi_smooth_isosurface, dmi_get_isosurface_smooth_kernel_ms,
                            *    dmi_get_isosurface_smooth_pass_ms; dmi_decimate_isosurface, dmi_get_isosurface_decimate_kernel_ms,
                            *    dmi_get_isosurface_decimate_pass_ms; dmi_color_process_isosurface, dmi_download_isosurface_colors,
-                           *    dmi_get_isosurface_color_kernel_ms */
+                           *    dmi_get_isosurface_color_kernel_ms; dmi_filter_isosurface_support, dmi_download_isosurface_support,
+                           *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -384,6 +385,45 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
  * triangle compaction), out[3] normals.  Zeros after a call that had nothing to do.  Waits for the last call's normals. */
 int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last);
 int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]);
+
+/* Trim of the context's mesh by view support, on the device: what every TSDF pipeline does to the back shell and to the sheets
+ * between seen and unseen space that an iso-contour of the summed ray potential carries besides the surface.  Additions to ABI 5;
+ * csrc/isosurface_support.hip.  The mesh is the one the context holds: V vertices p, T triangles, and normals n (f32, widened to
+ * f64) when it carries them.  The views are all that are resident in this context, W x H each.  Definition, met bit
+ * for bit; all arithmetic is f64, every operation is rounded, there is no FMA.  View m SUPPORTS vertex v when all of these hold:
+ *   - CAMERA COORDINATES: c_r = ((RT[4r]*x + RT[4r+1]*y) + RT[4r+2]*z) + RT[4r+3] for r = 0, 1, 2;
+ *   - PROJECTION: h_r = ((K[4r]*c_0 + K[4r+1]*c_1) + K[4r+2]*c_2) + K[4r+3], the fusion's own projection order;
+ *   - IN FRONT OF THE CAMERA: c_2 > 0;
+ *   - PIXEL: u = h_0/h_2, v = h_1/h_2, px = round(u), py = round(v) with half away from zero; a non-finite u or v, or one of
+ *     magnitude >= 2^31, is outside the image; then 0 <= px < W and 0 <= py < H;
+ *   - DEPTH: d is view m's resident fusion depth at image pixel (px, py), widened to f64 -- the value dmi_color_process_isosurface's
+ *     fused test reads: -1 where the best cost exceeded the threshold, the f32-rounded value under a forced DMI_DEPTH_F32 -- and
+ *     the test is d > 0 and fabs(c_2 - d) <= tolerance, the difference rounded; NaN, -1 and infinite depths reject the pair;
+ *   - FACING, only if require_facing != 0: m_r = (RT[4r]*n_0 + RT[4r+1]*n_1) + RT[4r+2]*n_2, s = (m_0*c_0 + m_1*c_1) + m_2*c_2, and
+ *     the pair counts iff s < 0: the normal, which points from inside to outside, points towards the camera; a NaN or zero s rejects.
+ * support[v] is the number of supporting views, an int32.  The filter:
+ *   - triangle (a, b, c) survives iff all three ids are < V and min(support[a], support[b], support[c]) >= min_views;
+ *   - a vertex survives iff a surviving triangle names it: the result has no unreferenced vertex;
+ *   - survivors keep ascending old id and original triangle order; positions and normals are copied bit for bit;
+ *   - min_views == 0 changes nothing in the mesh and only computes the counts; min_views > the number of views leaves (0, 0) and
+ *     is a success; the counts depend only on position and normal, so the filter is idempotent for the same arguments.
+ * Returns the mesh's sizes after the call.  After a call that removes anything the colours are dropped and
+ * dmi_download_isosurface_regions is refused until a component filter runs again, as after a decimation.  Results are built in the
+ * alternates and swapped in last: a call that fails leaves the mesh, normals, regions, colours and any earlier support array
+ * exactly as they were.  DMI_ERR_INVALID_ARGUMENT: null pointers; min_views < 0; a NaN, infinite or negative tolerance; no
+ * successful extraction yet; require_facing on a mesh without normals; V or T >= 2^32.  DMI_ERR_STATE: no views resident.  An
+ * empty mesh is a success.  The checks come in this order, so an empty mesh in a context without views is DMI_ERR_STATE: the
+ * counts are about the views, and there are none.  Synchronises once. */
+int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double tolerance, int32_t require_facing, uint64_t *n_vertices,
+                                  uint64_t *n_triangles);
+/* support[V] of the last dmi_filter_isosurface_support: one count per vertex of the mesh as that call left it.  Refused
+ * (DMI_ERR_INVALID_ARGUMENT) before any such call and after anything that has changed the mesh since: an extraction, the component
+ * filter, a smoothing with iterations > 0 or a decimation -- as the colours are dropped. */
+int dmi_download_isosurface_support(dmi_context *ctx, int32_t *support);
+/* hipEvent time of all kernels of the last dmi_filter_isosurface_support, and pass by pass: out[0] counts, out[1] triangle flags,
+ * marks and scans, out[2] compaction.  Zeros for the passes a call did not run (min_views == 0: the counts only). */
+int dmi_get_isosurface_support_kernel_ms(dmi_context *ctx, double *last);
+int dmi_get_isosurface_support_pass_ms(dmi_context *ctx, double out[3]);
 
 /* Diagnostic: how many (8 x 8 x column brick, view) pairs of the last dmi_fuse were proven to be handled
  * uniformly.  out[0] mixed (per-voxel path), out[1] all voxels accumulate -eta*rho, out[2] all accumulate 0,

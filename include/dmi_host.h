@@ -125,7 +125,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * dmi_color_context in the same pass that reads the depths, the mesh is extracted in the context that fused (its views stay
  * resident) and coloured last by dmi_color_process_isosurface -- with --meshColorationDepthTolerance T the fused visibility
  * test -- and the file is dmi_write_polydata_with_colors'.  A view without a UInt8 x 3 Color array of the views' size ends the
- * run non-zero with the file's name. */
+ * run non-zero with the file's name.  With --meshMinSupportViews N --meshSupportDepthTolerance T (one device) the mesh is extracted
+ * in the context that fused and trimmed by dmi_filter_isosurface_support before the component flags; --meshSupportArray writes the
+ * final mesh's counts as the Int32 point array NbSupportingViews, behind RegionId and before the colours. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of

@@ -1,0 +1,56 @@
+// Host stand-in for the few HIP names csrc/isosurface_support.hip uses, so that its kernels compile as plain C++ and run as loops
+// on the CPU under AddressSanitizer and UBSan (tests/test_isosurface_support_host.py).  A launch visits every (block, thread) in
+// turn; an atomic add is a plain add; the reciprocal seed is 1.0 / x (the kernel checks whatever seed it gets); a scalar load is
+// a load.  What this cannot show: the device's division, its scalar loads, visibility between workgroups.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#define __device__
+#define __host__
+#define __global__
+#define __forceinline__ inline
+#define __launch_bounds__(x)
+#define __restrict__
+#define address_space(x)  // (inside __attribute__(( )): an empty attribute)
+#define __builtin_amdgcn_rcp(x) (1.0 / (x))
+#define __builtin_amdgcn_readfirstlane(x) (x)
+typedef int hipError_t;
+constexpr hipError_t hipSuccess = 0;
+typedef void *hipStream_t;
+typedef void *hipEvent_t;
+struct dim3 {
+  unsigned x, y, z;
+  dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {}
+};
+struct launch_index {
+  unsigned x, y, z;
+};
+inline launch_index blockIdx, threadIdx, gridDim, blockDim;
+inline hipError_t hipGetLastError() { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) {
+  memset(p, v, n);
+  return hipSuccess;
+}
+template <typename T>
+inline T atomicAdd(T *p, T v) {
+  const T old = *p;
+  *p += v;
+  return old;
+}
+#define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...)             \
+  do {                                                                          \
+    const dim3 g_ = (grid), b_ = (block);                                       \
+    gridDim = {g_.x, g_.y, g_.z};                                               \
+    blockDim = {b_.x, b_.y, b_.z};                                              \
+    for (unsigned by_ = 0; by_ < g_.y; ++by_)                                   \
+      for (unsigned bx_ = 0; bx_ < g_.x; ++bx_)                                 \
+        for (unsigned tx_ = 0; tx_ < b_.x; ++tx_) {                             \
+          blockIdx = {bx_, by_, 0};                                             \
+          threadIdx = {tx_, 0, 0};                                              \
+          kernel(__VA_ARGS__);                                                  \
+        }                                                                       \
+  } while (0)
