@@ -96,6 +96,10 @@ DMI_UNIQUE_ID_BYTES = 128
 # the rasteriser's compile-time shape (csrc/mesh_depth_render.h: kRenderViewGroup, kRenderLaneCap), for tests that aim at its edges
 RENDER_VIEW_GROUP, RENDER_LANE_CAP = 16, 64
 
+# dmi_decimate_isosurface_placed's placements (DMI_DECIMATE_MEAN, DMI_DECIMATE_QUADRIC)
+DMI_DECIMATE_MEAN, DMI_DECIMATE_QUADRIC = 0, 1
+DECIMATE_PLACEMENTS = {"mean": DMI_DECIMATE_MEAN, "quadric": DMI_DECIMATE_QUADRIC}
+
 # every symbol include/dmi.h declares (tests/test_abi.py checks the library exports them all)
 ABI_SYMBOLS = [
     "dmi_default_options", "dmi_create", "dmi_destroy", "dmi_last_error", "dmi_add_views", "dmi_add_views_f32",
@@ -115,7 +119,7 @@ ABI_SYMBOLS = [
     "dmi_decimate_isosurface", "dmi_get_isosurface_decimate_kernel_ms", "dmi_get_isosurface_decimate_pass_ms",
     "dmi_color_process_isosurface", "dmi_download_isosurface_colors", "dmi_get_isosurface_color_kernel_ms",
     "dmi_filter_isosurface_support", "dmi_download_isosurface_support", "dmi_get_isosurface_support_kernel_ms",
-    "dmi_get_isosurface_support_pass_ms",
+    "dmi_get_isosurface_support_pass_ms", "dmi_decimate_isosurface_placed",
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
@@ -208,6 +212,8 @@ def load() -> ctypes.CDLL:
         L.dmi_decimate_isosurface.argtypes = [vp, dbl, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.dmi_get_isosurface_decimate_kernel_ms.argtypes = [vp, dp]
         L.dmi_get_isosurface_decimate_pass_ms.argtypes = [vp, dp]
+    if hasattr(L, "dmi_decimate_isosurface_placed"):
+        L.dmi_decimate_isosurface_placed.argtypes = [vp, dbl, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_filter_isosurface_support"):
         L.dmi_filter_isosurface_support.argtypes = [vp, i32, dbl, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.dmi_download_isosurface_support.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
@@ -606,13 +612,21 @@ class FusionContext:
         self._check(self._lib.dmi_get_isosurface_smooth_pass_ms(self._h, a))
         return dict(zip(("adjacency", "steps", "normals"), (float(x) for x in a)))
 
-    def decimate_isosurface(self, cell_size: float):
+    def decimate_isosurface(self, cell_size: float, placement: str = "mean"):
         """(vertices, triangles) left after vertex clustering of the context's mesh on the device with cubic cells of `cell_size`
         world units: every cluster becomes the mean of its members, collapsed and duplicate triangles and unreferenced vertices
         go; normals, if the mesh has them, become the decimated mesh's geometric ones; the regions of an earlier filter are
-        dropped (dmi_decimate_isosurface).  download_isosurface* return the decimated mesh afterwards."""
+        dropped (dmi_decimate_isosurface).  download_isosurface* return the decimated mesh afterwards.
+        placement="quadric" puts every cluster's vertex where the planes of its triangles meet instead (creases and corners stay;
+        the triangles are the same; dmi_decimate_isosurface_placed); any other string is a ValueError."""
+        if placement not in DECIMATE_PLACEMENTS:
+            raise ValueError(f"decimate_isosurface: placement {placement!r} is not one of {sorted(DECIMATE_PLACEMENTS)}")
         nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._check(self._lib.dmi_decimate_isosurface(self._h, float(cell_size), ctypes.byref(nv), ctypes.byref(nt)))
+        if placement == "mean":
+            self._check(self._lib.dmi_decimate_isosurface(self._h, float(cell_size), ctypes.byref(nv), ctypes.byref(nt)))
+        else:
+            self._check(self._lib.dmi_decimate_isosurface_placed(self._h, float(cell_size), DECIMATE_PLACEMENTS[placement],
+                                                                 ctypes.byref(nv), ctypes.byref(nt)))
         self._mesh_counts = (int(nv.value), int(nt.value), 0)
         return int(nv.value), int(nt.value)
 
@@ -1334,7 +1348,7 @@ class CliOptionsC(ctypes.Structure):
                 ("mesh_smooth_lambda", ctypes.c_double), ("mesh_smooth_mu", ctypes.c_double),
                 ("mesh_decimate_cell_size", ctypes.c_double), ("mesh_coloration", ctypes.c_int32),
                 ("mesh_coloration_fused", ctypes.c_int32), ("mesh_coloration_depth_tolerance", ctypes.c_double),
-                ("mesh_coloration_depth_from_mesh", ctypes.c_int32)]
+                ("mesh_coloration_depth_from_mesh", ctypes.c_int32), ("mesh_decimate_quadric", ctypes.c_int32)]
 
 
 def cli_read_arguments(args):

@@ -549,14 +549,19 @@ uint64_t decimate_bins(double lo, double hi, double h) {
   const double q = std::floor((hi - lo) / h);
   return q < 2097152.0 ? (uint64_t)q + 1 : 0;
 }
-}  // namespace
 
-int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vertices, uint64_t *n_triangles) {
-  return guarded(ctx, "dmi_decimate_isosurface", [&]() -> int {
-  const std::string entry = "dmi_decimate_isosurface";
+// both entries: `name` is the one the messages speak of
+int decimate_isosurface(dmi_context *ctx, const char *name, double cell_size, int32_t placement, uint64_t *n_vertices,
+                        uint64_t *n_triangles) {
+  return guarded(ctx, name, [&]() -> int {
+  const std::string entry = name;
   if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
   if (!(cell_size > 0.0) || cell_size - cell_size != 0.0)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": cell_size is not a finite number > 0");
+  if (placement != DMI_DECIMATE_MEAN && placement != DMI_DECIMATE_QUADRIC)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                entry + ": placement " + std::to_string(placement) + " is neither DMI_DECIMATE_MEAN nor DMI_DECIMATE_QUADRIC");
+  const bool quadric = placement == DMI_DECIMATE_QUADRIC;
   dmi_context::Mesh &mesh = ctx->mesh;
   dmi_context::Decimation &dc = ctx->decimation;
   dmi_context::Smoothing &sm = ctx->smoothing;
@@ -565,6 +570,8 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   // ids are u32 on the device: refused, never wrapped
   if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  if (quadric && 3 * nt >= (uint64_t(1) << 32))  // ... nor are the corner indices 3t + e
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit corner indices (3 T >= 2^32)");
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
   int rc = drain_decimation(ctx);  // (the events are about to be recorded again)
   if (rc != DMI_OK) return rc;
@@ -579,12 +586,13 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   }
   const bool normals = mesh.has_normals;
   size_t temp_bytes = 0, normals_temp_bytes = 0;
-  DMI_HIP(ctx, dmi::decimate_temp_bytes(nv, nt, &temp_bytes));
+  DMI_HIP(ctx, dmi::decimate_temp_bytes(nv, nt, quadric ? dmi::kDecimateQuadric : dmi::kDecimateMean, &temp_bytes));
   if (normals) DMI_HIP(ctx, dmi::smooth_temp_bytes(nv, nt, &normals_temp_bytes));  // (the decimated mesh is no larger)
   temp_bytes = std::max<size_t>(std::max(temp_bytes, normals_temp_bytes), 16);
   // the result's buffers (the component filter's alternates), the vertex keys, then the triangle keys and values, then the
-  // incidence of the normals (the smoother's key arrays), the per-vertex and per-triangle u32 arrays, rocPRIM's own storage
-  const uint64_t n_keys = std::max<uint64_t>(std::max(nv, 2 * nt), normals ? 3 * nt : 0);
+  // incidence of the normals (the smoother's key arrays), the per-vertex and per-triangle u32 arrays, rocPRIM's own storage; the
+  // quadric placement's corner pairs and their sort's other halves are 3T u64 in each key array too
+  const uint64_t n_keys = std::max<uint64_t>(std::max(nv, 2 * nt), normals || quadric ? 3 * nt : 0);
   rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&mesh.alt_triangles, std::max<uint64_t>(nt, 1) * kTriangleBytes},
                             {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&sm.keys, 2 * n_keys * 8},
                             {&dc.vertex_scratch, 8 * (nv + 1) * 4}, {&dc.triangle_scratch, 2 * (nt + 1) * 4}, {&dc.bounds, 64},
@@ -643,7 +651,7 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
                 entry + ": more than 2^21 bins on an axis; the smallest acceptable cell size for this mesh is " + text);
   }
-  DMI_HIP(ctx, dmi::launch_isosurface_decimate(m, g, s, dc.events + 2, ctx->stream));
+  DMI_HIP(ctx, dmi::launch_isosurface_decimate(m, g, s, quadric ? dmi::kDecimateQuadric : dmi::kDecimateMean, dc.events + 2, ctx->stream));
   uint32_t kept[2] = {0, 0};
   DMI_HIP(ctx, hipMemcpyAsync(&kept[0], s.cmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipMemcpyAsync(&kept[1], s.tmap + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -672,6 +680,16 @@ int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vert
   *n_triangles = kept[1];
   return DMI_OK;
   });
+}
+}  // namespace
+
+int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vertices, uint64_t *n_triangles) {
+  return decimate_isosurface(ctx, "dmi_decimate_isosurface", cell_size, DMI_DECIMATE_MEAN, n_vertices, n_triangles);
+}
+
+int dmi_decimate_isosurface_placed(dmi_context *ctx, double cell_size, int32_t placement, uint64_t *n_vertices,
+                                   uint64_t *n_triangles) {
+  return decimate_isosurface(ctx, "dmi_decimate_isosurface_placed", cell_size, placement, n_vertices, n_triangles);
 }
 
 int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last) {

@@ -520,7 +520,8 @@ struct DecimateGrid {                // the bins, from the bounds the first pass
 };
 struct DecimateScratch {
   unsigned long long *bounds;        // [8]: lo[3] and hi[3] as order-preserving integers, the non-finite flag, unused
-  uint64_t *keys[2];                 // [max(n_vertices, 2 n_triangles)] each: the vertex keys, then the triangle keys and values
+  uint64_t *keys[2];                 // [max(n_vertices, 2 n_triangles)] each: the vertex keys, then the triangle keys and values;
+                                     // [max(that, 3 n_triangles)] for the quadric placement: then the corner pairs, u32
   uint32_t *ids[2];                  // [n_vertices] each: the vertex ids sorted with their keys
   uint32_t *head, *rank;             // [n_vertices + 1]: first of a cluster, and the inclusive scan of that
   uint32_t *cluster_of, *start;      // [n_vertices + 1]: a vertex's cluster; a cluster's first sorted position
@@ -529,14 +530,16 @@ struct DecimateScratch {
   void *temp;                        // rocPRIM's
   size_t temp_bytes;
 };
-hipError_t decimate_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
+constexpr int kDecimateMean = 0, kDecimateQuadric = 1;  // DMI_DECIMATE_MEAN, DMI_DECIMATE_QUADRIC
+hipError_t decimate_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, int placement, size_t *bytes);
 // the bounds pass: s.bounds receives the six bounds (decimate_decode_bound) and the flag; `events`: 2, recorded around it
 hipError_t launch_decimate_bounds(const DecimateMesh &m, const DecimateScratch &s, hipEvent_t *events, hipStream_t stream);
 double decimate_decode_bound(unsigned long long ordered);
 // everything else: `events`: 4, recorded before the keys, after the ranks, after the triangles and after the representatives.
-// Afterwards s.cmap[n_vertices] and s.tmap[n_triangles] hold the output's sizes.
-hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, hipEvent_t *events,
-                                      hipStream_t stream);
+// Afterwards s.cmap[n_vertices] and s.tmap[n_triangles] hold the output's sizes.  `placement` chooses the representative pass
+// on the host: the mean's launches are the same whatever else exists; the quadric one needs 3 n_triangles < 2^32.
+hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, int placement,
+                                      hipEvent_t *events, hipStream_t stream);
 
 // The trim of that mesh by view support (isosurface_support.hip).  Nothing of the input mesh is written.
 struct SupportMesh {

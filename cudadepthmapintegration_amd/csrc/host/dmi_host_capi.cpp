@@ -376,6 +376,7 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_coloration_fused = o.meshColorationDepthToleranceGiven ? 1 : 0;
   out->mesh_coloration_depth_tolerance = o.meshColorationDepthTolerance;
   out->mesh_coloration_depth_from_mesh = o.meshColorationDepthFromMesh ? 1 : 0;
+  out->mesh_decimate_quadric = o.meshDecimateQuadric ? 1 : 0;
   return 1;
   });
 }

@@ -161,6 +161,11 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                 "decimated mesh's geometric normals, with --meshRegionIds the components are labelled again "
                                                 "on the decimated mesh (default 0 = off; not in the reference)",
                                   into_checked_double(&o->meshDecimateCellSize, &o->meshDecimateCellSizeGiven, [](double x) { return x > 0.0; })}},
+      {"--meshDecimateQuadric", {Kind::kFlag, "with --meshDecimateCellSize: place every cell's vertex by the quadric error of the cell's "
+                                              "triangles, as vtkQuadricClustering does, instead of at the mean of its vertices: creases "
+                                              "and corners inside a cell stay sharp and convex shapes do not shrink; the triangles are the "
+                                              "same either way (not in the reference)",
+                                 into_flag(&o->meshDecimateQuadric)}},
       {"--meshColoration", {Kind::kFlag, "with --extractMesh, on one GPU: colour the mesh on the GPU where it is, last of all, from the "
                                          "Color arrays of the depth-map files (UInt8 x 3, read in the same pass as the depths), and "
                                          "write the point arrays MeanColoration, MedianColoration and NbProjectedDepthMap as the "
@@ -283,6 +288,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     }
   if (o->meshDecimateCellSizeGiven && !o->extractMesh) {
     err << "Error : --meshDecimateCellSize needs --extractMesh (the decimation belongs to the extracted mesh).\n" << HelpText();
+    return false;
+  }
+  if (o->meshDecimateQuadric && !o->meshDecimateCellSizeGiven) {
+    err << "Error : --meshDecimateQuadric needs --meshDecimateCellSize (it places the decimation's vertices).\n" << HelpText();
     return false;
   }
   if (o->meshColoration && !o->extractMesh) {
@@ -755,7 +764,8 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       if (rc == DMI_OK && o.meshDecimateCellSize > 0) {  // last: on the mesh the component flags and the smoothing left
         result->meshVerticesBeforeDecimation = nv;
         result->meshTrianglesBeforeDecimation = nt;
-        rc = dmi_decimate_isosurface(ctx, o.meshDecimateCellSize, &nv, &nt);
+        rc = o.meshDecimateQuadric ? dmi_decimate_isosurface_placed(ctx, o.meshDecimateCellSize, DMI_DECIMATE_QUADRIC, &nv, &nt)
+                                   : dmi_decimate_isosurface(ctx, o.meshDecimateCellSize, &nv, &nt);
         if (rc == DMI_OK) rc = dmi_get_isosurface_decimate_kernel_ms(ctx, &result->meshDecimateKernelMs);
         if (rc == DMI_OK && o.meshRegionIds) {  // a cluster may have joined components: RegionId is labelled anew, nothing dropped
           uint64_t found = 0, kept = 0;
@@ -847,7 +857,8 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       log << "mesh smoothing: " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
           << "; " << result->meshSmoothKernelMs << " ms of GPU kernels" << std::endl;
     if (o.meshDecimateCellSize > 0)
-      log << "mesh decimation: cell size " << o.meshDecimateCellSize << "; " << result->meshVerticesBeforeDecimation << " vertices, "
+      log << "mesh decimation: cell size " << o.meshDecimateCellSize << (o.meshDecimateQuadric ? ", quadric placement" : "") << "; "
+          << result->meshVerticesBeforeDecimation << " vertices, "
           << result->meshTrianglesBeforeDecimation << " triangles before, " << result->meshVertices << " vertices, "
           << result->meshTriangles << " triangles after; " << result->meshDecimateKernelMs << " ms of GPU kernels" << std::endl;
     if (o.meshColoration) {
@@ -892,7 +903,8 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
       out << "  mesh smoothing  " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
           << ", " << result->meshSmoothKernelMs << " ms of GPU kernels\n";
     if (o.meshDecimateCellSize > 0)  // (only with --extractMesh)
-      out << "  mesh decimation  cell size " << o.meshDecimateCellSize << ", " << result->meshVerticesBeforeDecimation << " vertices, "
+      out << "  mesh decimation  cell size " << o.meshDecimateCellSize << (o.meshDecimateQuadric ? ", quadric placement" : "") << ", "
+          << result->meshVerticesBeforeDecimation << " vertices, "
           << result->meshTrianglesBeforeDecimation << " triangles before, " << result->meshVertices << " vertices, "
           << result->meshTriangles << " triangles after, " << result->meshDecimateKernelMs << " ms of GPU kernels\n";
     if (o.meshColoration) {  // (only with --extractMesh)

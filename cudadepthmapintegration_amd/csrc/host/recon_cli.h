@@ -14,7 +14,8 @@
 // would do) runs dmi_smooth_isosurface on the device after the component flags; with --meshNormals the Normals written are then
 // the smoothed mesh's geometric ones.  --meshDecimateCellSize v (not in the reference: what a vtkQuadricClustering or a
 // vtkCleanPolyData behind those would do) runs dmi_decimate_isosurface last, before the downloads; with --meshRegionIds the
-// labelling then runs again on the decimated mesh.  --meshMinSupportViews N with --meshSupportDepthTolerance T (not in the reference:
+// labelling then runs again on the decimated mesh; with --meshDecimateQuadric it is dmi_decimate_isosurface_placed with the quadric
+// placement.  --meshMinSupportViews N with --meshSupportDepthTolerance T (not in the reference:
 // the trim by observation support of every TSDF pipeline) runs dmi_filter_isosurface_support right after the extraction, before the
 // component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
@@ -74,6 +75,9 @@ struct Options {
   bool meshSupportNoFacing = false, meshSupportArray = false;
   // not in the reference: which GPU(s); several = dmi_multi_* (FusionDriver::SetDevices)
   std::vector<int> devices;
+  // not in the reference (needs --meshDecimateCellSize): the decimation places its vertices by quadric error
+  // (dmi_decimate_isosurface_placed, DMI_DECIMATE_QUADRIC) instead of at the mean
+  bool meshDecimateQuadric = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).

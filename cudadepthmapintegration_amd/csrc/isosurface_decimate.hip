@@ -24,6 +24,11 @@
 //   compaction  a lane per triangle writes the survivor, ids renumbered, stored order kept
 //   representatives  a lane per marked cluster walks its members in order (loads batched by four, additions in order) and
 //               writes the mean at the cluster's output number
+//   quadric     (DMI_DECIMATE_QUADRIC only, in place of the pass above and timed as it) a lane per corner 3t + e writes (cluster of
+//               tris[t][e], 3t + e) as u32 pairs; one stable sort over the cluster bits: a cluster's corners are a run, ascending
+//               in corner index.  A lane per marked cluster forms the mean as above, finds its run by two binary searches, adds
+//               the corners' plane quadrics about the mean in that order, solves the regularised 3x3 system by cofactors, clamps
+//               to the cluster's cell and writes at the cluster's output number
 //   normals     the smoother's incidence build and kernel on the output (launch_isosurface_geometric_normals), by the caller
 #include <algorithm>
 
@@ -197,15 +202,10 @@ __global__ __launch_bounds__(kBlock) void decimate_compact_triangles_kernel(cons
   for (int e = 0; e < 3; ++e) out[3 * w + e] = (int64_t)cmap[cluster_of[tris[3 * t + e]]];
 }
 
-// A lane per cluster; the members' rows are gathered four at a time (the loads of a batch are independent of each other, the
-// additions are not) and added in ascending id, the first one starting the sum.  n_clusters: *rank_last, on the device.
-__global__ __launch_bounds__(kBlock) void decimate_representatives_kernel(const double *__restrict__ p, const uint32_t *__restrict__ ids,
-                                                                          const uint32_t *__restrict__ start, const uint32_t *__restrict__ mark,
-                                                                          const uint32_t *__restrict__ cmap, const uint32_t *__restrict__ rank_last,
-                                                                          double *__restrict__ out) {
-  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (c >= *rank_last || !mark[c]) return;
-  const uint32_t lo = start[c], k = start[c + 1] - lo;
+// The mean of the k members of a cluster whose first sorted position is lo: the members' rows are gathered four at a time (the
+// loads of a batch are independent of each other, the additions are not) and added in ascending id, the first one starting the sum.
+__device__ __forceinline__ void cluster_mean(const double *__restrict__ p, const uint32_t *__restrict__ ids, uint32_t lo, uint32_t k,
+                                             double o[3]) {
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   for (uint32_t j = 0; j < k; j += 4) {
     double q[4][3];
@@ -230,10 +230,128 @@ __global__ __launch_bounds__(kBlock) void decimate_representatives_kernel(const 
     }
   }
   const double n = (double)k;
+  o[0] = s0 / n;
+  o[1] = s1 / n;
+  o[2] = s2 / n;
+}
+
+// A lane per cluster writes the mean of its members.  n_clusters: *rank_last, on the device.
+__global__ __launch_bounds__(kBlock) void decimate_representatives_kernel(const double *__restrict__ p, const uint32_t *__restrict__ ids,
+                                                                          const uint32_t *__restrict__ start, const uint32_t *__restrict__ mark,
+                                                                          const uint32_t *__restrict__ cmap, const uint32_t *__restrict__ rank_last,
+                                                                          double *__restrict__ out) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= *rank_last || !mark[c]) return;
+  const uint32_t lo = start[c];
+  double o[3];
+  cluster_mean(p, ids, lo, start[c + 1] - lo, o);
   const uint64_t w = cmap[c];
-  out[3 * w] = s0 / n;
-  out[3 * w + 1] = s1 / n;
-  out[3 * w + 2] = s2 / n;
+  out[3 * w] = o[0];
+  out[3 * w + 1] = o[1];
+  out[3 * w + 2] = o[2];
+}
+
+// DMI_DECIMATE_QUADRIC.  A lane per corner 3t + e: the cluster of tris[t][e] and the corner's index; a triangle that names an id
+// >= V has no corners: theirs get a key above every cluster number (a cluster number is below V < 2^B - 1).
+__global__ __launch_bounds__(kBlock) void decimate_corner_keys_kernel(const int64_t *__restrict__ tris, uint64_t n_corners,
+                                                                      uint64_t n_vertices, const uint32_t *__restrict__ cluster_of,
+                                                                      int id_bits, uint32_t *__restrict__ keys,
+                                                                      uint32_t *__restrict__ corners) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_corners) return;
+  const uint64_t t = i / 3, e = i - 3 * t;
+  const uint64_t a = (uint64_t)tris[3 * t], b = (uint64_t)tris[3 * t + 1], c = (uint64_t)tris[3 * t + 2];
+  uint32_t key = (uint32_t)key_limit(id_bits);
+  if (a < n_vertices && b < n_vertices && c < n_vertices) key = cluster_of[e == 0 ? a : e == 1 ? b : c];
+  keys[i] = key;
+  corners[i] = (uint32_t)i;
+}
+
+// the first position of the ascending keys[0 .. n) whose key is not below x
+__device__ __forceinline__ uint32_t first_not_below(const uint32_t *__restrict__ keys, uint32_t n, uint32_t x) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (keys[mid] < x) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// A lane per cluster: the mean o as above, then the cluster's corners in ascending corner index (its run of the sorted pairs).
+// Each adds its triangle's plane n . (x - p_a) = 0, n the unnormalised cross product, as nn^T to A and n d to g with the
+// origin at o; the corners of one triangle that follow each other in the run share the gather and the cross product (the same
+// values either way).  (A + 2^-10 tr I) x = -g by cofactors, y = o + x clamped to the cluster's cell; the mean wherever the
+// definition says so.  f64, every operation rounded (-ffp-contract=off).
+__global__ __launch_bounds__(kBlock) void decimate_quadric_representatives_kernel(
+    const double *__restrict__ p, const int64_t *__restrict__ tris, const uint32_t *__restrict__ ids, const uint32_t *__restrict__ start,
+    const uint32_t *__restrict__ mark, const uint32_t *__restrict__ cmap, const uint32_t *__restrict__ rank_last,
+    const uint32_t *__restrict__ corner_keys, const uint32_t *__restrict__ corners, uint32_t n_corners, DecimateGrid grid,
+    double *__restrict__ out) {
+  const uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= *rank_last || !mark[c]) return;
+  const uint32_t lo = start[c];
+  double o[3];
+  cluster_mean(p, ids, lo, start[c + 1] - lo, o);
+  const uint32_t first = first_not_below(corner_keys, n_corners, (uint32_t)c);
+  const uint32_t last = first_not_below(corner_keys, n_corners, (uint32_t)c + 1);  // (c + 1 <= V - 1 + 1 < 2^32)
+  double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+  double n0 = 0.0, n1 = 0.0, n2 = 0.0, d = 0.0;
+  uint32_t held = 0xffffffffu;  // the triangle whose n and d are held (a triangle index is below 2^32 / 3)
+  for (uint32_t j = first; j < last; ++j) {
+    const uint32_t t = corners[j] / 3;
+    if (t != held) {
+      const uint64_t ia = (uint64_t)tris[3 * (uint64_t)t], ib = (uint64_t)tris[3 * (uint64_t)t + 1], ic = (uint64_t)tris[3 * (uint64_t)t + 2];
+      const double pa0 = p[3 * ia], pa1 = p[3 * ia + 1], pa2 = p[3 * ia + 2];
+      const double u0 = p[3 * ib] - pa0, u1 = p[3 * ib + 1] - pa1, u2 = p[3 * ib + 2] - pa2;
+      const double v0 = p[3 * ic] - pa0, v1 = p[3 * ic + 1] - pa1, v2 = p[3 * ic + 2] - pa2;
+      n0 = u1 * v2 - u2 * v1;
+      n1 = u2 * v0 - u0 * v2;
+      n2 = u0 * v1 - u1 * v0;
+      const double q0 = pa0 - o[0], q1 = pa1 - o[1], q2 = pa2 - o[2];
+      d = -((n0 * q0 + n1 * q1) + n2 * q2);
+      held = t;
+    }
+    if (j == first) {
+      a00 = n0 * n0, a01 = n0 * n1, a02 = n0 * n2, a11 = n1 * n1, a12 = n1 * n2, a22 = n2 * n2;
+      g0 = n0 * d, g1 = n1 * d, g2 = n2 * d;
+    } else {
+      a00 = a00 + n0 * n0, a01 = a01 + n0 * n1, a02 = a02 + n0 * n2, a11 = a11 + n1 * n1, a12 = a12 + n1 * n2, a22 = a22 + n2 * n2;
+      g0 = g0 + n0 * d, g1 = g1 + n1 * d, g2 = g2 + n2 * d;
+    }
+  }
+  double y[3] = {o[0], o[1], o[2]};
+  const double tr = (a00 + a11) + a22;
+  if (first < last && tr > 0.0 && tr - tr == 0.0) {
+    const double mu = 0.0009765625 * tr;  // 2^-10
+    const double m00 = a00 + mu, m11 = a11 + mu, m22 = a22 + mu, m01 = a01, m02 = a02, m12 = a12;
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const double det = (m00 * c00 + m01 * c01) + m02 * c02;
+    if (det > 0.0 && det - det == 0.0) {
+      double x[3];
+      x[0] = -(((c00 * g0 + c01 * g1) + c02 * g2) / det);
+      x[1] = -(((c01 * g0 + c11 * g1) + c12 * g2) / det);
+      x[2] = -(((c02 * g0 + c12 * g1) + c22 * g2) / det);
+      const uint64_t m = ids[lo];  // any member names the cluster's cell
+      double z[3];
+      bool nan = false;
+#pragma unroll
+      for (int e = 0; e < 3; ++e) {
+        const double b = floor((p[3 * m + e] - grid.lo[e]) / grid.h);  // as the keys pass has it
+        const double lower = grid.lo[e] + b * grid.h, upper = grid.lo[e] + (b + 1.0) * grid.h;
+        z[e] = o[e] + x[e];
+        nan |= z[e] != z[e];
+        z[e] = z[e] < lower ? lower : z[e];
+        z[e] = z[e] > upper ? upper : z[e];
+      }
+      if (!nan) y[0] = z[0], y[1] = z[1], y[2] = z[2];
+    }
+  }
+  const uint64_t w = cmap[c];
+  out[3 * w] = y[0];
+  out[3 * w + 1] = y[1];
+  out[3 * w + 2] = y[2];
 }
 
 unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
@@ -257,11 +375,23 @@ hipError_t sort_pairs(void *temp, size_t *temp_bytes, uint64_t *ka, uint64_t *kb
   return e;
 }
 
+hipError_t sort_corners(void *temp, size_t *temp_bytes, uint32_t *ka, uint32_t *kb, uint32_t *va, uint32_t *vb, uint64_t n, int bits,
+                        uint32_t **sorted_keys, uint32_t **sorted_values, hipStream_t stream) {
+  rocprim::double_buffer<uint32_t> keys(ka, kb), values(va, vb);
+  size_t bytes = *temp_bytes;
+  const hipError_t e = rocprim::radix_sort_pairs(temp, bytes, keys, values, (size_t)n, 0u, (unsigned)bits, stream);
+  if (!temp) *temp_bytes = bytes;
+  if (sorted_keys) *sorted_keys = keys.current();
+  if (sorted_values) *sorted_values = values.current();
+  return e;
+}
+
 }  // namespace
 
-// the storage rocPRIM asks for: the largest of the two sorts' and the scans' (all 64 key bits: the bins are not known yet)
-hipError_t decimate_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes) {
-  size_t a = 0, b = 0, c = 0, d = 0;
+// the storage rocPRIM asks for: the largest of the two sorts' and the scans' (all 64 key bits: the bins are not known yet), and
+// of the corner sort's where the placement is the quadric one
+hipError_t decimate_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, int placement, size_t *bytes) {
+  size_t a = 0, b = 0, c = 0, d = 0, q = 0;
   hipError_t e = sort_pairs<uint32_t>(nullptr, &a, nullptr, nullptr, nullptr, nullptr, std::max<uint64_t>(n_vertices, 1), 64, nullptr, nullptr, nullptr);
   if (e != hipSuccess) return e;
   e = sort_pairs<uint64_t>(nullptr, &b, nullptr, nullptr, nullptr, nullptr, std::max<uint64_t>(n_triangles, 1), 64, nullptr, nullptr, nullptr);
@@ -270,7 +400,10 @@ hipError_t decimate_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t
   if (e != hipSuccess) return e;
   e = rocprim::exclusive_scan(nullptr, d, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t)0,
                               (size_t)(std::max(n_vertices, n_triangles) + 1), rocprim::plus<uint32_t>(), nullptr);
-  *bytes = std::max(std::max(a, b), std::max(c, d));
+  if (e != hipSuccess) return e;
+  if (placement == kDecimateQuadric)
+    e = sort_corners(nullptr, &q, nullptr, nullptr, nullptr, nullptr, std::max<uint64_t>(3 * n_triangles, 1), 32, nullptr, nullptr, nullptr);
+  *bytes = std::max(std::max(std::max(a, b), std::max(c, d)), q);
   return e;
 }
 
@@ -293,8 +426,8 @@ hipError_t launch_decimate_bounds(const DecimateMesh &m, const DecimateScratch &
   return events ? hipEventRecord(events[1], stream) : hipSuccess;
 }
 
-hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, hipEvent_t *events,
-                                      hipStream_t stream) {
+hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, int placement,
+                                      hipEvent_t *events, hipStream_t stream) {
   const uint64_t nv = m.n_vertices, nt = m.n_triangles;
   const int id_bits = bits_for(nv);
   // the bits of the largest key, n_0 n_1 n_2 - 1 (the product is at most 2^63)
@@ -339,6 +472,21 @@ hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid 
   }
   if ((e = mark(2)) != hipSuccess) return e;
   // representatives (a lane per possible cluster: how many there are is rank[V - 1], on the device)
+  if (placement == kDecimateQuadric) {
+    // the triangle keys are no longer needed: their arrays hold the corner pairs, u32, two buffers of 3T each in either
+    const uint64_t nc = 3 * nt;
+    uint32_t *ka = reinterpret_cast<uint32_t *>(s.keys[0]), *va = reinterpret_cast<uint32_t *>(s.keys[1]), *ck = ka, *cv = va;
+    if (nc) {
+      hipLaunchKernelGGL(decimate_corner_keys_kernel, dim3(blocks(nc)), dim3(kBlock), 0, stream, m.triangles, nc, nv, s.cluster_of, id_bits, ka, va);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      bytes = s.temp_bytes;
+      if ((e = sort_corners(s.temp, &bytes, ka, ka + nc, va, va + nc, nc, id_bits, &ck, &cv, stream)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(decimate_quadric_representatives_kernel, dim3(blocks(nv)), dim3(kBlock), 0, stream, m.vertices, m.triangles, sorted_ids,
+                       s.start, s.mark, s.cmap, s.rank + (nv - 1), ck, cv, (uint32_t)nc, g, m.out_vertices);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return mark(3);
+  }
   hipLaunchKernelGGL(decimate_representatives_kernel, dim3(blocks(nv)), dim3(kBlock), 0, stream, m.vertices, sorted_ids, s.start, s.mark, s.cmap, s.rank + (nv - 1), m.out_vertices);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return mark(3);

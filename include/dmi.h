@@ -50,7 +50,8 @@ extern "C" {
                            *    dmi_get_isosurface_smooth_pass_ms; dmi_decimate_isosurface, dmi_get_isosurface_decimate_kernel_ms,
                            *    dmi_get_isosurface_decimate_pass_ms; dmi_color_process_isosurface, dmi_download_isosurface_colors,
                            *    dmi_get_isosurface_color_kernel_ms; dmi_filter_isosurface_support, dmi_download_isosurface_support,
-                           *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms */
+                           *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms;
+                           *    dmi_decimate_isosurface_placed */
 
 typedef struct dmi_context dmi_context;
 
@@ -345,7 +346,10 @@ int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last);
 int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]);
 
 /* Decimation of the context's mesh on the device by vertex clustering (Rossignac-Borrel): what a vtkQuadricClustering or, with a
- * tiny cell, a vtkCleanPolyData placed behind the contour does (only the intent is shared, not the numbers).  Additions to ABI 5;
+ * tiny cell, a vtkCleanPolyData placed behind the contour does (only the intent is shared, not the numbers).  This entry places a
+ * cluster's vertex at the mean of its members and so shares only the clustering with vtkQuadricClustering;
+ * dmi_decimate_isosurface_placed below also places it by the quadric error of the cluster's triangles, as that filter does.
+ * Additions to ABI 5;
  * csrc/isosurface_decimate.hip.  The input is the mesh the context holds: V vertices (f64 world positions p) and T triangles of
  * vertex ids -- the last extraction's, the last component filter's or the last smoothing's.  Definition, met bit
  * for bit:
@@ -380,8 +384,45 @@ int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]);
  * swapped in last.  Synchronises twice: once to learn the bounds (and to refuse), once for the counts; the normals are enqueued
  * behind the second and nothing waits for them. */
 int dmi_decimate_isosurface(dmi_context *ctx, double cell_size, uint64_t *n_vertices, uint64_t *n_triangles);
-/* hipEvent time of all kernels of the last dmi_decimate_isosurface (the sum of its passes), and pass by pass: out[0] clustering
- * (bounds, keys, sort, ranks), out[1] representatives, out[2] triangles (remap, degenerate and duplicate removal, vertex and
+/* The same decimation with the placement of the representatives chosen.  DMI_DECIMATE_MEAN is dmi_decimate_isosurface itself:
+ * the same code path, results, life cycle and timings.  DMI_DECIMATE_QUADRIC places every cluster's vertex where the planes of
+ * the cluster's triangles meet in the least-squares sense (what vtkQuadricClustering's quadric error does), so that a crease or a
+ * corner inside a cell stays one instead of being sawn off, and a convex shape does not shrink.  Everything about bounds, bins,
+ * clusters, their order, the triangle remap, the degenerate and duplicate removal, the output numbering, the normals and the
+ * regions is dmi_decimate_isosurface's, word for word: the triangle array and the vertex count of the output are identical to the
+ * mean placement's; only the representative's coordinates change.  Definition, met bit for bit by the device and
+ * by tests/isosurface_decimate_quadric_np.py; all arithmetic f64, every operation rounded, no FMA:
+ *   - CORNERS: every input triangle t whose three ids are below V has three corners 3t + e, e = 0, 1, 2; corner 3t + e belongs
+ *     to the cluster of vertex tris[t][e].  Triangles that the clustering makes degenerate or duplicate are included (a triangle
+ *     wholly inside a cell is exactly what describes the surface there, and it counts three times in its cell, as in
+ *     vtkQuadricClustering);
+ *   - PER CORNER, with o the mean representative of the corner's cluster (dmi_decimate_isosurface's value) and (a, b, c) the
+ *     triangle's stored ids: u = p[b] - p[a], v = p[c] - p[a], n = (u1*v2 - u2*v1, u2*v0 - u0*v2, u0*v1 - u1*v0), q = p[a] - o,
+ *     d = -((n0*q0 + n1*q1) + n2*q2); the corner contributes (n0*n0, n0*n1, n0*n2, n1*n1, n1*n2, n2*n2) to A and (n0*d, n1*d,
+ *     n2*d) to g.  Nothing is normalised (the weight is 4 area^2); the origin is local (o), so large world coordinates lose
+ *     nothing;
+ *   - SUMS: A and g of a cluster are its corners' contributions added left to right in ascending corner index 3t + e, the first
+ *     contribution starting the sum;
+ *   - SOLVE: tr = (A00 + A11) + A22, mu = 2^-10 * tr, M = A with mu added to its three diagonal entries; the cofactors
+ *     c00 = M11*M22 - M12*M12, c01 = M02*M12 - M01*M22, c02 = M01*M12 - M02*M11, c11 = M00*M22 - M02*M02,
+ *     c12 = M01*M02 - M00*M12, c22 = M00*M11 - M01*M01; det = (M00*c00 + M01*c01) + M02*c02;
+ *     x_r = -(((c_r0*g0 + c_r1*g1) + c_r2*g2) / det) with c_10 = c01, c_20 = c02, c_21 = c12.  The regularisation is the
+ *     deterministic stand-in for VTK's truncated SVD: directions the planes do not determine keep the mean's coordinate;
+ *   - PLACEMENT: y_d = o_d + x_d, clamped to the cluster's cell: with b_d the cluster's bin, L_d = lo_d + (double)b_d * h and
+ *     U_d = lo_d + (double)(b_d + 1) * h; y_d < L_d gives L_d, y_d > U_d gives U_d.  The representative is the mean o, all three
+ *     coordinates, when the cluster has no corner, when tr is not a finite number > 0, when det is not a finite number > 0, or
+ *     when any y_d is NaN.
+ * The quadric placement's passes (corner keys, one stable radix sort over the cluster bits, a lane per cluster) run behind the
+ * triangle pass and are timed as out[1] of dmi_get_isosurface_decimate_pass_ms.  All refusals and guarantees of
+ * dmi_decimate_isosurface hold, the messages naming this entry; besides, DMI_ERR_INVALID_ARGUMENT for a placement that is neither
+ * constant and, with DMI_DECIMATE_QUADRIC, for 3 T >= 2^32 (corner indices are u32 on the device). */
+#define DMI_DECIMATE_MEAN 0
+#define DMI_DECIMATE_QUADRIC 1
+int dmi_decimate_isosurface_placed(dmi_context *ctx, double cell_size, int32_t placement, uint64_t *n_vertices,
+                                   uint64_t *n_triangles);
+/* hipEvent time of all kernels of the last dmi_decimate_isosurface or dmi_decimate_isosurface_placed (the sum of its passes), and
+ * pass by pass: out[0] clustering (bounds, keys, sort, ranks), out[1] representatives (with the quadric placement: its corner
+ * keys, their sort and its kernel), out[2] triangles (remap, degenerate and duplicate removal, vertex and
  * triangle compaction), out[3] normals.  Zeros after a call that had nothing to do.  Waits for the last call's normals. */
 int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last);
 int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]);

@@ -110,6 +110,8 @@ typedef struct dmi_cli_options {
   double mesh_coloration_depth_tolerance; /* ... its tolerance (finite, >= 0) */
   /* (dmi_color_render_isosurface_depths, dmi.h); appended to the struct: */
   int32_t mesh_coloration_depth_from_mesh; /* --meshColorationDepthFromMesh: that test against the mesh's own rendered depth */
+  /* (dmi_decimate_isosurface_placed, dmi.h); appended to the struct: */
+  int32_t mesh_decimate_quadric;         /* --meshDecimateQuadric: the decimation places its vertices by quadric error */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -121,7 +123,8 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * with --meshRegionIds the file is dmi_write_polydata_with_arrays' with RegionId.  With --meshSmoothIterations N the mesh goes
  * through dmi_smooth_isosurface after those (the Normals of --meshNormals are then the smoothed mesh's geometric ones).  With
  * --meshDecimateCellSize v it goes through dmi_decimate_isosurface last (Normals: the decimated mesh's geometric ones; RegionId:
- * from the labelling run again on the decimated mesh).  With --meshColoration (one device) the views' Color arrays go to a
+ * from the labelling run again on the decimated mesh; with --meshDecimateQuadric dmi_decimate_isosurface_placed and the quadric
+ * placement).  With --meshColoration (one device) the views' Color arrays go to a
  * dmi_color_context in the same pass that reads the depths, the mesh is extracted in the context that fused (its views stay
  * resident) and coloured last by dmi_color_process_isosurface -- with --meshColorationDepthTolerance T the fused visibility
  * test -- and the file is dmi_write_polydata_with_colors'.  A view without a UInt8 x 3 Color array of the views' size ends the

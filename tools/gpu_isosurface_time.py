@@ -10,7 +10,10 @@ against the bytes it must move, the scratch it needs, and the numpy restatement 
 mesh for orientation.  With --decimate H (grid spacings; several may be given; a tiny H that the mesh's 2^21 bins refuse
 becomes the smallest size it accepts: the weld) it times dmi_decimate_isosurface after a fresh extraction with normals, pass by
 pass, with the counts before and after and the bytes each pass must move; --decimate-check compares with the numpy restatement
-(tests/isosurface_decimate_np.py).  With --color it times the coloration of the device mesh
+(tests/isosurface_decimate_np.py).  With --decimate-quadric every round also times dmi_decimate_isosurface_placed with the quadric
+placement, after a fresh extraction of its own, in the same process and on the same mesh: the four passes of both placements
+side by side, the quadric call's total over the mean's, and the scratch (record "quadric"; --decimate-check compares it with
+tests/isosurface_decimate_quadric_np.py too).  With --color it times the coloration of the device mesh
 (dmi_color_process_isosurface) against dmi_color_process, the fused depth test against the own-planes test, and both again after a
 decimation (color_record).  With --render-depths it times the z-buffer rasteriser (dmi_color_render_isosurface_depths) on the
 mesh, pass by pass, with the count of queued pairs, and the colouring with rendered planes next to the colouring with fused depths
@@ -19,7 +22,7 @@ run; the records in profiles/ are of the default 512).
 
     python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
                                          [--smooth 10 [--smooth-lambda 0.5] [--smooth-mu -0.53]]
-                                         [--decimate 2 [--decimate 4 ...] [--decimate-check]]
+                                         [--decimate 2 [--decimate 4 ...] [--decimate-check] [--decimate-quadric]]
 """
 import argparse
 import json
@@ -149,7 +152,8 @@ def smooth_record(ctx, a):
 def decimate_record(ctx, a):
     """The --decimate record of the context's grid at a.iso: vertex clustering with cells of a.decimate grid spacings, a.repeat
     rounds after a warm-up round.  In every round the decimation follows a fresh extraction with normals whose own kernel time is
-    taken in the same breath.  With a.decimate_check the numpy restatement runs on the raw mesh and is compared bit for bit."""
+    taken in the same breath.  With a.decimate_check the numpy restatement runs on the raw mesh and is compared bit for bit.  With
+    a.decimate_quadric the quadric placement follows in every round, on a fresh extraction of its own (rec["quadric"])."""
     import time
 
     sys.path.insert(0, os.path.join(ROOT, "tests"))   # the host alternative IS the tests' numpy restatement
@@ -167,6 +171,18 @@ def decimate_record(ctx, a):
             rec["extraction_kernel_ms"].append(ex)
             rec["kernel_ms"].append(ctx.isosurface_decimate_kernel_ms())
             rec["pass_ms"].append(ctx.isosurface_decimate_pass_ms())
+        if a.decimate_check and r == a.repeat:          # (before the quadric placement replaces the mesh)
+            got = ctx.download_isosurface() + (ctx.download_isosurface_normals(),)
+        if a.decimate_quadric:
+            if r == 0:
+                quadric = rec["quadric"] = {"kernel_ms": [], "pass_ms": [], "device_bytes_before": int(ctx.info().device_bytes)}
+            ctx.extract_isosurface_with_normals(a.iso)
+            quadric["vertices_after"], quadric["triangles_after"] = ctx.decimate_isosurface(h, "quadric")
+            if r:
+                quadric["kernel_ms"].append(ctx.isosurface_decimate_kernel_ms())
+                quadric["pass_ms"].append(ctx.isosurface_decimate_pass_ms())
+            else:
+                quadric["device_bytes_after"] = int(ctx.info().device_bytes)
     nv, nt, nv2, nt2 = rec["vertices"], rec["triangles"], rec["vertices_after"], rec["triangles_after"]
     rec["kernel_ms_min"] = min(rec["kernel_ms"])
     rec["extraction_kernel_ms_min"] = min(rec["extraction_kernel_ms"])
@@ -182,12 +198,30 @@ def decimate_record(ctx, a):
     rec["floor_ms_c2p_rate"] = {k: v / C2P_TBPS / 1e9 for k, v in floors.items()}
     # the scratch of the call, rocPRIM's own storage aside
     rec["scratch_bytes"] = 2 * max(nv, 2 * nt, 3 * nt) * 8 + 32 * (nv + 1) + 8 * (nt + 1)
+    if a.decimate_quadric:
+        quadric["kernel_ms_min"] = min(quadric["kernel_ms"])
+        for p in ("clustering", "representatives", "triangles", "normals"):
+            quadric[p + "_ms_min"] = min(q[p] for q in quadric["pass_ms"])
+        quadric["over_mean"] = quadric["kernel_ms_min"] / rec["kernel_ms_min"]
+        # its representative pass moves at least: triangles read for the corner keys, key and corner written and read; per corner
+        # a triangle's ids and three positions gathered; positions and ids read for the mean, representatives written
+        quadric["representatives_floor_bytes"] = 24 * nt + 2 * 8 * 3 * nt + 3 * nt * (24 + 72) + 28 * nv + 24 * nv2
+        quadric["representatives_floor_ms_c2p_rate"] = quadric["representatives_floor_bytes"] / C2P_TBPS / 1e9
+        # the corner pairs and their sort's other halves fill the key arrays that the normals' incidence sizes anyway (3 T u64 each)
+        quadric["scratch_bytes"] = rec["scratch_bytes"]
+        quadric["corner_pair_bytes"] = 4 * 3 * nt * 4
     if a.decimate_check:
-        got = ctx.download_isosurface() + (ctx.download_isosurface_normals(),)
         t0 = time.perf_counter()
         want = D.decimate(raw[0], raw[1], h, raw[2])
         rec["host_numpy_s"] = time.perf_counter() - t0
         rec["host_matches_gpu"] = all(w.tobytes() == g.tobytes() for w, g in zip(want, got))
+        if a.decimate_quadric:
+            import isosurface_decimate_quadric_np as Q
+            got = ctx.download_isosurface() + (ctx.download_isosurface_normals(),)
+            t0 = time.perf_counter()
+            want = Q.decimate(raw[0], raw[1], h, raw[2])
+            quadric["host_numpy_s"] = time.perf_counter() - t0
+            quadric["host_matches_gpu"] = all(w.tobytes() == g.tobytes() for w, g in zip(want, got))
     return rec
 
 
@@ -320,6 +354,8 @@ def main():
     ap.add_argument("--decimate", type=float, action="append", default=[],
                     help="also time the vertex clustering with cells of this many grid spacings (may be given several times)")
     ap.add_argument("--decimate-check", action="store_true", help="... and compare each with the numpy restatement, bit for bit")
+    ap.add_argument("--decimate-quadric", action="store_true",
+                    help="... and time the quadric placement (dmi_decimate_isosurface_placed) next to each, in the same rounds")
     ap.add_argument("--color", action="store_true", help="also time the coloration of the device mesh against dmi_color_process")
     ap.add_argument("--color-views", type=int, default=64, help="... from the scene's first this many views")
     ap.add_argument("--color-decimate", type=float, default=2.0, help="... and again after a decimation at this many grid spacings")
