@@ -1,6 +1,6 @@
 // dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
 // (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
-// filter, the smoother, the decimation, the support trim, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip has the rest.
+// filter, the smoother, the decimation, the support trim, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip and dmi_capi_fuse.hip have the rest.
 #include "dmi_context.h"
 
 #include <algorithm>
@@ -42,7 +42,7 @@ int dmi_cell_to_point(dmi_context *ctx) {
   if (!ctx) return DMI_ERR_INVALID_ARGUMENT;
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
   // an external grid can be changed by its owner (e.g. an all-reduce) without the context knowing: always recompute
-  if (ctx->c2p.valid && ctx->own_grid) return DMI_OK;
+  if (ctx->c2p.valid && ctx->volume.own_grid) return DMI_OK;
   int rc = flush_zero_fill(ctx);
   if (rc != DMI_OK) return rc;
   rc = drain_c2p(ctx);
@@ -52,7 +52,7 @@ int dmi_cell_to_point(dmi_context *ctx) {
   if (!ctx->c2p.events[0])
     for (hipEvent_t &e : ctx->c2p.events) DMI_HIP(ctx, hipEventCreate(&e));
   DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[0], ctx->stream));
-  DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, ctx->c2p.points.as<double>(),
+  DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->volume.d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, ctx->c2p.points.as<double>(),
                                          ctx->grid.cell_dims[0], ctx->grid.cell_dims[1], ctx->grid.cell_dims[2], ctx->stream));
   DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[1], ctx->stream));
   ctx->c2p.pending = true;
@@ -730,7 +730,7 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   // the maps of the compaction are u32: refused, never wrapped
   if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
-  const size_t n_views = ctx->h_maps.size();
+  const size_t n_views = ctx->views.h_maps.size();
   if (n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident (call dmi_add_views first)");
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
   if (nv == 0) {  // an empty mesh stays empty, and its counts are empty
@@ -771,9 +771,9 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   dmi::SupportViews views{};
   views.maps = sup.maps.as<dmi::MapRec>();
   views.n_views = (int)n_views;
-  views.W = ctx->W;
-  views.H = ctx->H;
-  views.depth_is_f64 = ctx->depth_f64 ? 1 : 0;
+  views.W = ctx->views.W;
+  views.H = ctx->views.H;
+  views.depth_is_f64 = ctx->views.depth_f64 ? 1 : 0;
   dmi::SupportScratch s{};
   s.support = sup.work.as<int32_t>();
   s.out_support = sup.compacted.as<int32_t>();
@@ -784,11 +784,11 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   s.scan_temp_bytes = temp_bytes;
   // (a failure from here on leaves the context's mesh, its normals, regions, colours and counts as they were: no kernel writes
   // them, and the buffers are swapped only at the end)
-  // The records as they are now (h_maps is pageable: the copy is complete for the host when the call returns).  Not ctx->d_maps:
+  // The records as they are now (h_maps is pageable: the copy is complete for the host when the call returns).  Not ctx->views.maps:
   // that array is brought up to date only by a fusion (sync_maps in dmi_capi.hip, with the tiled kernel's records and the hit
   // counters), so it lags behind views added since, and bringing it up to date from here would tie this call to the fusion's
   // bookkeeping; 208 B a view per call is the price.
-  DMI_HIP(ctx, hipMemcpyAsync(sup.maps.ptr, ctx->h_maps.data(), n_views * sizeof(dmi::MapRec), hipMemcpyHostToDevice, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(sup.maps.ptr, ctx->views.h_maps.data(), n_views * sizeof(dmi::MapRec), hipMemcpyHostToDevice, ctx->stream));
   DMI_HIP(ctx, dmi::launch_isosurface_support_counts(m, views, tolerance, facing ? 1 : 0, s, sup.events, ctx->stream));
   uint32_t kept[2] = {(uint32_t)nv, (uint32_t)nt};
   if (trim) {
@@ -877,10 +877,10 @@ int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t
       return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the tolerance must be finite and >= 0");
     if (views.depth_test)
       return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the colour context's own depth test is on (dmi_color_set_depth_test); one test at a time");
-    if (views.n_views > 0 && ((int64_t)ctx->h_maps.size() != views.n_views || ctx->W != views.W || ctx->H != views.H))
+    if (views.n_views > 0 && ((int64_t)ctx->views.h_maps.size() != views.n_views || ctx->views.W != views.W || ctx->views.H != views.H))
       return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
-                  entry + ": the fused test needs the same views in both contexts: " + std::to_string(ctx->h_maps.size()) + " of " +
-                      std::to_string(ctx->W) + " x " + std::to_string(ctx->H) + " here, " + std::to_string(views.n_views) + " of " +
+                  entry + ": the fused test needs the same views in both contexts: " + std::to_string(ctx->views.h_maps.size()) + " of " +
+                      std::to_string(ctx->views.W) + " x " + std::to_string(ctx->views.H) + " here, " + std::to_string(views.n_views) + " of " +
                       std::to_string(views.W) + " x " + std::to_string(views.H) + " in the colour context");
   }
   if (views.n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident in the colour context (MC.cxx:102-106)");
@@ -896,7 +896,7 @@ int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t
     DMI_HIP(ctx, hipEventRecord(col.events[0], ctx->stream));
     std::vector<const void *> tables;
     if (fused)
-      for (const dmi::MapRec &r : ctx->h_maps) tables.push_back(r.depth);
+      for (const dmi::MapRec &r : ctx->views.h_maps) tables.push_back(r.depth);
     dmi::DeviceColoring work{};
     work.points = mesh.vertices.as<double>();
     work.n = (int64_t)nv;
@@ -905,7 +905,7 @@ int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t
     work.count = mesh.alt_color_count.as<int32_t>();
     work.after = col.events[0];
     work.fused_tables = fused ? tables.data() : nullptr;
-    work.fused_f64 = ctx->depth_f64;
+    work.fused_f64 = ctx->views.depth_f64;
     work.fused_tol = tolerance;
     double ms = 0.0;
     rc = dmi::color_device_vertices(c, work, &ms);

@@ -2,6 +2,7 @@
 // allocation a dmi::DeviceBuffer (capacity in bytes) grown by one rule, every group with a release().  Private: never installed.
 #pragma once
 #include "coloration_kernels.h"
+#include "dmi_buffer.h"
 #include "dmi_context.h"
 #include "mesh_depth_render.h"
 

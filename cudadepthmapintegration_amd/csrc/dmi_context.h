@@ -1,9 +1,11 @@
-// dmi_context.h -- the context behind the C ABI of include/dmi.h, and the helpers its translation units share (dmi_capi.hip:
-// creation, destruction, views, fusion, grid transfer, diagnostics; dmi_capi_mesh.hip: point data and the iso-surface).  The
-// colour context (dmi_color_context.h, dmi_capi_color.hip) is built from the same DeviceBuffer, growth rule, release() parts
-// and exception guard.  Private: never installed.
+// dmi_context.h -- the context behind the C ABI of include/dmi.h, in groups, and the helpers its translation units share
+// (dmi_capi.hip: creation, destruction, views, grid transfer, info, timings, probes; dmi_capi_fuse.hip: the fusion launch and the
+// diagnostics that read it; dmi_capi_mesh.hip: point data and the iso-surface).  Every device allocation is a dmi::DeviceBuffer
+// (dmi_buffer.h, capacity in bytes) grown by one of two rules, every group has a release().  The colour context
+// (dmi_color_context.h, dmi_capi_color.hip) is built from the same parts and exception guard.  Private: never installed.
 #pragma once
 #include "../../include/dmi.h"
+#include "dmi_buffer.h"
 #include "fusion_kernels.h"
 
 #include <exception>
@@ -31,34 +33,6 @@ struct EventPair {
   bool has_mid = false;
 };
 
-// A grow-only device allocation of the context: the pointer and its capacity travel together (one std::swap exchanges two
-// buffers whole).  Grown by grow_buffer (ensure_buffer), freed by its group's release(); owns nothing by itself.
-struct DeviceBuffer {
-  void *ptr = nullptr;
-  uint64_t capacity = 0;  // bytes
-  template <typename T>
-  T *as() const { return static_cast<T *>(ptr); }
-};
-
-inline bool holds(const DeviceBuffer &buffer, uint64_t bytes) { return buffer.ptr && buffer.capacity >= bytes; }
-// The growth rule of every context: a buffer that holds `bytes` is kept, any other is freed and allocated at exactly `bytes`; the
-// old contents are not kept.  A failure leaves it empty with capacity 0, so that the next call allocates again.
-inline hipError_t grow_buffer(DeviceBuffer &buffer, uint64_t bytes) {
-  if (holds(buffer, bytes)) return hipSuccess;
-  hipError_t e = buffer.ptr ? hipFree(buffer.ptr) : hipSuccess;
-  buffer = DeviceBuffer{};
-  if (e == hipSuccess) e = hipMalloc(&buffer.ptr, (size_t)bytes);
-  if (e == hipSuccess) buffer.capacity = bytes; else buffer.ptr = nullptr;
-  return e;
-}
-
-// what every group's release() is made of (the caller has selected the device)
-inline void free_buffers(std::initializer_list<DeviceBuffer *> buffers) {
-  for (DeviceBuffer *b : buffers) {
-    if (b->ptr) (void)hipFree(b->ptr);
-    *b = DeviceBuffer{};
-  }
-}
 template <size_t N>
 void destroy_events(hipEvent_t (&events)[N]) {
   for (hipEvent_t &e : events) {
@@ -82,68 +56,96 @@ struct dmi_context {
   hipStream_t download_stream = nullptr;  // dmi_fuse_range_download: the slabs' copies to the host
   std::vector<hipEvent_t> slab_events;    // ... and what each waits for
 
-  void *d_grid = nullptr;
-  bool own_grid = false;
-  std::vector<uint8_t> layer_is_zero;  // per cell layer: known to hold +0.0 everywhere (reset, not fused since)
-  bool zero_fill_pending = false;  // reset requested, memset deferred: the next fuse overwrites every voxel
-  // No voxel of the (context-owned) grid is -0.0: true after a reset and preserved by every fusion -- a sum that is not -0.0 never
-  // becomes one (x + y is -0.0 only when both are; a non-zero f64 sum does not round to zero) -- so the +0.0 adds of voxels far
-  // behind every surface stay unobservable from one dmi_fuse_range to the next, not only in the first (round 4: the chunked
-  // fusion of the drop-in filter ran its later chunks at half speed).  False once the caller has uploaded a grid, and for a
-  // caller-owned grid (whoever owns it may write anything between two calls).
-  bool grid_free_of_negative_zero = false;
-  uint32_t *d_voxel_hits = nullptr;
-  unsigned long long *d_map_hits = nullptr;
-  size_t map_hits_capacity = 0;
-
-  int32_t W = 0, H = 0;
-  bool depth_f64 = false;
   bool finite_bounded = true;  // grid descriptor magnitudes allow the K shortcuts
-  int k_mode = dmi::K_PINHOLE;          // the least structured K among the resident views (dmi_info)
-  std::vector<uint8_t> view_k_mode;     // per view: dmi::KMode of its K
-  std::vector<uint8_t> view_tile_ok;    // per view: meets the tiled kernel's per-view preconditions (make_tile_rec)
-  std::vector<dmi::Batch> batches;
-  std::vector<dmi::MapRec> h_maps;
-  dmi::MapRec *d_maps = nullptr;
-  size_t d_maps_capacity = 0;
-  bool maps_dirty = false;
 
-  // tiled kernel (fusion_tile.hip): per-map records, the r22*wz(k) table, a device copy of FuseArgs
-  std::vector<dmi::TileMapRec> h_tile_maps;
-  dmi::TileMapRec *d_tile_maps = nullptr;
-  std::vector<dmi::WinRec> h_win_recs;  // per view: what the window form of the FREE column reads (one line each)
-  dmi::WinRec *d_win_recs = nullptr;
-  std::vector<dmi::FootRec> h_foot_recs;  // per view: the brick's corners relative to its first voxel (window_origin_kernel)
-  dmi::FootRec *d_foot_recs = nullptr;
-  double *d_cz_table = nullptr;
-  size_t cz_table_capacity = 0;  // doubles
-  dmi::FuseArgs *d_fuse_args = nullptr;
-  double max_tile_err = 0.0;     // largest TileMapRec::err among the resident views
-  bool last_fuse_tiled = false;
-  bool last_fuse_classes = false;
-  int64_t last_class_bricks = 0;  // wave bricks of the last fuse
-  int32_t last_bricks_z = 0, last_tk = 0;
-  const dmi::WinPair *last_win_origin = nullptr;  // the last tiled launch's pair table (nullptr: it had no windows)
-  int32_t last_class_pitch = 0, last_first = 0, last_count = 0;
-  dmi::PyramidDesc pyramid{};    // geometry of every view's depth min/max pyramid
-  uint8_t *d_zero_row = nullptr;  // one row of BRICK_MIXED bytes: the class table of a fuse without classes
-  size_t zero_row_capacity = 0;
-  uint8_t *d_classes = nullptr;  // brick classes [wave bricks][class_pitch], then the coarse table [boxes][class_pitch]
-  size_t coarse_offset = 0;      // byte offset of the coarse table within d_classes (last fuse)
-  size_t classes_capacity = 0;   // bytes
-  int32_t *d_queue_heads = nullptr;          // TileArgs::queue_heads (128 ints)
-  unsigned long long *d_wg_times = nullptr;  // tuning builds: TileArgs::wg_times of the last tiled fuse
-  size_t wg_times_blocks = 0;
+  // ---- fusion (dmi_capi.hip, dmi_capi_fuse.hip): every capacity is in bytes ----
+  struct Views {  // the resident views: their store, their records, the staging of an upload
+    int32_t W = 0, H = 0;
+    bool depth_f64 = false;
+    int k_mode = dmi::K_PINHOLE;          // the least structured K among the resident views (dmi_info)
+    std::vector<uint8_t> view_k_mode;     // per view: dmi::KMode of its K
+    std::vector<uint8_t> view_tile_ok;    // per view: meets the tiled kernel's per-view preconditions (make_tile_rec)
+    double max_tile_err = 0.0;            // largest TileMapRec::err among the resident views
+    dmi::PyramidDesc pyramid{};           // geometry of every view's depth min/max pyramid
+    // one per dmi_add_views call; allocated and freed whole by the all-or-nothing upload (upload_batch, promote_to_f64)
+    std::vector<dmi::Batch> batches;
+    // per view, on the host and -- after sync_maps -- on the device: what the general kernel reads; the tiled kernel (fusion_tile.hip);
+    // the window form of its FREE column (one line each); the brick's corners relative to its first voxel (window_origin_kernel).
+    // The four device arrays grow as a unit (max(64, 2 n) records each).
+    std::vector<dmi::MapRec> h_maps;
+    std::vector<dmi::TileMapRec> h_tile_maps;
+    std::vector<dmi::WinRec> h_win_recs;
+    std::vector<dmi::FootRec> h_foot_recs;
+    dmi::DeviceBuffer maps, tile_maps, win_recs, foot_recs;
+    bool maps_dirty = false;  // the host records have changed since they were last copied
+    dmi::DeviceBuffer stage_depth, stage_cost;  // f64 staging of an upload's depths and best costs (<= 256 MiB of host data at a time)
+    dmi::DeviceBuffer lossy;  // 3 u64: lossy narrowings, pixels without a depth, mingled strips of the upload under way
+    hipEvent_t up_events[2] = {nullptr, nullptr};  // start, stop around the upload pass's kernels (dmi_get_upload_kernel_ms)
+    double last_upload_kernel_ms = 0.0, total_upload_kernel_ms = 0.0;
+    void release() {
+      for (dmi::Batch &b : batches) {
+        (void)hipFree(b.d_depth);
+        (void)hipFree(b.d_pyramid);
+      }
+      batches.clear();
+      dmi::free_buffers({&maps, &tile_maps, &win_recs, &foot_recs, &stage_depth, &stage_cost, &lossy});
+      dmi::destroy_events(up_events);
+    }
+  } views;
+  struct Hits {  // dmi_options::count_hits
+    dmi::DeviceBuffer voxel;  // u32 per voxel
+    dmi::DeviceBuffer map;    // u64 per view, max(64, 2 n) of them; keeps its counts when it grows
+    void release() { dmi::free_buffers({&voxel, &map}); }
+  } hits;
+  struct Volume {  // the grid's voxels
+    void *d_grid = nullptr;    // owned.ptr, or the caller's dmi_options::external_grid
+    dmi::DeviceBuffer owned;
+    bool own_grid = false;
+    std::vector<uint8_t> layer_is_zero;  // per cell layer: known to hold +0.0 everywhere (reset, not fused since)
+    bool zero_fill_pending = false;  // reset requested, memset deferred: the next fuse overwrites every voxel
+    // No voxel of the (context-owned) grid is -0.0: true after a reset and preserved by every fusion -- a sum that is not -0.0 never
+    // becomes one (x + y is -0.0 only when both are; a non-zero f64 sum does not round to zero) -- so the +0.0 adds of voxels far
+    // behind every surface stay unobservable from one dmi_fuse_range to the next, not only in the first (round 4: the chunked
+    // fusion of the drop-in filter ran its later chunks at half speed).  False once the caller has uploaded a grid, and for a
+    // caller-owned grid (whoever owns it may write anything between two calls).
+    bool grid_free_of_negative_zero = false;
+    dmi::DeviceBuffer convert;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
+    void release() {
+      dmi::free_buffers({&owned, &convert});
+      d_grid = nullptr;
+    }
+  } volume;
   // slot enumeration of the tiled kernel (TileArgs::sb_perm), one table per slab geometry seen (the z-slabs of a
   // multi-GPU fusion come round again every step)
   struct SlotPerm {
     int32_t super_x, super_y, super_z, zmajor;
-    int32_t *d_perm;
+    dmi::DeviceBuffer perm;
   };
-  std::vector<SlotPerm> slot_perms;
-  uint8_t *d_order_level = nullptr;  // workgroup order: scratch levels, order[], count
-  int32_t *d_order = nullptr;
-  size_t order_capacity = 0;     // slots
+  struct LaunchTables {  // what a tiled launch reads beside the views; queued launches may read them: grown by ensure_idle_buffers
+    dmi::DeviceBuffer cz_table;   // the r22*wz(k) table, then the sums of n free-space constants; allocated at twice the need
+    dmi::DeviceBuffer fuse_args;  // a device copy of FuseArgs
+    dmi::DeviceBuffer zero_row;   // one row of BRICK_MIXED bytes: the class table of a fuse without classes
+    dmi::DeviceBuffer classes;    // brick classes [wave bricks][class_pitch], then the coarse table [boxes][class_pitch], then the window pairs
+    size_t coarse_offset = 0;     // byte offset of the coarse table within classes (last fuse)
+    dmi::DeviceBuffer queue_heads;  // TileArgs::queue_heads (128 ints)
+    dmi::DeviceBuffer wg_times;     // tuning builds: TileArgs::wg_times of the last tiled fuse
+    size_t wg_times_blocks = 0;
+    std::vector<SlotPerm> slot_perms;
+    dmi::DeviceBuffer order, order_level;  // workgroup order: count and order[]; scratch levels.  Grown as a unit
+    void release() {
+      for (SlotPerm &sp : slot_perms) dmi::free_buffers({&sp.perm});
+      slot_perms.clear();
+      dmi::free_buffers({&cz_table, &fuse_args, &zero_row, &classes, &queue_heads, &wg_times, &order, &order_level});
+    }
+  } tables;
+  struct LastLaunch {  // what the diagnostics read (dmi_get_brick_class_histogram ...); filled by fuse_run in one place
+    bool tiled = false;
+    bool classes = false;
+    int64_t class_bricks = 0;  // wave bricks of the last fuse
+    int32_t bricks_z = 0, tk = 0;
+    const dmi::WinPair *win_origin = nullptr;  // the last tiled launch's pair table (nullptr: it had no windows)
+    int32_t class_pitch = 0, first = 0, count = 0;
+  } last;
 
   // ---- post-processing (dmi_capi_mesh.hip): every buffer is kept while large enough, every capacity is in bytes ----
   struct CellToPoint {
@@ -235,16 +237,9 @@ struct dmi_context {
     void release() { dmi::destroy_events(events); }
   } coloration;
 
-  void *d_convert = nullptr;  // staging of the grid up/downloads whose host type is not the grid's (kConvertChunk elements)
-  double *d_stage_depth = nullptr, *d_stage_cost = nullptr;
-  size_t stage_capacity = 0;  // elements per staging buffer
-  unsigned long long *d_lossy = nullptr;
-  hipEvent_t up_start = nullptr, up_stop = nullptr;  // around the upload pass's kernels (dmi_get_upload_kernel_ms)
-  double last_upload_kernel_ms = 0.0, total_upload_kernel_ms = 0.0;
-
   std::vector<dmi::EventPair> pending, pool;
   dmi_timings timings{};
-  uint64_t device_bytes = 0;
+  uint64_t device_bytes = 0;  // the sum of the capacities held, and the batches' bytes: kept by the growth helpers below
   std::string err;
 };
 
@@ -254,8 +249,23 @@ int fail(dmi_context *ctx, int code, const std::string &msg);  // records msg (c
 int drain_events(dmi_context *ctx);                            // the pending fusions' timings
 int drain_c2p(dmi_context *ctx);                               // ... and the pending cell-to-point pass's
 int flush_zero_fill(dmi_context *ctx);
+inline size_t grid_elem(const dmi_context *c) { return c->opt.grid_dtype == DMI_F64 ? 8 : 4; }
+bool grid_axis_aligned(const dmi_grid_desc &g);
+// Preconditions of the tiled kernel that do not depend on the view (the per-view part: Views::view_tile_ok)
+bool tile_eligible(const dmi_context *ctx);
+// Views [first, first + count) into the cell layers [z_first, z_first + z_count): what every fusing entry point ends in
+// (dmi_capi_fuse.hip)
+int fuse_views(dmi_context *ctx, int32_t first, int32_t count, int32_t z_first, int32_t z_count);
 // grow_buffer for a buffer of this context: device_bytes follows, a failure is recorded
 int ensure_buffer(dmi_context *ctx, DeviceBuffer &buffer, uint64_t bytes);
+// The rule for buffers that work queued on the context's stream may read (dmi::grow_idle_buffers): kept while they hold `needed`;
+// otherwise the stream is synchronised, all are freed and allocated at `allocate`, as a unit (a failure leaves all of them empty).
+// *fresh: they are new and want their fill.  In the steady state -- the same views, the same grid -- no call of the runtime.
+int ensure_idle_buffers(dmi_context *ctx, std::initializer_list<BufferGrowth> unit, bool *fresh = nullptr);
+inline int ensure_idle_buffer(dmi_context *ctx, DeviceBuffer &buffer, uint64_t needed, uint64_t allocate, bool *fresh = nullptr) {
+  return ensure_idle_buffers(ctx, {{&buffer, needed, allocate}}, fresh);
+}
+void drop_buffers(dmi_context *ctx, std::initializer_list<DeviceBuffer *> buffers);  // freed now, device_bytes follows
 struct BufferNeed {
   DeviceBuffer *buffer;
   uint64_t bytes;  // 0: not needed by this call, left as it is

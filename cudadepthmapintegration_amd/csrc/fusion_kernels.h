@@ -1,4 +1,4 @@
-// fusion_kernels.h -- device-side records and launchers shared by the C ABI (dmi_capi.hip)
+// fusion_kernels.h -- device-side records and launchers shared by the C ABI (dmi_capi.hip, dmi_capi_fuse.hip)
 // and the kernels (fusion_kernels.hip: general kernel + upload helpers; fusion_tile.hip: the
 // register-tiled kernel for axis-aligned grids and pinhole cameras).  gfx950 only.
 #pragma once
@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "fusion_launch_rules.h"  // the variant bits and the thresholds of the launch decisions
 
 struct dmi_context;  // include/dmi.h
 
@@ -30,9 +32,6 @@ struct alignas(16) DepthTile {
 // everywhere in it (a depth map after the best-cost threshold): what the coarse classification asks before it lets a box's
 // bricks inherit a per-voxel class.
 enum TileFlags : uint32_t { TILE_HAS_SENTINEL = 1, TILE_HAS_VALID = 2, TILE_HAS_NAN = 4, TILE_PART_HOLE_FREE = 8, TILE_PART_NO_VALID = 16 };
-// launches of at most this many wave bricks (the chip's SIMDs) run without brick classes (dmi_capi.hip)
-constexpr int64_t kNoClassesMaxBricks = 1024;
-constexpr int kNoClassesMaxViews = 48;  // ... and only launches of fewer views than this
 // coarse class table only: the box's bricks already hold the (BRICK_MIXED) class of the byte's low bits
 constexpr uint8_t COARSE_CHILDREN_WRITTEN = 0x80;
 
@@ -338,32 +337,10 @@ struct FuseConfig {
   int use_tile;  // host decision: the tiled kernel's preconditions hold
   int general_k; // tiled kernel: some view of the fused range has a K whose third row is not 0 0 1 0 (GENK instantiation)
   int holes;     // tiled kernel: holes scattered all over the resident views (an eighth of their 8-pixel strips hold both a hole
-                 // and a depth: maps after a best-cost threshold) -- column height and launch form (dmi_capi.hip, launch_shape)
+                 // and a depth: maps after a best-cost threshold) -- column height and launch form (fusion_launch_rules.h, launch_shape)
 };
 
-// tuning-variant bits (dmi_options::kernel_variant)
-enum VariantBits : int {
-  VAR_EXACT_DIVISION = 1,   // general kernel: no checked-reciprocal fast path
-  VAR_GENERAL_K = 2,        // general kernel: ignore K structure
-  VAR_BLOCK_SHAPE_MASK = 12,  // general kernel: bits 2..3 pick the 256-thread block shape
-  VAR_FORCE_GENERAL = 16,   // never use the tiled kernel
-  VAR_TILE_SHAPE_MASK = 0xE0,  // tiled kernel: bits 5..7 pick column height / workgroup shape
-  VAR_TILE_SHAPE_SHIFT = 5,
-  VAR_NO_BRICK_CLASSES = 256,  // tiled kernel: every (brick, map) pair takes the per-voxel path
-  VAR_SPATIAL_ORDER = 512,     // tiled kernel: workgroups in spatial order, not heaviest bricks first
-  VAR_FIXED_TILE_SHAPE = 4096,  // tiled kernel: tile-shape bits 0 mean shape 0 whatever the grid size (no automatic choice)
-  VAR_KEEP_BEHIND_ADDS = 1024,  // tiled kernel: perform the +0.0 adds of BRICK_BEHIND pairs even when they cannot matter
-  VAR_NO_INTERIOR = 2048,       // tiled kernel: full in-front / in-image tests for every mixed pair (never the INTERIOR variant)
-  VAR_XCD_RUNS = 8192,          // tiled kernel: ordered bricks dealt to the XCDs in runs (round 1) instead of one eighth of a level each
-  VAR_ZMAJOR_SLOTS = 16384,     // tiled kernel: super-bricks enumerated x fastest, then y, then z (until r03h) instead of in Z-order
-  VAR_PERSISTENT_ALWAYS = 32768,  // tiled kernel, one-wave workgroups: persistent whatever the number of views (default: from 96 views on)
-  VAR_PERSISTENT_NEVER = 65536,   // tiled kernel, one-wave workgroups: one workgroup per brick whatever the number of views
-  VAR_BRICK_CLASSES_ALWAYS = 131072,  // tiled kernel: classify and order the bricks of tiny grids too (default: not below 1025 bricks)
-  VAR_NO_WINDOWS = 262144,           // tiled kernel: the FREE column always gathers from the validity maps (no bit windows)
-  VAR_WINDOWS_ALWAYS = 524288,       // tiled kernel: bit windows whatever the depth maps look like (default: maps with scattered holes)
-  VAR_COST_ORDER = 1048576,          // tiled kernel, one-wave workgroups: bricks ordered by their number of mixed views whatever the grid's size
-  VAR_NO_COST_ORDER = 2097152        // ... never (four levels, an eighth of each per XCD, as on large grids)
-};
+// (the tuning-variant bits of dmi_options::kernel_variant, VAR_*: fusion_launch_rules.h)
 
 constexpr int kMaxColumnHeight = 16;  // the tallest column of any tile shape: what z-slab partitions must be multiples of
 // Column height (voxels along k owned by one lane) and workgroup shape of tile shape `s`.
@@ -410,10 +387,7 @@ hipError_t launch_classify_bricks(const TileArgs &args, const MapRec *maps_dev, 
 int64_t coarse_class_bytes(const TileArgs &args, int tk);
 // order[p] = slot (super_brick * 32 + brick) of the p-th workgroup, bricks with the most BRICK_MIXED pairs first;
 // level: scratch of super_x*super_y*super_z*32 bytes; wx, wy: waves per workgroup
-// slabs of up to this many bricks are fused in cost order (dmi_capi.hip).  0: by kernel_variant only -- measured at 128^3 .. 512^3
-// (profiles/r16f_form_sweep.txt) the fusion kernel gains 0-4 % from it and the two ordering launches, whose level counters are
-// atomics on 64 addresses, take 0.3 ms instead of 0.01 at 256^3
-constexpr int kCostOrderMaxSlots = 0;
+// (kCostOrderMaxSlots, the rule that picks the cost order: fusion_launch_rules.h)
 // bytes of the `level` scratch of launch_order_bricks for n_slots workgroup slots (levels + per-chunk counts)
 size_t order_scratch_bytes(size_t n_slots);
 hipError_t launch_order_bricks(const TileArgs &args, int wx, int wy, uint8_t *level, int *order, int *n_valid,

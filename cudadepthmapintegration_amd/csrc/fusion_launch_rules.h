@@ -1,0 +1,163 @@
+// fusion_launch_rules.h -- what a fusion launch looks like, decided from what the depth maps, the grid and the caller's variant
+// bits look like: plain arithmetic on integers and flags, no HIP type, so that every threshold can be checked at its boundary
+// without a GPU (tests/test_fusion_launch_host.py).  fuse_run (dmi_capi_fuse.hip) calls these and carries none of the
+// expressions itself.  Every number here was measured; the comment beside it says where.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace dmi {
+
+// launches of at most this many wave bricks (the chip's SIMDs) run without brick classes (fuse_without_classes)
+constexpr int64_t kNoClassesMaxBricks = 1024;
+constexpr int kNoClassesMaxViews = 48;  // ... and only launches of fewer views than this
+
+// tuning-variant bits (dmi_options::kernel_variant)
+enum VariantBits : int {
+  VAR_EXACT_DIVISION = 1,   // general kernel: no checked-reciprocal fast path
+  VAR_GENERAL_K = 2,        // general kernel: ignore K structure
+  VAR_BLOCK_SHAPE_MASK = 12,  // general kernel: bits 2..3 pick the 256-thread block shape
+  VAR_FORCE_GENERAL = 16,   // never use the tiled kernel
+  VAR_TILE_SHAPE_MASK = 0xE0,  // tiled kernel: bits 5..7 pick column height / workgroup shape
+  VAR_TILE_SHAPE_SHIFT = 5,
+  VAR_NO_BRICK_CLASSES = 256,  // tiled kernel: every (brick, map) pair takes the per-voxel path
+  VAR_SPATIAL_ORDER = 512,     // tiled kernel: workgroups in spatial order, not heaviest bricks first
+  VAR_FIXED_TILE_SHAPE = 4096,  // tiled kernel: tile-shape bits 0 mean shape 0 whatever the grid size (no automatic choice)
+  VAR_KEEP_BEHIND_ADDS = 1024,  // tiled kernel: perform the +0.0 adds of BRICK_BEHIND pairs even when they cannot matter
+  VAR_NO_INTERIOR = 2048,       // tiled kernel: full in-front / in-image tests for every mixed pair (never the INTERIOR variant)
+  VAR_XCD_RUNS = 8192,          // tiled kernel: ordered bricks dealt to the XCDs in runs (round 1) instead of one eighth of a level each
+  VAR_ZMAJOR_SLOTS = 16384,     // tiled kernel: super-bricks enumerated x fastest, then y, then z (until r03h) instead of in Z-order
+  VAR_PERSISTENT_ALWAYS = 32768,  // tiled kernel, one-wave workgroups: persistent whatever the number of views (default: from 96 views on)
+  VAR_PERSISTENT_NEVER = 65536,   // tiled kernel, one-wave workgroups: one workgroup per brick whatever the number of views
+  VAR_BRICK_CLASSES_ALWAYS = 131072,  // tiled kernel: classify and order the bricks of tiny grids too (default: not below 1025 bricks)
+  VAR_NO_WINDOWS = 262144,           // tiled kernel: the FREE column always gathers from the validity maps (no bit windows)
+  VAR_WINDOWS_ALWAYS = 524288,       // tiled kernel: bit windows whatever the depth maps look like (default: maps with scattered holes)
+  VAR_COST_ORDER = 1048576,          // tiled kernel, one-wave workgroups: bricks ordered by their number of mixed views whatever the grid's size
+  VAR_NO_COST_ORDER = 2097152        // ... never (four levels, an eighth of each per XCD, as on large grids)
+};
+
+// slabs of up to this many bricks are fused in cost order (cost_order).  0: by kernel_variant only -- measured at 128^3 .. 512^3
+// (profiles/r16f_form_sweep.txt) the fusion kernel gains 0-4 % from it and the two ordering launches, whose level counters are
+// atomics on 64 addresses, take 0.3 ms instead of 0.01 at 256^3
+constexpr int kCostOrderMaxSlots = 0;
+
+// What the holes of the resident depth maps look like.  `scattered` is an intermediate of the three rules it enters, kept for
+// the reader of a test's table.
+struct HoleTraits {
+  bool scattered = false;
+  bool holes = false;          // FuseConfig::holes
+  bool tall_by_holes = false;  // 16-voxel columns from 256^3 on
+  bool many_borders = false;   // windows, and 16-voxel columns
+  bool mostly_empty = false;   // 16-voxel columns from 384^3 on
+};
+
+// mingled: 8-pixel strips (a column of a tile row) with both a hole and a depth; without: pixels without a depth; strips, pixels:
+// all there are -- each summed over the resident views.
+inline HoleTraits hole_traits(unsigned long long mingled, unsigned long long without, unsigned long long strips, unsigned long long pixels) {
+  HoleTraits h;
+  // Holes SCATTERED over the depth maps (a best-cost threshold's work): from a hole density of a tenth of a per cent on,
+  // nearly every brick's footprint (600 - 1300 pixels) holds one, and the free-space pairs -- most of a fusion's pairs -- are
+  // per-voxel work (the FREE column): that decides the launch.  Measured at cfg 3 (profiles/r19m_hole_sweep.jsonl,
+  // r19n_hole_variants.jsonl; ms per fusion for 8-voxel columns / + windows / 16-voxel columns + windows):
+  //   f = 0.03 %  7.3 / 7.4 / 8.1     0.1 %  10.2 / 9.8 / 10.7     0.5 %  15.0 / 13.4 / 13.2     1 %  15.5 / 13.8 / 13.3
+  // (round 4's one bit -- an eighth of the 8-pixel strips holding both a hole and a depth, f >= 1.7 % -- left 0.5 % and 1 % at
+  // 15 ms, slower than 2 %'s 13.3).  The density is read from the share p of 8-pixel strips that hold both a hole and a depth
+  // (p ~ 8 f); holes in REGIONS (silhouettes against an empty background, patches a filter removed) have mingled strips only
+  // along their borders, many hole pixels per mingled strip, and keep the launch of maps without holes (1024^3 x 64 views of
+  // the sparse scene: 4.3 against 8.1 ms the other way).
+  h.scattered = without <= 6 * mingled;     // a scattered hole has its strip to itself; a disc of radius r has ~0.8 r pixels per border strip
+  h.holes = h.scattered && mingled * 160 > strips;    // p > 1/160 (f > 0.08 %): windows, persistent workgroups from 48 views on
+  // (1/40 until the kernel of late round 5: at f = 0.2 % and 0.3 % the 16-voxel columns then took 10.9 and 11.5 ms where the
+  // 8-voxel ones took 11.2 and 12.2, at 0.1 % a tie -- profiles/r21t_hole_variants.jsonl)
+  h.tall_by_holes = h.scattered && mingled * 80 > strips;         // p > 1/80 (f > 0.16 %): 16-voxel columns from 256^3 on
+  // holes in regions, but so many that a twenty-fifth of all strips lie on a border: windows for the free-space pairs along those
+  // borders, and 16-voxel columns.  Discs of 8-40 pixels radius (`--scene blobs`; share of mingled strips 1.7 / 2.7 / 4.8 / 8.5 %
+  // at 5 / 10 / 20 / 40 % of the image): default / windows + 16-voxel columns 6.1 / 6.2, 7.0 / 7.0, 8.5 / 8.1, 11.1 / 9.2 ms
+  // (profiles/r21v_hole_variants_blobs.jsonl; the first rule, a tenth of the strips, never fired on that scene).
+  h.many_borders = mingled * 25 > strips;
+  h.tall_by_holes = h.tall_by_holes || h.many_borders;
+  // ... and maps that are mostly EMPTY in large regions (a silhouette against nothing: a quarter of the pixels or more without a
+  // depth, the holes not mingled with depths): most (brick, view) pairs are skipped and a brick's fixed costs dominate
+  if (!h.holes) h.mostly_empty = without * 4 >= pixels && pixels > 0;
+  return h;
+}
+
+// The variant with the tile-shape bits of a launch whose caller did not pick a shape (any other launch: the variant as it is).
+// Tile shape when the caller did not pick one: grids up to 512^3 do better with 8-voxel columns at five waves per
+// SIMD (more, smaller work items and a finer brick classification: 0.65 vs 0.74 ms at 256^3 x 64 views, 11.2 vs 11.5
+// ms at 512^3 x 256), 1024^3 with 16-voxel columns (15.5 vs 17.7 ms at 1024^3 x 64: the classification of twice as
+// many bricks costs more than it saves); profiles/r01zc_*, r01zd_*, r01zi_*
+inline int with_default_tile_shape(int variant, bool tiled, const HoleTraits &h, int32_t nx, int32_t ny, int32_t nz) {
+  if (tiled && !(variant & (VAR_TILE_SHAPE_MASK | VAR_FIXED_TILE_SHAPE))) {
+    const int64_t bricks16 = (int64_t)((nx + 15) / 16) * ((ny + 15) / 16) * ((nz + 15) / 16);
+    // With holes in the depth maps (cfg.holes) most pairs are the FREE column's, whose voxels are cheap next to the set-up
+    // of a (brick, view) pair: 16-voxel columns halve the set-ups per voxel and win from 256^3 on (cfg 2 -2.7 %, 384^3 -3.7 %,
+    // cfg 3 -2.2 %, cfg 3 with VGA maps -5.6 %, cfg 4's share -5.7 %; 128^3 ties; dense cfg 3 +6.7 %: profiles/r08z_*)
+    // Mostly empty maps: 16-voxel columns from 384^3 on (sparse scene, round 4's last build: 512^3 x 256 views 2.36 -> 2.12 ms,
+    // 512^3 x 64 0.65 -> 0.57, 384^3 x 128 0.62 -> 0.59; 256^3 x 64 the other way, 0.13 -> 0.15: profiles/r18i_*, r18j_*)
+    if (bricks16 <= 32768 && !(h.tall_by_holes && bricks16 >= 4096) && !(h.mostly_empty && bricks16 >= 13824))
+      variant |= 7 << VAR_TILE_SHAPE_SHIFT;
+  }
+  return variant;
+}
+
+// wave_bricks: the 8 x 8 x column bricks of the WHOLE grid; views: those of this launch.
+// A launch of no more bricks than the chip has SIMDs (64^3 voxels in 8-voxel columns) fuses without classes: every brick
+// has a SIMD to itself, and the seven launches that classify and order the bricks take longer than the per-voxel work
+// they would save (64^3: 79 -> 49 us at 4 views, 278 -> 192 us at 64; from 96^3 on the classes win;
+// profiles/r07o_small_fusions_classes_on_off.txt).  Round 4, the preparation down to four launches: 64^3 x 4 views
+// 48 -> 40 us, x 16 73 -> 63 without classes -- and x 64 views 164 us WITH them against 201 (dense; speckle 218 / 204):
+// the rule now ends at 48 views (profiles/r16i_small_fusions_classes_on_off.txt).
+// (decided from the WHOLE grid's bricks: a slab launch of a larger grid -- dmi_fuse_slab, the overlapped exchanges of
+// dmi_multi_fuse -- keeps its classes, as the whole-grid launches the rule was calibrated on)
+inline bool fuse_without_classes(int variant, int64_t wave_bricks, int32_t views) {
+  if (variant & VAR_NO_BRICK_CLASSES) return true;
+  return !(variant & VAR_BRICK_CLASSES_ALWAYS) && wave_bricks <= kNoClassesMaxBricks && views < kNoClassesMaxViews;
+}
+
+// row pitch of the class tables: a power of two >= 64 views, so that views arriving in chunks (add, fuse, add,
+// fuse ...) change the layout -- and force a reallocation, which waits for the device -- only at doublings
+inline int32_t class_table_pitch(int32_t resident_views) {
+  int32_t pitch = 64;
+  while (pitch < resident_views) pitch *= 2;
+  return pitch;
+}
+
+// No sum of the launch can be -0.0 (the launches the kernel's ZF instantiations serve, fusion_tile.hip), and the +0.0 adds of the
+// pairs far behind every surface can be dropped (TileArgs::behind_mask):
+// +0.0 adds are no-ops unless a sum can be -0.0 (only an uploaded grid can bring one) or hits are counted
+inline bool zero_free(bool init_from_grid, bool grid_free_of_negative_zero, bool count_hits, int variant) {
+  return (!init_from_grid || grid_free_of_negative_zero) && !count_hits && !(variant & VAR_KEEP_BEHIND_ADDS);
+}
+
+// The window origins of the FREE column (TileArgs::win_origin), one word per class byte
+// (for depth maps with holes scattered all over them -- cfg.holes: what makes the FREE column the busiest one -- ; the
+// launch then runs the kernel's WIN instantiation, which pays for the window code in every column, fusion_tile.hip)
+struct WindowsQuestion {
+  bool tier1;        // DMI_TIER1 != 0: the build selects pixels in two tiers
+  bool general_k;    // FuseConfig::general_k
+  bool count_hits;
+  int variant;
+  bool holes, many_borders;  // HoleTraits
+  bool any_tier1;    // (a launch none of whose views has a window record has no window pair: the plain instantiation serves it)
+  // (and only where no sum can be -0.0 -- the launches the kernel's ZF instantiations serve, fusion_tile.hip -- and the depth
+  // tables are f32: elsewhere the FREE column keeps its gathers)
+  bool zero_free;
+  bool depth_f64;
+};
+inline bool use_windows(const WindowsQuestion &q) {
+  return q.tier1 && !q.general_k && !q.count_hits && !(q.variant & (VAR_NO_WINDOWS | VAR_NO_INTERIOR)) &&
+         (q.holes || q.many_borders || (q.variant & VAR_WINDOWS_ALWAYS)) && q.any_tier1 && q.zero_free && !q.depth_f64;
+}
+
+// waves_per_workgroup: TileShape::wx * wy; n_slots: the launch's workgroup slots.
+// Small grids (one-wave workgroups): the bricks ordered by their NUMBER of mixed views and dealt to the XCDs in short runs.
+// With a few bricks per wave the launch ends when its longest bricks do -- a brick's views are serial, ~3 us each however
+// empty the chip -- and four levels let a 30-view brick start halfway through (256^3 x 64 views: the last 0.1 of 0.35 ms
+// with under a third of the waves at work, profiles/r16b_wg_cfg2_*).  Large grids keep the four levels, an eighth of each
+// per XCD: their tail is short against the launch, and the XCDs' compact regions save L2 traffic.
+inline bool cost_order(int waves_per_workgroup, int variant, size_t n_slots) {
+  return waves_per_workgroup == 1 && !(variant & VAR_NO_COST_ORDER) && ((variant & VAR_COST_ORDER) || n_slots <= (size_t)kCostOrderMaxSlots);
+}
+
+}  // namespace dmi

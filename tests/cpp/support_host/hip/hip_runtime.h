@@ -2,6 +2,8 @@
 // on the CPU under AddressSanitizer and UBSan (tests/test_isosurface_support_host.py).  A launch visits every (block, thread) in
 // turn; an atomic add is a plain add; the reciprocal seed is 1.0 / x (the kernel checks whatever seed it gets); a scalar load is
 // a load.  What this cannot show: the device's division, its scalar loads, visibility between workgroups.
+// hipMalloc and hipFree are malloc and free -- so that AddressSanitizer sees a buffer freed twice or never -- with an allocator
+// that fails on the call a test names (tests/cpp/buffer_growth_host.cpp, for csrc/dmi_buffer.h).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -29,7 +31,27 @@ struct launch_index {
   unsigned x, y, z;
 };
 inline launch_index blockIdx, threadIdx, gridDim, blockDim;
+constexpr hipError_t hipErrorOutOfMemory = 2;
+struct hip_host_state {
+  long mallocs = 0, frees = 0, synchronizes = 0;
+  long fail_malloc_at = 0;  // the hipMalloc call (counted from 1) that fails; 0: none
+};
+inline hip_host_state hip_host;
 inline hipError_t hipGetLastError() { return hipSuccess; }
+inline hipError_t hipMalloc(void **p, size_t bytes) {
+  if (++hip_host.mallocs == hip_host.fail_malloc_at) return hipErrorOutOfMemory;
+  *p = malloc(bytes ? bytes : 1);
+  return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+inline hipError_t hipFree(void *p) {
+  ++hip_host.frees;
+  free(p);
+  return hipSuccess;
+}
+inline hipError_t hipStreamSynchronize(hipStream_t) {
+  ++hip_host.synchronizes;
+  return hipSuccess;
+}
 inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) {
   memset(p, v, n);
