@@ -122,6 +122,7 @@ ABI_SYMBOLS = [
     "dmi_get_isosurface_support_pass_ms", "dmi_decimate_isosurface_placed",
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
+    "dmi_filter_depth_consistency",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -262,6 +263,8 @@ def load() -> ctypes.CDLL:
     L.dmi_color_get_render_pass_ms.argtypes = [vp, dp]
     L.dmi_color_get_render_queued_pairs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     i64, i64p, i32p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    if hasattr(L, "dmi_filter_depth_consistency"):
+        L.dmi_filter_depth_consistency.argtypes = [dp, dp, dbl, dp, dp, i32, i32, i32, dbl, dbl, i32, i32, dp, i32p, dp]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -997,6 +1000,41 @@ def color_mesh(points, colors, K4, RT4, device: int = 0):
     return mean, median, count
 
 
+def filter_depth_consistency(views: Views, *, min_views: int, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0,
+                             threshold: float | None = None, device: int = 0, out: np.ndarray | None = None):
+    """Depth maps filtered by cross-view consistency (include/dmi.h: dmi_filter_depth_consistency): a depth is kept only where at
+    least min_views other views hold a depth within abs_tolerance + rel_tolerance * z of the same world point's camera z.
+    threshold applies views.best_cost first (best cost > threshold => -1).  Returns (Views with the filtered depths, the same cameras
+    and best_cost None; counts int32 [n, H, W]; the kernels' hipEvent time in ms).  out: where the filtered depths go; it may be
+    views.depth itself (f64, C-contiguous), which is then filtered in place."""
+    L = load()
+    d = np.ascontiguousarray(views.depth, dtype=np.float64)
+    if d.ndim != 3:
+        raise ValueError(f"views.depth must be [n, H, W], got {d.shape}")
+    n, H, W = d.shape
+    k = np.ascontiguousarray(views.K4, dtype=np.float64).reshape(-1)
+    rt = np.ascontiguousarray(views.RT4, dtype=np.float64).reshape(-1)
+    if k.size != 16 * n or rt.size != 16 * n:
+        raise ValueError("views.K4 and views.RT4 must be [n, 4, 4]")
+    bc = None
+    if threshold is not None and views.best_cost is not None:
+        bc = np.ascontiguousarray(views.best_cost, dtype=np.float64)
+        if bc.shape != d.shape:
+            raise ValueError("views.best_cost must have the shape of views.depth")
+    if out is None:
+        out = np.empty_like(d)
+    elif out.dtype != np.float64 or out.shape != d.shape or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous f64 array of the depths' shape")
+    counts = np.zeros(d.shape, dtype=np.int32)
+    ms = ctypes.c_double(0.0)
+    rc = L.dmi_filter_depth_consistency(_dp(d), None if bc is None else _dp(bc), 0.0 if threshold is None else float(threshold), _dp(k),
+                                        _dp(rt), n, W, H, float(abs_tolerance), float(rel_tolerance), int(min_views), int(device),
+                                        _dp(out), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(ms))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    return Views(out, views.K4, views.RT4, None), counts, float(ms.value)
+
+
 class ColorContext:
     """MeshColoration with resident views (dmi_color_create ... dmi_color_destroy)."""
 
@@ -1348,7 +1386,9 @@ class CliOptionsC(ctypes.Structure):
                 ("mesh_smooth_lambda", ctypes.c_double), ("mesh_smooth_mu", ctypes.c_double),
                 ("mesh_decimate_cell_size", ctypes.c_double), ("mesh_coloration", ctypes.c_int32),
                 ("mesh_coloration_fused", ctypes.c_int32), ("mesh_coloration_depth_tolerance", ctypes.c_double),
-                ("mesh_coloration_depth_from_mesh", ctypes.c_int32), ("mesh_decimate_quadric", ctypes.c_int32)]
+                ("mesh_coloration_depth_from_mesh", ctypes.c_int32), ("mesh_decimate_quadric", ctypes.c_int32),
+                ("depth_consistency_min_views", ctypes.c_int64), ("depth_consistency_tolerance", ctypes.c_double),
+                ("depth_consistency_rel_tolerance", ctypes.c_double)]
 
 
 def cli_read_arguments(args):

@@ -1,0 +1,185 @@
+// dmi_capi_consistency.hip -- dmi_filter_depth_consistency of include/dmi.h: the argument checks (all of them before the device is
+// touched), the staged upload, the launches of depth_consistency.hip and the staged download.  Context-free, like dmi_color_mesh:
+// everything the call allocates it frees before it returns.  A failure's text is dmi_last_error(NULL)'s.
+#include <stdlib.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "depth_consistency.h"
+#include "dmi_context.h"
+
+namespace {
+
+using dmi::fail;
+
+constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up and comes down in pieces of at most this, as dmi_add_views stages it
+
+bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
+
+#ifdef DMI_TUNING
+unsigned long long g_last_undecided = 0;
+#endif
+
+// what the call holds on the device and the events that time its kernels; released whatever way the call ends
+struct Holdings {
+  dmi::DeviceBuffer planes, counts, cameras, stage_depth, stage_cost, stage_count, undecided;
+  hipStream_t stream = nullptr;
+  hipEvent_t events[2] = {nullptr, nullptr};
+  ~Holdings() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    dmi::free_buffers({&planes, &counts, &cameras, &stage_depth, &stage_cost, &stage_count, &undecided});
+    for (hipEvent_t e : events)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+#define DMI_DC_HIP(call) DMI_HIP(nullptr, call)
+
+int filter(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4, int32_t n, int32_t W,
+           int32_t H, double abs_tolerance, double rel_tolerance, int32_t min_views, int32_t device, double *out_depth, int32_t *out_count,
+           double *kernel_ms) {
+  const std::string entry = "dmi_filter_depth_consistency: ";
+  auto bad = [&](const std::string &what) { return fail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!depth) return bad("depth is null");
+  if (!K4) return bad("K4 is null");
+  if (!RT4) return bad("RT4 is null");
+  if (!out_depth) return bad("out_depth is null");
+  if (n < 1) return bad("n >= 1 required");
+  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
+  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
+  if (min_views < 0) return bad("min_views >= 0 required");
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (best_cost && threshold != threshold) return bad("threshold is NaN");
+  for (int32_t m = 0; m < n; ++m) {
+    const double *K = K4 + 16 * (size_t)m;
+    const bool form = K[4] == 0.0 && K[8] == 0.0 && K[9] == 0.0 && K[10] == 1.0 && K[11] == 0.0 && K[0] != 0.0 && K[5] != 0.0 &&
+                      K[0] == K[0] && K[5] == K[5];
+    if (!form)
+      return bad("K4 of view " + std::to_string(m) + " is not of the form SetMatrixK produces (K4[1][0] == 0, third row 0 0 1 0, "
+                 "non-zero K4[0][0] and K4[1][1])");
+  }
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
+  }
+  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
+  DMI_DC_HIP(hipSetDevice(device));
+
+  dmi::ConsistencyTuning tuning;
+#ifdef DMI_TUNING
+  if (const char *v = getenv("DMI_DC_VIEW_GROUP")) tuning.view_group = atoi(v);
+  if (const char *v = getenv("DMI_DC_GATHER_AHEAD")) tuning.gather_ahead = atoi(v);
+#endif
+
+  Holdings h;
+  DMI_DC_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+  for (hipEvent_t &e : h.events) DMI_DC_HIP(hipEventCreate(&e));
+  const size_t plane = (size_t)W * H, views = (size_t)n;
+  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));
+  DMI_DC_HIP(dmi::grow_buffer(h.planes, views * plane * sizeof(double)));
+  DMI_DC_HIP(dmi::grow_buffer(h.counts, views * plane * sizeof(int32_t)));
+  DMI_DC_HIP(dmi::grow_buffer(h.cameras, views * sizeof(dmi::ConsistencyCamera)));
+  DMI_DC_HIP(dmi::grow_buffer(h.stage_depth, chunk * plane * sizeof(double)));
+  if (best_cost) DMI_DC_HIP(dmi::grow_buffer(h.stage_cost, chunk * plane * sizeof(double)));
+  if (out_count) DMI_DC_HIP(dmi::grow_buffer(h.stage_count, chunk * plane * sizeof(int32_t)));
+  unsigned long long *undecided = nullptr;
+#ifdef DMI_TUNING
+  DMI_DC_HIP(dmi::grow_buffer(h.undecided, sizeof(unsigned long long)));
+  undecided = h.undecided.as<unsigned long long>();
+  DMI_DC_HIP(hipMemsetAsync(undecided, 0, sizeof(unsigned long long), h.stream));
+#endif
+
+  double total_ms = 0.0;
+  auto add_span = [&]() -> hipError_t {  // (the stream has been synchronised behind events[1])
+    float ms = 0.f;
+    const hipError_t e = hipEventElapsedTime(&ms, h.events[0], h.events[1]);
+    if (e == hipSuccess) total_ms += (double)ms;
+    return e;
+  };
+
+  {
+    std::vector<dmi::ConsistencyCamera> cameras(views);
+    for (size_t m = 0; m < views; ++m) {
+      const double *K = K4 + 16 * m, *RT = RT4 + 16 * m;
+      for (int q = 0; q < 12; ++q) cameras[m].rt[q] = RT[q];
+      const double k[8] = {K[0], K[1], K[2], K[3], K[5], K[6], K[7], 0.0};
+      for (int q = 0; q < 8; ++q) cameras[m].k[q] = k[q];
+    }
+    DMI_DC_HIP(hipMemcpyAsync(h.cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, h.stream));
+    DMI_DC_HIP(hipStreamSynchronize(h.stream));  // `cameras` goes out of scope
+  }
+  DMI_DC_HIP(hipMemsetAsync(h.counts.ptr, 0, views * plane * sizeof(int32_t), h.stream));
+
+  // up: threshold, validity, -1 for everything else and the row flip happen in the pass that unpacks a staged piece
+  for (size_t m0 = 0; m0 < views; m0 += chunk) {
+    const size_t cnt = std::min(chunk, views - m0);
+    DMI_DC_HIP(hipMemcpyAsync(h.stage_depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    if (best_cost)
+      DMI_DC_HIP(hipMemcpyAsync(h.stage_cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    DMI_DC_HIP(hipEventRecord(h.events[0], h.stream));
+    DMI_DC_HIP(dmi::launch_consistency_upload(h.stage_depth.as<double>(), best_cost ? h.stage_cost.as<double>() : nullptr, threshold, W, H,
+                                              (int64_t)cnt, h.planes.as<double>(), (int64_t)m0, h.stream));
+    DMI_DC_HIP(hipEventRecord(h.events[1], h.stream));
+    DMI_DC_HIP(hipStreamSynchronize(h.stream));  // the stage buffers are reused by the next piece
+    DMI_DC_HIP(add_span());
+  }
+
+  // the counts: every source pixel against the target views, all in one launch or group by group
+  if (n > 1) {
+    const int group = tuning.view_group > 0 ? tuning.view_group : n;
+    DMI_DC_HIP(hipEventRecord(h.events[0], h.stream));
+    for (int t0 = 0; t0 < n; t0 += group)
+      DMI_DC_HIP(dmi::launch_consistency_count(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, t0,
+                                               std::min(n, t0 + group), abs_tolerance, rel_tolerance, tuning.gather_ahead,
+                                               h.counts.as<int32_t>(), undecided, h.stream));
+    DMI_DC_HIP(hipEventRecord(h.events[1], h.stream));
+    DMI_DC_HIP(hipStreamSynchronize(h.stream));
+    DMI_DC_HIP(add_span());
+  }
+
+  // down, through the same stage buffers
+  for (size_t m0 = 0; m0 < views; m0 += chunk) {
+    const size_t cnt = std::min(chunk, views - m0);
+    DMI_DC_HIP(hipEventRecord(h.events[0], h.stream));
+    DMI_DC_HIP(dmi::launch_consistency_finish(h.planes.as<double>(), h.counts.as<int32_t>(), W, H, (int64_t)m0, (int64_t)cnt, min_views,
+                                              h.stage_depth.as<double>(), out_count ? h.stage_count.as<int32_t>() : nullptr, h.stream));
+    DMI_DC_HIP(hipEventRecord(h.events[1], h.stream));
+    DMI_DC_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.stage_depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    if (out_count)
+      DMI_DC_HIP(hipMemcpyAsync(out_count + m0 * plane, h.stage_count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
+    DMI_DC_HIP(hipStreamSynchronize(h.stream));
+    DMI_DC_HIP(add_span());
+  }
+#ifdef DMI_TUNING
+  DMI_DC_HIP(hipMemcpy(&g_last_undecided, undecided, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+#endif
+  if (kernel_ms) *kernel_ms = total_ms;
+  return DMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmi_filter_depth_consistency(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
+                                 int32_t n, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance, int32_t min_views,
+                                 int32_t device, double *out_depth, int32_t *out_count, double *kernel_ms) {
+  return dmi::guarded(nullptr, "dmi_filter_depth_consistency", [&]() -> int {
+    return filter(depth, best_cost, threshold, K4, RT4, n, W, H, abs_tolerance, rel_tolerance, min_views, device, out_depth, out_count,
+                  kernel_ms);
+  });
+}
+
+#ifdef DMI_TUNING
+// tuning builds only (tools/gpu_depth_consistency_time.py): the pairs of the last call that pixel_fast left to pixel_exact
+unsigned long long dmi_tuning_depth_consistency_undecided(void) { return g_last_undecided; }
+#endif
+
+}  // extern "C"

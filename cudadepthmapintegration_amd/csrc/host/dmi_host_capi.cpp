@@ -377,6 +377,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_coloration_depth_tolerance = o.meshColorationDepthTolerance;
   out->mesh_coloration_depth_from_mesh = o.meshColorationDepthFromMesh ? 1 : 0;
   out->mesh_decimate_quadric = o.meshDecimateQuadric ? 1 : 0;
+  out->depth_consistency_min_views = o.depthConsistencyMinViews;
+  out->depth_consistency_tolerance = o.depthConsistencyTolerance;
+  out->depth_consistency_rel_tolerance = o.depthConsistencyRelTolerance;
   return 1;
   });
 }

@@ -12,6 +12,7 @@
 #include <fstream>
 #include <functional>
 #include <map>
+#include <memory>
 #include <ostream>
 #include <sstream>
 
@@ -206,6 +207,23 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                            "operation (needs --meshSupportDepthTolerance, works without --meshMinSupportViews; not in "
                                            "the reference)",
                               into_flag(&o->meshSupportArray)}},
+      {"--depthConsistencyMinViews", {Kind::kValue, "filter the depth maps by cross-view consistency on the GPU before they are fused: a "
+                                                    "depth stays only if at least this many other views, looking at the same world "
+                                                    "point, hold a depth that agrees with the point's distance from their camera; every "
+                                                    "other depth is dropped like one that fails --threshBestCost (a non-negative "
+                                                    "integer; 0 drops nothing).  All views are then read into host memory at once (at "
+                                                    "256 views of 1280 x 720 with costs and colours about 4.5 GB) and filtered on the "
+                                                    "first --device; the support trim and the fused test of the coloration see "
+                                                    "the filtered depths (not in the reference)",
+                                      into_count(&o->depthConsistencyMinViews)}},
+      {"--depthConsistencyTolerance", {Kind::kValue, "with --depthConsistencyMinViews: two depths agree within this distance (world "
+                                                     "units, finite, >= 0, default 0) plus the relative tolerance (not in the reference)",
+                                       into_checked_double(&o->depthConsistencyTolerance, &o->depthConsistencyToleranceGiven,
+                                                           [](double x) { return x >= 0.0; })}},
+      {"--depthConsistencyRelTolerance", {Kind::kValue, "with --depthConsistencyMinViews: ... plus this share of the distance from the "
+                                                        "other view's camera (finite, >= 0, default 0.01; not in the reference)",
+                                          into_checked_double(&o->depthConsistencyRelTolerance, &o->depthConsistencyRelToleranceGiven,
+                                                              [](double x) { return x >= 0.0; })}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -331,6 +349,16 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
       err << "Error : " << flag.first << " needs --meshMinSupportViews or --meshSupportArray.\n" << HelpText();
       return false;
     }
+  for (const auto &flag : {std::make_pair("--depthConsistencyTolerance", o->depthConsistencyToleranceGiven),
+                           std::make_pair("--depthConsistencyRelTolerance", o->depthConsistencyRelToleranceGiven)})
+    if (flag.second && o->depthConsistencyMinViews < 0) {
+      err << "Error : " << flag.first << " needs --depthConsistencyMinViews.\n" << HelpText();
+      return false;
+    }
+  if (o->depthConsistencyMinViews > 0x7fffffffLL) {
+    err << "Bad value for --depthConsistencyMinViews\n" << HelpText();
+    return false;
+  }
   // rmain:257-262
   if (!o->gridSpacing.empty() && !o->gridDims.empty()) {
     err << "Error : Spacing and dimensions can't be both set\n" << HelpText();
@@ -674,6 +702,43 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   const bool supportMesh = o.meshMinSupportViews >= 0 || o.meshSupportArray;
   const bool supportFacing = supportMesh && !o.meshSupportNoFacing;
   if (supportMesh) filter.SetKeepContext(true);
+  // --depthConsistencyMinViews: every view is read once, all are filtered on the first device, and the filter fuses them from memory
+  // (SetViews: the path that thresholds again, which changes nothing, and forwards the Color planes to the colour sink)
+  std::vector<std::unique_ptr<ReconstructionData>> consistentViews;
+  if (o.depthConsistencyMinViews >= 0) {
+    say("** Filter the depth maps by cross-view consistency...");
+    const std::vector<std::string> vtis = help::ExtractAllFilePath(vti_list.c_str()), krtds = help::ExtractAllFilePath(krtd_list.c_str());
+    if (vtis.empty() || krtds.size() < vtis.size()) {  // filt.cxx:161-165
+      result->error = "Error : There is no enough vti files, please check your vtiList.txt and krtdList.txt";
+      return 1;
+    }
+    std::vector<ReconstructionData *> views;
+    for (size_t m = 0; m < vtis.size(); ++m) {
+      consistentViews.emplace_back(new ReconstructionData(vtis[m], krtds[m]));
+      if (!consistentViews.back()->GetDepthMap()) {
+        result->error = "--depthConsistencyMinViews: cannot read depth map " + vtis[m];
+        return 1;
+      }
+      views.push_back(consistentViews.back().get());
+    }
+    DepthConsistencyReport report;
+    std::string error;
+    if (!FilterDepthConsistency(views, o.threshBestCost, (int)o.depthConsistencyMinViews, o.depthConsistencyTolerance,
+                                o.depthConsistencyRelTolerance, o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+      result->error = "--depthConsistencyMinViews: " + error;
+      return 1;
+    }
+    result->depthConsistencyViews = report.views;
+    result->depthConsistencyValidPixels = report.validPixels;
+    result->depthConsistencyKeptPixels = report.keptPixels;
+    result->depthConsistencyKernelMs = report.kernelMs;
+    std::ostringstream line;
+    line << "depth consistency: at least " << o.depthConsistencyMinViews << " of " << report.views - 1 << " other views, tolerance "
+         << o.depthConsistencyTolerance << " + " << o.depthConsistencyRelTolerance << " z; " << report.validPixels
+         << " pixels with a depth, " << report.keptPixels << " kept; " << report.kernelMs << " ms of GPU kernels";
+    say(line.str());
+    filter.SetViews(views);
+  }
   if (!filter.Update()) {
     result->error = filter.LastError().empty() ? "the reconstruction filter refused its parameters" : filter.LastError();
     return 1;
@@ -887,6 +952,11 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     for (int i = 0; i < argc; ++i) out << " " << argv[i];
     out << "\noutput volume  " << o.outputGridFilename << "\n";
     describe(o, out, false);
+    if (o.depthConsistencyMinViews >= 0)
+      out << "depth consistency\n  minimum agreeing views  " << o.depthConsistencyMinViews << "\n  tolerance  " << o.depthConsistencyTolerance
+          << " + " << o.depthConsistencyRelTolerance << " z\n  views  " << result->depthConsistencyViews << "\n  pixels with a depth  "
+          << result->depthConsistencyValidPixels << "\n  pixels kept  " << result->depthConsistencyKeptPixels << "\n  GPU kernels  "
+          << result->depthConsistencyKernelMs << " ms\n";
     if (o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
           << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";

@@ -17,7 +17,10 @@
 // labelling then runs again on the decimated mesh; with --meshDecimateQuadric it is dmi_decimate_isosurface_placed with the quadric
 // placement.  --meshMinSupportViews N with --meshSupportDepthTolerance T (not in the reference:
 // the trim by observation support of every TSDF pipeline) runs dmi_filter_isosurface_support right after the extraction, before the
-// component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.  Without --extractMesh
+// component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.
+// --depthConsistencyMinViews N with --depthConsistencyTolerance / --depthConsistencyRelTolerance (not in the reference: the geometric
+// consistency check of every depth-map fusion pipeline) reads all views into memory, filters their depths on the first device
+// (dmi_filter_depth_consistency) and fuses the filtered views through ReconstructionFilter::SetViews.  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
@@ -78,6 +81,11 @@ struct Options {
   // not in the reference (needs --meshDecimateCellSize): the decimation places its vertices by quadric error
   // (dmi_decimate_isosurface_placed, DMI_DECIMATE_QUADRIC) instead of at the mean
   bool meshDecimateQuadric = false;
+  // not in the reference: filter the depth maps by cross-view consistency on the GPU before they are fused
+  // (dmi_filter_depth_consistency: -1 = flag not given), with an absolute and a relative depth tolerance
+  long long depthConsistencyMinViews = -1;
+  double depthConsistencyTolerance = 0.0, depthConsistencyRelTolerance = 0.01;
+  bool depthConsistencyToleranceGiven = false, depthConsistencyRelToleranceGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -108,6 +116,10 @@ struct RunResult {
   // --meshMinSupportViews: the mesh that went into the trim, the views that were asked and the hipEvent time of its kernels
   unsigned long long meshVerticesBeforeSupport = 0, meshTrianglesBeforeSupport = 0, meshSupportViews = 0;
   double meshSupportKernelMs = 0.0;
+  // --depthConsistencyMinViews: the views filtered, their pixels with a depth after --threshBestCost, the pixels the filter kept
+  // and the hipEvent time of its kernels
+  unsigned long long depthConsistencyViews = 0, depthConsistencyValidPixels = 0, depthConsistencyKeptPixels = 0;
+  double depthConsistencyKernelMs = 0.0;
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.

@@ -665,6 +665,52 @@ bool FusionDriver::ProcessDepthMap(const std::vector<std::string> &vtiList, cons
   return ProcessDepthMap(n, fill, thresholdBestCost, io_scalar);
 }
 
+// Not in the reference (recon_host.h)
+bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int minViews,
+                            double absTolerance, double relTolerance, int device, DepthConsistencyReport *report, std::string *error) {
+  const size_t n = views.size();
+  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
+  if (!first) {
+    *error = "FilterDepthConsistency: no views, or view 0 has no depth map";
+    return false;
+  }
+  const int W = first->dims[0], H = first->dims[1];
+  const size_t npix = (size_t)W * H;
+  if (n > 0x7fffffffu) {
+    *error = "FilterDepthConsistency: too many views";
+    return false;
+  }
+  std::vector<double> depth(n * npix), K4(n * 16), RT(n * 16);
+  DepthConsistencyReport r;
+  r.views = n;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
+      *error = "FilterDepthConsistency: view " + std::to_string(m) + " has no depth map of the size of view 0";
+      return false;
+    }
+    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
+    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
+    std::memcpy(K4.data() + m * 16, views[m]->Get4MatrixK(), 16 * 8);
+    std::memcpy(RT.data() + m * 16, views[m]->GetMatrixTR(), 16 * 8);
+  }
+  for (const double d : depth) r.validPixels += d > 0.0 && d < HUGE_VAL ? 1 : 0;
+  const int rc = dmi_filter_depth_consistency(depth.data(), nullptr, 0.0, K4.data(), RT.data(), (int32_t)n, W, H, absTolerance, relTolerance,
+                                              minViews, device, depth.data(), nullptr, &r.kernelMs);
+  if (rc != DMI_OK) {
+    *error = dmi_last_error(nullptr);
+    return false;
+  }
+  for (const double d : depth) r.keptPixels += d > 0.0 ? 1 : 0;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage filtered = *views[m]->GetDepthMap();
+    filtered.depths.assign(depth.begin() + (ptrdiff_t)(m * npix), depth.begin() + (ptrdiff_t)((m + 1) * npix));
+    views[m]->SetDepthMap(filtered);
+  }
+  if (report) *report = r;
+  return true;
+}
+
 // ====================================================================================================
 // vtkCudaReconstructionFilter
 // ====================================================================================================

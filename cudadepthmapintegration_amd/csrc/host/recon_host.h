@@ -95,6 +95,20 @@ class ReconstructionData {
 using ViewSource = std::function<bool(size_t index, double *depth, double *best_cost, bool *has_cost, double K4[16],
                                       double RT[16], std::string *error)>;
 
+// Not in the reference: the views filtered by cross-view consistency on the GPU before they are fused (dmi_filter_depth_consistency,
+// include/dmi.h states the definition).  Every view is thresholded first (ApplyDepthThresholdFilter), then all of them are packed --
+// host memory holds every depth plane twice for the duration of the call --, filtered on `device`, and the filtered depths stored
+// back with SetDepthMap: a depth stays only where at least minViews other views hold a depth within absTolerance + relTolerance * z
+// of the same world point's camera z; everything else becomes -1.  The views must share one size and have depth maps.
+struct DepthConsistencyReport {
+  uint64_t views = 0;
+  uint64_t validPixels = 0;  // after the threshold: depths > 0 and finite
+  uint64_t keptPixels = 0;   // of those, the ones the filter kept
+  double kernelMs = 0.0;     // hipEvent time of the pass's kernels
+};
+bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int minViews,
+                            double absTolerance, double relTolerance, int device, DepthConsistencyReport *report, std::string *error);
+
 // ---- Reconstruction/CudaReconstruction.cu host driver -------------------------------------------------
 // The reference keeps the grid description in global __constant__ state between the two calls (cu:55-64);
 // here it lives in an object.  One FusionDriver = one CudaInitialize + ProcessDepthMap pair.

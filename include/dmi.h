@@ -51,7 +51,7 @@ extern "C" {
                            *    dmi_get_isosurface_decimate_pass_ms; dmi_color_process_isosurface, dmi_download_isosurface_colors,
                            *    dmi_get_isosurface_color_kernel_ms; dmi_filter_isosurface_support, dmi_download_isosurface_support,
                            *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms;
-                           *    dmi_decimate_isosurface_placed */
+                           *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency */
 
 typedef struct dmi_context dmi_context;
 
@@ -655,6 +655,45 @@ int dmi_color_get_render_kernel_ms(dmi_color_context *c, double *last);
 int dmi_color_get_render_pass_ms(dmi_color_context *c, double out[3]);
 int dmi_color_get_render_queued_pairs(dmi_color_context *c, uint64_t *out);
 int dmi_color_set_render_queue_capacity(dmi_color_context *c, uint64_t entries);
+
+/* ---- Depth maps filtered by cross-view consistency before they are fused (added after round 5,
+ * dmi_abi_version() stays 5) ----
+ * The reference puts only the best-cost threshold between a stereo depth map and the fusion; a pixel that passes it with a wrong
+ * depth is fused as if it were surface.  dmi_filter_depth_consistency keeps a depth only if enough other views, looking at the same
+ * world point, hold a depth that agrees.  Context-free, like dmi_color_mesh: it uploads, runs its kernels, downloads and frees.
+ *   depth     [n][H][W] f64 host, vtk point order (image pixel (px, py) is stored at row H-1-py)
+ *   best_cost [n][H][W] f64 host or NULL, with `threshold`
+ *   K4, RT4   [n][16]   f64 host, row-major 4x4, exactly what dmi_add_views takes
+ *   out_depth [n][H][W] f64 host; may be `depth` itself (the device works on its own copy)
+ *   out_count [n][H][W] int32 host or NULL;  kernel_ms (nullable): hipEvent time of the kernels alone
+ * Every K4 must have K4[1][0] == 0, the third row (0, 0, 1, 0) and non-zero K4[0][0] and K4[1][1]: all that SetMatrixK or a .krtd
+ * file produces.  THE 3 x 3 BLOCK OF RT4 IS TAKEN AS ORTHONORMAL, as a .krtd gives it: the back-projection uses its transpose.
+ * Definition, met bit for bit by the device and by tests/depth_consistency_np.py.  All arithmetic is f64, every operation is
+ * rounded on its own, nothing is contracted; comparisons with a NaN are false.
+ *   1. D_m = depth_m with -1 wherever best_cost_m > threshold (RD.cxx:138-167).  A pixel is VALID iff D > 0 and D < +inf: false for
+ *      NaN, -1, 0 and negatives.
+ *   2. Back-projection of valid pixel (px, py) of view s with depth d; K = K4_s, R[i][j] = RT4_s[i][j], T_i = RT4_s[i][3]:
+ *      yn = (py - K[1][2]) / K[1][1];  xn = ((px - K[0][2]) - K[0][1]*yn) / K[0][0];  c = (xn*d, yn*d, d);  q_i = c_i - T_i;
+ *      w_j = (R[0][j]*q_0 + R[1][j]*q_1) + R[2][j]*q_2 for j = 0, 1, 2.  The divisions are correctly rounded.
+ *   3. Every other view t != s (the result is a count: the order does not matter):
+ *      c'_i = ((RT4_t[i][0]*w_0 + RT4_t[i][1]*w_1) + RT4_t[i][2]*w_2) + RT4_t[i][3];
+ *      h_i = ((K4_t[i][0]*c'_0 + K4_t[i][1]*c'_1) + K4_t[i][2]*c'_2) + K4_t[i][3];  c'_2 > 0 is required;
+ *      the pixel by the fusion's rule: h_2 < 0 is out; u = h_0/h_2, v = h_1/h_2; round half away from zero; the bounds
+ *      0 <= round(u) < W and 0 <= round(v) < H tested in f64; non-finite is out;  d' = D_t at that pixel;
+ *      the pair AGREES iff d' > 0 and fabs(c'_2 - d') <= abs_tolerance + rel_tolerance*c'_2 (the product rounded, then the sum,
+ *      then the difference).
+ *   4. out_count = the number of agreeing views, 0 at a pixel that is not valid.  out_depth = D where the pixel is valid and its
+ *      count >= min_views, exactly -1.0 everywhere else.  The counts are always taken against the INPUT D of the other views, never
+ *      against an already filtered one; min_views == 0 therefore returns D with every invalid value normalised to -1, and the counts.
+ * Host data goes up and comes down in pieces of at most 256 MiB.  Device memory: 12 bytes per pixel and view plus the pieces.
+ * All arguments are checked before the device is touched.  DMI_ERR_INVALID_ARGUMENT, the message naming the argument: a null depth,
+ * K4, RT4 or out_depth; n < 1; W or H outside [1, 32768]; min_views < 0; a negative, NaN or infinite abs_tolerance or rel_tolerance;
+ * a NaN threshold when best_cost is given; a K4 outside the form above (the message names the view).  Then DMI_ERR_DEVICE without a
+ * device.  A refused call leaves out_depth and out_count untouched.  The call never exits and never throws; a failure's text is
+ * dmi_last_error(NULL)'s.  Synchronises. */
+int dmi_filter_depth_consistency(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
+                                 int32_t n, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance, int32_t min_views,
+                                 int32_t device, double *out_depth, int32_t *out_count, double *kernel_ms);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

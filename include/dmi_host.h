@@ -112,6 +112,10 @@ typedef struct dmi_cli_options {
   int32_t mesh_coloration_depth_from_mesh; /* --meshColorationDepthFromMesh: that test against the mesh's own rendered depth */
   /* (dmi_decimate_isosurface_placed, dmi.h); appended to the struct: */
   int32_t mesh_decimate_quadric;         /* --meshDecimateQuadric: the decimation places its vertices by quadric error */
+  /* not in the reference (dmi_filter_depth_consistency, dmi.h); appended to the struct: */
+  int64_t depth_consistency_min_views;   /* --depthConsistencyMinViews N: filter the depth maps before the fusion; -1: not given */
+  double depth_consistency_tolerance;    /* --depthConsistencyTolerance (default 0) */
+  double depth_consistency_rel_tolerance; /* --depthConsistencyRelTolerance (default 0.01) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -130,7 +134,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * test -- and the file is dmi_write_polydata_with_colors'.  A view without a UInt8 x 3 Color array of the views' size ends the
  * run non-zero with the file's name.  With --meshMinSupportViews N --meshSupportDepthTolerance T (one device) the mesh is extracted
  * in the context that fused and trimmed by dmi_filter_isosurface_support before the component flags; --meshSupportArray writes the
- * final mesh's counts as the Int32 point array NbSupportingViews, behind RegionId and before the colours. */
+ * final mesh's counts as the Int32 point array NbSupportingViews, behind RegionId and before the colours.  With
+ * --depthConsistencyMinViews N every view is read into memory, the depths are filtered by dmi_filter_depth_consistency on the first
+ * device and the filter fuses the filtered views (ReconstructionFilter::SetViews). */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
