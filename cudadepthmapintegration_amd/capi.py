@@ -122,7 +122,7 @@ ABI_SYMBOLS = [
     "dmi_get_isosurface_support_pass_ms", "dmi_decimate_isosurface_placed",
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
-    "dmi_filter_depth_consistency",
+    "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -265,6 +265,9 @@ def load() -> ctypes.CDLL:
     i64, i64p, i32p = ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
     if hasattr(L, "dmi_filter_depth_consistency"):
         L.dmi_filter_depth_consistency.argtypes = [dp, dp, dbl, dp, dp, i32, i32, i32, dbl, dbl, i32, i32, dp, i32p, dp]
+    if hasattr(L, "dmi_estimate_scene_bounds"):
+        L.dmi_estimate_scene_bounds.argtypes = [dp, dp, dbl, dp, dp, i32, i32, i32, dp, dbl, i32, i32, dp, dp,
+                                                ctypes.POINTER(ctypes.c_uint64), dp]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1035,6 +1038,42 @@ def filter_depth_consistency(views: Views, *, min_views: int, abs_tolerance: flo
     return Views(out, views.K4, views.RT4, None), counts, float(ms.value)
 
 
+def estimate_scene_bounds(views: Views, *, trim_fraction: float = 0.0, pixel_step: int = 1, axes=None, threshold: float | None = None,
+                          device: int = 0):
+    """The bounds of the scene the depth maps see (include/dmi.h: dmi_estimate_scene_bounds): per axis the element of rank k and
+    of rank N-1-k of the back-projected valid pixels' coordinates, k = min(int(trim_fraction * N), (N - 1) // 2), over every
+    pixel_step-th pixel of every pixel_step-th row.  axes: 3 x 3, the rows the coordinates are measured along (None: the world's).
+    threshold applies views.best_cost first (best cost > threshold => not valid).  Returns (lo [3] f64, hi [3] f64, the number of
+    points N, the kernels' hipEvent time in ms); N == 0 gives NaN bounds."""
+    L = load()
+    d = np.ascontiguousarray(views.depth, dtype=np.float64)
+    if d.ndim != 3:
+        raise ValueError(f"views.depth must be [n, H, W], got {d.shape}")
+    n, H, W = d.shape
+    k = np.ascontiguousarray(views.K4, dtype=np.float64).reshape(-1)
+    rt = np.ascontiguousarray(views.RT4, dtype=np.float64).reshape(-1)
+    if k.size != 16 * n or rt.size != 16 * n:
+        raise ValueError("views.K4 and views.RT4 must be [n, 4, 4]")
+    bc = None
+    if threshold is not None and views.best_cost is not None:
+        bc = np.ascontiguousarray(views.best_cost, dtype=np.float64)
+        if bc.shape != d.shape:
+            raise ValueError("views.best_cost must have the shape of views.depth")
+    a = None
+    if axes is not None:
+        a = np.ascontiguousarray(axes, dtype=np.float64).reshape(-1)
+        if a.size != 9:
+            raise ValueError("axes must be 3 x 3")
+    lo, hi = np.zeros(3, dtype=np.float64), np.zeros(3, dtype=np.float64)
+    count, ms = ctypes.c_uint64(0), ctypes.c_double(0.0)
+    rc = L.dmi_estimate_scene_bounds(_dp(d), None if bc is None else _dp(bc), 0.0 if threshold is None else float(threshold), _dp(k),
+                                     _dp(rt), n, W, H, None if a is None else _dp(a), float(trim_fraction), int(pixel_step),
+                                     int(device), _dp(lo), _dp(hi), ctypes.byref(count), ctypes.byref(ms))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    return lo, hi, int(count.value), float(ms.value)
+
+
 class ColorContext:
     """MeshColoration with resident views (dmi_color_create ... dmi_color_destroy)."""
 
@@ -1388,7 +1427,9 @@ class CliOptionsC(ctypes.Structure):
                 ("mesh_coloration_fused", ctypes.c_int32), ("mesh_coloration_depth_tolerance", ctypes.c_double),
                 ("mesh_coloration_depth_from_mesh", ctypes.c_int32), ("mesh_decimate_quadric", ctypes.c_int32),
                 ("depth_consistency_min_views", ctypes.c_int64), ("depth_consistency_tolerance", ctypes.c_double),
-                ("depth_consistency_rel_tolerance", ctypes.c_double)]
+                ("depth_consistency_rel_tolerance", ctypes.c_double),
+                ("grid_auto_bounds", ctypes.c_int32), ("grid_auto_bounds_trim", ctypes.c_double),
+                ("grid_auto_bounds_margin", ctypes.c_double), ("grid_auto_bounds_pixel_step", ctypes.c_int64)]
 
 
 def cli_read_arguments(args):

@@ -1,0 +1,200 @@
+// dmi_capi_bounds.hip -- dmi_estimate_scene_bounds of include/dmi.h: the argument checks (all of them before the device is touched),
+// the staged upload into resident planes (8g's upload pass), the count and select launches of scene_bounds.hip and one download of
+// the result.  Context-free, like dmi_filter_depth_consistency: everything the call allocates it frees before it returns.  A
+// failure's text is dmi_last_error(NULL)'s.
+#include <stdlib.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "dmi_context.h"
+#include "scene_bounds.h"
+
+namespace {
+
+using dmi::fail;
+
+constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up in pieces of whole views, as many as fit this (at least one)
+
+#ifdef DMI_TUNING
+double g_last_plain_read_ms = 0.0, g_last_select_ms = 0.0;
+#endif
+
+// what the call holds on the device and the events that time its kernels; released whatever way the call ends
+struct Holdings {
+  dmi::DeviceBuffer planes, cameras, stage_depth, stage_cost, state, hist;
+  hipStream_t stream = nullptr;
+  hipEvent_t events[2] = {nullptr, nullptr};
+  ~Holdings() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    dmi::free_buffers({&planes, &cameras, &stage_depth, &stage_cost, &state, &hist});
+    for (hipEvent_t e : events)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+#define DMI_SB_HIP(call) DMI_HIP(nullptr, call)
+
+int estimate(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4, int32_t n, int32_t W,
+             int32_t H, const double *axes9, double trim_fraction, int32_t pixel_step, int32_t device, double lo[3], double hi[3],
+             uint64_t *n_points, double *kernel_ms) {
+  const std::string entry = "dmi_estimate_scene_bounds: ";
+  auto bad = [&](const std::string &what) { return fail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!depth) return bad("depth is null");
+  if (!K4) return bad("K4 is null");
+  if (!RT4) return bad("RT4 is null");
+  if (!lo) return bad("lo is null");
+  if (!hi) return bad("hi is null");
+  if (!n_points) return bad("n_points is null");
+  if (n < 1) return bad("n >= 1 required");
+  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
+  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
+  if ((uint64_t)n * (uint64_t)W * (uint64_t)H >= (uint64_t(1) << 53)) return bad("n * W * H must stay below 2^53");
+  if (!(trim_fraction >= 0.0 && trim_fraction <= 0.5)) return bad("trim_fraction must lie in [0, 0.5]");  // false for NaN
+  if (pixel_step < 1) return bad("pixel_step >= 1 required");
+  if (best_cost && threshold != threshold) return bad("threshold is NaN");
+  dmi::BoundsAxes axes = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+  if (axes9)
+    for (int q = 0; q < 9; ++q) {
+      if (!std::isfinite(axes9[q])) return bad("axes9 holds a value that is not finite");
+      axes.a[q] = axes9[q];
+    }
+  for (int32_t m = 0; m < n; ++m) {
+    const double *K = K4 + 16 * (size_t)m;
+    const bool form = K[4] == 0.0 && K[8] == 0.0 && K[9] == 0.0 && K[10] == 1.0 && K[11] == 0.0 && K[0] != 0.0 && K[5] != 0.0 &&
+                      K[0] == K[0] && K[5] == K[5];
+    if (!form)
+      return bad("K4 of view " + std::to_string(m) + " is not of the form SetMatrixK produces (K4[1][0] == 0, third row 0 0 1 0, "
+                 "non-zero K4[0][0] and K4[1][1])");
+  }
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
+  }
+  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
+  DMI_SB_HIP(hipSetDevice(device));
+  int compute_units = 0;
+  DMI_SB_HIP(hipDeviceGetAttribute(&compute_units, hipDeviceAttributeMultiprocessorCount, device));
+
+  dmi::BoundsTuning tuning;
+#ifdef DMI_TUNING
+  if (const char *v = getenv("DMI_SB_AGGREGATE_ROUNDS")) tuning.aggregate_rounds = atoi(v);
+  if (const char *v = getenv("DMI_SB_SHARE_HISTOGRAMS")) tuning.share_histograms = atoi(v);
+#endif
+
+  Holdings h;
+  DMI_SB_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+  for (hipEvent_t &e : h.events) DMI_SB_HIP(hipEventCreate(&e));
+  const size_t plane = (size_t)W * H, views = (size_t)n;
+  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));
+  constexpr size_t kHistBytes = sizeof(unsigned long long) * dmi::bounds_rules::kTargets * dmi::bounds_rules::kBins;
+  DMI_SB_HIP(dmi::grow_buffer(h.planes, views * plane * sizeof(double)));
+  DMI_SB_HIP(dmi::grow_buffer(h.cameras, views * sizeof(dmi::ConsistencyCamera)));
+  DMI_SB_HIP(dmi::grow_buffer(h.stage_depth, chunk * plane * sizeof(double)));
+  if (best_cost) DMI_SB_HIP(dmi::grow_buffer(h.stage_cost, chunk * plane * sizeof(double)));
+  DMI_SB_HIP(dmi::grow_buffer(h.state, sizeof(dmi::BoundsState)));
+  DMI_SB_HIP(dmi::grow_buffer(h.hist, kHistBytes));
+
+  double total_ms = 0.0;
+  auto add_span = [&]() -> hipError_t {  // (the stream has been synchronised behind events[1])
+    float ms = 0.f;
+    const hipError_t e = hipEventElapsedTime(&ms, h.events[0], h.events[1]);
+    if (e == hipSuccess) total_ms += (double)ms;
+    return e;
+  };
+
+  {
+    std::vector<dmi::ConsistencyCamera> cameras(views);
+    for (size_t m = 0; m < views; ++m) {
+      const double *K = K4 + 16 * m, *RT = RT4 + 16 * m;
+      for (int q = 0; q < 12; ++q) cameras[m].rt[q] = RT[q];
+      const double k[8] = {K[0], K[1], K[2], K[3], K[5], K[6], K[7], 0.0};
+      for (int q = 0; q < 8; ++q) cameras[m].k[q] = k[q];
+    }
+    DMI_SB_HIP(hipMemcpyAsync(h.cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, h.stream));
+    DMI_SB_HIP(hipStreamSynchronize(h.stream));  // `cameras` goes out of scope
+  }
+  DMI_SB_HIP(hipMemsetAsync(h.state.ptr, 0, sizeof(dmi::BoundsState), h.stream));
+  DMI_SB_HIP(hipMemsetAsync(h.hist.ptr, 0, kHistBytes, h.stream));
+
+  // up: threshold, validity, -1 for everything else and the row flip happen in the pass that unpacks a staged piece
+  for (size_t m0 = 0; m0 < views; m0 += chunk) {
+    const size_t cnt = std::min(chunk, views - m0);
+    DMI_SB_HIP(hipMemcpyAsync(h.stage_depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    if (best_cost)
+      DMI_SB_HIP(hipMemcpyAsync(h.stage_cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    DMI_SB_HIP(hipEventRecord(h.events[0], h.stream));
+    DMI_SB_HIP(dmi::launch_consistency_upload(h.stage_depth.as<double>(), best_cost ? h.stage_cost.as<double>() : nullptr, threshold, W, H,
+                                              (int64_t)cnt, h.planes.as<double>(), (int64_t)m0, h.stream));
+    DMI_SB_HIP(hipEventRecord(h.events[1], h.stream));
+    DMI_SB_HIP(hipStreamSynchronize(h.stream));  // the stage buffers are reused by the next piece
+    DMI_SB_HIP(add_span());
+  }
+
+  // the select: count and select, pass after pass, with no host round trip in between
+  dmi::BoundsState *state = h.state.as<dmi::BoundsState>();
+  unsigned long long *hist = h.hist.as<unsigned long long>();
+  const unsigned blocks = dmi::bounds_count_blocks(n, W, H, pixel_step, compute_units);
+  DMI_SB_HIP(hipEventRecord(h.events[0], h.stream));
+  for (int pass = 0; pass < dmi::bounds_rules::kPasses; ++pass) {
+    DMI_SB_HIP(dmi::launch_bounds_count(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, pixel_step, axes, pass,
+                                        state, hist, blocks, tuning, h.stream));
+    DMI_SB_HIP(dmi::launch_bounds_select(state, hist, pass, trim_fraction, h.stream));
+  }
+  DMI_SB_HIP(hipEventRecord(h.events[1], h.stream));
+  dmi::BoundsState result;
+  DMI_SB_HIP(hipMemcpyAsync(&result, state, sizeof(result), hipMemcpyDeviceToHost, h.stream));
+  DMI_SB_HIP(hipStreamSynchronize(h.stream));
+  DMI_SB_HIP(add_span());
+#ifdef DMI_TUNING
+  {
+    float ms = 0.f;
+    DMI_SB_HIP(hipEventElapsedTime(&ms, h.events[0], h.events[1]));
+    g_last_select_ms = (double)ms;
+    // the yardstick: one plain read of the same planes (the stage buffer serves as the sink)
+    const unsigned read_blocks = (unsigned)std::min<size_t>((views * plane + 255) / 256, (size_t)std::max(compute_units, 1) * 8);
+    for (int round = 0; round < 2; ++round) {  // the second one is the measurement
+      DMI_SB_HIP(hipEventRecord(h.events[0], h.stream));
+      DMI_SB_HIP(dmi::launch_bounds_plain_read(h.planes.as<double>(), (int64_t)(views * plane), h.stage_depth.as<double>(), read_blocks,
+                                               h.stream));
+      DMI_SB_HIP(hipEventRecord(h.events[1], h.stream));
+      DMI_SB_HIP(hipStreamSynchronize(h.stream));
+    }
+    DMI_SB_HIP(hipEventElapsedTime(&ms, h.events[0], h.events[1]));
+    g_last_plain_read_ms = (double)ms;
+  }
+#endif
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = result.result[2 * a];
+    hi[a] = result.result[2 * a + 1];
+  }
+  *n_points = result.n;
+  if (kernel_ms) *kernel_ms = total_ms;
+  return DMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmi_estimate_scene_bounds(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
+                              int32_t n, int32_t W, int32_t H, const double *axes9, double trim_fraction, int32_t pixel_step,
+                              int32_t device, double lo[3], double hi[3], uint64_t *n_points, double *kernel_ms) {
+  return dmi::guarded(nullptr, "dmi_estimate_scene_bounds", [&]() -> int {
+    return estimate(depth, best_cost, threshold, K4, RT4, n, W, H, axes9, trim_fraction, pixel_step, device, lo, hi, n_points,
+                    kernel_ms);
+  });
+}
+
+#ifdef DMI_TUNING
+// tuning builds only (tools/gpu_scene_bounds_time.py): the last call's select passes alone, and a plain read of the same planes
+double dmi_tuning_scene_bounds_select_ms(void) { return g_last_select_ms; }
+double dmi_tuning_scene_bounds_plain_read_ms(void) { return g_last_plain_read_ms; }
+#endif
+
+}  // extern "C"

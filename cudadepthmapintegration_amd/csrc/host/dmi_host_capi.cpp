@@ -353,11 +353,11 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   }
   if (!ok) return 0;
   std::memset(out, 0, sizeof(*out));
-  for (int a = 0; a < 3; ++a) {
-    out->grid_dims[a] = o.gridDims[(size_t)a];
-    out->grid_spacing[a] = o.gridSpacing[(size_t)a];
-    out->grid_origin[a] = o.gridOrigin[(size_t)a];
-    out->grid_end[a] = o.gridEnd[(size_t)a];
+  for (int a = 0; a < 3; ++a) {  // (with --gridAutoBounds the run fills in what is empty here)
+    if (o.gridDims.size() == 3) out->grid_dims[a] = o.gridDims[(size_t)a];
+    if (o.gridSpacing.size() == 3) out->grid_spacing[a] = o.gridSpacing[(size_t)a];
+    if (o.gridOrigin.size() == 3) out->grid_origin[a] = o.gridOrigin[(size_t)a];
+    if (o.gridEnd.size() == 3) out->grid_end[a] = o.gridEnd[(size_t)a];
   }
   dmi::host::cli::CreateGridMatrixFromInput(o, out->grid_matrix);
   out->ray_thick = o.rayThick; out->ray_rho = o.rayRho; out->ray_eta = o.rayEta; out->ray_delta = o.rayDelta;
@@ -380,6 +380,10 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->depth_consistency_min_views = o.depthConsistencyMinViews;
   out->depth_consistency_tolerance = o.depthConsistencyTolerance;
   out->depth_consistency_rel_tolerance = o.depthConsistencyRelTolerance;
+  out->grid_auto_bounds = o.gridAutoBounds ? 1 : 0;
+  out->grid_auto_bounds_trim = o.gridAutoBoundsTrim;
+  out->grid_auto_bounds_margin = o.gridAutoBoundsMargin;
+  out->grid_auto_bounds_pixel_step = o.gridAutoBoundsPixelStep;
   return 1;
   });
 }

@@ -224,8 +224,50 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                         "other view's camera (finite, >= 0, default 0.01; not in the reference)",
                                           into_checked_double(&o->depthConsistencyRelTolerance, &o->depthConsistencyRelToleranceGiven,
                                                               [](double x) { return x >= 0.0; })}},
+      {"--gridAutoBounds", {Kind::kFlag, "take the grid's box from the depth maps instead of --gridOrigin and --gridEnd, which then must "
+                                         "not be given (one of --gridDims / --gridSpacing still is): every valid pixel is "
+                                         "back-projected on the GPU, and along each of the grid's axes the box runs from the "
+                                         "coordinate below which the share --gridAutoBoundsTrim of the points lies to the one above "
+                                         "which the same share lies, plus the margin -- a handful of wild depths does not decide "
+                                         "it.  All views are then read into host memory at once, on the first --device, and with "
+                                         "--depthConsistencyMinViews the filtered depths are what is measured (not in the reference)",
+                           into_flag(&o->gridAutoBounds)}},
+      {"--gridAutoBoundsTrim", {Kind::kValue, "with --gridAutoBounds: the share of the points left outside the box at either end of "
+                                              "each axis (in [0, 0.5], default 0.005; 0 is the plain minimum and maximum; not in "
+                                              "the reference)",
+                                into_checked_double(&o->gridAutoBoundsTrim, &o->gridAutoBoundsTrimGiven,
+                                                    [](double x) { return x >= 0.0 && x <= 0.5; })}},
+      {"--gridAutoBoundsMargin", {Kind::kValue, "with --gridAutoBounds: what is added on either side of each axis, as a share of the "
+                                                "trimmed extent (finite, >= 0, default 0.05; not in the reference)",
+                                  into_checked_double(&o->gridAutoBoundsMargin, &o->gridAutoBoundsMarginGiven,
+                                                      [](double x) { return x >= 0.0; })}},
+      {"--gridAutoBoundsPixelStep", {Kind::kValue, "with --gridAutoBounds: only every s-th pixel of every s-th row is measured (an "
+                                                   "integer >= 1, default 1; not in the reference)",
+                                     [o](const std::vector<std::string> &values) {
+                                       o->gridAutoBoundsPixelStepGiven = true;
+                                       return into_count(&o->gridAutoBoundsPixelStep)(values) && o->gridAutoBoundsPixelStep >= 1 &&
+                                              o->gridAutoBoundsPixelStep <= 0x7fffffffLL;
+                                     }}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
+}
+
+// rmain:310-344: the extent decides whichever of spacing / dimensions was not given, then --forceCubicVoxel
+void derive_spacing_or_dimensions(Options *o) {
+  double size[3];
+  for (int a = 0; a < 3; ++a) size[a] = o->gridEnd[a] - o->gridOrigin[a];
+  if (o->gridSpacing.empty()) {
+    o->gridSpacing.resize(3);
+    for (int a = 0; a < 3; ++a) o->gridSpacing[a] = size[a] / (double)o->gridDims[a];
+  }
+  if (o->gridDims.empty()) {
+    o->gridDims.resize(3);
+    for (int a = 0; a < 3; ++a) o->gridDims[a] = (int)(size[a] / o->gridSpacing[a]);
+  }
+  if (o->forceCubicVoxel) {  // rmain:337-344
+    const double smallest = *std::min_element(o->gridSpacing.begin(), o->gridSpacing.end());
+    o->gridSpacing.assign(3, smallest);
+  }
 }
 
 double dot3(const std::vector<double> &a, const std::vector<double> &b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -359,6 +401,18 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     err << "Bad value for --depthConsistencyMinViews\n" << HelpText();
     return false;
   }
+  for (const auto &flag : {std::make_pair("--gridAutoBoundsTrim", o->gridAutoBoundsTrimGiven),
+                           std::make_pair("--gridAutoBoundsMargin", o->gridAutoBoundsMarginGiven),
+                           std::make_pair("--gridAutoBoundsPixelStep", o->gridAutoBoundsPixelStepGiven)})
+    if (flag.second && !o->gridAutoBounds) {
+      err << "Error : " << flag.first << " needs --gridAutoBounds.\n" << HelpText();
+      return false;
+    }
+  if (o->gridAutoBounds && (!o->gridOrigin.empty() || !o->gridEnd.empty())) {
+    err << "Error : --gridAutoBounds takes the grid's box from the depth maps: --gridOrigin and --gridEnd must not be given.\n"
+        << HelpText();
+    return false;
+  }
   // rmain:257-262
   if (!o->gridSpacing.empty() && !o->gridDims.empty()) {
     err << "Error : Spacing and dimensions can't be both set\n" << HelpText();
@@ -382,8 +436,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   }
   // The reference indexes these vectors without looking at their length (rmain:311-313, 345-360): a missing
   // --gridOrigin / --gridEnd or a two-component axis is undefined behaviour there and an error here.
-  if (o->gridVecX.size() != 3 || o->gridVecY.size() != 3 || o->gridVecZ.size() != 3 || o->gridOrigin.size() != 3 ||
-      o->gridEnd.size() != 3 || (!o->gridDims.empty() && o->gridDims.size() != 3) ||
+  // (with --gridAutoBounds the two corners are absent: Run takes them from the depth maps)
+  const size_t corner = o->gridAutoBounds ? 0 : 3;
+  if (o->gridVecX.size() != 3 || o->gridVecY.size() != 3 || o->gridVecZ.size() != 3 || o->gridOrigin.size() != corner ||
+      o->gridEnd.size() != corner || (!o->gridDims.empty() && o->gridDims.size() != 3) ||
       (!o->gridSpacing.empty() && o->gridSpacing.size() != 3) || (o->gridDims.empty() && o->gridSpacing.empty())) {
     err << "Error : --gridOrigin, --gridEnd and the three axes take three values each, and one of --gridDims / "
            "--gridSpacing is required.\n";
@@ -393,21 +449,8 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     err << "Given vectors are not orthogonals.\n";
     return false;
   }
-  // rmain:310-335: the extent decides whichever of spacing / dimensions was not given
-  double size[3];
-  for (int a = 0; a < 3; ++a) size[a] = o->gridEnd[a] - o->gridOrigin[a];
-  if (o->gridSpacing.empty()) {
-    o->gridSpacing.resize(3);
-    for (int a = 0; a < 3; ++a) o->gridSpacing[a] = size[a] / (double)o->gridDims[a];
-  }
-  if (o->gridDims.empty()) {
-    o->gridDims.resize(3);
-    for (int a = 0; a < 3; ++a) o->gridDims[a] = (int)(size[a] / o->gridSpacing[a]);
-  }
-  if (o->forceCubicVoxel) {  // rmain:337-344
-    const double smallest = *std::min_element(o->gridSpacing.begin(), o->gridSpacing.end());
-    o->gridSpacing.assign(3, smallest);
-  }
+  if (o->gridAutoBounds) return true;  // the box is not known yet: Run estimates it and derives the rest
+  derive_spacing_or_dimensions(o);
   return true;
 }
 
@@ -655,18 +698,121 @@ void describe(const Options &o, std::ostream &out, bool with_sketch) {
 
 }  // namespace
 
-int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result) {
+int Run(const Options &given, int argc, const char *const *argv, std::ostream &log, RunResult *result) {
   const auto start = std::chrono::steady_clock::now();
+  Options resolved = given;  // --gridAutoBounds fills in the box and what follows from it
+  const Options &o = resolved;
   auto say = [&](const std::string &what) {
     if (o.verbose) log << what << "\n" << std::endl;
   };
   say("---START---");
+  const std::string vti_list = o.dataFolder + "/" + o.depthMapFile, krtd_list = o.dataFolder + "/" + o.krtFile;
+  // --depthConsistencyMinViews and --gridAutoBounds: every view is read once and held in memory; the filter then fuses them from
+  // there (SetViews: the path that thresholds again, which changes nothing, and forwards the Color planes to the colour sink)
+  std::vector<std::unique_ptr<ReconstructionData>> memoryViews;
+  std::vector<ReconstructionData *> views;
+  auto read_views = [&](const std::string &flag) {
+    const std::vector<std::string> vtis = help::ExtractAllFilePath(vti_list.c_str()), krtds = help::ExtractAllFilePath(krtd_list.c_str());
+    if (vtis.empty() || krtds.size() < vtis.size()) {  // filt.cxx:161-165
+      result->error = "Error : There is no enough vti files, please check your vtiList.txt and krtdList.txt";
+      return false;
+    }
+    for (size_t m = 0; m < vtis.size(); ++m) {
+      memoryViews.emplace_back(new ReconstructionData(vtis[m], krtds[m]));
+      if (!memoryViews.back()->GetDepthMap()) {
+        result->error = flag + ": cannot read depth map " + vtis[m];
+        return false;
+      }
+      views.push_back(memoryViews.back().get());
+    }
+    return true;
+  };
+  // all views filtered on the first device
+  auto filter_views = [&]() {
+    say("** Filter the depth maps by cross-view consistency...");
+    if (!read_views("--depthConsistencyMinViews")) return false;
+    DepthConsistencyReport report;
+    std::string error;
+    if (!FilterDepthConsistency(views, o.threshBestCost, (int)o.depthConsistencyMinViews, o.depthConsistencyTolerance,
+                                o.depthConsistencyRelTolerance, o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+      result->error = "--depthConsistencyMinViews: " + error;
+      return false;
+    }
+    result->depthConsistencyViews = report.views;
+    result->depthConsistencyValidPixels = report.validPixels;
+    result->depthConsistencyKeptPixels = report.keptPixels;
+    result->depthConsistencyKernelMs = report.kernelMs;
+    std::ostringstream line;
+    line << "depth consistency: at least " << o.depthConsistencyMinViews << " of " << report.views - 1 << " other views, tolerance "
+         << o.depthConsistencyTolerance << " + " << o.depthConsistencyRelTolerance << " z; " << report.validPixels
+         << " pixels with a depth, " << report.keptPixels << " kept; " << report.kernelMs << " ms of GPU kernels";
+    say(line.str());
+    return true;
+  };
+  if (o.gridAutoBounds) {
+    // the box before anything is described or set up: filtered depths if a filter was asked for, measured along the grid's axes
+    if (o.depthConsistencyMinViews >= 0 ? !filter_views() : !read_views("--gridAutoBounds")) return 1;
+    say("** Estimate the grid's bounds from the depth maps...");
+    // axes[j][i] = M[i][j] / |row_i|^2, M's rows the grid's axes: the inverse of the grid matrix for orthogonal rows, so that the
+    // bounds are in the coordinates --gridOrigin uses
+    const std::vector<double> *rows[3] = {&o.gridVecX, &o.gridVecY, &o.gridVecZ};
+    double axes[9];
+    for (int i = 0; i < 3; ++i) {
+      const double norm2 = dot3(*rows[i], *rows[i]);
+      for (int j = 0; j < 3; ++j) axes[j * 3 + i] = (*rows[i])[(size_t)j] / norm2;
+    }
+    for (const double v : axes)
+      if (!std::isfinite(v)) {
+        result->error = "--gridAutoBounds: an axis of the grid has no length";
+        return 1;
+      }
+    SceneBoundsReport bounds;
+    std::string error;
+    if (!EstimateSceneBounds(views, o.threshBestCost, axes, o.gridAutoBoundsTrim, (int)o.gridAutoBoundsPixelStep,
+                             o.devices.empty() ? 0 : o.devices[0], &bounds, &error)) {
+      result->error = "--gridAutoBounds: " + error;
+      return 1;
+    }
+    if (bounds.points == 0) {
+      result->error = "--gridAutoBounds: no pixel of the depth maps holds a depth, there is nothing to put a box around";
+      return 1;
+    }
+    resolved.gridOrigin.resize(3);
+    resolved.gridEnd.resize(3);
+    for (int a = 0; a < 3; ++a) {
+      if (bounds.hi[a] == bounds.lo[a]) {
+        result->error = "--gridAutoBounds: the depth maps' points have no extent along axis " + std::to_string(a) + " of the grid";
+        return 1;
+      }
+      const double pad = o.gridAutoBoundsMargin * (bounds.hi[a] - bounds.lo[a]);
+      resolved.gridOrigin[(size_t)a] = bounds.lo[a] - pad;
+      resolved.gridEnd[(size_t)a] = bounds.hi[a] + pad;
+      result->gridAutoBoundsLo[a] = bounds.lo[a];
+      result->gridAutoBoundsHi[a] = bounds.hi[a];
+    }
+    derive_spacing_or_dimensions(&resolved);
+    result->gridAutoBoundsPoints = bounds.points;
+    result->gridAutoBoundsKernelMs = bounds.kernelMs;
+    std::ostringstream line;
+    line.precision(17);
+    line << "grid bounds: trim " << o.gridAutoBoundsTrim << ", margin " << o.gridAutoBoundsMargin << ", pixel step "
+         << o.gridAutoBoundsPixelStep << "; " << bounds.points << " points of " << bounds.views << " views; trimmed bounds " << bounds.lo[0]
+         << " " << bounds.lo[1] << " " << bounds.lo[2] << " to " << bounds.hi[0] << " " << bounds.hi[1] << " " << bounds.hi[2]
+         << "; --gridOrigin " << o.gridOrigin[0] << " " << o.gridOrigin[1] << " " << o.gridOrigin[2] << " --gridEnd " << o.gridEnd[0]
+         << " " << o.gridEnd[1] << " " << o.gridEnd[2] << "; " << bounds.kernelMs << " ms of GPU kernels";
+    say(line.str());
+  }
+  for (int a = 0; a < 3; ++a) {
+    result->gridOrigin[a] = o.gridOrigin[(size_t)a];
+    result->gridEnd[a] = o.gridEnd[(size_t)a];
+    result->gridSpacing[a] = o.gridSpacing[(size_t)a];
+    result->gridDims[a] = o.gridDims[(size_t)a];
+  }
   if (o.verbose) describe(o, log, true);
   double matrix[16];
   CreateGridMatrixFromInput(o, matrix);
 
   say("** Launch reconstruction...");
-  const std::string vti_list = o.dataFolder + "/" + o.depthMapFile, krtd_list = o.dataFolder + "/" + o.krtFile;
   ReconstructionFilter filter;
   filter.SetFilePathKRTD(krtd_list.c_str());
   filter.SetFilePathVTI(vti_list.c_str());
@@ -702,43 +848,8 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
   const bool supportMesh = o.meshMinSupportViews >= 0 || o.meshSupportArray;
   const bool supportFacing = supportMesh && !o.meshSupportNoFacing;
   if (supportMesh) filter.SetKeepContext(true);
-  // --depthConsistencyMinViews: every view is read once, all are filtered on the first device, and the filter fuses them from memory
-  // (SetViews: the path that thresholds again, which changes nothing, and forwards the Color planes to the colour sink)
-  std::vector<std::unique_ptr<ReconstructionData>> consistentViews;
-  if (o.depthConsistencyMinViews >= 0) {
-    say("** Filter the depth maps by cross-view consistency...");
-    const std::vector<std::string> vtis = help::ExtractAllFilePath(vti_list.c_str()), krtds = help::ExtractAllFilePath(krtd_list.c_str());
-    if (vtis.empty() || krtds.size() < vtis.size()) {  // filt.cxx:161-165
-      result->error = "Error : There is no enough vti files, please check your vtiList.txt and krtdList.txt";
-      return 1;
-    }
-    std::vector<ReconstructionData *> views;
-    for (size_t m = 0; m < vtis.size(); ++m) {
-      consistentViews.emplace_back(new ReconstructionData(vtis[m], krtds[m]));
-      if (!consistentViews.back()->GetDepthMap()) {
-        result->error = "--depthConsistencyMinViews: cannot read depth map " + vtis[m];
-        return 1;
-      }
-      views.push_back(consistentViews.back().get());
-    }
-    DepthConsistencyReport report;
-    std::string error;
-    if (!FilterDepthConsistency(views, o.threshBestCost, (int)o.depthConsistencyMinViews, o.depthConsistencyTolerance,
-                                o.depthConsistencyRelTolerance, o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
-      result->error = "--depthConsistencyMinViews: " + error;
-      return 1;
-    }
-    result->depthConsistencyViews = report.views;
-    result->depthConsistencyValidPixels = report.validPixels;
-    result->depthConsistencyKeptPixels = report.keptPixels;
-    result->depthConsistencyKernelMs = report.kernelMs;
-    std::ostringstream line;
-    line << "depth consistency: at least " << o.depthConsistencyMinViews << " of " << report.views - 1 << " other views, tolerance "
-         << o.depthConsistencyTolerance << " + " << o.depthConsistencyRelTolerance << " z; " << report.validPixels
-         << " pixels with a depth, " << report.keptPixels << " kept; " << report.kernelMs << " ms of GPU kernels";
-    say(line.str());
-    filter.SetViews(views);
-  }
+  if (o.depthConsistencyMinViews >= 0 && !o.gridAutoBounds && !filter_views()) return 1;
+  if (!views.empty()) filter.SetViews(views);
   if (!filter.Update()) {
     result->error = filter.LastError().empty() ? "the reconstruction filter refused its parameters" : filter.LastError();
     return 1;
@@ -952,6 +1063,17 @@ int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, 
     for (int i = 0; i < argc; ++i) out << " " << argv[i];
     out << "\noutput volume  " << o.outputGridFilename << "\n";
     describe(o, out, false);
+    if (o.gridAutoBounds) {
+      const std::streamsize digits = out.precision(17);
+      out << "grid bounds from the depth maps\n  trim  " << o.gridAutoBoundsTrim << "\n  margin  " << o.gridAutoBoundsMargin
+          << "\n  pixel step  " << o.gridAutoBoundsPixelStep << "\n  points  " << result->gridAutoBoundsPoints << "\n  trimmed lower bounds  "
+          << result->gridAutoBoundsLo[0] << " " << result->gridAutoBoundsLo[1] << " " << result->gridAutoBoundsLo[2]
+          << "\n  trimmed upper bounds  " << result->gridAutoBoundsHi[0] << " " << result->gridAutoBoundsHi[1] << " "
+          << result->gridAutoBoundsHi[2] << "\n  --gridOrigin  " << o.gridOrigin[0] << " " << o.gridOrigin[1] << " " << o.gridOrigin[2]
+          << "\n  --gridEnd  " << o.gridEnd[0] << " " << o.gridEnd[1] << " " << o.gridEnd[2] << "\n  GPU kernels  "
+          << result->gridAutoBoundsKernelMs << " ms\n";
+      out.precision(digits);
+    }
     if (o.depthConsistencyMinViews >= 0)
       out << "depth consistency\n  minimum agreeing views  " << o.depthConsistencyMinViews << "\n  tolerance  " << o.depthConsistencyTolerance
           << " + " << o.depthConsistencyRelTolerance << " z\n  views  " << result->depthConsistencyViews << "\n  pixels with a depth  "

@@ -20,7 +20,12 @@
 // component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.
 // --depthConsistencyMinViews N with --depthConsistencyTolerance / --depthConsistencyRelTolerance (not in the reference: the geometric
 // consistency check of every depth-map fusion pipeline) reads all views into memory, filters their depths on the first device
-// (dmi_filter_depth_consistency) and fuses the filtered views through ReconstructionFilter::SetViews.  Without --extractMesh
+// (dmi_filter_depth_consistency) and fuses the filtered views through ReconstructionFilter::SetViews.
+// --gridAutoBounds (not in the reference, which needs --gridOrigin and --gridEnd from outside the data) takes the grid's box from the
+// depth maps themselves: all views are read into memory -- and filtered first with --depthConsistencyMinViews --, the first device
+// gives trimmed order statistics of the back-projected pixels along the grid's axes (dmi_estimate_scene_bounds;
+// --gridAutoBoundsTrim, --gridAutoBoundsPixelStep), a margin is added (--gridAutoBoundsMargin), and spacing or dimensions follow
+// as they do from a given box.  Without --extractMesh
 // --outputMeshFilename is accepted and checked as the reference does, and nothing is written to it.
 #pragma once
 
@@ -86,6 +91,14 @@ struct Options {
   long long depthConsistencyMinViews = -1;
   double depthConsistencyTolerance = 0.0, depthConsistencyRelTolerance = 0.01;
   bool depthConsistencyToleranceGiven = false, depthConsistencyRelToleranceGiven = false;
+  // not in the reference: the grid's box from the depth maps (dmi_estimate_scene_bounds) instead of --gridOrigin / --gridEnd, which
+  // then must be absent; ReadArguments leaves gridOrigin, gridEnd and whichever of gridDims / gridSpacing was not given empty, and Run
+  // fills them in.  The share of the points cut off at either end of an axis, the margin added on either side as a share of the
+  // trimmed extent, and the step between the pixels (and rows) that take part
+  bool gridAutoBounds = false;
+  double gridAutoBoundsTrim = 0.005, gridAutoBoundsMargin = 0.05;
+  long long gridAutoBoundsPixelStep = 1;
+  bool gridAutoBoundsTrimGiven = false, gridAutoBoundsMarginGiven = false, gridAutoBoundsPixelStepGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -120,6 +133,13 @@ struct RunResult {
   // and the hipEvent time of its kernels
   unsigned long long depthConsistencyViews = 0, depthConsistencyValidPixels = 0, depthConsistencyKeptPixels = 0;
   double depthConsistencyKernelMs = 0.0;
+  // --gridAutoBounds: the trimmed bounds along the grid's axes before the margin, the points they were taken from, the hipEvent time
+  // of the estimate's kernels, and the box, spacing and dimensions the run then used
+  double gridAutoBoundsLo[3] = {0.0, 0.0, 0.0}, gridAutoBoundsHi[3] = {0.0, 0.0, 0.0};
+  unsigned long long gridAutoBoundsPoints = 0;
+  double gridAutoBoundsKernelMs = 0.0;
+  double gridOrigin[3] = {0.0, 0.0, 0.0}, gridEnd[3] = {0.0, 0.0, 0.0}, gridSpacing[3] = {0.0, 0.0, 0.0};
+  int gridDims[3] = {0, 0, 0};
   std::string error;  // empty on success
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.

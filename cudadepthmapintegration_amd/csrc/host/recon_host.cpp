@@ -711,6 +711,45 @@ bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, doub
   return true;
 }
 
+// Not in the reference (recon_host.h)
+bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
+                         double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error) {
+  const size_t n = views.size();
+  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
+  if (!first) {
+    *error = "EstimateSceneBounds: no views, or view 0 has no depth map";
+    return false;
+  }
+  const int W = first->dims[0], H = first->dims[1];
+  const size_t npix = (size_t)W * H;
+  if (n > 0x7fffffffu) {
+    *error = "EstimateSceneBounds: too many views";
+    return false;
+  }
+  std::vector<double> depth(n * npix), K4(n * 16), RT(n * 16);
+  SceneBoundsReport r;
+  r.views = n;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
+      *error = "EstimateSceneBounds: view " + std::to_string(m) + " has no depth map of the size of view 0";
+      return false;
+    }
+    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
+    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
+    std::memcpy(K4.data() + m * 16, views[m]->Get4MatrixK(), 16 * 8);
+    std::memcpy(RT.data() + m * 16, views[m]->GetMatrixTR(), 16 * 8);
+  }
+  const int rc = dmi_estimate_scene_bounds(depth.data(), nullptr, 0.0, K4.data(), RT.data(), (int32_t)n, W, H, axes, trimFraction, pixelStep,
+                                           device, r.lo, r.hi, &r.points, &r.kernelMs);
+  if (rc != DMI_OK) {
+    *error = dmi_last_error(nullptr);
+    return false;
+  }
+  if (report) *report = r;
+  return true;
+}
+
 // ====================================================================================================
 // vtkCudaReconstructionFilter
 // ====================================================================================================

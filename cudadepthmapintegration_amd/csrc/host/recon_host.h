@@ -109,6 +109,20 @@ struct DepthConsistencyReport {
 bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int minViews,
                             double absTolerance, double relTolerance, int device, DepthConsistencyReport *report, std::string *error);
 
+// Not in the reference: the bounds of the scene the views see, along the rows of `axes` (row-major 3 x 3), on the GPU
+// (dmi_estimate_scene_bounds, include/dmi.h states the definition): per axis the coordinate of rank k and of rank N-1-k of the
+// back-projected valid pixels, k = min((uint64_t)(trimFraction * N), (N - 1) / 2), over every pixelStep-th pixel of every
+// pixelStep-th row.  Every view is thresholded first (ApplyDepthThresholdFilter) and all of them are packed, as
+// FilterDepthConsistency does; the views' depths are not changed beyond that.  points == 0 leaves lo and hi NaN.
+struct SceneBoundsReport {
+  uint64_t views = 0;
+  uint64_t points = 0;    // N: the points that were ordered
+  double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
+  double kernelMs = 0.0;  // hipEvent time of the call's kernels
+};
+bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
+                         double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error);
+
 // ---- Reconstruction/CudaReconstruction.cu host driver -------------------------------------------------
 // The reference keeps the grid description in global __constant__ state between the two calls (cu:55-64);
 // here it lives in an object.  One FusionDriver = one CudaInitialize + ProcessDepthMap pair.

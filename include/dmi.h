@@ -51,7 +51,8 @@ extern "C" {
                            *    dmi_get_isosurface_decimate_pass_ms; dmi_color_process_isosurface, dmi_download_isosurface_colors,
                            *    dmi_get_isosurface_color_kernel_ms; dmi_filter_isosurface_support, dmi_download_isosurface_support,
                            *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms;
-                           *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency */
+                           *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency;
+                           *    dmi_estimate_scene_bounds */
 
 typedef struct dmi_context dmi_context;
 
@@ -694,6 +695,40 @@ int dmi_color_set_render_queue_capacity(dmi_color_context *c, uint64_t entries);
 int dmi_filter_depth_consistency(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
                                  int32_t n, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance, int32_t min_views,
                                  int32_t device, double *out_depth, int32_t *out_count, double *kernel_ms);
+
+/* ---- The bounds of the scene the depth maps see (added after round 5, dmi_abi_version() stays 5) ----
+ * --gridOrigin and --gridEnd had to come from outside the data.  dmi_estimate_scene_bounds takes them from the depth maps and
+ * cameras the fusion reads: per grid axis, exact order statistics of the back-projected pixels, so that a handful of wild depths
+ * does not decide the box.  Context-free, like dmi_filter_depth_consistency: it uploads, runs its kernels, downloads six numbers
+ * and frees.
+ *   depth, best_cost, threshold, K4, RT4, n, W, H   exactly as dmi_filter_depth_consistency takes them, the K4 form included
+ *   axes9     [9] f64 host, row-major 3 x 3, or NULL for the identity: the axes the coordinates are measured along
+ *   trim_fraction  in [0, 0.5];  pixel_step >= 1
+ *   lo, hi    [3] f64 host;  n_points: the points that were ordered;  kernel_ms (nullable): hipEvent time of the kernels alone
+ * Definition, met bit for bit by the device and by tests/scene_bounds_np.py.  All arithmetic is f64, every operation is rounded on
+ * its own, nothing is contracted; comparisons with a NaN are false.
+ *   1. D and VALID are steps 1 and 2's validity of dmi_filter_depth_consistency: D_m = depth_m with -1 wherever best_cost_m >
+ *      threshold; a pixel is valid iff D > 0 and D < +inf.  A valid pixel (px, py) TAKES PART iff px % pixel_step == 0 and
+ *      py % pixel_step == 0; (px, py) are image coordinates, vtk row r is image row H-1-r.
+ *   2. w = the back-projection of step 2 of dmi_filter_depth_consistency, operation for operation.
+ *   3. s_a = (A[a][0]*w_0 + A[a][1]*w_1) + A[a][2]*w_2 for a = 0, 1, 2, A = axes9.  A point is COUNTED iff all three s_a are finite.
+ *      N = the number of counted points; *n_points = N.
+ *   4. The s_a of the counted points are ordered by the key bits ^ (bits >> 63 ? ~0 : 1 << 63) of their f64 bits: ascending key
+ *      order is numeric order, with -0.0 before +0.0.  k = min((uint64_t)(trim_fraction * (double)N), (N - 1) / 2).  lo[a] = the
+ *      element of rank k (0-based) of axis a, hi[a] = the element of rank N-1-k; the ranks are taken per axis, independently of the
+ *      other axes.  trim_fraction == 0 gives the exact minimum and maximum.
+ *   5. N == 0: DMI_OK, *n_points = 0, all six outputs NaN.
+ * Host data goes up in pieces of whole views, as many as fit 256 MiB (a single view larger than that goes up whole, as in
+ * dmi_filter_depth_consistency).  Device memory: 8 bytes per pixel and view plus the pieces; the points themselves are never stored.
+ * All arguments are checked before the device is touched.  DMI_ERR_INVALID_ARGUMENT, the message naming the argument: everything
+ * dmi_filter_depth_consistency refuses for the arguments the two calls share (a null depth, K4 or RT4; n < 1; W or H outside
+ * [1, 32768]; a NaN threshold when best_cost is given; a K4 outside the form, the message naming the view); a null lo, hi or
+ * n_points; a NaN or negative trim_fraction or one above 0.5; pixel_step < 1; an axes9 entry that is not finite; n*W*H >= 2^53.
+ * Then DMI_ERR_DEVICE without a device.  A refused call leaves lo, hi and *n_points untouched.  The call never exits and never
+ * throws; a failure's text is dmi_last_error(NULL)'s.  Synchronises. */
+int dmi_estimate_scene_bounds(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
+                              int32_t n, int32_t W, int32_t H, const double *axes9 /* nullable: identity */, double trim_fraction,
+                              int32_t pixel_step, int32_t device, double lo[3], double hi[3], uint64_t *n_points, double *kernel_ms);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

@@ -116,6 +116,12 @@ typedef struct dmi_cli_options {
   int64_t depth_consistency_min_views;   /* --depthConsistencyMinViews N: filter the depth maps before the fusion; -1: not given */
   double depth_consistency_tolerance;    /* --depthConsistencyTolerance (default 0) */
   double depth_consistency_rel_tolerance; /* --depthConsistencyRelTolerance (default 0.01) */
+  /* not in the reference (dmi_estimate_scene_bounds, dmi.h); appended to the struct.  With --gridAutoBounds grid_origin and grid_end
+   * are zero here, and so is whichever of grid_dims / grid_spacing was not given: the run derives them from the depth maps */
+  int32_t grid_auto_bounds;              /* --gridAutoBounds: the grid's box from the depth maps */
+  double grid_auto_bounds_trim;          /* --gridAutoBoundsTrim (default 0.005) */
+  double grid_auto_bounds_margin;        /* --gridAutoBoundsMargin (default 0.05) */
+  int64_t grid_auto_bounds_pixel_step;   /* --gridAutoBoundsPixelStep (default 1) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -136,7 +142,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * in the context that fused and trimmed by dmi_filter_isosurface_support before the component flags; --meshSupportArray writes the
  * final mesh's counts as the Int32 point array NbSupportingViews, behind RegionId and before the colours.  With
  * --depthConsistencyMinViews N every view is read into memory, the depths are filtered by dmi_filter_depth_consistency on the first
- * device and the filter fuses the filtered views (ReconstructionFilter::SetViews). */
+ * device and the filter fuses the filtered views (ReconstructionFilter::SetViews).  With --gridAutoBounds (--gridOrigin and
+ * --gridEnd absent) every view is read into memory as well, filtered first if that was asked for, and the grid's box is what
+ * dmi_estimate_scene_bounds gives along the grid's axes, plus a margin. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
