@@ -262,7 +262,8 @@ int class_table(dmi_context *ctx, const dmi::TileShape &sh, bool windows, TileAr
   t->classes = ctx->tables.classes.as<uint8_t>();
   if (windows) {
     t->win_origin = reinterpret_cast<dmi::WinPair *>(ctx->tables.classes.as<uint8_t>() + coarse_end);
-    t->win_delta = (int64_t)reinterpret_cast<intptr_t>(t->win_origin) - 16 * (int64_t)reinterpret_cast<intptr_t>(t->classes);
+    // (win_pair_index: the pair table has the class table's entries, fine_bytes of them at least, in blocks of 32 views)
+    t->n_class_bricks = (int64_t)t->wbricks_x * t->wbricks_y * t->bricks_z;
     t->win_recs = ctx->views.win_recs.as<dmi::WinRec>();
     t->foot_recs = ctx->views.foot_recs.as<dmi::FootRec>();
     t->vb_bytes = (int32_t)std::min<int64_t>(dmi::valid_bits_bytes(ctx->views.W, ctx->views.H), 0x7fffffff);

@@ -143,7 +143,7 @@ struct dmi_context {
     bool classes = false;
     int64_t class_bricks = 0;  // wave bricks of the last fuse
     int32_t bricks_z = 0, tk = 0;
-    const dmi::WinPair *win_origin = nullptr;  // the last tiled launch's pair table (nullptr: it had no windows)
+    const dmi::WinPair *win_origin = nullptr;  // the last tiled launch's pair table (nullptr: it had no windows); only asked whether there was one
     int32_t class_pitch = 0, first = 0, count = 0;
   } last;
 

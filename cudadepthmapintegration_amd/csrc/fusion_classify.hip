@@ -725,7 +725,18 @@ __global__ __launch_bounds__(256) void classify_kernel(const TileArgs a, const M
 // A wave is 64 consecutive bricks and walks over kOriginViews views, four class bytes per load; the view is
 // wave-uniform, so its camera record arrives through scalar loads (as in the fine pass), and the lanes that have the class are
 // neighbours in space: all of them or none, mostly.
-constexpr int kOriginViews = 8;   // views per workgroup (a multiple of 4): a brick's entries of one workgroup are ONE 128-byte line
+// A workgroup is kOriginBricks consecutive bricks x kOriginWaveSets sets of kOriginViews views: the SAME 64 bricks in all four
+// waves, each wave with eight views of one block of 32 (win_pair_index, fusion_launch_rules.h) -- what the workgroup writes is
+// then one run of 64 x 512 consecutive bytes of the pair table.
+// (-DDMI_WINPAIR_BRICK_MAJOR, the table as [brick][view]: four waves of different bricks with the same eight views; a brick's
+// entries of one workgroup are one 128-byte line, 4 KB from the next brick's)
+constexpr int kOriginViews = 8;   // views per wave (a multiple of 4)
+#ifdef DMI_WINPAIR_BRICK_MAJOR
+constexpr int kOriginBricks = 256, kOriginWaveSets = 1, kOriginAlign = 4;
+#else
+constexpr int kOriginBricks = 64, kOriginWaveSets = 4, kOriginAlign = kWinPairBlockViews;
+static_assert(kOriginViews * kOriginWaveSets == kWinPairBlockViews, "a workgroup's views are one block of the pair table");
+#endif
 constexpr uint32_t kNotWanted = 0xfffffffeu;  // (LDS only) the pair is not of the class: nothing is written for it
 template <bool ROT>
 __global__ __launch_bounds__(256) void window_origin_kernel(const TileArgs a, const MapRec *__restrict__ maps, int tk,
@@ -738,13 +749,21 @@ __global__ __launch_bounds__(256) void window_origin_kernel(const TileArgs a, co
   // apart from the next brick's), and as many read-modify-writes of class bytes.  Now the entries of the workgroup's 256 bricks x 8
   // views go through LDS and leave as whole 128-byte lines (eight lanes = a brick's eight views), and the class table is written
   // only for the exceptions: CLASS_NO_WINDOW on the few pairs without a window (1 % at cfg 3).
-  __shared__ WinPair tile[kOriginViews][256 + 1];  // [view][brick]; + 1: eight lanes reading a brick's views hit eight bank groups
+  // Those lines were still 4 KB apart, a brick's next line written by a workgroup 512 positions later.  With the table laid out
+  // by blocks of 32 views the workgroup's 64 bricks x 32 views are 32 KB in a row: lane after lane, 16 bytes each.
+  // [view][brick]; + 1: lanes reading a brick's consecutive views hit different bank groups (a row is 4 banks past a multiple of 64)
+  __shared__ WinPair tile[kOriginViews * kOriginWaveSets][kOriginBricks + 1];
+#ifdef DMI_WINPAIR_BRICK_MAJOR
   __shared__ int64_t rows[256];
+#endif
   const int bz_first = 2 * a.sbz_first;
   const int bz_count = min(2 * a.super_z, a.bricks_z - bz_first);
   const int64_t n_bricks = (int64_t)a.wbricks_x * a.wbricks_y * bz_count;
   const int lane = threadIdx.x & 63;
-  const int64_t local = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  // this lane's brick within the workgroup, and which of the workgroup's sets of group_views views its wave walks over
+  const int tb = threadIdx.x % kOriginBricks;
+  const int wset = kOriginWaveSets > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x / kOriginBricks) : 0;  // wave-uniform, and provably so
+  const int64_t local = (int64_t)blockIdx.x * kOriginBricks + tb;
   const bool exists = local < n_bricks;
   const int bx = (int)(local % a.wbricks_x);
   const int64_t t = local / a.wbricks_x;
@@ -762,15 +781,23 @@ __global__ __launch_bounds__(256) void window_origin_kernel(const TileArgs a, co
     wxa = row4(a.g + 0, gx, gy, gz), wya = row4(a.g + 4, gx, gy, gz), wza = row4(a.g + 8, gx, gy, gz);
   }
   const int m_begin = a.first_map, m_end = a.first_map + a.n_maps;
-  const int g_lo = (m_begin & ~3) + blockIdx.y * group_views;
+  // group_views (8, or 4 on a small grid: launch_window_origins) views per wave, kOriginWaveSets times as many per workgroup: a
+  // block of 32 views, or on a small grid a half of one -- a brick's entries of the workgroup are then 256 of its 512 bytes
+  const int g_wg = (m_begin & ~(kOriginAlign - 1)) + blockIdx.y * (group_views * kOriginWaveSets);
+  const int slot0 = wset * group_views;  // of this wave's views in the tile
+  const int g_lo = g_wg + slot0;
+#ifdef DMI_WINPAIR_BRICK_MAJOR
   rows[threadIdx.x] = row;
+#endif
   uint32_t held[kOriginViews / 4];
 #pragma unroll
   for (int g = 0; g < kOriginViews / 4; ++g) {
     const int m4 = g_lo + 4 * g;
     held[g] = (eligible && 4 * g < group_views && m4 < m_end) ? *reinterpret_cast<const uint32_t *>(classes + row + m4) : 0u;
+    if (4 * g < group_views) {  // the wave's own slots: nobody else writes them before the barrier
 #pragma unroll
-    for (int q = 0; q < 4; ++q) tile[4 * g + q][threadIdx.x].origin = kNotWanted;
+      for (int q = 0; q < 4; ++q) tile[slot0 + 4 * g + q][tb].origin = kNotWanted;
+    }
   }
 #pragma unroll
   for (int g = 0; g < kOriginViews / 4; ++g) {
@@ -840,13 +867,14 @@ __global__ __launch_bounds__(256) void window_origin_kernel(const TileArgs a, co
       }
       if (want) {
         if (wp.origin != kNotWanted)
-          tile[4 * g + q][threadIdx.x] = wp;
+          tile[slot0 + 4 * g + q][tb] = wp;
         else
           classes[row + m] = (uint8_t)(c | CLASS_NO_WINDOW);  // the exception: a byte store of its own
       }
     }
   }
   __syncthreads();
+#ifdef DMI_WINPAIR_BRICK_MAJOR
   // a brick's eight entries are one 128-byte line: eight consecutive lanes write it
   const int v = threadIdx.x & (kOriginViews - 1);
   const int m = g_lo + v;
@@ -858,6 +886,21 @@ __global__ __launch_bounds__(256) void window_origin_kernel(const TileArgs a, co
       if (wp.origin != kNotWanted) origins[rows[b] + m] = wp;
     }
   }
+#else
+  // The workgroup's entries in the table's order -- brick after brick, a brick's views of this block side by side -- 16 bytes
+  // per lane in consecutive lanes: a wave's store is 1 KB in a row.  Entries of bricks beyond the slab, of views beyond the
+  // launch's and of pairs that are not wanted were never filled in: nothing is written for them, in the table's bounds or out.
+  const int wg_views = group_views * kOriginWaveSets;  // 32 or 16
+  const int lg = 31 - __builtin_clz((unsigned)wg_views);
+  const int64_t brick0 = (int64_t)blockIdx.x * kOriginBricks + (int64_t)bz_first * a.wbricks_y * a.wbricks_x;  // over the whole grid
+  for (int e = threadIdx.x; e < kOriginBricks * wg_views; e += 256) {
+    const int b = e >> lg, v = e & (wg_views - 1);
+    const int m = g_wg + v;
+    if (m >= m_end) continue;
+    const WinPair wp = tile[v][b];
+    if (wp.origin != kNotWanted) origins[win_pair_index(brick0 + b, m, a.n_class_bricks)] = wp;
+  }
+#endif
 }
 
 // ---- heavy bricks first -------------------------------------------------------------------------------
@@ -1229,11 +1272,15 @@ hipError_t launch_window_origins(const TileArgs &a, const MapRec *maps_dev, int 
   if (n_bricks <= 0) return hipSuccess;
   // (a wave walks over its workgroup's views one after the other: on a small grid fewer views per workgroup, so that the chip
   // has eight workgroups per CU -- at 256^3 x 64 views 128 workgroups took 44 us)
-  const int64_t brick_groups = (n_bricks + 255) / 256;
-  const int span = a.first_map + a.n_maps - (a.first_map & ~3);
+  // (group_views is a wave's views; the workgroup's four waves take as many each, side by side in one block of 32 views of the
+  // pair table: 32 views per workgroup, 16 on a small grid)
+  const int64_t brick_groups = (n_bricks + kOriginBricks - 1) / kOriginBricks;
+  const int span = a.first_map + a.n_maps - (a.first_map & ~(kOriginAlign - 1));
   int group_views = kOriginViews;
-  while (group_views > 4 && brick_groups * ((span + group_views - 1) / group_views) < 2048) group_views >>= 1;
-  const dim3 grid((unsigned)brick_groups, (unsigned)((span + group_views - 1) / group_views));
+  const auto view_groups = [&](int gv) { return (span + gv * kOriginWaveSets - 1) / (gv * kOriginWaveSets); };
+  while (group_views > 4 && brick_groups * view_groups(group_views) < 2048) group_views >>= 1;
+  if (brick_groups > (int64_t)0x7fffffff || a.n_class_bricks > (int64_t)0x7fffffff) return hipErrorInvalidConfiguration;
+  const dim3 grid((unsigned)brick_groups, (unsigned)view_groups(group_views));
   if (a.rotated)
     hipLaunchKernelGGL((window_origin_kernel<true>), grid, dim3(256), 0, stream, a, maps_dev, tk, classes, a.win_origin, group_views);
   else

@@ -179,7 +179,7 @@ constexpr float kWinC1 = 0.5f - 0x1p-15f;  // what is left of 1/2 after every c.
 constexpr int kWinReach = kWinAnchorY ? kWindowRows - kWinAnchorY : kWindowRows - 1;
 // the brick's c.z may vary by this factor at most for the pair to get a window (bounds |hw| by the threshold's own c.z)
 constexpr double kWinCzRatio = 1.25;
-// Per windowed (brick, view) pair, TileArgs::win_origin[brick * class_pitch + view]: the window's first pixel (padded-image
+// Per windowed (brick, view) pair, TileArgs::win_origin[win_pair_index(brick, view, bricks)]: the window's first pixel (padded-image
 // coordinates, x0 | y0 << 16) and the fp32 images of hw.x, hw.y and c.z at voxel (0, 0, 0) of the brick
 struct alignas(16) WinPair {
   uint32_t origin;
@@ -274,12 +274,13 @@ struct TileArgs {
   // brick counters of the persistent workgroups, one per XCD at [16 * xcd]; zeroed by the table kernel of every launch
   int32_t *queue_heads;
   // Windows of the FREE column (round 4; WinPair since round 5): for a pair of class MIXED_FREE_OR_NODEPTH,
-  // win_origin[brick * class_pitch + view] holds the first pixel of a kWindowCols x kWindowRows window that holds the reference's
-  // pixel of every voxel of the brick, and the window-relative numerators at the brick's first voxel (window_origin_kernel,
-  // fusion_classify.hip).  The fusion kernel reaches the entry from the brick's class row: (WinPair *)(win_delta + 16 *
-  // (intptr_t)row) + view.
+  // win_origin[win_pair_index(brick, view, n_class_bricks)] holds the first pixel of a kWindowCols x kWindowRows window that holds
+  // the reference's pixel of every voxel of the brick, and the window-relative numerators at the brick's first voxel
+  // (window_origin_kernel, fusion_classify.hip).  The table is laid out [block of 32 views][brick][32 views]
+  // (fusion_launch_rules.h); the fusion kernel gets the brick's number from its class row, (row - classes) / class_pitch.
+  // (-DDMI_WINPAIR_BRICK_MAJOR: win_origin[brick * class_pitch + view], the table indexed like the class table)
   WinPair *win_origin;
-  int64_t win_delta;  // = win_origin - 16 * classes (as integers): the pair table is indexed like the class table
+  int64_t n_class_bricks;  // rows of the class table: wbricks_x * wbricks_y * bricks_z, the bricks of the WHOLE grid
   const WinRec *win_recs;  // [n_views]
   const FootRec *foot_recs;  // [n_views]
   int32_t vb_bytes, vb_rowskip;  // as TileMapRec's (the same for every view of a context)

@@ -123,6 +123,25 @@ inline int32_t class_table_pitch(int32_t resident_views) {
   return pitch;
 }
 
+// Entry of a (brick, view) pair in the window-pair table (TileArgs::win_origin), in entries of one WinPair.
+// brick: the class table's brick number over the WHOLE grid, (bz * wbricks_y + by) * wbricks_x + bx (a slab launch keeps
+// it); view: the resident view; n_class_bricks: wbricks_x * wbricks_y * bricks_z.
+// [block of 32 views][brick][32 views]: the fusion kernel reads a brick's 32 views of a block as one piece of 512 bytes, as it
+// did from a [brick][view] table, and window_origin_kernel -- a workgroup of 64 consecutive bricks and one block -- writes
+// 64 x 512 consecutive bytes, where the brick-major table had a line of it every 4 KB.  class_table_pitch is a
+// multiple of 32, so the blocks tile the table: the index is a bijection onto [0, n_class_bricks * pitch).
+// -DDMI_WINPAIR_BRICK_MAJOR builds both kernels for the [brick][view] table again (tools/exp_list_winpair_layout.txt);
+// they do not call this function then.
+#if defined(__HIP__)  // (compiled as HIP: the kernels call it)
+#define DMI_RULES_HD __host__ __device__
+#else
+#define DMI_RULES_HD
+#endif
+constexpr int kWinPairBlockViews = 32;
+DMI_RULES_HD inline int64_t win_pair_index(int64_t brick, int32_t view, int64_t n_class_bricks) {
+  return (((int64_t)(view >> 5) * n_class_bricks + brick) << 5) + (view & 31);
+}
+
 // No sum of the launch can be -0.0 (the launches the kernel's ZF instantiations serve, fusion_tile.hip), and the +0.0 adds of the
 // pairs far behind every surface can be dropped (TileArgs::behind_mask):
 // +0.0 adds are no-ops unless a sum can be -0.0 (only an uploaded grid can bring one) or hits are counted

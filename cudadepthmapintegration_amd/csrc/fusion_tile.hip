@@ -584,6 +584,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
   // once: every entry comes from HBM)
   // (round 5: WinPair entries of 16 bytes, 32 views at a time: lane l holds dwords 2l and 2l + 1 of the block's 128, i.e. view v's
   // origin and a.x in lane 2 (v & 31), its a.y and a.cz in the next lane)
+  // (the table is laid out [block of 32 views][brick][32 views], win_pair_index: those 512 bytes are one piece of it)
   [[maybe_unused]] uint32_t pair_a = 0, pair_b = 0;
   for (int wbase = first_map & ~7; wbase < m_end; wbase += 8) {
     if constexpr (WIN) {
@@ -591,8 +592,19 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         const kernarg_t ko = KFRESH();
         if (ko->win_origin) {
           typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-          const u32x2 *row = reinterpret_cast<const u32x2 *>(ko->win_delta + 16 * (int64_t)reinterpret_cast<intptr_t>(crow));
-          const u32x2 pr = row[2 * (wbase & ~31) + lane];
+          // the brick's 512 bytes of this block of views, win_pair_index(brick, wbase & ~31, n_class_bricks): all of the address
+          // but the lane's 8 bytes is formed on the scalar side, from this read of the argument block and the class row -- its
+          // offset is the brick's number times the pitch, a power of two (class_table_pitch) -- so nothing new lives across the column
+          const uint64_t row_off = (uint64_t)(reinterpret_cast<intptr_t>(crow) - reinterpret_cast<intptr_t>(ko->classes));
+#ifdef DMI_WINPAIR_BRICK_MAJOR
+          const u32x2 *row = reinterpret_cast<const u32x2 *>(reinterpret_cast<intptr_t>(ko->win_origin) + 16 * (int64_t)row_off) + 2 * (wbase & ~31);
+#else
+          const uint64_t brick = row_off >> __builtin_ctz((unsigned)ko->class_pitch);
+          // (bricks < 2^31, launch_classify_bricks; views < 2^16: a 32 x 32 -> 64 bit product)
+          const uint64_t block_first = (uint64_t)(uint32_t)ko->n_class_bricks * (uint32_t)(wbase >> 5);
+          const u32x2 *row = reinterpret_cast<const u32x2 *>(ko->win_origin + ((block_first + brick) << 5));
+#endif
+          const u32x2 pr = row[lane];
           pair_a = pr.x;
           pair_b = pr.y;
         }
@@ -651,7 +663,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
     }
     // ---- A pair with a WINDOW of validity bits (round 4): the FREE column without a gather per voxel.  The
     // pair has a window (its class byte carries no CLASS_NO_WINDOW): window_origin_kernel has proven that every voxel's reference pixel lies in
-    // the 32 x 64 pixels that start at (x0, y0) = TileArgs::win_origin[brick][view] (padded-image coordinates).  Lane r fetches
+    // the 32 x 64 pixels that start at (x0, y0) = the pair's entry of TileArgs::win_origin (padded-image coordinates).  Lane r fetches
     // row y0 + r of the view's validity bits (two dwords from one or two 128-byte tiles, funnel-shifted to start at x0): two
     // coalesced loads per (brick, view), in flight while the column is set up.  A voxel asks the lane that holds its row with
     // ds_bpermute_b32.  The candidate is formed in window-relative coordinates: rpm = fl32(hw * rcp + (1.5 * 2^23 + anchor)) is an
