@@ -3,8 +3,8 @@
 // do in the reference once the depth maps are resident.  fuse_run is a sequence of steps -- the general kernel's arguments, the
 // launch decisions (fusion_launch_rules.h), the tiled launch's geometry, its tables, the tuning hooks, the timed launch, the
 // bookkeeping --; every table grows through dmi::ensure_idle_buffers or dmi::ensure_buffer (dmi_context.h), so a fusion of the
-// same views into the same grid allocates, frees, fills and waits for nothing.  dmi_capi.hip has the context's life cycle and
-// the views.
+// same views into the same grid allocates, frees, fills and waits for nothing.  dmi_capi.hip has the context's life cycle,
+// dmi_capi_views.hip the views.
 #include "dmi_context.h"
 
 #include <algorithm>

@@ -1,6 +1,6 @@
 // dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
 // (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
-// filter, the smoother, the decimation, the support trim, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip and dmi_capi_fuse.hip have the rest.
+// filter, the smoother, the decimation, the support trim, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip, dmi_capi_views.hip and dmi_capi_fuse.hip have the rest.
 #include "dmi_context.h"
 
 #include <algorithm>
@@ -785,7 +785,7 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   // (a failure from here on leaves the context's mesh, its normals, regions, colours and counts as they were: no kernel writes
   // them, and the buffers are swapped only at the end)
   // The records as they are now (h_maps is pageable: the copy is complete for the host when the call returns).  Not ctx->views.maps:
-  // that array is brought up to date only by a fusion (sync_maps in dmi_capi.hip, with the tiled kernel's records and the hit
+  // that array is brought up to date only by a fusion (sync_maps in dmi_capi_fuse.hip, with the tiled kernel's records and the hit
   // counters), so it lags behind views added since, and bringing it up to date from here would tie this call to the fusion's
   // bookkeeping; 208 B a view per call is the price.
   DMI_HIP(ctx, hipMemcpyAsync(sup.maps.ptr, ctx->views.h_maps.data(), n_views * sizeof(dmi::MapRec), hipMemcpyHostToDevice, ctx->stream));

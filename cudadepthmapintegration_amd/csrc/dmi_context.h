@@ -1,6 +1,6 @@
 // dmi_context.h -- the context behind the C ABI of include/dmi.h, in groups, and the helpers its translation units share
-// (dmi_capi.hip: creation, destruction, views, grid transfer, info, timings, probes; dmi_capi_fuse.hip: the fusion launch and the
-// diagnostics that read it; dmi_capi_mesh.hip: point data and the iso-surface).  Every device allocation is a dmi::DeviceBuffer
+// (dmi_capi.hip: creation, destruction, grid transfer, info, timings, probes; dmi_capi_views.hip: the resident views;
+// dmi_capi_fuse.hip: the fusion launch and the diagnostics that read it; dmi_capi_mesh.hip: point data and the iso-surface).  Every device allocation is a dmi::DeviceBuffer
 // (dmi_buffer.h, capacity in bytes) grown by one of two rules, every group has a release().  The colour context
 // (dmi_color_context.h, dmi_capi_color.hip) is built from the same parts and exception guard.  Private: never installed.
 #pragma once
@@ -58,13 +58,13 @@ struct dmi_context {
 
   bool finite_bounded = true;  // grid descriptor magnitudes allow the K shortcuts
 
-  // ---- fusion (dmi_capi.hip, dmi_capi_fuse.hip): every capacity is in bytes ----
+  // ---- fusion (dmi_capi.hip, dmi_capi_views.hip, dmi_capi_fuse.hip): every capacity is in bytes ----
   struct Views {  // the resident views: their store, their records, the staging of an upload
     int32_t W = 0, H = 0;
     bool depth_f64 = false;
     int k_mode = dmi::K_PINHOLE;          // the least structured K among the resident views (dmi_info)
     std::vector<uint8_t> view_k_mode;     // per view: dmi::KMode of its K
-    std::vector<uint8_t> view_tile_ok;    // per view: meets the tiled kernel's per-view preconditions (make_tile_rec)
+    std::vector<uint8_t> view_tile_ok;    // per view: meets the tiled kernel's per-view preconditions (ViewRecords::tile_ok)
     double max_tile_err = 0.0;            // largest TileMapRec::err among the resident views
     dmi::PyramidDesc pyramid{};           // geometry of every view's depth min/max pyramid
     // one per dmi_add_views call; allocated and freed whole by the all-or-nothing upload (upload_batch, promote_to_f64)
@@ -250,7 +250,6 @@ int drain_events(dmi_context *ctx);                            // the pending fu
 int drain_c2p(dmi_context *ctx);                               // ... and the pending cell-to-point pass's
 int flush_zero_fill(dmi_context *ctx);
 inline size_t grid_elem(const dmi_context *c) { return c->opt.grid_dtype == DMI_F64 ? 8 : 4; }
-bool grid_axis_aligned(const dmi_grid_desc &g);
 // Preconditions of the tiled kernel that do not depend on the view (the per-view part: Views::view_tile_ok)
 bool tile_eligible(const dmi_context *ctx);
 // Views [first, first + count) into the cell layers [z_first, z_first + z_count): what every fusing entry point ends in

@@ -1,6 +1,7 @@
-// fusion_kernels.h -- device-side records and launchers shared by the C ABI (dmi_capi.hip, dmi_capi_fuse.hip)
-// and the kernels (fusion_kernels.hip: general kernel + upload helpers; fusion_tile.hip: the
-// register-tiled kernel for axis-aligned grids and pinhole cameras).  gfx950 only.
+// fusion_kernels.h -- device-side records and launchers shared by the C ABI (dmi_capi.hip, dmi_capi_views.hip,
+// dmi_capi_fuse.hip) and the kernels (fusion_kernels.hip: general kernel + upload helpers; fusion_tile.hip: the
+// register-tiled kernel for axis-aligned grids and pinhole cameras).  gfx950 only.  The per-view records (MapRec, TileMapRec,
+// WinRec, FootRec), their constants and the host arithmetic that fills them: view_records.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include <string.h>
 
 #include "fusion_launch_rules.h"  // the variant bits and the thresholds of the launch decisions
+#include "view_records.h"         // the per-view records, the validity maps' and the window column's constants
 
 struct dmi_context;  // include/dmi.h
 
@@ -18,8 +20,6 @@ namespace dmi {
 // dmi_grid_device_pointer it leaves the context's "no sum is -0.0" bookkeeping alone (dmi_capi.hip)
 int grid_pointer_for_sums(::dmi_context *ctx, void **ptr);
 
-// One depth map as the general kernel (and the exact fallback of the tiled kernel) reads it.  The loop
-// index over maps is wave-uniform, so a record arrives through scalar loads into SGPRs: no VGPRs, no LDS.
 // One tile of a depth table's min/max pyramid (level L: 2^L x 2^L pixels).  dmin/dmax bound every value of
 // the tile that is neither the -1 sentinel nor a NaN (rounded outward to f32); flags say what else is there.
 struct alignas(16) DepthTile {
@@ -47,138 +47,11 @@ struct PyramidDesc {
   int32_t offset[kPyramidMaxLevels];      // first tile of each level within a view's pyramid
 };
 
-struct alignas(16) MapRec {
-  double rt[12];      // rows 0..2 of [R|T]   (reference: matrixTR, cu:159,172)
-  double k[12];       // rows 0..2 of the 4x4 K (reference: matrixK, cu:159,176)
-  const void *depth;  // W*H depth table, float or double, image row order (row 0 = TOP row: the
-                      // reference's bottom-up vtk order, cu:141-149, is flipped once at upload)
-  const DepthTile *pyramid;  // this view's min/max pyramid (PyramidDesc::total_tiles entries)
-};
-static_assert(sizeof(MapRec) == 208, "MapRec layout");
-
-// What the tiled kernel needs per map (scalar loads, 128 B).  Only cz -- the camera-space depth that
-// enters the ray potential (cu:207) -- is evaluated in the reference's exact arithmetic; the
-// homogeneous pixel coordinates hx, hy only select a pixel, so the fast path evaluates them as an
-// affine function of the (axis-aligned) world coordinates and proves its choice (DESIGN.md
-// "Tiled kernel: proof obligations"); anything unproven goes through the exact expression.
-struct alignas(16) TileMapRec {
-  double rz0, rz1, rz3;    // RT row 2: r20, r21, r23 (r22 * wz(k) comes from the cz table)
-  double px, py, pz, p0;   // hx ~ px*wx + py*wy + pz*wz + p0   (row 0 of K*[R|T])
-  double qx, qy, qz, q0;   // hy ~ qx*wx + qy*wy + qz*wz + q0   (row 1 of K*[R|T])
-  double dhx, dhy;         // increments of hx, hy per voxel step along k
-  double err;              // bound on |hx_ref - hx_fast| and |hy_ref - hy_fast| (absolute)
-  const void *depth;       // same table as MapRec::depth
-  double cz_err;           // rotated grids: bound on |computed c.z - real c.z| (0 for axis-aligned grids, where the
-                           // computed c.z is monotone in every index and needs no margin)
-  double errk;             // what the fusion kernel multiplies by 1/h.z in its acceptance test: err, 2^16 * errz and 2^-22
-                           // times a bound on h.z over the grid, so that the test compares with the constant 1/2
-  // general K (third row not 0 0 1 0, cu:176): h.z ~ sx*wx + sy*wy + sz*wz + s0 (row 2 of K*[R|T]) and its step per
-  // voxel along k; errz bounds |h.z_ref - h.z_affine|.  For a pinhole K these restate RT row 2 and errz is 0.
-  double sx, sy, sz, s0, dhz, errz;
-  // Pinhole view on an axis-aligned grid: the same two rows in pixel coordinates measured from the image centre
-  // (cxc, cyc) = (W / 2, H / 2): hx'' = hx - cxc*c.z, i.e. row 0 of K*[R|T] minus cxc times row 2 of [R|T] (and hy''
-  // likewise).  round(h.x/h.z) = cxc + round(hx''/h.z) in exact arithmetic, |u''| <= W/2 halves what a relative error
-  // costs in pixels, and the fusion kernel's two-tier pixel selection (fusion_tile.hip "tier 1") works in them; cerr,
-  // cerrk: err and errk for these rows.  The classification kernels keep reading px .. q0.
-  double cpx, cpy, cpz, cp0, cqx, cqy, cqz, cq0;
-  double cdhx, cdhy, cerrk;
-  // tier 1 of the pixel selection: the centred numerators, c.z and the acceptance threshold as fp32 affine functions of
-  // the voxel's position in its column: steps per voxel of hx'', hy'', c.z and of the threshold
-  // c1*c.z - e1 (c1 = 1/2 - 2^-20, e1 the absolute margin of the view; +inf when the view does not qualify)
-  float t1_dhx, t1_dhy, t1_dcz, t1_dthr;
-  float t1_e1, t1_c1;  // e1 = t1_e1 + t1_erel * (max(|hx''|, |hy''|) at the column's first voxel + t1_hspan)
-  float t1_erel, t1_hspan;
-  int32_t t1_cidx;  // W * cyc + cxc: pixel index of the image centre
-  int32_t t1_ok;  // 0: tier 1 never accepts (t1_e1 = +inf); 1: e1 is the view's constant; 2: e1 per lane (t1_b)
-  // Validity map of the view (round 3): one byte per pixel, 1 = the pixel holds a depth (anything but the -1 sentinel), in
-  // tiles of 8 image rows over the image and its margin (kValidMargin): with X = x + margin, Y = y + margin and Wp = W + 2 margin,
-  // byte (x, y) at ((Y >> 3) * Wp + X) * 8 + (Y & 7), valid_map_bytes(W, H) in all.  The FREE column of
-  // the fusion kernel asks only "does my pixel hold a depth?"; an 8 x 8-lane patch of such questions touches a quarter of the
-  // cache lines in this layout and a quarter of the bytes, and costs the texture addresser half of what the same gather from
-  // the row-major f32 table costs (profiles/r06q_microbench_gather.txt).
-  const uint8_t *valid;
-  // ... and what turns a centred pixel into a byte of that map (fusion_tile.hip, FREE column), the same for every view of a
-  // context but read with the record, in the same scalar loads: (cyc + margin - 3.5) / 8, 8 Wp - 8, 8 (cxc + margin) + cyc + margin, valid_map_bytes
-  float vm_c0, vm_w8;
-  int32_t vm_base, vm_bytes;
-  // Validity BITS of the view (round 4): one bit per pixel of the padded image (the same margin), in tiles of 32 x 32 pixels =
-  // 32 dwords = one 128-byte line: bit (X & 31) of dword ((Y >> 5) * tiles_x + (X >> 5)) * 32 + (Y & 31), valid_bits_bytes(W, H)
-  // in all.  The FREE column's window form (fusion_tile.hip) fetches, per (brick, view), the 32 x 64 pixel window that holds
-  // every voxel's pixel -- one row per lane, two dword loads from one or two lines each -- and asks it with ds_bpermute_b32.
-  const uint32_t *vbits;
-  int32_t vb_bytes;    // valid_bits_bytes(W, H): the buffer range of one view's bits
-  int32_t vb_rowskip;  // (tiles_x - 1) * 128: what a step to the next tile row adds beyond the 128 bytes of the tile itself
-  int32_t vb_mx, vb_my;  // 0x4B400000 + margin + W / 2 (H / 2): the bits of the float 1.5 * 2^23 + (centre of the padded image)
-  // t1_ok == 2 (round 4): the view has no positive lower bound of c.z over the grid -- its camera stands inside or next to the
-  // volume -- so the bound |P| <= pmax that the margin e1 needs is formed per lane and (brick, view) from the column's own c.z:
-  // e1 = t1_e1 + t1_b * (HB / min c.z of the column + 1) + t1_erel * HB (fusion_tile.hip)
-  float t1_b;
-  int32_t vb_pad;
-};
 #ifndef DMI_TIER1
 #define DMI_TIER1 1  // 0: every instantiation selects its pixels in fp64 only (A/B builds, tools/exp_list*.txt)
 #endif
-// The maps carry a margin of kValidMargin pixels of "no depth" on every side: a pixel that far outside the image reads as a
-// hole, so the FREE column, which has no range test, also serves pairs whose footprint sticks out of the image by less (4b.9).
-constexpr int kValidMargin = 32;  // a multiple of 8 (whole tile rows)
-// A pixel with a depth holds this byte, one without 0: ((1 << byte) - 1) << 20 (one v_bfm_b32) is then the high word of the
-// double 1.0 or +0.0 that the FREE column multiplies its constant with (fusion_tile.hip, phase B)
-constexpr unsigned kValidByte = 10;
-__host__ __device__ inline int64_t valid_map_bytes(int W, int H) {
-  return (int64_t)((H + 2 * kValidMargin + 7) / 8) * (W + 2 * kValidMargin) * 8;
-}
-// the same image in bits (TileMapRec::vbits): tiles of 32 x 32 pixels, one column of tiles more than the padded image needs (a
-// window's second dword may lie in it)
-__host__ __device__ inline int valid_bits_tiles_x(int W) { return (W + 2 * kValidMargin + 31) / 32 + 1; }
-__host__ __device__ inline int valid_bits_tiles_y(int H) { return (H + 2 * kValidMargin + 31) / 32; }
-__host__ __device__ inline int64_t valid_bits_bytes(int W, int H) { return (int64_t)valid_bits_tiles_x(W) * valid_bits_tiles_y(H) * 128; }
-// the window of the FREE column: kWindowCols x kWindowRows pixels (a dword per lane); TileArgs::win_origin holds the window's
-// first pixel for the pair.  A launch with windows gives one to nearly every pair of class MIXED_FREE_OR_NODEPTH (99 % at cfg 3),
-// so the class byte marks the EXCEPTIONS: CLASS_NO_WINDOW, written by window_origin_kernel for the few pairs whose footprint
-// does not fit (until round 5 the bit said "has a window": sixteen million scattered read-modify-writes per fusion)
-constexpr int kWindowCols = 32, kWindowRows = 64;
+// class byte of a pair of class MIXED_FREE_OR_NODEPTH that has no window (kWindowCols, view_records.h)
 constexpr uint8_t CLASS_NO_WINDOW = 0x20;
-static_assert(sizeof(TileMapRec) == 368, "TileMapRec layout");
-
-// What the window form of the FREE column needs of a view (round 5): ONE 64-byte line, all fp32, fetched with one scalar load per
-// (brick, view) -- the 368-byte TileMapRec took five or six dependent batches of them, which with four waves per SIMD was what
-// the column waited for.  The centred numerators hx'', hy'' (TileMapRec::cpx ...) and c.z are affine in the voxel's indices; the
-// column works in coordinates relative to the WINDOW's centre Xc = first pixel + (kWinAnchorX, kWinAnchorY), hw = h'' - Xc * c.z,
-// whose value at the brick's first voxel window_origin_kernel has formed in fp64 (WinPair): |hw| <= (half a window + 1/2) * c.z, so
-// every fp32 rounding on the way costs 2^-24 of some thirty c.z instead of 2^-24 of up to W/2 c.z.  d*: steps of (hx'', hy'') per
-// voxel along i, j, k; c*: (step of c.z, c1 times it) -- the second half steps the acceptance threshold c1 * c.z - e_abs.
-struct alignas(64) WinRec {
-  const uint32_t *vbits;  // TileMapRec::vbits
-  float di[2], dj[2], dk[2];
-  float ci[2], cj[2], ck[2];
-  float e_abs;            // the absolute part of the margin (rounded up); +inf: the view has no windows
-  float c1;               // kWinC1
-};
-static_assert(sizeof(WinRec) == 64, "WinRec is one cache line");
-// What window_origin_kernel adds to a pair's anchor to reach the brick's eight corner voxels (corner c: bit 0 = i, 1 = j, 2 = k):
-// (hx'', hy'', c.z) at voxel (7 or 0, 7 or 0, tk - 1 or 0) minus their values at (0, 0, 0), fp32, for 8- and 16-voxel columns;
-// ferr: the centred rows' error bound cerr (4d.1), rounded up.  Wave-uniform: scalar operands of the kernel's packed adds.
-struct alignas(64) FootRec {
-  float s8[8][4];   // [corner] = (dhx'', dhy'', dcz, unused)
-  float s16[8][4];
-  float ferr, pad[15];
-};
-static_assert(sizeof(FootRec) == 320, "FootRec layout");
-// The window column counts its coordinates from the window's CENTRE, first pixel + (kWinAnchorX, kWinAnchorY): |hw| <= (half the
-// window + 1/2) * c.z, half of what the corner gave, and so are the c.z-proportional roundings that c1 has to absorb (4e.6).
-// -DDMI_WIN_CORNER_ANCHOR counts from the first pixel again, with the wider band that needs (same results: an A/B switch for
-// tools/gpu_exp.py, tools/exp_list_window_centre.txt).
-#ifdef DMI_WIN_CORNER_ANCHOR
-constexpr int kWinAnchorX = 0, kWinAnchorY = 0;
-constexpr float kWinC1 = 0.5f - 0x1p-14f;
-#else
-constexpr int kWinAnchorX = kWindowCols / 2, kWinAnchorY = kWindowRows / 2;
-constexpr float kWinC1 = 0.5f - 0x1p-15f;  // what is left of 1/2 after every c.z-proportional rounding of the window column (4e.6)
-#endif
-// an accepted candidate's magnitude stays below (this + 1/2) * kWinCzRatio + 3 (make_centred_rows)
-constexpr int kWinReach = kWinAnchorY ? kWindowRows - kWinAnchorY : kWindowRows - 1;
-// the brick's c.z may vary by this factor at most for the pair to get a window (bounds |hw| by the threshold's own c.z)
-constexpr double kWinCzRatio = 1.25;
 // Per windowed (brick, view) pair, TileArgs::win_origin[win_pair_index(brick, view, bricks)]: the window's first pixel (padded-image
 // coordinates, x0 | y0 << 16) and the fp32 images of hw.x, hw.y and c.z at voxel (0, 0, 0) of the brick
 struct alignas(16) WinPair {
@@ -186,14 +59,6 @@ struct alignas(16) WinPair {
   float ax, ay, acz;
 };
 static_assert(sizeof(WinPair) == 16, "WinPair layout");
-
-// How much of K's structure the uploaded views share; checked on the host, value-identical
-// shortcuts proven in DESIGN.md ("K specialisation").
-enum KMode : int {
-  K_GENERAL = 0,       // any rows 0..2: the reference expression in full (cu:90-92)
-  K_PINHOLE_SKEW = 1,  // [fx s cx 0; 0 fy cy 0; 0 0 1 0]
-  K_PINHOLE = 2        // ... with s == 0
-};
 
 struct FuseArgs {
   int32_t nx, ny, nz;  // voxels (cells) per axis

@@ -1,7 +1,7 @@
 // fusion_tile.hip -- register-tiled TSDF fusion kernel for gfx950 (MI355X): the fast path of dmi_fuse.
 //
-// Preconditions (checked on the host, dmi_capi.hip `tile_eligible` / `view_tile_ok`): all magnitudes are finite and
-// bounded, thickness >= 0 and delta >= 0; a view's K may be anything (a third row other than 0 0 1 0 takes the GENK
+// Preconditions (checked on the host: `tile_eligible`, dmi_capi.hip, and `ViewRecords::tile_ok`, view_records.h): all magnitudes
+// are finite and bounded, thickness >= 0 and delta >= 0; a view's K may be anything (a third row other than 0 0 1 0 takes the GENK
 // instantiation).  Views no fast path takes run the general kernel (fusion_kernels.hip).  The grid may have any axes
 // (the reference CLI builds the matrix from gridVecX/Y/Z, main.cxx:345-359): what follows describes the axis-aligned
 // case (3x3 part diagonal, the default); the ROT instantiation for rotated axes is described at the kernel.
