@@ -120,6 +120,7 @@ ABI_SYMBOLS = [
     "dmi_color_process_isosurface", "dmi_download_isosurface_colors", "dmi_get_isosurface_color_kernel_ms",
     "dmi_filter_isosurface_support", "dmi_download_isosurface_support", "dmi_get_isosurface_support_kernel_ms",
     "dmi_get_isosurface_support_pass_ms", "dmi_decimate_isosurface_placed",
+    "dmi_fill_isosurface_holes", "dmi_get_isosurface_holes_kernel_ms", "dmi_get_isosurface_holes_pass_ms",
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds",
@@ -215,6 +216,10 @@ def load() -> ctypes.CDLL:
         L.dmi_get_isosurface_decimate_pass_ms.argtypes = [vp, dp]
     if hasattr(L, "dmi_decimate_isosurface_placed"):
         L.dmi_decimate_isosurface_placed.argtypes = [vp, dbl, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "dmi_fill_isosurface_holes"):
+        L.dmi_fill_isosurface_holes.argtypes = [vp, ctypes.c_uint64] + [ctypes.POINTER(ctypes.c_uint64)] * 4
+        L.dmi_get_isosurface_holes_kernel_ms.argtypes = [vp, dp]
+        L.dmi_get_isosurface_holes_pass_ms.argtypes = [vp, dp]
     if hasattr(L, "dmi_filter_isosurface_support"):
         L.dmi_filter_isosurface_support.argtypes = [vp, i32, dbl, i32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.dmi_download_isosurface_support.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
@@ -647,6 +652,31 @@ class FusionContext:
         a = (ctypes.c_double * 4)()
         self._check(self._lib.dmi_get_isosurface_decimate_pass_ms(self._h, a))
         return dict(zip(("clustering", "representatives", "triangles", "normals"), (float(x) for x in a)))
+
+    def fill_isosurface_holes(self, max_edges: int):
+        """(vertices, triangles, holes filled, boundary edges left) after the small holes of the context's mesh are closed on the
+        device: every boundary loop of 3 .. `max_edges` edges whose vertices each have one boundary edge in and one out gets one
+        triangle (3 edges) or a new vertex at the mean of its rim and a fan round it; the old vertices and triangles stay in
+        place, the new ones follow them; normals, if the mesh has them, stay and the new vertices get geometric ones; the regions,
+        support counts and colours of earlier calls are dropped when something was filled (dmi_fill_isosurface_holes; DESIGN.md
+        8f).  download_isosurface* return the filled mesh afterwards."""
+        out = [ctypes.c_uint64(0) for _ in range(4)]
+        self._check(self._lib.dmi_fill_isosurface_holes(self._h, int(max_edges), *[ctypes.byref(x) for x in out]))
+        if int(out[2].value):
+            self._mesh_counts = (int(out[0].value), int(out[1].value), 0)
+        return tuple(int(x.value) for x in out)
+
+    def isosurface_holes_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the kernels of the last fill_isosurface_holes (dmi_get_isosurface_holes_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_isosurface_holes_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
+
+    def isosurface_holes_pass_ms(self) -> dict:
+        """The same pass by pass (dmi_get_isosurface_holes_pass_ms)."""
+        a = (ctypes.c_double * 3)()
+        self._check(self._lib.dmi_get_isosurface_holes_pass_ms(self._h, a))
+        return dict(zip(("boundary", "loops", "fill"), (float(x) for x in a)))
 
     def filter_isosurface_support(self, min_views: int, tolerance: float, facing: bool = True):
         """(vertices, triangles) left after the trim of the context's mesh by view support on the device: every vertex is given the
@@ -1429,7 +1459,8 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_consistency_min_views", ctypes.c_int64), ("depth_consistency_tolerance", ctypes.c_double),
                 ("depth_consistency_rel_tolerance", ctypes.c_double),
                 ("grid_auto_bounds", ctypes.c_int32), ("grid_auto_bounds_trim", ctypes.c_double),
-                ("grid_auto_bounds_margin", ctypes.c_double), ("grid_auto_bounds_pixel_step", ctypes.c_int64)]
+                ("grid_auto_bounds_margin", ctypes.c_double), ("grid_auto_bounds_pixel_step", ctypes.c_int64),
+                ("mesh_fill_holes", ctypes.c_int64)]
 
 
 def cli_read_arguments(args):

@@ -307,6 +307,7 @@ void dmi_destroy(dmi_context *ctx) {
   ctx->components.release();
   ctx->smoothing.release();
   ctx->decimation.release();
+  ctx->holes.release();
   ctx->support.release();
   ctx->coloration.release();
   for (hipEvent_t e : ctx->slab_events) (void)hipEventDestroy(e);

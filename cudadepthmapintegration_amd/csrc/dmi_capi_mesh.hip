@@ -712,6 +712,147 @@ int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]) {
   });
 }
 
+int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_filled,
+                              uint64_t *boundary_edges_left) {
+  return guarded(ctx, "dmi_fill_isosurface_holes", [&]() -> int {
+  const std::string entry = "dmi_fill_isosurface_holes";
+  if (!ctx || !n_vertices || !n_triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
+  if (max_edges > (uint64_t(1) << 20))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": max_edges " + std::to_string(max_edges) + " is not in [0, 2^20]");
+  dmi_context::Mesh &mesh = ctx->mesh;
+  dmi_context::Holes &ho = ctx->holes;
+  dmi_context::Smoothing &sm = ctx->smoothing;
+  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
+  // ids are u32 on the device, and so are the positions among the sorted edge keys: refused, never wrapped
+  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  if (6 * nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit edge positions (6 x triangles >= 2^32)");
+  if (nv >= (uint64_t(1) << 31))  // an edge key is two ids and the direction bit in 64 bits
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for the edge keys' direction bit (vertices >= 2^31)");
+  auto nothing = [&](uint64_t left) {  // the mesh, its regions, its support counts and its colours stay as they are
+    ho.last_kernel_ms = 0.0;
+    for (double &p : ho.last_pass_ms) p = 0.0;
+    *n_vertices = nv;
+    *n_triangles = nt;
+    if (n_filled) *n_filled = 0;
+    if (boundary_edges_left) *boundary_edges_left = left;
+    return DMI_OK;
+  };
+  if (nv == 0) return nothing(0);
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  const bool normals = mesh.has_normals;
+  size_t temp_bytes = 0;
+  DMI_HIP(ctx, dmi::holes_temp_bytes(nv, nt, &temp_bytes));
+  temp_bytes = std::max<size_t>(temp_bytes, 16);
+  const uint64_t n_keys = std::max<uint64_t>(3 * nt, 2);
+  int rc = ensure_buffers(ctx, {{&sm.keys, 2 * n_keys * 8}, {&ho.vertex_scratch, 5 * (nv + 1) * 4}, {&ho.counters, 32}, {&sm.temp, temp_bytes}});
+  if (rc != DMI_OK) return rc;
+  if (!ho.events[0])
+    for (hipEvent_t &e : ho.events) DMI_HIP(ctx, hipEventCreate(&e));
+  dmi::HolesMesh m{};
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.vertices = mesh.vertices.as<double>();
+  m.triangles = mesh.triangles.as<int64_t>();
+  m.normals = normals ? mesh.normals.as<float>() : nullptr;
+  dmi::HolesVertexScratch vs{};
+  uint32_t *vp = ho.vertex_scratch.as<uint32_t>();
+  vs.out_deg = vp;
+  vs.in_deg = vp + (nv + 1);
+  vs.succ = vp + 2 * (nv + 1);
+  vs.flag = vp + 3 * (nv + 1);
+  vs.rank = vp + 4 * (nv + 1);
+  uint64_t *const keys[2] = {sm.keys.as<uint64_t>(), sm.keys.as<uint64_t>() + n_keys};
+  unsigned long long *counters = ho.counters.as<unsigned long long>();
+  // (a failure from here on leaves the context's mesh as it was: no kernel writes it, and the buffers are swapped only at the end)
+  DMI_HIP(ctx, dmi::launch_holes_boundary(m, vs, keys, sm.temp.ptr, temp_bytes, counters, ho.events, ctx->stream));
+  uint32_t n_slots = 0;
+  unsigned long long counts[4] = {0, 0, 0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&n_slots, vs.rank + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(counts, counters, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the first of three: the boundary vertices
+  const uint64_t boundary_edges = counts[0];
+  if (max_edges < 3 || n_slots == 0) return nothing(boundary_edges);
+  rc = ensure_buffer(ctx, ho.loop_scratch, 11 * ((uint64_t)n_slots + 1) * 4);
+  if (rc != DMI_OK) return rc;
+  dmi::HolesLoopScratch ls{};
+  uint32_t *lp = ho.loop_scratch.as<uint32_t>();
+  const uint64_t pitch = (uint64_t)n_slots + 1;
+  ls.id = lp;
+  ls.next = lp + pitch;
+  ls.ptr[0] = lp + 2 * pitch;
+  ls.ptr[1] = lp + 3 * pitch;
+  ls.label[0] = lp + 4 * pitch;
+  ls.label[1] = lp + 5 * pitch;
+  ls.count = lp + 6 * pitch;
+  ls.new_vertices = lp + 7 * pitch;
+  ls.new_triangles = lp + 8 * pitch;
+  ls.vertex_offset = lp + 9 * pitch;
+  ls.triangle_offset = lp + 10 * pitch;
+  DMI_HIP(ctx, dmi::launch_holes_loops(m, vs, ls, n_slots, max_edges, sm.temp.ptr, temp_bytes, counters, ho.events[2], ctx->stream));
+  uint32_t added[2] = {0, 0};
+  DMI_HIP(ctx, hipMemcpyAsync(&added[0], ls.vertex_offset + n_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(&added[1], ls.triangle_offset + n_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(counts, counters, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the second: what the fill adds
+  if (counts[1] == 0) return nothing(boundary_edges);
+  const uint64_t out_nv = nv + added[0], out_nt = nt + added[1];
+  if (out_nv >= (uint64_t(1) << 32) || out_nt >= (uint64_t(1) << 32) || 6 * out_nt >= (uint64_t(1) << 32))
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the filled mesh would be too large for 32-bit ids (vertices or 6 x triangles >= 2^32)");
+  rc = ensure_buffers(ctx, {{&mesh.alt_vertices, out_nv * kVertexBytes}, {&mesh.alt_triangles, out_nt * kTriangleBytes},
+                            {&mesh.alt_normals, normals ? out_nv * kNormalBytes : 0}});
+  if (rc != DMI_OK) return rc;
+  dmi::HolesOutput out{};
+  out.vertices = mesh.alt_vertices.as<double>();
+  out.triangles = mesh.alt_triangles.as<int64_t>();
+  out.normals = normals ? mesh.alt_normals.as<float>() : nullptr;
+  DMI_HIP(ctx, dmi::launch_holes_fill(m, ls, n_slots, out, counters, ho.events[3], ctx->stream));
+  DMI_HIP(ctx, hipMemcpyAsync(counts, counters, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the third: the filled mesh
+  if (counts[3]) return fail(ctx, DMI_ERR_STATE, entry + ": a loop's walk did not close (the mesh is left as it was)");
+  float ms = 0.f;
+  DMI_HIP(ctx, hipEventElapsedTime(&ms, ho.events[0], ho.events[3]));
+  ho.last_kernel_ms = (double)ms;
+  for (int p = 0; p < 3; ++p) {
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, ho.events[p], ho.events[p + 1]));
+    ho.last_pass_ms[p] = (double)ms;
+  }
+  // the filled mesh becomes the context's; the buffers it came from are the next call's output
+  std::swap(mesh.vertices, mesh.alt_vertices);
+  std::swap(mesh.triangles, mesh.alt_triangles);
+  if (normals) std::swap(mesh.normals, mesh.alt_normals);
+  mesh.n_vertices = out_nv;
+  mesh.n_triangles = out_nt;
+  mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
+  mesh.regions = 0;
+  mesh.colored = false;   // ... nor are the colours
+  ctx->support.valid = false;  // ... nor the support counts
+  *n_vertices = out_nv;
+  *n_triangles = out_nt;
+  if (n_filled) *n_filled = counts[1];
+  if (boundary_edges_left) *boundary_edges_left = boundary_edges - counts[2];
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_holes_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_isosurface_holes_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_holes_kernel_ms: null argument");
+  *last = ctx->holes.last_kernel_ms;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_isosurface_holes_pass_ms(dmi_context *ctx, double out[3]) {
+  return guarded(ctx, "dmi_get_isosurface_holes_pass_ms", [&]() -> int {
+  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_holes_pass_ms: null argument");
+  for (int p = 0; p < 3; ++p) out[p] = ctx->holes.last_pass_ms[p];
+  return DMI_OK;
+  });
+}
+
 int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double tolerance, int32_t require_facing, uint64_t *n_vertices,
                                   uint64_t *n_triangles) {
   return guarded(ctx, "dmi_filter_isosurface_support", [&]() -> int {

@@ -213,6 +213,15 @@ struct dmi_context {
     double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // clustering, representatives, triangles, normals
     void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); dmi::destroy_events(events); }
   } decimation;
+  struct Holes {  // dmi_fill_isosurface_holes (isosurface_holes.hip); it also uses smoothing.keys and smoothing.temp
+    dmi::DeviceBuffer vertex_scratch;  // out-degree, in-degree, successor, flag, rank: 5 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer loop_scratch;    // id, next, 2 pointers, 2 labels, count, 2 additions, 2 offsets: 11 u32 arrays of (slots + 1)
+    dmi::DeviceBuffer counters;        // 4 u64
+    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
+    double last_kernel_ms = 0.0;
+    double last_pass_ms[3] = {0.0, 0.0, 0.0};  // boundary, loops, fill
+    void release() { dmi::free_buffers({&vertex_scratch, &loop_scratch, &counters}); dmi::destroy_events(events); }
+  } holes;
 
   struct Support {  // dmi_filter_isosurface_support (isosurface_support.hip)
     dmi::DeviceBuffer counts;          // [n] int32: the supporting views of every vertex of the mesh, as the last call left it

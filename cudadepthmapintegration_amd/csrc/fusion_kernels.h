@@ -381,6 +381,40 @@ double decimate_decode_bound(unsigned long long ordered);
 hipError_t launch_isosurface_decimate(const DecimateMesh &m, const DecimateGrid &g, const DecimateScratch &s, int placement,
                                       hipEvent_t *events, hipStream_t stream);
 
+// The hole filler of that mesh (isosurface_holes.hip).  Nothing of the input mesh is written.
+struct HolesMesh {
+  uint64_t n_vertices, n_triangles;  // 1 <= n_vertices < 2^31 (an edge key is two ids and a direction bit), 3 n_triangles < 2^32
+  const double *vertices;            // [n_vertices][3]
+  const int64_t *triangles;          // [n_triangles][3]
+  const float *normals;              // [n_vertices][3], or null: the mesh has none
+};
+struct HolesVertexScratch {          // [n_vertices + 1] each
+  uint32_t *out_deg, *in_deg;        // the boundary half-edges that start and end at a vertex
+  uint32_t *succ;                    // where the one that starts there ends (read for simple vertices only)
+  uint32_t *flag, *rank;             // a boundary vertex; the boundary vertices before it (its slot), the total at [n_vertices]
+};
+struct HolesLoopScratch {            // [slots + 1] each
+  uint32_t *id, *next;               // a slot's vertex; its successor's slot (a complex vertex: itself)
+  uint32_t *ptr[2], *label[2];       // the doubling's two buffers
+  uint32_t *count;                   // the slots that carry this slot as their label
+  uint32_t *new_vertices, *new_triangles, *vertex_offset, *triangle_offset;  // what a head adds, and the scans of that
+};
+struct HolesOutput {                 // room for the old mesh and what the loops pass counted
+  double *vertices;
+  int64_t *triangles;
+  float *normals;                    // or null
+};
+hipError_t holes_temp_bytes(uint64_t n_vertices, uint64_t n_triangles, size_t *bytes);
+int holes_rounds(uint64_t max_edges, uint64_t n_slots);  // the doubling rounds of launch_holes_loops
+// Three passes with a read of the counts between them (dmi_capi_mesh.hip); counters: 4 u64 (boundary edges, filled loops, their
+// edges, walks that did not close).  keys: [3 n_triangles] each.
+hipError_t launch_holes_boundary(const HolesMesh &m, const HolesVertexScratch &v, uint64_t *const keys[2], void *temp, size_t temp_bytes,
+                                 unsigned long long *counters, hipEvent_t *events, hipStream_t stream);
+hipError_t launch_holes_loops(const HolesMesh &m, const HolesVertexScratch &v, const HolesLoopScratch &l, uint32_t n_slots, uint64_t max_edges,
+                              void *temp, size_t temp_bytes, unsigned long long *counters, hipEvent_t event, hipStream_t stream);
+hipError_t launch_holes_fill(const HolesMesh &m, const HolesLoopScratch &l, uint32_t n_slots, const HolesOutput &out,
+                             unsigned long long *counters, hipEvent_t event, hipStream_t stream);
+
 // The trim of that mesh by view support (isosurface_support.hip).  Nothing of the input mesh is written.
 struct SupportMesh {
   uint64_t n_vertices, n_triangles;  // n_vertices >= 1, both below 2^32 (u32 maps on the device)

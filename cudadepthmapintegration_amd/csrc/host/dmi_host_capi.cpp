@@ -384,6 +384,7 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->grid_auto_bounds_trim = o.gridAutoBoundsTrim;
   out->grid_auto_bounds_margin = o.gridAutoBoundsMargin;
   out->grid_auto_bounds_pixel_step = o.gridAutoBoundsPixelStep;
+  out->mesh_fill_holes = o.meshFillHoles;
   return 1;
   });
 }

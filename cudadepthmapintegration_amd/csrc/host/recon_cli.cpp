@@ -167,6 +167,19 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                               "and corners inside a cell stay sharp and convex shapes do not shrink; the triangles are the "
                                               "same either way (not in the reference)",
                                  into_flag(&o->meshDecimateQuadric)}},
+      {"--meshFillHoles", {Kind::kValue, "with --extractMesh: close the mesh's small holes on the GPU, after --meshMinSupportViews and the "
+                                         "component flags and before the smoothing: every boundary loop of at most this many edges (an "
+                                         "integer in 3..1048576) gets a triangle, or a vertex at the mean of its rim and a fan round "
+                                         "it, as vtkFillHolesFilter closes holes; loops through a non-manifold vertex stay open; with "
+                                         "--meshNormals the new vertices get geometric normals, with --meshRegionIds the components "
+                                         "are labelled again on the filled mesh (default 0 = off; not in the reference)",
+                           [o](const std::vector<std::string> &values) {
+                             long long n = 0;
+                             if (!into_count(&n)(values) || n < 3 || n > 1048576) return false;
+                             o->meshFillHoles = n;
+                             o->meshFillHolesGiven = true;
+                             return true;
+                           }}},
       {"--meshColoration", {Kind::kFlag, "with --extractMesh, on one GPU: colour the mesh on the GPU where it is, last of all, from the "
                                          "Color arrays of the depth-map files (UInt8 x 3, read in the same pass as the depths), and "
                                          "write the point arrays MeanColoration, MedianColoration and NbProjectedDepthMap as the "
@@ -346,6 +359,10 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
       err << "Error : " << flag.first << " needs --extractMesh (the smoothing belongs to the extracted mesh).\n" << HelpText();
       return false;
     }
+  if (o->meshFillHolesGiven && !o->extractMesh) {
+    err << "Error : --meshFillHoles needs --extractMesh (the holes belong to the extracted mesh).\n" << HelpText();
+    return false;
+  }
   if (o->meshDecimateCellSizeGiven && !o->extractMesh) {
     err << "Error : --meshDecimateCellSize needs --extractMesh (the decimation belongs to the extracted mesh).\n" << HelpText();
     return false;
@@ -933,6 +950,18 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
         result->meshComponents = found;
         result->meshComponentsKept = kept;
       }
+      if (rc == DMI_OK && o.meshFillHoles > 0) {  // behind the trim and the component flags: the smoothing then moves the former rims
+        uint64_t filled = 0, left = 0;
+        rc = dmi_fill_isosurface_holes(ctx, (uint64_t)o.meshFillHoles, &nv, &nt, &filled, &left);
+        if (rc == DMI_OK) rc = dmi_get_isosurface_holes_kernel_ms(ctx, &result->meshFillHolesKernelMs);
+        result->meshHolesFilled = filled;
+        result->meshBoundaryEdgesLeft = left;
+        // the fill has dropped the regions: labelled anew, nothing dropped (behind a decimation that happens there)
+        if (rc == DMI_OK && o.meshRegionIds && filled > 0 && !(o.meshDecimateCellSize > 0)) {
+          uint64_t found = 0, kept = 0;
+          rc = dmi_filter_isosurface_components(ctx, DMI_COMPONENTS_MIN_TRIANGLES, 0, &nv, &nt, &found, &kept);
+        }
+      }
       if (rc == DMI_OK && o.meshSmoothIterations > 0) {  // on the mesh the component flags left, before anything is downloaded
         rc = dmi_smooth_isosurface(ctx, (int32_t)o.meshSmoothIterations, o.meshSmoothLambda, o.meshSmoothMu);
         if (rc == DMI_OK) rc = dmi_get_isosurface_smooth_kernel_ms(ctx, &result->meshSmoothKernelMs);
@@ -1029,6 +1058,9 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
       log << "mesh components: " << result->meshComponents << " found, " << result->meshComponentsKept << " kept; "
           << result->meshVerticesExtracted << " vertices, " << result->meshTrianglesExtracted << " triangles before, "
           << result->meshVertices << " vertices, " << result->meshTriangles << " triangles after" << std::endl;
+    if (o.meshFillHoles > 0)
+      log << "mesh holes: at most " << o.meshFillHoles << " edges; " << result->meshHolesFilled << " filled, "
+          << result->meshBoundaryEdgesLeft << " boundary edges left; " << result->meshFillHolesKernelMs << " ms of GPU kernels" << std::endl;
     if (o.meshSmoothIterations > 0)
       log << "mesh smoothing: " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
           << "; " << result->meshSmoothKernelMs << " ms of GPU kernels" << std::endl;
@@ -1091,6 +1123,9 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
       out << "  mesh components found  " << result->meshComponents << "\n  mesh components kept  " << result->meshComponentsKept
           << "\n  mesh vertices before the component filter  " << result->meshVerticesExtracted
           << "\n  mesh triangles before the component filter  " << result->meshTrianglesExtracted << "\n";
+    if (o.meshFillHoles > 0)  // (only with --extractMesh)
+      out << "  mesh holes  at most " << o.meshFillHoles << " edges, " << result->meshHolesFilled << " filled, "
+          << result->meshBoundaryEdgesLeft << " boundary edges left, " << result->meshFillHolesKernelMs << " ms of GPU kernels\n";
     if (o.meshSmoothIterations > 0)  // (only with --extractMesh)
       out << "  mesh smoothing  " << o.meshSmoothIterations << " iterations, lambda " << o.meshSmoothLambda << ", mu " << o.meshSmoothMu
           << ", " << result->meshSmoothKernelMs << " ms of GPU kernels\n";

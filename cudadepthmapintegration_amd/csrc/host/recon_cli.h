@@ -18,6 +18,8 @@
 // placement.  --meshMinSupportViews N with --meshSupportDepthTolerance T (not in the reference:
 // the trim by observation support of every TSDF pipeline) runs dmi_filter_isosurface_support right after the extraction, before the
 // component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.
+// --meshFillHoles N (not in the reference: what a vtkFillHolesFilter behind those would do) runs dmi_fill_isosurface_holes behind
+// the component flags and in front of the smoothing, which then moves the patches and the former rims with the rest.
 // --depthConsistencyMinViews N with --depthConsistencyTolerance / --depthConsistencyRelTolerance (not in the reference: the geometric
 // consistency check of every depth-map fusion pipeline) reads all views into memory, filters their depths on the first device
 // (dmi_filter_depth_consistency) and fuses the filtered views through ReconstructionFilter::SetViews.
@@ -99,6 +101,10 @@ struct Options {
   double gridAutoBoundsTrim = 0.005, gridAutoBoundsMargin = 0.05;
   long long gridAutoBoundsPixelStep = 1;
   bool gridAutoBoundsTrimGiven = false, gridAutoBoundsMarginGiven = false, gridAutoBoundsPixelStepGiven = false;
+  // not in the reference (needs --extractMesh): close the mesh's boundary loops of at most N edges on the GPU
+  // (dmi_fill_isosurface_holes) behind the support trim and the component flags and in front of the smoothing (0: off)
+  long long meshFillHoles = 0;
+  bool meshFillHolesGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -141,6 +147,9 @@ struct RunResult {
   double gridOrigin[3] = {0.0, 0.0, 0.0}, gridEnd[3] = {0.0, 0.0, 0.0}, gridSpacing[3] = {0.0, 0.0, 0.0};
   int gridDims[3] = {0, 0, 0};
   std::string error;  // empty on success
+  // --meshFillHoles: the loops filled, the boundary edges left and the hipEvent time of the fill's kernels
+  unsigned long long meshHolesFilled = 0, meshBoundaryEdgesLeft = 0;
+  double meshFillHolesKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);

@@ -52,7 +52,8 @@ extern "C" {
                            *    dmi_get_isosurface_color_kernel_ms; dmi_filter_isosurface_support, dmi_download_isosurface_support,
                            *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms;
                            *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency;
-                           *    dmi_estimate_scene_bounds */
+                           *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
+                           *    dmi_get_isosurface_holes_pass_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -427,6 +428,53 @@ int dmi_decimate_isosurface_placed(dmi_context *ctx, double cell_size, int32_t p
  * triangle compaction), out[3] normals.  Zeros after a call that had nothing to do.  Waits for the last call's normals. */
 int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last);
 int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]);
+
+/* Small holes of the context's mesh closed on the device: the counterpart of a vtkFillHolesFilter behind the contour, for the
+ * pinholes the support trim and the consistency filter leave, whose rims the smoother would otherwise pin.  Additions to ABI 5;
+ * csrc/isosurface_holes.hip.  The mesh is the one the context holds, whichever call left it: V vertices p ([V][3] f64), T
+ * triangles ([T][3] int64).  Definition, met bit for bit by the device and by tests/isosurface_holes_np.py:
+ *   half-edges   a triangle (a, b, c) with three distinct ids below V names the half-edges a->b, b->c, c->a.  A triangle that
+ *                names an id twice names none (the smoother counts the one real edge of (a, b, a); here such a triangle is not
+ *                there at all), nor does one that names an id >= V.
+ *   boundary     the undirected edge {a, b} is a boundary edge when exactly one triangle names it (the smoother's rule; an edge
+ *                three or more triangles name is none).  Its boundary half-edge is the one half-edge over it, in the direction
+ *                its triangle stores.
+ *   vertices     a vertex at which a boundary half-edge starts or ends is SIMPLE when exactly one starts and exactly one ends
+ *                there, else COMPLEX (a bow-tie, a vertex on a non-manifold seam).  next(a) of a simple vertex a is the end of the
+ *                half-edge that starts at a.
+ *   loops        a loop is a cycle h_0, h_1 = next(h_0), ..., h_{L-1} with next(h_{L-1}) = h_0 of simple vertices, h_0 the
+ *                smallest id among them.  A chain that reaches a complex vertex is no loop and is never filled.  Loops are
+ *                ordered by ascending h_0.
+ *   fill         a loop is filled when 3 <= L <= max_edges.  L == 3 adds the triangle (h_0, h_2, h_1) and no vertex.  L >= 4 adds
+ *                one vertex c, c_d = s_d / (double)L with s_d = ((p[h_0][d] + p[h_1][d]) + p[h_2][d]) + ... added left to right
+ *                in walk order (f64, every operation rounded, no FMA), and the L triangles (h_{(i+1) mod L}, h_i, c), i = 0 ..
+ *                L-1: the rim's direction reversed, so the patch is oriented like its neighbours.  Non-finite coordinates
+ *                propagate as the arithmetic makes them.
+ *   output       the first V vertices and the first T triangles are the input's, bit for bit and in place; the new vertices are
+ *                V, V+1, ... over the filled loops with L >= 4 in loop order; the new triangles follow loop by loop in loop
+ *                order, inside a loop in the order above.
+ *   normals      a mesh that carries normals keeps those of its old vertices (a former rim vertex too); a new vertex gets the
+ *                geometric normal of dmi_smooth_isosurface's definition over its L triangles in ascending index, which is the
+ *                walk order.  A mesh without normals stays without.
+ * RegionId / RegionSize, the support counts and the colours no longer describe a mesh that was filled: they are dropped as the
+ * decimation drops them (the downloads are refused until their producer runs again).  A call that fills nothing -- an empty
+ * mesh, no loop of 3 .. max_edges edges, max_edges < 3 -- is a success that leaves the mesh and all of these untouched.
+ * Nothing here is clever: the rim of an open sheet is a loop like any other, the rim of an isolated triangle is closed by its
+ * mirror image, and a fan round the centroid of a rim that is far from flat or from convex may fold.  max_edges is what keeps
+ * large rims open; dmi_reconstruction runs the fill behind its component flags, which have removed the isolated pieces.
+ * n_vertices, n_triangles: the mesh afterwards.  n_filled, boundary_edges_left (each may be null): the loops filled, and the
+ * boundary edges of the mesh afterwards (those of complex chains and of loops not filled).
+ * DMI_ERR_INVALID_ARGUMENT: a null context or null size pointers, max_edges > 2^20, no extraction yet, input or output V or T >=
+ * 2^32 or 6 T >= 2^32 (ids and edge positions are u32 on the device), and input V >= 2^31 (an edge key is two ids and the
+ * stored direction in 64 bits).  A failing call leaves the mesh exactly as it was: the result is built in the alternate buffers
+ * and swapped in last.  Synchronises the context's stream three times (the boundary vertices, the additions, the result). */
+int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_vertices, uint64_t *n_triangles,
+                              uint64_t *n_filled, uint64_t *boundary_edges_left);
+/* hipEvent time of all kernels of the last dmi_fill_isosurface_holes, and pass by pass: out[0] boundary (keys, sort, half-edges,
+ * vertex classes), out[1] loops (labels, lengths, scans), out[2] fill (copy, centroids, triangles, normals).  Zeros after a call
+ * that filled nothing. */
+int dmi_get_isosurface_holes_kernel_ms(dmi_context *ctx, double *last);
+int dmi_get_isosurface_holes_pass_ms(dmi_context *ctx, double out[3]);
 
 /* Trim of the context's mesh by view support, on the device: what every TSDF pipeline does to the back shell and to the sheets
  * between seen and unseen space that an iso-contour of the summed ray potential carries besides the surface.  Additions to ABI 5;

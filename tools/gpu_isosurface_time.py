@@ -17,7 +17,8 @@ tests/isosurface_decimate_quadric_np.py too).  With --color it times the colorat
 (dmi_color_process_isosurface) against dmi_color_process, the fused depth test against the own-planes test, and both again after a
 decimation (color_record).  With --render-depths it times the z-buffer rasteriser (dmi_color_render_isosurface_depths) on the
 mesh, pass by pass, with the count of queued pairs, and the colouring with rendered planes next to the colouring with fused depths
-(render_record).  --grid N runs the whole tool on an N^3 grid (a quick
+(render_record).  With --holes N (several may be given) it times dmi_fill_isosurface_holes on the mesh the support trim
+leaves, pass by pass (holes_record); --image W H sets the views' size (cfg 2: --grid 256 --views 64 --image 640 480).  --grid N runs the whole tool on an N^3 grid (a quick
 run; the records in profiles/ are of the default 512).
 
     python tools/gpu_isosurface_time.py [--iso 1.0] [--views 256] [--repeat 5] [--normals] [--components [--min-triangles 100]]
@@ -225,6 +226,46 @@ def decimate_record(ctx, a):
     return rec
 
 
+def holes_record(ctx, a, spacing):
+    """The --holes record: dmi_fill_isosurface_holes at every a.holes (max_edges) on the mesh of the context's grid at a.iso after the
+    support trim (a.holes_min_views views within a.holes_tolerance grid spacings; 0 views: no trim), a.repeat rounds after a warm-up
+    round, the values of max_edges alternating inside a round.  In every round the fill follows a fresh extraction with normals
+    and a fresh trim.  With a.holes_check the numpy restatement runs on the trimmed mesh and is compared bit for bit."""
+    import time
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))   # the host alternative IS the tests' numpy restatement
+    import isosurface_holes_np as H
+    rec = {"min_views": a.holes_min_views, "tolerance": a.holes_tolerance * spacing, "runs": {}}
+    for r in range(a.repeat + 1):                       # round 0 is the warm-up: buffers sized, code loaded
+        for m in a.holes:
+            run = rec["runs"].setdefault(str(m), {"max_edges": m, "kernel_ms": [], "pass_ms": []})
+            ctx.extract_isosurface_with_normals(a.iso)
+            if a.holes_min_views > 0:
+                ctx.filter_isosurface_support(a.holes_min_views, a.holes_tolerance * spacing)
+            if r == a.repeat and a.holes_check:
+                raw = ctx.download_isosurface() + (ctx.download_isosurface_normals(),)
+            run["vertices"], run["triangles"] = ctx._current_mesh_counts()[:2]
+            run["vertices_after"], run["triangles_after"], run["filled"], run["boundary_edges_left"] = ctx.fill_isosurface_holes(m)
+            if r:
+                run["kernel_ms"].append(ctx.isosurface_holes_kernel_ms())
+                run["pass_ms"].append(ctx.isosurface_holes_pass_ms())
+            if r == a.repeat and a.holes_check:
+                got = ctx.download_isosurface() + (ctx.download_isosurface_normals(),)
+                t0 = time.perf_counter()
+                want = H.fill(raw[0], raw[1], m, raw[2])
+                run["host_numpy_s"] = time.perf_counter() - t0
+                run["host_matches_gpu"] = all(want[k].tobytes() == g.tobytes() for k, g in zip(("vertices", "triangles", "normals"), got))
+                sizes = want["loop_sizes"]
+                run["boundary_edges"] = want["boundary_edges_left"] + sum(len(h) for h in want["filled"])
+                run["loops"], run["longest_loop"] = len(sizes), max(sizes, default=0)
+                run["longest_filled"] = max((len(h) for h in want["filled"]), default=0)
+    for run in rec["runs"].values():
+        run["kernel_ms_min"] = min(run["kernel_ms"])
+        for p in ("boundary", "loops", "fill"):
+            run[p + "_ms_min"] = min(q[p] for q in run["pass_ms"])
+    return rec
+
+
 def color_record(ctx, a, spacing):
     """The --color record: the mesh of the context's grid at a.iso coloured from the scene's first a.color_views views, the calls
     alternating in one process, a.repeat times each.  The mesh is extracted in a second context that holds those views (the fused
@@ -362,6 +403,12 @@ def main():
     ap.add_argument("--render-depths", action="store_true", help="also time the rendering of the mesh's own depth planes and the colouring with them")
     ap.add_argument("--render-views", type=int, default=256, help="... into the scene's first this many views")
     ap.add_argument("--render-queue", type=int, default=0, help="... with this queue capacity (0: the default)")
+    ap.add_argument("--holes", type=int, action="append", default=[],
+                    help="also time the hole filler at this max_edges (may be given several times) on the mesh the support trim leaves")
+    ap.add_argument("--holes-min-views", type=int, default=3, help="... the trim's views (0: no trim)")
+    ap.add_argument("--holes-tolerance", type=float, default=2.0, help="... and its depth tolerance in grid spacings")
+    ap.add_argument("--holes-check", action="store_true", help="... and compare each with the numpy restatement, bit for bit")
+    ap.add_argument("--image", type=int, nargs=2, default=[1280, 720], help="the views' width and height (cfg 2: 640 480)")
     ap.add_argument("--grid", type=int, default=512, help="cells per axis (512: the cfg-3 grid)")
     a = ap.parse_args()
     grid = scene.default_grid(a.grid)
@@ -369,7 +416,7 @@ def main():
     spacing = float(max(grid.spacing))
     with capi.FusionContext(grid, ray) as ctx:
         for c0 in range(0, a.views, 32):
-            v, thr = scene.make_scene_views("speckle", 256, 1280, 720, seed=1000, view_range=(c0, min(a.views, c0 + 32)),
+            v, thr = scene.make_scene_views("speckle", 256, a.image[0], a.image[1], seed=1000, view_range=(c0, min(a.views, c0 + 32)),
                                             noise_sigma=spacing)
             ctx.add_views(v, threshold=thr)
         ctx.fuse()
@@ -391,6 +438,7 @@ def main():
         decimate = []
         for h in a.decimate:
             decimate.append(decimate_record(ctx, argparse.Namespace(**{**vars(a), "decimate": h})))
+        holes = holes_record(ctx, a, spacing) if a.holes else None
         color = color_record(ctx, a, spacing) if a.color else None
         render = render_record(ctx, a, spacing) if a.render_depths else None
     n_points = (a.grid + 1) ** 3
@@ -408,6 +456,8 @@ def main():
         out["smooth"] = smooth
     if decimate:
         out["decimate"] = decimate
+    if holes is not None:
+        out["holes"] = holes
     if color is not None:
         out["color"] = color
     if render is not None:
