@@ -248,6 +248,16 @@ def scratch_sizes(asm_text: str) -> dict:
     return out
 
 
+def lds_sizes(asm_text: str) -> dict:
+    """.amdhsa_group_segment_fixed_size of every fuse_tile_kernel instantiation (bytes of LDS per workgroup: the window
+    instantiations' pair area, fusion_tile.hip; it bounds the waves a CU holds as the registers do)."""
+    out = {}
+    for m in re.finditer(r"\.amdhsa_kernel (_ZN3dmi\S*fuse_tile_kernel\S*)\b(.*?)\.end_amdhsa_kernel", asm_text, re.S):
+        size = re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", m.group(2))
+        out[m.group(1)] = int(size.group(1)) if size else 0
+    return out
+
+
 def wait_state_counts(asm_text: str) -> dict:
     """s_nop instructions per fuse_tile_kernel instantiation: a canary, not a rule.  hipcc puts a wait state between an asm
     statement and an immediate reader of its result; the tier-1 chains are written so that few are needed (fusion_tile.hip, struct
@@ -300,6 +310,7 @@ def run_accumulator_audit(verbose: bool = False) -> int:
     # column), f64 depth tables and general K are the rare paths (launch_shape): listed, not bounded.  A toolchain or source
     # change that makes a production kernel spill is caught here, not in a profile months later.
     nops = wait_state_counts(text)
+    lds = lds_sizes(text)
     table = {}
     for name, size in scratch.items():
         m = re.search(r"fuse_tile_kernelI(\w)(\w)Li(\d+)ELi(\d)ELi(\d)ELi(\d)ELi(\d)ELb([01])ELb([01])ELb([01])ELb([01])ELb([01])(?:ELb([01]))?E", name)
@@ -310,9 +321,15 @@ def run_accumulator_audit(verbose: bool = False) -> int:
         production = depth == "f" and count == "0" and genk == "0" and wx == "1" and wy == "1"
         # (a tuning build carries debug counters through the kernel: a few slots are its own)
         limit = None if not production else ((16 if "-DDMI_TUNING" in COMMON_FLAGS else 0) if tk == "16" else 48)
-        table[key] = {"scratch_bytes_per_lane": size, "production": production, "limit": limit, "s_nop": nops.get(name)}
+        table[key] = {"scratch_bytes_per_lane": size, "production": production, "limit": limit, "s_nop": nops.get(name),
+                      "lds_bytes_per_workgroup": lds.get(name, 0)}
         if limit is not None and size > limit:
             bad.append(f"{name}: {size} bytes of scratch memory per lane in a production instantiation (limit {limit})")
+        # LDS must not cost a production kernel a wave: its registers allow 4 waves per SIMD with 16-voxel columns, 5 with 8-voxel
+        # ones (acc_base + 2 * tk VGPRs), a one-wave workgroup each, on a CU of 4 SIMDs and 160 KB of LDS
+        waves_per_cu = 4 * (4 if tk == "16" else 5)
+        if production and lds.get(name, 0) * waves_per_cu > 160 * 1024:
+            bad.append(f"{name}: {lds[name]} bytes of LDS per one-wave workgroup: {waves_per_cu} of them do not fit a CU's 160 KB")
     if bad:
         raise RuntimeError("accumulator-register audit of fusion_tile.hip FAILED (a toolchain change broke the hidden "
                            "register file; results would be silently wrong):\n  " + "\n  ".join(bad[:20]))

@@ -351,7 +351,8 @@ int tile_tables(dmi_context *ctx, const FuseArgs &a, FuseConfig *cfg, const dmi:
     q.any_tier1 = any_tier1;
     q.zero_free = zero_free;
     q.depth_f64 = ctx->views.depth_f64;
-    rc = class_table(ctx, sh, dmi::use_windows(q), &t);
+    const bool windows = dmi::use_windows(q) && dmi::win_pair_pieces_addressable((int64_t)t.wbricks_x * t.wbricks_y * t.bricks_z);
+    rc = class_table(ctx, sh, windows, &t);
     if (rc == DMI_OK && !(cfg->variant & dmi::VAR_SPATIAL_ORDER)) rc = order_tables(ctx, sh, cfg->variant, &t);
   }
   if (zero_free) t.behind_mask = 0x0101010101010101ull;

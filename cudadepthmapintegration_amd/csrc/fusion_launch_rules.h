@@ -142,6 +142,29 @@ DMI_RULES_HD inline int64_t win_pair_index(int64_t brick, int32_t view, int64_t 
   return (((int64_t)(view >> 5) * n_class_bricks + brick) << 5) + (view & 31);
 }
 
+// The fusion kernel fetches a brick's pieces of two consecutive blocks with one buffer load (fusion_tile.hip: the pair area in
+// LDS): the distance between them, n_class_bricks * 32 entries of 16 bytes, plus a piece must be below 2^32 - 1, the largest
+// range a buffer has (at 2^23 - 1 bricks the second piece's last entry would lie beyond it and read as zeros).  A grid of 2^22
+// bricks or more (2 G voxels with 8-voxel columns) is fused without windows.
+inline bool win_pair_pieces_addressable(int64_t n_class_bricks) { return n_class_bricks < (int64_t(1) << 22); }
+// One of those loads: the buffer it reads from starts at byte `first` of the table -- the brick's piece of `block` -- and ranges over
+// `range` bytes, to the table's end (n_class_bricks * class_pitch entries) or 2^32 - 1 bytes, whichever comes first.  A lane reads 16
+// bytes at (lane & 31) * 16, plus win_pair_piece_stride for lanes 32-63 (the piece of block + 1).  A block beyond the pitch has range
+// 0: the hardware's range check answers every lane with zeros, and no byte outside the table is ever asked for.
+struct WinPairFill {
+  uint64_t first;
+  uint32_t range;
+};
+DMI_RULES_HD inline uint64_t win_pair_piece_stride(uint64_t n_class_bricks) { return n_class_bricks << 9; }
+DMI_RULES_HD inline WinPairFill win_pair_fill(uint64_t brick, uint32_t block, uint64_t n_class_bricks, uint32_t class_pitch) {
+  const uint64_t table_bytes = (n_class_bricks * class_pitch) << 4;
+  WinPairFill f;
+  f.first = (n_class_bricks * block + brick) << 9;
+  const uint64_t rest = table_bytes > f.first ? table_bytes - f.first : 0;
+  f.range = rest > 0xffffffffull ? 0xffffffffu : (uint32_t)rest;
+  return f;
+}
+
 // No sum of the launch can be -0.0 (the launches the kernel's ZF instantiations serve, fusion_tile.hip), and the +0.0 adds of the
 // pairs far behind every surface can be dropped (TileArgs::behind_mask):
 // +0.0 adds are no-ops unless a sum can be -0.0 (only an uploaded grid can bring one) or hits are counted

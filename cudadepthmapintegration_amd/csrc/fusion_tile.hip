@@ -111,6 +111,12 @@ __device__ __forceinline__ f32x2 pk_fma_lo0_vs(f32x2 a, f32x2 b, unsigned long l
   asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(a), "v"(b), "s"(c_bits));
   return d;
 }
+// ... c = a pair of floats in vector registers (the window pair's entry as it comes out of LDS)
+__device__ __forceinline__ f32x2 pk_fma_lo0_vv(f32x2 a, f32x2 b, f32x2 c) {
+  f32x2 d;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
 // a.hi * b + c on both halves (only the high float of a is read)
 __device__ __forceinline__ f32x2 pk_fma_hi0_vv(f32x2 a, f32x2 b, f32x2 c) {
   f32x2 d;
@@ -227,6 +233,41 @@ template <typename T>
 __device__ __forceinline__ T cload(const T *p) {
   return *reinterpret_cast<const T __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(p));
 }
+
+// ---- the window pairs of a brick in LDS (WIN instantiations; -DDMI_WINPAIR_LANE_HELD builds the lane-held form instead) --------
+// One wave's area: the WinPair entries of a GROUP of 256 views, view v's at (v & 255) * 16.  The workgroup is one wave, so the
+// area is the kernel's whole LDS allocation and nobody else reads or writes it.
+#if defined(DMI_WINPAIR_BRICK_MAJOR) && !defined(DMI_WINPAIR_LANE_HELD)
+#error "-DDMI_WINPAIR_BRICK_MAJOR (the [brick][view] pair table) is built with the lane-held entries only: add -DDMI_WINPAIR_LANE_HELD"
+#endif
+constexpr int kPairGroupViews = 256;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const u32x4 __attribute__((address_space(3))) *pair_area_t;
+__device__ __forceinline__ pair_area_t pair_area() {
+  __shared__ u32x4 area[kPairGroupViews];
+  return (pair_area_t)area;
+}
+// One LDS-direct load of 1 KB: lane l's 16 bytes at byte `voff` of the buffer go to LDS byte `lds_dst` + 16 l.  The descriptor's
+// range check answers an offset beyond the buffer with zeros instead of a fault.  No register receives anything: the data is
+// there once vmcnt has counted the instruction down (pair_area_wait), which the compiler knows nothing of.
+// M0 holds the destination; it is the compiler's register, saved and restored here.  s_nop 4: the descriptor and M0 may have been
+// written by the scalar instruction before this statement (5 wait states before a vector memory instruction reads them).
+__device__ __forceinline__ void pair_area_load(u32x4 rsrc /* wave-uniform */, unsigned voff, unsigned lds_dst /* wave-uniform */) {
+  unsigned keep;
+  asm volatile(
+      "s_waitcnt lgkmcnt(0)\n\t"  // no read of the area is still on its way (the brick or the group before)
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 4\n\t"
+      "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(voff), "s"(lds_dst), "s"(rsrc)
+      : "memory");
+}
+// every load of the area has landed (and every other vector memory access of the wave: at the head of a window pair none is
+// in flight but the area's)
+__device__ __forceinline__ void pair_area_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // buffer loads: 32-bit per-lane byte offset, hardware range check (an out-of-range offset returns 0
 // instead of faulting), descriptor in SGPRs built once per map.  The table is stored top-down, so the
@@ -585,8 +626,47 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
   // (round 5: WinPair entries of 16 bytes, 32 views at a time: lane l holds dwords 2l and 2l + 1 of the block's 128, i.e. view v's
   // origin and a.x in lane 2 (v & 31), its a.y and a.cz in the next lane)
   // (the table is laid out [block of 32 views][brick][32 views], win_pair_index: those 512 bytes are one piece of it)
+  // (r40a: the entries go to LDS instead, a GROUP of 256 views at a time -- eight of those pieces, requested together when the brick
+  // starts and when the view loop enters another group, by four LDS-direct loads whose trips overlap; a window pair reads its 16
+  // bytes from there.  No register holds anything of it across a column, and a brick of up to 256 views waits for the table once
+  // instead of once per 32 views.  -DDMI_WINPAIR_LANE_HELD builds the lane-held form: tools/exp_list_winpair_lds.txt)
+#ifdef DMI_WINPAIR_LANE_HELD
   [[maybe_unused]] uint32_t pair_a = 0, pair_b = 0;
+#endif
   for (int wbase = first_map & ~7; wbase < m_end; wbase += 8) {
+#ifndef DMI_WINPAIR_LANE_HELD
+    if constexpr (WIN) {
+      if ((wbase & (kPairGroupViews - 8)) == 0 || wbase == (first_map & ~7)) {  // wave-uniform: the first word of a group, or of the fusion
+        const kernarg_t ko = KFRESH();
+        if (ko->win_origin) {
+          // Block b's piece of this brick starts at byte ((b * n_class_bricks + brick) << 9) of the table (win_pair_index).  One load
+          // takes two of them: lanes 0-31 the piece of block b, lanes 32-63 that of block b + 1, win_pair_piece_stride bytes further
+          // on (a 32-bit offset: win_pair_pieces_addressable, asked by the host).  A descriptor per load, based on block b's piece and
+          // ranging to the table's end (win_pair_fill, fusion_launch_rules.h; tests/cpp/winpair_fill_host.cpp): blocks beyond the
+          // table's pitch get a range of 0 and read zeros.  All of it but the lane's offset is scalar arithmetic on this read of
+          // the argument block.
+          const uint64_t row_off = (uint64_t)(reinterpret_cast<intptr_t>(crow) - reinterpret_cast<intptr_t>(ko->classes));
+          const uint64_t brick = row_off >> __builtin_ctz((unsigned)ko->class_pitch);
+          const uint64_t n_bricks = (uint64_t)(uint32_t)ko->n_class_bricks;  // (< 2^22)
+          const uint64_t table = reinterpret_cast<uint64_t>(ko->win_origin);
+          const unsigned voff = ((unsigned)(lane & 31) << 4) + ((lane & 32) ? (unsigned)win_pair_piece_stride(n_bricks) : 0u);
+          const unsigned area0 = (unsigned)reinterpret_cast<uintptr_t>(pair_area());
+          const unsigned block0 = (unsigned)(wbase >> 8) << 3;  // the group's first block
+#pragma unroll
+          for (int q = 0; q < kPairGroupViews / 64; ++q) {
+            const WinPairFill f = win_pair_fill(brick, block0 + 2u * (unsigned)q, n_bricks, (uint32_t)ko->class_pitch);
+            const uint64_t base = table + f.first;
+            u32x4 rsrc;
+            rsrc.x = (uint32_t)base;
+            rsrc.y = (uint32_t)(base >> 32) & 0xffffu;  // stride 0: a raw buffer
+            rsrc.z = f.range;
+            rsrc.w = 0x00020000u;
+            pair_area_load(rsrc, voff, area0 + 1024u * (unsigned)q);
+          }
+        }
+      }
+    }
+#else
     if constexpr (WIN) {
       if ((wbase & 24) == 0 || wbase == (first_map & ~7)) {  // wave-uniform: the first word of a block of 32 views, or of the fusion
         const kernarg_t ko = KFRESH();
@@ -610,6 +690,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         }
       }
     }
+#endif
     // fetched one word ahead: its latency hides behind this word's views.  behind_mask turns BEHIND (2) into SKIP (3)
     // when x + 0.0 == x for every running sum: sums that start at +0.0 never become -0.0
     const unsigned long long cword = cnext | ((cnext >> 1) & (ZF ? 0x0101010101010101ull : KC(behind_mask)));
@@ -686,12 +767,25 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         ++dbg_win;
         if (dbg_cols == dbg_win) ++dbg_win_early;
 #endif
+#ifdef DMI_WINPAIR_LANE_HELD
         // the pair's entry (WinPair): four dwords out of the two lane-held vectors
         const int pl = (m & 31) * 2;
         const uint32_t org = (uint32_t)__builtin_amdgcn_readlane((int)pair_a, pl);
         const unsigned long long A2 = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)pair_b, pl) |
                                       ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)pair_a, pl + 1) << 32);
         const float acz = __int_as_float(__builtin_amdgcn_readlane((int)pair_b, pl + 1));
+#else
+        // the pair's entry (WinPair) out of the wave's area in LDS: one read of 16 bytes at a wave-uniform address, every lane
+        // gets the same four dwords.  The origin goes on to the scalar side (the addresses below are formed there); a and c.z are
+        // per-lane operands as they are.  The read is on its way while the window record is fetched: one wait covers both.
+        pair_area_wait();
+        const u32x4 entry = pair_area()[m & (kPairGroupViews - 1)];
+        const uint32_t org = (uint32_t)__builtin_amdgcn_readfirstlane((int)entry.x);
+        f32x2 A2;
+        A2.x = __uint_as_float(entry.y);
+        A2.y = __uint_as_float(entry.z);
+        const float acz = __uint_as_float(entry.w);
+#endif
         const int x0p = (int)(org & 0xffffu), y0p = (int)(org >> 16);
         // the view's window record: ONE line through one scalar load (WinRec, fusion_kernels.h)
         const kernarg_t kw = KFRESH();
@@ -744,7 +838,11 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         const f32x2 Bwi = pk_fnma_slo(O, pair_of(8), vec_of(2));
         const f32x2 Bwj = pk_fnma_slo(O, pair_of(10), vec_of(4));
         const f32x2 DH = pk_fnma_slo(O, pair_of(12), vec_of(6));
+#ifdef DMI_WINPAIR_LANE_HELD
         const f32x2 H0 = pk_fma_hi0_vv(LJ, Bwj, pk_fma_lo0_vs(LJ, Bwi, A2));
+#else
+        const f32x2 H0 = pk_fma_hi0_vv(LJ, Bwj, pk_fma_lo0_vv(LJ, Bwi, A2));
+#endif
         f32x2 CA;  // (c.z, threshold) at the brick's first voxel: thr = c1 * c.z - e_abs
         CA.x = acz;
         CA.y = __builtin_fmaf(acz, __uint_as_float(R[15]), -__uint_as_float(R[14]));
@@ -1618,27 +1716,33 @@ hipError_t launch_shape(const TileArgs &a, const FuseConfig &cfg, hipStream_t s)
            : cfg.holes ? (a.n_maps >= 48 && voxels >= (int64_t(1) << 25))
                        : (a.n_maps >= kPersistentMinViews && voxels >= (int64_t(1) << 27));
   }
-  // (persistent one-wave workgroups: as many as the chip holds, asked once per instantiation)
-  auto launch = [&](auto kernel, bool persistent) {
+  // (persistent one-wave workgroups: as many as the chip holds, asked once per KERNEL -- the kernels of one shape all have the
+  // same type, so the question hangs on a tag type per call below, not on the kernel's: they differ in registers and in LDS)
+  auto launch = [&](auto kernel, bool persistent, auto which) {
     unsigned n = blocks;
     if (persistent && one_wave) {
-      static const unsigned resident = resident_workgroups(kernel, 64);
+      static const unsigned resident = resident_workgroups(kernel, 64);  // (one per instantiation of this call operator, i.e. per `which`)
       n = std::min(n, resident);
     }
+    (void)which;
     hipLaunchKernelGGL(kernel, dim3(n), block, 0, s, a);
     return hipGetLastError();
   };
+  typedef std::integral_constant<int, 0> counted_t;
+  typedef std::integral_constant<int, 1> per_brick_t;
+  typedef std::integral_constant<int, 2> persistent_t;
+  typedef std::integral_constant<int, 3> general_t;
   if constexpr (!WIN) {  // hit counters (a diagnostic): the persistent form whatever the size
-    if (cfg.count_hits) return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, true, ROT, GENK>, true);
+    if (cfg.count_hits) return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, true, ROT, GENK>, true, counted_t{});
   }
   if constexpr (one_wave && !rare) {
     if (zf) {
-      if (!stay) return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, false, ROT, GENK, false, WIN, true>, false);
-      return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, false, ROT, GENK, true, WIN, true>, true);
+      if (!stay) return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, false, ROT, GENK, false, WIN, true>, false, per_brick_t{});
+      return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, false, ROT, GENK, true, WIN, true>, true, persistent_t{});
     }
   }
   // a grid that may hold -0.0 (handed out as a device pointer, or uploaded with one in it): the persistent form whatever the size
-  if constexpr (!WIN) return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, false, ROT, GENK>, true);
+  if constexpr (!WIN) return launch(fuse_tile_kernel<DepthT, GridT, TK, WX, WY, MINW, GROUP, false, ROT, GENK>, true, general_t{});
   return hipErrorInvalidValue;
 }
 
