@@ -124,6 +124,7 @@ ABI_SYMBOLS = [
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds",
+    "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
     "dmi_multi_add_views_f32", "dmi_multi_add_local_views", "dmi_multi_add_local_views_f32", "dmi_multi_clear_views", "dmi_multi_fuse", "dmi_multi_synchronize",
@@ -132,6 +133,17 @@ ABI_SYMBOLS = [
 ]
 
 _lib = None
+
+
+def point_smoothing_weights(sigma: float, truncate: float = 3.0) -> np.ndarray:
+    """k_0..k_r, the normalised weights of one axis of the point smoothing with r = ceil(truncate * sigma), as the library
+    computes them (dmi_point_smoothing_weights; no GPU needed).  DmiError with code 1 for parameters outside the definition."""
+    L = load()
+    r, k = ctypes.c_int32(0), np.zeros(17, dtype=np.float64)
+    code = L.dmi_point_smoothing_weights(float(sigma), float(truncate), ctypes.byref(r), _dp(k))
+    if code != 0:
+        raise DmiError(code, (L.dmi_last_error(None) or b"").decode())
+    return k[:int(r.value) + 1].copy()
 
 
 class DmiError(RuntimeError):
@@ -225,6 +237,11 @@ def load() -> ctypes.CDLL:
         L.dmi_download_isosurface_support.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
         L.dmi_get_isosurface_support_kernel_ms.argtypes = [vp, dp]
         L.dmi_get_isosurface_support_pass_ms.argtypes = [vp, dp]
+    if hasattr(L, "dmi_set_point_smoothing"):
+        L.dmi_point_smoothing_weights.argtypes = [dbl, dbl, ctypes.POINTER(i32), dp]
+        L.dmi_set_point_smoothing.argtypes = [vp, dp, dbl]
+        L.dmi_get_point_smoothing.argtypes = [vp, dp, dp]
+        L.dmi_get_point_smoothing_kernel_ms.argtypes = [vp, dp]
     L.dmi_get_brick_class_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.dmi_get_mixed_reason_histogram.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     if hasattr(L, "dmi_get_window_pair_count"):  # (absent from an older prebuilt library loaded for an A/B timing, tools/gpu_exp.py)
@@ -503,6 +520,27 @@ class FusionContext:
         out = np.empty((nz + 1) * (ny + 1) * (nx + 1), dtype=np.float64)
         self._check(self._lib.dmi_download_point_data_f64(self._h, _dp(out)))
         return out.reshape(nz + 1, ny + 1, nx + 1)
+
+    def set_point_smoothing(self, sigma, truncate: float = 3.0) -> None:
+        """A Gaussian over the point data from now on: every computation of the point data is followed by three separable
+        passes with `sigma` lattice steps per axis (a scalar stands for all three; 0 skips an axis, all 0 switch it off),
+        cut off at `truncate` sigmas, and download_point_data, iso_active_cells and the extractions read the smoothed field
+        (dmi_set_point_smoothing).  A refused call keeps the old setting."""
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (3,)))
+        self._check(self._lib.dmi_set_point_smoothing(self._h, _dp(s), float(truncate)))
+
+    def point_smoothing(self):
+        """(sigma [3] f64, truncate) of the setting (dmi_get_point_smoothing); zeros and 3.0 in a new context."""
+        s, t = np.zeros(3, dtype=np.float64), ctypes.c_double(0)
+        self._check(self._lib.dmi_get_point_smoothing(self._h, _dp(s), ctypes.byref(t)))
+        return s, float(t.value)
+
+    def point_smoothing_kernel_ms(self) -> float:
+        """hipEvent milliseconds of the smoothing kernels of the last computation of the point data; 0 while the setting is off
+        (dmi_get_point_smoothing_kernel_ms)."""
+        a = ctypes.c_double(0)
+        self._check(self._lib.dmi_get_point_smoothing_kernel_ms(self._h, ctypes.byref(a)))
+        return float(a.value)
 
     def iso_active_cells(self, iso: float, ids: bool = True):
         """(count, ids): the cells whose corner point values straddle `iso` (dmi_iso_active_cells); ids ascending int64, or
@@ -1460,7 +1498,8 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_consistency_rel_tolerance", ctypes.c_double),
                 ("grid_auto_bounds", ctypes.c_int32), ("grid_auto_bounds_trim", ctypes.c_double),
                 ("grid_auto_bounds_margin", ctypes.c_double), ("grid_auto_bounds_pixel_step", ctypes.c_int64),
-                ("mesh_fill_holes", ctypes.c_int64)]
+                ("mesh_fill_holes", ctypes.c_int64),
+                ("contour_smooth_sigma", ctypes.c_double * 3), ("contour_smooth_truncate", ctypes.c_double)]
 
 
 def cli_read_arguments(args):

@@ -302,6 +302,7 @@ void dmi_destroy(dmi_context *ctx) {
   ctx->volume.release();
   ctx->tables.release();
   ctx->c2p.release();
+  ctx->point_smoothing.release();
   ctx->mesh.release();
   ctx->extraction.release();
   ctx->components.release();

@@ -26,12 +26,21 @@ int64_t n_points(const dmi_context *c) {
 }  // namespace
 
 int dmi::drain_c2p(dmi_context *ctx) {
-  if (!ctx->c2p.pending) return DMI_OK;
-  DMI_HIP(ctx, hipEventSynchronize(ctx->c2p.events[1]));
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->c2p.events[0], ctx->c2p.events[1]));
-  ctx->timings.last_cell_to_point_ms = ms;
-  ctx->c2p.pending = false;
+  if (ctx->c2p.pending) {
+    DMI_HIP(ctx, hipEventSynchronize(ctx->c2p.events[1]));
+    float ms = 0.f;
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->c2p.events[0], ctx->c2p.events[1]));
+    ctx->timings.last_cell_to_point_ms = ms;
+    ctx->c2p.pending = false;
+  }
+  dmi_context::PointSmoothing &ps = ctx->point_smoothing;
+  if (ps.pending) {  // the smoothing passes that followed it (dmi_set_point_smoothing)
+    DMI_HIP(ctx, hipEventSynchronize(ps.events[1]));
+    float ms = 0.f;
+    DMI_HIP(ctx, hipEventElapsedTime(&ms, ps.events[0], ps.events[1]));
+    ps.last_kernel_ms = ms;
+    ps.pending = false;
+  }
   return DMI_OK;
 }
 
@@ -49,12 +58,31 @@ int dmi_cell_to_point(dmi_context *ctx) {
   if (rc != DMI_OK) return rc;
   rc = ensure_buffer(ctx, ctx->c2p.points, (uint64_t)n_points(ctx) * 8);
   if (rc != DMI_OK) return rc;
+  // dmi_set_point_smoothing: the passes ping-pong between the point buffer and a second one of its size and must end in the
+  // former, so after an odd number of them the cell -> point pass writes into the second
+  dmi_context::PointSmoothing &ps = ctx->point_smoothing;
+  const int passes = ps.on ? dmi::point_smooth_launches(ps.args) : 0;
+  if (ps.on) {
+    rc = ensure_buffer(ctx, ps.scratch, (uint64_t)n_points(ctx) * 8);
+    if (rc != DMI_OK) return rc;
+    if (!ps.events[0])
+      for (hipEvent_t &e : ps.events) DMI_HIP(ctx, hipEventCreate(&e));
+  }
+  double *first = passes % 2 ? ps.scratch.as<double>() : ctx->c2p.points.as<double>();
+  double *second = passes % 2 ? ctx->c2p.points.as<double>() : ps.scratch.as<double>();
   if (!ctx->c2p.events[0])
     for (hipEvent_t &e : ctx->c2p.events) DMI_HIP(ctx, hipEventCreate(&e));
   DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[0], ctx->stream));
-  DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->volume.d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, ctx->c2p.points.as<double>(),
+  DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->volume.d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, first,
                                          ctx->grid.cell_dims[0], ctx->grid.cell_dims[1], ctx->grid.cell_dims[2], ctx->stream));
   DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[1], ctx->stream));
+  if (ps.on) {
+    DMI_HIP(ctx, hipEventRecord(ps.events[0], ctx->stream));
+    DMI_HIP(ctx, dmi::launch_point_smooth(first, second, ctx->grid.cell_dims[0], ctx->grid.cell_dims[1], ctx->grid.cell_dims[2], ps.args,
+                                          ctx->stream));
+    DMI_HIP(ctx, hipEventRecord(ps.events[1], ctx->stream));
+    ps.pending = true;
+  }
   ctx->c2p.pending = true;
   ctx->c2p.valid = true;
   return DMI_OK;
@@ -80,6 +108,68 @@ int dmi_point_data_device_pointer(dmi_context *ctx, void **ptr) {
   int rc = dmi_cell_to_point(ctx);
   if (rc != DMI_OK) return rc;
   *ptr = ctx->c2p.points.ptr;
+  return DMI_OK;
+  });
+}
+
+int dmi_point_smoothing_weights(double sigma, double truncate, int32_t *radius, double *weights) {
+  return guarded(nullptr, "dmi_point_smoothing_weights", [&]() -> int {
+  if (dmi::point_smoothing_weights(sigma, truncate, radius, weights) != 0)
+    return fail(nullptr, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_point_smoothing_weights: sigma must be finite and >= 0, truncate finite and in (0, 4], ceil(truncate * sigma) <= 16, "
+                "and the pointers not null");
+  return DMI_OK;
+  });
+}
+
+int dmi_set_point_smoothing(dmi_context *ctx, const double sigma[3], double truncate) {
+  return guarded(ctx, "dmi_set_point_smoothing", [&]() -> int {
+  if (!ctx || !sigma) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_set_point_smoothing: null argument");
+  if (ctx->opt.z_first != 0)
+    return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                "dmi_set_point_smoothing: the context holds a z-slab (z_first != 0); its lattice is not the grid's");
+  dmi::PointSmoothArgs args{};
+  for (int a = 0; a < 3; ++a)
+    if (dmi::point_smoothing_weights(sigma[a], truncate, &args.r[a], args.k[a]) != 0)
+      return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
+                  "dmi_set_point_smoothing: sigma[" + std::to_string(a) + "] must be finite and >= 0, truncate finite and in (0, 4], and "
+                  "the radius ceil(truncate * sigma) at most 16");
+  dmi_context::PointSmoothing &ps = ctx->point_smoothing;
+  if (sigma[0] == ps.sigma[0] && sigma[1] == ps.sigma[1] && sigma[2] == ps.sigma[2] && truncate == ps.truncate) return DMI_OK;
+  const bool on = sigma[0] != 0.0 || sigma[1] != 0.0 || sigma[2] != 0.0;
+  for (int a = 0; a < 3; ++a) ps.sigma[a] = sigma[a] + 0.0;  // (a -0.0 is stored as 0)
+  ps.truncate = truncate;
+  ps.args = args;
+  if (!on && !ps.on) return DMI_OK;  // off before and after: the point data is what it was
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  ps.on = on;
+  ctx->c2p.valid = false;
+  if (!on) {  // the state after dmi_create: no second buffer, no kernel time
+    const int rc = drain_c2p(ctx);
+    ps.last_kernel_ms = 0.0;
+    dmi::drop_buffers(ctx, {&ps.scratch});  // (hipFree waits for the passes that may still read it)
+    return rc;
+  }
+  return DMI_OK;
+  });
+}
+
+int dmi_get_point_smoothing(dmi_context *ctx, double sigma[3], double *truncate) {
+  return guarded(ctx, "dmi_get_point_smoothing", [&]() -> int {
+  if (!ctx || !sigma || !truncate) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_point_smoothing: null argument");
+  for (int a = 0; a < 3; ++a) sigma[a] = ctx->point_smoothing.sigma[a];
+  *truncate = ctx->point_smoothing.truncate;
+  return DMI_OK;
+  });
+}
+
+int dmi_get_point_smoothing_kernel_ms(dmi_context *ctx, double *last) {
+  return guarded(ctx, "dmi_get_point_smoothing_kernel_ms", [&]() -> int {
+  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_point_smoothing_kernel_ms: null argument");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  const int rc = drain_c2p(ctx);
+  if (rc != DMI_OK) return rc;
+  *last = ctx->point_smoothing.on ? ctx->point_smoothing.last_kernel_ms : 0.0;
   return DMI_OK;
   });
 }

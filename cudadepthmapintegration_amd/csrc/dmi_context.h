@@ -155,6 +155,18 @@ struct dmi_context {
     bool pending = false;
     void release() { dmi::free_buffers({&points}); dmi::destroy_events(events); }
   } c2p;
+  // dmi_set_point_smoothing (point_smooth.hip): while `on`, every computation of c2p.points is followed by the smoothing passes
+  // and c2p.points holds their result
+  struct PointSmoothing {
+    double sigma[3] = {0.0, 0.0, 0.0}, truncate = 3.0;
+    bool on = false;             // some sigma is not 0
+    dmi::PointSmoothArgs args{}; // the radii and weights of the setting
+    dmi::DeviceBuffer scratch;   // the passes' second buffer, of the point data's size; held only while on
+    hipEvent_t events[2] = {nullptr, nullptr};  // start, stop around the smoothing kernels
+    bool pending = false;
+    double last_kernel_ms = 0.0;  // of the last recomputation; 0 when off
+    void release() { dmi::free_buffers({&scratch}); dmi::destroy_events(events); }
+  } point_smoothing;
   // The mesh of the last extraction, as the support trim, the filter, the smoother and the decimation have left it.  The filter and the decimation
   // write into the alternates and the smoother steps through alt_vertices and smoothing.vertices (normals into alt_normals);
   // whichever holds the result is then swapped with the mesh's own buffer.

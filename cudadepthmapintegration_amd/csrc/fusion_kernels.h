@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "fusion_launch_rules.h"  // the variant bits and the thresholds of the launch decisions
+#include "point_smooth_rules.h"   // the point smoothing's radius cap and weights
 #include "view_records.h"         // the per-view records, the validity maps' and the window column's constants
 
 struct dmi_context;  // include/dmi.h
@@ -263,6 +264,17 @@ hipError_t launch_order_bricks(const TileArgs &args, int wx, int wy, uint8_t *le
 // from cells[nz][ny][nx] (grid_post.hip)
 hipError_t launch_cell_to_point(const void *cells, int cells_are_f64, double *points, int nx, int ny, int nz,
                                 hipStream_t stream);
+
+// The separable Gaussian over the point data (point_smooth.hip): per axis x, y, z the radius (0: the axis is
+// skipped) and the normalised weights k_0..k_r (point_smooth_rules.h: point_smoothing_weights)
+struct PointSmoothArgs {
+  int32_t r[3];
+  double k[3][kPointSmoothMaxRadius + 1];
+};
+// How many kernels launch_point_smooth runs for these radii.  It reads `first` ((nx+1)(ny+1)(nz+1) f64) and ping-pongs between the
+// two buffers: the result is in `first` after an even number of launches and in `second` after an odd one.
+int point_smooth_launches(const PointSmoothArgs &a);
+hipError_t launch_point_smooth(double *first, double *second, int nx, int ny, int nz, const PointSmoothArgs &a, hipStream_t stream);
 
 // Iso-value pre-pass over the point data (grid_post.hip): blocks of 256 cells of one x-row; counts / bases have
 // iso_block_count() + 1 entries (bases' last one receives the total number of active cells)

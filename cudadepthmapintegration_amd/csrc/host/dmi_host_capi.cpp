@@ -385,6 +385,8 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->grid_auto_bounds_margin = o.gridAutoBoundsMargin;
   out->grid_auto_bounds_pixel_step = o.gridAutoBoundsPixelStep;
   out->mesh_fill_holes = o.meshFillHoles;
+  for (size_t a = 0; a < o.contourSmoothSigma.size() && a < 3; ++a) out->contour_smooth_sigma[a] = o.contourSmoothSigma[a];
+  out->contour_smooth_truncate = o.contourSmoothTruncate;
   return 1;
   });
 }

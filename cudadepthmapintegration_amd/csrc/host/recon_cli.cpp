@@ -16,6 +16,7 @@
 #include <ostream>
 #include <sstream>
 
+#include "../point_smooth_rules.h"
 #include "recon_host.h"
 
 namespace dmi {
@@ -261,6 +262,26 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                        return into_count(&o->gridAutoBoundsPixelStep)(values) && o->gridAutoBoundsPixelStep >= 1 &&
                                               o->gridAutoBoundsPixelStep <= 0x7fffffffLL;
                                      }}},
+      {"--contourSmoothSigma", {Kind::kMulti, "with --extractMesh: smooth the point data on the GPU with a Gaussian right before the "
+                                              "contour, as a vtkImageGaussianSmooth in front of vtkContourFilter does: sigma in voxels, "
+                                              "one value or one per grid axis (finite, >= 0; 0 skips the axis; the radius "
+                                              "ceil(truncate * sigma) is at most 16).  The .mha and .vts volumes and the count of "
+                                              "active cells stay what was fused (default 0 = off; not in the reference)",
+                                [o](const std::vector<std::string> &values) {
+                                  if (values.size() != 1 && values.size() != 3) return false;
+                                  o->contourSmoothSigma.clear();
+                                  for (const std::string &v : values) {
+                                    double x = 0.0;
+                                    if (!parse_number(v, &x) || !std::isfinite(x) || x < 0.0) return false;
+                                    o->contourSmoothSigma.push_back(x);
+                                  }
+                                  o->contourSmoothSigma.resize(3, o->contourSmoothSigma[0]);
+                                  return true;
+                                }}},
+      {"--contourSmoothTruncate", {Kind::kValue, "with --contourSmoothSigma: the Gaussian is cut off at this many sigmas (finite, in "
+                                                 "(0, 4], default 3; not in the reference)",
+                                   into_checked_double(&o->contourSmoothTruncate, &o->contourSmoothTruncateGiven,
+                                                       [](double x) { return x > 0.0 && x <= 4.0; })}},
       {"--help", {Kind::kFlag, "print this text", into_flag(help)}},
   };
 }
@@ -362,6 +383,20 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   if (o->meshFillHolesGiven && !o->extractMesh) {
     err << "Error : --meshFillHoles needs --extractMesh (the holes belong to the extracted mesh).\n" << HelpText();
     return false;
+  }
+  for (const auto &flag : {std::make_pair("--contourSmoothSigma", !o->contourSmoothSigma.empty()),
+                           std::make_pair("--contourSmoothTruncate", o->contourSmoothTruncateGiven)})
+    if (flag.second && !o->extractMesh) {
+      err << "Error : " << flag.first << " needs --extractMesh (the smoothing belongs to the contour).\n" << HelpText();
+      return false;
+    }
+  for (const double sigma : o->contourSmoothSigma) {  // the library's own rule: ceil(truncate * sigma) <= 16
+    int32_t radius = 0;
+    double weights[17];
+    if (dmi::point_smoothing_weights(sigma, o->contourSmoothTruncate, &radius, weights) != 0) {
+      err << "Bad value for --contourSmoothSigma: the radius ceil(truncate * sigma) must not exceed 16\n" << HelpText();
+      return false;
+    }
   }
   if (o->meshDecimateCellSizeGiven && !o->extractMesh) {
     err << "Error : --meshDecimateCellSize needs --extractMesh (the decimation belongs to the extracted mesh).\n" << HelpText();
@@ -713,6 +748,11 @@ void describe(const Options &o, std::ostream &out, bool with_sketch) {
       << (o.extractMesh ? " (surface extracted: --extractMesh)\n" : " (no surface is extracted by this tool)\n");
 }
 
+// --contourSmoothSigma with a sigma that is not 0
+bool contourSmoothed(const Options &o) {
+  return std::any_of(o.contourSmoothSigma.begin(), o.contourSmoothSigma.end(), [](double s) { return s > 0.0; });
+}
+
 }  // namespace
 
 int Run(const Options &given, int argc, const char *const *argv, std::ostream &log, RunResult *result) {
@@ -921,8 +961,18 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (rc == DMI_OK && o.extractMesh) {
       // vtkContourFilter + vtkTransformFilter (rmain:166-182) on the device; vtkXMLPolyDataWriter (rmain:184-187) below
       uint64_t nv = 0, nt = 0;
+      // --contourSmoothSigma: set here, behind the download and the pre-pass above, so that the volume files and the count of
+      // active cells are what they are without the flag; the extraction recomputes the point data and smooths it
+      const bool contourSmooth = contourSmoothed(o);
+      if (contourSmooth) {
+        rc = dmi_set_point_smoothing(ctx, o.contourSmoothSigma.data(), o.contourSmoothTruncate);
+        double weights[17];
+        for (int a = 0; a < 3; ++a)  // (the radii, for the log: the parser has checked the parameters)
+          (void)dmi::point_smoothing_weights(o.contourSmoothSigma[(size_t)a], o.contourSmoothTruncate, &result->contourSmoothRadius[a], weights);
+      }
       // (the facing test needs the normals whether they are written or not)
-      rc = o.meshNormals || supportFacing ? dmi_extract_isosurface_normals(ctx, o.contour, &nv, &nt) : dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      if (rc == DMI_OK) rc = o.meshNormals || supportFacing ? dmi_extract_isosurface_normals(ctx, o.contour, &nv, &nt) : dmi_extract_isosurface(ctx, o.contour, &nv, &nt);
+      if (rc == DMI_OK && contourSmooth) rc = dmi_get_point_smoothing_kernel_ms(ctx, &result->contourSmoothKernelMs);
       if (rc == DMI_OK && o.meshMinSupportViews > 0) {  // first: the fragments it leaves are the component flags' to remove
         result->meshVerticesBeforeSupport = nv;
         result->meshTrianglesBeforeSupport = nt;
@@ -1049,6 +1099,11 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     log << "mesh: " << o.outputMeshFilename << ": " << result->meshVertices << " vertices, " << result->meshTriangles
         << " triangles at the contour value " << o.contour << " (" << result->contourActiveCells << " of "
         << (long long)(dims[0] - 1) * (dims[1] - 1) * (dims[2] - 1) << " cells straddle it)" << std::endl;
+    if (contourSmoothed(o))
+      log << "contour smoothing: sigma " << o.contourSmoothSigma[0] << " " << o.contourSmoothSigma[1] << " " << o.contourSmoothSigma[2]
+          << " voxels, truncate " << o.contourSmoothTruncate << ", radii " << result->contourSmoothRadius[0] << " "
+          << result->contourSmoothRadius[1] << " " << result->contourSmoothRadius[2] << "; " << result->contourSmoothKernelMs
+          << " ms of GPU kernels" << std::endl;
     if (o.meshMinSupportViews > 0)
       log << "mesh support: at least " << o.meshMinSupportViews << " of " << result->meshSupportViews << " views, depth tolerance "
           << o.meshSupportDepthTolerance << (supportFacing ? ", facing" : ", any facing") << "; " << result->meshVerticesBeforeSupport
@@ -1114,6 +1169,11 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
           << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";
+    if (contourSmoothed(o))  // (only with --extractMesh)
+      out << "  contour smoothing  sigma " << o.contourSmoothSigma[0] << " " << o.contourSmoothSigma[1] << " " << o.contourSmoothSigma[2]
+          << " voxels, truncate " << o.contourSmoothTruncate << ", radii " << result->contourSmoothRadius[0] << " "
+          << result->contourSmoothRadius[1] << " " << result->contourSmoothRadius[2] << ", " << result->contourSmoothKernelMs
+          << " ms of GPU kernels\n";
     if (o.meshMinSupportViews > 0)  // (only with --extractMesh)
       out << "  mesh support  at least " << o.meshMinSupportViews << " of " << result->meshSupportViews << " views, depth tolerance "
           << o.meshSupportDepthTolerance << (supportFacing ? ", facing" : ", any facing") << ", " << result->meshVerticesBeforeSupport

@@ -20,6 +20,9 @@
 // component flags, which then remove the fragments it leaves; --meshSupportArray writes the final mesh's counts.
 // --meshFillHoles N (not in the reference: what a vtkFillHolesFilter behind those would do) runs dmi_fill_isosurface_holes behind
 // the component flags and in front of the smoothing, which then moves the patches and the former rims with the rest.
+// --contourSmoothSigma S [S S] with --contourSmoothTruncate T (not in the reference: what a vtkImageGaussianSmooth in front of the
+// contour would do) sets dmi_set_point_smoothing directly before the extraction, after the point data of the .mha has been
+// downloaded and the active cells counted: the volume files hold what was fused, the smoothing belongs to the contour.
 // --depthConsistencyMinViews N with --depthConsistencyTolerance / --depthConsistencyRelTolerance (not in the reference: the geometric
 // consistency check of every depth-map fusion pipeline) reads all views into memory, filters their depths on the first device
 // (dmi_filter_depth_consistency) and fuses the filtered views through ReconstructionFilter::SetViews.
@@ -105,6 +108,11 @@ struct Options {
   // (dmi_fill_isosurface_holes) behind the support trim and the component flags and in front of the smoothing (0: off)
   long long meshFillHoles = 0;
   bool meshFillHolesGiven = false;
+  // not in the reference (needs --extractMesh): a Gaussian over the point data on the GPU right before the contour
+  // (dmi_set_point_smoothing), sigma per grid axis in voxels (one value stands for all three; all 0: off) and its truncation
+  std::vector<double> contourSmoothSigma;
+  double contourSmoothTruncate = 3.0;
+  bool contourSmoothTruncateGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -150,6 +158,9 @@ struct RunResult {
   // --meshFillHoles: the loops filled, the boundary edges left and the hipEvent time of the fill's kernels
   unsigned long long meshHolesFilled = 0, meshBoundaryEdgesLeft = 0;
   double meshFillHolesKernelMs = 0.0;
+  // --contourSmoothSigma: the radii per axis and the hipEvent time of the smoothing's kernels
+  int contourSmoothRadius[3] = {0, 0, 0};
+  double contourSmoothKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);

@@ -53,7 +53,8 @@ extern "C" {
                            *    dmi_get_isosurface_support_kernel_ms, dmi_get_isosurface_support_pass_ms;
                            *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency;
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
-                           *    dmi_get_isosurface_holes_pass_ms */
+                           *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
+                           *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -227,6 +228,39 @@ int dmi_grid_device_pointer(dmi_context *ctx, void **ptr);
 int dmi_cell_to_point(dmi_context *ctx);
 int dmi_download_point_data_f64(dmi_context *ctx, double *out);
 int dmi_point_data_device_pointer(dmi_context *ctx, void **ptr);
+
+/* A separable Gaussian over the point data, between dmi_cell_to_point and the contour: what a vtkImageGaussianSmooth in front of
+ * vtkContourFilter does to the voxel-scale noise of the summed ray potentials (only the intent is shared with that filter, not the
+ * numbers).  Additions to ABI 5, dmi_abi_version() stays 5; csrc/point_smooth.hip.  The input is the point data P on the lattice
+ * (nx+1) x (ny+1) x (nz+1), x fastest, exactly what dmi_cell_to_point produces; the output Q has the same shape and REPLACES it
+ * for every consumer.  Definition, met bit for bit:
+ *   - sigma[3] in LATTICE STEPS, one per grid axis (not world units: the filter acts on the lattice), each finite and >= 0;
+ *     truncate finite and in (0, 4];
+ *   - the radius on axis a is r_a = (int)ceil(truncate * sigma[a]); r_a > 16 is refused; sigma[a] == 0 means the axis is skipped,
+ *     and its pass is the identity on bits, not a multiplication by 1;
+ *   - weights, on the host, f64: w_i = exp(-(double)(i*i) / (2*sigma*sigma)) for i = 0..r, S = w_0 + 2*(((w_1 + w_2) + ...) + w_r),
+ *     k_i = w_i / S.  The library is the authority on these numbers (one libm's exp may differ from another's in the last bit):
+ *     dmi_point_smoothing_weights returns them;
+ *   - three passes, x then y then z, each over the full f64 result of the one before.  For a point with index q on the pass's axis,
+ *     which has N points: v(t) = the value at clamp(t, 0, N-1) (the border replicated, so a constant field stays constant up to the
+ *     rounding of the sum of the k); acc = k_0 * v(q); then for i = 1..r ascending acc = acc + k_i * (v(q-i) + v(q+i));
+ *   - f64, every operation rounded, no FMA, no reassociation; NaN, +-inf and signed zeros come out as this arithmetic makes them.
+ * dmi_point_smoothing_weights: pure host code, no device needed: *radius and weights[0..r] = k_0..k_r (room for 17) for one axis.
+ * DMI_ERR_INVALID_ARGUMENT for a sigma, truncate or radius outside the definition and for null pointers.
+ * dmi_set_point_smoothing is a SETTING of the context, not a one-shot filter: it stores the parameters and marks the point data
+ * stale; from then on every computation of the point data (dmi_cell_to_point, and whatever runs it) is followed by the passes, and
+ * dmi_download_point_data_f64, dmi_point_data_device_pointer, dmi_iso_active_cells, both extractions and the gradient normals
+ * read Q.  All sigmas 0 switches it off: the state after dmi_create, bit-identical to a context in which it was never set.  While it
+ * is on the context holds one more buffer of the point data's size.  Setting the values that are set already invalidates nothing.
+ * DMI_ERR_INVALID_ARGUMENT, the old setting kept: null pointers, parameters outside the definition, and a context created with
+ * dmi_options.z_first != 0 (a z-slab's lattice has the wrong borders, as for the extraction).
+ * dmi_get_point_smoothing returns the setting (zeros and 3 after dmi_create).  dmi_get_point_smoothing_kernel_ms: hipEvent time of
+ * the smoothing kernels of the last computation of the point data (dmi_timings.last_cell_to_point_ms stays the cell -> point kernel
+ * alone); 0 while the setting is off.  Synchronises if that computation is still running. */
+int dmi_point_smoothing_weights(double sigma, double truncate, int32_t *radius, double *weights /* [17]: k_0..k_r */);
+int dmi_set_point_smoothing(dmi_context *ctx, const double sigma[3], double truncate);
+int dmi_get_point_smoothing(dmi_context *ctx, double sigma[3], double *truncate);
+int dmi_get_point_smoothing_kernel_ms(dmi_context *ctx, double *last);
 
 /* The pre-pass of the step after that (Reconstruction/main.cxx:169-173: vtkContourFilter at `contour` over the point data,
  * i.e. marching cubes over every cell): which cells can produce triangles at all.  A corner is inside when its point value

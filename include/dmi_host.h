@@ -124,6 +124,9 @@ typedef struct dmi_cli_options {
   int64_t grid_auto_bounds_pixel_step;   /* --gridAutoBoundsPixelStep (default 1) */
   /* not in the reference, only with --extractMesh (dmi_fill_isosurface_holes, dmi.h); appended to the struct: */
   int64_t mesh_fill_holes;               /* --meshFillHoles N: close boundary loops of at most N edges before the smoothing; 0: off */
+  /* not in the reference, only with --extractMesh (dmi_set_point_smoothing, dmi.h); appended to the struct: */
+  double contour_smooth_sigma[3];        /* --contourSmoothSigma S [S S]: Gaussian over the point data before the contour, voxels; 0: off */
+  double contour_smooth_truncate;        /* --contourSmoothTruncate (default 3) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -148,7 +151,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * --gridEnd absent) every view is read into memory as well, filtered first if that was asked for, and the grid's box is what
  * dmi_estimate_scene_bounds gives along the grid's axes, plus a margin.  With --meshFillHoles N the mesh goes through
  * dmi_fill_isosurface_holes behind the support trim and the component flags and in front of the smoothing (RegionId: from the
- * labelling run again on the filled mesh, unless a decimation behind it does that). */
+ * labelling run again on the filled mesh, unless a decimation behind it does that).  With --contourSmoothSigma S the context's
+ * point smoothing is set (dmi_set_point_smoothing) directly before the extraction: the .mha, the .vts and the count of active cells
+ * are what they are without the flag. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
