@@ -854,6 +854,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         asm volatile("" : "+s"(M2));  // a register pair for the column's life (as a constant its high half was rebuilt for every other voxel)
         float magic_v = 0x1.8p23f + (float)(4 * kWinAnchorY);  // ... plus 4 * the anchor's row (the row address below), in a vector register (a scalar operand would make the FMA above a slower encoding)
         asm volatile("" : "+v"(magic_v));
+#ifdef DMI_WIN_REDO_LOADS_IN_LOOP  // (the redo loop as it was: its text below, under the same switch)
         // fp64 values at the column's first voxel for the redo below: the centred h.x, h.y (TileMapRec::cpx ...) and the exact
         // c.z (cu:92, cu:172), as every tier-1 column starts from them
         auto first_voxel = [&](double &hxf, double &hyf, double &czf64) __attribute__((always_inline)) {
@@ -870,6 +871,7 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
           hxf = __builtin_fma(cload(&rf->cpx), wxf, __builtin_fma(cload(&rf->cpy), wyf, __builtin_fma(cload(&rf->cpz), wzf, cload(&rf->cp0))));
           hyf = __builtin_fma(cload(&rf->cqx), wxf, __builtin_fma(cload(&rf->cqy), wyf, __builtin_fma(cload(&rf->cqz), wzf, cload(&rf->cq0))));
         };
+#endif
         uint32_t undecided = 0, und_kk = 0;  // per lane / wave-uniform: bit kk = voxel kk is redone after the column
         uint32_t window = 0;                 // this lane's row of the window
         constexpr int WG = 4;                // voxels per group
@@ -882,7 +884,17 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
 #else
         constexpr bool kNewton = true;
 #endif
+        // The group's 32 links and four row addresses are ONE asm statement (win_group4, fusion_tile_acc.inc): between two
+        // statements the compiler pads a wait state before an immediate reader, inside one nothing is padded.
+        // -DDMI_WIN_GROUP_LINKS: every link a statement of its own, as before (same results: tools/exp_list_window_group_asm.txt);
+        // -DDMI_T1_RCP_EVERY_VOXEL implies it.  The 8-voxel kernels (80 registers for the compiler) keep the links: see kGroupAsm.
+#if defined(DMI_WIN_GROUP_LINKS) || defined(DMI_T1_RCP_EVERY_VOXEL)
+        constexpr bool kGroupAsm = false;
+#else
+        constexpr bool kGroupAsm = TK == 16;
+#endif
         [[maybe_unused]] f32x2 r_below;      // (low half) the reciprocal of the last voxel of the group before
+        [[maybe_unused]] float r_below_asm;  // the same where the group is one statement: it stays in one register
         // A group's look-ups are issued after its candidates and consumed after the NEXT group's candidates: neither the
         // window's loads nor a look-up's trip through the LDS crossbar is waited for
         uint32_t pw[WG], pc[WG];             // the previous group's words and columns
@@ -913,7 +925,16 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
           // whether the statement was a transcendental or wrote half a register) -- six per voxel when a chain runs on its own
           mask_t m_und[WG];
           constexpr int IL = DMI_T1_CHAINS;  // voxels whose chains alternate
-          if constexpr (kNewton) {
+          if constexpr (kGroupAsm) {
+            f32x2 rpm[WG];
+            float mx[WG], thr[WG];
+            win_group4<BASE>(g0, H0, DH, C0, DC, M2, magic_v, r_below_asm, rpm, mx, thr, wg);
+  #pragma unroll
+            for (int u = 0; u < WG; ++u) {
+              m_und[u] = ballot(!(mx[u] < thr[u]));  // (a NaN is not accepted)
+              cg[u] = (uint32_t)__float_as_int(rpm[u].x);
+            }
+          } else if constexpr (kNewton) {
             // The group's four chains by hand: the reciprocals hang on one another (voxel u's on voxel u - 1's), so the chains are
             // staggered by two links instead of running side by side -- still one instruction at least between a producer and its reader
             static_assert(WG == 4, "the link order below is written for groups of four");
@@ -1008,6 +1029,9 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         // ---- the voxels in which some lane was not accepted (about 2 % of a wave's): tier 2 (DESIGN.md 4.1-4.5 in centred
         // coordinates), then the reference's own expression for what that leaves; at most one add per voxel and view, after the
         // column and before the next view: every voxel accumulates in view order (cu:211)
+#ifdef DMI_WIN_REDO_LOADS_IN_LOOP
+        // every redone voxel fetches the record and the column's first voxel anew: the loop as it was, text for text (an A/B switch
+        // for tools/gpu_exp.py, tools/exp_list_window_group_asm.txt)
 #pragma unroll 1
         while (und_kk) {  // wave-uniform
 #ifdef DMI_TUNING
@@ -1061,6 +1085,98 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
             if (kk == q) acc_add_v<BASE, TK>(q, ballot(hit), val);  // wave-uniform
           }
         }
+#else
+        // What a redone voxel needs once its h'', its exact c.z and the record's cerrk are there:
+        auto redo_voxel = [&](int kk, double hxk, double hyk, double cz2, double cerrk) __attribute__((always_inline)) {
+          const bool mine = (undecided >> kk) & 1u;
+          const double r0 = __builtin_amdgcn_rcp(cz2);
+          const double e0 = __builtin_fma(-cz2, r0, 1.0);
+          const double r = __builtin_fma(r0, e0, r0);
+          const double ua2 = hxk * r, va2 = hyk * r;
+          const double ru2 = __builtin_rint(ua2), rv2 = __builtin_rint(va2);
+          const double fu = ua2 - ru2, fv = va2 - rv2;
+          const double chk = __builtin_fma(cerrk, r, __builtin_fmax(__builtin_fabs(fu), __builtin_fabs(fv)));
+          const bool p2 = mine && chk < 0.5 && __builtin_fabs(e0) < tiny;
+          // a proven pixel is the reference's and lies in the window; column and row within it: the centred pixel minus the
+          // window's first one.  The other lanes' look-up is not used.
+          const int col = cvt_saturating(ru2) - x0c, row = cvt_saturating(rv2) - y0c;
+          const uint32_t word = (uint32_t)__builtin_amdgcn_ds_bpermute(row << 2, (int)window);
+          double val = free_space;  // 4b.8: every voxel of the pair with a depth accumulates -eta*rho (cu:115)
+          bool hit = p2 && ((word >> (col & 31)) & 1u);
+          const bool exact = mine && !p2;
+          if (ballot(exact)) {  // rare: its own reads of the argument block and of the record
+            const kernarg_t ke = KFRESH();
+            const __amdgpu_buffer_rsrc_t rsrc =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(cload(&(ke->tile_maps + m)->depth)), (short)0, ke->depth_bytes, 0x00020000);
+            double ev = 0.0;
+            const bool eh = exact ? tile_exact<DepthT>(KC(full), m, rsrc, i, j, k0 + kk, ev) : false;
+            if (exact) {
+              hit = eh;
+              val = ev;
+            }
+          }
+#pragma unroll
+          for (int q = 0; q < TK; ++q) {
+            if (kk == q) acc_add_v<BASE, TK>(q, ballot(hit), val);  // wave-uniform
+          }
+        };
+        if (und_kk) {  // wave-uniform
+          // Everything of the redo that does not depend on the voxel, once per pair: the record's fields in ONE batch of scalar loads
+          // (three lines of the record: cpx .. cq0 are sixteen dwords, cdhx, cdhy, cerrk and rz0, rz1, rz3 four doubles each) ahead
+          // of the first wait, the column's first voxel (h'' in fp64) and the part of c.z that the whole column shares.  Per
+          // voxel only its entry of the cz table is fetched.  Same operations on the same operands in the same order as before.
+          typedef double rec4 __attribute__((ext_vector_type(4), aligned(8)));
+          typedef double rec8 __attribute__((ext_vector_type(8), aligned(8)));
+          const kernarg_t k2 = KFRESH();
+          const TileMapRec *r2 = k2->tile_maps + m;
+          // (the record is 16-byte aligned, scalar loads ask for 4: the types say 8, the template of cload would say 64)
+          const rec8 cp = *reinterpret_cast<const rec8 __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(&r2->cpx));   // cpx cpy cpz cp0 cqx cqy cqz cq0
+          const rec4 cd = *reinterpret_cast<const rec4 __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(&r2->cdhx));  // cdhx cdhy cerrk (and the four tier-1 steps)
+          const rec4 rz = *reinterpret_cast<const rec4 __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(&r2->rz0));   // rz0 rz1 rz3 (and px)
+          constexpr size_t oc = offsetof(TileMapRec, cpx), od = offsetof(TileMapRec, cdhx);
+          static_assert(offsetof(TileMapRec, cpy) == oc + 8 && offsetof(TileMapRec, cpz) == oc + 16 && offsetof(TileMapRec, cp0) == oc + 24 &&
+                            offsetof(TileMapRec, cqx) == oc + 32 && offsetof(TileMapRec, cqy) == oc + 40 && offsetof(TileMapRec, cqz) == oc + 48 &&
+                            offsetof(TileMapRec, cq0) == oc + 56 && offsetof(TileMapRec, cdhy) == od + 8 && offsetof(TileMapRec, cerrk) == od + 16 &&
+                            od + 32 <= sizeof(TileMapRec) && offsetof(TileMapRec, rz0) == 0 && offsetof(TileMapRec, rz1) == 8 &&
+                            offsetof(TileMapRec, rz3) == 16,
+                        "the redo reads these fields of TileMapRec as three vectors: every one where the vector's element is");
+          [[maybe_unused]] double gx = 0, gy = 0, gz = 0, r22 = 0, sz2 = 0;
+          [[maybe_unused]] const double *cz_row = nullptr;
+          double wxf = wx, wyf = wy, wzf = wz0;
+          if constexpr (ROT) {
+            gx = k2->g[3], gy = k2->g[7], gz = k2->g[11];
+            r22 = cload(&k2->maps[m].rt[10]);
+            cz_row = k2->cz_table + (int64_t)k0 * 4;
+            const czvec4 b = cload(reinterpret_cast<const czvec4 *>(cz_row));
+            wxf = (wx + b[0]) + gx, wyf = (wy + b[1]) + gy, wzf = (wz0 + b[2]) + gz;
+          } else {
+            cz_row = k2->cz_table + (int64_t)m * k2->kpad + k0;
+            sz2 = rz[0] * wx + rz[1] * wy;
+          }
+          const double hxf = __builtin_fma(cp[0], wxf, __builtin_fma(cp[1], wyf, __builtin_fma(cp[2], wzf, cp[3])));
+          const double hyf = __builtin_fma(cp[4], wxf, __builtin_fma(cp[5], wyf, __builtin_fma(cp[6], wzf, cp[7])));
+#pragma unroll 1
+          do {
+#ifdef DMI_TUNING
+            ++dbg_redo;
+            ++dbg_win_redo;
+#endif
+            const int kk = __builtin_ctz(und_kk);
+            und_kk &= und_kk - 1;
+            const double kd = (double)kk;
+            const double hxk = __builtin_fma(kd, cd[0], hxf), hyk = __builtin_fma(kd, cd[1], hyf);
+            double cz2;  // the exact c.z of this voxel (cu:92, cu:172)
+            if constexpr (ROT) {
+              const czvec4 b = cload(reinterpret_cast<const czvec4 *>(cz_row + (int64_t)kk * 4));
+              const double wxk = (wx + b[0]) + gx, wyk = (wy + b[1]) + gy, wzk = (wz0 + b[2]) + gz;
+              cz2 = ((rz[0] * wxk + rz[1] * wyk) + r22 * wzk) + rz[2];
+            } else {
+              cz2 = (sz2 + cload(cz_row + kk)) + rz[2];
+            }
+            redo_voxel(kk, hxk, hyk, cz2, cd[2]);
+          } while (und_kk);
+        }
+#endif
         continue;
       }
     }
