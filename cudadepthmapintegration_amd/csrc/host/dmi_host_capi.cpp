@@ -387,6 +387,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->mesh_fill_holes = o.meshFillHoles;
   for (size_t a = 0; a < o.contourSmoothSigma.size() && a < 3; ++a) out->contour_smooth_sigma[a] = o.contourSmoothSigma[a];
   out->contour_smooth_truncate = o.contourSmoothTruncate;
+  out->depth_speckle_min_pixels = o.depthSpeckleMinPixels;
+  out->depth_speckle_tolerance = o.depthSpeckleTolerance;
+  out->depth_speckle_rel_tolerance = o.depthSpeckleRelTolerance;
   return 1;
   });
 }

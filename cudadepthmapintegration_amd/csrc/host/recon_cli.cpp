@@ -238,6 +238,26 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                         "other view's camera (finite, >= 0, default 0.01; not in the reference)",
                                           into_checked_double(&o->depthConsistencyRelTolerance, &o->depthConsistencyRelToleranceGiven,
                                                               [](double x) { return x >= 0.0; })}},
+      {"--depthSpeckleMinPixels", {Kind::kValue, "remove the small segments of the depth maps on the GPU before they are fused, and "
+                                                 "before --depthConsistencyMinViews and --gridAutoBounds see them: neighbouring pixels "
+                                                 "(left, right, above, below) whose depths agree form a segment, and the depths of a "
+                                                 "segment of fewer than this many pixels are dropped like ones that fail "
+                                                 "--threshBestCost (a non-negative integer; 0 drops nothing).  All views are then read "
+                                                 "into host memory at once, as with --depthConsistencyMinViews, and filtered on the "
+                                                 "first --device (not in the reference)",
+                                   into_count(&o->depthSpeckleMinPixels)}},
+      {"--depthSpeckleTolerance", {Kind::kValue, "with --depthSpeckleMinPixels: two neighbouring depths agree within this distance "
+                                                 "(world units, finite, >= 0, default 0) plus the relative tolerance (not in the reference)",
+                                   into_checked_double(&o->depthSpeckleTolerance, &o->depthSpeckleToleranceGiven,
+                                                       [](double x) { return x >= 0.0; })}},
+      {"--depthSpeckleRelTolerance", {Kind::kValue, "with --depthSpeckleMinPixels: ... plus this share of the smaller of the two depths "
+                                                    "(finite, >= 0, default 0.01).  The value must fit the image resolution: on a "
+                                                    "slanted surface the depth steps from pixel to pixel by an amount that grows as "
+                                                    "the image gets coarser, and a tolerance below that step cuts the surface into "
+                                                    "rows that are then dropped as small segments (0.01 suits 640 x 480 and above; "
+                                                    "images of 80 x 60 need about 0.05; not in the reference)",
+                                      into_checked_double(&o->depthSpeckleRelTolerance, &o->depthSpeckleRelToleranceGiven,
+                                                          [](double x) { return x >= 0.0; })}},
       {"--gridAutoBounds", {Kind::kFlag, "take the grid's box from the depth maps instead of --gridOrigin and --gridEnd, which then must "
                                          "not be given (one of --gridDims / --gridSpacing still is): every valid pixel is "
                                          "back-projected on the GPU, and along each of the grid's axes the box runs from the "
@@ -453,6 +473,12 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     err << "Bad value for --depthConsistencyMinViews\n" << HelpText();
     return false;
   }
+  for (const auto &flag : {std::make_pair("--depthSpeckleTolerance", o->depthSpeckleToleranceGiven),
+                           std::make_pair("--depthSpeckleRelTolerance", o->depthSpeckleRelToleranceGiven)})
+    if (flag.second && o->depthSpeckleMinPixels < 0) {
+      err << "Error : " << flag.first << " needs --depthSpeckleMinPixels.\n" << HelpText();
+      return false;
+    }
   for (const auto &flag : {std::make_pair("--gridAutoBoundsTrim", o->gridAutoBoundsTrimGiven),
                            std::make_pair("--gridAutoBoundsMargin", o->gridAutoBoundsMarginGiven),
                            std::make_pair("--gridAutoBoundsPixelStep", o->gridAutoBoundsPixelStepGiven)})
@@ -769,6 +795,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   std::vector<std::unique_ptr<ReconstructionData>> memoryViews;
   std::vector<ReconstructionData *> views;
   auto read_views = [&](const std::string &flag) {
+    if (!views.empty()) return true;  // (an earlier filter of this run has read them)
     const std::vector<std::string> vtis = help::ExtractAllFilePath(vti_list.c_str()), krtds = help::ExtractAllFilePath(krtd_list.c_str());
     if (vtis.empty() || krtds.size() < vtis.size()) {  // filt.cxx:161-165
       result->error = "Error : There is no enough vti files, please check your vtiList.txt and krtdList.txt";
@@ -782,6 +809,32 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
       }
       views.push_back(memoryViews.back().get());
     }
+    return true;
+  };
+  // the small segments of all views removed on the first device: before the consistency filter, so that an island cannot vouch for
+  // another view's island
+  auto speckle_views = [&]() {
+    say("** Remove the small segments of the depth maps...");
+    if (!read_views("--depthSpeckleMinPixels")) return false;
+    DepthSpeckleReport report;
+    std::string error;
+    if (!FilterDepthSpeckles(views, o.threshBestCost, o.depthSpeckleMinPixels, o.depthSpeckleTolerance, o.depthSpeckleRelTolerance,
+                             o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+      result->error = "--depthSpeckleMinPixels: " + error;
+      return false;
+    }
+    result->depthSpeckleViews = report.views;
+    result->depthSpeckleValidPixels = report.validPixels;
+    result->depthSpeckleKeptPixels = report.keptPixels;
+    result->depthSpeckleSegments = report.segments;
+    result->depthSpeckleKeptSegments = report.keptSegments;
+    result->depthSpeckleKernelMs = report.kernelMs;
+    std::ostringstream line;
+    line << "depth speckles: segments of at least " << o.depthSpeckleMinPixels << " pixels, tolerance " << o.depthSpeckleTolerance << " + "
+         << o.depthSpeckleRelTolerance << " z; " << report.views << " views, " << report.validPixels << " pixels with a depth, "
+         << report.keptPixels << " kept; " << report.segments << " segments, " << report.keptSegments << " kept; " << report.kernelMs
+         << " ms of GPU kernels";
+    say(line.str());
     return true;
   };
   // all views filtered on the first device
@@ -808,6 +861,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   };
   if (o.gridAutoBounds) {
     // the box before anything is described or set up: filtered depths if a filter was asked for, measured along the grid's axes
+    if (o.depthSpeckleMinPixels >= 0 && !speckle_views()) return 1;
     if (o.depthConsistencyMinViews >= 0 ? !filter_views() : !read_views("--gridAutoBounds")) return 1;
     say("** Estimate the grid's bounds from the depth maps...");
     // axes[j][i] = M[i][j] / |row_i|^2, M's rows the grid's axes: the inverse of the grid matrix for orthogonal rows, so that the
@@ -905,6 +959,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   const bool supportMesh = o.meshMinSupportViews >= 0 || o.meshSupportArray;
   const bool supportFacing = supportMesh && !o.meshSupportNoFacing;
   if (supportMesh) filter.SetKeepContext(true);
+  if (o.depthSpeckleMinPixels >= 0 && !o.gridAutoBounds && !speckle_views()) return 1;
   if (o.depthConsistencyMinViews >= 0 && !o.gridAutoBounds && !filter_views()) return 1;
   if (!views.empty()) filter.SetViews(views);
   if (!filter.Update()) {
@@ -1161,6 +1216,12 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << result->gridAutoBoundsKernelMs << " ms\n";
       out.precision(digits);
     }
+    if (o.depthSpeckleMinPixels >= 0)
+      out << "depth speckles\n  minimum segment pixels  " << o.depthSpeckleMinPixels << "\n  tolerance  " << o.depthSpeckleTolerance << " + "
+          << o.depthSpeckleRelTolerance << " z\n  views  " << result->depthSpeckleViews << "\n  pixels with a depth  "
+          << result->depthSpeckleValidPixels << "\n  pixels kept  " << result->depthSpeckleKeptPixels << "\n  segments  "
+          << result->depthSpeckleSegments << "\n  segments kept  " << result->depthSpeckleKeptSegments << "\n  GPU kernels  "
+          << result->depthSpeckleKernelMs << " ms\n";
     if (o.depthConsistencyMinViews >= 0)
       out << "depth consistency\n  minimum agreeing views  " << o.depthConsistencyMinViews << "\n  tolerance  " << o.depthConsistencyTolerance
           << " + " << o.depthConsistencyRelTolerance << " z\n  views  " << result->depthConsistencyViews << "\n  pixels with a depth  "

@@ -26,6 +26,9 @@
 // --depthConsistencyMinViews N with --depthConsistencyTolerance / --depthConsistencyRelTolerance (not in the reference: the geometric
 // consistency check of every depth-map fusion pipeline) reads all views into memory, filters their depths on the first device
 // (dmi_filter_depth_consistency) and fuses the filtered views through ReconstructionFilter::SetViews.
+// --depthSpeckleMinPixels N with --depthSpeckleTolerance / --depthSpeckleRelTolerance (not in the reference: the speckle filter of
+// every stereo pipeline) takes the same in-memory path and runs FIRST (dmi_filter_depth_speckles), so that an island of wrong
+// depths cannot vouch for another view's island; the consistency filter, the bounds estimate and the fusion see what it left.
 // --gridAutoBounds (not in the reference, which needs --gridOrigin and --gridEnd from outside the data) takes the grid's box from the
 // depth maps themselves: all views are read into memory -- and filtered first with --depthConsistencyMinViews --, the first device
 // gives trimmed order statistics of the back-projected pixels along the grid's axes (dmi_estimate_scene_bounds;
@@ -113,6 +116,11 @@ struct Options {
   std::vector<double> contourSmoothSigma;
   double contourSmoothTruncate = 3.0;
   bool contourSmoothTruncateGiven = false;
+  // not in the reference: remove the depth maps' small segments on the GPU before anything else sees them
+  // (dmi_filter_depth_speckles: -1 = flag not given), with an absolute and a relative depth tolerance between 4-neighbours
+  long long depthSpeckleMinPixels = -1;
+  double depthSpeckleTolerance = 0.0, depthSpeckleRelTolerance = 0.01;
+  bool depthSpeckleToleranceGiven = false, depthSpeckleRelToleranceGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -161,6 +169,11 @@ struct RunResult {
   // --contourSmoothSigma: the radii per axis and the hipEvent time of the smoothing's kernels
   int contourSmoothRadius[3] = {0, 0, 0};
   double contourSmoothKernelMs = 0.0;
+  // --depthSpeckleMinPixels: the views filtered, their pixels with a depth after --threshBestCost, the pixels the filter kept, the
+  // segments it found and the ones it kept, and the hipEvent time of its kernels
+  unsigned long long depthSpeckleViews = 0, depthSpeckleValidPixels = 0, depthSpeckleKeptPixels = 0, depthSpeckleSegments = 0,
+                     depthSpeckleKeptSegments = 0;
+  double depthSpeckleKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);

@@ -712,6 +712,59 @@ bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, doub
 }
 
 // Not in the reference (recon_host.h)
+bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long minPixels,
+                         double absTolerance, double relTolerance, int device, DepthSpeckleReport *report, std::string *error) {
+  const size_t n = views.size();
+  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
+  if (!first) {
+    *error = "FilterDepthSpeckles: no views, or view 0 has no depth map";
+    return false;
+  }
+  const int W = first->dims[0], H = first->dims[1];
+  const size_t npix = (size_t)W * H;
+  if (n > 0x7fffffffu) {
+    *error = "FilterDepthSpeckles: too many views";
+    return false;
+  }
+  std::vector<double> depth(n * npix);
+  DepthSpeckleReport r;
+  r.views = n;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
+      *error = "FilterDepthSpeckles: view " + std::to_string(m) + " has no depth map of the size of view 0";
+      return false;
+    }
+    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
+    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
+  }
+  for (const double d : depth) r.validPixels += d > 0.0 && d < HUGE_VAL ? 1 : 0;
+  std::vector<int32_t> size(n * npix);
+  const int rc = dmi_filter_depth_speckles(depth.data(), nullptr, 0.0, (int32_t)n, W, H, absTolerance, relTolerance, minPixels, device,
+                                           depth.data(), size.data(), &r.kernelMs);
+  if (rc != DMI_OK) {
+    *error = dmi_last_error(nullptr);
+    return false;
+  }
+  for (const double d : depth) r.keptPixels += d > 0.0 ? 1 : 0;
+  // a segment of s pixels shows s times in the sizes: the pixels of size s, over s, are the segments of that size
+  std::vector<uint64_t> pixelsOfSize(npix + 1, 0);
+  for (const int32_t s : size)
+    if (s > 0 && (size_t)s <= npix) ++pixelsOfSize[(size_t)s];
+  for (size_t s = 1; s <= npix; ++s) {
+    r.segments += pixelsOfSize[s] / s;
+    if ((long long)s >= minPixels) r.keptSegments += pixelsOfSize[s] / s;
+  }
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage filtered = *views[m]->GetDepthMap();
+    filtered.depths.assign(depth.begin() + (ptrdiff_t)(m * npix), depth.begin() + (ptrdiff_t)((m + 1) * npix));
+    views[m]->SetDepthMap(filtered);
+  }
+  if (report) *report = r;
+  return true;
+}
+
+// Not in the reference (recon_host.h)
 bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
                          double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error) {
   const size_t n = views.size();

@@ -109,6 +109,23 @@ struct DepthConsistencyReport {
 bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int minViews,
                             double absTolerance, double relTolerance, int device, DepthConsistencyReport *report, std::string *error);
 
+// Not in the reference: the views without their small depth segments, filtered on the GPU before they are fused
+// (dmi_filter_depth_speckles, include/dmi.h states the definition).  It works as FilterDepthConsistency does: every view is
+// thresholded first (ApplyDepthThresholdFilter), all of them are packed, filtered in place on `device`, and the filtered depths
+// stored back with SetDepthMap: a depth stays only where its connected segment -- 4-neighbours whose depths differ by at most
+// absTolerance + relTolerance * the smaller one -- has at least minPixels pixels; everything else becomes -1.  The cameras are not
+// read.  The views must share one size and have depth maps.
+struct DepthSpeckleReport {
+  uint64_t views = 0;
+  uint64_t validPixels = 0;     // after the threshold: depths > 0 and finite
+  uint64_t keptPixels = 0;      // of those, the ones the filter kept
+  uint64_t segments = 0;        // the segments of all views before the filter ...
+  uint64_t keptSegments = 0;    // ... and the ones of at least minPixels pixels
+  double kernelMs = 0.0;        // hipEvent time of the pass's kernels
+};
+bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long minPixels,
+                         double absTolerance, double relTolerance, int device, DepthSpeckleReport *report, std::string *error);
+
 // Not in the reference: the bounds of the scene the views see, along the rows of `axes` (row-major 3 x 3), on the GPU
 // (dmi_estimate_scene_bounds, include/dmi.h states the definition): per axis the coordinate of rank k and of rank N-1-k of the
 // back-projected valid pixels, k = min((uint64_t)(trimFraction * N), (N - 1) / 2), over every pixelStep-th pixel of every

@@ -31,44 +31,17 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "fusion_kernels.h"
+#include "union_find_device.h"
 
 namespace dmi {
 namespace {
 
 constexpr int kBlock = 256;
 
-__device__ __forceinline__ uint32_t load_parent(const uint32_t *parent, uint32_t v) {
-  return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of v's tree as far as this thread can see, halving the path on the way: each step moves to a strictly smaller id
-__device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t v) {
-  uint32_t p = load_parent(parent, v);
-  while (p != v) {
-    const uint32_t g = load_parent(parent, p);
-    if (g != p) __hip_atomic_store(parent + v, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // an ancestor: same set, smaller
-    v = p;
-    p = g;
-  }
-  return v;
-}
-
-// *retries += 1 for every compare-and-swap that lost its race
-__device__ __forceinline__ void unite(uint32_t *parent, uint32_t a, uint32_t b, uint32_t *retries) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return;
-    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-    uint32_t seen = hi;
-    if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      return;
-    // hi was linked by someone else meanwhile: seen < hi is its parent, a member of the same set; go on from there
-    ++*retries;
-    a = seen;
-    b = lo;
-  }
-}
+// the union-find itself is shared with depth_speckle.hip (union_find_device.h, where the visibility argument above is restated)
+using union_find::find_root;
+using union_find::load_parent;
+using union_find::unite;
 
 __global__ __launch_bounds__(kBlock) void components_init_kernel(uint32_t *__restrict__ parent, uint32_t *__restrict__ size, uint64_t n) {
   const uint64_t v = (uint64_t)blockIdx.x * kBlock + threadIdx.x;

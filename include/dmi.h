@@ -54,7 +54,7 @@ extern "C" {
                            *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency;
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
-                           *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms */
+                           *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles */
 
 typedef struct dmi_context dmi_context;
 
@@ -811,6 +811,42 @@ int dmi_filter_depth_consistency(const double *depth, const double *best_cost, d
 int dmi_estimate_scene_bounds(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
                               int32_t n, int32_t W, int32_t H, const double *axes9 /* nullable: identity */, double trim_fraction,
                               int32_t pixel_step, int32_t device, double lo[3], double hi[3], uint64_t *n_points, double *kernel_ms);
+
+/* ---- Small depth-map segments removed before the maps are fused (added after round 5, dmi_abi_version()
+ * stays 5) ----
+ * The speckle filter of every stereo pipeline: a small island of pixels whose depth is continuous among themselves but not with
+ * their surroundings is a matching error, and needs no second view to be recognised.  Fused, it leaves a floating speck and carves
+ * along its rays through the surface behind it.  dmi_filter_depth_speckles labels the connected segments of every view and keeps
+ * the depths of the segments that are large enough.  Context-free, like dmi_filter_depth_consistency: it uploads, runs its kernels,
+ * downloads and frees.  It takes no cameras.
+ *   depth, best_cost, threshold   exactly as dmi_filter_depth_consistency takes them: [n][H][W] f64 host in vtk point order,
+ *             best_cost nullable
+ *   out_depth [n][H][W] f64 host; may be `depth` itself
+ *   out_size  [n][H][W] int32 host or NULL;  kernel_ms (nullable): hipEvent time of the kernels alone, summed over the pieces
+ * Definition, met bit for bit by the device and by tests/depth_speckle_np.py.  All arithmetic is f64, every operation is rounded
+ * on its own, nothing is contracted; comparisons with a NaN are false.
+ *   1. D_m = depth_m with -1 wherever best_cost_m > threshold.  A pixel is VALID iff D > 0 and D < +inf.
+ *   2. Two valid pixels of the SAME view that are 4-neighbours are LINKED iff
+ *      fabs(Da - Db) <= abs_tolerance + rel_tolerance * fmin(Da, Db): the product rounded, then the sum, then the difference.
+ *      4-neighbours are the same row with adjacent columns, or the same column with adjacent rows; the row order does not matter
+ *      to this relation, so nothing is flipped.  The last pixel of a row and the first of the next are not neighbours; pixels of
+ *      different views are never neighbours.  The relation is symmetric because of fmin.
+ *   3. A SEGMENT is a connected component of the valid pixels of one view under LINKED.  Its SIZE is its number of pixels.
+ *   4. out_size = the pixel's segment size, 0 at a pixel that is not valid.
+ *   5. out_depth = D where the pixel is valid and its size >= min_pixels, exactly -1.0 elsewhere.  min_pixels == 0 returns D with
+ *      every invalid value normalised to -1, and the sizes.
+ * The result depends only on the partition into segments, so it is the same to the bit whatever order the hardware runs in: two
+ * calls give identical bytes.
+ * Host data goes up and comes down in pieces of whole views, as many as fit 256 MiB (a single larger view goes whole, as in
+ * dmi_estimate_scene_bounds).  The device holds the planes of one piece at a time -- 16 bytes per pixel of the piece, 8 more with
+ * best_cost, 4 more with out_size --, so device memory does not grow with n.
+ * All arguments are checked before the device is touched.  DMI_ERR_INVALID_ARGUMENT, the message naming the argument: a null depth
+ * or out_depth; n < 1; W or H outside [1, 32768]; min_pixels < 0; a negative, NaN or infinite abs_tolerance or rel_tolerance; a NaN
+ * threshold when best_cost is given.  Then DMI_ERR_DEVICE without a device.  A refused call leaves out_depth and out_size
+ * untouched.  The call never exits and never throws; a failure's text is dmi_last_error(NULL)'s.  Synchronises. */
+int dmi_filter_depth_speckles(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H,
+                              double abs_tolerance, double rel_tolerance, int64_t min_pixels, int32_t device, double *out_depth,
+                              int32_t *out_size, double *kernel_ms);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

@@ -127,6 +127,10 @@ typedef struct dmi_cli_options {
   /* not in the reference, only with --extractMesh (dmi_set_point_smoothing, dmi.h); appended to the struct: */
   double contour_smooth_sigma[3];        /* --contourSmoothSigma S [S S]: Gaussian over the point data before the contour, voxels; 0: off */
   double contour_smooth_truncate;        /* --contourSmoothTruncate (default 3) */
+  /* not in the reference (dmi_filter_depth_speckles, dmi.h); appended to the struct: */
+  int64_t depth_speckle_min_pixels;      /* --depthSpeckleMinPixels N: drop depth-map segments of fewer pixels before the fusion; -1: not given */
+  double depth_speckle_tolerance;        /* --depthSpeckleTolerance (default 0) */
+  double depth_speckle_rel_tolerance;    /* --depthSpeckleRelTolerance (default 0.01) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -153,7 +157,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * dmi_fill_isosurface_holes behind the support trim and the component flags and in front of the smoothing (RegionId: from the
  * labelling run again on the filled mesh, unless a decimation behind it does that).  With --contourSmoothSigma S the context's
  * point smoothing is set (dmi_set_point_smoothing) directly before the extraction: the .mha, the .vts and the count of active cells
- * are what they are without the flag. */
+ * are what they are without the flag.  With --depthSpeckleMinPixels N every view is read into memory as with
+ * --depthConsistencyMinViews and the depths go through dmi_filter_depth_speckles first of all: the consistency filter, the bounds
+ * estimate and the fusion see what it left. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
