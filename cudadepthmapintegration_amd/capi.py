@@ -123,7 +123,7 @@ ABI_SYMBOLS = [
     "dmi_fill_isosurface_holes", "dmi_get_isosurface_holes_kernel_ms", "dmi_get_isosurface_holes_pass_ms",
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
-    "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds", "dmi_filter_depth_speckles",
+    "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds", "dmi_filter_depth_speckles", "dmi_fill_depth_holes",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -292,6 +292,8 @@ def load() -> ctypes.CDLL:
                                                 ctypes.POINTER(ctypes.c_uint64), dp]
     if hasattr(L, "dmi_filter_depth_speckles"):  # (DMI_LIB_OVERRIDE may name an older library)
         L.dmi_filter_depth_speckles.argtypes = [dp, dp, dbl, i32, i32, i32, dbl, dbl, i64, i32, dp, i32p, dp]
+    if hasattr(L, "dmi_fill_depth_holes"):
+        L.dmi_fill_depth_holes.argtypes = [dp, dp, dbl, i32, i32, i32, dbl, dbl, i64, i32, dp, i32p, dp]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1140,6 +1142,39 @@ def filter_depth_speckles(views: Views, *, min_pixels: int, abs_tolerance: float
     return Views(out, views.K4, views.RT4, None), sizes, float(ms.value)
 
 
+def fill_depth_holes(views: Views, *, max_pixels: int, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0,
+                     threshold: float | None = None, device: int = 0, out: np.ndarray | None = None):
+    """Depth maps with their small holes filled (include/dmi.h: dmi_fill_depth_holes): a hole is a 4-connected component of the
+    pixels without a depth; one of at most max_pixels pixels that does not touch the image's border and whose rim depths lo..hi
+    satisfy hi - lo <= abs_tolerance + rel_tolerance * lo gets, at every pixel, a depth interpolated between the nearest valid
+    pixels of its row and of its column.  threshold applies views.best_cost first (best cost > threshold => -1).  The cameras are
+    not read.  Returns (Views with the filled depths, the same cameras and best_cost None; sizes int32 [n, H, W]: every pixel's hole
+    size, 0 at a valid pixel; the kernels' hipEvent time in ms).  out: where the filled depths go; it may be views.depth itself
+    (f64, C-contiguous), which is then filled in place."""
+    L = load()
+    d = np.ascontiguousarray(views.depth, dtype=np.float64)
+    if d.ndim != 3:
+        raise ValueError(f"views.depth must be [n, H, W], got {d.shape}")
+    n, H, W = d.shape
+    bc = None
+    if threshold is not None and views.best_cost is not None:
+        bc = np.ascontiguousarray(views.best_cost, dtype=np.float64)
+        if bc.shape != d.shape:
+            raise ValueError("views.best_cost must have the shape of views.depth")
+    if out is None:
+        out = np.empty_like(d)
+    elif out.dtype != np.float64 or out.shape != d.shape or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous f64 array of the depths' shape")
+    sizes = np.zeros(d.shape, dtype=np.int32)
+    ms = ctypes.c_double(0.0)
+    rc = L.dmi_fill_depth_holes(_dp(d), None if bc is None else _dp(bc), 0.0 if threshold is None else float(threshold), n, W, H,
+                                float(abs_tolerance), float(rel_tolerance), int(max_pixels), int(device), _dp(out),
+                                sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(ms))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    return Views(out, views.K4, views.RT4, None), sizes, float(ms.value)
+
+
 def estimate_scene_bounds(views: Views, *, trim_fraction: float = 0.0, pixel_step: int = 1, axes=None, threshold: float | None = None,
                           device: int = 0):
     """The bounds of the scene the depth maps see (include/dmi.h: dmi_estimate_scene_bounds): per axis the element of rank k and
@@ -1535,7 +1570,9 @@ class CliOptionsC(ctypes.Structure):
                 ("mesh_fill_holes", ctypes.c_int64),
                 ("contour_smooth_sigma", ctypes.c_double * 3), ("contour_smooth_truncate", ctypes.c_double),
                 ("depth_speckle_min_pixels", ctypes.c_int64), ("depth_speckle_tolerance", ctypes.c_double),
-                ("depth_speckle_rel_tolerance", ctypes.c_double)]
+                ("depth_speckle_rel_tolerance", ctypes.c_double),
+                ("depth_fill_holes_max_pixels", ctypes.c_int64), ("depth_fill_holes_tolerance", ctypes.c_double),
+                ("depth_fill_holes_rel_tolerance", ctypes.c_double)]
 
 
 def cli_read_arguments(args):

@@ -390,6 +390,9 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->depth_speckle_min_pixels = o.depthSpeckleMinPixels;
   out->depth_speckle_tolerance = o.depthSpeckleTolerance;
   out->depth_speckle_rel_tolerance = o.depthSpeckleRelTolerance;
+  out->depth_fill_holes_max_pixels = o.depthFillHolesMaxPixels;
+  out->depth_fill_holes_tolerance = o.depthFillHolesTolerance;
+  out->depth_fill_holes_rel_tolerance = o.depthFillHolesRelTolerance;
   return 1;
   });
 }

@@ -258,6 +258,24 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                     "images of 80 x 60 need about 0.05; not in the reference)",
                                       into_checked_double(&o->depthSpeckleRelTolerance, &o->depthSpeckleRelToleranceGiven,
                                                           [](double x) { return x >= 0.0; })}},
+      {"--depthFillHolesMaxPixels", {Kind::kValue, "fill the small holes of the depth maps on the GPU before they are fused, behind "
+                                                   "--depthSpeckleMinPixels and before --depthConsistencyMinViews and --gridAutoBounds "
+                                                   "see them: neighbouring pixels (left, right, above, below) without a depth form a "
+                                                   "hole, and a hole of at most this many pixels that does not touch the image's border "
+                                                   "and whose surrounding depths agree gets depths interpolated from the nearest pixels "
+                                                   "of every pixel's row and column (a non-negative integer; 0 fills nothing).  All "
+                                                   "views are then read into host memory at once, as with --depthSpeckleMinPixels, and "
+                                                   "filled on the first --device (not in the reference)",
+                                     into_count(&o->depthFillHolesMaxPixels)}},
+      {"--depthFillHolesTolerance", {Kind::kValue, "with --depthFillHolesMaxPixels: the depths round a hole agree if the largest "
+                                                   "exceeds the smallest by at most this distance (world units, finite, >= 0, default "
+                                                   "0) plus the relative tolerance (not in the reference)",
+                                     into_checked_double(&o->depthFillHolesTolerance, &o->depthFillHolesToleranceGiven,
+                                                         [](double x) { return x >= 0.0; })}},
+      {"--depthFillHolesRelTolerance", {Kind::kValue, "with --depthFillHolesMaxPixels: ... plus this share of the smallest depth "
+                                                      "round the hole (finite, >= 0, default 0.01; not in the reference)",
+                                        into_checked_double(&o->depthFillHolesRelTolerance, &o->depthFillHolesRelToleranceGiven,
+                                                            [](double x) { return x >= 0.0; })}},
       {"--gridAutoBounds", {Kind::kFlag, "take the grid's box from the depth maps instead of --gridOrigin and --gridEnd, which then must "
                                          "not be given (one of --gridDims / --gridSpacing still is): every valid pixel is "
                                          "back-projected on the GPU, and along each of the grid's axes the box runs from the "
@@ -477,6 +495,12 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
                            std::make_pair("--depthSpeckleRelTolerance", o->depthSpeckleRelToleranceGiven)})
     if (flag.second && o->depthSpeckleMinPixels < 0) {
       err << "Error : " << flag.first << " needs --depthSpeckleMinPixels.\n" << HelpText();
+      return false;
+    }
+  for (const auto &flag : {std::make_pair("--depthFillHolesTolerance", o->depthFillHolesToleranceGiven),
+                           std::make_pair("--depthFillHolesRelTolerance", o->depthFillHolesRelToleranceGiven)})
+    if (flag.second && o->depthFillHolesMaxPixels < 0) {
+      err << "Error : " << flag.first << " needs --depthFillHolesMaxPixels.\n" << HelpText();
       return false;
     }
   for (const auto &flag : {std::make_pair("--gridAutoBoundsTrim", o->gridAutoBoundsTrimGiven),
@@ -837,6 +861,30 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     say(line.str());
     return true;
   };
+  // the small holes of all views filled on the first device: behind the speckle filter, so that a removed island is refilled from
+  // its surroundings, and in front of the consistency filter, so that every invented depth still has to be confirmed
+  auto fill_views = [&]() {
+    say("** Fill the small holes of the depth maps...");
+    if (!read_views("--depthFillHolesMaxPixels")) return false;
+    DepthHolesReport report;
+    std::string error;
+    if (!FillDepthHoles(views, o.threshBestCost, o.depthFillHolesMaxPixels, o.depthFillHolesTolerance, o.depthFillHolesRelTolerance,
+                        o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+      result->error = "--depthFillHolesMaxPixels: " + error;
+      return false;
+    }
+    result->depthFillHolesViews = report.views;
+    result->depthFillHolesHoles = report.holes;
+    result->depthFillHolesFilledHoles = report.filledHoles;
+    result->depthFillHolesFilledPixels = report.filledPixels;
+    result->depthFillHolesKernelMs = report.kernelMs;
+    std::ostringstream line;
+    line << "depth holes: holes of at most " << o.depthFillHolesMaxPixels << " pixels, tolerance " << o.depthFillHolesTolerance << " + "
+         << o.depthFillHolesRelTolerance << " z; " << report.views << " views, " << report.holes << " holes, " << report.filledHoles
+         << " filled; " << report.filledPixels << " pixels filled; " << report.kernelMs << " ms of GPU kernels";
+    say(line.str());
+    return true;
+  };
   // all views filtered on the first device
   auto filter_views = [&]() {
     say("** Filter the depth maps by cross-view consistency...");
@@ -862,6 +910,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   if (o.gridAutoBounds) {
     // the box before anything is described or set up: filtered depths if a filter was asked for, measured along the grid's axes
     if (o.depthSpeckleMinPixels >= 0 && !speckle_views()) return 1;
+    if (o.depthFillHolesMaxPixels >= 0 && !fill_views()) return 1;
     if (o.depthConsistencyMinViews >= 0 ? !filter_views() : !read_views("--gridAutoBounds")) return 1;
     say("** Estimate the grid's bounds from the depth maps...");
     // axes[j][i] = M[i][j] / |row_i|^2, M's rows the grid's axes: the inverse of the grid matrix for orthogonal rows, so that the
@@ -960,6 +1009,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   const bool supportFacing = supportMesh && !o.meshSupportNoFacing;
   if (supportMesh) filter.SetKeepContext(true);
   if (o.depthSpeckleMinPixels >= 0 && !o.gridAutoBounds && !speckle_views()) return 1;
+  if (o.depthFillHolesMaxPixels >= 0 && !o.gridAutoBounds && !fill_views()) return 1;
   if (o.depthConsistencyMinViews >= 0 && !o.gridAutoBounds && !filter_views()) return 1;
   if (!views.empty()) filter.SetViews(views);
   if (!filter.Update()) {
@@ -1222,6 +1272,11 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << result->depthSpeckleValidPixels << "\n  pixels kept  " << result->depthSpeckleKeptPixels << "\n  segments  "
           << result->depthSpeckleSegments << "\n  segments kept  " << result->depthSpeckleKeptSegments << "\n  GPU kernels  "
           << result->depthSpeckleKernelMs << " ms\n";
+    if (o.depthFillHolesMaxPixels >= 0)
+      out << "depth holes\n  maximum hole pixels  " << o.depthFillHolesMaxPixels << "\n  tolerance  " << o.depthFillHolesTolerance << " + "
+          << o.depthFillHolesRelTolerance << " z\n  views  " << result->depthFillHolesViews << "\n  holes  " << result->depthFillHolesHoles
+          << "\n  holes filled  " << result->depthFillHolesFilledHoles << "\n  pixels filled  " << result->depthFillHolesFilledPixels
+          << "\n  GPU kernels  " << result->depthFillHolesKernelMs << " ms\n";
     if (o.depthConsistencyMinViews >= 0)
       out << "depth consistency\n  minimum agreeing views  " << o.depthConsistencyMinViews << "\n  tolerance  " << o.depthConsistencyTolerance
           << " + " << o.depthConsistencyRelTolerance << " z\n  views  " << result->depthConsistencyViews << "\n  pixels with a depth  "

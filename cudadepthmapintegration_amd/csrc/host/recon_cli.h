@@ -29,6 +29,10 @@
 // --depthSpeckleMinPixels N with --depthSpeckleTolerance / --depthSpeckleRelTolerance (not in the reference: the speckle filter of
 // every stereo pipeline) takes the same in-memory path and runs FIRST (dmi_filter_depth_speckles), so that an island of wrong
 // depths cannot vouch for another view's island; the consistency filter, the bounds estimate and the fusion see what it left.
+// --depthFillHolesMaxPixels N with --depthFillHolesTolerance / --depthFillHolesRelTolerance (not in the reference: the gap
+// interpolation of stereo pipelines) takes the same in-memory path and runs behind the speckle filter and in front of the
+// consistency filter (dmi_fill_depth_holes): an island the first removed is refilled from its surroundings, and every invented
+// depth still has to be confirmed by other views where the second is on.
 // --gridAutoBounds (not in the reference, which needs --gridOrigin and --gridEnd from outside the data) takes the grid's box from the
 // depth maps themselves: all views are read into memory -- and filtered first with --depthConsistencyMinViews --, the first device
 // gives trimmed order statistics of the back-projected pixels along the grid's axes (dmi_estimate_scene_bounds;
@@ -121,6 +125,11 @@ struct Options {
   long long depthSpeckleMinPixels = -1;
   double depthSpeckleTolerance = 0.0, depthSpeckleRelTolerance = 0.01;
   bool depthSpeckleToleranceGiven = false, depthSpeckleRelToleranceGiven = false;
+  // not in the reference: fill the depth maps' small holes on the GPU behind the speckle filter (dmi_fill_depth_holes: -1 = flag
+  // not given), with an absolute and a relative tolerance on the depths round a hole
+  long long depthFillHolesMaxPixels = -1;
+  double depthFillHolesTolerance = 0.0, depthFillHolesRelTolerance = 0.01;
+  bool depthFillHolesToleranceGiven = false, depthFillHolesRelToleranceGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -174,6 +183,10 @@ struct RunResult {
   unsigned long long depthSpeckleViews = 0, depthSpeckleValidPixels = 0, depthSpeckleKeptPixels = 0, depthSpeckleSegments = 0,
                      depthSpeckleKeptSegments = 0;
   double depthSpeckleKernelMs = 0.0;
+  // --depthFillHolesMaxPixels: the views filled, the holes found in them, the holes and the pixels filled, and the hipEvent time
+  // of the kernels
+  unsigned long long depthFillHolesViews = 0, depthFillHolesHoles = 0, depthFillHolesFilledHoles = 0, depthFillHolesFilledPixels = 0;
+  double depthFillHolesKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);

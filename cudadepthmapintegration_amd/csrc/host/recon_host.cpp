@@ -765,6 +765,70 @@ bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double 
 }
 
 // Not in the reference (recon_host.h)
+bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long maxPixels, double absTolerance,
+                    double relTolerance, int device, DepthHolesReport *report, std::string *error) {
+  const size_t n = views.size();
+  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
+  if (!first) {
+    *error = "FillDepthHoles: no views, or view 0 has no depth map";
+    return false;
+  }
+  const int W = first->dims[0], H = first->dims[1];
+  const size_t npix = (size_t)W * H;
+  if (n > 0x7fffffffu) {
+    *error = "FillDepthHoles: too many views";
+    return false;
+  }
+  std::vector<double> depth(n * npix);
+  DepthHolesReport r;
+  r.views = n;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
+      *error = "FillDepthHoles: view " + std::to_string(m) + " has no depth map of the size of view 0";
+      return false;
+    }
+    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
+    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
+  }
+  std::vector<int32_t> size(n * npix);
+  const int rc = dmi_fill_depth_holes(depth.data(), nullptr, 0.0, (int32_t)n, W, H, absTolerance, relTolerance, maxPixels, device,
+                                      depth.data(), size.data(), &r.kernelMs);
+  if (rc != DMI_OK) {
+    *error = dmi_last_error(nullptr);
+    return false;
+  }
+  // a hole of s pixels shows s times in the sizes, and a filled hole is filled at every pixel: the pixels of size s, over s, are
+  // the holes of that size
+  std::vector<uint64_t> pixelsOfSize(npix + 1, 0), filledOfSize(npix + 1, 0);
+  for (size_t i = 0; i < size.size(); ++i) {
+    const int32_t s = size[i];
+    if (s <= 0 || (size_t)s > npix) continue;
+    ++pixelsOfSize[(size_t)s];
+    if (depth[i] != -1.0) {
+      ++filledOfSize[(size_t)s];
+      ++r.filledPixels;
+    }
+  }
+  for (size_t s = 1; s <= npix; ++s) {
+    r.holes += pixelsOfSize[s] / s;
+    r.filledHoles += filledOfSize[s] / s;
+  }
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage filled = *views[m]->GetDepthMap();
+    filled.depths.assign(depth.begin() + (ptrdiff_t)(m * npix), depth.begin() + (ptrdiff_t)((m + 1) * npix));
+    // a pixel the threshold had dropped and the fill gave a depth again must pass the threshold from now on: the consistency
+    // filter, the bounds estimate and the fusion all apply it once more
+    if (filled.best_cost.size() == npix)
+      for (size_t i = 0; i < npix; ++i)
+        if (filled.depths[i] != -1.0 && filled.best_cost[i] > thresholdBestCost) filled.best_cost[i] = thresholdBestCost;
+    views[m]->SetDepthMap(filled);
+  }
+  if (report) *report = r;
+  return true;
+}
+
+// Not in the reference (recon_host.h)
 bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
                          double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error) {
   const size_t n = views.size();

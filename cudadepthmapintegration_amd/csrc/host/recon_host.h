@@ -126,6 +126,23 @@ struct DepthSpeckleReport {
 bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long minPixels,
                          double absTolerance, double relTolerance, int device, DepthSpeckleReport *report, std::string *error);
 
+// Not in the reference: the views with their small depth holes filled on the GPU before they are fused (dmi_fill_depth_holes,
+// include/dmi.h states the definition).  It works as FilterDepthSpeckles does: every view is thresholded first, all of them are
+// packed, filled in place on `device`, and the filled depths stored back with SetDepthMap: a connected component of pixels
+// without a depth that has at most maxPixels pixels, does not touch the image's border and whose rim depths lo..hi satisfy
+// hi - lo <= absTolerance + relTolerance * lo is interpolated from the nearest valid pixels of every pixel's row and column.
+// The cameras are not read.  The views must share one size and have depth maps.  Where the threshold had made the hole, the
+// stored best cost of a filled pixel becomes the threshold itself, so that the later steps, which threshold again, keep the depth.
+struct DepthHolesReport {
+  uint64_t views = 0;
+  uint64_t holes = 0;          // the holes of all views ...
+  uint64_t filledHoles = 0;    // ... and the ones that were filled
+  uint64_t filledPixels = 0;   // their pixels
+  double kernelMs = 0.0;       // hipEvent time of the pass's kernels
+};
+bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long maxPixels, double absTolerance,
+                    double relTolerance, int device, DepthHolesReport *report, std::string *error);
+
 // Not in the reference: the bounds of the scene the views see, along the rows of `axes` (row-major 3 x 3), on the GPU
 // (dmi_estimate_scene_bounds, include/dmi.h states the definition): per axis the coordinate of rank k and of rank N-1-k of the
 // back-projected valid pixels, k = min((uint64_t)(trimFraction * N), (N - 1) / 2), over every pixelStep-th pixel of every

@@ -54,7 +54,8 @@ extern "C" {
                            *    dmi_decimate_isosurface_placed; dmi_filter_depth_consistency;
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
-                           *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles */
+                           *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles;
+                           *    dmi_fill_depth_holes */
 
 typedef struct dmi_context dmi_context;
 
@@ -847,6 +848,53 @@ int dmi_estimate_scene_bounds(const double *depth, const double *best_cost, doub
 int dmi_filter_depth_speckles(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H,
                               double abs_tolerance, double rel_tolerance, int64_t min_pixels, int32_t device, double *out_depth,
                               int32_t *out_size, double *kernel_ms);
+
+/* ---- Small depth-map holes filled before the maps are fused (added after round 5, dmi_abi_version() stays 5) ----
+ * The gap interpolation of stereo pipelines: the best-cost threshold scatters single-pixel holes, the speckle filter cuts out
+ * islands, and a pixel without a depth casts no ray -- it adds no surface and carves no free space.  A small hole inside a smooth
+ * wall is not missing information.  dmi_fill_depth_holes labels the connected components of the pixels WITHOUT a depth in every
+ * view and interpolates the small ones whose rim is continuous.  Context-free, like dmi_filter_depth_speckles: it uploads, runs
+ * its kernels, downloads and frees.  It takes no cameras.
+ *   depth, best_cost, threshold   exactly as dmi_filter_depth_speckles takes them: [n][H][W] f64 host in vtk point order,
+ *             best_cost nullable
+ *   out_depth [n][H][W] f64 host; may be `depth` itself
+ *   out_size  [n][H][W] int32 host or NULL;  kernel_ms (nullable): hipEvent time of the kernels alone, summed over the pieces
+ * Definition, met bit for bit by the device and by tests/depth_holes_np.py.  All arithmetic is f64, every operation is rounded
+ * on its own, nothing is contracted; comparisons with a NaN are false.
+ *   1. D_m = depth_m with -1 wherever best_cost_m > threshold.  A pixel is VALID iff D > 0 and D < +inf (step 1 of
+ *      dmi_filter_depth_speckles).
+ *   2. A HOLE is a connected component of the NOT-valid pixels of one view under 4-neighbourhood: the same row with adjacent
+ *      columns, or the same column with adjacent rows.  The last pixel of a row and the first of the next are not neighbours;
+ *      pixels of different views are never neighbours; nothing is flipped.  Its SIZE is its number of pixels.  It TOUCHES THE
+ *      BORDER iff one of its pixels has x == 0, x == W-1, y == 0 or y == H-1.
+ *   3. The RIM of a hole is the set of valid pixels that are 4-neighbours of any of its pixels.  lo is the smallest D on the rim,
+ *      hi the largest: exact minima and maxima, so the order of evaluation does not matter.
+ *   4. A hole is FILLABLE iff SIZE <= max_pixels, it does not touch the border, and
+ *      hi - lo <= abs_tolerance + rel_tolerance * lo: the product rounded, then the sum, then the difference.  For a rim of two
+ *      depths this is the LINKED predicate of dmi_filter_depth_speckles.
+ *   5. For a pixel (x, y) of a fillable hole, xl < x < xr are the nearest valid columns in its row and yu < y < yd the nearest
+ *      valid rows in its column.  All four exist and lie on this hole's own rim, because the hole does not touch the border.
+ *      With the integer spans converted to f64 exactly:
+ *        h    = (D[y][xl]*(xr-x) + D[y][xr]*(x-xl)) / (xr-xl)
+ *        v    = (D[yu][x]*(yd-y) + D[yd][x]*(y-yu)) / (yd-yu)
+ *        fill = (h*(yd-yu) + v*(xr-xl)) / ((yd-yu) + (xr-xl))
+ *      so the shorter span gets the larger weight.  The divisions are correctly rounded; each sum is taken left to right as
+ *      written.  Only INPUT depths are read, never a filled one.
+ *   6. out_depth = D at a valid pixel, fill at a pixel of a fillable hole, exactly -1.0 elsewhere.  out_size = the pixel's hole
+ *      size, 0 at a valid pixel; the pixels of a hole that is not fillable get their size too.  max_pixels == 0 returns D with
+ *      every invalid value normalised to -1, and the sizes.
+ * The result depends only on the partition into holes, on exact minima and maxima and on input depths, so it is the same to the
+ * bit whatever order the hardware runs in: two calls give identical bytes.
+ * Host data goes up and comes down in pieces of whole views, as many as fit 256 MiB (a single larger view goes whole, as in
+ * dmi_filter_depth_speckles).  The device holds the planes of one piece at a time -- 32 bytes per pixel of the piece, 8 more with
+ * best_cost, 4 more with out_size --, so device memory does not grow with n.
+ * All arguments are checked before the device is touched.  DMI_ERR_INVALID_ARGUMENT, the message naming the argument: a null depth
+ * or out_depth; n < 1; W or H outside [1, 32768]; max_pixels < 0; a negative, NaN or infinite abs_tolerance or rel_tolerance; a NaN
+ * threshold when best_cost is given.  Then DMI_ERR_DEVICE without a device.  A refused call leaves out_depth and out_size
+ * untouched.  The call never exits and never throws; a failure's text is dmi_last_error(NULL)'s.  Synchronises. */
+int dmi_fill_depth_holes(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H,
+                         double abs_tolerance, double rel_tolerance, int64_t max_pixels, int32_t device, double *out_depth,
+                         int32_t *out_size, double *kernel_ms);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default
