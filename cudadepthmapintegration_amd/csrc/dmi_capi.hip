@@ -481,13 +481,14 @@ int dmi_download_hits(dmi_context *ctx, uint32_t *voxel_hits, uint64_t *map_hits
     DMI_HIP(ctx, hipMemcpyAsync(voxel_hits, ctx->hits.voxel.ptr, ctx->n_voxels * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                 ctx->stream));
   if (map_hits) {
+    // the counters grow at the next fusion (sync_maps): views added since the last one may lie beyond them and have no hit yet,
+    // while the views before keep what they have gathered
     const size_t n = ctx->views.h_maps.size();
-    if (n > 0 && dmi::holds(ctx->hits.map, n * sizeof(uint64_t))) {
-      static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "u64");
-      DMI_HIP(ctx, hipMemcpyAsync(map_hits, ctx->hits.map.ptr, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    } else {
-      for (size_t i = 0; i < n; ++i) map_hits[i] = 0;
-    }
+    const size_t counted = ctx->hits.map.ptr ? std::min<size_t>(n, (size_t)(ctx->hits.map.capacity / sizeof(uint64_t))) : 0;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "u64");
+    if (counted > 0)
+      DMI_HIP(ctx, hipMemcpyAsync(map_hits, ctx->hits.map.ptr, counted * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    for (size_t i = counted; i < n; ++i) map_hits[i] = 0;
   }
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return drain_events(ctx);

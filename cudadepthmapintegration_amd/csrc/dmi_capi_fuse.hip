@@ -26,23 +26,25 @@ using dmi::TileMapRec;
 namespace {
 
 // The views' records on the device, and a hit counter for each.  The four record arrays grow as a unit: a later call finds all
-// four at one capacity or all four empty.
+// four at one capacity or all four empty.  How much a launch may read of each and how much a growth allocates is the record
+// tables' rule (fusion_launch_rules.h: the window column reads one WinRec beyond the last view).
+static_assert(dmi::kRecordBytes[dmi::REC_MAP] == sizeof(MapRec) && dmi::kRecordBytes[dmi::REC_TILE_MAP] == sizeof(TileMapRec) &&
+              dmi::kRecordBytes[dmi::REC_WIN] == sizeof(dmi::WinRec) && dmi::kRecordBytes[dmi::REC_FOOT] == sizeof(dmi::FootRec) &&
+              dmi::kRecordBytes[dmi::REC_HITS] == sizeof(unsigned long long), "the record tables' rule has the records' sizes");
 int sync_maps(dmi_context *ctx) {
   dmi_context::Views &v = ctx->views;
   const size_t n = v.h_maps.size();
-  const size_t cap = std::max<size_t>(64, n * 2);
+  auto growth = [n](dmi::DeviceBuffer *b, dmi::RecordTable t) { return dmi::BufferGrowth{b, dmi::record_bytes_read(t, n), dmi::record_bytes_allocated(t, n)}; };
   bool fresh = false;
-  int rc = dmi::ensure_idle_buffers(ctx, {{&v.maps, n * sizeof(MapRec), cap * sizeof(MapRec)},
-                                          {&v.tile_maps, n * sizeof(TileMapRec), cap * sizeof(TileMapRec)},
-                                          {&v.win_recs, n * sizeof(dmi::WinRec), cap * sizeof(dmi::WinRec)},
-                                          {&v.foot_recs, n * sizeof(dmi::FootRec), cap * sizeof(dmi::FootRec)}}, &fresh);
+  int rc = dmi::ensure_idle_buffers(ctx, {growth(&v.maps, dmi::REC_MAP), growth(&v.tile_maps, dmi::REC_TILE_MAP),
+                                          growth(&v.win_recs, dmi::REC_WIN), growth(&v.foot_recs, dmi::REC_FOOT)}, &fresh);
   if (rc != DMI_OK) return rc;
   if (fresh) v.maps_dirty = true;
   dmi::DeviceBuffer &hits = ctx->hits.map;
-  if (ctx->opt.count_hits && !dmi::holds(hits, n * sizeof(unsigned long long))) {
+  if (ctx->opt.count_hits && !dmi::holds(hits, dmi::record_bytes_read(dmi::REC_HITS, n))) {
     // grow, keeping the counts gathered so far
     dmi::DeviceBuffer grown;
-    rc = dmi::ensure_buffer(ctx, grown, cap * sizeof(unsigned long long));
+    rc = dmi::ensure_buffer(ctx, grown, dmi::record_bytes_allocated(dmi::REC_HITS, n));
     if (rc != DMI_OK) return rc;
     hipError_t e = hipMemsetAsync(grown.ptr, 0, grown.capacity, ctx->stream);
     if (e == hipSuccess && hits.ptr) {

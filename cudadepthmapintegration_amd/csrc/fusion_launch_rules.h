@@ -165,6 +165,29 @@ DMI_RULES_HD inline WinPairFill win_pair_fill(uint64_t brick, uint32_t block, ui
   return f;
 }
 
+// ---- the views' record tables (sync_maps, dmi_capi_fuse.hip): how many records a growth allocates, and how many bytes of each
+// table a launch over the resident views [0, n) may read.  sync_maps asks for record_bytes_read and allocates
+// record_bytes_allocated, so a table is grown exactly when a launch could read past its end.
+// What reads a table beyond the launch's last view (every consumer in fusion_tile.hip, fusion_classify.hip, fusion_kernels.hip and
+// fusion_device.h read once, for an index of first_map + n_maps or more):
+//   MapRec      none.  The general kernel's loop and tile_exact stop at m_end; classify_bricks clamps its view to n_maps - 1 and
+//               the coarse pass returns for mm >= n_maps; fill_launch_tables takes e / kpad < n_maps.
+//   TileMapRec  none.  Read beside MapRec under the same index everywhere; the tiled kernel's view loop masks the class words to
+//               [first_map, m_end) before it touches a record.
+//   WinRec      ONE record: the window column of fusion_tile.hip fetches a dword at offset 0x40 of the record it works on -- the
+//               first dword of the NEXT view's record, a prefetch whose value is never used -- so the launch's last view reaches
+//               record n.  window_origin_kernel tests m < m_end first: none there.
+//   FootRec     none.  Only window_origin_kernel reads it, under that same test.
+//   hit counters (u64 per view): none.  atomicAdd at the view's own index inside the loops above.
+// The sizes are those of view_records.h; dmi_capi_fuse.hip asserts that they are.
+enum RecordTable : int { REC_MAP = 0, REC_TILE_MAP = 1, REC_WIN = 2, REC_FOOT = 3, REC_HITS = 4, kRecordTables = 5 };
+constexpr uint64_t kRecordBytes[kRecordTables] = {208, 368, 64, 320, 8};
+constexpr uint64_t kRecordsReadAhead[kRecordTables] = {0, 0, 1, 0, 0};
+// views often arrive in chunks (add, fuse, add, fuse ...): a growth allocates twice the records there are views, 64 at least
+inline uint64_t record_capacity(uint64_t n_views) { return n_views * 2 > 64 ? n_views * 2 : 64; }
+inline uint64_t record_bytes_read(RecordTable t, uint64_t n_views) { return (n_views + kRecordsReadAhead[t]) * kRecordBytes[t]; }
+inline uint64_t record_bytes_allocated(RecordTable t, uint64_t n_views) { return record_capacity(n_views) * kRecordBytes[t]; }
+
 // No sum of the launch can be -0.0 (the launches the kernel's ZF instantiations serve, fusion_tile.hip), and the +0.0 adds of the
 // pairs far behind every surface can be dropped (TileArgs::behind_mask):
 // +0.0 adds are no-ops unless a sum can be -0.0 (only an uploaded grid can bring one) or hits are counted

@@ -794,7 +794,8 @@ __global__ __launch_bounds__(64 * WX * WY, MINW) void fuse_tile_kernel(const Til
         const u32x16 R = *reinterpret_cast<const u32x16 __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(wrec));
 #ifndef DMI_NO_WINREC_PREFETCH
         // the NEXT view's record on its way into the scalar cache (most of a brick's window views are consecutive): one dword of
-        // its line into a register that is only waited for, after the column (the table has room beyond the last view)
+        // its line into a register that is only waited for, after the column (the last view's fetch reads record n of the table:
+        // the record tables' rule, fusion_launch_rules.h -- kRecordsReadAhead[REC_WIN] --, has sync_maps hold n + 1 records)
         // (issued once THIS record has arrived -- the unused operand says so --: the wait for it must not cover the next one's trip)
         int next_rec;
         asm volatile("s_load_dword %0, %1, 0x40" : "=&s"(next_rec) : "s"(wrec), "s"(R[15]));

@@ -214,7 +214,7 @@ int dmi_download_grid_f32(dmi_context *ctx, float *out);
 int dmi_fuse_range_download(dmi_context *ctx, int32_t first, int32_t count, void *out, int32_t out_dtype, int32_t n_slabs);
 
 /* voxel_hits [n_voxels] u32 and/or map_hits [n_views] u64 (either may be NULL).
- * Needs count_hits at creation. */
+ * Needs count_hits at creation.  A view added since the last fusion reads 0; the views before it keep their counts. */
 int dmi_download_hits(dmi_context *ctx, uint32_t *voxel_hits, uint64_t *map_hits);
 
 /* Device pointer of the grid (context-owned or external) for zero-copy consumers. */

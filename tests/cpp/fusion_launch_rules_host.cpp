@@ -92,6 +92,47 @@ int main() {
   { WindowsQuestion q = all; q.zero_free = false; EXPECT(!use_windows(q)); }
   { WindowsQuestion q = all; q.depth_f64 = true; EXPECT(!use_windows(q)); }
 
+  // ---- the views' record tables: capacity, bytes read, bytes allocated (tests/test_gpu_sequence_fuzz.py restates these numbers)
+  {
+    const uint64_t ns[10] = {1, 31, 32, 33, 63, 64, 65, 129, 130, 131};
+    const uint64_t caps[10] = {64, 64, 64, 66, 126, 128, 130, 258, 260, 262};
+    const uint64_t sizes[kRecordTables] = {208, 368, 64, 320, 8};
+    for (int q = 0; q < 10; ++q) {
+      const uint64_t n = ns[q];
+      EXPECT(record_capacity(n) == caps[q]);
+      for (int t = 0; t < kRecordTables; ++t) {
+        const uint64_t ahead = t == REC_WIN ? 1 : 0;   // the window column's prefetch: offset 0x40 of the last view's record
+        EXPECT(record_bytes_read((RecordTable)t, n) == (n + ahead) * sizes[t]);
+        EXPECT(record_bytes_allocated((RecordTable)t, n) == caps[q] * sizes[t]);
+        EXPECT(record_bytes_allocated((RecordTable)t, n) >= record_bytes_read((RecordTable)t, n));
+      }
+      // the prefetch's four bytes, at 64 (n - 1) + 0x40 .. + 4, lie inside what the launch is said to read
+      EXPECT(64 * (n - 1) + 0x40 + 4 <= record_bytes_read(REC_WIN, n));
+    }
+    EXPECT(record_capacity(0) == 64);
+    // a context that fuses at a views and then at b >= a (dmi_buffer.h: a table that holds what is needed is kept, any other is
+    // allocated anew, all four as a unit): what it holds covers what the second launch reads, for every table
+    int uncovered = 0, kept_at_capacity = 0;
+    for (uint64_t a = 1; a <= 140; ++a)
+      for (uint64_t b = a; b <= 140; ++b) {
+        uint64_t held[kRecordTables];
+        for (int t = 0; t < kRecordTables; ++t) held[t] = record_bytes_allocated((RecordTable)t, a);   // the first fuse: nothing held before
+        bool enough = true;
+        for (int t = REC_MAP; t <= REC_FOOT; ++t) enough = enough && held[t] >= record_bytes_read((RecordTable)t, b);
+        if (!enough)
+          for (int t = REC_MAP; t <= REC_FOOT; ++t) held[t] = record_bytes_allocated((RecordTable)t, b);
+        if (held[REC_HITS] < record_bytes_read(REC_HITS, b)) held[REC_HITS] = record_bytes_allocated(REC_HITS, b);   // grown by itself
+        for (int t = 0; t < kRecordTables; ++t)
+          if (held[t] < record_bytes_read((RecordTable)t, b)) ++uncovered;
+        // b == the capacity held: the window table must have been grown (the old rule kept it, 4 bytes short)
+        if (b == record_capacity(a) && held[REC_WIN] == record_bytes_allocated(REC_WIN, a)) ++kept_at_capacity;
+      }
+    EXPECT(uncovered == 0);
+    EXPECT(kept_at_capacity == 0);
+    // (the pair the defect was reported with: 32 views, then 64)
+    EXPECT(record_bytes_allocated(REC_WIN, 32) == 4096 && record_bytes_read(REC_WIN, 64) == 4160);
+  }
+
   // ---- no sum can be -0.0: the ZF instantiations and the behind mask
   EXPECT(zero_free(false, false, false, 0));
   EXPECT(zero_free(false, true, false, 0));

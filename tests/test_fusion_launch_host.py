@@ -3,7 +3,10 @@ with AddressSanitizer + UBSan and run; nothing is loaded into Python.
 
   fusion_launch_rules_host  csrc/fusion_launch_rules.h -- hole traits, default tile shape, classes on or off, class pitch, windows,
                             the zero-free rule and the cost order -- at every threshold's boundary; the expected values restate the
-                            expressions fuse_run carried before the rules had a header of their own.
+                            expressions fuse_run carried before the rules had a header of their own.  The record tables' rule
+                            (capacity, bytes read, bytes allocated) at n = 1, 31, 32, 33, 63, 64, 65, 129, 130, 131, and a replay of
+                            "fuse at a views, then at b >= a" for all 1 <= a <= b <= 140: what is held covers what is read -- the
+                            WinRec beyond the last view, which the window column prefetches, included.
   buffer_growth_host        csrc/dmi_buffer.h against host stand-ins for hipMalloc / hipFree / hipStreamSynchronize
                             (tests/cpp/support_host/) whose allocator fails on the N-th call, for every N over a four-buffer unit
                             growth and a single one: no buffer keeps an old capacity, the byte count is the sum of the capacities,
