@@ -124,6 +124,7 @@ ABI_SYMBOLS = [
     "dmi_color_render_depths", "dmi_color_render_isosurface_depths", "dmi_color_download_depths", "dmi_color_get_render_kernel_ms",
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds", "dmi_filter_depth_speckles", "dmi_fill_depth_holes",
+    "dmi_depth_smoothing_weights", "dmi_smooth_depths",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -294,6 +295,9 @@ def load() -> ctypes.CDLL:
         L.dmi_filter_depth_speckles.argtypes = [dp, dp, dbl, i32, i32, i32, dbl, dbl, i64, i32, dp, i32p, dp]
     if hasattr(L, "dmi_fill_depth_holes"):
         L.dmi_fill_depth_holes.argtypes = [dp, dp, dbl, i32, i32, i32, dbl, dbl, i64, i32, dp, i32p, dp]
+    if hasattr(L, "dmi_smooth_depths"):
+        L.dmi_depth_smoothing_weights.argtypes = [dbl, dbl, ctypes.POINTER(i32), dp]
+        L.dmi_smooth_depths.argtypes = [dp, dp, dbl, i32, i32, i32, dbl, dbl, dbl, dbl, i32, i32, dp, i32p, dp]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1175,6 +1179,51 @@ def fill_depth_holes(views: Views, *, max_pixels: int, abs_tolerance: float = 0.
     return Views(out, views.K4, views.RT4, None), sizes, float(ms.value)
 
 
+def depth_smoothing_weights(sigma: float, truncate: float = 2.0) -> np.ndarray:
+    """s[0..r], the spatial weights of one axis of the depth smoothing with r = ceil(truncate * sigma): s[0] = 1, not normalised, as
+    the library computes them (dmi_depth_smoothing_weights; no GPU needed).  DmiError with code 1 for parameters outside the
+    definition."""
+    L = load()
+    r, s = ctypes.c_int32(0), np.zeros(9, dtype=np.float64)
+    code = L.dmi_depth_smoothing_weights(float(sigma), float(truncate), ctypes.byref(r), _dp(s))
+    if code != 0:
+        raise DmiError(code, (L.dmi_last_error(None) or b"").decode())
+    return s[:int(r.value) + 1].copy()
+
+
+def smooth_depths(views: Views, *, sigma: float, truncate: float = 2.0, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0,
+                  iterations: int = 1, threshold: float | None = None, device: int = 0, out: np.ndarray | None = None):
+    """Depth maps smoothed with their edges preserved (include/dmi.h: dmi_smooth_depths): every valid depth c moves to the weighted
+    mean of the valid depths q within r = ceil(truncate * sigma) pixels with (q - c)^2 < tau^2, tau = abs_tolerance +
+    rel_tolerance * c, the weight a spatial Gaussian times Tukey's biweight of q - c; `iterations` passes, each on the output of
+    the one before.  threshold applies views.best_cost first (best cost > threshold => -1).  The cameras are not read.  Returns
+    (Views with the smoothed depths, the same cameras and best_cost None; counts int32 [n, H, W]: the taps taken at every pixel in
+    the last pass, 0 at a pixel without a depth; the kernels' hipEvent time in ms).  out: where the smoothed depths go; it may be
+    views.depth itself (f64, C-contiguous), which is then smoothed in place."""
+    L = load()
+    d = np.ascontiguousarray(views.depth, dtype=np.float64)
+    if d.ndim != 3:
+        raise ValueError(f"views.depth must be [n, H, W], got {d.shape}")
+    n, H, W = d.shape
+    bc = None
+    if threshold is not None and views.best_cost is not None:
+        bc = np.ascontiguousarray(views.best_cost, dtype=np.float64)
+        if bc.shape != d.shape:
+            raise ValueError("views.best_cost must have the shape of views.depth")
+    if out is None:
+        out = np.empty_like(d)
+    elif out.dtype != np.float64 or out.shape != d.shape or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous f64 array of the depths' shape")
+    counts = np.zeros(d.shape, dtype=np.int32)
+    ms = ctypes.c_double(0.0)
+    rc = L.dmi_smooth_depths(_dp(d), None if bc is None else _dp(bc), 0.0 if threshold is None else float(threshold), n, W, H,
+                             float(sigma), float(truncate), float(abs_tolerance), float(rel_tolerance), int(iterations), int(device),
+                             _dp(out), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(ms))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    return Views(out, views.K4, views.RT4, None), counts, float(ms.value)
+
+
 def estimate_scene_bounds(views: Views, *, trim_fraction: float = 0.0, pixel_step: int = 1, axes=None, threshold: float | None = None,
                           device: int = 0):
     """The bounds of the scene the depth maps see (include/dmi.h: dmi_estimate_scene_bounds): per axis the element of rank k and
@@ -1572,7 +1621,10 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_speckle_min_pixels", ctypes.c_int64), ("depth_speckle_tolerance", ctypes.c_double),
                 ("depth_speckle_rel_tolerance", ctypes.c_double),
                 ("depth_fill_holes_max_pixels", ctypes.c_int64), ("depth_fill_holes_tolerance", ctypes.c_double),
-                ("depth_fill_holes_rel_tolerance", ctypes.c_double)]
+                ("depth_fill_holes_rel_tolerance", ctypes.c_double),
+                ("depth_smooth_sigma", ctypes.c_double), ("depth_smooth_truncate", ctypes.c_double),
+                ("depth_smooth_tolerance", ctypes.c_double), ("depth_smooth_rel_tolerance", ctypes.c_double),
+                ("depth_smooth_iterations", ctypes.c_int64)]
 
 
 def cli_read_arguments(args):

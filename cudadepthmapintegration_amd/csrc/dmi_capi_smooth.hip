@@ -1,0 +1,126 @@
+// dmi_capi_smooth.hip -- dmi_smooth_depths and dmi_depth_smoothing_weights of include/dmi.h: the argument checks (all of them before
+// the device is touched), and per piece of whole views the upload, one launch of depth_smooth.hip per iteration between two planes
+// and the download.  Context-free, like dmi_fill_depth_holes: everything the call allocates it frees before it returns; the device
+// holds the planes of one piece at a time.  A failure's text is dmi_last_error(NULL)'s.
+#include <algorithm>
+#include <string>
+
+#include "depth_smooth.h"
+#include "dmi_context.h"
+
+namespace {
+
+using dmi::fail;
+
+constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up and comes down in pieces of whole views, as many as fit this
+
+bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
+
+// what the call holds on the device and the events that time its kernels; released whatever way the call ends
+struct Holdings {
+  dmi::DeviceBuffer plane[2], cost, count;
+  hipStream_t stream = nullptr;
+  hipEvent_t events[2] = {nullptr, nullptr};  // before the first iteration's launch and behind the last one's
+  ~Holdings() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    dmi::free_buffers({&plane[0], &plane[1], &cost, &count});
+    for (hipEvent_t e : events)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+#define DMI_DS_HIP(call) DMI_HIP(nullptr, call)
+
+int smooth(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H, double sigma,
+           double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations, int32_t device, double *out_depth,
+           int32_t *out_count, double *kernel_ms) {
+  const std::string entry = "dmi_smooth_depths: ";
+  auto bad = [&](const std::string &what) { return fail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!depth) return bad("depth is null");
+  if (!out_depth) return bad("out_depth is null");
+  if (n < 1) return bad("n >= 1 required");
+  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
+  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
+  if (!finite_and_not_negative(sigma)) return bad("sigma must be finite and >= 0");
+  if (!(truncate > 0.0 && truncate <= 4.0)) return bad("truncate must lie in (0, 4]");
+  int32_t radius = 0;
+  double s[dmi::kDepthSmoothMaxRadius + 1];
+  if (dmi::depth_smoothing_weights(sigma, truncate, &radius, s) != 0)
+    return bad("the radius ceil(truncate * sigma) must not exceed " + std::to_string(dmi::kDepthSmoothMaxRadius));
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (iterations < 1 || iterations > dmi::kDepthSmoothMaxIterations)
+    return bad("iterations must lie in [1, " + std::to_string(dmi::kDepthSmoothMaxIterations) + "]");
+  if (best_cost && threshold != threshold) return bad("threshold is NaN");
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
+  }
+  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
+  DMI_DS_HIP(hipSetDevice(device));
+
+  Holdings h;
+  DMI_DS_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+  for (hipEvent_t &e : h.events) DMI_DS_HIP(hipEventCreate(&e));
+  const size_t plane = (size_t)W * H, views = (size_t)n;
+  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));  // a larger view goes whole
+  DMI_DS_HIP(dmi::grow_buffer(h.plane[0], chunk * plane * sizeof(double)));
+  DMI_DS_HIP(dmi::grow_buffer(h.plane[1], chunk * plane * sizeof(double)));
+  if (best_cost) DMI_DS_HIP(dmi::grow_buffer(h.cost, chunk * plane * sizeof(double)));
+  if (out_count) DMI_DS_HIP(dmi::grow_buffer(h.count, chunk * plane * sizeof(int32_t)));
+  const dmi::SmoothArgs args = dmi::smooth_args(s, radius, abs_tolerance, rel_tolerance);
+
+  double total_ms = 0.0;
+  for (size_t m0 = 0; m0 < views; m0 += chunk) {
+    const size_t cnt = std::min(chunk, views - m0);
+    DMI_DS_HIP(hipMemcpyAsync(h.plane[0].ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    if (best_cost)
+      DMI_DS_HIP(hipMemcpyAsync(h.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    DMI_DS_HIP(hipEventRecord(h.events[0], h.stream));
+    int from = 0;  // iteration k + 1 reads the complete output of iteration k: the two planes take turns
+    for (int32_t k = 0; k < iterations; ++k, from ^= 1) {
+      const bool first = k == 0, last = k + 1 == iterations;
+      DMI_DS_HIP(dmi::launch_depth_smooth(h.plane[from].as<double>(), first && best_cost ? h.cost.as<double>() : nullptr, threshold,
+                                          h.plane[from ^ 1].as<double>(), last && out_count ? h.count.as<int32_t>() : nullptr,
+                                          (int64_t)cnt, W, H, args, h.stream));
+    }
+    DMI_DS_HIP(hipEventRecord(h.events[1], h.stream));
+    DMI_DS_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.plane[from].ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    if (out_count)
+      DMI_DS_HIP(hipMemcpyAsync(out_count + m0 * plane, h.count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
+    DMI_DS_HIP(hipStreamSynchronize(h.stream));  // the planes are reused by the next piece
+    float ms = 0.f;
+    DMI_DS_HIP(hipEventElapsedTime(&ms, h.events[0], h.events[1]));
+    total_ms += (double)ms;
+  }
+  if (kernel_ms) *kernel_ms = total_ms;
+  return DMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmi_depth_smoothing_weights(double sigma, double truncate, int32_t *radius, double *weights) {
+  return dmi::guarded(nullptr, "dmi_depth_smoothing_weights", [&]() -> int {
+    if (dmi::depth_smoothing_weights(sigma, truncate, radius, weights) != 0)
+      return fail(nullptr, DMI_ERR_INVALID_ARGUMENT,
+                  "dmi_depth_smoothing_weights: sigma must be finite and >= 0, truncate finite and in (0, 4], ceil(truncate * sigma) <= 8, "
+                  "and the pointers not null");
+    return DMI_OK;
+  });
+}
+
+int dmi_smooth_depths(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H, double sigma,
+                      double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations, int32_t device,
+                      double *out_depth, int32_t *out_count, double *kernel_ms) {
+  return dmi::guarded(nullptr, "dmi_smooth_depths", [&]() -> int {
+    return smooth(depth, best_cost, threshold, n, W, H, sigma, truncate, abs_tolerance, rel_tolerance, iterations, device, out_depth,
+                  out_count, kernel_ms);
+  });
+}
+
+}  // extern "C"

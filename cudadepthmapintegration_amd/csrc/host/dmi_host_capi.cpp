@@ -393,6 +393,11 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->depth_fill_holes_max_pixels = o.depthFillHolesMaxPixels;
   out->depth_fill_holes_tolerance = o.depthFillHolesTolerance;
   out->depth_fill_holes_rel_tolerance = o.depthFillHolesRelTolerance;
+  out->depth_smooth_sigma = o.depthSmoothSigma;
+  out->depth_smooth_truncate = o.depthSmoothTruncate;
+  out->depth_smooth_tolerance = o.depthSmoothTolerance;
+  out->depth_smooth_rel_tolerance = o.depthSmoothRelTolerance;
+  out->depth_smooth_iterations = o.depthSmoothIterations;
   return 1;
   });
 }

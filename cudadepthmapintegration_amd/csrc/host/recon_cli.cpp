@@ -16,6 +16,7 @@
 #include <ostream>
 #include <sstream>
 
+#include "../depth_smooth_rules.h"
 #include "../point_smooth_rules.h"
 #include "recon_host.h"
 
@@ -276,6 +277,35 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                                       "round the hole (finite, >= 0, default 0.01; not in the reference)",
                                         into_checked_double(&o->depthFillHolesRelTolerance, &o->depthFillHolesRelToleranceGiven,
                                                             [](double x) { return x >= 0.0; })}},
+      {"--depthSmoothSigma", {Kind::kValue, "smooth the depth maps on the GPU before they are fused, their edges preserved, behind "
+                                            "--depthFillHolesMaxPixels and before --depthConsistencyMinViews and --gridAutoBounds see "
+                                            "them: every depth moves to a weighted mean of the depths round it that differ from it by "
+                                            "less than the tolerance, the weight falling off with the distance as a Gaussian of this "
+                                            "sigma in pixels and with the depth difference (finite, >= 0; the radius "
+                                            "ceil(truncate * sigma) is at most 8).  No pixel gains or loses its depth.  All views are "
+                                            "then read into host memory at once, as with --depthSpeckleMinPixels, and smoothed on the "
+                                            "first --device (not in the reference)",
+                              into_checked_double(&o->depthSmoothSigma, &o->depthSmoothSigmaGiven, [](double x) { return x >= 0.0; })}},
+      {"--depthSmoothTruncate", {Kind::kValue, "with --depthSmoothSigma: the Gaussian is cut off at this many sigmas (finite, in (0, 4], "
+                                               "default 2; not in the reference)",
+                                 into_checked_double(&o->depthSmoothTruncate, &o->depthSmoothTruncateGiven,
+                                                     [](double x) { return x > 0.0 && x <= 4.0; })}},
+      {"--depthSmoothTolerance", {Kind::kValue, "with --depthSmoothSigma: a neighbouring depth takes part if it differs from the pixel's "
+                                                "by less than this distance (world units, finite, >= 0, default 0) plus the relative "
+                                                "tolerance; a step higher than that is not smoothed across (not in the reference)",
+                                  into_checked_double(&o->depthSmoothTolerance, &o->depthSmoothToleranceGiven,
+                                                      [](double x) { return x >= 0.0; })}},
+      {"--depthSmoothRelTolerance", {Kind::kValue, "with --depthSmoothSigma: ... plus this share of the pixel's depth (finite, >= 0, "
+                                                   "default 0.01; not in the reference)",
+                                     into_checked_double(&o->depthSmoothRelTolerance, &o->depthSmoothRelToleranceGiven,
+                                                         [](double x) { return x >= 0.0; })}},
+      {"--depthSmoothIterations", {Kind::kValue, "with --depthSmoothSigma: smooth this many times, each pass on the result of the one "
+                                                 "before (an integer in [1, 16], default 1; not in the reference)",
+                                   [o](const std::vector<std::string> &values) {
+                                     o->depthSmoothIterationsGiven = true;
+                                     return into_count(&o->depthSmoothIterations)(values) && o->depthSmoothIterations >= 1 &&
+                                            o->depthSmoothIterations <= dmi::kDepthSmoothMaxIterations;
+                                   }}},
       {"--gridAutoBounds", {Kind::kFlag, "take the grid's box from the depth maps instead of --gridOrigin and --gridEnd, which then must "
                                          "not be given (one of --gridDims / --gridSpacing still is): every valid pixel is "
                                          "back-projected on the GPU, and along each of the grid's axes the box runs from the "
@@ -503,6 +533,23 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
       err << "Error : " << flag.first << " needs --depthFillHolesMaxPixels.\n" << HelpText();
       return false;
     }
+  for (const auto &flag : {std::make_pair("--depthSmoothTruncate", o->depthSmoothTruncateGiven),
+                           std::make_pair("--depthSmoothTolerance", o->depthSmoothToleranceGiven),
+                           std::make_pair("--depthSmoothRelTolerance", o->depthSmoothRelToleranceGiven),
+                           std::make_pair("--depthSmoothIterations", o->depthSmoothIterationsGiven)})
+    if (flag.second && !o->depthSmoothSigmaGiven) {
+      err << "Error : " << flag.first << " needs --depthSmoothSigma.\n" << HelpText();
+      return false;
+    }
+  if (o->depthSmoothSigmaGiven) {  // the library's own rule: ceil(truncate * sigma) <= 8
+    int32_t radius = 0;
+    double weights[dmi::kDepthSmoothMaxRadius + 1];
+    if (dmi::depth_smoothing_weights(o->depthSmoothSigma, o->depthSmoothTruncate, &radius, weights) != 0) {
+      err << "Bad value for --depthSmoothSigma: the radius ceil(truncate * sigma) must not exceed " << dmi::kDepthSmoothMaxRadius << "\n"
+          << HelpText();
+      return false;
+    }
+  }
   for (const auto &flag : {std::make_pair("--gridAutoBoundsTrim", o->gridAutoBoundsTrimGiven),
                            std::make_pair("--gridAutoBoundsMargin", o->gridAutoBoundsMarginGiven),
                            std::make_pair("--gridAutoBoundsPixelStep", o->gridAutoBoundsPixelStepGiven)})
@@ -885,6 +932,31 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     say(line.str());
     return true;
   };
+  // the depths of all views smoothed on the first device: behind the hole fill, so that invented depths are smoothed with their
+  // surroundings, and in front of the consistency filter, so that every smoothed depth still has to be confirmed
+  auto smooth_views = [&]() {
+    say("** Smooth the depth maps...");
+    if (!read_views("--depthSmoothSigma")) return false;
+    DepthSmoothReport report;
+    std::string error;
+    if (!SmoothDepths(views, o.threshBestCost, o.depthSmoothSigma, o.depthSmoothTruncate, o.depthSmoothTolerance,
+                      o.depthSmoothRelTolerance, (int)o.depthSmoothIterations, o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+      result->error = "--depthSmoothSigma: " + error;
+      return false;
+    }
+    result->depthSmoothViews = report.views;
+    result->depthSmoothValidPixels = report.validPixels;
+    result->depthSmoothChangedPixels = report.changedPixels;
+    result->depthSmoothMeanTaps = report.meanTaps;
+    result->depthSmoothKernelMs = report.kernelMs;
+    std::ostringstream line;
+    line << "depth smoothing: sigma " << o.depthSmoothSigma << " pixels, truncate " << o.depthSmoothTruncate << ", tolerance "
+         << o.depthSmoothTolerance << " + " << o.depthSmoothRelTolerance << " z, " << o.depthSmoothIterations << " iterations; "
+         << report.views << " views, " << report.validPixels << " pixels with a depth, " << report.changedPixels << " changed; "
+         << report.meanTaps << " taps per pixel; " << report.kernelMs << " ms of GPU kernels";
+    say(line.str());
+    return true;
+  };
   // all views filtered on the first device
   auto filter_views = [&]() {
     say("** Filter the depth maps by cross-view consistency...");
@@ -911,6 +983,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     // the box before anything is described or set up: filtered depths if a filter was asked for, measured along the grid's axes
     if (o.depthSpeckleMinPixels >= 0 && !speckle_views()) return 1;
     if (o.depthFillHolesMaxPixels >= 0 && !fill_views()) return 1;
+    if (o.depthSmoothSigmaGiven && !smooth_views()) return 1;
     if (o.depthConsistencyMinViews >= 0 ? !filter_views() : !read_views("--gridAutoBounds")) return 1;
     say("** Estimate the grid's bounds from the depth maps...");
     // axes[j][i] = M[i][j] / |row_i|^2, M's rows the grid's axes: the inverse of the grid matrix for orthogonal rows, so that the
@@ -1010,6 +1083,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   if (supportMesh) filter.SetKeepContext(true);
   if (o.depthSpeckleMinPixels >= 0 && !o.gridAutoBounds && !speckle_views()) return 1;
   if (o.depthFillHolesMaxPixels >= 0 && !o.gridAutoBounds && !fill_views()) return 1;
+  if (o.depthSmoothSigmaGiven && !o.gridAutoBounds && !smooth_views()) return 1;
   if (o.depthConsistencyMinViews >= 0 && !o.gridAutoBounds && !filter_views()) return 1;
   if (!views.empty()) filter.SetViews(views);
   if (!filter.Update()) {
@@ -1277,6 +1351,12 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << o.depthFillHolesRelTolerance << " z\n  views  " << result->depthFillHolesViews << "\n  holes  " << result->depthFillHolesHoles
           << "\n  holes filled  " << result->depthFillHolesFilledHoles << "\n  pixels filled  " << result->depthFillHolesFilledPixels
           << "\n  GPU kernels  " << result->depthFillHolesKernelMs << " ms\n";
+    if (o.depthSmoothSigmaGiven)
+      out << "depth smoothing\n  sigma  " << o.depthSmoothSigma << " pixels\n  truncate  " << o.depthSmoothTruncate << "\n  tolerance  "
+          << o.depthSmoothTolerance << " + " << o.depthSmoothRelTolerance << " z\n  iterations  " << o.depthSmoothIterations
+          << "\n  views  " << result->depthSmoothViews << "\n  pixels with a depth  " << result->depthSmoothValidPixels
+          << "\n  pixels changed  " << result->depthSmoothChangedPixels << "\n  taps per pixel  " << result->depthSmoothMeanTaps
+          << "\n  GPU kernels  " << result->depthSmoothKernelMs << " ms\n";
     if (o.depthConsistencyMinViews >= 0)
       out << "depth consistency\n  minimum agreeing views  " << o.depthConsistencyMinViews << "\n  tolerance  " << o.depthConsistencyTolerance
           << " + " << o.depthConsistencyRelTolerance << " z\n  views  " << result->depthConsistencyViews << "\n  pixels with a depth  "

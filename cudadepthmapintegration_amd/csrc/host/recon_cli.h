@@ -33,6 +33,10 @@
 // interpolation of stereo pipelines) takes the same in-memory path and runs behind the speckle filter and in front of the
 // consistency filter (dmi_fill_depth_holes): an island the first removed is refilled from its surroundings, and every invented
 // depth still has to be confirmed by other views where the second is on.
+// --depthSmoothSigma S with --depthSmoothTruncate / --depthSmoothTolerance / --depthSmoothRelTolerance / --depthSmoothIterations
+// (not in the reference: the bilateral filter of TSDF pipelines) takes the same in-memory path and runs behind the hole fill and
+// in front of the consistency filter (dmi_smooth_depths): invented depths are smoothed with their surroundings, and every
+// smoothed depth still has to be confirmed by other views where the consistency filter is on.
 // --gridAutoBounds (not in the reference, which needs --gridOrigin and --gridEnd from outside the data) takes the grid's box from the
 // depth maps themselves: all views are read into memory -- and filtered first with --depthConsistencyMinViews --, the first device
 // gives trimmed order statistics of the back-projected pixels along the grid's axes (dmi_estimate_scene_bounds;
@@ -130,6 +134,13 @@ struct Options {
   long long depthFillHolesMaxPixels = -1;
   double depthFillHolesTolerance = 0.0, depthFillHolesRelTolerance = 0.01;
   bool depthFillHolesToleranceGiven = false, depthFillHolesRelToleranceGiven = false;
+  // not in the reference: smooth the depth maps on the GPU, edges preserved, behind the hole fill (dmi_smooth_depths: sigma in
+  // pixels, -1 = flag not given), with the reach in sigmas, an absolute and a relative tolerance on the depth difference of a tap,
+  // and the number of passes
+  double depthSmoothSigma = -1.0, depthSmoothTruncate = 2.0, depthSmoothTolerance = 0.0, depthSmoothRelTolerance = 0.01;
+  long long depthSmoothIterations = 1;
+  bool depthSmoothSigmaGiven = false, depthSmoothTruncateGiven = false, depthSmoothToleranceGiven = false, depthSmoothRelToleranceGiven = false,
+       depthSmoothIterationsGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -187,6 +198,10 @@ struct RunResult {
   // of the kernels
   unsigned long long depthFillHolesViews = 0, depthFillHolesHoles = 0, depthFillHolesFilledHoles = 0, depthFillHolesFilledPixels = 0;
   double depthFillHolesKernelMs = 0.0;
+  // --depthSmoothSigma: the views smoothed, their pixels with a depth, the ones whose depth changed, the taps taken per valid
+  // pixel in the last iteration, and the hipEvent time of the kernels
+  unsigned long long depthSmoothViews = 0, depthSmoothValidPixels = 0, depthSmoothChangedPixels = 0;
+  double depthSmoothMeanTaps = 0.0, depthSmoothKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);

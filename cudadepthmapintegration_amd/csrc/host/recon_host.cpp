@@ -829,6 +829,58 @@ bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thres
 }
 
 // Not in the reference (recon_host.h)
+bool SmoothDepths(const std::vector<ReconstructionData *> &views, double thresholdBestCost, double sigma, double truncate,
+                  double absTolerance, double relTolerance, int iterations, int device, DepthSmoothReport *report, std::string *error) {
+  const size_t n = views.size();
+  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
+  if (!first) {
+    *error = "SmoothDepths: no views, or view 0 has no depth map";
+    return false;
+  }
+  const int W = first->dims[0], H = first->dims[1];
+  const size_t npix = (size_t)W * H;
+  if (n > 0x7fffffffu) {
+    *error = "SmoothDepths: too many views";
+    return false;
+  }
+  std::vector<double> depth(n * npix);
+  DepthSmoothReport r;
+  r.views = n;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
+      *error = "SmoothDepths: view " + std::to_string(m) + " has no depth map of the size of view 0";
+      return false;
+    }
+    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
+    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
+  }
+  std::vector<int32_t> count(n * npix);
+  const int rc = dmi_smooth_depths(depth.data(), nullptr, 0.0, (int32_t)n, W, H, sigma, truncate, absTolerance, relTolerance,
+                                   (int32_t)iterations, device, depth.data(), count.data(), &r.kernelMs);
+  if (rc != DMI_OK) {
+    *error = dmi_last_error(nullptr);
+    return false;
+  }
+  uint64_t taps = 0;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage smoothed = *views[m]->GetDepthMap();
+    const double *out = depth.data() + m * npix;
+    for (size_t i = 0; i < npix; ++i) {
+      if (out[i] == -1.0) continue;  // what is not valid comes out as -1, and nothing else does
+      ++r.validPixels;
+      taps += (uint64_t)count[m * npix + i];
+      if (out[i] != smoothed.depths[i]) ++r.changedPixels;
+    }
+    smoothed.depths.assign(out, out + npix);
+    views[m]->SetDepthMap(smoothed);
+  }
+  r.meanTaps = r.validPixels ? (double)taps / (double)r.validPixels : 0.0;
+  if (report) *report = r;
+  return true;
+}
+
+// Not in the reference (recon_host.h)
 bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
                          double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error) {
   const size_t n = views.size();

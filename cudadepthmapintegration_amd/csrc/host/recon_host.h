@@ -143,6 +143,22 @@ struct DepthHolesReport {
 bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long maxPixels, double absTolerance,
                     double relTolerance, int device, DepthHolesReport *report, std::string *error);
 
+// Not in the reference: the views' depths smoothed on the GPU, edges preserved, before they are fused (dmi_smooth_depths,
+// include/dmi.h states the definition).  It works as FillDepthHoles does: every view is thresholded first, all of them are
+// packed, smoothed in place on `device`, and the smoothed depths stored back with SetDepthMap: every valid depth moves to the
+// weighted mean of the valid depths within ceil(truncate * sigma) pixels that differ from it by less than
+// absTolerance + relTolerance * depth, `iterations` times.  No pixel gains or loses its depth, so the best costs are left alone.
+// The cameras are not read.  The views must share one size and have depth maps.
+struct DepthSmoothReport {
+  uint64_t views = 0;
+  uint64_t validPixels = 0;    // the pixels with a depth (before and after: the step changes no validity) ...
+  uint64_t changedPixels = 0;  // ... and the ones whose depth is no longer what it was
+  double meanTaps = 0.0;       // taps taken per valid pixel in the last iteration, the centre included
+  double kernelMs = 0.0;       // hipEvent time of the kernels
+};
+bool SmoothDepths(const std::vector<ReconstructionData *> &views, double thresholdBestCost, double sigma, double truncate,
+                  double absTolerance, double relTolerance, int iterations, int device, DepthSmoothReport *report, std::string *error);
+
 // Not in the reference: the bounds of the scene the views see, along the rows of `axes` (row-major 3 x 3), on the GPU
 // (dmi_estimate_scene_bounds, include/dmi.h states the definition): per axis the coordinate of rank k and of rank N-1-k of the
 // back-projected valid pixels, k = min((uint64_t)(trimFraction * N), (N - 1) / 2), over every pixelStep-th pixel of every

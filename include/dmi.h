@@ -55,7 +55,7 @@ extern "C" {
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
                            *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles;
-                           *    dmi_fill_depth_holes */
+                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths */
 
 typedef struct dmi_context dmi_context;
 
@@ -895,6 +895,60 @@ int dmi_filter_depth_speckles(const double *depth, const double *best_cost, doub
 int dmi_fill_depth_holes(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H,
                          double abs_tolerance, double rel_tolerance, int64_t max_pixels, int32_t device, double *out_depth,
                          int32_t *out_size, double *kernel_ms);
+
+/* ---- Depth maps smoothed, edges preserved, before the maps are fused (added after round 5, dmi_abi_version() stays 5) ----
+ * The bilateral filter that every TSDF pipeline since KinectFusion runs over each depth map first.  The filters above decide
+ * WHETHER a pixel holds a depth; none changes a depth that stays, so per-pixel depth noise goes into the fusion untouched, and a
+ * depth a voxel too far has carved free space that no smoothing of the fused field gives back.  dmi_smooth_depths moves every
+ * valid depth to a weighted mean of the valid depths round it that lie within a tolerance of it: a spatial Gaussian times
+ * Tukey's biweight of the depth difference, written so that it needs no division per tap and no transcendental on the device.
+ * Context-free, like dmi_fill_depth_holes: it uploads, runs its kernel once per iteration, downloads and frees.  It takes no
+ * cameras.
+ *   depth, best_cost, threshold   exactly as dmi_fill_depth_holes takes them: [n][H][W] f64 host in vtk point order, best_cost
+ *             nullable; best cost > threshold gives -1, applied once, before the first iteration
+ *   out_depth [n][H][W] f64 host; may be `depth` itself
+ *   out_count [n][H][W] int32 host or NULL: the taps taken at the pixel in the LAST iteration
+ *   kernel_ms (nullable): hipEvent time of the kernels alone, summed over the pieces
+ * Definition, met bit for bit by the device and by tests/depth_smooth_np.py.  All arithmetic is f64, every operation is rounded
+ * on its own, nothing is contracted; comparisons with a NaN are false.
+ *   Validity.  A pixel is VALID iff D > 0 and D < +inf (step 1 of dmi_filter_depth_speckles).  A pixel that is not valid comes
+ *   out as -1.0, with count 0.  A valid pixel stays valid.
+ *   Spatial weights (dmi_depth_smoothing_weights, host code, no device needed: *radius and weights[0..r], room for 9).
+ *     r = (int)ceil(truncate * sigma)
+ *     s[0] = 1, s[i] = exp(-(double)(i*i) / (2*sigma*sigma)) for i = 1..r
+ *   computed on the host in double and NOT normalised: the quotient below cancels any scale.  r == 0 is legal and gives the
+ *   identity on valid pixels.
+ *   One iteration at a valid centre c:
+ *     tau = abs_tolerance + rel_tolerance * c;   T = tau * tau;   num = 0;  den = 0;  count = 0
+ *     for dy = -r..r (outer), dx = -r..r (inner), tap q inside the image and valid:
+ *         delta = q - c;  u = delta * delta
+ *         if (u < T):
+ *             g = T - u
+ *             w = (s[|dy|] * s[|dx|]) * (g * g)
+ *             num = num + w * delta;  den = den + w;  count += 1
+ *     out = c + num / den
+ *     if !(den > 0 && den < inf && out > 0 && out < inf): out = c
+ *   The test u < T is strict; a tap that fails it adds nothing.  (g * g) is (1 - u/T)^2, Tukey's biweight, up to the factor T^2
+ *   that the quotient cancels.  The division is correctly rounded.  count is the number of taps taken; the centre counts
+ *   whenever T > 0.  Taps never cross a row end or a view seam: a tap outside the image does not exist.
+ *   Iteration k+1 reads the complete output of iteration k.  out_count is the last iteration's.
+ * Consequences: a step higher than tau is not crossed, and plateaus on either side of it come out bit-identical; |out - c| <= tau
+ * per iteration, up to a relative 1e-12; both tolerances zero give the identity.
+ * Every output pixel depends on its iteration's input plane alone and is summed in the one order above, so the result is the
+ * same to the bit whatever order the hardware runs in: two calls give identical bytes.
+ * Host data goes up and comes down in pieces of whole views, as many as fit 256 MiB (a single larger view goes whole).  The device
+ * holds two depth planes of one piece at a time -- 16 bytes per pixel of the piece, 8 more with best_cost, 4 more with out_count.
+ * All arguments are checked before the device is touched.  DMI_ERR_INVALID_ARGUMENT, the message naming the argument: a null depth
+ * or out_depth; n < 1; W or H outside [1, 32768]; a sigma that is not finite or is negative; a truncate outside (0, 4]; a radius
+ * above 8; a negative, NaN or infinite abs_tolerance or rel_tolerance; iterations outside [1, 16]; a NaN threshold when best_cost
+ * is given.  Then DMI_ERR_DEVICE without a device.  A refused call leaves out_depth and out_count untouched.  The call never
+ * exits and never throws; a failure's text is dmi_last_error(NULL)'s.  Synchronises.
+ * dmi_depth_smoothing_weights refuses (DMI_ERR_INVALID_ARGUMENT, nothing written) null pointers and the sigma, truncate and radius
+ * that dmi_smooth_depths refuses. */
+int dmi_depth_smoothing_weights(double sigma, double truncate, int32_t *radius, double *weights /* [9]: s[0]..s[r] */);
+int dmi_smooth_depths(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H,
+                      double sigma, double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations,
+                      int32_t device, double *out_depth, int32_t *out_count, double *kernel_ms);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

@@ -135,6 +135,12 @@ typedef struct dmi_cli_options {
   int64_t depth_fill_holes_max_pixels;   /* --depthFillHolesMaxPixels N: fill depth-map holes of at most N pixels before the fusion; -1: not given */
   double depth_fill_holes_tolerance;     /* --depthFillHolesTolerance (default 0) */
   double depth_fill_holes_rel_tolerance; /* --depthFillHolesRelTolerance (default 0.01) */
+  /* not in the reference (dmi_smooth_depths, dmi.h); appended to the struct: */
+  double depth_smooth_sigma;             /* --depthSmoothSigma S: smooth the depth maps, edges preserved, before the fusion; -1: not given */
+  double depth_smooth_truncate;          /* --depthSmoothTruncate (default 2) */
+  double depth_smooth_tolerance;         /* --depthSmoothTolerance (default 0) */
+  double depth_smooth_rel_tolerance;     /* --depthSmoothRelTolerance (default 0.01) */
+  int64_t depth_smooth_iterations;       /* --depthSmoothIterations (default 1) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
@@ -164,7 +170,8 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
  * are what they are without the flag.  With --depthSpeckleMinPixels N every view is read into memory as with
  * --depthConsistencyMinViews and the depths go through dmi_filter_depth_speckles first of all: the consistency filter, the bounds
  * estimate and the fusion see what it left.  With --depthFillHolesMaxPixels N the depths then go through
- * dmi_fill_depth_holes: behind the speckle filter, in front of the consistency filter, the bounds estimate and the fusion. */
+ * dmi_fill_depth_holes: behind the speckle filter, in front of the consistency filter, the bounds estimate and the fusion.  With
+ * --depthSmoothSigma S they then go through dmi_smooth_depths: behind the hole fill, in front of the same three. */
 int dmi_cli_main(int32_t argc, const char *const *argv);
 
 /* What vtkXMLPolyDataWriter makes of a triangle mesh (rmain:184-187), without VTK: a VTK XML PolyData file in the layout of
