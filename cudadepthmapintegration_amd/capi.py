@@ -401,7 +401,7 @@ class FusionContext:
         self.grid = grid
         self.grid_dtype = grid_dtype
         self.n_voxels = grid.n_voxels
-        self._mesh_counts = None  # (vertices, triangles, kept components) of the context's mesh; None: no mesh (the C side's mesh_valid)
+        self._mesh_counts = None  # (vertices, triangles, kept components) of the context's mesh; None: no extraction has succeeded yet
         rc = self._lib.dmi_create(ctypes.byref(g), ctypes.byref(r), ctypes.byref(o), ctypes.byref(self._h))
         if rc != DMI_OK:
             self._h = ctypes.c_void_p()
@@ -567,7 +567,8 @@ class FusionContext:
         """(vertices [n, 3] f64 world coordinates, triangles [m, 3] int64): marching cubes over the point data at `iso` on the
         device (dmi_extract_isosurface + dmi_download_isosurface; Reconstruction/main.cxx:166-182)."""
         nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._mesh_counts = None    # a failed extraction leaves no mesh
+        # (a refused extraction -- a NaN iso -- leaves the mesh of the last successful one, and these counts with it; one that fails
+        # later leaves no mesh on the C side, which then refuses the downloads itself)
         self._check(self._lib.dmi_extract_isosurface(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
         verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
         tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
@@ -580,8 +581,7 @@ class FusionContext:
         unit normal per vertex from the point data's gradient, in world coordinates (dmi_extract_isosurface_normals +
         dmi_download_isosurface + dmi_download_isosurface_normals)."""
         nv, nt = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        self._mesh_counts = None    # a failed extraction leaves no mesh
-        self._check(self._lib.dmi_extract_isosurface_normals(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
+        self._check(self._lib.dmi_extract_isosurface_normals(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))   # (as above)
         verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
         tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
         normals = np.empty((max(int(nv.value), 1), 3), dtype=np.float32)

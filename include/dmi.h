@@ -285,7 +285,7 @@ int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t 
  *     inside to the outside), by ascending cell id, then table order; degenerate ones (t = 0 or 1) are kept;
  *   - the cells that emit triangles are exactly the dmi_iso_active_cells ids.
  * An empty surface is a success (0 and 0).  DMI_ERR_INVALID_ARGUMENT for a NaN iso, null pointers and a context created
- * with dmi_options.z_first != 0 (a z-slab's lattice has the wrong borders). */
+ * with dmi_options.z_first != 0 (a z-slab's lattice has the wrong borders); a call refused for these leaves the last mesh. */
 int dmi_extract_isosurface(dmi_context *ctx, double iso, uint64_t *n_vertices, uint64_t *n_triangles);
 /* The mesh of the last dmi_extract_isosurface: vertices [n][3] f64 world coordinates, triangles [m][3] int64 vertex ids
  * (vtkIdType).  DMI_ERR_INVALID_ARGUMENT before any successful extraction.  Synchronises. */
