@@ -73,6 +73,18 @@ class InfoC(ctypes.Structure):
                 ("tiled_kernel", ctypes.c_int32), ("device_bytes", ctypes.c_uint64), ("pixels_without_depth", ctypes.c_uint64)]
 
 
+class ViewsInfoC(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("W", ctypes.c_int32), ("H", ctypes.c_int32), ("device", ctypes.c_int32),
+                ("device_bytes", ctypes.c_uint64), ("steps", ctypes.c_uint64), ("h2d_plane_bytes", ctypes.c_uint64),
+                ("d2h_plane_bytes", ctypes.c_uint64), ("last_report_kernel_ms", ctypes.c_double)]
+
+
+class ViewsStepReportC(ctypes.Structure):
+    _fields_ = [("valid_before", ctypes.c_uint64), ("valid_after", ctypes.c_uint64), ("changed", ctypes.c_uint64),
+                ("groups", ctypes.c_uint64), ("groups_kept", ctypes.c_uint64), ("aux_sum", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 class MultiOptionsC(ctypes.Structure):
     _fields_ = [("grid_dtype", ctypes.c_int32), ("depth_storage", ctypes.c_int32), ("kernel_variant", ctypes.c_int32),
                 ("partition", ctypes.c_int32), ("exchange", ctypes.c_int32), ("n_slabs", ctypes.c_int32)]
@@ -125,6 +137,9 @@ ABI_SYMBOLS = [
     "dmi_color_set_render_queue_capacity", "dmi_color_get_render_pass_ms", "dmi_color_get_render_queued_pairs",
     "dmi_filter_depth_consistency", "dmi_estimate_scene_bounds", "dmi_filter_depth_speckles", "dmi_fill_depth_holes",
     "dmi_depth_smoothing_weights", "dmi_smooth_depths",
+    "dmi_views_create", "dmi_views_destroy", "dmi_views_last_error", "dmi_views_add", "dmi_views_clear", "dmi_views_get_info",
+    "dmi_sizeof_views_info", "dmi_views_set_piece_bytes", "dmi_views_filter_speckles", "dmi_views_fill_holes", "dmi_views_smooth",
+    "dmi_views_filter_consistency", "dmi_views_estimate_bounds", "dmi_views_download", "dmi_add_views_from_set",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -298,6 +313,25 @@ def load() -> ctypes.CDLL:
     if hasattr(L, "dmi_smooth_depths"):
         L.dmi_depth_smoothing_weights.argtypes = [dbl, dbl, ctypes.POINTER(i32), dp]
         L.dmi_smooth_depths.argtypes = [dp, dp, dbl, i32, i32, i32, dbl, dbl, dbl, dbl, i32, i32, dp, i32p, dp]
+    if hasattr(L, "dmi_views_create"):
+        rp = ctypes.POINTER(ViewsStepReportC)
+        L.dmi_views_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]
+        L.dmi_views_destroy.argtypes = [vp]
+        L.dmi_views_destroy.restype = None
+        L.dmi_views_last_error.argtypes = [vp]
+        L.dmi_views_last_error.restype = ctypes.c_char_p
+        L.dmi_views_add.argtypes = [vp, dp, dp, dbl, dp, dp, i32]
+        L.dmi_views_clear.argtypes = [vp]
+        L.dmi_views_get_info.argtypes = [vp, ctypes.POINTER(ViewsInfoC)]
+        L.dmi_sizeof_views_info.restype = ctypes.c_size_t
+        L.dmi_views_set_piece_bytes.argtypes = [vp, ctypes.c_uint64]
+        L.dmi_views_filter_speckles.argtypes = [vp, dbl, dbl, i64, i32p, rp]
+        L.dmi_views_fill_holes.argtypes = [vp, dbl, dbl, i64, i32p, rp]
+        L.dmi_views_smooth.argtypes = [vp, dbl, dbl, dbl, dbl, i32, i32p, rp]
+        L.dmi_views_filter_consistency.argtypes = [vp, dbl, dbl, i32, i32p, rp]
+        L.dmi_views_estimate_bounds.argtypes = [vp, dp, dbl, i32, dp, dp, ctypes.POINTER(ctypes.c_uint64), dp]
+        L.dmi_views_download.argtypes = [vp, i32, i32, dp]
+        L.dmi_add_views_from_set.argtypes = [vp, vp, i32, i32]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -448,6 +482,14 @@ class FusionContext:
         self._check(self._lib.dmi_add_views(self._h, _dp(d), _dp(bc) if bc is not None else None,
                                             float(threshold) if threshold is not None else 0.0,
                                             _dp(K4), _dp(RT4), n, W, H))
+
+    def add_views_from_set(self, view_set: "ViewSet", first: int | None = None, count: int | None = None):
+        """Append views [first, first + count) of a resident ViewSet (all of them by default) as add_views would append their
+        downloaded depths: the upload pass reads the set's planes on the device, nothing passes through the host, and the set
+        stays as it is (dmi_add_views_from_set)."""
+        first = 0 if first is None else int(first)
+        count = view_set.info().n - first if count is None else int(count)
+        self._check(self._lib.dmi_add_views_from_set(self._h, view_set._h, first, count))
 
     def clear_views(self):
         self._check(self._lib.dmi_clear_views(self._h))
@@ -1260,6 +1302,119 @@ def estimate_scene_bounds(views: Views, *, trim_fraction: float = 0.0, pixel_ste
     return lo, hi, int(count.value), float(ms.value)
 
 
+class ViewSet:
+    """Depth maps resident on the device from the first filter to the fusion (dmi_views_create ... dmi_views_destroy;
+    include/dmi.h states the definition).  add() uploads once; every step replaces the set's depths by exactly what the
+    context-free function of the same name returns for them, and returns its report -- computed on the device -- as a dict;
+    FusionContext.add_views_from_set hands the depths over without a host copy."""
+
+    def __init__(self, W: int, H: int, device: int = 0):
+        self._lib = load()
+        self._h = ctypes.c_void_p()
+        self.W, self.H = int(W), int(H)
+        rc = self._lib.dmi_views_create(int(device), self.W, self.H, ctypes.byref(self._h))
+        if rc != DMI_OK:
+            self._h = ctypes.c_void_p()
+            raise DmiError(rc, self._lib.dmi_views_last_error(None).decode())
+
+    def _check(self, rc):
+        if rc != DMI_OK:
+            raise DmiError(rc, self._lib.dmi_views_last_error(self._h).decode())
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._lib.dmi_views_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, views: Views, threshold: float | None = None):
+        """Append views (depth [n, H, W] f64 in vtk row order, K4 / RT4 [n, 4, 4]).  threshold applies views.best_cost (best cost >
+        threshold => -1), here and once: the costs are not kept."""
+        d = np.ascontiguousarray(views.depth, dtype=np.float64)
+        if d.ndim != 3 or d.shape[1:] != (self.H, self.W):
+            raise ValueError(f"views.depth must be [n, {self.H}, {self.W}], got {d.shape}")
+        n = d.shape[0]
+        k = np.ascontiguousarray(views.K4, dtype=np.float64).reshape(-1)
+        rt = np.ascontiguousarray(views.RT4, dtype=np.float64).reshape(-1)
+        if k.size != 16 * n or rt.size != 16 * n:
+            raise ValueError("views.K4 and views.RT4 must be [n, 4, 4]")
+        bc = None
+        if threshold is not None and views.best_cost is not None:
+            bc = np.ascontiguousarray(views.best_cost, dtype=np.float64)
+            if bc.shape != d.shape:
+                raise ValueError("views.best_cost must have the shape of views.depth")
+        self._check(self._lib.dmi_views_add(self._h, _dp(d), None if bc is None else _dp(bc), 0.0 if threshold is None else float(threshold),
+                                            _dp(k), _dp(rt), n))
+
+    def clear(self):
+        self._check(self._lib.dmi_views_clear(self._h))
+
+    def set_piece_bytes(self, n_bytes: int):
+        """Bound the f64 planes of the views a pass works on at a time (whole views, at least one).  No result depends on it."""
+        self._check(self._lib.dmi_views_set_piece_bytes(self._h, int(n_bytes)))
+
+    def info(self) -> ViewsInfoC:
+        out = ViewsInfoC()
+        self._check(self._lib.dmi_views_get_info(self._h, ctypes.byref(out)))
+        return out
+
+    def _step(self, call, args, return_aux):
+        aux = np.zeros((self.info().n, self.H, self.W), dtype=np.int32) if return_aux else None
+        r = ViewsStepReportC()
+        self._check(call(self._h, *args, None if aux is None else aux.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(r)))
+        report = {name: getattr(r, name) for name, _ in ViewsStepReportC._fields_}
+        return (report, aux) if return_aux else report
+
+    def filter_speckles(self, *, min_pixels: int, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0, return_aux: bool = False):
+        """filter_depth_speckles on the set's depths.  Returns the report, and the sizes int32 [n, H, W] with return_aux."""
+        return self._step(self._lib.dmi_views_filter_speckles, (float(abs_tolerance), float(rel_tolerance), int(min_pixels)), return_aux)
+
+    def fill_holes(self, *, max_pixels: int, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0, return_aux: bool = False):
+        """fill_depth_holes on the set's depths.  Returns the report, and the hole sizes int32 [n, H, W] with return_aux."""
+        return self._step(self._lib.dmi_views_fill_holes, (float(abs_tolerance), float(rel_tolerance), int(max_pixels)), return_aux)
+
+    def smooth(self, *, sigma: float, truncate: float = 2.0, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0, iterations: int = 1,
+               return_aux: bool = False):
+        """smooth_depths on the set's depths.  Returns the report, and the last pass's tap counts int32 [n, H, W] with return_aux."""
+        return self._step(self._lib.dmi_views_smooth, (float(sigma), float(truncate), float(abs_tolerance), float(rel_tolerance),
+                                                       int(iterations)), return_aux)
+
+    def filter_consistency(self, *, min_views: int, abs_tolerance: float = 0.0, rel_tolerance: float = 0.0, return_aux: bool = False):
+        """filter_depth_consistency on the set's depths.  Returns the report, and the counts int32 [n, H, W] with return_aux."""
+        return self._step(self._lib.dmi_views_filter_consistency, (float(abs_tolerance), float(rel_tolerance), int(min_views)), return_aux)
+
+    def estimate_bounds(self, *, trim_fraction: float = 0.0, pixel_step: int = 1, axes=None):
+        """estimate_scene_bounds on the set's depths: (lo [3] f64, hi [3] f64, the number of points, the kernels' time in ms)."""
+        a = None
+        if axes is not None:
+            a = np.ascontiguousarray(axes, dtype=np.float64).reshape(-1)
+            if a.size != 9:
+                raise ValueError("axes must be 3 x 3")
+        lo, hi = np.zeros(3, dtype=np.float64), np.zeros(3, dtype=np.float64)
+        count, ms = ctypes.c_uint64(0), ctypes.c_double(0.0)
+        self._check(self._lib.dmi_views_estimate_bounds(self._h, None if a is None else _dp(a), float(trim_fraction), int(pixel_step),
+                                                        _dp(lo), _dp(hi), ctypes.byref(count), ctypes.byref(ms)))
+        return lo, hi, int(count.value), float(ms.value)
+
+    def download(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """The set's depths of views [first, first + count) (all from `first` on by default), [count, H, W] f64 in vtk row order."""
+        count = self.info().n - int(first) if count is None else int(count)
+        out = np.empty((max(count, 0), self.H, self.W), dtype=np.float64)
+        self._check(self._lib.dmi_views_download(self._h, int(first), count, _dp(out)))
+        return out
+
+
 class ColorContext:
     """MeshColoration with resident views (dmi_color_create ... dmi_color_destroy)."""
 
@@ -1624,7 +1779,7 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_fill_holes_rel_tolerance", ctypes.c_double),
                 ("depth_smooth_sigma", ctypes.c_double), ("depth_smooth_truncate", ctypes.c_double),
                 ("depth_smooth_tolerance", ctypes.c_double), ("depth_smooth_rel_tolerance", ctypes.c_double),
-                ("depth_smooth_iterations", ctypes.c_int64)]
+                ("depth_smooth_iterations", ctypes.c_int64), ("depth_staged_filters", ctypes.c_int32)]
 
 
 def cli_read_arguments(args):

@@ -273,12 +273,11 @@ __global__ __launch_bounds__(kBlock) void holes_output_kernel(HolesPiece piece, 
     const int64_t size = (int64_t)rules::record_count(word);
     if (piece.out_size) piece.out_size[base + at] = (int32_t)size;
     double value = -1.0;
-    bool fillable = size <= max_pixels && !rules::record_touches_border(word);
-    if (fillable) {  // step 4: the product, then the sum, then the difference, each rounded on its own (-ffp-contract=off)
+    bool fillable = size <= max_pixels && !rules::record_touches_border(word);  // (the rim is read for these holes only)
+    if (fillable) {  // step 4: depth_holes_rules.h
       const uint64_t lo_bits = piece.rim_lo[base + g], hi_bits = piece.rim_hi[base + g];
-      const double lo = __longlong_as_double((long long)lo_bits), hi = __longlong_as_double((long long)hi_bits);
-      const double bound = abs_tolerance + rel_tolerance * lo;
-      fillable = lo_bits != rules::kNoRimLo && hi - lo <= bound;
+      fillable = rules::fillable(word, lo_bits != rules::kNoRimLo, __longlong_as_double((long long)lo_bits),
+                                 __longlong_as_double((long long)hi_bits), max_pixels, abs_tolerance, rel_tolerance);
     }
     if (fillable) {
       const int below = rules::nearest_valid_below(valid, lane), above = rules::nearest_valid_above(valid, lane);

@@ -41,6 +41,16 @@ DMI_SPECKLE_HD inline int nearest_valid_above(uint64_t valid, int lane) {
   return above ? lane + 1 + speckle_rules::count_trailing_zeros64(above) : 64;
 }
 
+// Step 4 of the definition at a hole's final root: `word` is its record, lo and hi the smallest and largest depth on its rim
+// (has_rim: it has one).  The product, then the sum, then the difference, each rounded on its own (-ffp-contract=off).  The output
+// pass asks this per hole pixel, the resident view set's report (view_set_kernels.hip) once per hole.
+DMI_SPECKLE_HD inline bool fillable(uint32_t word, bool has_rim, double lo, double hi, int64_t max_pixels, double abs_tolerance,
+                                    double rel_tolerance) {
+  if ((int64_t)record_count(word) > max_pixels || record_touches_border(word) || !has_rim) return false;
+  const double bound = abs_tolerance + rel_tolerance * lo;
+  return hi - lo <= bound;
+}
+
 // A pixel of a fillable hole reaches its nearest valid pixel in a row or column within SIZE <= max_pixels steps, and within the
 // image: the walk makes at most this many.
 DMI_SPECKLE_HD inline int64_t walk_limit(int64_t max_pixels, int32_t extent) { return max_pixels < extent ? max_pixels : extent; }

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dmi_context.h"
+#include "dmi_view_set.h"
 #include "scene_bounds.h"
 
 namespace {
@@ -56,20 +57,9 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
   if (!(trim_fraction >= 0.0 && trim_fraction <= 0.5)) return bad("trim_fraction must lie in [0, 0.5]");  // false for NaN
   if (pixel_step < 1) return bad("pixel_step >= 1 required");
   if (best_cost && threshold != threshold) return bad("threshold is NaN");
-  dmi::BoundsAxes axes = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
-  if (axes9)
-    for (int q = 0; q < 9; ++q) {
-      if (!std::isfinite(axes9[q])) return bad("axes9 holds a value that is not finite");
-      axes.a[q] = axes9[q];
-    }
-  for (int32_t m = 0; m < n; ++m) {
-    const double *K = K4 + 16 * (size_t)m;
-    const bool form = K[4] == 0.0 && K[8] == 0.0 && K[9] == 0.0 && K[10] == 1.0 && K[11] == 0.0 && K[0] != 0.0 && K[5] != 0.0 &&
-                      K[0] == K[0] && K[5] == K[5];
-    if (!form)
-      return bad("K4 of view " + std::to_string(m) + " is not of the form SetMatrixK produces (K4[1][0] == 0, third row 0 0 1 0, "
-                 "non-zero K4[0][0] and K4[1][1])");
-  }
+  dmi::BoundsAxes axes;
+  if (!dmi::bounds_axes(axes9, &axes)) return bad("axes9 holds a value that is not finite");
+  if (const int32_t m = dmi::first_view_with_other_k(K4, n); m >= 0) return bad(dmi::other_k_message(m));
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -81,11 +71,7 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
   int compute_units = 0;
   DMI_SB_HIP(hipDeviceGetAttribute(&compute_units, hipDeviceAttributeMultiprocessorCount, device));
 
-  dmi::BoundsTuning tuning;
-#ifdef DMI_TUNING
-  if (const char *v = getenv("DMI_SB_AGGREGATE_ROUNDS")) tuning.aggregate_rounds = atoi(v);
-  if (const char *v = getenv("DMI_SB_SHARE_HISTOGRAMS")) tuning.share_histograms = atoi(v);
-#endif
+  const dmi::BoundsTuning tuning = dmi::bounds_tuning_from_environment();
 
   Holdings h;
   DMI_SB_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
@@ -109,13 +95,7 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
   };
 
   {
-    std::vector<dmi::ConsistencyCamera> cameras(views);
-    for (size_t m = 0; m < views; ++m) {
-      const double *K = K4 + 16 * m, *RT = RT4 + 16 * m;
-      for (int q = 0; q < 12; ++q) cameras[m].rt[q] = RT[q];
-      const double k[8] = {K[0], K[1], K[2], K[3], K[5], K[6], K[7], 0.0};
-      for (int q = 0; q < 8; ++q) cameras[m].k[q] = k[q];
-    }
+    const std::vector<dmi::ConsistencyCamera> cameras = dmi::consistency_cameras(K4, RT4, views);
     DMI_SB_HIP(hipMemcpyAsync(h.cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, h.stream));
     DMI_SB_HIP(hipStreamSynchronize(h.stream));  // `cameras` goes out of scope
   }
@@ -137,19 +117,10 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
   }
 
   // the select: count and select, pass after pass, with no host round trip in between
-  dmi::BoundsState *state = h.state.as<dmi::BoundsState>();
-  unsigned long long *hist = h.hist.as<unsigned long long>();
-  const unsigned blocks = dmi::bounds_count_blocks(n, W, H, pixel_step, compute_units);
-  DMI_SB_HIP(hipEventRecord(h.events[0], h.stream));
-  for (int pass = 0; pass < dmi::bounds_rules::kPasses; ++pass) {
-    DMI_SB_HIP(dmi::launch_bounds_count(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, pixel_step, axes, pass,
-                                        state, hist, blocks, tuning, h.stream));
-    DMI_SB_HIP(dmi::launch_bounds_select(state, hist, pass, trim_fraction, h.stream));
-  }
-  DMI_SB_HIP(hipEventRecord(h.events[1], h.stream));
   dmi::BoundsState result;
-  DMI_SB_HIP(hipMemcpyAsync(&result, state, sizeof(result), hipMemcpyDeviceToHost, h.stream));
-  DMI_SB_HIP(hipStreamSynchronize(h.stream));
+  DMI_SB_HIP(dmi::run_bounds_select(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, pixel_step, axes, trim_fraction,
+                                    h.state.as<dmi::BoundsState>(), h.hist.as<unsigned long long>(), compute_units, tuning, h.stream,
+                                    h.events, &result));
   DMI_SB_HIP(add_span());
 #ifdef DMI_TUNING
   {
@@ -179,6 +150,48 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
 }
 
 }  // namespace
+
+namespace dmi {
+
+bool bounds_axes(const double *axes9, BoundsAxes *out) {
+  *out = BoundsAxes{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+  if (axes9)
+    for (int q = 0; q < 9; ++q) {
+      if (!std::isfinite(axes9[q])) return false;
+      out->a[q] = axes9[q];
+    }
+  return true;
+}
+
+BoundsTuning bounds_tuning_from_environment() {
+  BoundsTuning tuning;
+#ifdef DMI_TUNING
+  if (const char *v = getenv("DMI_SB_AGGREGATE_ROUNDS")) tuning.aggregate_rounds = atoi(v);
+  if (const char *v = getenv("DMI_SB_SHARE_HISTOGRAMS")) tuning.share_histograms = atoi(v);
+#endif
+  return tuning;
+}
+
+// The select on the n resident planes (image row order; state and hist zeroed): count and select, pass after pass, with no host
+// round trip in between, between two events; then the state comes down and the stream is synchronised.  What
+// dmi_estimate_scene_bounds runs behind its upload passes, and the resident view set (dmi_capi_viewset.hip) on the planes it has
+// flipped.
+hipError_t run_bounds_select(const double *planes, const ConsistencyCamera *cameras, int32_t n, int32_t W, int32_t H, int32_t pixel_step,
+                             const BoundsAxes &axes, double trim_fraction, BoundsState *state, unsigned long long *hist, int compute_units,
+                             const BoundsTuning &tuning, hipStream_t stream, hipEvent_t events[2], BoundsState *result) {
+  const unsigned blocks = bounds_count_blocks(n, W, H, pixel_step, compute_units);
+  hipError_t e = hipEventRecord(events[0], stream);
+  for (int pass = 0; e == hipSuccess && pass < bounds_rules::kPasses; ++pass) {
+    e = launch_bounds_count(planes, cameras, n, W, H, pixel_step, axes, pass, state, hist, blocks, tuning, stream);
+    if (e == hipSuccess) e = launch_bounds_select(state, hist, pass, trim_fraction, stream);
+  }
+  if (e == hipSuccess) e = hipEventRecord(events[1], stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(result, state, sizeof(*result), hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  return e;
+}
+
+}  // namespace dmi
 
 extern "C" {
 

@@ -10,6 +10,7 @@
 
 #include "depth_consistency.h"
 #include "dmi_context.h"
+#include "dmi_view_set.h"
 
 namespace {
 
@@ -55,14 +56,7 @@ int filter(const double *depth, const double *best_cost, double threshold, const
   if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
   if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
   if (best_cost && threshold != threshold) return bad("threshold is NaN");
-  for (int32_t m = 0; m < n; ++m) {
-    const double *K = K4 + 16 * (size_t)m;
-    const bool form = K[4] == 0.0 && K[8] == 0.0 && K[9] == 0.0 && K[10] == 1.0 && K[11] == 0.0 && K[0] != 0.0 && K[5] != 0.0 &&
-                      K[0] == K[0] && K[5] == K[5];
-    if (!form)
-      return bad("K4 of view " + std::to_string(m) + " is not of the form SetMatrixK produces (K4[1][0] == 0, third row 0 0 1 0, "
-                 "non-zero K4[0][0] and K4[1][1])");
-  }
+  if (const int32_t m = dmi::first_view_with_other_k(K4, n); m >= 0) return bad(dmi::other_k_message(m));
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -72,11 +66,7 @@ int filter(const double *depth, const double *best_cost, double threshold, const
   if (device < 0 || device >= ndev) return bad("device ordinal out of range");
   DMI_DC_HIP(hipSetDevice(device));
 
-  dmi::ConsistencyTuning tuning;
-#ifdef DMI_TUNING
-  if (const char *v = getenv("DMI_DC_VIEW_GROUP")) tuning.view_group = atoi(v);
-  if (const char *v = getenv("DMI_DC_GATHER_AHEAD")) tuning.gather_ahead = atoi(v);
-#endif
+  const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
 
   Holdings h;
   DMI_DC_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
@@ -105,13 +95,7 @@ int filter(const double *depth, const double *best_cost, double threshold, const
   };
 
   {
-    std::vector<dmi::ConsistencyCamera> cameras(views);
-    for (size_t m = 0; m < views; ++m) {
-      const double *K = K4 + 16 * m, *RT = RT4 + 16 * m;
-      for (int q = 0; q < 12; ++q) cameras[m].rt[q] = RT[q];
-      const double k[8] = {K[0], K[1], K[2], K[3], K[5], K[6], K[7], 0.0};
-      for (int q = 0; q < 8; ++q) cameras[m].k[q] = k[q];
-    }
+    const std::vector<dmi::ConsistencyCamera> cameras = dmi::consistency_cameras(K4, RT4, views);
     DMI_DC_HIP(hipMemcpyAsync(h.cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, h.stream));
     DMI_DC_HIP(hipStreamSynchronize(h.stream));  // `cameras` goes out of scope
   }
@@ -133,13 +117,8 @@ int filter(const double *depth, const double *best_cost, double threshold, const
 
   // the counts: every source pixel against the target views, all in one launch or group by group
   if (n > 1) {
-    const int group = tuning.view_group > 0 ? tuning.view_group : n;
-    DMI_DC_HIP(hipEventRecord(h.events[0], h.stream));
-    for (int t0 = 0; t0 < n; t0 += group)
-      DMI_DC_HIP(dmi::launch_consistency_count(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, t0,
-                                               std::min(n, t0 + group), abs_tolerance, rel_tolerance, tuning.gather_ahead,
-                                               h.counts.as<int32_t>(), undecided, h.stream));
-    DMI_DC_HIP(hipEventRecord(h.events[1], h.stream));
+    DMI_DC_HIP(dmi::run_consistency_count(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
+                                          rel_tolerance, tuning, h.counts.as<int32_t>(), undecided, h.stream, h.events));
     DMI_DC_HIP(hipStreamSynchronize(h.stream));
     DMI_DC_HIP(add_span());
   }
@@ -165,6 +144,60 @@ int filter(const double *depth, const double *best_cost, double threshold, const
 }
 
 }  // namespace
+
+namespace dmi {
+
+int32_t first_view_with_other_k(const double *K4, int32_t n) {
+  for (int32_t m = 0; m < n; ++m) {
+    const double *K = K4 + 16 * (size_t)m;
+    const bool form = K[4] == 0.0 && K[8] == 0.0 && K[9] == 0.0 && K[10] == 1.0 && K[11] == 0.0 && K[0] != 0.0 && K[5] != 0.0 &&
+                      K[0] == K[0] && K[5] == K[5];
+    if (!form) return m;
+  }
+  return -1;
+}
+
+std::string other_k_message(int32_t m) {
+  return "K4 of view " + std::to_string(m) + " is not of the form SetMatrixK produces (K4[1][0] == 0, third row 0 0 1 0, "
+         "non-zero K4[0][0] and K4[1][1])";
+}
+
+std::vector<ConsistencyCamera> consistency_cameras(const double *K4, const double *RT4, size_t views) {
+  std::vector<ConsistencyCamera> cameras(views);
+  for (size_t m = 0; m < views; ++m) {
+    const double *K = K4 + 16 * m, *RT = RT4 + 16 * m;
+    for (int q = 0; q < 12; ++q) cameras[m].rt[q] = RT[q];
+    const double k[8] = {K[0], K[1], K[2], K[3], K[5], K[6], K[7], 0.0};
+    for (int q = 0; q < 8; ++q) cameras[m].k[q] = k[q];
+  }
+  return cameras;
+}
+
+ConsistencyTuning consistency_tuning_from_environment() {
+  ConsistencyTuning tuning;
+#ifdef DMI_TUNING
+  if (const char *v = getenv("DMI_DC_VIEW_GROUP")) tuning.view_group = atoi(v);
+  if (const char *v = getenv("DMI_DC_GATHER_AHEAD")) tuning.gather_ahead = atoi(v);
+#endif
+  return tuning;
+}
+
+// The counts of every source pixel of the n resident planes (image row order, zeroed counts) against the target views, all in one
+// launch or group by group, between two events.  What dmi_filter_depth_consistency runs between its upload and its finish passes,
+// and the resident view set (dmi_capi_viewset.hip) on the planes it has flipped.  n > 1.
+hipError_t run_consistency_count(const double *planes, const ConsistencyCamera *cameras, int32_t n, int32_t W, int32_t H,
+                                 double abs_tolerance, double rel_tolerance, const ConsistencyTuning &tuning, int32_t *counts,
+                                 unsigned long long *undecided, hipStream_t stream, hipEvent_t events[2]) {
+  const int group = tuning.view_group > 0 ? tuning.view_group : n;
+  hipError_t e = hipEventRecord(events[0], stream);
+  for (int t0 = 0; e == hipSuccess && t0 < n; t0 += group)
+    e = launch_consistency_count(planes, cameras, n, W, H, t0, std::min(n, t0 + group), abs_tolerance, rel_tolerance, tuning.gather_ahead,
+                                 counts, undecided, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[1], stream);
+  return e;
+}
+
+}  // namespace dmi
 
 extern "C" {
 

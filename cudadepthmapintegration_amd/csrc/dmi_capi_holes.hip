@@ -7,6 +7,7 @@
 
 #include "depth_holes.h"
 #include "dmi_context.h"
+#include "dmi_view_set.h"
 
 namespace {
 
@@ -91,15 +92,7 @@ int fill(const double *depth, const double *best_cost, double threshold, int32_t
     DMI_DH_HIP(hipMemcpyAsync(h.depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
     if (best_cost)
       DMI_DH_HIP(hipMemcpyAsync(h.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    DMI_DH_HIP(hipEventRecord(h.events[0], h.stream));
-    DMI_DH_HIP(dmi::launch_holes_local(piece, threshold, W, H, h.stream));
-    DMI_DH_HIP(hipEventRecord(h.events[1], h.stream));
-    DMI_DH_HIP(dmi::launch_holes_border(piece, W, H, h.stream));
-    DMI_DH_HIP(hipEventRecord(h.events[2], h.stream));
-    DMI_DH_HIP(dmi::launch_holes_merge(piece, W, H, h.stream));
-    DMI_DH_HIP(hipEventRecord(h.events[3], h.stream));
-    DMI_DH_HIP(dmi::launch_holes_output(piece, W, H, abs_tolerance, rel_tolerance, max_pixels, h.stream));
-    DMI_DH_HIP(hipEventRecord(h.events[4], h.stream));
+    DMI_DH_HIP(dmi::run_holes_piece(piece, threshold, W, H, abs_tolerance, rel_tolerance, max_pixels, h.stream, h.events));
     DMI_DH_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
     if (out_size)
       DMI_DH_HIP(hipMemcpyAsync(out_size + m0 * plane, h.out_size.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
@@ -118,6 +111,26 @@ int fill(const double *depth, const double *best_cost, double threshold, int32_t
 }
 
 }  // namespace
+
+namespace dmi {
+
+// The fill on the device planes of one piece: the four passes, an event before the first and one behind each.  What
+// dmi_fill_depth_holes runs between its copies, and the resident view set (dmi_capi_viewset.hip) on its own planes.
+hipError_t run_holes_piece(const HolesPiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
+                           int64_t max_pixels, hipStream_t stream, hipEvent_t events[5]) {
+  hipError_t e = hipEventRecord(events[0], stream);
+  if (e == hipSuccess) e = launch_holes_local(piece, threshold, W, H, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[1], stream);
+  if (e == hipSuccess) e = launch_holes_border(piece, W, H, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[2], stream);
+  if (e == hipSuccess) e = launch_holes_merge(piece, W, H, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[3], stream);
+  if (e == hipSuccess) e = launch_holes_output(piece, W, H, abs_tolerance, rel_tolerance, max_pixels, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[4], stream);
+  return e;
+}
+
+}  // namespace dmi
 
 extern "C" {
 

@@ -7,6 +7,7 @@
 
 #include "depth_smooth.h"
 #include "dmi_context.h"
+#include "dmi_view_set.h"
 
 namespace {
 
@@ -79,16 +80,12 @@ int smooth(const double *depth, const double *best_cost, double threshold, int32
     DMI_DS_HIP(hipMemcpyAsync(h.plane[0].ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
     if (best_cost)
       DMI_DS_HIP(hipMemcpyAsync(h.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    DMI_DS_HIP(hipEventRecord(h.events[0], h.stream));
-    int from = 0;  // iteration k + 1 reads the complete output of iteration k: the two planes take turns
-    for (int32_t k = 0; k < iterations; ++k, from ^= 1) {
-      const bool first = k == 0, last = k + 1 == iterations;
-      DMI_DS_HIP(dmi::launch_depth_smooth(h.plane[from].as<double>(), first && best_cost ? h.cost.as<double>() : nullptr, threshold,
-                                          h.plane[from ^ 1].as<double>(), last && out_count ? h.count.as<int32_t>() : nullptr,
-                                          (int64_t)cnt, W, H, args, h.stream));
-    }
-    DMI_DS_HIP(hipEventRecord(h.events[1], h.stream));
-    DMI_DS_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.plane[from].ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    // iteration k + 1 reads the complete output of iteration k: the two planes take turns
+    const double *result = nullptr;
+    DMI_DS_HIP(dmi::run_smooth_piece(h.plane[0].as<double>(), best_cost ? h.cost.as<double>() : nullptr, threshold, h.plane[1].as<double>(),
+                                     h.plane[0].as<double>(), out_count ? h.count.as<int32_t>() : nullptr, (int64_t)cnt, W, H, args,
+                                     iterations, h.stream, h.events, &result));
+    DMI_DS_HIP(hipMemcpyAsync(out_depth + m0 * plane, result, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
     if (out_count)
       DMI_DS_HIP(hipMemcpyAsync(out_count + m0 * plane, h.count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
     DMI_DS_HIP(hipStreamSynchronize(h.stream));  // the planes are reused by the next piece
@@ -101,6 +98,30 @@ int smooth(const double *depth, const double *best_cost, double threshold, int32
 }
 
 }  // namespace
+
+namespace dmi {
+
+// The smoothing on the device planes of one piece: `iterations` launches between an event before the first and one behind the last.
+// The first reads src (with cost, nullable, and the threshold) and writes ping, the second reads ping and writes pong, and so on in
+// turns; *result is the one the last wrote, count (nullable) the last one's taps.  pong may be src: dmi_smooth_depths alternates
+// between its two planes.  The resident view set (dmi_capi_viewset.hip) keeps src as it is.
+hipError_t run_smooth_piece(const double *src, const double *cost, double threshold, double *ping, double *pong, int32_t *count,
+                            int64_t views, int32_t W, int32_t H, const SmoothArgs &args, int32_t iterations, hipStream_t stream,
+                            hipEvent_t events[2], const double **result) {
+  hipError_t e = hipEventRecord(events[0], stream);
+  const double *from = src;
+  for (int32_t k = 0; e == hipSuccess && k < iterations; ++k) {
+    const bool first = k == 0, last = k + 1 == iterations;
+    double *const to = k % 2 == 0 ? ping : pong;
+    e = launch_depth_smooth(from, first ? cost : nullptr, threshold, to, last ? count : nullptr, views, W, H, args, stream);
+    from = to;
+  }
+  if (e == hipSuccess) e = hipEventRecord(events[1], stream);
+  *result = from;
+  return e;
+}
+
+}  // namespace dmi
 
 extern "C" {
 

@@ -9,6 +9,7 @@
 
 #include "depth_speckle.h"
 #include "dmi_context.h"
+#include "dmi_view_set.h"
 
 namespace {
 
@@ -60,11 +61,7 @@ int filter(const double *depth, const double *best_cost, double threshold, int32
   if (device < 0 || device >= ndev) return bad("device ordinal out of range");
   DMI_DS_HIP(hipSetDevice(device));
 
-  dmi::SpeckleTuning tuning;
-#ifdef DMI_TUNING
-  if (const char *v = getenv("DMI_DS_TILE_HEIGHT")) tuning.tile_height = atoi(v);
-  if (const char *v = getenv("DMI_DS_RUNS")) tuning.runs = atoi(v) != 0;
-#endif
+  const dmi::SpeckleTuning tuning = dmi::speckle_tuning_from_environment();
 
   Holdings h;
   DMI_DS_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
@@ -95,15 +92,7 @@ int filter(const double *depth, const double *best_cost, double threshold, int32
     DMI_DS_HIP(hipMemcpyAsync(h.depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
     if (best_cost)
       DMI_DS_HIP(hipMemcpyAsync(h.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    DMI_DS_HIP(hipEventRecord(h.events[0], h.stream));
-    DMI_DS_HIP(dmi::launch_speckle_local(piece, threshold, W, H, abs_tolerance, rel_tolerance, tuning, h.stream));
-    DMI_DS_HIP(hipEventRecord(h.events[1], h.stream));
-    DMI_DS_HIP(dmi::launch_speckle_border(piece, W, H, tuning, h.stream));
-    DMI_DS_HIP(hipEventRecord(h.events[2], h.stream));
-    DMI_DS_HIP(dmi::launch_speckle_sizes(piece, W, H, h.stream));
-    DMI_DS_HIP(hipEventRecord(h.events[3], h.stream));
-    DMI_DS_HIP(dmi::launch_speckle_output(piece, W, H, min_pixels, h.stream));
-    DMI_DS_HIP(hipEventRecord(h.events[4], h.stream));
+    DMI_DS_HIP(dmi::run_speckle_piece(piece, threshold, W, H, abs_tolerance, rel_tolerance, min_pixels, tuning, h.stream, h.events));
     DMI_DS_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
     if (out_size)
       DMI_DS_HIP(hipMemcpyAsync(out_size + m0 * plane, h.out_size.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
@@ -122,6 +111,35 @@ int filter(const double *depth, const double *best_cost, double threshold, int32
 }
 
 }  // namespace
+
+namespace dmi {
+
+// The filter on the device planes of one piece: the four passes, an event before the first and one behind each.  What
+// dmi_filter_depth_speckles runs between its copies, and the resident view set (dmi_capi_viewset.hip) on its own planes.
+hipError_t run_speckle_piece(const SpecklePiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
+                             int64_t min_pixels, const SpeckleTuning &tuning, hipStream_t stream, hipEvent_t events[5]) {
+  hipError_t e = hipEventRecord(events[0], stream);
+  if (e == hipSuccess) e = launch_speckle_local(piece, threshold, W, H, abs_tolerance, rel_tolerance, tuning, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[1], stream);
+  if (e == hipSuccess) e = launch_speckle_border(piece, W, H, tuning, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[2], stream);
+  if (e == hipSuccess) e = launch_speckle_sizes(piece, W, H, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[3], stream);
+  if (e == hipSuccess) e = launch_speckle_output(piece, W, H, min_pixels, stream);
+  if (e == hipSuccess) e = hipEventRecord(events[4], stream);
+  return e;
+}
+
+SpeckleTuning speckle_tuning_from_environment() {
+  SpeckleTuning tuning;
+#ifdef DMI_TUNING
+  if (const char *v = getenv("DMI_DS_TILE_HEIGHT")) tuning.tile_height = atoi(v);
+  if (const char *v = getenv("DMI_DS_RUNS")) tuning.runs = atoi(v) != 0;
+#endif
+  return tuning;
+}
+
+}  // namespace dmi
 
 extern "C" {
 

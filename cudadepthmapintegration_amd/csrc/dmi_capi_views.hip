@@ -4,6 +4,7 @@
 // make_view_records, this file sets their device pointers.  The context it works on is dmi_context.h's; dmi_capi.hip has the
 // context's life cycle and the shared helpers.
 #include "dmi_context.h"
+#include "dmi_view_set.h"
 
 #include <chrono>
 #include <cstring>
@@ -63,8 +64,10 @@ int promote_to_f64(dmi_context *ctx) {
 
 // Uploads n maps (host f64 or f32) into a new batch buffer of the current storage type.
 // Returns the number of lossy f32 conversions through *lossy_out.
+// on_device: depth64 is device memory the upload stream may read now (a view set's planes, dmi_add_views_from_set): the upload
+// pass reads it where it is, nothing is staged.
 int upload_batch(dmi_context *ctx, const double *depth64, const float *depth32, const double *best_cost,
-                 double threshold, int32_t n, Batch *out, unsigned long long *lossy_out) {
+                 double threshold, int32_t n, Batch *out, unsigned long long *lossy_out, bool on_device) {
   const size_t npix = (size_t)ctx->views.W * ctx->views.H;
   const size_t esz = depth_elem(ctx);
   Batch b;
@@ -95,14 +98,16 @@ int upload_batch(dmi_context *ctx, const double *depth64, const float *depth32, 
   const size_t in_elem = depth32 ? 4 : 8;
   const size_t maps_per_chunk = std::max<size_t>(1, (size_t(256) << 20) / (npix * 8));
   const size_t chunk = std::min<size_t>(maps_per_chunk, (size_t)n);
-  rc = ensure_stage(ctx, chunk * npix, best_cost != nullptr);
+  if (!on_device) rc = ensure_stage(ctx, chunk * npix, best_cost != nullptr);
   if (rc == DMI_OK) {
     hipError_t e = hipMemsetAsync(ctx->views.lossy.as<unsigned long long>(), 0, 3 * sizeof(unsigned long long), ctx->upload_stream);  // [1], [2]: launch_build_valid_maps' counts
     for (size_t m0 = 0; e == hipSuccess && m0 < (size_t)n; m0 += chunk) {
       const size_t cnt = std::min(chunk, (size_t)n - m0);
       const char *src = depth32 ? reinterpret_cast<const char *>(depth32) : reinterpret_cast<const char *>(depth64);
-      e = hipMemcpyAsync(ctx->views.stage_depth.as<double>(), src + m0 * npix * in_elem, cnt * npix * in_elem, hipMemcpyHostToDevice,
-                         ctx->upload_stream);
+      const double *staged = on_device ? depth64 + m0 * npix : ctx->views.stage_depth.as<double>();
+      if (!on_device)
+        e = hipMemcpyAsync(ctx->views.stage_depth.as<double>(), src + m0 * npix * in_elem, cnt * npix * in_elem, hipMemcpyHostToDevice,
+                           ctx->upload_stream);
       if (e == hipSuccess && best_cost)
         e = hipMemcpyAsync(ctx->views.stage_cost.as<double>(), best_cost + m0 * npix, cnt * npix * 8, hipMemcpyHostToDevice, ctx->upload_stream);
       void *dst = static_cast<char *>(b.d_depth) + m0 * npix * esz;
@@ -110,7 +115,7 @@ int upload_batch(dmi_context *ctx, const double *depth64, const float *depth32, 
       const bool timed = m0 + cnt >= (size_t)n && ctx->views.up_events[0] && ctx->views.up_events[1];  // (the last chunk of the call: with it, the pyramid levels)
       if (e == hipSuccess && timed) e = hipEventRecord(ctx->views.up_events[0], ctx->upload_stream);
       if (e == hipSuccess)
-        e = dmi::launch_upload_views(ctx->views.stage_depth.as<double>(), depth32 ? 0 : 1, (!depth32 && best_cost) ? ctx->views.stage_cost.as<double>() : nullptr, threshold,
+        e = dmi::launch_upload_views(staged, depth32 ? 0 : 1, (!depth32 && best_cost) ? ctx->views.stage_cost.as<double>() : nullptr, threshold,
                                      dst, ctx->views.depth_f64 ? 1 : 0, (int64_t)cnt, ctx->views.W, ctx->views.H, ctx->views.pyramid,
                                      b.d_pyramid + m0 * (size_t)ctx->views.pyramid.total_tiles,
                                      reinterpret_cast<uint8_t *>(b.d_pyramid) + b.valid_offset + m0 * (size_t)dmi::valid_map_bytes(ctx->views.W, ctx->views.H),
@@ -152,7 +157,8 @@ int upload_batch(dmi_context *ctx, const double *depth64, const float *depth32, 
 }
 
 int add_views_impl(dmi_context *ctx, const double *depth64, const float *depth32, const double *best_cost,
-                   double threshold, const double *K4, const double *RT4, int32_t n, int32_t width, int32_t height) {
+                   double threshold, const double *K4, const double *RT4, int32_t n, int32_t width, int32_t height,
+                   bool on_device = false) {
   if (!ctx) return DMI_ERR_INVALID_ARGUMENT;
   if ((!depth64 && !depth32) || !K4 || !RT4) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_add_views: null pointer");
   if (n <= 0) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_add_views: n must be positive");
@@ -174,7 +180,7 @@ int add_views_impl(dmi_context *ctx, const double *depth64, const float *depth32
 
   Batch b;
   unsigned long long lossy = 0;
-  int rc = upload_batch(ctx, depth64, depth32, best_cost, threshold, n, &b, &lossy);
+  int rc = upload_batch(ctx, depth64, depth32, best_cost, threshold, n, &b, &lossy, on_device);
   if (rc != DMI_OK) return rc;
   if (lossy != 0 && !ctx->views.depth_f64 && ctx->opt.depth_storage == DMI_DEPTH_AUTO) {
     // some depth is not an f32: keep every bit -> promote the whole store and redo this batch in f64
@@ -183,7 +189,7 @@ int add_views_impl(dmi_context *ctx, const double *depth64, const float *depth32
     ctx->device_bytes -= npix * n * 4 + b.aux_bytes;
     rc = promote_to_f64(ctx);
     if (rc != DMI_OK) return rc;
-    rc = upload_batch(ctx, depth64, depth32, best_cost, threshold, n, &b, &lossy);
+    rc = upload_batch(ctx, depth64, depth32, best_cost, threshold, n, &b, &lossy, on_device);
     if (rc != DMI_OK) return rc;
   }
   ctx->views.batches.push_back(b);
@@ -240,6 +246,26 @@ int dmi_add_views_f32(dmi_context *ctx, const float *depth, const double *K4, co
                       int32_t width, int32_t height) {
   return guarded(ctx, "dmi_add_views_f32", [&]() -> int {
   return add_views_impl(ctx, nullptr, depth, nullptr, 0.0, K4, RT4, n, width, height);
+  });
+}
+
+int dmi_add_views_from_set(dmi_context *ctx, const dmi_view_set *s, int32_t first, int32_t count) {
+  return guarded(ctx, "dmi_add_views_from_set", [&]() -> int {
+  if (!ctx) return DMI_ERR_INVALID_ARGUMENT;
+  auto bad = [&](const char *what) { return fail(ctx, DMI_ERR_INVALID_ARGUMENT, std::string("dmi_add_views_from_set: ") + what); };
+  if (!s) return bad("the set is null");
+  if (s->n < 1) return bad("the set holds no views");
+  if (first < 0 || count < 1 || (int64_t)first + count > s->n) return bad("first and count must name views of the set");
+  if (s->device != ctx->opt.device) return bad("the set and the context must be on one device");
+  if (!ctx->views.batches.empty() && (s->W != ctx->views.W || s->H != ctx->views.H))
+    return bad("every view of a context must share width and height");
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  // the set's queued work first (its calls synchronise, so this costs nothing; it states the order)
+  DMI_HIP(ctx, hipEventRecord(s->handed_over, s->stream));
+  DMI_HIP(ctx, hipStreamWaitEvent(ctx->upload_stream, s->handed_over, 0));
+  const size_t npix = (size_t)s->W * (size_t)s->H;
+  return add_views_impl(ctx, s->plane[s->current].as<double>() + (size_t)first * npix, nullptr, nullptr, 0.0,
+                        s->K4.data() + 16 * (size_t)first, s->RT4.data() + 16 * (size_t)first, count, s->W, s->H, true);
   });
 }
 

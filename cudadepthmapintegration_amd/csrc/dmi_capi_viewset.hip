@@ -1,0 +1,612 @@
+// dmi_capi_viewset.hip -- dmi_views_* of include/dmi.h: the resident view set (dmi_view_set.h).  The argument checks (all of them
+// before the device is touched), the set's life cycle, the ingest of an add, and per step the pieces of whole views
+// (view_set_rules.h): each piece runs the per-piece body its context-free counterpart runs -- every sequence of launches lives
+// beside that entry point; the single launches of 8g's upload and finish passes are made here, on the set's own planes -- from D
+// into the alternate plane, and the report kernels of view_set_kernels.hip behind it.  The planes change
+// places when every piece has succeeded.  A failure's text is dmi_views_last_error(s)'s.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "dmi_context.h"
+#include "dmi_view_set.h"
+#include "view_set_kernels.h"
+
+namespace dmi {
+
+namespace {
+thread_local std::string g_create_error;
+}
+
+int views_fail(dmi_view_set *s, int code, const std::string &msg) {
+  if (s)
+    s->err = msg;
+  else
+    g_create_error = msg;
+  return code;
+}
+
+}  // namespace dmi
+
+namespace {
+
+namespace rules = dmi::view_set_rules;
+int fail(dmi_view_set *s, int code, const std::string &msg) { return dmi::views_fail(s, code, msg); }
+dmi_view_set *const kNoSet = nullptr;  // a failure without a set: the thread's last create failure
+
+bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
+
+#define VS_HIP(s, call)                                                                             \
+  do {                                                                                              \
+    hipError_t e_ = (call);                                                                         \
+    if (e_ != hipSuccess) {                                                                         \
+      (void)hipGetLastError();                                                                      \
+      return fail(s, e_ == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE,            \
+                  std::string(#call) + ": " + hipGetErrorString(e_));                               \
+    }                                                                                               \
+  } while (0)
+
+template <typename Body>
+int guarded(dmi_view_set *s, const char *entry, Body &&body) noexcept {
+  return dmi::guarded_by<dmi_view_set>(&dmi::views_fail, s, entry, static_cast<Body &&>(body));
+}
+
+hipError_t grow(dmi_view_set *s, dmi::DeviceBuffer &buffer, uint64_t bytes) { return dmi::grow_buffer(buffer, bytes, s->device_bytes); }
+
+// what a consistency or bounds pass holds beside the set's planes: freed whatever way the pass ends
+struct WholeSetScratch {
+  dmi_view_set *s;
+  ~WholeSetScratch() {
+    (void)hipStreamSynchronize(s->stream);
+    dmi::free_buffers({&s->flipped, &s->counts, &s->cameras, &s->state, &s->hist}, s->device_bytes);
+  }
+};
+
+struct Pieces {
+  size_t plane;  // pixels of a view
+  int64_t per, count;
+};
+Pieces pieces_of(const dmi_view_set *s, int64_t n) {
+  Pieces p;
+  p.plane = (size_t)s->W * (size_t)s->H;
+  p.per = rules::piece_views(s->piece_bytes, s->W, s->H, n);
+  p.count = rules::piece_count(n, p.per);
+  return p;
+}
+
+double *plane_of(const dmi_view_set *s, int which) { return s->plane[which].as<double>(); }
+unsigned long long *counters_of(const dmi_view_set *s) { return s->counters.as<unsigned long long>(); }
+
+int begin_step(dmi_view_set *s) {
+  VS_HIP(s, hipSetDevice(s->device));
+  VS_HIP(s, hipMemsetAsync(s->counters.ptr, 0, dmi::kVsCounters * sizeof(unsigned long long), s->stream));
+  return DMI_OK;
+}
+
+// the piece's work is queued: wait for it and add the spans between `n_events` pass events and between the report's two
+int end_piece(dmi_view_set *s, int n_events, double *pass_ms, double *report_ms) {
+  VS_HIP(s, hipStreamSynchronize(s->stream));  // the scratch and the events are reused by the next piece
+  for (int p = 0; p + 1 < n_events; ++p) {
+    float ms = 0.f;
+    VS_HIP(s, hipEventElapsedTime(&ms, s->events[p], s->events[p + 1]));
+    *pass_ms += (double)ms;
+  }
+  float ms = 0.f;
+  VS_HIP(s, hipEventElapsedTime(&ms, s->report_events[0], s->report_events[1]));
+  *report_ms += (double)ms;
+  return DMI_OK;
+}
+
+// every piece has succeeded: the counters come down, the planes change places, the report is written
+int end_step(dmi_view_set *s, rules::Step step, double pass_ms, double report_ms, dmi_views_step_report *r) {
+  unsigned long long c[dmi::kVsCounters];
+  VS_HIP(s, hipMemcpyAsync(c, s->counters.ptr, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  s->current ^= 1;
+  s->steps += 1;
+  s->last_report_kernel_ms = report_ms;
+  if (r) {
+    const rules::Report made = rules::make_report(step, {c[dmi::kVsValidBefore], c[dmi::kVsValidAfter], c[dmi::kVsDiffering],
+                                                         c[dmi::kVsAuxSum], c[dmi::kVsRoots], c[dmi::kVsRootsKept]});
+    r->valid_before = made.valid_before;
+    r->valid_after = made.valid_after;
+    r->changed = made.changed;
+    r->groups = made.groups;
+    r->groups_kept = made.groups_kept;
+    r->aux_sum = made.aux_sum;
+    r->kernel_ms = pass_ms;
+  }
+  return DMI_OK;
+}
+
+int create(int32_t device, int32_t W, int32_t H, dmi_view_set **out) {
+  const std::string entry = "dmi_views_create: ";
+  auto bad = [&](const std::string &what) { return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!out) return bad("out is null");
+  *out = nullptr;
+  if (W < 1 || W > rules::kMaxSide) return bad("W must lie in [1, 32768]");
+  if (H < 1 || H > rules::kMaxSide) return bad("H must lie in [1, 32768]");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return fail(kNoSet, DMI_ERR_DEVICE, entry + "no HIP device available");
+  }
+  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
+  dmi_view_set *s = new dmi_view_set;
+  s->device = device;
+  s->W = W;
+  s->H = H;
+  auto give_up = [&](hipError_t e, const char *what) {
+    (void)hipGetLastError();
+    const std::string msg = entry + what + ": " + hipGetErrorString(e);
+    dmi_views_destroy(s);
+    return fail(kNoSet, e == hipErrorOutOfMemory ? DMI_ERR_OUT_OF_MEMORY : DMI_ERR_DEVICE, msg);
+  };
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return give_up(e, "hipSetDevice");
+  e = hipDeviceGetAttribute(&s->compute_units, hipDeviceAttributeMultiprocessorCount, device);
+  if (e != hipSuccess) return give_up(e, "hipDeviceGetAttribute");
+  e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) return give_up(e, "hipStreamCreateWithFlags");
+  for (hipEvent_t &ev : s->events)
+    if ((e = hipEventCreate(&ev)) != hipSuccess) return give_up(e, "hipEventCreate");
+  for (hipEvent_t &ev : s->report_events)
+    if ((e = hipEventCreate(&ev)) != hipSuccess) return give_up(e, "hipEventCreate");
+  if ((e = hipEventCreateWithFlags(&s->handed_over, hipEventDisableTiming)) != hipSuccess) return give_up(e, "hipEventCreate");
+  if ((e = grow(s, s->counters, dmi::kVsCounters * sizeof(unsigned long long))) != hipSuccess) return give_up(e, "hipMalloc");
+  *out = s;
+  return DMI_OK;
+}
+
+int add(dmi_view_set *s, const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4, int32_t n) {
+  const std::string entry = "dmi_views_add: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!depth) return bad("depth is null");
+  if (!K4) return bad("K4 is null");
+  if (!RT4) return bad("RT4 is null");
+  if (n < 1) return bad("n >= 1 required");
+  if ((int64_t)s->n + n > 0x7fffffffLL) return bad("the set cannot hold more than 2^31 - 1 views");
+  if (best_cost && threshold != threshold) return bad("threshold is NaN");
+  const size_t plane = (size_t)s->W * (size_t)s->H, held = (size_t)s->n, total = held + (size_t)n;
+  uint64_t resident = 0;
+  if (!rules::resident_bytes(total, s->W, s->H, &resident)) return bad("the views' planes do not fit 64 bits of bytes");
+
+  VS_HIP(s, hipSetDevice(s->device));
+  // both planes hold `total` views, D keeps its contents: all or nothing
+  if (!dmi::holds(s->plane[s->current], total * plane * 8)) {
+    dmi::DeviceBuffer grown;
+    hipError_t e = grow(s, grown, total * plane * 8);
+    if (e == hipSuccess && held)
+      e = hipMemcpyAsync(grown.ptr, s->plane[s->current].ptr, held * plane * 8, hipMemcpyDeviceToDevice, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+      dmi::free_buffers({&grown}, s->device_bytes);
+      VS_HIP(s, e);
+    }
+    dmi::free_buffers({&s->plane[s->current]}, s->device_bytes);
+    s->plane[s->current] = grown;
+  }
+  VS_HIP(s, grow(s, s->plane[s->current ^ 1], total * plane * 8));
+
+  const Pieces p = pieces_of(s, n);
+  // (two doubles of room: a staged piece stands as far from a 16-byte boundary as its place in D does)
+  VS_HIP(s, grow(s, s->stage_depth, (uint64_t)p.per * plane * 8 + 16));
+  if (best_cost) VS_HIP(s, grow(s, s->stage_cost, (uint64_t)p.per * plane * 8 + 16));
+  VS_HIP(s, hipMemsetAsync(s->counters.ptr, 0, dmi::kVsCounters * sizeof(unsigned long long), s->stream));
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece piece = rules::piece_at(n, p.per, q);
+    double *const dst = plane_of(s, s->current) + (held + (size_t)piece.first) * plane;
+    const size_t shift = (size_t)((reinterpret_cast<uintptr_t>(dst) & 15) / 8), elems = (size_t)piece.count * plane;
+    double *const up_depth = s->stage_depth.as<double>() + shift;
+    double *const up_cost = best_cost ? s->stage_cost.as<double>() + shift : nullptr;
+    VS_HIP(s, hipMemcpyAsync(up_depth, depth + (size_t)piece.first * plane, elems * 8, hipMemcpyHostToDevice, s->stream));
+    if (best_cost)
+      VS_HIP(s, hipMemcpyAsync(up_cost, best_cost + (size_t)piece.first * plane, elems * 8, hipMemcpyHostToDevice, s->stream));
+    VS_HIP(s, dmi::launch_view_set_ingest(up_depth, up_cost, threshold, dst, elems, counters_of(s), s->compute_units, s->stream));
+    VS_HIP(s, hipStreamSynchronize(s->stream));  // the stage buffers are reused by the next piece
+  }
+  s->h2d_plane_bytes += (uint64_t)n * plane * 8 * (best_cost ? 2 : 1);
+  s->K4.insert(s->K4.end(), K4, K4 + 16 * (size_t)n);
+  s->RT4.insert(s->RT4.end(), RT4, RT4 + 16 * (size_t)n);
+  s->n = (int32_t)total;
+  return DMI_OK;
+}
+
+int filter_speckles(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t min_pixels, int32_t *out_size,
+                    dmi_views_step_report *r) {
+  const std::string entry = "dmi_views_filter_speckles: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (s->n < 1) return bad("the set holds no views");
+  if (min_pixels < 0) return bad("min_pixels >= 0 required");
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+
+  const int W = s->W, H = s->H;
+  const dmi::SpeckleTuning tuning = dmi::speckle_tuning_from_environment();
+  const Pieces p = pieces_of(s, s->n);
+  const size_t tiles = (size_t)dmi::speckle_tiles(W, H, p.per, tuning);
+  int rc = begin_step(s);
+  if (rc != DMI_OK) return rc;
+  VS_HIP(s, grow(s, s->label, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
+  VS_HIP(s, grow(s, s->record, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
+  VS_HIP(s, grow(s, s->border_down, tiles * sizeof(uint64_t)));
+  VS_HIP(s, grow(s, s->border_right, tiles * sizeof(uint64_t)));
+  if (out_size) VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));
+
+  double pass_ms = 0.0, report_ms = 0.0;
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece at = rules::piece_at(s->n, p.per, q);
+    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
+    const double *const src = plane_of(s, s->current) + offset;
+    dmi::SpecklePiece piece;
+    piece.depth = plane_of(s, s->current ^ 1) + offset;  // the passes work in place: on a copy of D's piece
+    piece.cost = nullptr;
+    piece.label = s->label.as<uint32_t>();
+    piece.size = s->record.as<uint32_t>();
+    piece.border_down = s->border_down.as<uint64_t>();
+    piece.border_right = s->border_right.as<uint64_t>();
+    piece.out_size = out_size ? s->aux.as<int32_t>() : nullptr;
+    piece.count = at.count;
+    VS_HIP(s, hipMemcpyAsync(piece.depth, src, elems * 8, hipMemcpyDeviceToDevice, s->stream));
+    VS_HIP(s, dmi::run_speckle_piece(piece, 0.0, W, H, abs_tolerance, rel_tolerance, min_pixels, tuning, s->stream, s->events));
+    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
+    VS_HIP(s, dmi::launch_view_set_segment_roots(piece, W, H, min_pixels, counters_of(s), s->compute_units, s->stream));
+    VS_HIP(s, dmi::launch_view_set_report(src, piece.depth, nullptr, elems, counters_of(s), s->compute_units, s->stream));
+    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
+    if (out_size)
+      VS_HIP(s, hipMemcpyAsync(out_size + offset, piece.out_size, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    if ((rc = end_piece(s, 5, &pass_ms, &report_ms)) != DMI_OK) return rc;
+  }
+  if (out_size) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
+  return end_step(s, rules::kSpeckles, pass_ms, report_ms, r);
+}
+
+int fill_holes(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t max_pixels, int32_t *out_size,
+               dmi_views_step_report *r) {
+  const std::string entry = "dmi_views_fill_holes: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (s->n < 1) return bad("the set holds no views");
+  if (max_pixels < 0) return bad("max_pixels >= 0 required");
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+
+  const int W = s->W, H = s->H;
+  const Pieces p = pieces_of(s, s->n);
+  const size_t tiles = (size_t)dmi::holes_tiles(W, H, p.per);
+  int rc = begin_step(s);
+  if (rc != DMI_OK) return rc;
+  VS_HIP(s, grow(s, s->label, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
+  VS_HIP(s, grow(s, s->record, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
+  VS_HIP(s, grow(s, s->rim_lo, (uint64_t)p.per * p.plane * sizeof(uint64_t)));
+  VS_HIP(s, grow(s, s->rim_hi, (uint64_t)p.per * p.plane * sizeof(uint64_t)));
+  VS_HIP(s, grow(s, s->border_down, tiles * sizeof(uint64_t)));
+  VS_HIP(s, grow(s, s->border_right, tiles * sizeof(uint64_t)));
+  if (out_size) VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));
+
+  double pass_ms = 0.0, report_ms = 0.0;
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece at = rules::piece_at(s->n, p.per, q);
+    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
+    const double *const src = plane_of(s, s->current) + offset;
+    dmi::HolesPiece piece;
+    piece.depth = plane_of(s, s->current ^ 1) + offset;  // the output pass writes hole pixels only: into a copy of D's piece
+    piece.cost = nullptr;
+    piece.label = s->label.as<uint32_t>();
+    piece.record = s->record.as<uint32_t>();
+    piece.rim_lo = s->rim_lo.as<uint64_t>();
+    piece.rim_hi = s->rim_hi.as<uint64_t>();
+    piece.border_down = s->border_down.as<uint64_t>();
+    piece.border_right = s->border_right.as<uint64_t>();
+    piece.out_size = out_size ? s->aux.as<int32_t>() : nullptr;
+    piece.count = at.count;
+    VS_HIP(s, hipMemcpyAsync(piece.depth, src, elems * 8, hipMemcpyDeviceToDevice, s->stream));
+    VS_HIP(s, dmi::run_holes_piece(piece, 0.0, W, H, abs_tolerance, rel_tolerance, max_pixels, s->stream, s->events));
+    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
+    VS_HIP(s, dmi::launch_view_set_hole_roots(piece, W, H, abs_tolerance, rel_tolerance, max_pixels, counters_of(s), s->compute_units,
+                                               s->stream));
+    VS_HIP(s, dmi::launch_view_set_report(src, piece.depth, nullptr, elems, counters_of(s), s->compute_units, s->stream));
+    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
+    if (out_size)
+      VS_HIP(s, hipMemcpyAsync(out_size + offset, piece.out_size, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    if ((rc = end_piece(s, 5, &pass_ms, &report_ms)) != DMI_OK) return rc;
+  }
+  if (out_size) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
+  return end_step(s, rules::kHoles, pass_ms, report_ms, r);
+}
+
+int smooth(dmi_view_set *s, double sigma, double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations,
+           int32_t *out_count, dmi_views_step_report *r) {
+  const std::string entry = "dmi_views_smooth: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (s->n < 1) return bad("the set holds no views");
+  if (!finite_and_not_negative(sigma)) return bad("sigma must be finite and >= 0");
+  if (!(truncate > 0.0 && truncate <= 4.0)) return bad("truncate must lie in (0, 4]");
+  int32_t radius = 0;
+  double weights[dmi::kDepthSmoothMaxRadius + 1];
+  if (dmi::depth_smoothing_weights(sigma, truncate, &radius, weights) != 0)
+    return bad("the radius ceil(truncate * sigma) must not exceed " + std::to_string(dmi::kDepthSmoothMaxRadius));
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (iterations < 1 || iterations > dmi::kDepthSmoothMaxIterations)
+    return bad("iterations must lie in [1, " + std::to_string(dmi::kDepthSmoothMaxIterations) + "]");
+
+  const int W = s->W, H = s->H;
+  const Pieces p = pieces_of(s, s->n);
+  const dmi::SmoothArgs args = dmi::smooth_args(weights, radius, abs_tolerance, rel_tolerance);
+  int rc = begin_step(s);
+  if (rc != DMI_OK) return rc;
+  if (iterations > 1) VS_HIP(s, grow(s, s->second, (uint64_t)p.per * p.plane * 8));
+  VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));  // the report sums the taps whether asked for or not
+
+  double pass_ms = 0.0, report_ms = 0.0;
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece at = rules::piece_at(s->n, p.per, q);
+    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
+    const double *const src = plane_of(s, s->current) + offset;
+    double *const dst = plane_of(s, s->current ^ 1) + offset, *const other = s->second.as<double>();
+    // the last iteration writes dst: the iterations start on whichever of the two makes it so.  D is read, never written.
+    const bool odd = iterations % 2 == 1;
+    int32_t *const count = s->aux.as<int32_t>();
+    const double *result = nullptr;
+    VS_HIP(s, dmi::run_smooth_piece(src, nullptr, 0.0, odd ? dst : other, odd ? other : dst, count, at.count, W, H, args, iterations,
+                                     s->stream, s->events, &result));
+    if (result != dst) return fail(s, DMI_ERR_STATE, entry + "the iterations did not end in the alternate plane");
+    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
+    VS_HIP(s, dmi::launch_view_set_report(src, dst, count, elems, counters_of(s), s->compute_units, s->stream));
+    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
+    if (out_count) VS_HIP(s, hipMemcpyAsync(out_count + offset, count, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    if ((rc = end_piece(s, 2, &pass_ms, &report_ms)) != DMI_OK) return rc;
+  }
+  if (out_count) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
+  return end_step(s, rules::kSmooth, pass_ms, report_ms, r);
+}
+
+// D of every piece into s->flipped, thresholded already, rows flipped to image order (8g's upload pass, device to device)
+int flip_planes(dmi_view_set *s, const Pieces &p, double *pass_ms) {
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece at = rules::piece_at(s->n, p.per, q);
+    VS_HIP(s, hipEventRecord(s->events[0], s->stream));
+    VS_HIP(s, dmi::launch_consistency_upload(plane_of(s, s->current) + (size_t)at.first * p.plane, nullptr, 0.0, s->W, s->H, at.count,
+                                              s->flipped.as<double>(), at.first, s->stream));
+    VS_HIP(s, hipEventRecord(s->events[1], s->stream));
+    VS_HIP(s, hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
+    *pass_ms += (double)ms;
+  }
+  return DMI_OK;
+}
+
+int upload_cameras(dmi_view_set *s) {
+  const size_t views = (size_t)s->n;
+  VS_HIP(s, grow(s, s->cameras, views * sizeof(dmi::ConsistencyCamera)));
+  const std::vector<dmi::ConsistencyCamera> cameras = dmi::consistency_cameras(s->K4.data(), s->RT4.data(), views);
+  VS_HIP(s, hipMemcpyAsync(s->cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));  // `cameras` goes out of scope
+  return DMI_OK;
+}
+
+int filter_consistency(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int32_t min_views, int32_t *out_count,
+                       dmi_views_step_report *r) {
+  const std::string entry = "dmi_views_filter_consistency: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (s->n < 1) return bad("the set holds no views");
+  if (min_views < 0) return bad("min_views >= 0 required");
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const int32_t m = dmi::first_view_with_other_k(s->K4.data(), s->n); m >= 0) return bad(dmi::other_k_message(m));
+
+  const int W = s->W, H = s->H, n = s->n;
+  const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
+  const Pieces p = pieces_of(s, n);
+  int rc = begin_step(s);
+  if (rc != DMI_OK) return rc;
+  WholeSetScratch scratch{s};
+  VS_HIP(s, grow(s, s->flipped, (uint64_t)n * p.plane * 8));
+  VS_HIP(s, grow(s, s->counts, (uint64_t)n * p.plane * sizeof(int32_t)));
+  if (out_count) VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));
+  if ((rc = upload_cameras(s)) != DMI_OK) return rc;
+  VS_HIP(s, hipMemsetAsync(s->counts.ptr, 0, (size_t)n * p.plane * sizeof(int32_t), s->stream));
+
+  double pass_ms = 0.0, report_ms = 0.0;
+  if ((rc = flip_planes(s, p, &pass_ms)) != DMI_OK) return rc;
+  if (n > 1) {
+    VS_HIP(s, dmi::run_consistency_count(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
+                                          rel_tolerance, tuning, s->counts.as<int32_t>(), nullptr, s->stream, s->events));
+    VS_HIP(s, hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
+    pass_ms += (double)ms;
+  }
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece at = rules::piece_at(n, p.per, q);
+    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
+    const double *const src = plane_of(s, s->current) + offset;
+    double *const dst = plane_of(s, s->current ^ 1) + offset;
+    VS_HIP(s, hipEventRecord(s->events[0], s->stream));
+    VS_HIP(s, dmi::launch_consistency_finish(s->flipped.as<double>(), s->counts.as<int32_t>(), W, H, at.first, at.count, min_views, dst,
+                                              out_count ? s->aux.as<int32_t>() : nullptr, s->stream));
+    VS_HIP(s, hipEventRecord(s->events[1], s->stream));
+    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
+    VS_HIP(s, dmi::launch_view_set_report(src, dst, nullptr, elems, counters_of(s), s->compute_units, s->stream));
+    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
+    if (out_count) VS_HIP(s, hipMemcpyAsync(out_count + offset, s->aux.ptr, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    if ((rc = end_piece(s, 2, &pass_ms, &report_ms)) != DMI_OK) return rc;
+  }
+  if (out_count) s->d2h_plane_bytes += (uint64_t)n * p.plane * sizeof(int32_t);
+  return end_step(s, rules::kConsistency, pass_ms, report_ms, r);
+}
+
+int estimate_bounds(dmi_view_set *s, const double *axes9, double trim_fraction, int32_t pixel_step, double lo[3], double hi[3],
+                    uint64_t *n_points, double *kernel_ms) {
+  const std::string entry = "dmi_views_estimate_bounds: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!lo) return bad("lo is null");
+  if (!hi) return bad("hi is null");
+  if (!n_points) return bad("n_points is null");
+  if (s->n < 1) return bad("the set holds no views");
+  if ((uint64_t)s->n * (uint64_t)s->W * (uint64_t)s->H >= (uint64_t(1) << 53)) return bad("n * W * H must stay below 2^53");
+  if (!(trim_fraction >= 0.0 && trim_fraction <= 0.5)) return bad("trim_fraction must lie in [0, 0.5]");  // false for NaN
+  if (pixel_step < 1) return bad("pixel_step >= 1 required");
+  dmi::BoundsAxes axes;
+  if (!dmi::bounds_axes(axes9, &axes)) return bad("axes9 holds a value that is not finite");
+  if (const int32_t m = dmi::first_view_with_other_k(s->K4.data(), s->n); m >= 0) return bad(dmi::other_k_message(m));
+
+  const int n = s->n;
+  const dmi::BoundsTuning tuning = dmi::bounds_tuning_from_environment();
+  const Pieces p = pieces_of(s, n);
+  constexpr size_t kHistBytes = sizeof(unsigned long long) * dmi::bounds_rules::kTargets * dmi::bounds_rules::kBins;
+  VS_HIP(s, hipSetDevice(s->device));
+  WholeSetScratch scratch{s};
+  VS_HIP(s, grow(s, s->flipped, (uint64_t)n * p.plane * 8));
+  VS_HIP(s, grow(s, s->state, sizeof(dmi::BoundsState)));
+  VS_HIP(s, grow(s, s->hist, kHistBytes));
+  int rc = upload_cameras(s);
+  if (rc != DMI_OK) return rc;
+  VS_HIP(s, hipMemsetAsync(s->state.ptr, 0, sizeof(dmi::BoundsState), s->stream));
+  VS_HIP(s, hipMemsetAsync(s->hist.ptr, 0, kHistBytes, s->stream));
+  double pass_ms = 0.0;
+  if ((rc = flip_planes(s, p, &pass_ms)) != DMI_OK) return rc;
+  dmi::BoundsState result;
+  VS_HIP(s, dmi::run_bounds_select(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, s->W, s->H, pixel_step, axes,
+                                    trim_fraction, s->state.as<dmi::BoundsState>(), s->hist.as<unsigned long long>(), s->compute_units,
+                                    tuning, s->stream, s->events, &result));
+  float ms = 0.f;
+  VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
+  pass_ms += (double)ms;
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = result.result[2 * a];
+    hi[a] = result.result[2 * a + 1];
+  }
+  *n_points = result.n;
+  if (kernel_ms) *kernel_ms = pass_ms;
+  s->steps += 1;
+  return DMI_OK;
+}
+
+int download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth) {
+  const std::string entry = "dmi_views_download: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!out_depth) return bad("out_depth is null");
+  if (s->n < 1) return bad("the set holds no views");
+  if (first < 0 || count < 1 || (int64_t)first + count > s->n) return bad("first and count must name views of the set");
+  const size_t plane = (size_t)s->W * (size_t)s->H;
+  VS_HIP(s, hipSetDevice(s->device));
+  VS_HIP(s, hipMemcpyAsync(out_depth, plane_of(s, s->current) + (size_t)first * plane, (size_t)count * plane * 8, hipMemcpyDeviceToHost,
+                            s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  s->d2h_plane_bytes += (uint64_t)count * plane * 8;
+  return DMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dmi_views_create(int32_t device, int32_t W, int32_t H, dmi_view_set **out) {
+  return guarded(nullptr, "dmi_views_create", [&]() -> int { return create(device, W, H, out); });
+}
+
+void dmi_views_destroy(dmi_view_set *s) {
+  if (!s) return;
+  (void)hipSetDevice(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  dmi::free_buffers({&s->plane[0], &s->plane[1], &s->stage_depth, &s->stage_cost, &s->label, &s->record, &s->rim_lo, &s->rim_hi,
+                     &s->border_down, &s->border_right, &s->second, &s->aux, &s->flipped, &s->counts, &s->cameras, &s->state, &s->hist,
+                     &s->counters});
+  dmi::destroy_events(s->events);
+  dmi::destroy_events(s->report_events);
+  if (s->handed_over) (void)hipEventDestroy(s->handed_over);
+  if (s->stream) (void)hipStreamDestroy(s->stream);
+  (void)hipGetLastError();
+  delete s;
+}
+
+const char *dmi_views_last_error(const dmi_view_set *s) { return s ? s->err.c_str() : dmi::g_create_error.c_str(); }
+
+int dmi_views_add(dmi_view_set *s, const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4,
+                  int32_t n) {
+  return guarded(s, "dmi_views_add", [&]() -> int { return add(s, depth, best_cost, threshold, K4, RT4, n); });
+}
+
+int dmi_views_clear(dmi_view_set *s) {
+  return guarded(s, "dmi_views_clear", [&]() -> int {
+    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_clear: the set is null");
+    s->n = 0;
+    s->K4.clear();
+    s->RT4.clear();
+    return DMI_OK;
+  });
+}
+
+int dmi_views_get_info(dmi_view_set *s, dmi_views_info *out) {
+  return guarded(s, "dmi_views_get_info", [&]() -> int {
+    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_info: the set is null");
+    if (!out) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_info: out is null");
+    out->n = s->n;
+    out->W = s->W;
+    out->H = s->H;
+    out->device = s->device;
+    out->device_bytes = s->device_bytes;
+    out->steps = s->steps;
+    out->h2d_plane_bytes = s->h2d_plane_bytes;
+    out->d2h_plane_bytes = s->d2h_plane_bytes;
+    out->last_report_kernel_ms = s->last_report_kernel_ms;
+    return DMI_OK;
+  });
+}
+
+size_t dmi_sizeof_views_info(void) { return sizeof(dmi_views_info); }
+
+int dmi_views_set_piece_bytes(dmi_view_set *s, uint64_t bytes) {
+  return guarded(s, "dmi_views_set_piece_bytes", [&]() -> int {
+    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_piece_bytes: the set is null");
+    if (bytes == 0) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_piece_bytes: bytes >= 1 required");
+    s->piece_bytes = bytes;
+    return DMI_OK;
+  });
+}
+
+int dmi_views_filter_speckles(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t min_pixels, int32_t *out_size,
+                              dmi_views_step_report *r) {
+  return guarded(s, "dmi_views_filter_speckles",
+                 [&]() -> int { return filter_speckles(s, abs_tolerance, rel_tolerance, min_pixels, out_size, r); });
+}
+
+int dmi_views_fill_holes(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t max_pixels, int32_t *out_size,
+                         dmi_views_step_report *r) {
+  return guarded(s, "dmi_views_fill_holes", [&]() -> int { return fill_holes(s, abs_tolerance, rel_tolerance, max_pixels, out_size, r); });
+}
+
+int dmi_views_smooth(dmi_view_set *s, double sigma, double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations,
+                     int32_t *out_count, dmi_views_step_report *r) {
+  return guarded(s, "dmi_views_smooth",
+                 [&]() -> int { return smooth(s, sigma, truncate, abs_tolerance, rel_tolerance, iterations, out_count, r); });
+}
+
+int dmi_views_filter_consistency(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int32_t min_views, int32_t *out_count,
+                                 dmi_views_step_report *r) {
+  return guarded(s, "dmi_views_filter_consistency",
+                 [&]() -> int { return filter_consistency(s, abs_tolerance, rel_tolerance, min_views, out_count, r); });
+}
+
+int dmi_views_estimate_bounds(dmi_view_set *s, const double *axes9, double trim_fraction, int32_t pixel_step, double lo[3], double hi[3],
+                              uint64_t *n_points, double *kernel_ms) {
+  return guarded(s, "dmi_views_estimate_bounds",
+                 [&]() -> int { return estimate_bounds(s, axes9, trim_fraction, pixel_step, lo, hi, n_points, kernel_ms); });
+}
+
+int dmi_views_download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth) {
+  return guarded(s, "dmi_views_download", [&]() -> int { return download(s, first, count, out_depth); });
+}
+
+}  // extern "C"

@@ -1,0 +1,76 @@
+// dmi_view_set.h -- the resident view set behind dmi_views_* of include/dmi.h (dmi_capi_viewset.hip): the depth planes
+// of n views that stay on one device from the first filter to the fusion, the scratch of one piece of a pass, and the per-piece
+// bodies that the context-free entry points (dmi_capi_speckle.hip, dmi_capi_holes.hip, dmi_capi_smooth.hip,
+// dmi_capi_consistency.hip, dmi_capi_bounds.hip) share with it: one implementation per filter.  Private: never installed.
+#pragma once
+#include "../../include/dmi.h"
+#include "depth_consistency.h"
+#include "depth_holes.h"
+#include "depth_smooth.h"
+#include "depth_speckle.h"
+#include "dmi_buffer.h"
+#include "scene_bounds.h"
+#include "view_set_rules.h"
+
+#include <string>
+#include <vector>
+
+struct dmi_view_set {
+  int32_t device = 0, W = 0, H = 0;
+  int32_t n = 0;
+  int compute_units = 0;
+  // D is plane[current], [n][H][W] f64 in vtk point order, normalised: a valid depth or -1.  A step writes plane[current ^ 1] and
+  // the two change places when it has succeeded; an add grows both.
+  dmi::DeviceBuffer plane[2];
+  int current = 0;
+  std::vector<double> K4, RT4;  // [n][16] each, as they came
+  // the scratch of one piece, kept while large enough: the staging of an add; the labelling planes of the speckle filter and the
+  // hole fill (label and record serve both); the plane the smoothing's iterations alternate with; the size or count plane
+  dmi::DeviceBuffer stage_depth, stage_cost, label, record, rim_lo, rim_hi, border_down, border_right, second, aux;
+  // held during a consistency or bounds pass only: the planes in image row order, the counts, the cameras, the select's state
+  dmi::DeviceBuffer flipped, counts, cameras, state, hist;
+  dmi::DeviceBuffer counters;  // dmi::kVsCounters u64 (view_set_kernels.h)
+  hipStream_t stream = nullptr;
+  hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // around a piece's passes
+  hipEvent_t report_events[2] = {nullptr, nullptr};                      // around a piece's report kernels
+  hipEvent_t handed_over = nullptr;  // what a fusion context's upload stream waits for (dmi_add_views_from_set)
+  uint64_t piece_bytes = dmi::view_set_rules::kDefaultPieceBytes;
+  uint64_t device_bytes = 0;  // the sum of the capacities held
+  uint64_t steps = 0, h2d_plane_bytes = 0, d2h_plane_bytes = 0;
+  double last_report_kernel_ms = 0.0;
+  std::string err;
+};
+
+namespace dmi {
+
+int views_fail(dmi_view_set *s, int code, const std::string &msg);  // records msg (s == nullptr: for dmi_views_last_error(nullptr))
+
+// ---- one implementation per filter: defined beside the context-free entry point that runs it between its copies ----
+
+// dmi_capi_speckle.hip: the four passes on a piece, an event before the first and one behind each
+hipError_t run_speckle_piece(const SpecklePiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
+                             int64_t min_pixels, const SpeckleTuning &tuning, hipStream_t stream, hipEvent_t events[5]);
+SpeckleTuning speckle_tuning_from_environment();  // the defaults, unless a tuning build's environment says otherwise
+// dmi_capi_holes.hip: the same for the hole fill
+hipError_t run_holes_piece(const HolesPiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
+                           int64_t max_pixels, hipStream_t stream, hipEvent_t events[5]);
+// dmi_capi_smooth.hip: the iterations on a piece, src -> ping -> pong -> ping ...; *result: what the last one wrote
+hipError_t run_smooth_piece(const double *src, const double *cost, double threshold, double *ping, double *pong, int32_t *count,
+                            int64_t views, int32_t W, int32_t H, const SmoothArgs &args, int32_t iterations, hipStream_t stream,
+                            hipEvent_t events[2], const double **result);
+// dmi_capi_consistency.hip: the K4 check both camera-reading calls make, their cameras, and the count launches on flipped planes
+int32_t first_view_with_other_k(const double *K4, int32_t n);  // -1: every K4 is of the form SetMatrixK produces
+std::string other_k_message(int32_t view);
+std::vector<ConsistencyCamera> consistency_cameras(const double *K4, const double *RT4, size_t views);
+ConsistencyTuning consistency_tuning_from_environment();
+hipError_t run_consistency_count(const double *planes, const ConsistencyCamera *cameras, int32_t n, int32_t W, int32_t H,
+                                 double abs_tolerance, double rel_tolerance, const ConsistencyTuning &tuning, int32_t *counts,
+                                 unsigned long long *undecided, hipStream_t stream, hipEvent_t events[2]);
+// dmi_capi_bounds.hip: the axes (false: one is not finite), and the count and select passes with the state's download
+bool bounds_axes(const double *axes9, BoundsAxes *out);
+BoundsTuning bounds_tuning_from_environment();
+hipError_t run_bounds_select(const double *planes, const ConsistencyCamera *cameras, int32_t n, int32_t W, int32_t H, int32_t pixel_step,
+                             const BoundsAxes &axes, double trim_fraction, BoundsState *state, unsigned long long *hist, int compute_units,
+                             const BoundsTuning &tuning, hipStream_t stream, hipEvent_t events[2], BoundsState *result);
+
+}  // namespace dmi

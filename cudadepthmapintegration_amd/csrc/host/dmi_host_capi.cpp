@@ -398,6 +398,7 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->depth_smooth_tolerance = o.depthSmoothTolerance;
   out->depth_smooth_rel_tolerance = o.depthSmoothRelTolerance;
   out->depth_smooth_iterations = o.depthSmoothIterations;
+  out->depth_staged_filters = o.depthStagedFilters ? 1 : 0;
   return 1;
   });
 }

@@ -306,6 +306,13 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                      return into_count(&o->depthSmoothIterations)(values) && o->depthSmoothIterations >= 1 &&
                                             o->depthSmoothIterations <= dmi::kDepthSmoothMaxIterations;
                                    }}},
+      {"--depthStagedFilters", {Kind::kFlag, "with --depthSpeckleMinPixels, --depthFillHolesMaxPixels, --depthSmoothSigma, "
+                                             "--depthConsistencyMinViews or --gridAutoBounds: run these steps through the staged "
+                                             "calls, each with an upload and a download of its own, instead of keeping the depth "
+                                             "maps on the GPU from the first step to the fusion; every output is the same, only the "
+                                             "times differ (the tool takes this path by itself when the GPU's memory cannot hold the "
+                                             "resident depth maps; not in the reference)",
+                               into_flag(&o->depthStagedFilters)}},
       {"--gridAutoBounds", {Kind::kFlag, "take the grid's box from the depth maps instead of --gridOrigin and --gridEnd, which then must "
                                          "not be given (one of --gridDims / --gridSpacing still is): every valid pixel is "
                                          "back-projected on the GPU, and along each of the grid's axes the box runs from the "
@@ -519,6 +526,13 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     }
   if (o->depthConsistencyMinViews > 0x7fffffffLL) {
     err << "Bad value for --depthConsistencyMinViews\n" << HelpText();
+    return false;
+  }
+  if (o->depthStagedFilters && o->depthSpeckleMinPixels < 0 && o->depthFillHolesMaxPixels < 0 && !o->depthSmoothSigmaGiven &&
+      o->depthConsistencyMinViews < 0 && !o->gridAutoBounds) {
+    err << "Error : --depthStagedFilters needs --depthSpeckleMinPixels, --depthFillHolesMaxPixels, --depthSmoothSigma, "
+           "--depthConsistencyMinViews or --gridAutoBounds.\n"
+        << HelpText();
     return false;
   }
   for (const auto &flag : {std::make_pair("--depthSpeckleTolerance", o->depthSpeckleToleranceGiven),
@@ -882,6 +896,54 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     }
     return true;
   };
+  // The steps below run on a resident view set: the views go up once, every step works where they are, and the
+  // filter fuses them from there.  --depthStagedFilters keeps the staged calls; so does, from then on, a set that the device's
+  // memory cannot hold: its depths are stored into the host views and the step that failed is run again the staged way.
+  DepthViewSet resident;
+  bool staged = o.depthStagedFilters;
+  const int stepDevice = o.devices.empty() ? 0 : o.devices[0];
+  // true: the step is to run on the set, which is loaded
+  auto on_set = [&]() {
+    if (staged || resident.Loaded()) return !staged;
+    if (resident.Load(views, o.threshBestCost, stepDevice)) return true;
+    if (resident.LastCode() == DMI_ERR_OUT_OF_MEMORY) {
+      say("the depth maps do not fit the GPU's memory as a resident set: the staged filters are used (" + resident.LastError() + ")");
+      staged = true;
+      return false;
+    }
+    if (resident.LastCode() == DMI_ERR_INVALID_ARGUMENT) {  // views the set cannot take: the staged call says what is wrong with them
+      say("the depth maps cannot form a resident set: the staged filters are used (" + resident.LastError() + ")");
+      staged = true;
+      return false;
+    }
+    return true;  // (another failure: run_step reports it)
+  };
+  // a step on the set has failed: true if the staged path is to take over (out of memory, and the depths are back on the host)
+  auto taken_over = [&](const std::string &flag, std::string *error) {
+    *error = resident.LastError();
+    if (resident.LastCode() != DMI_ERR_OUT_OF_MEMORY || !resident.Loaded()) return false;
+    if (!resident.Store(views, o.threshBestCost)) {
+      *error = resident.LastError();
+      return false;
+    }
+    say(flag + ": the GPU's memory does not hold this step on the resident set: the staged filters are used from here (" + *error + ")");
+    resident.Release();
+    staged = true;
+    return true;
+  };
+  // runs `on_resident` on the set or `on_host` the staged way; false: `error` says why
+  auto run_step = [&](const std::string &flag, const std::function<bool()> &on_resident, const std::function<bool(std::string *)> &on_host,
+                      std::string *error) {
+    if (on_set()) {
+      if (!resident.Loaded()) {
+        *error = resident.LastError();
+        return false;
+      }
+      if (on_resident()) return true;
+      if (!taken_over(flag, error)) return false;
+    }
+    return on_host(error);
+  };
   // the small segments of all views removed on the first device: before the consistency filter, so that an island cannot vouch for
   // another view's island
   auto speckle_views = [&]() {
@@ -889,8 +951,13 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (!read_views("--depthSpeckleMinPixels")) return false;
     DepthSpeckleReport report;
     std::string error;
-    if (!FilterDepthSpeckles(views, o.threshBestCost, o.depthSpeckleMinPixels, o.depthSpeckleTolerance, o.depthSpeckleRelTolerance,
-                             o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+    if (!run_step("--depthSpeckleMinPixels",
+                  [&]() { return resident.FilterSpeckles(o.depthSpeckleMinPixels, o.depthSpeckleTolerance, o.depthSpeckleRelTolerance, &report); },
+                  [&](std::string *why) {
+                    return FilterDepthSpeckles(views, o.threshBestCost, o.depthSpeckleMinPixels, o.depthSpeckleTolerance,
+                                               o.depthSpeckleRelTolerance, stepDevice, &report, why);
+                  },
+                  &error)) {
       result->error = "--depthSpeckleMinPixels: " + error;
       return false;
     }
@@ -915,8 +982,13 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (!read_views("--depthFillHolesMaxPixels")) return false;
     DepthHolesReport report;
     std::string error;
-    if (!FillDepthHoles(views, o.threshBestCost, o.depthFillHolesMaxPixels, o.depthFillHolesTolerance, o.depthFillHolesRelTolerance,
-                        o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+    if (!run_step("--depthFillHolesMaxPixels",
+                  [&]() { return resident.FillHoles(o.depthFillHolesMaxPixels, o.depthFillHolesTolerance, o.depthFillHolesRelTolerance, &report); },
+                  [&](std::string *why) {
+                    return FillDepthHoles(views, o.threshBestCost, o.depthFillHolesMaxPixels, o.depthFillHolesTolerance,
+                                          o.depthFillHolesRelTolerance, stepDevice, &report, why);
+                  },
+                  &error)) {
       result->error = "--depthFillHolesMaxPixels: " + error;
       return false;
     }
@@ -939,8 +1011,16 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (!read_views("--depthSmoothSigma")) return false;
     DepthSmoothReport report;
     std::string error;
-    if (!SmoothDepths(views, o.threshBestCost, o.depthSmoothSigma, o.depthSmoothTruncate, o.depthSmoothTolerance,
-                      o.depthSmoothRelTolerance, (int)o.depthSmoothIterations, o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+    if (!run_step("--depthSmoothSigma",
+                  [&]() {
+                    return resident.Smooth(o.depthSmoothSigma, o.depthSmoothTruncate, o.depthSmoothTolerance, o.depthSmoothRelTolerance,
+                                           (int)o.depthSmoothIterations, &report);
+                  },
+                  [&](std::string *why) {
+                    return SmoothDepths(views, o.threshBestCost, o.depthSmoothSigma, o.depthSmoothTruncate, o.depthSmoothTolerance,
+                                        o.depthSmoothRelTolerance, (int)o.depthSmoothIterations, stepDevice, &report, why);
+                  },
+                  &error)) {
       result->error = "--depthSmoothSigma: " + error;
       return false;
     }
@@ -963,8 +1043,16 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (!read_views("--depthConsistencyMinViews")) return false;
     DepthConsistencyReport report;
     std::string error;
-    if (!FilterDepthConsistency(views, o.threshBestCost, (int)o.depthConsistencyMinViews, o.depthConsistencyTolerance,
-                                o.depthConsistencyRelTolerance, o.devices.empty() ? 0 : o.devices[0], &report, &error)) {
+    if (!run_step("--depthConsistencyMinViews",
+                  [&]() {
+                    return resident.FilterConsistency((int)o.depthConsistencyMinViews, o.depthConsistencyTolerance,
+                                                      o.depthConsistencyRelTolerance, &report);
+                  },
+                  [&](std::string *why) {
+                    return FilterDepthConsistency(views, o.threshBestCost, (int)o.depthConsistencyMinViews, o.depthConsistencyTolerance,
+                                                  o.depthConsistencyRelTolerance, stepDevice, &report, why);
+                  },
+                  &error)) {
       result->error = "--depthConsistencyMinViews: " + error;
       return false;
     }
@@ -1001,8 +1089,13 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
       }
     SceneBoundsReport bounds;
     std::string error;
-    if (!EstimateSceneBounds(views, o.threshBestCost, axes, o.gridAutoBoundsTrim, (int)o.gridAutoBoundsPixelStep,
-                             o.devices.empty() ? 0 : o.devices[0], &bounds, &error)) {
+    if (!run_step("--gridAutoBounds",
+                  [&]() { return resident.EstimateBounds(axes, o.gridAutoBoundsTrim, (int)o.gridAutoBoundsPixelStep, &bounds); },
+                  [&](std::string *why) {
+                    return EstimateSceneBounds(views, o.threshBestCost, axes, o.gridAutoBoundsTrim, (int)o.gridAutoBoundsPixelStep, stepDevice,
+                                               &bounds, why);
+                  },
+                  &error)) {
       result->error = "--gridAutoBounds: " + error;
       return 1;
     }
@@ -1086,6 +1179,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   if (o.depthSmoothSigmaGiven && !o.gridAutoBounds && !smooth_views()) return 1;
   if (o.depthConsistencyMinViews >= 0 && !o.gridAutoBounds && !filter_views()) return 1;
   if (!views.empty()) filter.SetViews(views);
+  if (resident.Loaded()) filter.SetResidentViews(&resident);
   if (!filter.Update()) {
     result->error = filter.LastError().empty() ? "the reconstruction filter refused its parameters" : filter.LastError();
     return 1;

@@ -127,6 +127,9 @@ struct Options {
   // not in the reference: remove the depth maps' small segments on the GPU before anything else sees them
   // (dmi_filter_depth_speckles: -1 = flag not given), with an absolute and a relative depth tolerance between 4-neighbours
   long long depthSpeckleMinPixels = -1;
+  // --depthStagedFilters (not in the reference): run the depth-map steps through the context-free calls, every step with its own
+  // upload and download, instead of on a resident view set.  Needs one of the five flags that use the set.
+  bool depthStagedFilters = false;
   double depthSpeckleTolerance = 0.0, depthSpeckleRelTolerance = 0.01;
   bool depthSpeckleToleranceGiven = false, depthSpeckleRelToleranceGiven = false;
   // not in the reference: fill the depth maps' small holes on the GPU behind the speckle filter (dmi_fill_depth_holes: -1 = flag

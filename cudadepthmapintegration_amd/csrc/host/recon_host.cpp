@@ -356,8 +356,8 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
   }
   const size_t npix = (size_t)W * H;
   const bool multi = !Devices.empty();
-  if (multi && (ColorSink || KeepContext)) {
-    Error = "ProcessDepthMap: a colour sink and a kept context need a single GPU";
+  if (multi && (ColorSink || KeepContext || ResidentSet)) {
+    Error = "ProcessDepthMap: a colour sink, a kept context and a resident view set need a single GPU";
     return false;
   }
   if (KeptContext) dmi_destroy(KeptContext);
@@ -513,7 +513,7 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
     // costs is thresholded on the device (fused into the upload kernel); a mixed chunk on this copy, view by view.
     bool every_view_has_cost = true;
     for (size_t v = 0; v < c.count; ++v) every_view_has_cost = every_view_has_cost && c.has_cost[v];
-    if (!every_view_has_cost)
+    if (!every_view_has_cost && !ResidentSet)
       for (size_t v = 0; v < c.count; ++v)
         if (c.has_cost[v])
           for (size_t i = 0; i < npix; ++i)
@@ -523,7 +523,9 @@ bool FusionDriver::ProcessDepthMap(size_t n_views, const ViewSource &fill, doubl
     if (multi) {
       rc = dmi_multi_add_views(mctx, c.depth, cost, thresholdBestCost, c.K4.data(), c.RT.data(), (int32_t)c.count, W, H);
     } else {
-      rc = dmi_add_views(ctx, c.depth, cost, thresholdBestCost, c.K4.data(), c.RT.data(), (int32_t)c.count, W, H);
+      // (a resident set holds the chunk's depths, thresholded when it was loaded: they go from its planes to the context's)
+      rc = ResidentSet ? dmi_add_views_from_set(ctx, ResidentSet, (int32_t)c.first, (int32_t)c.count)
+                       : dmi_add_views(ctx, c.depth, cost, thresholdBestCost, c.K4.data(), c.RT.data(), (int32_t)c.count, W, H);
       // replaces the kernel launches of these views (cu:363); runs while the next chunk is filled and copied.  The LAST chunk
       // is fused together with the copy back, below: slab by slab, each slab on its way to the host under the next one's fusion
       if (c.first + c.count == n_views) {
@@ -603,8 +605,8 @@ bool FusionDriver::ProcessDepthMap(const std::vector<ReconstructionData *> &view
       *error = "ProcessDepthMap: view " + std::to_string(index) + " has no depth map of the size given to CudaInitialize";
       return false;
     }
-    std::memcpy(depth, img->depths.data(), npix * 8);
-    *has_cost = img->best_cost.size() == npix;
+    if (!ResidentSet) std::memcpy(depth, img->depths.data(), npix * 8);  // (a resident set holds the depths: nothing to stage)
+    *has_cost = !ResidentSet && img->best_cost.size() == npix;
     if (*has_cost) std::memcpy(cost, img->best_cost.data(), npix * 8);
     if (FillColor) {
       if (img->color.size() != npix * 3) {
@@ -617,6 +619,13 @@ bool FusionDriver::ProcessDepthMap(const std::vector<ReconstructionData *> &view
     std::memcpy(RT, d->GetMatrixTR(), 16 * 8);  // cu:353
     return true;
   };
+  if (ResidentSet) {
+    dmi_views_info info;
+    if (dmi_views_get_info(ResidentSet, &info) != DMI_OK || (size_t)info.n != views.size() || info.W != W || info.H != H) {
+      Error = "ProcessDepthMap: the resident view set does not hold these views (their number or their size differs)";
+      return false;
+    }
+  }
   return ProcessDepthMap(views.size(), fill, thresholdBestCost, io_scalar);
 }
 
@@ -919,6 +928,165 @@ bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double 
   return true;
 }
 
+// Not in the reference (recon_host.h)
+bool DepthViewSet::Fail(const char *what) {
+  Error = std::string(what) + ": " + dmi_views_last_error(Set);
+  return false;
+}
+
+void DepthViewSet::Release() {
+  if (Set) dmi_views_destroy(Set);
+  Set = nullptr;
+  NViews = 0;
+}
+
+bool DepthViewSet::Load(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int device) {
+  Release();
+  Code = DMI_ERR_INVALID_ARGUMENT;
+  const size_t n = views.size();
+  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
+  if (!first) {
+    Error = "DepthViewSet: no views, or view 0 has no depth map";
+    return false;
+  }
+  if (n > 0x7fffffffu) {
+    Error = "DepthViewSet: too many views";
+    return false;
+  }
+  W = first->dims[0];
+  H = first->dims[1];
+  Dev = device;
+  const size_t npix = (size_t)W * H;
+  for (size_t m = 0; m < n; ++m) {
+    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
+      Error = "DepthViewSet: view " + std::to_string(m) + " has no depth map of the size of view 0";
+      return false;
+    }
+  }
+  if ((Code = dmi_views_create(device, W, H, &Set)) != DMI_OK) {
+    Error = std::string("dmi_views_create: ") + dmi_views_last_error(nullptr);
+    Set = nullptr;
+    return false;
+  }
+  const size_t chunk = std::max<size_t>(1, std::min(n, (size_t(256) << 20) / std::max<size_t>(1, npix * 8)));
+  std::vector<double> depth(chunk * npix), cost(chunk * npix), K4(chunk * 16), RT(chunk * 16);
+  for (size_t m0 = 0; m0 < n; m0 += chunk) {
+    const size_t cnt = std::min(chunk, n - m0);
+    bool every_view_has_cost = true;
+    for (size_t v = 0; v < cnt; ++v) every_view_has_cost = every_view_has_cost && views[m0 + v]->GetDepthMap()->best_cost.size() == npix;
+    for (size_t v = 0; v < cnt; ++v) {
+      const DepthImage *img = views[m0 + v]->GetDepthMap();
+      std::memcpy(depth.data() + v * npix, img->depths.data(), npix * 8);
+      if (every_view_has_cost) {
+        std::memcpy(cost.data() + v * npix, img->best_cost.data(), npix * 8);
+      } else if (img->best_cost.size() == npix) {  // a mixed piece: on this copy, view by view (RD.cxx:159-166)
+        for (size_t i = 0; i < npix; ++i)
+          if (img->best_cost[i] > thresholdBestCost) depth[v * npix + i] = -1;
+      }
+      std::memcpy(K4.data() + v * 16, views[m0 + v]->Get4MatrixK(), 16 * 8);
+      std::memcpy(RT.data() + v * 16, views[m0 + v]->GetMatrixTR(), 16 * 8);
+    }
+    Code = dmi_views_add(Set, depth.data(), every_view_has_cost ? cost.data() : nullptr, thresholdBestCost, K4.data(), RT.data(), (int32_t)cnt);
+    if (Code != DMI_OK) {
+      Fail("dmi_views_add");
+      Release();
+      return false;
+    }
+  }
+  NViews = n;
+  return true;
+}
+
+bool DepthViewSet::FilterSpeckles(long long minPixels, double absTolerance, double relTolerance, DepthSpeckleReport *report) {
+  dmi_views_step_report r;
+  if ((Code = dmi_views_filter_speckles(Set, absTolerance, relTolerance, minPixels, nullptr, &r)) != DMI_OK)
+    return Fail("dmi_views_filter_speckles");
+  if (report) {
+    *report = DepthSpeckleReport();
+    report->views = NViews;
+    report->validPixels = r.valid_before;
+    report->keptPixels = r.valid_after;
+    report->segments = r.groups;
+    report->keptSegments = r.groups_kept;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
+bool DepthViewSet::FillHoles(long long maxPixels, double absTolerance, double relTolerance, DepthHolesReport *report) {
+  dmi_views_step_report r;
+  if ((Code = dmi_views_fill_holes(Set, absTolerance, relTolerance, maxPixels, nullptr, &r)) != DMI_OK) return Fail("dmi_views_fill_holes");
+  if (report) {
+    *report = DepthHolesReport();
+    report->views = NViews;
+    report->holes = r.groups;
+    report->filledHoles = r.groups_kept;
+    report->filledPixels = r.changed;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
+bool DepthViewSet::Smooth(double sigma, double truncate, double absTolerance, double relTolerance, int iterations,
+                          DepthSmoothReport *report) {
+  dmi_views_step_report r;
+  if ((Code = dmi_views_smooth(Set, sigma, truncate, absTolerance, relTolerance, (int32_t)iterations, nullptr, &r)) != DMI_OK)
+    return Fail("dmi_views_smooth");
+  if (report) {
+    *report = DepthSmoothReport();
+    report->views = NViews;
+    report->validPixels = r.valid_after;
+    report->changedPixels = r.changed;
+    report->meanTaps = r.valid_after ? (double)r.aux_sum / (double)r.valid_after : 0.0;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
+bool DepthViewSet::FilterConsistency(int minViews, double absTolerance, double relTolerance, DepthConsistencyReport *report) {
+  dmi_views_step_report r;
+  if ((Code = dmi_views_filter_consistency(Set, absTolerance, relTolerance, (int32_t)minViews, nullptr, &r)) != DMI_OK)
+    return Fail("dmi_views_filter_consistency");
+  if (report) {
+    *report = DepthConsistencyReport();
+    report->views = NViews;
+    report->validPixels = r.valid_before;
+    report->keptPixels = r.valid_after;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
+bool DepthViewSet::EstimateBounds(const double axes[9], double trimFraction, int pixelStep, SceneBoundsReport *report) {
+  SceneBoundsReport r;
+  r.views = NViews;
+  if ((Code = dmi_views_estimate_bounds(Set, axes, trimFraction, (int32_t)pixelStep, r.lo, r.hi, &r.points, &r.kernelMs)) != DMI_OK)
+    return Fail("dmi_views_estimate_bounds");
+  if (report) *report = r;
+  return true;
+}
+
+bool DepthViewSet::Store(const std::vector<ReconstructionData *> &views, double thresholdBestCost) {
+  if (!Set || views.size() != NViews) {
+    Code = DMI_ERR_INVALID_ARGUMENT;
+    Error = "DepthViewSet: these are not the views the set was loaded from";
+    return false;
+  }
+  const size_t npix = (size_t)W * H;
+  std::vector<double> depth(npix);
+  for (size_t m = 0; m < NViews; ++m) {  // (a view at a time: host memory holds one plane more)
+    if ((Code = dmi_views_download(Set, (int32_t)m, 1, depth.data())) != DMI_OK) return Fail("dmi_views_download");
+    DepthImage stored = *views[m]->GetDepthMap();
+    stored.depths = depth;
+    if (stored.best_cost.size() == npix)
+      for (size_t i = 0; i < npix; ++i)
+        if (stored.depths[i] != -1.0 && stored.best_cost[i] > thresholdBestCost) stored.best_cost[i] = thresholdBestCost;
+    views[m]->SetDepthMap(stored);
+  }
+  return true;
+}
+
 // ====================================================================================================
 // vtkCudaReconstructionFilter
 // ====================================================================================================
@@ -1017,6 +1185,20 @@ int ReconstructionFilter::Compute(int gridDims[3], double gridOrig[3], double gr
   KeptContext = nullptr;
   driver.SetInitialGridIsZero(true);  // RequestData zero-filled outScalar just before (filt.cxx:133)
   bool result;
+  if (Resident && !Views.empty()) {
+    if (!Resident->Loaded() || Resident->Views() != Views.size()) {
+      Error = "Error : the resident view set does not hold the views that were set";
+      return -1;
+    }
+    if (!Devices.empty()) {  // several GPUs: the depths come down once and the views go the staged way
+      if (!Resident->Store(Views, ThresholdBestCost)) {
+        Error = Resident->LastError();
+        return -1;
+      }
+    } else {
+      driver.SetResidentSet(Resident->Handle());
+    }
+  }
   if (!Views.empty()) {
     int *depthMapGrid = Views[0]->GetDepthMapDimensions();  // filt.cxx:167-168: sizes from view 0
     driver.CudaInitialize(GridMatrix, gridDims, gridOrig, gridSpacing, RayPotentialThickness, RayPotentialRho,

@@ -173,6 +173,47 @@ struct SceneBoundsReport {
 bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
                          double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error);
 
+// Not in the reference: the views' depths resident on one GPU from the first of the steps above to the fusion (dmi_view_set,
+// include/dmi.h).  Load thresholds and uploads every view once; each step runs where the depths are and fills the
+// report of its staged counterpart above from the counters the device returns, with the same numbers; ReconstructionFilter::
+// SetResidentViews then fuses the depths without a host copy.  The host views keep their files' depths -- only Store writes the
+// set's depths back into them.  Every method returns false on error: LastError() has the text, LastCode() the dmi_status.
+class DepthViewSet {
+ public:
+  DepthViewSet() = default;
+  ~DepthViewSet() { Release(); }
+  DepthViewSet(const DepthViewSet &) = delete;
+  DepthViewSet &operator=(const DepthViewSet &) = delete;
+
+  // The views must share one size and have depth maps.  The threshold goes through dmi_views_add with the best costs where every
+  // view of a piece has them, as FusionDriver does; a view without costs is not thresholded (RD.cxx:156-157).  The views go up in
+  // pieces of at most 256 MiB of depths.
+  bool Load(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int device);
+  bool Loaded() const { return Set != nullptr; }
+  void Release();
+  bool FilterSpeckles(long long minPixels, double absTolerance, double relTolerance, DepthSpeckleReport *report);
+  bool FillHoles(long long maxPixels, double absTolerance, double relTolerance, DepthHolesReport *report);
+  bool Smooth(double sigma, double truncate, double absTolerance, double relTolerance, int iterations, DepthSmoothReport *report);
+  bool FilterConsistency(int minViews, double absTolerance, double relTolerance, DepthConsistencyReport *report);
+  bool EstimateBounds(const double axes[9], double trimFraction, int pixelStep, SceneBoundsReport *report);
+  // The set's depths into the views they were loaded from (one download), so that the staged functions above and SetViews go on
+  // from here: a depth whose best cost the threshold would drop again gets the threshold as its cost, as FillDepthHoles does.
+  bool Store(const std::vector<ReconstructionData *> &views, double thresholdBestCost);
+  dmi_view_set *Handle() const { return Set; }
+  size_t Views() const { return NViews; }
+  int Device() const { return Dev; }
+  const std::string &LastError() const { return Error; }
+  int LastCode() const { return Code; }
+
+ private:
+  bool Fail(const char *what);
+  dmi_view_set *Set = nullptr;
+  size_t NViews = 0;
+  int W = 0, H = 0, Dev = 0;
+  std::string Error;
+  int Code = 0;
+};
+
 // ---- Reconstruction/CudaReconstruction.cu host driver -------------------------------------------------
 // The reference keeps the grid description in global __constant__ state between the two calls (cu:55-64);
 // here it lives in an object.  One FusionDriver = one CudaInitialize + ProcessDepthMap pair.
@@ -226,6 +267,11 @@ class FusionDriver {
   // right after the chunk's depths went to the fusion context: every file is read once.  A view without a UInt8 x 3 Color array
   // of the views' size fails the call with the file's name.  Single GPU only.
   void SetColorSink(dmi_color_context *sink) { ColorSink = sink; }
+  // Not in the reference.  With a resident set, ProcessDepthMap(views, ...) takes the depths of views [first, first + count) of
+  // every chunk from the set (dmi_add_views_from_set) instead of copying them from the host views -- the same chunks, so every voxel
+  // accumulates its views in the same order -- and asks the views for their sizes, matrices and Color planes only.  The set must
+  // hold as many views as the call is given.  Single GPU only.
+  void SetResidentSet(dmi_view_set *set) { ResidentSet = set; }
   // Keep the (single-GPU) fusion context of a successful ProcessDepthMap instead of destroying it: its views stay resident and
   // its grid is the fused one.  TakeContext hands it over (the caller destroys it); the destructor destroys one nobody took.
   void SetKeepContext(bool keep) { KeepContext = keep; }
@@ -256,6 +302,7 @@ class FusionDriver {
   double FuseKernelMs = 0.0;
   std::string Error;
   dmi_color_context *ColorSink = nullptr;
+  dmi_view_set *ResidentSet = nullptr;
   bool KeepContext = false;
   dmi_context *KeptContext = nullptr;
   unsigned char *FillColor = nullptr;  // where the view being filled puts its colour plane (null: not wanted)
@@ -286,6 +333,11 @@ class ReconstructionFilter {
   // In-memory alternative to the two list files: when views are set, Compute uses them instead of reading
   // FilePathVTI / FilePathKRTD (the paths must still be set, as RequestData checks them first, filt.cxx:114).
   void SetViews(const std::vector<ReconstructionData *> &views) { Views = views; }
+  // Not in the reference.  With SetViews: the views' depths are the ones resident in `set` (loaded from these views, in this order)
+  // and reach the fusion by dmi_add_views_from_set, in the chunks SetViews alone would upload them in, so the grid is the same; the
+  // views still give their matrices, and their Color planes to the colour sink.  With several devices (SetDevices) the set's depths
+  // are stored into the views once (DepthViewSet::Store) and the SetViews path is taken.  Null: back to SetViews alone.
+  void SetResidentViews(DepthViewSet *set) { Resident = set; }
 
   // RequestData (filt.cxx:96-151): 1 on success, 0 when a path is unset (filt.cxx:114-118) or rho and
   // thickness are both 0 (filt.cxx:138-142).  Unlike the reference, a failure inside Compute also
@@ -331,6 +383,7 @@ class ReconstructionFilter {
   double InOrigin[3], InSpacing[3];
   bool HasInput = false;
   std::vector<ReconstructionData *> Views;
+  DepthViewSet *Resident = nullptr;
   std::vector<double> OutScalar;
   std::string Error;
   int Device = 0, KernelVariant = 0;

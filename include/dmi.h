@@ -950,6 +950,98 @@ int dmi_smooth_depths(const double *depth, const double *best_cost, double thres
                       double sigma, double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations,
                       int32_t device, double *out_depth, int32_t *out_count, double *kernel_ms);
 
+/* ---- A resident view set: the depth maps stay on the device from the first filter to the fusion (added after
+ * round 5, dmi_abi_version() stays 5) ----
+ * The five calls above are context-free: each uploads the depth planes, runs a few milliseconds of kernels, downloads and frees,
+ * and dmi_add_views uploads the result once more.  A dmi_view_set is bound to one device and one image size and OWNS the planes
+ * between the steps: one upload (dmi_views_add), the steps on the device, and a hand-over to a fusion context that does not pass
+ * through the host (dmi_add_views_from_set).  No arithmetic differs: every result is, byte for byte, what the context-free call
+ * gives.
+ *   D          the set's depths, [n][H][W] f64 on the device in vtk point order, NORMALISED: a valid depth (> 0 and < +inf) or -1.
+ *   dmi_views_add   appends n views.  It stores step 1 of dmi_filter_depth_speckles: D = depth, with -1 wherever best_cost
+ *              (nullable) > threshold and wherever the value is not valid.  The threshold is applied here, once; the costs are not
+ *              kept.  K4 and RT4 ([n][16] each) are kept as they came.  May be called repeatedly.
+ *   The four steps.  Each replaces D by exactly the out_depth that its context-free counterpart returns for depth = D, best_cost =
+ *              NULL, the same parameters, the set's K4 / RT4, n, W and H:
+ *                dmi_views_filter_speckles     dmi_filter_depth_speckles
+ *                dmi_views_fill_holes          dmi_fill_depth_holes
+ *                dmi_views_smooth              dmi_smooth_depths
+ *                dmi_views_filter_consistency  dmi_filter_depth_consistency
+ *              out_size / out_count: a nullable host array [n][H][W], exactly the counterpart's; downloaded only when asked for.
+ *   dmi_views_estimate_bounds   exactly dmi_estimate_scene_bounds on D.  D is not changed.
+ *   dmi_views_download          D of the views [first, first + count), [count][H][W] f64 host in vtk point order.
+ *   "Exactly" means byte for byte, for every piece size: the filters work per view and the consistency count does not depend on an
+ *   order, so cutting the views into pieces cannot change a bit.  dmi_views_set_piece_bytes bounds the f64 planes of the views a
+ *   pass works on at a time (as many whole views as fit, at least one; the default is the context-free calls' 256 MiB); it exists
+ *   to bound the scratch, and so that a test can prove the sentence before at small shapes.
+ *   dmi_views_step_report (r, nullable) is computed on the device, from one read of the planes before and after the step and
+ *   from the roots the labelling passes hold; no plane is downloaded for it:
+ *     step          valid_before / valid_after            changed                      groups / groups_kept               aux_sum
+ *     speckles      pixels with a depth / pixels kept     removed pixels               segments / segments >= min_pixels  0
+ *     holes         valid pixels before / after           filled pixels                holes / holes filled               0
+ *     smooth        valid pixels (equal)                  pixels whose value differs   0 / 0                              sum of the last
+ *                                                         from before the call                                           iteration's taps
+ *     consistency   pixels with a depth / pixels kept     removed pixels               0 / 0                              0
+ *   kernel_ms is the hipEvent time of the counterpart's kernels alone, summed over the pieces; the report's own kernels are timed
+ *   apart (dmi_views_info::last_report_kernel_ms).
+ *   dmi_add_views_from_set leaves ctx in the state that dmi_add_views(ctx, D[first .. first + count), NULL, 0, K4, RT4, count, W, H)
+ *   would: the same tables and the same DMI_DEPTH_AUTO decision (the promotion to f64 when a depth is not an f32 included), the
+ *   same pyramids, validity maps and hole counters, therefore the same fused grid, dmi_get_view_paths and dmi_get_info
+ *   (device_bytes apart: nothing is staged).  The upload pass reads the set's planes where they are: no staging buffer, no host copy.  The context copies and never aliases: the
+ *   set stays unchanged and may be destroyed afterwards.  The call orders the set's stream before the context's upload stream and
+ *   synchronises as dmi_add_views does.  Both must be on one device and the set's size must be that of the context's views
+ *   (DMI_ERR_INVALID_ARGUMENT otherwise); ctx and the set must not be used by another thread meanwhile.
+ * Memory.  16 bytes per pixel and view for the two planes (a step writes the alternate plane and the two change places when it
+ * has succeeded: a failed step leaves D as it was); the scratch of one piece (per pixel of the piece: 16 during an add, 8 for the
+ * speckle filter, 24 for the hole fill, up to 12 for the smoothing, 4 more with out_size / out_count); during a consistency or
+ * bounds pass the planes in image row order and the counts, 12 bytes per pixel and view, freed when the pass ends.  For 256 views of
+ * 1280 x 720 that is about 3.8 GB resident and 6.6 GB at the peak.  dmi_views_info::device_bytes is what the set holds now.
+ *   dmi_views_info   n, W, H, device; device_bytes; steps: the steps that have succeeded since creation (the four, and the bounds
+ *              estimates); h2d_plane_bytes / d2h_plane_bytes: the image-sized data the set has moved over PCIe since creation
+ *              (depths and costs up; downloads, sizes and counts down) -- matrices and the few hundred bytes of a report do not
+ *              count; last_report_kernel_ms: the hipEvent time of the last step's report kernels.
+ * Errors.  Every argument check of the counterpart applies, with the same texts apart from the entry's name, and all checks run
+ * before the device is touched.  DMI_ERR_INVALID_ARGUMENT besides: a null set; a step, estimate, download or hand-over on an empty
+ * set; first < 0, count < 1 or first + count > n; an add whose n < 1 or whose depth, K4 or RT4 is null, or whose threshold is NaN
+ * with a best_cost; piece bytes of 0.  dmi_views_create refuses a null `out` and W or H outside [1, 32768] with
+ * DMI_ERR_INVALID_ARGUMENT before it reports a missing device (DMI_ERR_DEVICE) or an ordinal out of range.  A refused or failed
+ * call leaves D, n and the host arrays as they were.  No call exits or throws; a failure's text is dmi_views_last_error(s)'s (s ==
+ * NULL: the thread's last create failure), for dmi_add_views_from_set dmi_last_error(ctx)'s.  Every call synchronises.
+ * dmi_views_clear drops the views and keeps the allocations; dmi_views_destroy(NULL) is a no-op. */
+typedef struct dmi_view_set dmi_view_set;
+typedef struct dmi_views_info {
+  int32_t n, W, H, device;
+  uint64_t device_bytes;
+  uint64_t steps;
+  uint64_t h2d_plane_bytes, d2h_plane_bytes;
+  double last_report_kernel_ms;
+} dmi_views_info;
+typedef struct dmi_views_step_report {
+  uint64_t valid_before, valid_after, changed, groups, groups_kept, aux_sum;
+  double kernel_ms;
+} dmi_views_step_report;
+int dmi_views_create(int32_t device, int32_t W, int32_t H, dmi_view_set **out);
+void dmi_views_destroy(dmi_view_set *s);
+const char *dmi_views_last_error(const dmi_view_set *s);
+int dmi_views_add(dmi_view_set *s, const double *depth, const double *best_cost, double threshold, const double *K4,
+                  const double *RT4, int32_t n);
+int dmi_views_clear(dmi_view_set *s);
+int dmi_views_get_info(dmi_view_set *s, dmi_views_info *out);
+size_t dmi_sizeof_views_info(void);
+int dmi_views_set_piece_bytes(dmi_view_set *s, uint64_t bytes);
+int dmi_views_filter_speckles(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t min_pixels, int32_t *out_size,
+                              dmi_views_step_report *r);
+int dmi_views_fill_holes(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t max_pixels, int32_t *out_size,
+                         dmi_views_step_report *r);
+int dmi_views_smooth(dmi_view_set *s, double sigma, double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations,
+                     int32_t *out_count, dmi_views_step_report *r);
+int dmi_views_filter_consistency(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int32_t min_views, int32_t *out_count,
+                                 dmi_views_step_report *r);
+int dmi_views_estimate_bounds(dmi_view_set *s, const double *axes9, double trim_fraction, int32_t pixel_step, double lo[3],
+                              double hi[3], uint64_t *n_points, double *kernel_ms);
+int dmi_views_download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth);
+int dmi_add_views_from_set(dmi_context *ctx, const dmi_view_set *s, int32_t first, int32_t count);
+
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default
  * stream, cu:302-386); the seam where this plugs in is the pair of driver calls at
