@@ -85,6 +85,11 @@ class ViewsStepReportC(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class ViewsPointsReportC(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("owned", ctypes.c_uint64), ("points", ctypes.c_uint64),
+                ("with_normal", ctypes.c_uint64), ("kernel_ms", ctypes.c_double)]
+
+
 class MultiOptionsC(ctypes.Structure):
     _fields_ = [("grid_dtype", ctypes.c_int32), ("depth_storage", ctypes.c_int32), ("kernel_variant", ctypes.c_int32),
                 ("partition", ctypes.c_int32), ("exchange", ctypes.c_int32), ("n_slabs", ctypes.c_int32)]
@@ -140,6 +145,7 @@ ABI_SYMBOLS = [
     "dmi_views_create", "dmi_views_destroy", "dmi_views_last_error", "dmi_views_add", "dmi_views_clear", "dmi_views_get_info",
     "dmi_sizeof_views_info", "dmi_views_set_piece_bytes", "dmi_views_filter_speckles", "dmi_views_fill_holes", "dmi_views_smooth",
     "dmi_views_filter_consistency", "dmi_views_estimate_bounds", "dmi_views_download", "dmi_add_views_from_set",
+    "dmi_views_build_points", "dmi_views_download_points", "dmi_views_get_points_pass_ms",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -332,6 +338,11 @@ def load() -> ctypes.CDLL:
         L.dmi_views_estimate_bounds.argtypes = [vp, dp, dbl, i32, dp, dp, ctypes.POINTER(ctypes.c_uint64), dp]
         L.dmi_views_download.argtypes = [vp, i32, i32, dp]
         L.dmi_add_views_from_set.argtypes = [vp, vp, i32, i32]
+    if hasattr(L, "dmi_views_build_points"):
+        u64 = ctypes.c_uint64
+        L.dmi_views_build_points.argtypes = [vp, dbl, dbl, dbl, dbl, i32, i32, i32, ctypes.POINTER(u64), ctypes.POINTER(ViewsPointsReportC)]
+        L.dmi_views_download_points.argtypes = [vp, u64, u64, dp, ctypes.POINTER(ctypes.c_float), i32p, i32p, i32p]
+        L.dmi_views_get_points_pass_ms.argtypes = [vp, dp]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1413,6 +1424,45 @@ class ViewSet:
         out = np.empty((max(count, 0), self.H, self.W), dtype=np.float64)
         self._check(self._lib.dmi_views_download(self._h, int(first), count, _dp(out)))
         return out
+
+    def build_points(self, *, abs_tolerance: float, rel_tolerance: float, normal_abs_tolerance: float | None = None,
+                     normal_rel_tolerance: float | None = None, min_views: int = 1, pixel_step: int = 1, dedupe: bool = True) -> dict:
+        """The fused point cloud of the set's depths (include/dmi.h: dmi_views_build_points): the valid pixels, every pixel_step-th
+        of every pixel_step-th row, that at least min_views other views agree with, and -- with dedupe -- that no lower view holds
+        already, each with a normal from its own depth map.  The normal tolerances default to the agreement pair (None).  The points
+        stay on the device (download_points) until the depths change.  Returns the report: valid, candidates, owned, points,
+        with_normal, kernel_ms."""
+        n_abs = abs_tolerance if normal_abs_tolerance is None else normal_abs_tolerance
+        n_rel = rel_tolerance if normal_rel_tolerance is None else normal_rel_tolerance
+        count, r = ctypes.c_uint64(0), ViewsPointsReportC()
+        self._check(self._lib.dmi_views_build_points(self._h, float(abs_tolerance), float(rel_tolerance), float(n_abs), float(n_rel),
+                                                     int(min_views), int(pixel_step), int(dedupe), ctypes.byref(count), ctypes.byref(r)))
+        self._n_points = int(count.value)
+        return {name: getattr(r, name) for name, _ in ViewsPointsReportC._fields_}
+
+    def points_pass_ms(self) -> dict:
+        """The last build_points' kernel time by pass (ms): flip, count, flags, scan (the block counts with it), scatter."""
+        out = np.zeros(5, dtype=np.float64)
+        self._check(self._lib.dmi_views_get_points_pass_ms(self._h, _dp(out)))
+        return dict(zip(("flip", "count", "flags", "scan", "scatter"), out.tolist()))
+
+    def download_points(self, first: int = 0, count: int | None = None) -> dict:
+        """The points [first, first + count) of the last build_points (all from `first` on by default): xyz f64 [count, 3], normal
+        f32 [count, 3] (zero where a point has none), view, pixel (py * W + px in image coordinates) and count (the views that
+        agree) int32 [count], in ascending (view, py, px)."""
+        first = int(first)
+        if count is None:  # (what the last build reported; whether those points still stand is the library's to say)
+            count = max(getattr(self, "_n_points", 0) - first, 0)
+        count = int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        arrays = dict(xyz=np.empty((count, 3), dtype=np.float64), normal=np.empty((count, 3), dtype=np.float32),
+                      view=np.empty(count, dtype=np.int32), pixel=np.empty(count, dtype=np.int32), count=np.empty(count, dtype=np.int32))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        self._check(self._lib.dmi_views_download_points(
+            self._h, first, count, _dp(arrays["xyz"]), arrays["normal"].ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            arrays["view"].ctypes.data_as(i32p), arrays["pixel"].ctypes.data_as(i32p), arrays["count"].ctypes.data_as(i32p)))
+        return arrays
 
 
 class ColorContext:

@@ -60,9 +60,20 @@ struct WholeSetScratch {
   dmi_view_set *s;
   ~WholeSetScratch() {
     (void)hipStreamSynchronize(s->stream);
-    dmi::free_buffers({&s->flipped, &s->counts, &s->cameras, &s->state, &s->hist}, s->device_bytes);
+    dmi::free_buffers({&s->flipped, &s->counts, &s->cameras, &s->state, &s->hist, &s->flags, &s->block_counts, &s->block_offsets},
+                      s->device_bytes);
   }
 };
+
+// D changes, or the views do: the points of the last build describe neither any longer
+void drop_points(dmi_view_set *s) {
+  if (s->points.ptr) {
+    (void)hipSetDevice(s->device);
+    dmi::free_buffers({&s->points}, s->device_bytes);
+  }
+  s->n_points = 0;
+  s->points_current = false;
+}
 
 struct Pieces {
   size_t plane;  // pixels of a view
@@ -104,6 +115,7 @@ int end_step(dmi_view_set *s, rules::Step step, double pass_ms, double report_ms
   unsigned long long c[dmi::kVsCounters];
   VS_HIP(s, hipMemcpyAsync(c, s->counters.ptr, sizeof(c), hipMemcpyDeviceToHost, s->stream));
   VS_HIP(s, hipStreamSynchronize(s->stream));
+  drop_points(s);
   s->current ^= 1;
   s->steps += 1;
   s->last_report_kernel_ms = report_ms;
@@ -212,6 +224,7 @@ int add(dmi_view_set *s, const double *depth, const double *best_cost, double th
   s->K4.insert(s->K4.end(), K4, K4 + 16 * (size_t)n);
   s->RT4.insert(s->RT4.end(), RT4, RT4 + 16 * (size_t)n);
   s->n = (int32_t)total;
+  drop_points(s);
   return DMI_OK;
 }
 
@@ -508,6 +521,140 @@ int download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth) {
   return DMI_OK;
 }
 
+int build_points(dmi_view_set *s, double abs_tolerance, double rel_tolerance, double normal_abs_tolerance, double normal_rel_tolerance,
+                 int32_t min_views, int32_t pixel_step, int32_t dedupe, uint64_t *n_points, dmi_views_points_report *r) {
+  namespace pr = dmi::points_rules;
+  const std::string entry = "dmi_views_build_points: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
+  if (!n_points) return bad("n_points is null");
+  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(normal_abs_tolerance)) return bad("normal_abs_tolerance must be finite and >= 0");
+  if (!finite_and_not_negative(normal_rel_tolerance)) return bad("normal_rel_tolerance must be finite and >= 0");
+  if (min_views < 0) return bad("min_views >= 0 required");
+  if (pixel_step < 1) return bad("pixel_step >= 1 required");
+  if (dedupe != 0 && dedupe != 1) return bad("dedupe must be 0 or 1");
+  if (s->n < 1) return bad("the set holds no views");
+  if (!pr::blocks_fit_one_launch(s->n, s->W, s->H)) return bad("n * ceil(W * H / 256) must stay below 2^31");
+  if (const int32_t m = dmi::first_view_with_other_k(s->K4.data(), s->n); m >= 0) return bad(dmi::other_k_message(m));
+
+  const int W = s->W, H = s->H, n = s->n;
+  const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
+  const Pieces p = pieces_of(s, n);
+  const int64_t blocks = pr::total_blocks(n, W, H);
+  const dmi::PointsParams params{W, H, min_views, pixel_step, dedupe, abs_tolerance, rel_tolerance, normal_abs_tolerance,
+                                 normal_rel_tolerance};
+  int rc = begin_step(s);
+  if (rc != DMI_OK) return rc;
+  WholeSetScratch scratch{s};
+  VS_HIP(s, grow(s, s->flipped, (uint64_t)n * p.plane * 8));
+  VS_HIP(s, grow(s, s->counts, (uint64_t)n * p.plane * sizeof(int32_t)));
+  VS_HIP(s, grow(s, s->flags, (uint64_t)n * p.plane));
+  VS_HIP(s, grow(s, s->block_counts, (uint64_t)blocks * sizeof(uint32_t)));
+  VS_HIP(s, grow(s, s->block_offsets, ((uint64_t)blocks + 1) * sizeof(uint64_t)));  // the total stands behind the offsets
+  if ((rc = upload_cameras(s)) != DMI_OK) return rc;
+  VS_HIP(s, hipMemsetAsync(s->counts.ptr, 0, (size_t)n * p.plane * sizeof(int32_t), s->stream));
+  VS_HIP(s, hipMemsetAsync(s->flags.ptr, 0, (size_t)n * p.plane, s->stream));
+
+  double pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if ((rc = flip_planes(s, p, &pass_ms[0])) != DMI_OK) return rc;
+  if (n > 1) {
+    VS_HIP(s, dmi::run_consistency_count(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
+                                          rel_tolerance, tuning, s->counts.as<int32_t>(), nullptr, s->stream, s->events));
+    VS_HIP(s, hipStreamSynchronize(s->stream));
+    float ms = 0.f;
+    VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
+    pass_ms[1] = (double)ms;
+  }
+  uint64_t *const offsets = s->block_offsets.as<uint64_t>();
+  VS_HIP(s, hipEventRecord(s->events[0], s->stream));
+  VS_HIP(s, dmi::launch_points_flags(s->flipped.as<double>(), s->counts.as<int32_t>(), s->cameras.as<dmi::ConsistencyCamera>(), n, params,
+                                      s->flags.as<uint8_t>(), s->stream));
+  VS_HIP(s, hipEventRecord(s->events[1], s->stream));
+  VS_HIP(s, dmi::launch_points_block_counts(s->flags.as<uint8_t>(), n, W, H, s->block_counts.as<uint32_t>(), s->stream));
+  VS_HIP(s, dmi::launch_points_scan(s->block_counts.as<uint32_t>(), blocks, offsets, offsets + blocks, counters_of(s), s->stream));
+  VS_HIP(s, hipEventRecord(s->events[2], s->stream));
+  uint64_t total = 0;
+  VS_HIP(s, hipMemcpyAsync(&total, offsets + blocks, sizeof(total), hipMemcpyDeviceToHost, s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+
+  // the arrays, at exactly the size needed; the points of an earlier build stay until these are complete
+  pr::Layout layout;
+  if (!pr::layout_of(total, &layout)) return fail(s, DMI_ERR_OUT_OF_MEMORY, entry + "the points do not fit 64 bits of bytes");
+  dmi::DeviceBuffer fresh;
+  struct Guard {
+    dmi_view_set *s;
+    dmi::DeviceBuffer *b;
+    ~Guard() { dmi::free_buffers({b}, s->device_bytes); }  // (empty once the buffer has become the set's)
+  } guard{s, &fresh};
+  if (total) VS_HIP(s, grow(s, fresh, layout.bytes));
+  VS_HIP(s, hipEventRecord(s->events[3], s->stream));
+  if (total) {  // (the block counts have been scanned: their memory takes the blocks' normals)
+    VS_HIP(s, dmi::launch_points_scatter(s->flipped.as<double>(), s->counts.as<int32_t>(), s->cameras.as<dmi::ConsistencyCamera>(),
+                                          s->flags.as<uint8_t>(), n, params, offsets, layout, fresh.as<unsigned char>(),
+                                          s->block_counts.as<uint32_t>(), s->stream));
+    VS_HIP(s, dmi::launch_points_sum_normals(s->block_counts.as<uint32_t>(), blocks, counters_of(s), s->stream));
+  }
+  VS_HIP(s, hipEventRecord(s->events[4], s->stream));
+  unsigned long long c[dmi::kPtCounters];
+  VS_HIP(s, hipMemcpyAsync(c, s->counters.ptr, sizeof(c), hipMemcpyDeviceToHost, s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  for (int e = 0; e < 2; ++e) {
+    float ms = 0.f;
+    VS_HIP(s, hipEventElapsedTime(&ms, s->events[e], s->events[e + 1]));
+    pass_ms[2 + e] = (double)ms;
+  }
+  float ms = 0.f;
+  VS_HIP(s, hipEventElapsedTime(&ms, s->events[3], s->events[4]));
+  pass_ms[4] = (double)ms;
+
+  drop_points(s);
+  std::swap(s->points, fresh);
+  s->n_points = total;
+  s->points_current = true;
+  s->steps += 1;
+  double kernel_ms = 0.0;
+  for (int e = 0; e < 5; ++e) kernel_ms += (s->points_pass_ms[e] = pass_ms[e]);
+  *n_points = total;
+  if (r) {
+    r->valid = c[dmi::kPtValid];
+    r->candidates = c[dmi::kPtCandidates];
+    r->owned = c[dmi::kPtOwned];
+    r->points = total;
+    r->with_normal = c[dmi::kPtWithNormal];
+    r->kernel_ms = kernel_ms;
+  }
+  return DMI_OK;
+}
+
+int download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz, float *normal, int32_t *view, int32_t *pixel,
+                    int32_t *n_views) {
+  namespace pr = dmi::points_rules;
+  const std::string entry = "dmi_views_download_points: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + "the set holds no points: dmi_views_build_points comes first");
+  if (first > s->n_points || count > s->n_points - first)
+    return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "first + count must not exceed the number of points");
+  if (count == 0) return DMI_OK;
+  pr::Layout layout;
+  (void)pr::layout_of(s->n_points, &layout);  // (it fitted when the points were built)
+  const unsigned char *const base = s->points.as<unsigned char>();
+  VS_HIP(s, hipSetDevice(s->device));
+  auto copy = [&](void *dst, uint64_t array, uint64_t stride) {
+    return dst ? hipMemcpyAsync(dst, base + pr::entry_offset(array, first, stride), (size_t)(count * stride), hipMemcpyDeviceToHost,
+                                s->stream)
+               : hipSuccess;
+  };
+  VS_HIP(s, copy(xyz, layout.xyz, 24));
+  VS_HIP(s, copy(normal, layout.normal, 12));
+  VS_HIP(s, copy(view, layout.view, 4));
+  VS_HIP(s, copy(pixel, layout.pixel, 4));
+  VS_HIP(s, copy(n_views, layout.count, 4));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  return DMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -522,7 +669,7 @@ void dmi_views_destroy(dmi_view_set *s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   dmi::free_buffers({&s->plane[0], &s->plane[1], &s->stage_depth, &s->stage_cost, &s->label, &s->record, &s->rim_lo, &s->rim_hi,
                      &s->border_down, &s->border_right, &s->second, &s->aux, &s->flipped, &s->counts, &s->cameras, &s->state, &s->hist,
-                     &s->counters});
+                     &s->flags, &s->block_counts, &s->block_offsets, &s->points, &s->counters});
   dmi::destroy_events(s->events);
   dmi::destroy_events(s->report_events);
   if (s->handed_over) (void)hipEventDestroy(s->handed_over);
@@ -541,6 +688,7 @@ int dmi_views_add(dmi_view_set *s, const double *depth, const double *best_cost,
 int dmi_views_clear(dmi_view_set *s) {
   return guarded(s, "dmi_views_clear", [&]() -> int {
     if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_clear: the set is null");
+    drop_points(s);
     s->n = 0;
     s->K4.clear();
     s->RT4.clear();
@@ -607,6 +755,31 @@ int dmi_views_estimate_bounds(dmi_view_set *s, const double *axes9, double trim_
 
 int dmi_views_download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth) {
   return guarded(s, "dmi_views_download", [&]() -> int { return download(s, first, count, out_depth); });
+}
+
+int dmi_views_build_points(dmi_view_set *s, double abs_tolerance, double rel_tolerance, double normal_abs_tolerance,
+                           double normal_rel_tolerance, int32_t min_views, int32_t pixel_step, int32_t dedupe, uint64_t *n_points,
+                           dmi_views_points_report *r) {
+  return guarded(s, "dmi_views_build_points", [&]() -> int {
+    return build_points(s, abs_tolerance, rel_tolerance, normal_abs_tolerance, normal_rel_tolerance, min_views, pixel_step, dedupe,
+                        n_points, r);
+  });
+}
+
+int dmi_views_download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz, float *normal, int32_t *view, int32_t *pixel,
+                              int32_t *n_views) {
+  return guarded(s, "dmi_views_download_points",
+                 [&]() -> int { return download_points(s, first, count, xyz, normal, view, pixel, n_views); });
+}
+
+int dmi_views_get_points_pass_ms(dmi_view_set *s, double out_ms[5]) {
+  return guarded(s, "dmi_views_get_points_pass_ms", [&]() -> int {
+    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_points_pass_ms: the set is null");
+    if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_points_pass_ms: out_ms is null");
+    if (!s->points_current) return fail(s, DMI_ERR_STATE, "dmi_views_get_points_pass_ms: the set holds no points");
+    for (int e = 0; e < 5; ++e) out_ms[e] = s->points_pass_ms[e];
+    return DMI_OK;
+  });
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "../../include/dmi.h"
 #include "depth_consistency.h"
 #include "depth_holes.h"
+#include "depth_points.h"
 #include "depth_smooth.h"
 #include "depth_speckle.h"
 #include "dmi_buffer.h"
@@ -29,7 +30,15 @@ struct dmi_view_set {
   dmi::DeviceBuffer stage_depth, stage_cost, label, record, rim_lo, rim_hi, border_down, border_right, second, aux;
   // held during a consistency or bounds pass only: the planes in image row order, the counts, the cameras, the select's state
   dmi::DeviceBuffer flipped, counts, cameras, state, hist;
-  dmi::DeviceBuffer counters;  // dmi::kVsCounters u64 (view_set_kernels.h)
+  // held during dmi_views_build_points only, beside flipped, counts and cameras: a flag byte per pixel, and per block of the
+  // compaction its count and its offset (depth_points_rules.h)
+  dmi::DeviceBuffer flags, block_counts, block_offsets;
+  // the point cloud of the last dmi_views_build_points, 48 bytes per point (points_rules::Layout); dropped by whatever changes D
+  dmi::DeviceBuffer points;
+  uint64_t n_points = 0;
+  bool points_current = false;
+  double points_pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last build's flip, count, flags, block counts + scan, scatter
+  dmi::DeviceBuffer counters;  // dmi::kVsCounters u64 (view_set_kernels.h); a build's dmi::kPtCounters stand in the same array
   hipStream_t stream = nullptr;
   hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // around a piece's passes
   hipEvent_t report_events[2] = {nullptr, nullptr};                      // around a piece's report kernels

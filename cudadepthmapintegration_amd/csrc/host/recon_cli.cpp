@@ -306,6 +306,51 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                      return into_count(&o->depthSmoothIterations)(values) && o->depthSmoothIterations >= 1 &&
                                             o->depthSmoothIterations <= dmi::kDepthSmoothMaxIterations;
                                    }}},
+      {"--outputPointCloudFilename", {Kind::kValue, "write the fused point cloud of the depth maps to this .vtp: the points the views "
+                                                    "agree on, each once, with a normal taken from its own depth map -- built on the GPU "
+                                                    "from the depth maps that are fused, behind every --depth... step.  Points "
+                                                    "(Float64), one vertex cell per point, and the point arrays Normals, ViewIndex and "
+                                                    "NbAgreeingViews.  Needs --pointCloudTolerance or --pointCloudRelTolerance unless "
+                                                    "--depthConsistencyMinViews gives the tolerances; the depth maps stay on the GPU, so "
+                                                    "--depthStagedFilters is refused (not in the reference)",
+                                      into_string(&o->outputPointCloudFilename)}},
+      {"--pointCloudMinViews", {Kind::kValue, "with --outputPointCloudFilename: a pixel becomes a point only if at least this many other "
+                                              "views agree with its depth (a non-negative integer, default 1; not in the reference)",
+                                [o](const std::vector<std::string> &values) {
+                                  o->pointCloudMinViewsGiven = true;
+                                  return into_count(&o->pointCloudMinViews)(values) && o->pointCloudMinViews <= 0x7fffffffLL;
+                                }}},
+      {"--pointCloudTolerance", {Kind::kValue, "with --outputPointCloudFilename: two depths agree within this distance (world units, "
+                                               "finite, >= 0) plus the relative tolerance; default: --depthConsistencyTolerance when "
+                                               "--depthConsistencyMinViews is given (not in the reference)",
+                                 into_checked_double(&o->pointCloudTolerance, &o->pointCloudToleranceGiven, [](double x) { return x >= 0.0; })}},
+      {"--pointCloudRelTolerance", {Kind::kValue, "with --outputPointCloudFilename: ... plus this share of the distance from the other "
+                                                  "view's camera (finite, >= 0); default: --depthConsistencyRelTolerance when "
+                                                  "--depthConsistencyMinViews is given (not in the reference)",
+                                    into_checked_double(&o->pointCloudRelTolerance, &o->pointCloudRelToleranceGiven,
+                                                        [](double x) { return x >= 0.0; })}},
+      {"--pointCloudNormalTolerance", {Kind::kValue, "with --outputPointCloudFilename: a neighbouring pixel enters a point's normal only "
+                                                     "if its depth lies within this distance (finite, >= 0) plus the relative normal "
+                                                     "tolerance of the point's; default: the agreement tolerance (not in the reference)",
+                                       into_checked_double(&o->pointCloudNormalTolerance, &o->pointCloudNormalToleranceGiven,
+                                                           [](double x) { return x >= 0.0; })}},
+      {"--pointCloudNormalRelTolerance", {Kind::kValue, "with --outputPointCloudFilename: ... plus this share of the point's depth "
+                                                        "(finite, >= 0); default: the relative agreement tolerance (not in the reference)",
+                                          into_checked_double(&o->pointCloudNormalRelTolerance, &o->pointCloudNormalRelToleranceGiven,
+                                                              [](double x) { return x >= 0.0; })}},
+      {"--pointCloudPixelStep", {Kind::kValue, "with --outputPointCloudFilename: only every k-th pixel of every k-th row becomes a point "
+                                               "(an integer >= 1, default 1; not in the reference)",
+                                 [o](const std::vector<std::string> &values) {
+                                   o->pointCloudPixelStepGiven = true;
+                                   return into_count(&o->pointCloudPixelStep)(values) && o->pointCloudPixelStep >= 1 &&
+                                          o->pointCloudPixelStep <= 0x7fffffffLL;
+                                 }}},
+      {"--pointCloudKeepDuplicates", {Kind::kFlag, "with --outputPointCloudFilename: every view keeps its points; without the flag a "
+                                                   "point that a lower view holds already is dropped (not in the reference)",
+                                      into_flag(&o->pointCloudKeepDuplicates)}},
+      {"--pointCloudColors", {Kind::kFlag, "with --outputPointCloudFilename: the point array Color (UInt8 RGB), each point's pixel of its "
+                                           "view's Color array; every depth map file must carry one (not in the reference)",
+                              into_flag(&o->pointCloudColors)}},
       {"--depthStagedFilters", {Kind::kFlag, "with --depthSpeckleMinPixels, --depthFillHolesMaxPixels, --depthSmoothSigma, "
                                              "--depthConsistencyMinViews or --gridAutoBounds: run these steps through the staged "
                                              "calls, each with an upload and a download of its own, instead of keeping the depth "
@@ -528,6 +573,44 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
     err << "Bad value for --depthConsistencyMinViews\n" << HelpText();
     return false;
   }
+  const bool pointCloud = !o->outputPointCloudFilename.empty();
+  for (const auto &flag : {std::make_pair("--pointCloudMinViews", o->pointCloudMinViewsGiven),
+                           std::make_pair("--pointCloudTolerance", o->pointCloudToleranceGiven),
+                           std::make_pair("--pointCloudRelTolerance", o->pointCloudRelToleranceGiven),
+                           std::make_pair("--pointCloudNormalTolerance", o->pointCloudNormalToleranceGiven),
+                           std::make_pair("--pointCloudNormalRelTolerance", o->pointCloudNormalRelToleranceGiven),
+                           std::make_pair("--pointCloudPixelStep", o->pointCloudPixelStepGiven),
+                           std::make_pair("--pointCloudKeepDuplicates", o->pointCloudKeepDuplicates),
+                           std::make_pair("--pointCloudColors", o->pointCloudColors)})
+    if (flag.second && !pointCloud) {
+      err << "Error : " << flag.first << " needs --outputPointCloudFilename.\n" << HelpText();
+      return false;
+    }
+  if (pointCloud) {
+    if (!ends_with_or_contains(o->outputPointCloudFilename, ".vtp")) {
+      err << "Error : --outputPointCloudFilename must name a .vtp file.\n" << HelpText();
+      return false;
+    }
+    if (o->depthStagedFilters) {
+      err << "Error : --outputPointCloudFilename builds the points on the resident depth maps, which --depthStagedFilters does not "
+             "keep.\n"
+          << HelpText();
+      return false;
+    }
+    if (!o->pointCloudToleranceGiven && !o->pointCloudRelToleranceGiven && o->depthConsistencyMinViews < 0) {
+      err << "Error : --outputPointCloudFilename needs --pointCloudTolerance or --pointCloudRelTolerance when "
+             "--depthConsistencyMinViews does not give the tolerances.\n"
+          << HelpText();
+      return false;
+    }
+    // the agreement pair from the consistency filter's where that was given, the normal pair from the agreement pair
+    if (o->depthConsistencyMinViews >= 0) {
+      if (!o->pointCloudToleranceGiven) o->pointCloudTolerance = o->depthConsistencyTolerance;
+      if (!o->pointCloudRelToleranceGiven) o->pointCloudRelTolerance = o->depthConsistencyRelTolerance;
+    }
+    if (!o->pointCloudNormalToleranceGiven) o->pointCloudNormalTolerance = o->pointCloudTolerance;
+    if (!o->pointCloudNormalRelToleranceGiven) o->pointCloudNormalRelTolerance = o->pointCloudRelTolerance;
+  }
   if (o->depthStagedFilters && o->depthSpeckleMinPixels < 0 && o->depthFillHolesMaxPixels < 0 && !o->depthSmoothSigmaGiven &&
       o->depthConsistencyMinViews < 0 && !o->gridAutoBounds) {
     err << "Error : --depthStagedFilters needs --depthSpeckleMinPixels, --depthFillHolesMaxPixels, --depthSmoothSigma, "
@@ -734,6 +817,66 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
     *error = "WriteStructuredGrid: write failed: " + path;
+    return false;
+  }
+  return true;
+}
+
+bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
+                     const int32_t *agreeing, const uint8_t *color, std::string *error) {
+  if (nPoints < 0) {
+    *error = "WritePointCloud: negative count";
+    return false;
+  }
+  std::ofstream out(path, std::ios::binary);
+  if (!out) {
+    *error = "WritePointCloud: cannot open " + path;
+    return false;
+  }
+  const uint64_t n = (uint64_t)nPoints, header = sizeof(uint64_t);
+  const uint64_t point_bytes = n * 3 * sizeof(double), cell_bytes = n * sizeof(int64_t), normal_bytes = n * 3 * sizeof(float),
+                 int_bytes = n * sizeof(int32_t), rgb_bytes = n * 3;
+  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, Color -- [UInt64 byte count] bytes each
+  const uint64_t conn_offset = header + point_bytes, offsets_offset = conn_offset + header + cell_bytes;
+  const uint64_t normal_offset = offsets_offset + header + cell_bytes, view_offset = normal_offset + header + normal_bytes;
+  const uint64_t agreeing_offset = view_offset + header + int_bytes, color_offset = agreeing_offset + header + int_bytes;
+  out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
+         "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
+      << nPoints << "\" NumberOfVerts=\"" << nPoints << "\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"0\">\n"
+      << "      <PointData Normals=\"Normals\">\n        <DataArray type=\"Float32\" Name=\"Normals\" NumberOfComponents=\"3\" "
+         "format=\"appended\" offset=\""
+      << normal_offset << "\"/>\n        <DataArray type=\"Int32\" Name=\"ViewIndex\" format=\"appended\" offset=\"" << view_offset
+      << "\"/>\n        <DataArray type=\"Int32\" Name=\"NbAgreeingViews\" format=\"appended\" offset=\"" << agreeing_offset << "\"/>\n";
+  if (color)
+    out << "        <DataArray type=\"UInt8\" Name=\"Color\" NumberOfComponents=\"3\" format=\"appended\" offset=\"" << color_offset
+        << "\"/>\n";
+  out << "      </PointData>\n      <Points>\n        <DataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\" "
+         "format=\"appended\" offset=\"0\"/>\n      </Points>\n      <Verts>\n        <DataArray type=\"Int64\" Name=\"connectivity\" "
+         "format=\"appended\" offset=\""
+      << conn_offset << "\"/>\n        <DataArray type=\"Int64\" Name=\"offsets\" format=\"appended\" offset=\"" << offsets_offset
+      << "\"/>\n      </Verts>\n    </Piece>\n  </PolyData>\n  <AppendedData encoding=\"raw\">\n   _";
+  auto write = [&](const void *data, uint64_t bytes) {
+    out.write(reinterpret_cast<const char *>(&bytes), sizeof(bytes));
+    out.write(reinterpret_cast<const char *>(data), (std::streamsize)bytes);
+  };
+  write(points, point_bytes);
+  for (const int64_t first : {int64_t(0), int64_t(1)}) {  // connectivity 0, 1, 2 ...; offsets 1, 2, 3 ...: in pieces
+    out.write(reinterpret_cast<const char *>(&cell_bytes), sizeof(cell_bytes));
+    std::vector<int64_t> run((size_t)std::min<int64_t>(nPoints, int64_t(1) << 20));
+    for (int64_t done = 0; done < nPoints;) {
+      const int64_t count = std::min<int64_t>(nPoints - done, (int64_t)run.size());
+      for (int64_t q = 0; q < count; ++q) run[(size_t)q] = first + done + q;
+      out.write(reinterpret_cast<const char *>(run.data()), (std::streamsize)(count * sizeof(int64_t)));
+      done += count;
+    }
+  }
+  write(normals, normal_bytes);
+  write(view, int_bytes);
+  write(agreeing, int_bytes);
+  if (color) write(color, rgb_bytes);
+  out << "\n  </AppendedData>\n</VTKFile>\n";
+  if (!out) {
+    *error = "WritePointCloud: write failed: " + path;
     return false;
   }
   return true;
@@ -1067,6 +1210,62 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     say(line.str());
     return true;
   };
+  // the point cloud of the depth maps that are fused: built on the resident set behind the last depth-map step, written at once
+  auto point_cloud = [&]() {
+    say("** Build the point cloud of the depth maps...");
+    const std::string flag = "--outputPointCloudFilename";
+    if (!read_views(flag)) return false;
+    if (!on_set() || !resident.Loaded()) {
+      result->error = flag + ": the points are built on the resident depth maps, and " +
+                      (staged ? "the staged filters have taken over (" + resident.LastError() + ")" : resident.LastError());
+      return false;
+    }
+    DepthPointsReport report;
+    DepthPoints points;
+    if (!resident.BuildPoints(o.pointCloudTolerance, o.pointCloudRelTolerance, o.pointCloudNormalTolerance, o.pointCloudNormalRelTolerance,
+                              (int)o.pointCloudMinViews, (int)o.pointCloudPixelStep, !o.pointCloudKeepDuplicates, &report) ||
+        !resident.DownloadPoints(&points)) {
+      result->error = flag + ": " + resident.LastError();
+      return false;
+    }
+    std::vector<uint8_t> color;
+    if (o.pointCloudColors) {  // each point's pixel of its view's Color array: image row py is vtk row H-1-py
+      const int64_t W = resident.Width(), H = resident.Height();
+      for (size_t m = 0; m < views.size(); ++m)
+        if (views[m]->GetDepthMap()->color.size() != (size_t)(W * H * 3)) {
+          result->error = "--pointCloudColors: view " + std::to_string(m) + " has no Color array of three UInt8 per pixel";
+          return false;
+        }
+      color.resize(3 * points.view.size());
+      for (size_t q = 0; q < points.view.size(); ++q) {
+        const int64_t py = points.pixel[q] / W, px = points.pixel[q] - py * W;
+        const unsigned char *const rgb = views[(size_t)points.view[q]]->GetDepthMap()->color.data() + 3 * ((H - 1 - py) * W + px);
+        std::copy(rgb, rgb + 3, color.begin() + 3 * (std::ptrdiff_t)q);
+      }
+    }
+    std::string error;
+    if (!WritePointCloud(o.outputPointCloudFilename, points.xyz.data(), (int64_t)points.view.size(), points.normal.data(), points.view.data(),
+                         points.count.data(), o.pointCloudColors ? color.data() : nullptr, &error)) {
+      result->error = error;
+      return false;
+    }
+    result->pointCloudViews = report.views;
+    result->pointCloudValidPixels = report.validPixels;
+    result->pointCloudCandidates = report.candidates;
+    result->pointCloudOwned = report.owned;
+    result->pointCloudPoints = report.points;
+    result->pointCloudWithNormal = report.withNormal;
+    result->pointCloudKernelMs = report.kernelMs;
+    std::ostringstream line;
+    line << "point cloud: at least " << o.pointCloudMinViews << " agreeing views, tolerance " << o.pointCloudTolerance << " + "
+         << o.pointCloudRelTolerance << " z, normal tolerance " << o.pointCloudNormalTolerance << " + " << o.pointCloudNormalRelTolerance
+         << " z, pixel step " << o.pointCloudPixelStep << (o.pointCloudKeepDuplicates ? ", duplicates kept; " : "; ") << report.views
+         << " views, " << report.validPixels << " pixels with a depth, " << report.candidates << " candidates, " << report.owned
+         << " held by a lower view, " << report.points << " points, " << report.withNormal << " with a normal; " << report.kernelMs
+         << " ms of GPU kernels";
+    say(line.str());
+    return true;
+  };
   if (o.gridAutoBounds) {
     // the box before anything is described or set up: filtered depths if a filter was asked for, measured along the grid's axes
     if (o.depthSpeckleMinPixels >= 0 && !speckle_views()) return 1;
@@ -1178,6 +1377,7 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
   if (o.depthFillHolesMaxPixels >= 0 && !o.gridAutoBounds && !fill_views()) return 1;
   if (o.depthSmoothSigmaGiven && !o.gridAutoBounds && !smooth_views()) return 1;
   if (o.depthConsistencyMinViews >= 0 && !o.gridAutoBounds && !filter_views()) return 1;
+  if (!o.outputPointCloudFilename.empty() && !point_cloud()) return 1;
   if (!views.empty()) filter.SetViews(views);
   if (resident.Loaded()) filter.SetResidentViews(&resident);
   if (!filter.Update()) {
@@ -1456,6 +1656,14 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << " + " << o.depthConsistencyRelTolerance << " z\n  views  " << result->depthConsistencyViews << "\n  pixels with a depth  "
           << result->depthConsistencyValidPixels << "\n  pixels kept  " << result->depthConsistencyKeptPixels << "\n  GPU kernels  "
           << result->depthConsistencyKernelMs << " ms\n";
+    if (!o.outputPointCloudFilename.empty())
+      out << "point cloud\n  file  " << o.outputPointCloudFilename << "\n  minimum agreeing views  " << o.pointCloudMinViews
+          << "\n  tolerance  " << o.pointCloudTolerance << " + " << o.pointCloudRelTolerance << " z\n  normal tolerance  "
+          << o.pointCloudNormalTolerance << " + " << o.pointCloudNormalRelTolerance << " z\n  pixel step  " << o.pointCloudPixelStep
+          << "\n  duplicates  " << (o.pointCloudKeepDuplicates ? "kept" : "dropped") << "\n  views  " << result->pointCloudViews
+          << "\n  pixels with a depth  " << result->pointCloudValidPixels << "\n  candidates  " << result->pointCloudCandidates
+          << "\n  held by a lower view  " << result->pointCloudOwned << "\n  points  " << result->pointCloudPoints
+          << "\n  points with a normal  " << result->pointCloudWithNormal << "\n  GPU kernels  " << result->pointCloudKernelMs << " ms\n";
     if (o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
           << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";

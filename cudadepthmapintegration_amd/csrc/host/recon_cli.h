@@ -144,6 +144,17 @@ struct Options {
   long long depthSmoothIterations = 1;
   bool depthSmoothSigmaGiven = false, depthSmoothTruncateGiven = false, depthSmoothToleranceGiven = false, depthSmoothRelToleranceGiven = false,
        depthSmoothIterationsGiven = false;
+  // not in the reference: the fused point cloud of the depth maps that are fused (dmi_views_build_points), written to
+  // this .vtp: the points at least pointCloudMinViews other views agree with, within the agreement tolerances (they default to the
+  // --depthConsistency pair when that was given; otherwise one of them is required), each once unless pointCloudKeepDuplicates, with
+  // a normal whose neighbours lie within the normal tolerances (they default to the agreement pair), of every k-th pixel of every
+  // k-th row; with pointCloudColors the views' Color at each point's pixel
+  std::string outputPointCloudFilename;
+  long long pointCloudMinViews = 1, pointCloudPixelStep = 1;
+  double pointCloudTolerance = 0.0, pointCloudRelTolerance = 0.0, pointCloudNormalTolerance = 0.0, pointCloudNormalRelTolerance = 0.0;
+  bool pointCloudMinViewsGiven = false, pointCloudPixelStepGiven = false, pointCloudToleranceGiven = false,
+       pointCloudRelToleranceGiven = false, pointCloudNormalToleranceGiven = false, pointCloudNormalRelToleranceGiven = false;
+  bool pointCloudKeepDuplicates = false, pointCloudColors = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -205,6 +216,10 @@ struct RunResult {
   // pixel in the last iteration, and the hipEvent time of the kernels
   unsigned long long depthSmoothViews = 0, depthSmoothValidPixels = 0, depthSmoothChangedPixels = 0;
   double depthSmoothMeanTaps = 0.0, depthSmoothKernelMs = 0.0;
+  // --outputPointCloudFilename: the report of the build (include/dmi.h: dmi_views_points_report) and the views it read
+  unsigned long long pointCloudViews = 0, pointCloudValidPixels = 0, pointCloudCandidates = 0, pointCloudOwned = 0, pointCloudPoints = 0,
+                     pointCloudWithNormal = 0;
+  double pointCloudKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);
@@ -224,6 +239,11 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
                    std::string *error, const float *normals = nullptr, double contour = 0.0, const int64_t *regionIds = nullptr,
                    const uint8_t *mean = nullptr, const uint8_t *median = nullptr, const int32_t *count = nullptr,
                    const int32_t *support = nullptr);
+// a point cloud as VTK XML PolyData in the same conventions: Float64 Points, one Verts cell per point (Int64 connectivity 0, 1, 2
+// ... and offsets 1, 2, 3 ...), the point arrays Normals (Float32 x 3, the section's Normals), ViewIndex and NbAgreeingViews (Int32)
+// and, with `color` ([nPoints][3] u8), Color (UInt8 x 3) behind them
+bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
+                     const int32_t *agreeing, const uint8_t *color, std::string *error);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

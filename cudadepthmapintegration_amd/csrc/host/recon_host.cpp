@@ -1067,6 +1067,40 @@ bool DepthViewSet::EstimateBounds(const double axes[9], double trimFraction, int
   return true;
 }
 
+bool DepthViewSet::BuildPoints(double absTolerance, double relTolerance, double normalAbsTolerance, double normalRelTolerance, int minViews,
+                               int pixelStep, bool dedupe, DepthPointsReport *report) {
+  dmi_views_points_report r;
+  uint64_t n = 0;
+  if ((Code = dmi_views_build_points(Set, absTolerance, relTolerance, normalAbsTolerance, normalRelTolerance, (int32_t)minViews,
+                                     (int32_t)pixelStep, dedupe ? 1 : 0, &n, &r)) != DMI_OK)
+    return Fail("dmi_views_build_points");
+  NPoints = n;
+  if (report) {
+    *report = DepthPointsReport();
+    report->views = NViews;
+    report->validPixels = r.valid;
+    report->candidates = r.candidates;
+    report->owned = r.owned;
+    report->points = r.points;
+    report->withNormal = r.with_normal;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
+bool DepthViewSet::DownloadPoints(DepthPoints *points) {
+  const size_t n = (size_t)NPoints;
+  points->xyz.resize(3 * n);
+  points->normal.resize(3 * n);
+  points->view.resize(n);
+  points->pixel.resize(n);
+  points->count.resize(n);
+  if ((Code = dmi_views_download_points(Set, 0, NPoints, points->xyz.data(), points->normal.data(), points->view.data(),
+                                        points->pixel.data(), points->count.data())) != DMI_OK)
+    return Fail("dmi_views_download_points");
+  return true;
+}
+
 bool DepthViewSet::Store(const std::vector<ReconstructionData *> &views, double thresholdBestCost) {
   if (!Set || views.size() != NViews) {
     Code = DMI_ERR_INVALID_ARGUMENT;

@@ -173,6 +173,19 @@ struct SceneBoundsReport {
 bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
                          double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error);
 
+// Not in the reference: the fused point cloud of a resident view set (dmi_views_build_points, include/dmi.h states the definition;
+// DESIGN.md 8n): the report of a build, and the points as DepthViewSet::DownloadPoints brings them down.
+struct DepthPointsReport {
+  uint64_t views = 0;
+  uint64_t validPixels = 0, candidates = 0, owned = 0, points = 0, withNormal = 0;
+  double kernelMs = 0.0;  // hipEvent time of the build's kernels
+};
+struct DepthPoints {
+  std::vector<double> xyz;    // [n][3]
+  std::vector<float> normal;  // [n][3], zero where a point has none
+  std::vector<int32_t> view, pixel, count;  // [n]: the view, py * W + px in image coordinates, the views that agree
+};
+
 // Not in the reference: the views' depths resident on one GPU from the first of the steps above to the fusion (dmi_view_set,
 // include/dmi.h).  Load thresholds and uploads every view once; each step runs where the depths are and fills the
 // report of its staged counterpart above from the counters the device returns, with the same numbers; ReconstructionFilter::
@@ -196,6 +209,12 @@ class DepthViewSet {
   bool Smooth(double sigma, double truncate, double absTolerance, double relTolerance, int iterations, DepthSmoothReport *report);
   bool FilterConsistency(int minViews, double absTolerance, double relTolerance, DepthConsistencyReport *report);
   bool EstimateBounds(const double axes[9], double trimFraction, int pixelStep, SceneBoundsReport *report);
+  // The point cloud of the set's current depths, built on the device and kept there until the depths change; then all of it
+  bool BuildPoints(double absTolerance, double relTolerance, double normalAbsTolerance, double normalRelTolerance, int minViews,
+                   int pixelStep, bool dedupe, DepthPointsReport *report);
+  bool DownloadPoints(DepthPoints *points);
+  int Width() const { return W; }
+  int Height() const { return H; }
   // The set's depths into the views they were loaded from (one download), so that the staged functions above and SetViews go on
   // from here: a depth whose best cost the threshold would drop again gets the threshold as its cost, as FillDepthHoles does.
   bool Store(const std::vector<ReconstructionData *> &views, double thresholdBestCost);
@@ -209,6 +228,7 @@ class DepthViewSet {
   bool Fail(const char *what);
   dmi_view_set *Set = nullptr;
   size_t NViews = 0;
+  uint64_t NPoints = 0;  // of the last BuildPoints
   int W = 0, H = 0, Dev = 0;
   std::string Error;
   int Code = 0;

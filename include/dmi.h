@@ -55,7 +55,7 @@ extern "C" {
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
                            *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles;
-                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths */
+                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -1041,6 +1041,67 @@ int dmi_views_estimate_bounds(dmi_view_set *s, const double *axes9, double trim_
                               double hi[3], uint64_t *n_points, double *kernel_ms);
 int dmi_views_download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth);
 int dmi_add_views_from_set(dmi_context *ctx, const dmi_view_set *s, int32_t first, int32_t count);
+
+/* ---- The fused point cloud of a resident view set (added after round 5, dmi_abi_version() stays 5) ----
+ * The other product of a set of filtered depth maps: the points the views agree on, each once, with a normal.
+ * dmi_views_build_points builds it on the device from the set's current D; dmi_views_download_points brings ranges of it to the
+ * host.  Definition, met bit for bit by the device and by tests/depth_points_np.py.
+ * All arithmetic is f64, with every operation rounded on its own and nothing contracted.  Comparisons with a NaN are false.
+ * Divisions and the square root are correctly rounded.
+ * D, VALID, image coordinates (px, py) (vtk row r = image row H-1-r) and the K4 form are exactly those of
+ * dmi_filter_depth_consistency.
+ * Parameters: abs_tolerance, rel_tolerance: agreement.  normal_abs_tolerance, normal_rel_tolerance: normals.  min_views >= 0.
+ * pixel_step >= 1.  dedupe (0/1).
+ *   1. Counts.  count is step 4's out_count of dmi_filter_depth_consistency on the set's current D, with abs_tolerance,
+ *      rel_tolerance.
+ *   2. Candidates.  A pixel is a CANDIDATE iff it is valid, px % pixel_step == 0, py % pixel_step == 0 and count >= min_views.
+ *   3. Ownership (only with dedupe).  A candidate of view s is OWNED iff there is a view t < s for which both of these hold:
+ *      the pair AGREES (step 3 of the consistency definition, operation for operation, with w from step 2); the pixel of t it lands
+ *      on is itself a candidate.  A candidate is EMITTED iff it is not owned.  The rule is deliberately one-directional and needs no
+ *      ordering between workgroups.  The lowest view that holds a surface keeps it.
+ *   4. Position.  w of step 2, as three f64.
+ *   5. Normal.  c(x, y) is step 2's camera-space point of pixel (x, y) with its own depth.  A neighbour (x', y') inside the image
+ *      is USABLE iff it is valid (whether or not it takes part) and fabs(d' - d) <= normal_abs_tolerance + normal_rel_tolerance*d
+ *      (product rounded, then the sum, then the difference).
+ *      tx: if (px+1, py) and (px-1, py) are both usable: c(px+1,py) - c(px-1,py).  If only the right one is usable:
+ *      c(px+1,py) - c(px,py).  If only the left one is usable: c(px,py) - c(px-1,py).  Otherwise there is no normal.
+ *      ty: likewise with (px, py+1) as the "plus" neighbour and (px, py-1) as the "minus" one.
+ *      m_0 = tx_1*ty_2 - tx_2*ty_1, m_1 = tx_2*ty_0 - tx_0*ty_2, m_2 = tx_0*ty_1 - tx_1*ty_0.
+ *      s = (m_0*c_0 + m_1*c_1) + m_2*c_2.  If s > 0, m = -m, so the normal faces the camera.
+ *      g_j = (R[0][j]*m_0 + R[1][j]*m_1) + R[2][j]*m_2.
+ *      L = sqrt((g_0*g_0 + g_1*g_1) + g_2*g_2).
+ *      The point HAS A NORMAL iff tx and ty exist and L is finite and > 0.  Then n_j = g_j / L rounded to f32.  This is the form
+ *      dmi_extract_isosurface_normals already uses for its last step.  Otherwise n = (0, 0, 0).
+ *   6. Order.  The emitted points are stored in ascending (view, py, px).
+ *   7. Per-point outputs.  xyz f64[3].  normal f32[3].  view int32.  pixel int32 = py*W + px.  count int32.
+ * Build.  D is not changed.  The points stay on the device until the next dmi_views_add, dmi_views_clear, step that replaces D, or
+ * build; dmi_views_estimate_bounds and dmi_views_download keep them.  A successful build counts as a step in dmi_views_info::steps,
+ * and the point buffers (48 bytes per point, allocated after the scan at exactly the size needed) count in device_bytes.  If that
+ * allocation fails the call returns DMI_ERR_OUT_OF_MEMORY and leaves the set, its D and any earlier points as they were.  During
+ * the call the set holds the planes in image row order, the counts, a flag byte per pixel and 12 bytes per 256 pixels besides: 13
+ * bytes per pixel and view, freed when the call ends.  *n_points: the number of points; zero points is DMI_OK.
+ *   dmi_views_points_report (r, nullable)   valid: the valid pixels of D; candidates, owned: steps 2 and 3; points: the emitted
+ *              candidates; with_normal: the points that have a normal; kernel_ms: the hipEvent time of the kernels of the build.
+ *   dmi_views_get_points_pass_ms   the same time by pass: the planes' flip, the counts, the candidate and ownership flags, the block
+ *              counts with their scan, the scatter.  DMI_ERR_STATE without a current build.
+ * Download.  The points [first, first + count) into the arrays given, each nullable: xyz [count][3] f64, normal [count][3] f32,
+ * view, pixel and n_views (the count of step 7) [count] int32.  DMI_ERR_STATE without a current build; DMI_ERR_INVALID_ARGUMENT when
+ * first + count exceeds the point count.
+ * The result is byte for byte the same for every dmi_views_set_piece_bytes.
+ * DMI_ERR_INVALID_ARGUMENT before the device is touched, the message naming the argument: a null set or n_points; a negative, NaN
+ * or infinite tolerance; min_views < 0; pixel_step < 1; dedupe outside {0, 1}; an empty set; n * ceil(W * H / 256) >= 2^31; a K4
+ * outside the form (the message names the view).  A refused call leaves the set as it was.  The calls never exit, never throw, and
+ * synchronise, like the rest of the section. */
+typedef struct dmi_views_points_report {
+  uint64_t valid, candidates, owned, points, with_normal;
+  double kernel_ms;
+} dmi_views_points_report;
+int dmi_views_build_points(dmi_view_set *s, double abs_tolerance, double rel_tolerance, double normal_abs_tolerance,
+                           double normal_rel_tolerance, int32_t min_views, int32_t pixel_step, int32_t dedupe, uint64_t *n_points,
+                           dmi_views_points_report *r /* nullable */);
+int dmi_views_download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz, float *normal, int32_t *view,
+                              int32_t *pixel, int32_t *n_views /* each nullable */);
+int dmi_views_get_points_pass_ms(dmi_view_set *s, double out_ms[5]);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default
