@@ -90,6 +90,12 @@ class ViewsPointsReportC(ctypes.Structure):
                 ("with_normal", ctypes.c_uint64), ("kernel_ms", ctypes.c_double)]
 
 
+class PointsThinReportC(ctypes.Structure):
+    _fields_ = [("points_in", ctypes.c_uint64), ("cells", ctypes.c_uint64), ("cells_kept", ctypes.c_uint64),
+                ("multi_view_cells", ctypes.c_uint64), ("largest_cell", ctypes.c_uint64), ("with_normal", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 class MultiOptionsC(ctypes.Structure):
     _fields_ = [("grid_dtype", ctypes.c_int32), ("depth_storage", ctypes.c_int32), ("kernel_variant", ctypes.c_int32),
                 ("partition", ctypes.c_int32), ("exchange", ctypes.c_int32), ("n_slabs", ctypes.c_int32)]
@@ -146,6 +152,8 @@ ABI_SYMBOLS = [
     "dmi_sizeof_views_info", "dmi_views_set_piece_bytes", "dmi_views_filter_speckles", "dmi_views_fill_holes", "dmi_views_smooth",
     "dmi_views_filter_consistency", "dmi_views_estimate_bounds", "dmi_views_download", "dmi_add_views_from_set",
     "dmi_views_build_points", "dmi_views_download_points", "dmi_views_get_points_pass_ms",
+    "dmi_thin_point_cloud", "dmi_views_thin_points", "dmi_views_download_point_members", "dmi_views_get_thin_pass_ms",
+    "dmi_views_set_thin_wave_cell_points",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -343,6 +351,15 @@ def load() -> ctypes.CDLL:
         L.dmi_views_build_points.argtypes = [vp, dbl, dbl, dbl, dbl, i32, i32, i32, ctypes.POINTER(u64), ctypes.POINTER(ViewsPointsReportC)]
         L.dmi_views_download_points.argtypes = [vp, u64, u64, dp, ctypes.POINTER(ctypes.c_float), i32p, i32p, i32p]
         L.dmi_views_get_points_pass_ms.argtypes = [vp, dp]
+    if hasattr(L, "dmi_thin_point_cloud"):
+        u64, fp, u32p = ctypes.c_uint64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint32)
+        tp = ctypes.POINTER(PointsThinReportC)
+        L.dmi_thin_point_cloud.argtypes = [dp, fp, i32p, i32p, i32p, u64, dbl, i32, i32, dp, fp, i32p, i32p, i32p, u32p,
+                                           ctypes.POINTER(u64), tp]
+        L.dmi_views_thin_points.argtypes = [vp, dbl, i32, ctypes.POINTER(u64), tp]
+        L.dmi_views_download_point_members.argtypes = [vp, u64, u64, u32p]
+        L.dmi_views_get_thin_pass_ms.argtypes = [vp, dp]
+        L.dmi_views_set_thin_wave_cell_points.argtypes = [vp, i32]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1313,6 +1330,56 @@ def estimate_scene_bounds(views: Views, *, trim_fraction: float = 0.0, pixel_ste
     return lo, hi, int(count.value), float(ms.value)
 
 
+def thin_point_cloud(xyz, normal=None, view=None, pixel=None, count=None, *, cell_size: float, min_points: int = 1, device: int = 0,
+                     in_place: bool = False, return_members: bool = True):
+    """A point cloud thinned and merged on a voxel grid (include/dmi.h: dmi_thin_point_cloud): one point per occupied cell of
+    size cell_size that has at least min_points members, at their mean, with a merged normal, the first member's view and pixel
+    and the largest count.  xyz [P, 3] f64; normal [P, 3] f32, view, pixel, count [P] int32, each optional (absent: zeros).
+    Returns (arrays, report): arrays has xyz, normal, view, pixel, count and -- with return_members -- members (uint32), in cell
+    order; report has points_in, cells, cells_kept, multi_view_cells, largest_cell, with_normal, kernel_ms.  in_place: the
+    arrays given (C-contiguous, of the dtypes above) receive the result themselves and the returned arrays are views of them."""
+    L = load()
+    kinds = dict(xyz=(np.float64, 3), normal=(np.float32, 3), view=(np.int32, 1), pixel=(np.int32, 1), count=(np.int32, 1))
+    given = dict(xyz=xyz, normal=normal, view=view, pixel=pixel, count=count)
+    if xyz is None:
+        raise ValueError("xyz is required")
+    inputs = {}
+    for name, a in given.items():
+        dtype, width = kinds[name]
+        if a is None:
+            inputs[name] = None
+            continue
+        b = np.ascontiguousarray(a, dtype=dtype)
+        if in_place and b is not a:
+            raise ValueError(f"in_place needs a C-contiguous {np.dtype(dtype).name} array for {name}")
+        inputs[name] = b
+    p = inputs["xyz"].size // 3
+    for name, b in inputs.items():
+        if b is not None and b.size != p * kinds[name][1]:
+            raise ValueError(f"{name} must hold {kinds[name][1]} values per point")
+    out = {name: (inputs[name].reshape(-1) if in_place and inputs[name] is not None else np.empty(p * width, dtype=dtype))
+           for name, (dtype, width) in kinds.items()}
+    members = np.empty(p, dtype=np.uint32) if return_members else None
+    i32p, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+
+    def ptr(a, kind):
+        return None if a is None else a.ctypes.data_as(kind)
+
+    n_out, r = ctypes.c_uint64(0), PointsThinReportC()
+    rc = L.dmi_thin_point_cloud(ptr(inputs["xyz"], ctypes.POINTER(ctypes.c_double)), ptr(inputs["normal"], fp), ptr(inputs["view"], i32p),
+                                ptr(inputs["pixel"], i32p), ptr(inputs["count"], i32p), p, float(cell_size), int(min_points), int(device),
+                                ptr(out["xyz"], ctypes.POINTER(ctypes.c_double)), ptr(out["normal"], fp), ptr(out["view"], i32p),
+                                ptr(out["pixel"], i32p), ptr(out["count"], i32p), ptr(members, ctypes.POINTER(ctypes.c_uint32)),
+                                ctypes.byref(n_out), ctypes.byref(r))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    q = int(n_out.value)
+    arrays = {name: (out[name][:q * width].reshape(q, 3) if width == 3 else out[name][:q]) for name, (_, width) in kinds.items()}
+    if return_members:
+        arrays["members"] = members[:q]
+    return arrays, {name: getattr(r, name) for name, _ in PointsThinReportC._fields_}
+
+
 class ViewSet:
     """Depth maps resident on the device from the first filter to the fusion (dmi_views_create ... dmi_views_destroy;
     include/dmi.h states the definition).  add() uploads once; every step replaces the set's depths by exactly what the
@@ -1463,6 +1530,38 @@ class ViewSet:
             self._h, first, count, _dp(arrays["xyz"]), arrays["normal"].ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
             arrays["view"].ctypes.data_as(i32p), arrays["pixel"].ctypes.data_as(i32p), arrays["count"].ctypes.data_as(i32p)))
         return arrays
+
+    def thin_points(self, cell_size: float, min_points: int = 1) -> dict:
+        """The set's cloud replaced by its thinned one (include/dmi.h: dmi_views_thin_points): one point per occupied cell of size
+        cell_size with at least min_points members, at their mean.  On a cloud built with dedupe=False the mean averages what the
+        views saw of one surface element.  Once per build.  Returns the report: points_in, cells, cells_kept, multi_view_cells,
+        largest_cell, with_normal, kernel_ms; download_points serves the thinned cloud, download_point_members its cell sizes."""
+        count, r = ctypes.c_uint64(0), PointsThinReportC()
+        self._check(self._lib.dmi_views_thin_points(self._h, float(cell_size), int(min_points), ctypes.byref(count), ctypes.byref(r)))
+        self._n_points = int(count.value)
+        return {name: getattr(r, name) for name, _ in PointsThinReportC._fields_}
+
+    def download_point_members(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """How many input points each of the points [first, first + count) was merged from, uint32 (1 on a cloud not thinned)."""
+        first = int(first)
+        if count is None:
+            count = max(getattr(self, "_n_points", 0) - first, 0)
+        count = int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        out = np.empty(count, dtype=np.uint32)
+        self._check(self._lib.dmi_views_download_point_members(self._h, first, count, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def thin_pass_ms(self) -> dict:
+        """The last thin_points' kernel time by pass (ms): bounds, keys, sort, ranks (with their scans), representatives."""
+        out = np.zeros(5, dtype=np.float64)
+        self._check(self._lib.dmi_views_get_thin_pass_ms(self._h, _dp(out)))
+        return dict(zip(("bounds", "keys", "sort", "ranks", "representatives"), out.tolist()))
+
+    def set_thin_wave_cell_points(self, k: int):
+        """Cells of more than k members are summed by a wave of their own.  No result depends on it."""
+        self._check(self._lib.dmi_views_set_thin_wave_cell_points(self._h, int(k)))
 
 
 class ColorContext:
@@ -1829,7 +1928,8 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_fill_holes_rel_tolerance", ctypes.c_double),
                 ("depth_smooth_sigma", ctypes.c_double), ("depth_smooth_truncate", ctypes.c_double),
                 ("depth_smooth_tolerance", ctypes.c_double), ("depth_smooth_rel_tolerance", ctypes.c_double),
-                ("depth_smooth_iterations", ctypes.c_int64), ("depth_staged_filters", ctypes.c_int32)]
+                ("depth_smooth_iterations", ctypes.c_int64), ("depth_staged_filters", ctypes.c_int32),
+                ("point_cloud_cell_size", ctypes.c_double), ("point_cloud_min_cell_points", ctypes.c_int64)]
 
 
 def cli_read_arguments(args):

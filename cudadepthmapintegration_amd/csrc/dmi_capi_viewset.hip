@@ -73,6 +73,7 @@ void drop_points(dmi_view_set *s) {
   }
   s->n_points = 0;
   s->points_current = false;
+  s->points_thinned = false;
 }
 
 struct Pieces {
@@ -655,6 +656,70 @@ int download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz
   return DMI_OK;
 }
 
+// the set's cloud replaced by its thinned one: dmi::run_thin_points (dmi_capi_points_thin.hip) on the arrays of s->points
+int thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t *n_points, dmi_points_thin_report *r) {
+  namespace pr = dmi::points_rules;
+  const std::string entry = "dmi_views_thin_points";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + ": the set is null");
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + ": " + what); };
+  if (!n_points) return bad("n_points is null");
+  if (!(cell_size > 0.0) || cell_size - cell_size != 0.0) return bad("cell_size is not a finite number > 0");
+  if (min_points < 1) return bad("min_points >= 1 required");
+  if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + ": the set holds no points: dmi_views_build_points comes first");
+  if (s->points_thinned)
+    return fail(s, DMI_ERR_STATE, entry + ": the cloud is thinned already (a centroid of centroids is not the centroid): build again");
+  if (s->n_points > dmi::thin_rules::kMaxPoints) return bad("the cloud must hold fewer than 2^32 points");
+
+  VS_HIP(s, hipSetDevice(s->device));
+  dmi::ThinOutcome outcome;
+  if (s->n_points) {
+    pr::Layout in;
+    (void)pr::layout_of(s->n_points, &in);  // (it fitted when the points were built)
+    const unsigned char *const base = s->points.as<unsigned char>();
+    dmi::ThinCloud cloud{};
+    cloud.xyz = reinterpret_cast<const double *>(base + in.xyz);
+    cloud.normal = reinterpret_cast<const float *>(base + in.normal);
+    cloud.view = reinterpret_cast<const int32_t *>(base + in.view);
+    cloud.pixel = reinterpret_cast<const int32_t *>(base + in.pixel);
+    cloud.count = reinterpret_cast<const int32_t *>(base + in.count);
+    cloud.n = s->n_points;
+    std::string message;
+    const int rc = dmi::run_thin_points(entry, cloud, cell_size, min_points, s->thin_wave_cell_points, s->stream, s->device_bytes,
+                                        &outcome, &message);
+    if (rc != DMI_OK) return fail(s, rc, message);  // (nothing of the call is left; the cloud is as it was)
+  }
+  dmi::free_buffers({&s->points}, s->device_bytes);
+  s->points = outcome.result;
+  s->n_points = outcome.n_out;
+  s->points_thinned = true;
+  s->steps += 1;
+  for (int e = 0; e < 5; ++e) s->thin_pass_ms[e] = outcome.pass_ms[e];
+  *n_points = outcome.n_out;
+  if (r) *r = outcome.report;
+  return DMI_OK;
+}
+
+int download_point_members(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out) {
+  const std::string entry = "dmi_views_download_point_members: ";
+  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + "the set holds no points: dmi_views_build_points comes first");
+  if (first > s->n_points || count > s->n_points - first)
+    return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "first + count must not exceed the number of points");
+  if (count == 0) return DMI_OK;
+  if (!out) return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "out is null");
+  if (!s->points_thinned) {  // every point of a built cloud is one pixel
+    std::fill(out, out + count, 1u);
+    return DMI_OK;
+  }
+  dmi::thin_rules::Layout layout;
+  (void)dmi::thin_rules::layout_of(s->n_points, &layout);
+  VS_HIP(s, hipSetDevice(s->device));
+  VS_HIP(s, hipMemcpyAsync(out, s->points.as<unsigned char>() + layout.members + first * 4, (size_t)(count * 4), hipMemcpyDeviceToHost,
+                            s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  return DMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -778,6 +843,34 @@ int dmi_views_get_points_pass_ms(dmi_view_set *s, double out_ms[5]) {
     if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_points_pass_ms: out_ms is null");
     if (!s->points_current) return fail(s, DMI_ERR_STATE, "dmi_views_get_points_pass_ms: the set holds no points");
     for (int e = 0; e < 5; ++e) out_ms[e] = s->points_pass_ms[e];
+    return DMI_OK;
+  });
+}
+
+int dmi_views_thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t *n_points, dmi_points_thin_report *r) {
+  return guarded(s, "dmi_views_thin_points", [&]() -> int { return thin_points(s, cell_size, min_points, n_points, r); });
+}
+
+int dmi_views_download_point_members(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out) {
+  return guarded(s, "dmi_views_download_point_members", [&]() -> int { return download_point_members(s, first, count, out); });
+}
+
+int dmi_views_get_thin_pass_ms(dmi_view_set *s, double out_ms[5]) {
+  return guarded(s, "dmi_views_get_thin_pass_ms", [&]() -> int {
+    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_thin_pass_ms: the set is null");
+    if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_thin_pass_ms: out_ms is null");
+    if (!s->points_current || !s->points_thinned)
+      return fail(s, DMI_ERR_STATE, "dmi_views_get_thin_pass_ms: the set holds no thinned cloud");
+    for (int e = 0; e < 5; ++e) out_ms[e] = s->thin_pass_ms[e];
+    return DMI_OK;
+  });
+}
+
+int dmi_views_set_thin_wave_cell_points(dmi_view_set *s, int32_t k) {
+  return guarded(s, "dmi_views_set_thin_wave_cell_points", [&]() -> int {
+    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_thin_wave_cell_points: the set is null");
+    if (k < 1) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_thin_wave_cell_points: k >= 1 required");
+    s->thin_wave_cell_points = (uint32_t)k;
     return DMI_OK;
   });
 }

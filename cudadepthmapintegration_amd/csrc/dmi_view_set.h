@@ -7,6 +7,7 @@
 #include "depth_consistency.h"
 #include "depth_holes.h"
 #include "depth_points.h"
+#include "depth_points_thin.h"
 #include "depth_smooth.h"
 #include "depth_speckle.h"
 #include "dmi_buffer.h"
@@ -37,6 +38,11 @@ struct dmi_view_set {
   dmi::DeviceBuffer points;
   uint64_t n_points = 0;
   bool points_current = false;
+  // dmi_views_thin_points has replaced the build's cloud by its thinned one: 52 bytes per point (thin_rules::Layout, whose first
+  // five arrays stand where points_rules::Layout has them); dropped with the points
+  bool points_thinned = false;
+  double thin_pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last thinning's bounds, keys, sort, ranks with their scans, representatives
+  uint32_t thin_wave_cell_points = dmi::thin_rules::kDefaultWaveCellPoints;  // dmi_views_set_thin_wave_cell_points
   double points_pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last build's flip, count, flags, block counts + scan, scatter
   dmi::DeviceBuffer counters;  // dmi::kVsCounters u64 (view_set_kernels.h); a build's dmi::kPtCounters stand in the same array
   hipStream_t stream = nullptr;
@@ -56,6 +62,18 @@ int views_fail(dmi_view_set *s, int code, const std::string &msg);  // records m
 
 // ---- one implementation per filter: defined beside the context-free entry point that runs it between its copies ----
 
+// dmi_capi_points_thin.hip: the thinning of a cloud that is on the device (n in [1, 2^32), cell_size and min_points checked by the
+// caller): bounds, keys, sort, ranks and representatives with their three synchronisations; everything but the result is freed
+// before it returns, `held` following every allocation.  DMI_OK, or a code with *message saying why (`entry` names the caller): then
+// nothing is left allocated and the cloud is as it was.
+struct ThinOutcome {
+  DeviceBuffer result;  // thin_rules::Layout for n_out points; empty when there are none.  The caller's to free.
+  uint64_t n_out = 0;
+  dmi_points_thin_report report{};
+  double pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+};
+int run_thin_points(const std::string &entry, const ThinCloud &cloud, double cell_size, int32_t min_points, uint32_t wave_cell_points,
+                    hipStream_t stream, uint64_t &held, ThinOutcome *outcome, std::string *message);
 // dmi_capi_speckle.hip: the four passes on a piece, an event before the first and one behind each
 hipError_t run_speckle_piece(const SpecklePiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
                              int64_t min_pixels, const SpeckleTuning &tuning, hipStream_t stream, hipEvent_t events[5]);

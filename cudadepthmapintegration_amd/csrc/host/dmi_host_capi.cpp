@@ -399,6 +399,8 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->depth_smooth_rel_tolerance = o.depthSmoothRelTolerance;
   out->depth_smooth_iterations = o.depthSmoothIterations;
   out->depth_staged_filters = o.depthStagedFilters ? 1 : 0;
+  out->point_cloud_cell_size = o.pointCloudCellSizeGiven ? o.pointCloudCellSize : 0.0;
+  out->point_cloud_min_cell_points = o.pointCloudMinCellPoints;
   return 1;
   });
 }

@@ -346,8 +346,22 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                           o->pointCloudPixelStep <= 0x7fffffffLL;
                                  }}},
       {"--pointCloudKeepDuplicates", {Kind::kFlag, "with --outputPointCloudFilename: every view keeps its points; without the flag a "
-                                                   "point that a lower view holds already is dropped (not in the reference)",
+                                                   "point that a lower view holds already is dropped.  Together with "
+                                                   "--pointCloudCellSize this is what averages across views: the views' points of one "
+                                                   "surface element are merged into their mean (not in the reference)",
                                       into_flag(&o->pointCloudKeepDuplicates)}},
+      {"--pointCloudCellSize", {Kind::kValue, "with --outputPointCloudFilename: thin the cloud on the GPU before it is written, to one "
+                                              "point per occupied cell of a grid of this size (world units, finite, > 0): the mean of "
+                                              "the cell's points, their normals merged, the first one's view, the largest "
+                                              "NbAgreeingViews, and the point array NbMergedPoints (not in the reference)",
+                                into_checked_double(&o->pointCloudCellSize, &o->pointCloudCellSizeGiven, [](double x) { return x > 0.0; })}},
+      {"--pointCloudMinCellPoints", {Kind::kValue, "with --pointCloudCellSize: drop the cells that hold fewer points than this (an "
+                                                   "integer >= 1, default 1; not in the reference)",
+                                     [o](const std::vector<std::string> &values) {
+                                       o->pointCloudMinCellPointsGiven = true;
+                                       return into_count(&o->pointCloudMinCellPoints)(values) && o->pointCloudMinCellPoints >= 1 &&
+                                              o->pointCloudMinCellPoints <= 0x7fffffffLL;
+                                     }}},
       {"--pointCloudColors", {Kind::kFlag, "with --outputPointCloudFilename: the point array Color (UInt8 RGB), each point's pixel of its "
                                            "view's Color array; every depth map file must carry one (not in the reference)",
                               into_flag(&o->pointCloudColors)}},
@@ -581,11 +595,16 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
                            std::make_pair("--pointCloudNormalRelTolerance", o->pointCloudNormalRelToleranceGiven),
                            std::make_pair("--pointCloudPixelStep", o->pointCloudPixelStepGiven),
                            std::make_pair("--pointCloudKeepDuplicates", o->pointCloudKeepDuplicates),
-                           std::make_pair("--pointCloudColors", o->pointCloudColors)})
+                           std::make_pair("--pointCloudColors", o->pointCloudColors),
+                           std::make_pair("--pointCloudCellSize", o->pointCloudCellSizeGiven)})
     if (flag.second && !pointCloud) {
       err << "Error : " << flag.first << " needs --outputPointCloudFilename.\n" << HelpText();
       return false;
     }
+  if (o->pointCloudMinCellPointsGiven && !o->pointCloudCellSizeGiven) {
+    err << "Error : --pointCloudMinCellPoints needs --pointCloudCellSize.\n" << HelpText();
+    return false;
+  }
   if (pointCloud) {
     if (!ends_with_or_contains(o->outputPointCloudFilename, ".vtp")) {
       err << "Error : --outputPointCloudFilename must name a .vtp file.\n" << HelpText();
@@ -823,7 +842,7 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 }
 
 bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
-                     const int32_t *agreeing, const uint8_t *color, std::string *error) {
+                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged) {
   if (nPoints < 0) {
     *error = "WritePointCloud: negative count";
     return false;
@@ -836,10 +855,12 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
   const uint64_t n = (uint64_t)nPoints, header = sizeof(uint64_t);
   const uint64_t point_bytes = n * 3 * sizeof(double), cell_bytes = n * sizeof(int64_t), normal_bytes = n * 3 * sizeof(float),
                  int_bytes = n * sizeof(int32_t), rgb_bytes = n * 3;
-  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, Color -- [UInt64 byte count] bytes each
+  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, NbMergedPoints, Color -- [UInt64 byte count]
+  // bytes each
   const uint64_t conn_offset = header + point_bytes, offsets_offset = conn_offset + header + cell_bytes;
   const uint64_t normal_offset = offsets_offset + header + cell_bytes, view_offset = normal_offset + header + normal_bytes;
-  const uint64_t agreeing_offset = view_offset + header + int_bytes, color_offset = agreeing_offset + header + int_bytes;
+  const uint64_t agreeing_offset = view_offset + header + int_bytes, merged_offset = agreeing_offset + header + int_bytes;
+  const uint64_t color_offset = merged ? merged_offset + header + int_bytes : merged_offset;
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
       << nPoints << "\" NumberOfVerts=\"" << nPoints << "\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"0\">\n"
@@ -847,6 +868,8 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
          "format=\"appended\" offset=\""
       << normal_offset << "\"/>\n        <DataArray type=\"Int32\" Name=\"ViewIndex\" format=\"appended\" offset=\"" << view_offset
       << "\"/>\n        <DataArray type=\"Int32\" Name=\"NbAgreeingViews\" format=\"appended\" offset=\"" << agreeing_offset << "\"/>\n";
+  if (merged)
+    out << "        <DataArray type=\"UInt32\" Name=\"NbMergedPoints\" format=\"appended\" offset=\"" << merged_offset << "\"/>\n";
   if (color)
     out << "        <DataArray type=\"UInt8\" Name=\"Color\" NumberOfComponents=\"3\" format=\"appended\" offset=\"" << color_offset
         << "\"/>\n";
@@ -873,6 +896,7 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
   write(normals, normal_bytes);
   write(view, int_bytes);
   write(agreeing, int_bytes);
+  if (merged) write(merged, int_bytes);
   if (color) write(color, rgb_bytes);
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
@@ -1221,9 +1245,11 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
       return false;
     }
     DepthPointsReport report;
+    DepthThinReport thinned;
     DepthPoints points;
     if (!resident.BuildPoints(o.pointCloudTolerance, o.pointCloudRelTolerance, o.pointCloudNormalTolerance, o.pointCloudNormalRelTolerance,
                               (int)o.pointCloudMinViews, (int)o.pointCloudPixelStep, !o.pointCloudKeepDuplicates, &report) ||
+        (o.pointCloudCellSizeGiven && !resident.ThinPoints(o.pointCloudCellSize, (int)o.pointCloudMinCellPoints, &thinned)) ||
         !resident.DownloadPoints(&points)) {
       result->error = flag + ": " + resident.LastError();
       return false;
@@ -1245,7 +1271,8 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     }
     std::string error;
     if (!WritePointCloud(o.outputPointCloudFilename, points.xyz.data(), (int64_t)points.view.size(), points.normal.data(), points.view.data(),
-                         points.count.data(), o.pointCloudColors ? color.data() : nullptr, &error)) {
+                         points.count.data(), o.pointCloudColors ? color.data() : nullptr, &error,
+                         o.pointCloudCellSizeGiven ? points.members.data() : nullptr)) {
       result->error = error;
       return false;
     }
@@ -1264,6 +1291,20 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
          << " held by a lower view, " << report.points << " points, " << report.withNormal << " with a normal; " << report.kernelMs
          << " ms of GPU kernels";
     say(line.str());
+    if (o.pointCloudCellSizeGiven) {
+      result->pointCloudCells = thinned.cells;
+      result->pointCloudCellsKept = thinned.cellsKept;
+      result->pointCloudMultiViewCells = thinned.multiViewCells;
+      result->pointCloudLargestCell = thinned.largestCell;
+      result->pointCloudThinnedWithNormal = thinned.withNormal;
+      result->pointCloudThinKernelMs = thinned.kernelMs;
+      std::ostringstream thin;
+      thin << "point cloud thinning: cells of " << o.pointCloudCellSize << ", at least " << o.pointCloudMinCellPoints << " points; "
+           << thinned.pointsIn << " points in " << thinned.cells << " cells, " << thinned.cellsKept << " kept, " << thinned.multiViewCells
+           << " fed by more than one view, the largest of " << thinned.largestCell << " points, " << thinned.withNormal
+           << " with a normal; " << thinned.kernelMs << " ms of GPU kernels";
+      say(thin.str());
+    }
     return true;
   };
   if (o.gridAutoBounds) {
@@ -1664,6 +1705,12 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << "\n  pixels with a depth  " << result->pointCloudValidPixels << "\n  candidates  " << result->pointCloudCandidates
           << "\n  held by a lower view  " << result->pointCloudOwned << "\n  points  " << result->pointCloudPoints
           << "\n  points with a normal  " << result->pointCloudWithNormal << "\n  GPU kernels  " << result->pointCloudKernelMs << " ms\n";
+    if (!o.outputPointCloudFilename.empty() && o.pointCloudCellSizeGiven)
+      out << "point cloud thinning\n  cell size  " << o.pointCloudCellSize << "\n  minimum points per cell  " << o.pointCloudMinCellPoints
+          << "\n  occupied cells  " << result->pointCloudCells << "\n  cells kept  " << result->pointCloudCellsKept
+          << "\n  cells fed by more than one view  " << result->pointCloudMultiViewCells << "\n  largest cell  "
+          << result->pointCloudLargestCell << "\n  points with a normal  " << result->pointCloudThinnedWithNormal << "\n  GPU kernels  "
+          << result->pointCloudThinKernelMs << " ms\n";
     if (o.extractMesh)
       out << "contour\n  cells straddling the value  " << result->contourActiveCells << "\n  mesh  " << o.outputMeshFilename << "\n  mesh vertices  "
           << result->meshVertices << "\n  mesh triangles  " << result->meshTriangles << "\n";

@@ -155,6 +155,13 @@ struct Options {
   bool pointCloudMinViewsGiven = false, pointCloudPixelStepGiven = false, pointCloudToleranceGiven = false,
        pointCloudRelToleranceGiven = false, pointCloudNormalToleranceGiven = false, pointCloudNormalRelToleranceGiven = false;
   bool pointCloudKeepDuplicates = false, pointCloudColors = false;
+  // with pointCloudCellSize the cloud is thinned on the GPU behind the build, before it is written (dmi_views_thin_points,
+  // DESIGN.md 8o): one point per occupied cell of this size that holds at least pointCloudMinCellPoints points, at their mean, and
+  // the .vtp gets the point array NbMergedPoints.  pointCloudKeepDuplicates together with a cell size is what averages across views:
+  // every view's points of one surface element fall into one cell, and the mean averages their independent depth noise
+  double pointCloudCellSize = 0.0;
+  long long pointCloudMinCellPoints = 1;
+  bool pointCloudCellSizeGiven = false, pointCloudMinCellPointsGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -220,6 +227,10 @@ struct RunResult {
   unsigned long long pointCloudViews = 0, pointCloudValidPixels = 0, pointCloudCandidates = 0, pointCloudOwned = 0, pointCloudPoints = 0,
                      pointCloudWithNormal = 0;
   double pointCloudKernelMs = 0.0;
+  // --pointCloudCellSize: the report of the thinning (include/dmi.h: dmi_points_thin_report); pointCloudPoints stays the build's
+  unsigned long long pointCloudCells = 0, pointCloudCellsKept = 0, pointCloudMultiViewCells = 0, pointCloudLargestCell = 0,
+                     pointCloudThinnedWithNormal = 0;
+  double pointCloudThinKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);
@@ -241,9 +252,10 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
                    const int32_t *support = nullptr);
 // a point cloud as VTK XML PolyData in the same conventions: Float64 Points, one Verts cell per point (Int64 connectivity 0, 1, 2
 // ... and offsets 1, 2, 3 ...), the point arrays Normals (Float32 x 3, the section's Normals), ViewIndex and NbAgreeingViews (Int32)
-// and, with `color` ([nPoints][3] u8), Color (UInt8 x 3) behind them
+// and, with `color` ([nPoints][3] u8), Color (UInt8 x 3) behind them; with `merged` ([nPoints] u32: the points each point of a thinned
+// cloud was merged from) NbMergedPoints (UInt32) behind NbAgreeingViews.  Without `merged` the file is what it was before the array existed.
 bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
-                     const int32_t *agreeing, const uint8_t *color, std::string *error);
+                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged = nullptr);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

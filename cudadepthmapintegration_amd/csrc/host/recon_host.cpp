@@ -1088,8 +1088,29 @@ bool DepthViewSet::BuildPoints(double absTolerance, double relTolerance, double 
   return true;
 }
 
+bool DepthViewSet::ThinPoints(double cellSize, int minPoints, DepthThinReport *report) {
+  dmi_points_thin_report r;
+  uint64_t n = 0;
+  if ((Code = dmi_views_thin_points(Set, cellSize, (int32_t)minPoints, &n, &r)) != DMI_OK) return Fail("dmi_views_thin_points");
+  NPoints = n;
+  if (report) {
+    *report = DepthThinReport();
+    report->pointsIn = r.points_in;
+    report->cells = r.cells;
+    report->cellsKept = r.cells_kept;
+    report->multiViewCells = r.multi_view_cells;
+    report->largestCell = r.largest_cell;
+    report->withNormal = r.with_normal;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
 bool DepthViewSet::DownloadPoints(DepthPoints *points) {
   const size_t n = (size_t)NPoints;
+  points->members.resize(n);
+  if ((Code = dmi_views_download_point_members(Set, 0, NPoints, points->members.data())) != DMI_OK)
+    return Fail("dmi_views_download_point_members");
   points->xyz.resize(3 * n);
   points->normal.resize(3 * n);
   points->view.resize(n);

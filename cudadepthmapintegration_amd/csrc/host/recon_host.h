@@ -184,6 +184,12 @@ struct DepthPoints {
   std::vector<double> xyz;    // [n][3]
   std::vector<float> normal;  // [n][3], zero where a point has none
   std::vector<int32_t> view, pixel, count;  // [n]: the view, py * W + px in image coordinates, the views that agree
+  std::vector<uint32_t> members;            // [n]: the points each was merged from (1 unless DepthViewSet::ThinPoints has run)
+};
+// ... and the report of a thinning of it on a voxel grid (dmi_views_thin_points)
+struct DepthThinReport {
+  uint64_t pointsIn = 0, cells = 0, cellsKept = 0, multiViewCells = 0, largestCell = 0, withNormal = 0;
+  double kernelMs = 0.0;  // hipEvent time of the thinning's kernels
 };
 
 // Not in the reference: the views' depths resident on one GPU from the first of the steps above to the fusion (dmi_view_set,
@@ -212,6 +218,9 @@ class DepthViewSet {
   // The point cloud of the set's current depths, built on the device and kept there until the depths change; then all of it
   bool BuildPoints(double absTolerance, double relTolerance, double normalAbsTolerance, double normalRelTolerance, int minViews,
                    int pixelStep, bool dedupe, DepthPointsReport *report);
+  // The built cloud replaced, on the device, by one point per occupied cell of cellSize that holds at least minPoints points, at
+  // their mean (once per build); DownloadPoints then brings the thinned cloud
+  bool ThinPoints(double cellSize, int minPoints, DepthThinReport *report);
   bool DownloadPoints(DepthPoints *points);
   int Width() const { return W; }
   int Height() const { return H; }

@@ -55,7 +55,7 @@ extern "C" {
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
                            *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles;
-                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms */
+                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms; dmi_thin_point_cloud, dmi_views_thin_points, dmi_views_download_point_members, dmi_views_get_thin_pass_ms, dmi_views_set_thin_wave_cell_points */
 
 typedef struct dmi_context dmi_context;
 
@@ -1102,6 +1102,72 @@ int dmi_views_build_points(dmi_view_set *s, double abs_tolerance, double rel_tol
 int dmi_views_download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz, float *normal, int32_t *view,
                               int32_t *pixel, int32_t *n_views /* each nullable */);
 int dmi_views_get_points_pass_ms(dmi_view_set *s, double out_ms[5]);
+
+/* ---- A point cloud thinned and merged on a voxel grid (added after round 5, dmi_abi_version() stays 5) ----
+ * One point per occupied cell of a grid of one cell size, at the mean of the points that fell into it, with a merged normal: what
+ * PCL's VoxelGrid or Open3D's voxel_down_sample does to a cloud (only the intent is shared, not the numbers); cells with fewer than
+ * min_points members can be dropped, which is the density outlier filter of those tools.  On a cloud built with dedupe = 0 the
+ * members of a cell are the same surface element as several views saw it, and the mean averages their independent depth noise.
+ * csrc/depth_points_thin.hip.  Definition, met bit for bit by the device and by tests/depth_points_thin_np.py.
+ * The input is a cloud of P points in a given order, each with xyz f64[3], normal f32[3] (the zero vector: no normal), view, pixel and
+ * count int32; an absent input array is one of zeros.  Parameters: cell_size, min_points.  All arithmetic is f64, with every
+ * operation rounded on its own, no FMA and no reassociation; comparisons with a NaN are false; divisions and the square root are
+ * correctly rounded.
+ *   1. BOUNDS and BINS are dmi_decimate_isosurface's, word for word, with p = xyz: lo_d and hi_d are the minimum and the maximum of
+ *      xyz[i][d] over all P points (exact, independent of order); a non-finite coordinate anywhere refuses the call; with
+ *      h = cell_size, b_d(i) = floor((xyz[i][d] - lo_d) / h), the subtraction and the division each rounded, no reciprocal;
+ *      n_d = b_d evaluated at hi_d, plus 1; any n_d > 2^21 refuses the call (the message names the smallest acceptable cell size);
+ *      the key (b_2*n_1 + b_1)*n_0 + b_0 stays within 63 bits.
+ *   2. CELLS.  A cell is the set of all input points with the same (b_0, b_1, b_2).  Cells are ordered by ascending (b_2, b_1, b_0);
+ *      the members m_0 < m_1 < ... of a cell are taken in ascending input index (for a view set's cloud: ascending (view, py, px)).
+ *   3. KEPT.  A cell of k members is kept iff k >= min_points (min_points >= 1).
+ *   4. One output point per kept cell, in cell order:
+ *      xyz_d = (((xyz[m_0][d] + xyz[m_1][d]) + xyz[m_2][d]) + ...) / (double)k, the first member starting the sum (a cell of one
+ *      keeps its point's bits, a -0.0 included);
+ *      normal: with k == 1 the member's, copied.  Otherwise t_j = (((double)normal[m_0][j] + (double)normal[m_1][j]) + ...) over all
+ *      members (one without a normal adds its zeros), L = sqrt((t_0*t_0 + t_1*t_1) + t_2*t_2), and n_j = (float)(t_j / L) iff L is
+ *      finite and > 0; otherwise the normal is (0, 0, 0);
+ *      view and pixel: those of m_0 (a colour looked up through them is a real member's);
+ *      count: the maximum of the members' counts;  members (uint32): k.
+ *   5. REPORT (dmi_points_thin_report).  points_in: P.  cells: the occupied cells.  cells_kept: the kept ones = the output's points.
+ *      multi_view_cells: kept cells whose first and last member differ in view.  largest_cell: the most members any cell has, kept
+ *      or not.  with_normal: output points whose normal is not the zero vector.  kernel_ms: the hipEvent time of the call's kernels.
+ *
+ * dmi_thin_point_cloud is context-free, like the depth-map filters: host arrays in, host arrays out; it uploads in pieces, runs the
+ * kernels, downloads and frees.  normal, view, pixel and count are nullable, and so are out_members and r; the other output arrays
+ * hold P entries and may be the input arrays.  *n_out: the output's points.  P == 0 is a success with 0 points that touches no
+ * device.  DMI_ERR_INVALID_ARGUMENT before the device is touched: a cell_size that is NaN, infinite or <= 0; min_points < 1;
+ * P >= 2^32; a null xyz, output array or n_out; a device out of range.  The refusals of step 1, made on the device's bounds, return
+ * DMI_ERR_INVALID_ARGUMENT too.  A call that is refused or fails leaves the outputs untouched.  dmi_last_error(NULL) has the text.
+ *
+ * dmi_views_thin_points replaces the set's current cloud (dmi_views_build_points) by exactly what dmi_thin_point_cloud returns for
+ * it: the same implementation, with no copy to the host.  The result is built beside the old cloud and swapped in last: a call that
+ * is refused or fails leaves the old cloud.  DMI_ERR_STATE without a current build, and on a cloud that is thinned already (a
+ * centroid of centroids is not the centroid: build again).  A success counts as a step in dmi_views_info::steps; the thinned cloud
+ * (52 bytes a point) counts in device_bytes; whatever drops the built cloud drops this one.  dmi_views_download_points serves the
+ * thinned cloud as it serves the built one.  During the call the set holds 68 bytes per input point besides the two clouds
+ * (DESIGN.md 8o), freed when it ends.  It synchronises three times: for the bounds, for the counts, for the report.
+ *   dmi_views_download_point_members   k of the points [first, first + count); 1 for every point of a cloud that is not thinned.
+ *              DMI_ERR_STATE without a current build.
+ *   dmi_views_get_thin_pass_ms   the last thinning's kernel time by pass: bounds, keys, sort, ranks with their scans,
+ *              representatives.  DMI_ERR_STATE unless the current cloud is a thinned one.
+ *   dmi_views_set_thin_wave_cell_points   a cell of more than k members (k >= 1) is summed by a wave of its own, any other by one
+ *              lane.  Like dmi_color_set_render_queue_capacity, no value changes a bit of the result; it lets a test drive the wave
+ *              pass at small shapes.  dmi_thin_point_cloud uses the default, 32. */
+typedef struct dmi_points_thin_report {
+  uint64_t points_in, cells, cells_kept, multi_view_cells, largest_cell, with_normal;
+  double kernel_ms;
+} dmi_points_thin_report;
+int dmi_thin_point_cloud(const double *xyz, const float *normal /* nullable */, const int32_t *view /* nullable */,
+                         const int32_t *pixel /* nullable */, const int32_t *count /* nullable */, uint64_t n_points, double cell_size,
+                         int32_t min_points, int32_t device, double *out_xyz, float *out_normal, int32_t *out_view, int32_t *out_pixel,
+                         int32_t *out_count, uint32_t *out_members /* nullable */, uint64_t *n_out,
+                         dmi_points_thin_report *r /* nullable */);
+int dmi_views_thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t *n_points,
+                          dmi_points_thin_report *r /* nullable */);
+int dmi_views_download_point_members(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out);
+int dmi_views_get_thin_pass_ms(dmi_view_set *s, double out_ms[5]);
+int dmi_views_set_thin_wave_cell_points(dmi_view_set *s, int32_t k);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

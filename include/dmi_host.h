@@ -142,6 +142,9 @@ typedef struct dmi_cli_options {
   double depth_smooth_rel_tolerance;     /* --depthSmoothRelTolerance (default 0.01) */
   int64_t depth_smooth_iterations;       /* --depthSmoothIterations (default 1) */
   int32_t depth_staged_filters;          /* --depthStagedFilters: the depth-map steps through the staged calls, not on a resident view set */
+  /* not in the reference, only with --outputPointCloudFilename (dmi_views_thin_points, dmi.h); appended to the struct: */
+  double point_cloud_cell_size;          /* --pointCloudCellSize v: thin the point cloud on a voxel grid before it is written; 0: not given */
+  int64_t point_cloud_min_cell_points;   /* --pointCloudMinCellPoints N (default 1) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
