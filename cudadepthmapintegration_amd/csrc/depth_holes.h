@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "depth_holes_rules.h"
+#include "dmi_buffer.h"
 
 namespace dmi {
 
@@ -25,6 +26,13 @@ struct HolesPiece {
   int32_t *out_size;      // [count][H][W] or null
   int64_t count;
 };
+// a piece of `count` views over its buffers, for the context-free call's staged piece and the resident view set's alike
+inline HolesPiece holes_piece(double *depth, const double *cost, const DeviceBuffer &label, const DeviceBuffer &record,
+                              const DeviceBuffer &rim_lo, const DeviceBuffer &rim_hi, const DeviceBuffer &border_down,
+                              const DeviceBuffer &border_right, int32_t *out_size, int64_t count) {
+  return {depth, cost, label.as<uint32_t>(), record.as<uint32_t>(), rim_lo.as<uint64_t>(), rim_hi.as<uint64_t>(), border_down.as<uint64_t>(),
+          border_right.as<uint64_t>(), out_size, count};
+}
 
 // tiles of a piece (the border arrays hold this many entries each): depth_speckle_rules.h's 64 x 32
 int64_t holes_tiles(int32_t W, int32_t H, int64_t count);

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "depth_speckle_rules.h"
+#include "dmi_buffer.h"
 
 namespace dmi {
 
@@ -27,6 +28,11 @@ struct SpecklePiece {
   int32_t *out_size;      // [count][H][W] or null
   int64_t count;
 };
+// a piece of `count` views over its buffers, for the context-free call's staged piece and the resident view set's alike
+inline SpecklePiece speckle_piece(double *depth, const double *cost, const DeviceBuffer &label, const DeviceBuffer &size,
+                                  const DeviceBuffer &border_down, const DeviceBuffer &border_right, int32_t *out_size, int64_t count) {
+  return {depth, cost, label.as<uint32_t>(), size.as<uint32_t>(), border_down.as<uint64_t>(), border_right.as<uint64_t>(), out_size, count};
+}
 
 // tiles of a piece under `tuning` (the border arrays hold this many entries each)
 int64_t speckle_tiles(int32_t W, int32_t H, int64_t count, const SpeckleTuning &tuning);

@@ -1,6 +1,6 @@
 // dmi_capi_bounds.hip -- dmi_estimate_scene_bounds of include/dmi.h: the argument checks (all of them before the device is touched),
 // the staged upload into resident planes (8g's upload pass), the count and select launches of scene_bounds.hip and one download of
-// the result.  Context-free, like dmi_filter_depth_consistency: everything the call allocates it frees before it returns.  A
+// the result.  Context-free, on the scaffold of dmi_depth_call.h: everything the call allocates it frees before it returns.  A
 // failure's text is dmi_last_error(NULL)'s.
 #include <stdlib.h>
 
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "dmi_context.h"
+#include "dmi_depth_call.h"
 #include "dmi_view_set.h"
 #include "scene_bounds.h"
 
@@ -17,27 +18,9 @@ namespace {
 
 using dmi::fail;
 
-constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up in pieces of whole views, as many as fit this (at least one)
-
 #ifdef DMI_TUNING
 double g_last_plain_read_ms = 0.0, g_last_select_ms = 0.0;
 #endif
-
-// what the call holds on the device and the events that time its kernels; released whatever way the call ends
-struct Holdings {
-  dmi::DeviceBuffer planes, cameras, stage_depth, stage_cost, state, hist;
-  hipStream_t stream = nullptr;
-  hipEvent_t events[2] = {nullptr, nullptr};
-  ~Holdings() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    dmi::free_buffers({&planes, &cameras, &stage_depth, &stage_cost, &state, &hist});
-    for (hipEvent_t e : events)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-#define DMI_SB_HIP(call) DMI_HIP(nullptr, call)
 
 int estimate(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4, int32_t n, int32_t W,
              int32_t H, const double *axes9, double trim_fraction, int32_t pixel_step, int32_t device, double lo[3], double hi[3],
@@ -50,9 +33,7 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
   if (!lo) return bad("lo is null");
   if (!hi) return bad("hi is null");
   if (!n_points) return bad("n_points is null");
-  if (n < 1) return bad("n >= 1 required");
-  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
-  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
+  if (const char *what = dmi::size_refusal(n, W, H)) return bad(what);
   if ((uint64_t)n * (uint64_t)W * (uint64_t)H >= (uint64_t(1) << 53)) return bad("n * W * H must stay below 2^53");
   if (!(trim_fraction >= 0.0 && trim_fraction <= 0.5)) return bad("trim_fraction must lie in [0, 0.5]");  // false for NaN
   if (pixel_step < 1) return bad("pixel_step >= 1 required");
@@ -61,82 +42,52 @@ int estimate(const double *depth, const double *best_cost, double threshold, con
   if (!dmi::bounds_axes(axes9, &axes)) return bad("axes9 holds a value that is not finite");
   if (const int32_t m = dmi::first_view_with_other_k(K4, n); m >= 0) return bad(dmi::other_k_message(m));
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
-  }
-  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
-  DMI_SB_HIP(hipSetDevice(device));
-  int compute_units = 0;
-  DMI_SB_HIP(hipDeviceGetAttribute(&compute_units, hipDeviceAttributeMultiprocessorCount, device));
-
+  // what the call holds on the device; the two events stand around whatever pass is being timed
+  struct {
+    dmi::DeviceBuffer planes, cameras, stage_depth, stage_cost, state, hist;
+  } b;
+  dmi::CallHoldings h({&b.planes, &b.cameras, &b.stage_depth, &b.stage_cost, &b.state, &b.hist});
+  if (const dmi::CallFailure f = h.open(entry, device, 2, true); f.code != DMI_OK) return fail(nullptr, f.code, f.text);
+  const int compute_units = h.compute_units;
   const dmi::BoundsTuning tuning = dmi::bounds_tuning_from_environment();
-
-  Holdings h;
-  DMI_SB_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-  for (hipEvent_t &e : h.events) DMI_SB_HIP(hipEventCreate(&e));
   const size_t plane = (size_t)W * H, views = (size_t)n;
-  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));
+  const size_t chunk = dmi::staged_views(plane * sizeof(double), views);
   constexpr size_t kHistBytes = sizeof(unsigned long long) * dmi::bounds_rules::kTargets * dmi::bounds_rules::kBins;
-  DMI_SB_HIP(dmi::grow_buffer(h.planes, views * plane * sizeof(double)));
-  DMI_SB_HIP(dmi::grow_buffer(h.cameras, views * sizeof(dmi::ConsistencyCamera)));
-  DMI_SB_HIP(dmi::grow_buffer(h.stage_depth, chunk * plane * sizeof(double)));
-  if (best_cost) DMI_SB_HIP(dmi::grow_buffer(h.stage_cost, chunk * plane * sizeof(double)));
-  DMI_SB_HIP(dmi::grow_buffer(h.state, sizeof(dmi::BoundsState)));
-  DMI_SB_HIP(dmi::grow_buffer(h.hist, kHistBytes));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.planes, views * plane * sizeof(double)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.cameras, views * sizeof(dmi::ConsistencyCamera)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.stage_depth, chunk * plane * sizeof(double)));
+  if (best_cost) DMI_HIP(nullptr, dmi::grow_buffer(b.stage_cost, chunk * plane * sizeof(double)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.state, sizeof(dmi::BoundsState)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.hist, kHistBytes));
 
   double total_ms = 0.0;
-  auto add_span = [&]() -> hipError_t {  // (the stream has been synchronised behind events[1])
-    float ms = 0.f;
-    const hipError_t e = hipEventElapsedTime(&ms, h.events[0], h.events[1]);
-    if (e == hipSuccess) total_ms += (double)ms;
-    return e;
-  };
-
-  {
-    const std::vector<dmi::ConsistencyCamera> cameras = dmi::consistency_cameras(K4, RT4, views);
-    DMI_SB_HIP(hipMemcpyAsync(h.cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, h.stream));
-    DMI_SB_HIP(hipStreamSynchronize(h.stream));  // `cameras` goes out of scope
-  }
-  DMI_SB_HIP(hipMemsetAsync(h.state.ptr, 0, sizeof(dmi::BoundsState), h.stream));
-  DMI_SB_HIP(hipMemsetAsync(h.hist.ptr, 0, kHistBytes, h.stream));
-
-  // up: threshold, validity, -1 for everything else and the row flip happen in the pass that unpacks a staged piece
-  for (size_t m0 = 0; m0 < views; m0 += chunk) {
-    const size_t cnt = std::min(chunk, views - m0);
-    DMI_SB_HIP(hipMemcpyAsync(h.stage_depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    if (best_cost)
-      DMI_SB_HIP(hipMemcpyAsync(h.stage_cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    DMI_SB_HIP(hipEventRecord(h.events[0], h.stream));
-    DMI_SB_HIP(dmi::launch_consistency_upload(h.stage_depth.as<double>(), best_cost ? h.stage_cost.as<double>() : nullptr, threshold, W, H,
-                                              (int64_t)cnt, h.planes.as<double>(), (int64_t)m0, h.stream));
-    DMI_SB_HIP(hipEventRecord(h.events[1], h.stream));
-    DMI_SB_HIP(hipStreamSynchronize(h.stream));  // the stage buffers are reused by the next piece
-    DMI_SB_HIP(add_span());
-  }
+  DMI_HIP(nullptr, dmi::upload_cameras(b.cameras, K4, RT4, views, h.stream));
+  DMI_HIP(nullptr, hipMemsetAsync(b.state.ptr, 0, sizeof(dmi::BoundsState), h.stream));
+  DMI_HIP(nullptr, hipMemsetAsync(b.hist.ptr, 0, kHistBytes, h.stream));
+  DMI_HIP(nullptr, dmi::upload_flipped(depth, best_cost, threshold, W, H, views, chunk, b.stage_depth, b.stage_cost, b.planes.as<double>(), h.stream,
+                                       h.events, &total_ms));
 
   // the select: count and select, pass after pass, with no host round trip in between
   dmi::BoundsState result;
-  DMI_SB_HIP(dmi::run_bounds_select(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, pixel_step, axes, trim_fraction,
-                                    h.state.as<dmi::BoundsState>(), h.hist.as<unsigned long long>(), compute_units, tuning, h.stream,
-                                    h.events, &result));
-  DMI_SB_HIP(add_span());
+  DMI_HIP(nullptr, dmi::run_bounds_select(b.planes.as<double>(), b.cameras.as<dmi::ConsistencyCamera>(), n, W, H, pixel_step, axes, trim_fraction,
+                                          b.state.as<dmi::BoundsState>(), b.hist.as<unsigned long long>(), compute_units, tuning, h.stream,
+                                          h.events, &result));
+  DMI_HIP(nullptr, dmi::add_spans(h.events, 1, &total_ms));
 #ifdef DMI_TUNING
   {
     float ms = 0.f;
-    DMI_SB_HIP(hipEventElapsedTime(&ms, h.events[0], h.events[1]));
+    DMI_HIP(nullptr, hipEventElapsedTime(&ms, h.events[0], h.events[1]));
     g_last_select_ms = (double)ms;
     // the yardstick: one plain read of the same planes (the stage buffer serves as the sink)
     const unsigned read_blocks = (unsigned)std::min<size_t>((views * plane + 255) / 256, (size_t)std::max(compute_units, 1) * 8);
     for (int round = 0; round < 2; ++round) {  // the second one is the measurement
-      DMI_SB_HIP(hipEventRecord(h.events[0], h.stream));
-      DMI_SB_HIP(dmi::launch_bounds_plain_read(h.planes.as<double>(), (int64_t)(views * plane), h.stage_depth.as<double>(), read_blocks,
-                                               h.stream));
-      DMI_SB_HIP(hipEventRecord(h.events[1], h.stream));
-      DMI_SB_HIP(hipStreamSynchronize(h.stream));
+      DMI_HIP(nullptr, hipEventRecord(h.events[0], h.stream));
+      DMI_HIP(nullptr, dmi::launch_bounds_plain_read(b.planes.as<double>(), (int64_t)(views * plane), b.stage_depth.as<double>(), read_blocks,
+                                                     h.stream));
+      DMI_HIP(nullptr, hipEventRecord(h.events[1], h.stream));
+      DMI_HIP(nullptr, hipStreamSynchronize(h.stream));
     }
-    DMI_SB_HIP(hipEventElapsedTime(&ms, h.events[0], h.events[1]));
+    DMI_HIP(nullptr, hipEventElapsedTime(&ms, h.events[0], h.events[1]));
     g_last_plain_read_ms = (double)ms;
   }
 #endif

@@ -1,6 +1,6 @@
 // dmi_capi_consistency.hip -- dmi_filter_depth_consistency of include/dmi.h: the argument checks (all of them before the device is
-// touched), the staged upload, the launches of depth_consistency.hip and the staged download.  Context-free, like dmi_color_mesh:
-// everything the call allocates it frees before it returns.  A failure's text is dmi_last_error(NULL)'s.
+// touched), the staged upload, the launches of depth_consistency.hip and the staged download.  Context-free, on the scaffold of
+// dmi_depth_call.h: everything the call allocates it frees before it returns.  A failure's text is dmi_last_error(NULL)'s.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -10,35 +10,16 @@
 
 #include "depth_consistency.h"
 #include "dmi_context.h"
+#include "dmi_depth_call.h"
 #include "dmi_view_set.h"
 
 namespace {
 
 using dmi::fail;
 
-constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up and comes down in pieces of at most this, as dmi_add_views stages it
-
-bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
-
 #ifdef DMI_TUNING
 unsigned long long g_last_undecided = 0;
 #endif
-
-// what the call holds on the device and the events that time its kernels; released whatever way the call ends
-struct Holdings {
-  dmi::DeviceBuffer planes, counts, cameras, stage_depth, stage_cost, stage_count, undecided;
-  hipStream_t stream = nullptr;
-  hipEvent_t events[2] = {nullptr, nullptr};
-  ~Holdings() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    dmi::free_buffers({&planes, &counts, &cameras, &stage_depth, &stage_cost, &stage_count, &undecided});
-    for (hipEvent_t e : events)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-#define DMI_DC_HIP(call) DMI_HIP(nullptr, call)
 
 int filter(const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4, int32_t n, int32_t W,
            int32_t H, double abs_tolerance, double rel_tolerance, int32_t min_views, int32_t device, double *out_depth, int32_t *out_count,
@@ -49,95 +30,63 @@ int filter(const double *depth, const double *best_cost, double threshold, const
   if (!K4) return bad("K4 is null");
   if (!RT4) return bad("RT4 is null");
   if (!out_depth) return bad("out_depth is null");
-  if (n < 1) return bad("n >= 1 required");
-  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
-  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
+  if (const char *what = dmi::size_refusal(n, W, H)) return bad(what);
   if (min_views < 0) return bad("min_views >= 0 required");
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
   if (best_cost && threshold != threshold) return bad("threshold is NaN");
   if (const int32_t m = dmi::first_view_with_other_k(K4, n); m >= 0) return bad(dmi::other_k_message(m));
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
-  }
-  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
-  DMI_DC_HIP(hipSetDevice(device));
-
+  // what the call holds on the device; the two events stand around whatever pass is being timed
+  struct {
+    dmi::DeviceBuffer planes, counts, cameras, stage_depth, stage_cost, stage_count, undecided;
+  } b;
+  dmi::CallHoldings h({&b.planes, &b.counts, &b.cameras, &b.stage_depth, &b.stage_cost, &b.stage_count, &b.undecided});
+  if (const dmi::CallFailure f = h.open(entry, device, 2); f.code != DMI_OK) return fail(nullptr, f.code, f.text);
   const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
-
-  Holdings h;
-  DMI_DC_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-  for (hipEvent_t &e : h.events) DMI_DC_HIP(hipEventCreate(&e));
   const size_t plane = (size_t)W * H, views = (size_t)n;
-  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));
-  DMI_DC_HIP(dmi::grow_buffer(h.planes, views * plane * sizeof(double)));
-  DMI_DC_HIP(dmi::grow_buffer(h.counts, views * plane * sizeof(int32_t)));
-  DMI_DC_HIP(dmi::grow_buffer(h.cameras, views * sizeof(dmi::ConsistencyCamera)));
-  DMI_DC_HIP(dmi::grow_buffer(h.stage_depth, chunk * plane * sizeof(double)));
-  if (best_cost) DMI_DC_HIP(dmi::grow_buffer(h.stage_cost, chunk * plane * sizeof(double)));
-  if (out_count) DMI_DC_HIP(dmi::grow_buffer(h.stage_count, chunk * plane * sizeof(int32_t)));
+  const size_t chunk = dmi::staged_views(plane * sizeof(double), views);
+  DMI_HIP(nullptr, dmi::grow_buffer(b.planes, views * plane * sizeof(double)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.counts, views * plane * sizeof(int32_t)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.cameras, views * sizeof(dmi::ConsistencyCamera)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.stage_depth, chunk * plane * sizeof(double)));
+  if (best_cost) DMI_HIP(nullptr, dmi::grow_buffer(b.stage_cost, chunk * plane * sizeof(double)));
+  if (out_count) DMI_HIP(nullptr, dmi::grow_buffer(b.stage_count, chunk * plane * sizeof(int32_t)));
   unsigned long long *undecided = nullptr;
 #ifdef DMI_TUNING
-  DMI_DC_HIP(dmi::grow_buffer(h.undecided, sizeof(unsigned long long)));
-  undecided = h.undecided.as<unsigned long long>();
-  DMI_DC_HIP(hipMemsetAsync(undecided, 0, sizeof(unsigned long long), h.stream));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.undecided, sizeof(unsigned long long)));
+  undecided = b.undecided.as<unsigned long long>();
+  DMI_HIP(nullptr, hipMemsetAsync(undecided, 0, sizeof(unsigned long long), h.stream));
 #endif
 
   double total_ms = 0.0;
-  auto add_span = [&]() -> hipError_t {  // (the stream has been synchronised behind events[1])
-    float ms = 0.f;
-    const hipError_t e = hipEventElapsedTime(&ms, h.events[0], h.events[1]);
-    if (e == hipSuccess) total_ms += (double)ms;
-    return e;
-  };
-
-  {
-    const std::vector<dmi::ConsistencyCamera> cameras = dmi::consistency_cameras(K4, RT4, views);
-    DMI_DC_HIP(hipMemcpyAsync(h.cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, h.stream));
-    DMI_DC_HIP(hipStreamSynchronize(h.stream));  // `cameras` goes out of scope
-  }
-  DMI_DC_HIP(hipMemsetAsync(h.counts.ptr, 0, views * plane * sizeof(int32_t), h.stream));
-
-  // up: threshold, validity, -1 for everything else and the row flip happen in the pass that unpacks a staged piece
-  for (size_t m0 = 0; m0 < views; m0 += chunk) {
-    const size_t cnt = std::min(chunk, views - m0);
-    DMI_DC_HIP(hipMemcpyAsync(h.stage_depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    if (best_cost)
-      DMI_DC_HIP(hipMemcpyAsync(h.stage_cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    DMI_DC_HIP(hipEventRecord(h.events[0], h.stream));
-    DMI_DC_HIP(dmi::launch_consistency_upload(h.stage_depth.as<double>(), best_cost ? h.stage_cost.as<double>() : nullptr, threshold, W, H,
-                                              (int64_t)cnt, h.planes.as<double>(), (int64_t)m0, h.stream));
-    DMI_DC_HIP(hipEventRecord(h.events[1], h.stream));
-    DMI_DC_HIP(hipStreamSynchronize(h.stream));  // the stage buffers are reused by the next piece
-    DMI_DC_HIP(add_span());
-  }
+  DMI_HIP(nullptr, dmi::upload_cameras(b.cameras, K4, RT4, views, h.stream));
+  DMI_HIP(nullptr, hipMemsetAsync(b.counts.ptr, 0, views * plane * sizeof(int32_t), h.stream));
+  DMI_HIP(nullptr, dmi::upload_flipped(depth, best_cost, threshold, W, H, views, chunk, b.stage_depth, b.stage_cost, b.planes.as<double>(), h.stream,
+                                       h.events, &total_ms));
 
   // the counts: every source pixel against the target views, all in one launch or group by group
   if (n > 1) {
-    DMI_DC_HIP(dmi::run_consistency_count(h.planes.as<double>(), h.cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
-                                          rel_tolerance, tuning, h.counts.as<int32_t>(), undecided, h.stream, h.events));
-    DMI_DC_HIP(hipStreamSynchronize(h.stream));
-    DMI_DC_HIP(add_span());
+    DMI_HIP(nullptr, dmi::run_consistency_count(b.planes.as<double>(), b.cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
+                                                rel_tolerance, tuning, b.counts.as<int32_t>(), undecided, h.stream, h.events));
+    DMI_HIP(nullptr, hipStreamSynchronize(h.stream));
+    DMI_HIP(nullptr, dmi::add_spans(h.events, 1, &total_ms));
   }
 
   // down, through the same stage buffers
   for (size_t m0 = 0; m0 < views; m0 += chunk) {
     const size_t cnt = std::min(chunk, views - m0);
-    DMI_DC_HIP(hipEventRecord(h.events[0], h.stream));
-    DMI_DC_HIP(dmi::launch_consistency_finish(h.planes.as<double>(), h.counts.as<int32_t>(), W, H, (int64_t)m0, (int64_t)cnt, min_views,
-                                              h.stage_depth.as<double>(), out_count ? h.stage_count.as<int32_t>() : nullptr, h.stream));
-    DMI_DC_HIP(hipEventRecord(h.events[1], h.stream));
-    DMI_DC_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.stage_depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    DMI_HIP(nullptr, hipEventRecord(h.events[0], h.stream));
+    DMI_HIP(nullptr, dmi::launch_consistency_finish(b.planes.as<double>(), b.counts.as<int32_t>(), W, H, (int64_t)m0, (int64_t)cnt, min_views,
+                                                    b.stage_depth.as<double>(), out_count ? b.stage_count.as<int32_t>() : nullptr, h.stream));
+    DMI_HIP(nullptr, hipEventRecord(h.events[1], h.stream));
+    DMI_HIP(nullptr, hipMemcpyAsync(out_depth + m0 * plane, b.stage_depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
     if (out_count)
-      DMI_DC_HIP(hipMemcpyAsync(out_count + m0 * plane, h.stage_count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
-    DMI_DC_HIP(hipStreamSynchronize(h.stream));
-    DMI_DC_HIP(add_span());
+      DMI_HIP(nullptr, hipMemcpyAsync(out_count + m0 * plane, b.stage_count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
+    DMI_HIP(nullptr, hipStreamSynchronize(h.stream));
+    DMI_HIP(nullptr, dmi::add_spans(h.events, 1, &total_ms));
   }
 #ifdef DMI_TUNING
-  DMI_DC_HIP(hipMemcpy(&g_last_undecided, undecided, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  DMI_HIP(nullptr, hipMemcpy(&g_last_undecided, undecided, sizeof(unsigned long long), hipMemcpyDeviceToHost));
 #endif
   if (kernel_ms) *kernel_ms = total_ms;
   return DMI_OK;

@@ -1,6 +1,6 @@
 // dmi_capi_points_thin.hip -- dmi_thin_point_cloud of include/dmi.h: the argument checks (all of them before the device is touched),
-// the upload of the host arrays in pieces, the thinning, one download of the result.  Context-free, like the depth-map filters:
-// everything the call allocates it frees before it returns.  A failure's text is dmi_last_error(NULL)'s.  The thinning itself,
+// the upload of the host arrays in pieces, the thinning, one download of the result.  Context-free, on the scaffold of
+// dmi_depth_call.h: everything the call allocates it frees before it returns.  A failure's text is dmi_last_error(NULL)'s.  The thinning itself,
 // dmi::run_thin_points, is what dmi_views_thin_points (dmi_capi_viewset.hip) runs on the set's own cloud: one implementation.
 #include <algorithm>
 #include <cmath>
@@ -10,6 +10,7 @@
 
 #include "depth_points_rules.h"
 #include "dmi_context.h"
+#include "dmi_depth_call.h"
 #include "dmi_view_set.h"
 
 namespace dmi {
@@ -158,16 +159,6 @@ using dmi::fail;
 
 constexpr size_t kPieceBytes = size_t(64) << 20;  // host arrays go up, and come down, in pieces of this size
 
-struct Holdings {
-  dmi::DeviceBuffer cloud, result;
-  hipStream_t stream = nullptr;
-  ~Holdings() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    dmi::free_buffers({&cloud, &result});
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
 hipError_t copy_in_pieces(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t stream) {
   for (size_t at = 0; at < bytes; at += kPieceBytes) {
     const hipError_t e = hipMemcpyAsync(static_cast<char *>(dst) + at, static_cast<const char *>(src) + at, std::min(kPieceBytes, bytes - at),
@@ -195,20 +186,15 @@ int thin(const double *xyz, const float *normal, const int32_t *view, const int3
   if (!xyz) return bad("xyz is null");
   if (!out_xyz || !out_normal || !out_view || !out_pixel || !out_count) return bad("an output array is null");
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(nullptr, DMI_ERR_DEVICE, entry + ": no HIP device available");
-  }
-  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
-  DMI_HIP(nullptr, hipSetDevice(device));
-
-  Holdings h;
-  DMI_HIP(nullptr, hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+  struct {
+    dmi::DeviceBuffer cloud, result;
+  } b;
+  dmi::CallHoldings h({&b.cloud, &b.result});  // (the thinning has its own events)
+  if (const dmi::CallFailure f = h.open(entry + ": ", device, 0); f.code != DMI_OK) return fail(nullptr, f.code, f.text);
   pr::Layout in;
   if (!pr::layout_of(n, &in)) return bad("the points do not fit 64 bits of bytes");
-  DMI_HIP(nullptr, dmi::grow_buffer(h.cloud, in.bytes));
-  unsigned char *const base = h.cloud.as<unsigned char>();
+  DMI_HIP(nullptr, dmi::grow_buffer(b.cloud, in.bytes));
+  unsigned char *const base = b.cloud.as<unsigned char>();
   auto up = [&](const void *src, uint64_t offset, uint64_t stride) {  // an absent array is one of zeros
     return src ? copy_in_pieces(base + offset, src, (size_t)(n * stride), hipMemcpyHostToDevice, h.stream)
                : hipMemsetAsync(base + offset, 0, (size_t)(n * stride), h.stream);
@@ -232,13 +218,13 @@ int thin(const double *xyz, const float *normal, const int32_t *view, const int3
   uint64_t held = 0;
   const int rc = dmi::run_thin_points(entry, cloud, cell_size, min_points, dmi::thin_rules::kDefaultWaveCellPoints, h.stream, held,
                                       &outcome, &message);
-  h.result = outcome.result;  // (freed with the rest)
+  b.result = outcome.result;  // (freed with the rest)
   if (rc != DMI_OK) return fail(nullptr, rc, message);
 
   const uint64_t q = outcome.n_out;
   dmi::thin_rules::Layout out;
   (void)dmi::thin_rules::layout_of(q, &out);
-  const unsigned char *const from = h.result.as<unsigned char>();
+  const unsigned char *const from = b.result.as<unsigned char>();
   auto down = [&](void *dst, uint64_t offset, uint64_t stride) {
     return dst && q ? copy_in_pieces(dst, from + offset, (size_t)(q * stride), hipMemcpyDeviceToHost, h.stream) : hipSuccess;
   };

@@ -1,37 +1,18 @@
 // dmi_capi_smooth.hip -- dmi_smooth_depths and dmi_depth_smoothing_weights of include/dmi.h: the argument checks (all of them before
 // the device is touched), and per piece of whole views the upload, one launch of depth_smooth.hip per iteration between two planes
-// and the download.  Context-free, like dmi_fill_depth_holes: everything the call allocates it frees before it returns; the device
-// holds the planes of one piece at a time.  A failure's text is dmi_last_error(NULL)'s.
+// and the download.  Context-free, on the scaffold of dmi_depth_call.h: everything the call allocates it frees before it returns; the
+// device holds the planes of one piece at a time.  A failure's text is dmi_last_error(NULL)'s.
 #include <algorithm>
 #include <string>
 
 #include "depth_smooth.h"
 #include "dmi_context.h"
+#include "dmi_depth_call.h"
 #include "dmi_view_set.h"
 
 namespace {
 
 using dmi::fail;
-
-constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up and comes down in pieces of whole views, as many as fit this
-
-bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
-
-// what the call holds on the device and the events that time its kernels; released whatever way the call ends
-struct Holdings {
-  dmi::DeviceBuffer plane[2], cost, count;
-  hipStream_t stream = nullptr;
-  hipEvent_t events[2] = {nullptr, nullptr};  // before the first iteration's launch and behind the last one's
-  ~Holdings() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    dmi::free_buffers({&plane[0], &plane[1], &cost, &count});
-    for (hipEvent_t e : events)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-#define DMI_DS_HIP(call) DMI_HIP(nullptr, call)
 
 int smooth(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H, double sigma,
            double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations, int32_t device, double *out_depth,
@@ -40,58 +21,48 @@ int smooth(const double *depth, const double *best_cost, double threshold, int32
   auto bad = [&](const std::string &what) { return fail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!depth) return bad("depth is null");
   if (!out_depth) return bad("out_depth is null");
-  if (n < 1) return bad("n >= 1 required");
-  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
-  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
-  if (!finite_and_not_negative(sigma)) return bad("sigma must be finite and >= 0");
+  if (const char *what = dmi::size_refusal(n, W, H)) return bad(what);
+  if (!dmi::finite_and_not_negative(sigma)) return bad("sigma must be finite and >= 0");
   if (!(truncate > 0.0 && truncate <= 4.0)) return bad("truncate must lie in (0, 4]");
   int32_t radius = 0;
   double s[dmi::kDepthSmoothMaxRadius + 1];
   if (dmi::depth_smoothing_weights(sigma, truncate, &radius, s) != 0)
     return bad("the radius ceil(truncate * sigma) must not exceed " + std::to_string(dmi::kDepthSmoothMaxRadius));
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
   if (iterations < 1 || iterations > dmi::kDepthSmoothMaxIterations)
     return bad("iterations must lie in [1, " + std::to_string(dmi::kDepthSmoothMaxIterations) + "]");
   if (best_cost && threshold != threshold) return bad("threshold is NaN");
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
-  }
-  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
-  DMI_DS_HIP(hipSetDevice(device));
-
-  Holdings h;
-  DMI_DS_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-  for (hipEvent_t &e : h.events) DMI_DS_HIP(hipEventCreate(&e));
+  // what the call holds on the device; the events stand before the first iteration's launch and behind the last one's
+  struct {
+    dmi::DeviceBuffer plane[2], cost, count;
+  } b;
+  dmi::CallHoldings h({&b.plane[0], &b.plane[1], &b.cost, &b.count});
+  if (const dmi::CallFailure f = h.open(entry, device, 2); f.code != DMI_OK) return fail(nullptr, f.code, f.text);
   const size_t plane = (size_t)W * H, views = (size_t)n;
-  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));  // a larger view goes whole
-  DMI_DS_HIP(dmi::grow_buffer(h.plane[0], chunk * plane * sizeof(double)));
-  DMI_DS_HIP(dmi::grow_buffer(h.plane[1], chunk * plane * sizeof(double)));
-  if (best_cost) DMI_DS_HIP(dmi::grow_buffer(h.cost, chunk * plane * sizeof(double)));
-  if (out_count) DMI_DS_HIP(dmi::grow_buffer(h.count, chunk * plane * sizeof(int32_t)));
+  const size_t chunk = dmi::staged_views(plane * sizeof(double), views);
+  DMI_HIP(nullptr, dmi::grow_buffer(b.plane[0], chunk * plane * sizeof(double)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.plane[1], chunk * plane * sizeof(double)));
+  if (best_cost) DMI_HIP(nullptr, dmi::grow_buffer(b.cost, chunk * plane * sizeof(double)));
+  if (out_count) DMI_HIP(nullptr, dmi::grow_buffer(b.count, chunk * plane * sizeof(int32_t)));
   const dmi::SmoothArgs args = dmi::smooth_args(s, radius, abs_tolerance, rel_tolerance);
 
   double total_ms = 0.0;
   for (size_t m0 = 0; m0 < views; m0 += chunk) {
     const size_t cnt = std::min(chunk, views - m0);
-    DMI_DS_HIP(hipMemcpyAsync(h.plane[0].ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    DMI_HIP(nullptr, hipMemcpyAsync(b.plane[0].ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
     if (best_cost)
-      DMI_DS_HIP(hipMemcpyAsync(h.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+      DMI_HIP(nullptr, hipMemcpyAsync(b.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
     // iteration k + 1 reads the complete output of iteration k: the two planes take turns
     const double *result = nullptr;
-    DMI_DS_HIP(dmi::run_smooth_piece(h.plane[0].as<double>(), best_cost ? h.cost.as<double>() : nullptr, threshold, h.plane[1].as<double>(),
-                                     h.plane[0].as<double>(), out_count ? h.count.as<int32_t>() : nullptr, (int64_t)cnt, W, H, args,
-                                     iterations, h.stream, h.events, &result));
-    DMI_DS_HIP(hipMemcpyAsync(out_depth + m0 * plane, result, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+    DMI_HIP(nullptr, dmi::run_smooth_piece(b.plane[0].as<double>(), best_cost ? b.cost.as<double>() : nullptr, threshold, b.plane[1].as<double>(),
+                                           b.plane[0].as<double>(), out_count ? b.count.as<int32_t>() : nullptr, (int64_t)cnt, W, H, args,
+                                           iterations, h.stream, h.events, &result));
+    DMI_HIP(nullptr, hipMemcpyAsync(out_depth + m0 * plane, result, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
     if (out_count)
-      DMI_DS_HIP(hipMemcpyAsync(out_count + m0 * plane, h.count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
-    DMI_DS_HIP(hipStreamSynchronize(h.stream));  // the planes are reused by the next piece
-    float ms = 0.f;
-    DMI_DS_HIP(hipEventElapsedTime(&ms, h.events[0], h.events[1]));
-    total_ms += (double)ms;
+      DMI_HIP(nullptr, hipMemcpyAsync(out_count + m0 * plane, b.count.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
+    DMI_HIP(nullptr, hipStreamSynchronize(h.stream));  // the planes are reused by the next piece
+    DMI_HIP(nullptr, dmi::add_spans(h.events, 1, &total_ms));
   }
   if (kernel_ms) *kernel_ms = total_ms;
   return DMI_OK;

@@ -1,6 +1,6 @@
 // dmi_capi_speckle.hip -- dmi_filter_depth_speckles of include/dmi.h: the argument checks (all of them before the device is touched),
-// and per piece of whole views the upload, the four launches of depth_speckle.hip and the download.  Context-free, like
-// dmi_filter_depth_consistency: everything the call allocates it frees before it returns; the device holds the planes of one piece
+// and per piece of whole views the upload, the four launches of depth_speckle.hip and the download.  Context-free, on the
+// scaffold of dmi_depth_call.h: everything the call allocates it frees before it returns; the device holds the planes of one piece
 // at a time.  A failure's text is dmi_last_error(NULL)'s.
 #include <stdlib.h>
 
@@ -9,35 +9,16 @@
 
 #include "depth_speckle.h"
 #include "dmi_context.h"
+#include "dmi_depth_call.h"
 #include "dmi_view_set.h"
 
 namespace {
 
 using dmi::fail;
 
-constexpr size_t kStageBytes = size_t(256) << 20;  // host data goes up and comes down in pieces of whole views, as many as fit this
-
-bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
-
 #ifdef DMI_TUNING
 double g_last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};
 #endif
-
-// what the call holds on the device and the events that time its kernels; released whatever way the call ends
-struct Holdings {
-  dmi::DeviceBuffer depth, cost, label, size, border_down, border_right, out_size;
-  hipStream_t stream = nullptr;
-  hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // before the local pass and behind each of the four
-  ~Holdings() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    dmi::free_buffers({&depth, &cost, &label, &size, &border_down, &border_right, &out_size});
-    for (hipEvent_t e : events)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-#define DMI_DS_HIP(call) DMI_HIP(nullptr, call)
 
 int filter(const double *depth, const double *best_cost, double threshold, int32_t n, int32_t W, int32_t H, double abs_tolerance,
            double rel_tolerance, int64_t min_pixels, int32_t device, double *out_depth, int32_t *out_size, double *kernel_ms) {
@@ -45,63 +26,44 @@ int filter(const double *depth, const double *best_cost, double threshold, int32
   auto bad = [&](const std::string &what) { return fail(nullptr, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!depth) return bad("depth is null");
   if (!out_depth) return bad("out_depth is null");
-  if (n < 1) return bad("n >= 1 required");
-  if (W < 1 || W > 32768) return bad("W must lie in [1, 32768]");
-  if (H < 1 || H > 32768) return bad("H must lie in [1, 32768]");
+  if (const char *what = dmi::size_refusal(n, W, H)) return bad(what);
   if (min_pixels < 0) return bad("min_pixels >= 0 required");
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
   if (best_cost && threshold != threshold) return bad("threshold is NaN");
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    return fail(nullptr, DMI_ERR_DEVICE, entry + "no HIP device available");
-  }
-  if (device < 0 || device >= ndev) return bad("device ordinal out of range");
-  DMI_DS_HIP(hipSetDevice(device));
-
+  // what the call holds on the device; the events stand before the local pass and behind each of the four
+  struct {
+    dmi::DeviceBuffer depth, cost, label, size, border_down, border_right, out_size;
+  } b;
+  dmi::CallHoldings h({&b.depth, &b.cost, &b.label, &b.size, &b.border_down, &b.border_right, &b.out_size});
+  if (const dmi::CallFailure f = h.open(entry, device, 5); f.code != DMI_OK) return fail(nullptr, f.code, f.text);
   const dmi::SpeckleTuning tuning = dmi::speckle_tuning_from_environment();
-
-  Holdings h;
-  DMI_DS_HIP(hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
-  for (hipEvent_t &e : h.events) DMI_DS_HIP(hipEventCreate(&e));
   const size_t plane = (size_t)W * H, views = (size_t)n;
-  const size_t chunk = std::min(views, std::max<size_t>(1, kStageBytes / (plane * sizeof(double))));  // a larger view goes whole
+  const size_t chunk = dmi::staged_views(plane * sizeof(double), views);
   const size_t tiles = (size_t)dmi::speckle_tiles(W, H, (int64_t)chunk, tuning);
-  DMI_DS_HIP(dmi::grow_buffer(h.depth, chunk * plane * sizeof(double)));
-  if (best_cost) DMI_DS_HIP(dmi::grow_buffer(h.cost, chunk * plane * sizeof(double)));
-  DMI_DS_HIP(dmi::grow_buffer(h.label, chunk * plane * sizeof(uint32_t)));
-  DMI_DS_HIP(dmi::grow_buffer(h.size, chunk * plane * sizeof(uint32_t)));
-  DMI_DS_HIP(dmi::grow_buffer(h.border_down, tiles * sizeof(uint64_t)));
-  DMI_DS_HIP(dmi::grow_buffer(h.border_right, tiles * sizeof(uint64_t)));
-  if (out_size) DMI_DS_HIP(dmi::grow_buffer(h.out_size, chunk * plane * sizeof(int32_t)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.depth, chunk * plane * sizeof(double)));
+  if (best_cost) DMI_HIP(nullptr, dmi::grow_buffer(b.cost, chunk * plane * sizeof(double)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.label, chunk * plane * sizeof(uint32_t)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.size, chunk * plane * sizeof(uint32_t)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.border_down, tiles * sizeof(uint64_t)));
+  DMI_HIP(nullptr, dmi::grow_buffer(b.border_right, tiles * sizeof(uint64_t)));
+  if (out_size) DMI_HIP(nullptr, dmi::grow_buffer(b.out_size, chunk * plane * sizeof(int32_t)));
 
   double pass_ms[4] = {0.0, 0.0, 0.0, 0.0};
   for (size_t m0 = 0; m0 < views; m0 += chunk) {
     const size_t cnt = std::min(chunk, views - m0);
-    dmi::SpecklePiece piece;
-    piece.depth = h.depth.as<double>();
-    piece.cost = best_cost ? h.cost.as<double>() : nullptr;
-    piece.label = h.label.as<uint32_t>();
-    piece.size = h.size.as<uint32_t>();
-    piece.border_down = h.border_down.as<uint64_t>();
-    piece.border_right = h.border_right.as<uint64_t>();
-    piece.out_size = out_size ? h.out_size.as<int32_t>() : nullptr;
-    piece.count = (int64_t)cnt;
-    DMI_DS_HIP(hipMemcpyAsync(h.depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    const dmi::SpecklePiece piece =
+        dmi::speckle_piece(b.depth.as<double>(), best_cost ? b.cost.as<double>() : nullptr, b.label, b.size, b.border_down, b.border_right,
+                           out_size ? b.out_size.as<int32_t>() : nullptr, (int64_t)cnt);
+    DMI_HIP(nullptr, hipMemcpyAsync(b.depth.ptr, depth + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
     if (best_cost)
-      DMI_DS_HIP(hipMemcpyAsync(h.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
-    DMI_DS_HIP(dmi::run_speckle_piece(piece, threshold, W, H, abs_tolerance, rel_tolerance, min_pixels, tuning, h.stream, h.events));
-    DMI_DS_HIP(hipMemcpyAsync(out_depth + m0 * plane, h.depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+      DMI_HIP(nullptr, hipMemcpyAsync(b.cost.ptr, best_cost + m0 * plane, cnt * plane * sizeof(double), hipMemcpyHostToDevice, h.stream));
+    DMI_HIP(nullptr, dmi::run_speckle_piece(piece, threshold, W, H, abs_tolerance, rel_tolerance, min_pixels, tuning, h.stream, h.events));
+    DMI_HIP(nullptr, hipMemcpyAsync(out_depth + m0 * plane, b.depth.ptr, cnt * plane * sizeof(double), hipMemcpyDeviceToHost, h.stream));
     if (out_size)
-      DMI_DS_HIP(hipMemcpyAsync(out_size + m0 * plane, h.out_size.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
-    DMI_DS_HIP(hipStreamSynchronize(h.stream));  // the planes are reused by the next piece
-    for (int p = 0; p < 4; ++p) {
-      float ms = 0.f;
-      DMI_DS_HIP(hipEventElapsedTime(&ms, h.events[p], h.events[p + 1]));
-      pass_ms[p] += (double)ms;
-    }
+      DMI_HIP(nullptr, hipMemcpyAsync(out_size + m0 * plane, b.out_size.ptr, cnt * plane * sizeof(int32_t), hipMemcpyDeviceToHost, h.stream));
+    DMI_HIP(nullptr, hipStreamSynchronize(h.stream));  // the planes are reused by the next piece
+    DMI_HIP(nullptr, dmi::add_spans(h.events, 4, pass_ms));
   }
 #ifdef DMI_TUNING
   for (int p = 0; p < 4; ++p) g_last_pass_ms[p] = pass_ms[p];

@@ -2,8 +2,9 @@
 // before the device is touched), the set's life cycle, the ingest of an add, and per step the pieces of whole views
 // (view_set_rules.h): each piece runs the per-piece body its context-free counterpart runs -- every sequence of launches lives
 // beside that entry point; the single launches of 8g's upload and finish passes are made here, on the set's own planes -- from D
-// into the alternate plane, and the report kernels of view_set_kernels.hip behind it.  The planes change
-// places when every piece has succeeded.  A failure's text is dmi_views_last_error(s)'s.
+// into the alternate plane, and the report kernels of view_set_kernels.hip behind it (run_pieces).  The planes change
+// places when every piece has succeeded.  The checks the entries share with the context-free calls, the camera upload, the flip of
+// a piece and the spans between events are dmi_depth_call.h's.  A failure's text is dmi_views_last_error(s)'s.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "dmi_context.h"
+#include "dmi_depth_call.h"
 #include "dmi_view_set.h"
 #include "view_set_kernels.h"
 
@@ -36,7 +38,7 @@ namespace rules = dmi::view_set_rules;
 int fail(dmi_view_set *s, int code, const std::string &msg) { return dmi::views_fail(s, code, msg); }
 dmi_view_set *const kNoSet = nullptr;  // a failure without a set: the thread's last create failure
 
-bool finite_and_not_negative(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }  // false for NaN
+using dmi::finite_and_not_negative;
 
 #define VS_HIP(s, call)                                                                             \
   do {                                                                                              \
@@ -54,6 +56,14 @@ int guarded(dmi_view_set *s, const char *entry, Body &&body) noexcept {
 }
 
 hipError_t grow(dmi_view_set *s, dmi::DeviceBuffer &buffer, uint64_t bytes) { return dmi::grow_buffer(buffer, bytes, s->device_bytes); }
+
+// what every entry opens with (`entry` ends in ": "): DMI_OK, or the refusal of a call without a set, of a set without views
+int require_set(dmi_view_set *s, const std::string &entry) {
+  return s ? DMI_OK : fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+}
+int require_views(dmi_view_set *s, const std::string &entry) {
+  return s->n >= 1 ? DMI_OK : fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "the set holds no views");
+}
 
 // what a consistency or bounds pass holds beside the set's planes: freed whatever way the pass ends
 struct WholeSetScratch {
@@ -100,14 +110,8 @@ int begin_step(dmi_view_set *s) {
 // the piece's work is queued: wait for it and add the spans between `n_events` pass events and between the report's two
 int end_piece(dmi_view_set *s, int n_events, double *pass_ms, double *report_ms) {
   VS_HIP(s, hipStreamSynchronize(s->stream));  // the scratch and the events are reused by the next piece
-  for (int p = 0; p + 1 < n_events; ++p) {
-    float ms = 0.f;
-    VS_HIP(s, hipEventElapsedTime(&ms, s->events[p], s->events[p + 1]));
-    *pass_ms += (double)ms;
-  }
-  float ms = 0.f;
-  VS_HIP(s, hipEventElapsedTime(&ms, s->report_events[0], s->report_events[1]));
-  *report_ms += (double)ms;
+  VS_HIP(s, dmi::add_spans(s->events, n_events - 1, pass_ms, 0));
+  VS_HIP(s, dmi::add_spans(s->report_events, 1, report_ms));
   return DMI_OK;
 }
 
@@ -139,8 +143,7 @@ int create(int32_t device, int32_t W, int32_t H, dmi_view_set **out) {
   auto bad = [&](const std::string &what) { return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!out) return bad("out is null");
   *out = nullptr;
-  if (W < 1 || W > rules::kMaxSide) return bad("W must lie in [1, 32768]");
-  if (H < 1 || H > rules::kMaxSide) return bad("H must lie in [1, 32768]");
+  if (const char *what = dmi::side_refusal(W, H)) return bad(what);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     (void)hipGetLastError();
@@ -175,7 +178,7 @@ int create(int32_t device, int32_t W, int32_t H, dmi_view_set **out) {
 
 int add(dmi_view_set *s, const double *depth, const double *best_cost, double threshold, const double *K4, const double *RT4, int32_t n) {
   const std::string entry = "dmi_views_add: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!depth) return bad("depth is null");
   if (!K4) return bad("K4 is null");
@@ -229,21 +232,52 @@ int add(dmi_view_set *s, const double *depth, const double *best_cost, double th
   return DMI_OK;
 }
 
+// One piece of a step: `count` views from view `first`, `offset` pixels into a plane and `elems` pixels long; D's and the alternate
+// plane's
+struct PieceSpan {
+  int64_t first, count;
+  size_t offset, elems;
+  const double *src;
+  double *dst;
+};
+
+// The pieces of a step, one after the other: `passes` queues a piece's work from D into the alternate plane around s->events[0 ..
+// n_events), `report` the report kernels behind it; the piece of the int32 plane s->aux comes down where out_plane asks for it, and
+// the piece is waited for.  Every piece has succeeded: the step ends (end_step).  pass_ms: what the step has timed before its pieces.
+template <typename Passes, typename Report>
+int run_pieces(dmi_view_set *s, const Pieces &p, rules::Step step, int n_events, int32_t *out_plane, double pass_ms,
+               dmi_views_step_report *r, Passes &&passes, Report &&report) {
+  double report_ms = 0.0;
+  for (int64_t q = 0; q < p.count; ++q) {
+    const rules::Piece at = rules::piece_at(s->n, p.per, q);
+    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
+    const PieceSpan piece{at.first, at.count, offset, elems, plane_of(s, s->current) + offset, plane_of(s, s->current ^ 1) + offset};
+    int rc = passes(piece);
+    if (rc != DMI_OK) return rc;
+    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
+    if ((rc = report(piece)) != DMI_OK) return rc;
+    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
+    if (out_plane) VS_HIP(s, hipMemcpyAsync(out_plane + offset, s->aux.ptr, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    if ((rc = end_piece(s, n_events, &pass_ms, &report_ms)) != DMI_OK) return rc;
+  }
+  if (out_plane) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
+  return end_step(s, step, pass_ms, report_ms, r);
+}
+
 int filter_speckles(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t min_pixels, int32_t *out_size,
                     dmi_views_step_report *r) {
   const std::string entry = "dmi_views_filter_speckles: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if (min_pixels < 0) return bad("min_pixels >= 0 required");
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
 
   const int W = s->W, H = s->H;
   const dmi::SpeckleTuning tuning = dmi::speckle_tuning_from_environment();
   const Pieces p = pieces_of(s, s->n);
   const size_t tiles = (size_t)dmi::speckle_tiles(W, H, p.per, tuning);
-  int rc = begin_step(s);
+  const int rc = begin_step(s);
   if (rc != DMI_OK) return rc;
   VS_HIP(s, grow(s, s->label, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
   VS_HIP(s, grow(s, s->record, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
@@ -251,48 +285,36 @@ int filter_speckles(dmi_view_set *s, double abs_tolerance, double rel_tolerance,
   VS_HIP(s, grow(s, s->border_right, tiles * sizeof(uint64_t)));
   if (out_size) VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));
 
-  double pass_ms = 0.0, report_ms = 0.0;
-  for (int64_t q = 0; q < p.count; ++q) {
-    const rules::Piece at = rules::piece_at(s->n, p.per, q);
-    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
-    const double *const src = plane_of(s, s->current) + offset;
-    dmi::SpecklePiece piece;
-    piece.depth = plane_of(s, s->current ^ 1) + offset;  // the passes work in place: on a copy of D's piece
-    piece.cost = nullptr;
-    piece.label = s->label.as<uint32_t>();
-    piece.size = s->record.as<uint32_t>();
-    piece.border_down = s->border_down.as<uint64_t>();
-    piece.border_right = s->border_right.as<uint64_t>();
-    piece.out_size = out_size ? s->aux.as<int32_t>() : nullptr;
-    piece.count = at.count;
-    VS_HIP(s, hipMemcpyAsync(piece.depth, src, elems * 8, hipMemcpyDeviceToDevice, s->stream));
-    VS_HIP(s, dmi::run_speckle_piece(piece, 0.0, W, H, abs_tolerance, rel_tolerance, min_pixels, tuning, s->stream, s->events));
-    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
-    VS_HIP(s, dmi::launch_view_set_segment_roots(piece, W, H, min_pixels, counters_of(s), s->compute_units, s->stream));
-    VS_HIP(s, dmi::launch_view_set_report(src, piece.depth, nullptr, elems, counters_of(s), s->compute_units, s->stream));
-    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
-    if (out_size)
-      VS_HIP(s, hipMemcpyAsync(out_size + offset, piece.out_size, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    if ((rc = end_piece(s, 5, &pass_ms, &report_ms)) != DMI_OK) return rc;
-  }
-  if (out_size) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
-  return end_step(s, rules::kSpeckles, pass_ms, report_ms, r);
+  dmi::SpecklePiece piece{};
+  return run_pieces(
+      s, p, rules::kSpeckles, 5, out_size, 0.0, r,
+      [&](const PieceSpan &at) -> int {  // the passes work in place: on a copy of D's piece
+        piece = dmi::speckle_piece(at.dst, nullptr, s->label, s->record, s->border_down, s->border_right,
+                                   out_size ? s->aux.as<int32_t>() : nullptr, at.count);
+        VS_HIP(s, hipMemcpyAsync(piece.depth, at.src, at.elems * 8, hipMemcpyDeviceToDevice, s->stream));
+        VS_HIP(s, dmi::run_speckle_piece(piece, 0.0, W, H, abs_tolerance, rel_tolerance, min_pixels, tuning, s->stream, s->events));
+        return DMI_OK;
+      },
+      [&](const PieceSpan &at) -> int {
+        VS_HIP(s, dmi::launch_view_set_segment_roots(piece, W, H, min_pixels, counters_of(s), s->compute_units, s->stream));
+        VS_HIP(s, dmi::launch_view_set_report(at.src, piece.depth, nullptr, at.elems, counters_of(s), s->compute_units, s->stream));
+        return DMI_OK;
+      });
 }
 
 int fill_holes(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int64_t max_pixels, int32_t *out_size,
                dmi_views_step_report *r) {
   const std::string entry = "dmi_views_fill_holes: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if (max_pixels < 0) return bad("max_pixels >= 0 required");
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
 
   const int W = s->W, H = s->H;
   const Pieces p = pieces_of(s, s->n);
   const size_t tiles = (size_t)dmi::holes_tiles(W, H, p.per);
-  int rc = begin_step(s);
+  const int rc = begin_step(s);
   if (rc != DMI_OK) return rc;
   VS_HIP(s, grow(s, s->label, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
   VS_HIP(s, grow(s, s->record, (uint64_t)p.per * p.plane * sizeof(uint32_t)));
@@ -302,97 +324,73 @@ int fill_holes(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int6
   VS_HIP(s, grow(s, s->border_right, tiles * sizeof(uint64_t)));
   if (out_size) VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));
 
-  double pass_ms = 0.0, report_ms = 0.0;
-  for (int64_t q = 0; q < p.count; ++q) {
-    const rules::Piece at = rules::piece_at(s->n, p.per, q);
-    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
-    const double *const src = plane_of(s, s->current) + offset;
-    dmi::HolesPiece piece;
-    piece.depth = plane_of(s, s->current ^ 1) + offset;  // the output pass writes hole pixels only: into a copy of D's piece
-    piece.cost = nullptr;
-    piece.label = s->label.as<uint32_t>();
-    piece.record = s->record.as<uint32_t>();
-    piece.rim_lo = s->rim_lo.as<uint64_t>();
-    piece.rim_hi = s->rim_hi.as<uint64_t>();
-    piece.border_down = s->border_down.as<uint64_t>();
-    piece.border_right = s->border_right.as<uint64_t>();
-    piece.out_size = out_size ? s->aux.as<int32_t>() : nullptr;
-    piece.count = at.count;
-    VS_HIP(s, hipMemcpyAsync(piece.depth, src, elems * 8, hipMemcpyDeviceToDevice, s->stream));
-    VS_HIP(s, dmi::run_holes_piece(piece, 0.0, W, H, abs_tolerance, rel_tolerance, max_pixels, s->stream, s->events));
-    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
-    VS_HIP(s, dmi::launch_view_set_hole_roots(piece, W, H, abs_tolerance, rel_tolerance, max_pixels, counters_of(s), s->compute_units,
-                                               s->stream));
-    VS_HIP(s, dmi::launch_view_set_report(src, piece.depth, nullptr, elems, counters_of(s), s->compute_units, s->stream));
-    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
-    if (out_size)
-      VS_HIP(s, hipMemcpyAsync(out_size + offset, piece.out_size, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    if ((rc = end_piece(s, 5, &pass_ms, &report_ms)) != DMI_OK) return rc;
-  }
-  if (out_size) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
-  return end_step(s, rules::kHoles, pass_ms, report_ms, r);
+  dmi::HolesPiece piece{};
+  return run_pieces(
+      s, p, rules::kHoles, 5, out_size, 0.0, r,
+      [&](const PieceSpan &at) -> int {  // the output pass writes hole pixels only: into a copy of D's piece
+        piece = dmi::holes_piece(at.dst, nullptr, s->label, s->record, s->rim_lo, s->rim_hi, s->border_down, s->border_right,
+                                 out_size ? s->aux.as<int32_t>() : nullptr, at.count);
+        VS_HIP(s, hipMemcpyAsync(piece.depth, at.src, at.elems * 8, hipMemcpyDeviceToDevice, s->stream));
+        VS_HIP(s, dmi::run_holes_piece(piece, 0.0, W, H, abs_tolerance, rel_tolerance, max_pixels, s->stream, s->events));
+        return DMI_OK;
+      },
+      [&](const PieceSpan &at) -> int {
+        VS_HIP(s, dmi::launch_view_set_hole_roots(piece, W, H, abs_tolerance, rel_tolerance, max_pixels, counters_of(s), s->compute_units,
+                                                   s->stream));
+        VS_HIP(s, dmi::launch_view_set_report(at.src, piece.depth, nullptr, at.elems, counters_of(s), s->compute_units, s->stream));
+        return DMI_OK;
+      });
 }
 
 int smooth(dmi_view_set *s, double sigma, double truncate, double abs_tolerance, double rel_tolerance, int32_t iterations,
            int32_t *out_count, dmi_views_step_report *r) {
   const std::string entry = "dmi_views_smooth: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if (!finite_and_not_negative(sigma)) return bad("sigma must be finite and >= 0");
   if (!(truncate > 0.0 && truncate <= 4.0)) return bad("truncate must lie in (0, 4]");
   int32_t radius = 0;
   double weights[dmi::kDepthSmoothMaxRadius + 1];
   if (dmi::depth_smoothing_weights(sigma, truncate, &radius, weights) != 0)
     return bad("the radius ceil(truncate * sigma) must not exceed " + std::to_string(dmi::kDepthSmoothMaxRadius));
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
   if (iterations < 1 || iterations > dmi::kDepthSmoothMaxIterations)
     return bad("iterations must lie in [1, " + std::to_string(dmi::kDepthSmoothMaxIterations) + "]");
 
   const int W = s->W, H = s->H;
   const Pieces p = pieces_of(s, s->n);
   const dmi::SmoothArgs args = dmi::smooth_args(weights, radius, abs_tolerance, rel_tolerance);
-  int rc = begin_step(s);
+  const int rc = begin_step(s);
   if (rc != DMI_OK) return rc;
   if (iterations > 1) VS_HIP(s, grow(s, s->second, (uint64_t)p.per * p.plane * 8));
   VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));  // the report sums the taps whether asked for or not
 
-  double pass_ms = 0.0, report_ms = 0.0;
-  for (int64_t q = 0; q < p.count; ++q) {
-    const rules::Piece at = rules::piece_at(s->n, p.per, q);
-    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
-    const double *const src = plane_of(s, s->current) + offset;
-    double *const dst = plane_of(s, s->current ^ 1) + offset, *const other = s->second.as<double>();
-    // the last iteration writes dst: the iterations start on whichever of the two makes it so.  D is read, never written.
-    const bool odd = iterations % 2 == 1;
-    int32_t *const count = s->aux.as<int32_t>();
-    const double *result = nullptr;
-    VS_HIP(s, dmi::run_smooth_piece(src, nullptr, 0.0, odd ? dst : other, odd ? other : dst, count, at.count, W, H, args, iterations,
-                                     s->stream, s->events, &result));
-    if (result != dst) return fail(s, DMI_ERR_STATE, entry + "the iterations did not end in the alternate plane");
-    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
-    VS_HIP(s, dmi::launch_view_set_report(src, dst, count, elems, counters_of(s), s->compute_units, s->stream));
-    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
-    if (out_count) VS_HIP(s, hipMemcpyAsync(out_count + offset, count, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    if ((rc = end_piece(s, 2, &pass_ms, &report_ms)) != DMI_OK) return rc;
-  }
-  if (out_count) s->d2h_plane_bytes += (uint64_t)s->n * p.plane * sizeof(int32_t);
-  return end_step(s, rules::kSmooth, pass_ms, report_ms, r);
+  int32_t *const count = s->aux.as<int32_t>();
+  return run_pieces(
+      s, p, rules::kSmooth, 2, out_count, 0.0, r,
+      [&](const PieceSpan &at) -> int {
+        // the last iteration writes dst: the iterations start on whichever of the two makes it so.  D is read, never written.
+        double *const other = s->second.as<double>();
+        const bool odd = iterations % 2 == 1;
+        const double *result = nullptr;
+        VS_HIP(s, dmi::run_smooth_piece(at.src, nullptr, 0.0, odd ? at.dst : other, odd ? other : at.dst, count, at.count, W, H, args,
+                                         iterations, s->stream, s->events, &result));
+        if (result != at.dst) return fail(s, DMI_ERR_STATE, entry + "the iterations did not end in the alternate plane");
+        return DMI_OK;
+      },
+      [&](const PieceSpan &at) -> int {
+        VS_HIP(s, dmi::launch_view_set_report(at.src, at.dst, count, at.elems, counters_of(s), s->compute_units, s->stream));
+        return DMI_OK;
+      });
 }
 
 // D of every piece into s->flipped, thresholded already, rows flipped to image order (8g's upload pass, device to device)
 int flip_planes(dmi_view_set *s, const Pieces &p, double *pass_ms) {
   for (int64_t q = 0; q < p.count; ++q) {
     const rules::Piece at = rules::piece_at(s->n, p.per, q);
-    VS_HIP(s, hipEventRecord(s->events[0], s->stream));
-    VS_HIP(s, dmi::launch_consistency_upload(plane_of(s, s->current) + (size_t)at.first * p.plane, nullptr, 0.0, s->W, s->H, at.count,
-                                              s->flipped.as<double>(), at.first, s->stream));
-    VS_HIP(s, hipEventRecord(s->events[1], s->stream));
-    VS_HIP(s, hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
-    *pass_ms += (double)ms;
+    VS_HIP(s, dmi::flip_piece(plane_of(s, s->current) + (size_t)at.first * p.plane, nullptr, 0.0, s->W, s->H, at.first, at.count,
+                              s->flipped.as<double>(), s->stream, s->events, pass_ms));
   }
   return DMI_OK;
 }
@@ -400,73 +398,83 @@ int flip_planes(dmi_view_set *s, const Pieces &p, double *pass_ms) {
 int upload_cameras(dmi_view_set *s) {
   const size_t views = (size_t)s->n;
   VS_HIP(s, grow(s, s->cameras, views * sizeof(dmi::ConsistencyCamera)));
-  const std::vector<dmi::ConsistencyCamera> cameras = dmi::consistency_cameras(s->K4.data(), s->RT4.data(), views);
-  VS_HIP(s, hipMemcpyAsync(s->cameras.ptr, cameras.data(), views * sizeof(dmi::ConsistencyCamera), hipMemcpyHostToDevice, s->stream));
-  VS_HIP(s, hipStreamSynchronize(s->stream));  // `cameras` goes out of scope
+  VS_HIP(s, dmi::upload_cameras(s->cameras, s->K4.data(), s->RT4.data(), views, s->stream));
+  return DMI_OK;
+}
+
+// What the consistency filter and the point cloud open with, behind begin_step and with a WholeSetScratch standing: the flipped
+// planes and the counts grown, then `more` in its order, the cameras up, the counts and what of `more` asks for it zeroed, D flipped
+// (its time added to *flip_ms) and, with more than one view, counted (added to *count_ms).
+struct Scratch {
+  dmi::DeviceBuffer *buffer;
+  uint64_t bytes;
+  bool zeroed;
+};
+int flip_and_count(dmi_view_set *s, const Pieces &p, double abs_tolerance, double rel_tolerance, const std::vector<Scratch> &more,
+                   double *flip_ms, double *count_ms) {
+  const int n = s->n;
+  const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
+  VS_HIP(s, grow(s, s->flipped, (uint64_t)n * p.plane * 8));
+  VS_HIP(s, grow(s, s->counts, (uint64_t)n * p.plane * sizeof(int32_t)));
+  for (const Scratch &m : more) VS_HIP(s, grow(s, *m.buffer, m.bytes));
+  int rc = upload_cameras(s);
+  if (rc != DMI_OK) return rc;
+  VS_HIP(s, hipMemsetAsync(s->counts.ptr, 0, (size_t)n * p.plane * sizeof(int32_t), s->stream));
+  for (const Scratch &m : more)
+    if (m.zeroed) VS_HIP(s, hipMemsetAsync(m.buffer->ptr, 0, (size_t)m.bytes, s->stream));
+  if ((rc = flip_planes(s, p, flip_ms)) != DMI_OK) return rc;
+  if (n > 1) {
+    VS_HIP(s, dmi::run_consistency_count(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, s->W, s->H, abs_tolerance,
+                                          rel_tolerance, tuning, s->counts.as<int32_t>(), nullptr, s->stream, s->events));
+    VS_HIP(s, hipStreamSynchronize(s->stream));
+    VS_HIP(s, dmi::add_spans(s->events, 1, count_ms));
+  }
   return DMI_OK;
 }
 
 int filter_consistency(dmi_view_set *s, double abs_tolerance, double rel_tolerance, int32_t min_views, int32_t *out_count,
                        dmi_views_step_report *r) {
   const std::string entry = "dmi_views_filter_consistency: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if (min_views < 0) return bad("min_views >= 0 required");
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
   if (const int32_t m = dmi::first_view_with_other_k(s->K4.data(), s->n); m >= 0) return bad(dmi::other_k_message(m));
 
-  const int W = s->W, H = s->H, n = s->n;
-  const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
-  const Pieces p = pieces_of(s, n);
+  const int W = s->W, H = s->H;
+  const Pieces p = pieces_of(s, s->n);
   int rc = begin_step(s);
   if (rc != DMI_OK) return rc;
   WholeSetScratch scratch{s};
-  VS_HIP(s, grow(s, s->flipped, (uint64_t)n * p.plane * 8));
-  VS_HIP(s, grow(s, s->counts, (uint64_t)n * p.plane * sizeof(int32_t)));
-  if (out_count) VS_HIP(s, grow(s, s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t)));
-  if ((rc = upload_cameras(s)) != DMI_OK) return rc;
-  VS_HIP(s, hipMemsetAsync(s->counts.ptr, 0, (size_t)n * p.plane * sizeof(int32_t), s->stream));
-
-  double pass_ms = 0.0, report_ms = 0.0;
-  if ((rc = flip_planes(s, p, &pass_ms)) != DMI_OK) return rc;
-  if (n > 1) {
-    VS_HIP(s, dmi::run_consistency_count(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
-                                          rel_tolerance, tuning, s->counts.as<int32_t>(), nullptr, s->stream, s->events));
-    VS_HIP(s, hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
-    pass_ms += (double)ms;
-  }
-  for (int64_t q = 0; q < p.count; ++q) {
-    const rules::Piece at = rules::piece_at(n, p.per, q);
-    const size_t offset = (size_t)at.first * p.plane, elems = (size_t)at.count * p.plane;
-    const double *const src = plane_of(s, s->current) + offset;
-    double *const dst = plane_of(s, s->current ^ 1) + offset;
-    VS_HIP(s, hipEventRecord(s->events[0], s->stream));
-    VS_HIP(s, dmi::launch_consistency_finish(s->flipped.as<double>(), s->counts.as<int32_t>(), W, H, at.first, at.count, min_views, dst,
-                                              out_count ? s->aux.as<int32_t>() : nullptr, s->stream));
-    VS_HIP(s, hipEventRecord(s->events[1], s->stream));
-    VS_HIP(s, hipEventRecord(s->report_events[0], s->stream));
-    VS_HIP(s, dmi::launch_view_set_report(src, dst, nullptr, elems, counters_of(s), s->compute_units, s->stream));
-    VS_HIP(s, hipEventRecord(s->report_events[1], s->stream));
-    if (out_count) VS_HIP(s, hipMemcpyAsync(out_count + offset, s->aux.ptr, elems * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    if ((rc = end_piece(s, 2, &pass_ms, &report_ms)) != DMI_OK) return rc;
-  }
-  if (out_count) s->d2h_plane_bytes += (uint64_t)n * p.plane * sizeof(int32_t);
-  return end_step(s, rules::kConsistency, pass_ms, report_ms, r);
+  std::vector<Scratch> more;
+  if (out_count) more.push_back({&s->aux, (uint64_t)p.per * p.plane * sizeof(int32_t), false});
+  double pass_ms = 0.0;
+  if ((rc = flip_and_count(s, p, abs_tolerance, rel_tolerance, more, &pass_ms, &pass_ms)) != DMI_OK) return rc;
+  return run_pieces(
+      s, p, rules::kConsistency, 2, out_count, pass_ms, r,
+      [&](const PieceSpan &at) -> int {
+        VS_HIP(s, hipEventRecord(s->events[0], s->stream));
+        VS_HIP(s, dmi::launch_consistency_finish(s->flipped.as<double>(), s->counts.as<int32_t>(), W, H, at.first, at.count, min_views, at.dst,
+                                                  out_count ? s->aux.as<int32_t>() : nullptr, s->stream));
+        VS_HIP(s, hipEventRecord(s->events[1], s->stream));
+        return DMI_OK;
+      },
+      [&](const PieceSpan &at) -> int {
+        VS_HIP(s, dmi::launch_view_set_report(at.src, at.dst, nullptr, at.elems, counters_of(s), s->compute_units, s->stream));
+        return DMI_OK;
+      });
 }
 
 int estimate_bounds(dmi_view_set *s, const double *axes9, double trim_fraction, int32_t pixel_step, double lo[3], double hi[3],
                     uint64_t *n_points, double *kernel_ms) {
   const std::string entry = "dmi_views_estimate_bounds: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!lo) return bad("lo is null");
   if (!hi) return bad("hi is null");
   if (!n_points) return bad("n_points is null");
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if ((uint64_t)s->n * (uint64_t)s->W * (uint64_t)s->H >= (uint64_t(1) << 53)) return bad("n * W * H must stay below 2^53");
   if (!(trim_fraction >= 0.0 && trim_fraction <= 0.5)) return bad("trim_fraction must lie in [0, 0.5]");  // false for NaN
   if (pixel_step < 1) return bad("pixel_step >= 1 required");
@@ -493,9 +501,7 @@ int estimate_bounds(dmi_view_set *s, const double *axes9, double trim_fraction, 
   VS_HIP(s, dmi::run_bounds_select(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, s->W, s->H, pixel_step, axes,
                                     trim_fraction, s->state.as<dmi::BoundsState>(), s->hist.as<unsigned long long>(), s->compute_units,
                                     tuning, s->stream, s->events, &result));
-  float ms = 0.f;
-  VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
-  pass_ms += (double)ms;
+  VS_HIP(s, dmi::add_spans(s->events, 1, &pass_ms));
   for (int a = 0; a < 3; ++a) {
     lo[a] = result.result[2 * a];
     hi[a] = result.result[2 * a + 1];
@@ -508,10 +514,10 @@ int estimate_bounds(dmi_view_set *s, const double *axes9, double trim_fraction, 
 
 int download(dmi_view_set *s, int32_t first, int32_t count, double *out_depth) {
   const std::string entry = "dmi_views_download: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!out_depth) return bad("out_depth is null");
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if (first < 0 || count < 1 || (int64_t)first + count > s->n) return bad("first and count must name views of the set");
   const size_t plane = (size_t)s->W * (size_t)s->H;
   VS_HIP(s, hipSetDevice(s->device));
@@ -526,22 +532,20 @@ int build_points(dmi_view_set *s, double abs_tolerance, double rel_tolerance, do
                  int32_t min_views, int32_t pixel_step, int32_t dedupe, uint64_t *n_points, dmi_views_points_report *r) {
   namespace pr = dmi::points_rules;
   const std::string entry = "dmi_views_build_points: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + what); };
   if (!n_points) return bad("n_points is null");
-  if (!finite_and_not_negative(abs_tolerance)) return bad("abs_tolerance must be finite and >= 0");
-  if (!finite_and_not_negative(rel_tolerance)) return bad("rel_tolerance must be finite and >= 0");
+  if (const char *what = dmi::tolerance_refusal(abs_tolerance, rel_tolerance)) return bad(what);
   if (!finite_and_not_negative(normal_abs_tolerance)) return bad("normal_abs_tolerance must be finite and >= 0");
   if (!finite_and_not_negative(normal_rel_tolerance)) return bad("normal_rel_tolerance must be finite and >= 0");
   if (min_views < 0) return bad("min_views >= 0 required");
   if (pixel_step < 1) return bad("pixel_step >= 1 required");
   if (dedupe != 0 && dedupe != 1) return bad("dedupe must be 0 or 1");
-  if (s->n < 1) return bad("the set holds no views");
+  if (const int rc = require_views(s, entry)) return rc;
   if (!pr::blocks_fit_one_launch(s->n, s->W, s->H)) return bad("n * ceil(W * H / 256) must stay below 2^31");
   if (const int32_t m = dmi::first_view_with_other_k(s->K4.data(), s->n); m >= 0) return bad(dmi::other_k_message(m));
 
   const int W = s->W, H = s->H, n = s->n;
-  const dmi::ConsistencyTuning tuning = dmi::consistency_tuning_from_environment();
   const Pieces p = pieces_of(s, n);
   const int64_t blocks = pr::total_blocks(n, W, H);
   const dmi::PointsParams params{W, H, min_views, pixel_step, dedupe, abs_tolerance, rel_tolerance, normal_abs_tolerance,
@@ -549,25 +553,13 @@ int build_points(dmi_view_set *s, double abs_tolerance, double rel_tolerance, do
   int rc = begin_step(s);
   if (rc != DMI_OK) return rc;
   WholeSetScratch scratch{s};
-  VS_HIP(s, grow(s, s->flipped, (uint64_t)n * p.plane * 8));
-  VS_HIP(s, grow(s, s->counts, (uint64_t)n * p.plane * sizeof(int32_t)));
-  VS_HIP(s, grow(s, s->flags, (uint64_t)n * p.plane));
-  VS_HIP(s, grow(s, s->block_counts, (uint64_t)blocks * sizeof(uint32_t)));
-  VS_HIP(s, grow(s, s->block_offsets, ((uint64_t)blocks + 1) * sizeof(uint64_t)));  // the total stands behind the offsets
-  if ((rc = upload_cameras(s)) != DMI_OK) return rc;
-  VS_HIP(s, hipMemsetAsync(s->counts.ptr, 0, (size_t)n * p.plane * sizeof(int32_t), s->stream));
-  VS_HIP(s, hipMemsetAsync(s->flags.ptr, 0, (size_t)n * p.plane, s->stream));
-
   double pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  if ((rc = flip_planes(s, p, &pass_ms[0])) != DMI_OK) return rc;
-  if (n > 1) {
-    VS_HIP(s, dmi::run_consistency_count(s->flipped.as<double>(), s->cameras.as<dmi::ConsistencyCamera>(), n, W, H, abs_tolerance,
-                                          rel_tolerance, tuning, s->counts.as<int32_t>(), nullptr, s->stream, s->events));
-    VS_HIP(s, hipStreamSynchronize(s->stream));
-    float ms = 0.f;
-    VS_HIP(s, hipEventElapsedTime(&ms, s->events[0], s->events[1]));
-    pass_ms[1] = (double)ms;
-  }
+  rc = flip_and_count(s, p, abs_tolerance, rel_tolerance,
+                      {{&s->flags, (uint64_t)n * p.plane, true},
+                       {&s->block_counts, (uint64_t)blocks * sizeof(uint32_t), false},
+                       {&s->block_offsets, ((uint64_t)blocks + 1) * sizeof(uint64_t), false}},  // the total stands behind the offsets
+                      &pass_ms[0], &pass_ms[1]);
+  if (rc != DMI_OK) return rc;
   uint64_t *const offsets = s->block_offsets.as<uint64_t>();
   VS_HIP(s, hipEventRecord(s->events[0], s->stream));
   VS_HIP(s, dmi::launch_points_flags(s->flipped.as<double>(), s->counts.as<int32_t>(), s->cameras.as<dmi::ConsistencyCamera>(), n, params,
@@ -601,14 +593,8 @@ int build_points(dmi_view_set *s, double abs_tolerance, double rel_tolerance, do
   unsigned long long c[dmi::kPtCounters];
   VS_HIP(s, hipMemcpyAsync(c, s->counters.ptr, sizeof(c), hipMemcpyDeviceToHost, s->stream));
   VS_HIP(s, hipStreamSynchronize(s->stream));
-  for (int e = 0; e < 2; ++e) {
-    float ms = 0.f;
-    VS_HIP(s, hipEventElapsedTime(&ms, s->events[e], s->events[e + 1]));
-    pass_ms[2 + e] = (double)ms;
-  }
-  float ms = 0.f;
-  VS_HIP(s, hipEventElapsedTime(&ms, s->events[3], s->events[4]));
-  pass_ms[4] = (double)ms;
+  VS_HIP(s, dmi::add_spans(s->events, 2, &pass_ms[2]));
+  VS_HIP(s, dmi::add_spans(s->events + 3, 1, &pass_ms[4]));
 
   drop_points(s);
   std::swap(s->points, fresh);
@@ -633,7 +619,7 @@ int download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz
                     int32_t *n_views) {
   namespace pr = dmi::points_rules;
   const std::string entry = "dmi_views_download_points: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + "the set holds no points: dmi_views_build_points comes first");
   if (first > s->n_points || count > s->n_points - first)
     return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "first + count must not exceed the number of points");
@@ -660,7 +646,7 @@ int download_points(dmi_view_set *s, uint64_t first, uint64_t count, double *xyz
 int thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t *n_points, dmi_points_thin_report *r) {
   namespace pr = dmi::points_rules;
   const std::string entry = "dmi_views_thin_points";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + ": the set is null");
+  if (const int rc = require_set(s, entry + ": ")) return rc;
   auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + ": " + what); };
   if (!n_points) return bad("n_points is null");
   if (!(cell_size > 0.0) || cell_size - cell_size != 0.0) return bad("cell_size is not a finite number > 0");
@@ -701,7 +687,7 @@ int thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t 
 
 int download_point_members(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out) {
   const std::string entry = "dmi_views_download_point_members: ";
-  if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, entry + "the set is null");
+  if (const int rc = require_set(s, entry)) return rc;
   if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + "the set holds no points: dmi_views_build_points comes first");
   if (first > s->n_points || count > s->n_points - first)
     return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "first + count must not exceed the number of points");
@@ -752,7 +738,7 @@ int dmi_views_add(dmi_view_set *s, const double *depth, const double *best_cost,
 
 int dmi_views_clear(dmi_view_set *s) {
   return guarded(s, "dmi_views_clear", [&]() -> int {
-    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_clear: the set is null");
+    if (const int rc = require_set(s, "dmi_views_clear: ")) return rc;
     drop_points(s);
     s->n = 0;
     s->K4.clear();
@@ -763,7 +749,7 @@ int dmi_views_clear(dmi_view_set *s) {
 
 int dmi_views_get_info(dmi_view_set *s, dmi_views_info *out) {
   return guarded(s, "dmi_views_get_info", [&]() -> int {
-    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_info: the set is null");
+    if (const int rc = require_set(s, "dmi_views_get_info: ")) return rc;
     if (!out) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_info: out is null");
     out->n = s->n;
     out->W = s->W;
@@ -782,7 +768,7 @@ size_t dmi_sizeof_views_info(void) { return sizeof(dmi_views_info); }
 
 int dmi_views_set_piece_bytes(dmi_view_set *s, uint64_t bytes) {
   return guarded(s, "dmi_views_set_piece_bytes", [&]() -> int {
-    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_piece_bytes: the set is null");
+    if (const int rc = require_set(s, "dmi_views_set_piece_bytes: ")) return rc;
     if (bytes == 0) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_piece_bytes: bytes >= 1 required");
     s->piece_bytes = bytes;
     return DMI_OK;
@@ -839,7 +825,7 @@ int dmi_views_download_points(dmi_view_set *s, uint64_t first, uint64_t count, d
 
 int dmi_views_get_points_pass_ms(dmi_view_set *s, double out_ms[5]) {
   return guarded(s, "dmi_views_get_points_pass_ms", [&]() -> int {
-    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_points_pass_ms: the set is null");
+    if (const int rc = require_set(s, "dmi_views_get_points_pass_ms: ")) return rc;
     if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_points_pass_ms: out_ms is null");
     if (!s->points_current) return fail(s, DMI_ERR_STATE, "dmi_views_get_points_pass_ms: the set holds no points");
     for (int e = 0; e < 5; ++e) out_ms[e] = s->points_pass_ms[e];
@@ -857,7 +843,7 @@ int dmi_views_download_point_members(dmi_view_set *s, uint64_t first, uint64_t c
 
 int dmi_views_get_thin_pass_ms(dmi_view_set *s, double out_ms[5]) {
   return guarded(s, "dmi_views_get_thin_pass_ms", [&]() -> int {
-    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_thin_pass_ms: the set is null");
+    if (const int rc = require_set(s, "dmi_views_get_thin_pass_ms: ")) return rc;
     if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_thin_pass_ms: out_ms is null");
     if (!s->points_current || !s->points_thinned)
       return fail(s, DMI_ERR_STATE, "dmi_views_get_thin_pass_ms: the set holds no thinned cloud");
@@ -868,7 +854,7 @@ int dmi_views_get_thin_pass_ms(dmi_view_set *s, double out_ms[5]) {
 
 int dmi_views_set_thin_wave_cell_points(dmi_view_set *s, int32_t k) {
   return guarded(s, "dmi_views_set_thin_wave_cell_points", [&]() -> int {
-    if (!s) return fail(kNoSet, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_thin_wave_cell_points: the set is null");
+    if (const int rc = require_set(s, "dmi_views_set_thin_wave_cell_points: ")) return rc;
     if (k < 1) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_thin_wave_cell_points: k >= 1 required");
     s->thin_wave_cell_points = (uint32_t)k;
     return DMI_OK;

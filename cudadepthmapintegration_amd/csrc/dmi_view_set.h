@@ -1,7 +1,8 @@
 // dmi_view_set.h -- the resident view set behind dmi_views_* of include/dmi.h (dmi_capi_viewset.hip): the depth planes
 // of n views that stay on one device from the first filter to the fusion, the scratch of one piece of a pass, and the per-piece
 // bodies that the context-free entry points (dmi_capi_speckle.hip, dmi_capi_holes.hip, dmi_capi_smooth.hip,
-// dmi_capi_consistency.hip, dmi_capi_bounds.hip) share with it: one implementation per filter.  Private: never installed.
+// dmi_capi_consistency.hip, dmi_capi_bounds.hip) share with it: one implementation per filter.  What those calls and the set's
+// entries share around the bodies -- checks, staging, cameras, spans -- is dmi_depth_call.h's.  Private: never installed.
 #pragma once
 #include "../../include/dmi.h"
 #include "depth_consistency.h"
@@ -10,7 +11,7 @@
 #include "depth_points_thin.h"
 #include "depth_smooth.h"
 #include "depth_speckle.h"
-#include "dmi_buffer.h"
+#include "dmi_depth_call.h"
 #include "scene_bounds.h"
 #include "view_set_rules.h"
 
@@ -85,10 +86,10 @@ hipError_t run_holes_piece(const HolesPiece &piece, double threshold, int32_t W,
 hipError_t run_smooth_piece(const double *src, const double *cost, double threshold, double *ping, double *pong, int32_t *count,
                             int64_t views, int32_t W, int32_t H, const SmoothArgs &args, int32_t iterations, hipStream_t stream,
                             hipEvent_t events[2], const double **result);
-// dmi_capi_consistency.hip: the K4 check both camera-reading calls make, their cameras, and the count launches on flipped planes
+// dmi_capi_consistency.hip: the K4 check both camera-reading calls make, their cameras (consistency_cameras, declared where it is
+// uploaded: dmi_depth_call.h), and the count launches on flipped planes
 int32_t first_view_with_other_k(const double *K4, int32_t n);  // -1: every K4 is of the form SetMatrixK produces
 std::string other_k_message(int32_t view);
-std::vector<ConsistencyCamera> consistency_cameras(const double *K4, const double *RT4, size_t views);
 ConsistencyTuning consistency_tuning_from_environment();
 hipError_t run_consistency_count(const double *planes, const ConsistencyCamera *cameras, int32_t n, int32_t W, int32_t H,
                                  double abs_tolerance, double rel_tolerance, const ConsistencyTuning &tuning, int32_t *counts,

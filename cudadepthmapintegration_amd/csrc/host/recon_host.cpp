@@ -674,48 +674,96 @@ bool FusionDriver::ProcessDepthMap(const std::vector<std::string> &vtiList, cons
   return ProcessDepthMap(n, fill, thresholdBestCost, io_scalar);
 }
 
-// Not in the reference (recon_host.h)
-bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int minViews,
-                            double absTolerance, double relTolerance, int device, DepthConsistencyReport *report, std::string *error) {
+// ---- what the depth-map filters below and DepthViewSet::Load share: the views checked and gathered, the planes put back ----
+namespace {
+
+// The views' common size: view 0 has a depth map and there are not too many of them.  false: *error says why, in `caller`'s name.
+bool CommonViewSize(const char *caller, const std::vector<ReconstructionData *> &views, int *W, int *H, std::string *error) {
   const size_t n = views.size();
   DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
   if (!first) {
-    *error = "FilterDepthConsistency: no views, or view 0 has no depth map";
+    *error = std::string(caller) + ": no views, or view 0 has no depth map";
     return false;
   }
-  const int W = first->dims[0], H = first->dims[1];
-  const size_t npix = (size_t)W * H;
   if (n > 0x7fffffffu) {
-    *error = "FilterDepthConsistency: too many views";
+    *error = std::string(caller) + ": too many views";
     return false;
   }
-  std::vector<double> depth(n * npix), K4(n * 16), RT(n * 16);
-  DepthConsistencyReport r;
-  r.views = n;
+  *W = first->dims[0];
+  *H = first->dims[1];
+  return true;
+}
+
+// view m has a depth map of that size
+bool ViewHasSize(const char *caller, const std::vector<ReconstructionData *> &views, size_t m, int W, int H, std::string *error) {
+  DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
+  if (img && img->dims[0] == W && img->dims[1] == H && img->depths.size() == (size_t)W * H) return true;
+  *error = std::string(caller) + ": view " + std::to_string(m) + " has no depth map of the size of view 0";
+  return false;
+}
+
+struct GatheredViews {
+  int W = 0, H = 0;
+  size_t npix = 0;
+  std::vector<double> depth;   // [n][H][W], thresholded
+  std::vector<double> K4, RT;  // [n][16] each, where asked for
+};
+
+// View after view: checked, thresholded (ApplyDepthThresholdFilter) and copied; a view that fails leaves the ones before it
+// thresholded.
+bool GatherViews(const char *caller, const std::vector<ReconstructionData *> &views, double thresholdBestCost, bool withCameras,
+                 GatheredViews *g, std::string *error) {
+  if (!CommonViewSize(caller, views, &g->W, &g->H, error)) return false;
+  const size_t n = views.size(), npix = g->npix = (size_t)g->W * g->H;
+  g->depth.resize(n * npix);
+  if (withCameras) {
+    g->K4.resize(n * 16);
+    g->RT.resize(n * 16);
+  }
   for (size_t m = 0; m < n; ++m) {
-    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
-    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
-      *error = "FilterDepthConsistency: view " + std::to_string(m) + " has no depth map of the size of view 0";
-      return false;
-    }
+    if (!ViewHasSize(caller, views, m, g->W, g->H, error)) return false;
     views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
-    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
-    std::memcpy(K4.data() + m * 16, views[m]->Get4MatrixK(), 16 * 8);
-    std::memcpy(RT.data() + m * 16, views[m]->GetMatrixTR(), 16 * 8);
+    std::memcpy(g->depth.data() + m * npix, views[m]->GetDepthMap()->depths.data(), npix * 8);
+    if (withCameras) {
+      std::memcpy(g->K4.data() + m * 16, views[m]->Get4MatrixK(), 16 * 8);
+      std::memcpy(g->RT.data() + m * 16, views[m]->GetMatrixTR(), 16 * 8);
+    }
   }
-  for (const double d : depth) r.validPixels += d > 0.0 && d < HUGE_VAL ? 1 : 0;
-  const int rc = dmi_filter_depth_consistency(depth.data(), nullptr, 0.0, K4.data(), RT.data(), (int32_t)n, W, H, absTolerance, relTolerance,
-                                              minViews, device, depth.data(), nullptr, &r.kernelMs);
-  if (rc != DMI_OK) {
-    *error = dmi_last_error(nullptr);
-    return false;
+  return true;
+}
+
+// The planes back into the views; perView(m, before, &after) -- the view's map as it was and as it is about to be set -- where given.
+void ScatterViews(const std::vector<ReconstructionData *> &views, const GatheredViews &g,
+                  const std::function<void(size_t, const DepthImage &, DepthImage *)> &perView = nullptr) {
+  for (size_t m = 0; m < views.size(); ++m) {
+    const DepthImage &before = *views[m]->GetDepthMap();
+    DepthImage after = before;
+    after.depths.assign(g.depth.begin() + (ptrdiff_t)(m * g.npix), g.depth.begin() + (ptrdiff_t)((m + 1) * g.npix));
+    if (perView) perView(m, before, &after);
+    views[m]->SetDepthMap(after);
   }
-  for (const double d : depth) r.keptPixels += d > 0.0 ? 1 : 0;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage filtered = *views[m]->GetDepthMap();
-    filtered.depths.assign(depth.begin() + (ptrdiff_t)(m * npix), depth.begin() + (ptrdiff_t)((m + 1) * npix));
-    views[m]->SetDepthMap(filtered);
-  }
+}
+
+bool LastError(std::string *error) {
+  *error = dmi_last_error(nullptr);
+  return false;
+}
+
+}  // namespace
+
+// Not in the reference (recon_host.h)
+bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, double thresholdBestCost, int minViews,
+                            double absTolerance, double relTolerance, int device, DepthConsistencyReport *report, std::string *error) {
+  GatheredViews g;
+  if (!GatherViews("FilterDepthConsistency", views, thresholdBestCost, true, &g, error)) return false;
+  DepthConsistencyReport r;
+  r.views = views.size();
+  for (const double d : g.depth) r.validPixels += d > 0.0 && d < HUGE_VAL ? 1 : 0;
+  if (dmi_filter_depth_consistency(g.depth.data(), nullptr, 0.0, g.K4.data(), g.RT.data(), (int32_t)views.size(), g.W, g.H, absTolerance,
+                                   relTolerance, minViews, device, g.depth.data(), nullptr, &r.kernelMs) != DMI_OK)
+    return LastError(error);
+  for (const double d : g.depth) r.keptPixels += d > 0.0 ? 1 : 0;
+  ScatterViews(views, g);
   if (report) *report = r;
   return true;
 }
@@ -723,39 +771,17 @@ bool FilterDepthConsistency(const std::vector<ReconstructionData *> &views, doub
 // Not in the reference (recon_host.h)
 bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long minPixels,
                          double absTolerance, double relTolerance, int device, DepthSpeckleReport *report, std::string *error) {
-  const size_t n = views.size();
-  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
-  if (!first) {
-    *error = "FilterDepthSpeckles: no views, or view 0 has no depth map";
-    return false;
-  }
-  const int W = first->dims[0], H = first->dims[1];
-  const size_t npix = (size_t)W * H;
-  if (n > 0x7fffffffu) {
-    *error = "FilterDepthSpeckles: too many views";
-    return false;
-  }
-  std::vector<double> depth(n * npix);
+  GatheredViews g;
+  if (!GatherViews("FilterDepthSpeckles", views, thresholdBestCost, false, &g, error)) return false;
+  const size_t npix = g.npix;
   DepthSpeckleReport r;
-  r.views = n;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
-    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
-      *error = "FilterDepthSpeckles: view " + std::to_string(m) + " has no depth map of the size of view 0";
-      return false;
-    }
-    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
-    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
-  }
-  for (const double d : depth) r.validPixels += d > 0.0 && d < HUGE_VAL ? 1 : 0;
-  std::vector<int32_t> size(n * npix);
-  const int rc = dmi_filter_depth_speckles(depth.data(), nullptr, 0.0, (int32_t)n, W, H, absTolerance, relTolerance, minPixels, device,
-                                           depth.data(), size.data(), &r.kernelMs);
-  if (rc != DMI_OK) {
-    *error = dmi_last_error(nullptr);
-    return false;
-  }
-  for (const double d : depth) r.keptPixels += d > 0.0 ? 1 : 0;
+  r.views = views.size();
+  for (const double d : g.depth) r.validPixels += d > 0.0 && d < HUGE_VAL ? 1 : 0;
+  std::vector<int32_t> size(g.depth.size());
+  if (dmi_filter_depth_speckles(g.depth.data(), nullptr, 0.0, (int32_t)views.size(), g.W, g.H, absTolerance, relTolerance, minPixels, device,
+                                g.depth.data(), size.data(), &r.kernelMs) != DMI_OK)
+    return LastError(error);
+  for (const double d : g.depth) r.keptPixels += d > 0.0 ? 1 : 0;
   // a segment of s pixels shows s times in the sizes: the pixels of size s, over s, are the segments of that size
   std::vector<uint64_t> pixelsOfSize(npix + 1, 0);
   for (const int32_t s : size)
@@ -764,11 +790,7 @@ bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double 
     r.segments += pixelsOfSize[s] / s;
     if ((long long)s >= minPixels) r.keptSegments += pixelsOfSize[s] / s;
   }
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage filtered = *views[m]->GetDepthMap();
-    filtered.depths.assign(depth.begin() + (ptrdiff_t)(m * npix), depth.begin() + (ptrdiff_t)((m + 1) * npix));
-    views[m]->SetDepthMap(filtered);
-  }
+  ScatterViews(views, g);
   if (report) *report = r;
   return true;
 }
@@ -776,37 +798,16 @@ bool FilterDepthSpeckles(const std::vector<ReconstructionData *> &views, double 
 // Not in the reference (recon_host.h)
 bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thresholdBestCost, long long maxPixels, double absTolerance,
                     double relTolerance, int device, DepthHolesReport *report, std::string *error) {
-  const size_t n = views.size();
-  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
-  if (!first) {
-    *error = "FillDepthHoles: no views, or view 0 has no depth map";
-    return false;
-  }
-  const int W = first->dims[0], H = first->dims[1];
-  const size_t npix = (size_t)W * H;
-  if (n > 0x7fffffffu) {
-    *error = "FillDepthHoles: too many views";
-    return false;
-  }
-  std::vector<double> depth(n * npix);
+  GatheredViews g;
+  if (!GatherViews("FillDepthHoles", views, thresholdBestCost, false, &g, error)) return false;
+  const size_t npix = g.npix;
+  const std::vector<double> &depth = g.depth;
   DepthHolesReport r;
-  r.views = n;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
-    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
-      *error = "FillDepthHoles: view " + std::to_string(m) + " has no depth map of the size of view 0";
-      return false;
-    }
-    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
-    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
-  }
-  std::vector<int32_t> size(n * npix);
-  const int rc = dmi_fill_depth_holes(depth.data(), nullptr, 0.0, (int32_t)n, W, H, absTolerance, relTolerance, maxPixels, device,
-                                      depth.data(), size.data(), &r.kernelMs);
-  if (rc != DMI_OK) {
-    *error = dmi_last_error(nullptr);
-    return false;
-  }
+  r.views = views.size();
+  std::vector<int32_t> size(depth.size());
+  if (dmi_fill_depth_holes(g.depth.data(), nullptr, 0.0, (int32_t)views.size(), g.W, g.H, absTolerance, relTolerance, maxPixels, device,
+                           g.depth.data(), size.data(), &r.kernelMs) != DMI_OK)
+    return LastError(error);
   // a hole of s pixels shows s times in the sizes, and a filled hole is filled at every pixel: the pixels of size s, over s, are
   // the holes of that size
   std::vector<uint64_t> pixelsOfSize(npix + 1, 0), filledOfSize(npix + 1, 0);
@@ -823,16 +824,13 @@ bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thres
     r.holes += pixelsOfSize[s] / s;
     r.filledHoles += filledOfSize[s] / s;
   }
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage filled = *views[m]->GetDepthMap();
-    filled.depths.assign(depth.begin() + (ptrdiff_t)(m * npix), depth.begin() + (ptrdiff_t)((m + 1) * npix));
-    // a pixel the threshold had dropped and the fill gave a depth again must pass the threshold from now on: the consistency
-    // filter, the bounds estimate and the fusion all apply it once more
-    if (filled.best_cost.size() == npix)
+  // a pixel the threshold had dropped and the fill gave a depth again must pass the threshold from now on: the consistency
+  // filter, the bounds estimate and the fusion all apply it once more
+  ScatterViews(views, g, [&](size_t, const DepthImage &, DepthImage *filled) {
+    if (filled->best_cost.size() == npix)
       for (size_t i = 0; i < npix; ++i)
-        if (filled.depths[i] != -1.0 && filled.best_cost[i] > thresholdBestCost) filled.best_cost[i] = thresholdBestCost;
-    views[m]->SetDepthMap(filled);
-  }
+        if (filled->depths[i] != -1.0 && filled->best_cost[i] > thresholdBestCost) filled->best_cost[i] = thresholdBestCost;
+  });
   if (report) *report = r;
   return true;
 }
@@ -840,50 +838,24 @@ bool FillDepthHoles(const std::vector<ReconstructionData *> &views, double thres
 // Not in the reference (recon_host.h)
 bool SmoothDepths(const std::vector<ReconstructionData *> &views, double thresholdBestCost, double sigma, double truncate,
                   double absTolerance, double relTolerance, int iterations, int device, DepthSmoothReport *report, std::string *error) {
-  const size_t n = views.size();
-  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
-  if (!first) {
-    *error = "SmoothDepths: no views, or view 0 has no depth map";
-    return false;
-  }
-  const int W = first->dims[0], H = first->dims[1];
-  const size_t npix = (size_t)W * H;
-  if (n > 0x7fffffffu) {
-    *error = "SmoothDepths: too many views";
-    return false;
-  }
-  std::vector<double> depth(n * npix);
+  GatheredViews g;
+  if (!GatherViews("SmoothDepths", views, thresholdBestCost, false, &g, error)) return false;
+  const size_t npix = g.npix;
   DepthSmoothReport r;
-  r.views = n;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
-    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
-      *error = "SmoothDepths: view " + std::to_string(m) + " has no depth map of the size of view 0";
-      return false;
-    }
-    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
-    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
-  }
-  std::vector<int32_t> count(n * npix);
-  const int rc = dmi_smooth_depths(depth.data(), nullptr, 0.0, (int32_t)n, W, H, sigma, truncate, absTolerance, relTolerance,
-                                   (int32_t)iterations, device, depth.data(), count.data(), &r.kernelMs);
-  if (rc != DMI_OK) {
-    *error = dmi_last_error(nullptr);
-    return false;
-  }
+  r.views = views.size();
+  std::vector<int32_t> count(g.depth.size());
+  if (dmi_smooth_depths(g.depth.data(), nullptr, 0.0, (int32_t)views.size(), g.W, g.H, sigma, truncate, absTolerance, relTolerance,
+                        (int32_t)iterations, device, g.depth.data(), count.data(), &r.kernelMs) != DMI_OK)
+    return LastError(error);
   uint64_t taps = 0;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage smoothed = *views[m]->GetDepthMap();
-    const double *out = depth.data() + m * npix;
+  ScatterViews(views, g, [&](size_t m, const DepthImage &before, DepthImage *smoothed) {
     for (size_t i = 0; i < npix; ++i) {
-      if (out[i] == -1.0) continue;  // what is not valid comes out as -1, and nothing else does
+      if (smoothed->depths[i] == -1.0) continue;  // what is not valid comes out as -1, and nothing else does
       ++r.validPixels;
       taps += (uint64_t)count[m * npix + i];
-      if (out[i] != smoothed.depths[i]) ++r.changedPixels;
+      if (smoothed->depths[i] != before.depths[i]) ++r.changedPixels;
     }
-    smoothed.depths.assign(out, out + npix);
-    views[m]->SetDepthMap(smoothed);
-  }
+  });
   r.meanTaps = r.validPixels ? (double)taps / (double)r.validPixels : 0.0;
   if (report) *report = r;
   return true;
@@ -892,38 +864,13 @@ bool SmoothDepths(const std::vector<ReconstructionData *> &views, double thresho
 // Not in the reference (recon_host.h)
 bool EstimateSceneBounds(const std::vector<ReconstructionData *> &views, double thresholdBestCost, const double axes[9],
                          double trimFraction, int pixelStep, int device, SceneBoundsReport *report, std::string *error) {
-  const size_t n = views.size();
-  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
-  if (!first) {
-    *error = "EstimateSceneBounds: no views, or view 0 has no depth map";
-    return false;
-  }
-  const int W = first->dims[0], H = first->dims[1];
-  const size_t npix = (size_t)W * H;
-  if (n > 0x7fffffffu) {
-    *error = "EstimateSceneBounds: too many views";
-    return false;
-  }
-  std::vector<double> depth(n * npix), K4(n * 16), RT(n * 16);
+  GatheredViews g;
+  if (!GatherViews("EstimateSceneBounds", views, thresholdBestCost, true, &g, error)) return false;
   SceneBoundsReport r;
-  r.views = n;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
-    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
-      *error = "EstimateSceneBounds: view " + std::to_string(m) + " has no depth map of the size of view 0";
-      return false;
-    }
-    views[m]->ApplyDepthThresholdFilter(thresholdBestCost);
-    std::memcpy(depth.data() + m * npix, img->depths.data(), npix * 8);
-    std::memcpy(K4.data() + m * 16, views[m]->Get4MatrixK(), 16 * 8);
-    std::memcpy(RT.data() + m * 16, views[m]->GetMatrixTR(), 16 * 8);
-  }
-  const int rc = dmi_estimate_scene_bounds(depth.data(), nullptr, 0.0, K4.data(), RT.data(), (int32_t)n, W, H, axes, trimFraction, pixelStep,
-                                           device, r.lo, r.hi, &r.points, &r.kernelMs);
-  if (rc != DMI_OK) {
-    *error = dmi_last_error(nullptr);
-    return false;
-  }
+  r.views = views.size();
+  if (dmi_estimate_scene_bounds(g.depth.data(), nullptr, 0.0, g.K4.data(), g.RT.data(), (int32_t)views.size(), g.W, g.H, axes, trimFraction,
+                                pixelStep, device, r.lo, r.hi, &r.points, &r.kernelMs) != DMI_OK)
+    return LastError(error);
   if (report) *report = r;
   return true;
 }
@@ -944,26 +891,11 @@ bool DepthViewSet::Load(const std::vector<ReconstructionData *> &views, double t
   Release();
   Code = DMI_ERR_INVALID_ARGUMENT;
   const size_t n = views.size();
-  DepthImage *first = n && views[0] ? views[0]->GetDepthMap() : nullptr;
-  if (!first) {
-    Error = "DepthViewSet: no views, or view 0 has no depth map";
-    return false;
-  }
-  if (n > 0x7fffffffu) {
-    Error = "DepthViewSet: too many views";
-    return false;
-  }
-  W = first->dims[0];
-  H = first->dims[1];
+  if (!CommonViewSize("DepthViewSet", views, &W, &H, &Error)) return false;
   Dev = device;
   const size_t npix = (size_t)W * H;
-  for (size_t m = 0; m < n; ++m) {
-    DepthImage *img = views[m] ? views[m]->GetDepthMap() : nullptr;
-    if (!img || img->dims[0] != W || img->dims[1] != H || img->depths.size() != npix) {
-      Error = "DepthViewSet: view " + std::to_string(m) + " has no depth map of the size of view 0";
-      return false;
-    }
-  }
+  for (size_t m = 0; m < n; ++m)
+    if (!ViewHasSize("DepthViewSet", views, m, W, H, &Error)) return false;
   if ((Code = dmi_views_create(device, W, H, &Set)) != DMI_OK) {
     Error = std::string("dmi_views_create: ") + dmi_views_last_error(nullptr);
     Set = nullptr;

@@ -3,7 +3,9 @@
 // turn; an atomic add is a plain add; the reciprocal seed is 1.0 / x (the kernel checks whatever seed it gets); a scalar load is
 // a load.  What this cannot show: the device's division, its scalar loads, visibility between workgroups.
 // hipMalloc and hipFree are malloc and free -- so that AddressSanitizer sees a buffer freed twice or never -- with an allocator
-// that fails on the call a test names (tests/cpp/buffer_growth_host.cpp, for csrc/dmi_buffer.h).
+// that fails on the call a test names (tests/cpp/buffer_growth_host.cpp, for csrc/dmi_buffer.h).  Streams and events are allocations
+// too, counted as they are created and destroyed; the number of devices is the test's to set; a copy is a memcpy, a span between two
+// events one millisecond (tests/cpp/depth_call_host.cpp, for csrc/dmi_depth_call.h).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -32,12 +34,67 @@ struct launch_index {
 };
 inline launch_index blockIdx, threadIdx, gridDim, blockDim;
 constexpr hipError_t hipErrorOutOfMemory = 2;
+constexpr hipError_t hipErrorNoDevice = 100;
+constexpr hipError_t hipErrorInvalidDevice = 101;
+constexpr unsigned hipStreamNonBlocking = 1;
+enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount };
+enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
 struct hip_host_state {
   long mallocs = 0, frees = 0, synchronizes = 0;
   long fail_malloc_at = 0;  // the hipMalloc call (counted from 1) that fails; 0: none
+  int devices = 1;          // what hipGetDeviceCount says; below 0: it fails
+  int compute_units = 256;
+  long device_counts = 0, set_devices = 0, attributes = 0, copies = 0, elapsed_times = 0;
+  long streams_created = 0, streams_destroyed = 0, events_created = 0, events_destroyed = 0;
 };
 inline hip_host_state hip_host;
 inline hipError_t hipGetLastError() { return hipSuccess; }
+inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "error"; }
+inline hipError_t hipGetDeviceCount(int *n) {
+  ++hip_host.device_counts;
+  if (hip_host.devices < 0) return hipErrorNoDevice;
+  *n = hip_host.devices;
+  return hipSuccess;
+}
+inline hipError_t hipSetDevice(int device) {
+  ++hip_host.set_devices;
+  return device >= 0 && device < hip_host.devices ? hipSuccess : hipErrorInvalidDevice;
+}
+inline hipError_t hipDeviceGetAttribute(int *value, hipDeviceAttribute_t, int) {
+  ++hip_host.attributes;
+  *value = hip_host.compute_units;
+  return hipSuccess;
+}
+inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) {
+  ++hip_host.streams_created;
+  *s = malloc(1);
+  return hipSuccess;
+}
+inline hipError_t hipStreamDestroy(hipStream_t s) {
+  ++hip_host.streams_destroyed;
+  free(s);
+  return hipSuccess;
+}
+inline hipError_t hipEventCreate(hipEvent_t *e) {
+  ++hip_host.events_created;
+  *e = malloc(1);
+  return hipSuccess;
+}
+inline hipError_t hipEventDestroy(hipEvent_t e) {
+  ++hip_host.events_destroyed;
+  free(e);
+  return hipSuccess;
+}
+inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) {
+  ++hip_host.elapsed_times;
+  *ms = 1.f;
+  return hipSuccess;
+}
+inline hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t) {
+  ++hip_host.copies;
+  memcpy(dst, src, bytes);
+  return hipSuccess;
+}
 inline hipError_t hipMalloc(void **p, size_t bytes) {
   if (++hip_host.mallocs == hip_host.fail_malloc_at) return hipErrorOutOfMemory;
   *p = malloc(bytes ? bytes : 1);
