@@ -96,6 +96,12 @@ class PointsThinReportC(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class PointsRadiusReportC(ctypes.Structure):
+    _fields_ = [("points_in", ctypes.c_uint64), ("points_kept", ctypes.c_uint64), ("isolated", ctypes.c_uint64),
+                ("max_neighbors", ctypes.c_uint64), ("neighbor_sum", ctypes.c_uint64), ("distance_tests", ctypes.c_uint64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 class MultiOptionsC(ctypes.Structure):
     _fields_ = [("grid_dtype", ctypes.c_int32), ("depth_storage", ctypes.c_int32), ("kernel_variant", ctypes.c_int32),
                 ("partition", ctypes.c_int32), ("exchange", ctypes.c_int32), ("n_slabs", ctypes.c_int32)]
@@ -154,6 +160,8 @@ ABI_SYMBOLS = [
     "dmi_views_build_points", "dmi_views_download_points", "dmi_views_get_points_pass_ms",
     "dmi_thin_point_cloud", "dmi_views_thin_points", "dmi_views_download_point_members", "dmi_views_get_thin_pass_ms",
     "dmi_views_set_thin_wave_cell_points",
+    "dmi_count_point_neighbors", "dmi_views_filter_points_radius", "dmi_views_download_point_neighbors", "dmi_views_get_radius_pass_ms",
+    "dmi_views_set_radius_group_points",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -360,6 +368,13 @@ def load() -> ctypes.CDLL:
         L.dmi_views_download_point_members.argtypes = [vp, u64, u64, u32p]
         L.dmi_views_get_thin_pass_ms.argtypes = [vp, dp]
         L.dmi_views_set_thin_wave_cell_points.argtypes = [vp, i32]
+    if hasattr(L, "dmi_count_point_neighbors"):
+        u32p, rp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(PointsRadiusReportC)
+        L.dmi_count_point_neighbors.argtypes = [dp, u64, dbl, i32, i32, u32p, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(u64), rp]
+        L.dmi_views_filter_points_radius.argtypes = [vp, dbl, i32, ctypes.POINTER(u64), rp]
+        L.dmi_views_download_point_neighbors.argtypes = [vp, u64, u64, u32p]
+        L.dmi_views_get_radius_pass_ms.argtypes = [vp, dp]
+        L.dmi_views_set_radius_group_points.argtypes = [vp, i32]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1380,6 +1395,25 @@ def thin_point_cloud(xyz, normal=None, view=None, pixel=None, count=None, *, cel
     return arrays, {name: getattr(r, name) for name, _ in PointsThinReportC._fields_}
 
 
+def count_point_neighbors(xyz, *, radius: float, min_neighbors: int = 1, device: int = 0):
+    """Every point's number of other points within `radius`, and which points have at least min_neighbors of them (include/dmi.h:
+    dmi_count_point_neighbors).  xyz [P, 3] f64.  Returns (neighbors uint32 [P], keep bool [P], report): report has points_in,
+    points_kept, isolated, max_neighbors, neighbor_sum, distance_tests, kernel_ms.  xyz[keep] is the filtered cloud."""
+    L = load()
+    a = np.ascontiguousarray(xyz, dtype=np.float64)
+    if a.size % 3:
+        raise ValueError("xyz must hold 3 values per point")
+    p = a.size // 3
+    neighbors, keep = np.empty(p, dtype=np.uint32), np.empty(p, dtype=np.uint8)
+    n_kept, r = ctypes.c_uint64(0), PointsRadiusReportC()
+    rc = L.dmi_count_point_neighbors(_dp(a), p, float(radius), int(min_neighbors), int(device),
+                                     neighbors.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                     keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(n_kept), ctypes.byref(r))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    return neighbors, keep.astype(bool), {name: getattr(r, name) for name, _ in PointsRadiusReportC._fields_}
+
+
 class ViewSet:
     """Depth maps resident on the device from the first filter to the fusion (dmi_views_create ... dmi_views_destroy;
     include/dmi.h states the definition).  add() uploads once; every step replaces the set's depths by exactly what the
@@ -1562,6 +1596,39 @@ class ViewSet:
     def set_thin_wave_cell_points(self, k: int):
         """Cells of more than k members are summed by a wave of their own.  No result depends on it."""
         self._check(self._lib.dmi_views_set_thin_wave_cell_points(self._h, int(k)))
+
+    def filter_points_radius(self, radius: float, min_neighbors: int = 1) -> dict:
+        """The set's cloud, built or thinned, replaced by its points that have at least min_neighbors other points within `radius`
+        (include/dmi.h: dmi_views_filter_points_radius), in their order, every array carried as it is.  min_neighbors=0 drops
+        nothing and only counts.  Returns the report: points_in, points_kept, isolated, max_neighbors, neighbor_sum,
+        distance_tests, kernel_ms; download_point_neighbors serves the counts of the kept points."""
+        count, r = ctypes.c_uint64(0), PointsRadiusReportC()
+        self._check(self._lib.dmi_views_filter_points_radius(self._h, float(radius), int(min_neighbors), ctypes.byref(count),
+                                                             ctypes.byref(r)))
+        self._n_points = int(count.value)
+        return {name: getattr(r, name) for name, _ in PointsRadiusReportC._fields_}
+
+    def download_point_neighbors(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """How many neighbours each of the points [first, first + count) had in the cloud the last filter_points_radius found, uint32."""
+        first = int(first)
+        if count is None:
+            count = max(getattr(self, "_n_points", 0) - first, 0)
+        count = int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        out = np.empty(count, dtype=np.uint32)
+        self._check(self._lib.dmi_views_download_point_neighbors(self._h, first, count, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return out
+
+    def radius_pass_ms(self) -> dict:
+        """The last filter_points_radius' kernel time by pass (ms): bounds, keys, sort, ranks, permute, count, compaction."""
+        out = np.zeros(7, dtype=np.float64)
+        self._check(self._lib.dmi_views_get_radius_pass_ms(self._h, _dp(out)))
+        return dict(zip(("bounds", "keys", "sort", "ranks", "permute", "count", "compaction"), out.tolist()))
+
+    def set_radius_group_points(self, k: int):
+        """A wave of the neighbour count takes at most k points of one grid row as its queries (1..64).  No result depends on it."""
+        self._check(self._lib.dmi_views_set_radius_group_points(self._h, int(k)))
 
 
 class ColorContext:
@@ -1929,7 +1996,8 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_smooth_sigma", ctypes.c_double), ("depth_smooth_truncate", ctypes.c_double),
                 ("depth_smooth_tolerance", ctypes.c_double), ("depth_smooth_rel_tolerance", ctypes.c_double),
                 ("depth_smooth_iterations", ctypes.c_int64), ("depth_staged_filters", ctypes.c_int32),
-                ("point_cloud_cell_size", ctypes.c_double), ("point_cloud_min_cell_points", ctypes.c_int64)]
+                ("point_cloud_cell_size", ctypes.c_double), ("point_cloud_min_cell_points", ctypes.c_int64),
+                ("point_cloud_outlier_radius", ctypes.c_double), ("point_cloud_min_neighbors", ctypes.c_int64)]
 
 
 def cli_read_arguments(args):

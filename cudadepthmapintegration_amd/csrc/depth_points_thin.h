@@ -60,6 +60,11 @@ struct ThinRanks {
 };
 
 hipError_t thin_temp_bytes(uint64_t n, size_t *bytes);
+// rocPRIM's stable radix sort of (key, value) pairs over the low `bits` of the keys between two buffers each; with temp == nullptr
+// it only returns the storage it needs in *temp_bytes.  *sorted_keys, *sorted_values: where the result stands.  The search grid of
+// depth_points_radius.hip sorts with it too.
+hipError_t thin_sort_pairs(void *temp, size_t *temp_bytes, uint64_t *ka, uint64_t *kb, uint32_t *va, uint32_t *vb, uint64_t n, int bits,
+                           uint64_t **sorted_keys, uint32_t **sorted_values, hipStream_t stream);
 double thin_decode_bound(unsigned long long ordered);
 // the bounds pass: counters[kThinLo .. kThinNonFinite], every other counter zero
 hipError_t launch_thin_bounds(const ThinCloud &cloud, unsigned long long *counters, hipStream_t stream);

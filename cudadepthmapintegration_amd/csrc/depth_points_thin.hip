@@ -348,8 +348,10 @@ __global__ __launch_bounds__(kBlock) void thin_wave_cells_kernel(ThinCloud cloud
 
 unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-hipError_t sort_pairs(void *temp, size_t *temp_bytes, uint64_t *ka, uint64_t *kb, uint32_t *va, uint32_t *vb, uint64_t n, int bits,
-                      uint64_t **sorted_keys, uint32_t **sorted_values, hipStream_t stream) {
+}  // namespace
+
+hipError_t thin_sort_pairs(void *temp, size_t *temp_bytes, uint64_t *ka, uint64_t *kb, uint32_t *va, uint32_t *vb, uint64_t n, int bits,
+                           uint64_t **sorted_keys, uint32_t **sorted_values, hipStream_t stream) {
   rocprim::double_buffer<uint64_t> keys(ka, kb);
   rocprim::double_buffer<uint32_t> values(va, vb);
   size_t bytes = *temp_bytes;
@@ -360,12 +362,10 @@ hipError_t sort_pairs(void *temp, size_t *temp_bytes, uint64_t *ka, uint64_t *kb
   return e;
 }
 
-}  // namespace
-
 // the storage rocPRIM asks for: the largest of the sort's (all 64 key bits: the bins are not known yet) and the two scans'
 hipError_t thin_temp_bytes(uint64_t n, size_t *bytes) {
   size_t a = 0, b = 0, c = 0;
-  hipError_t e = sort_pairs(nullptr, &a, nullptr, nullptr, nullptr, nullptr, std::max<uint64_t>(n, 1), 64, nullptr, nullptr, nullptr);
+  hipError_t e = thin_sort_pairs(nullptr, &a, nullptr, nullptr, nullptr, nullptr, std::max<uint64_t>(n, 1), 64, nullptr, nullptr, nullptr);
   if (e != hipSuccess) return e;
   e = rocprim::inclusive_scan(nullptr, b, (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)(n + 1), rocprim::plus<uint32_t>(), nullptr);
   if (e != hipSuccess) return e;
@@ -404,7 +404,7 @@ hipError_t launch_thin_cells(const ThinCloud &cloud, const ThinGrid &g, uint32_t
   uint64_t *sorted_keys = nullptr;
   uint32_t *sorted_ids = nullptr;
   size_t bytes = s.temp_bytes;
-  if ((e = sort_pairs(s.temp, &bytes, s.keys[0], s.keys[1], s.ids[0], s.ids[1], n, bits, &sorted_keys, &sorted_ids, stream)) != hipSuccess)
+  if ((e = thin_sort_pairs(s.temp, &bytes, s.keys[0], s.keys[1], s.ids[0], s.ids[1], n, bits, &sorted_keys, &sorted_ids, stream)) != hipSuccess)
     return e;
   if ((e = hipEventRecord(events[2], stream)) != hipSuccess) return e;
   // the key array the sort did not end in takes the head flags and the ranks ...

@@ -84,6 +84,7 @@ void drop_points(dmi_view_set *s) {
   s->n_points = 0;
   s->points_current = false;
   s->points_thinned = false;
+  s->points_filtered = false;
 }
 
 struct Pieces {
@@ -678,6 +679,7 @@ int thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t 
   s->points = outcome.result;
   s->n_points = outcome.n_out;
   s->points_thinned = true;
+  s->points_filtered = false;  // (the counts went with the old cloud)
   s->steps += 1;
   for (int e = 0; e < 5; ++e) s->thin_pass_ms[e] = outcome.pass_ms[e];
   *n_points = outcome.n_out;
@@ -701,6 +703,65 @@ int download_point_members(dmi_view_set *s, uint64_t first, uint64_t count, uint
   (void)dmi::thin_rules::layout_of(s->n_points, &layout);
   VS_HIP(s, hipSetDevice(s->device));
   VS_HIP(s, hipMemcpyAsync(out, s->points.as<unsigned char>() + layout.members + first * 4, (size_t)(count * 4), hipMemcpyDeviceToHost,
+                            s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  return DMI_OK;
+}
+
+// the set's cloud, built or thinned, replaced by its points with at least min_neighbors neighbours within radius:
+// dmi::run_radius_points (dmi_capi_points_radius.hip) on the arrays of s->points
+int filter_points_radius(dmi_view_set *s, double radius, int32_t min_neighbors, uint64_t *n_points, dmi_points_radius_report *r) {
+  const std::string entry = "dmi_views_filter_points_radius";
+  if (const int rc = require_set(s, entry + ": ")) return rc;
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + ": " + what); };
+  if (!n_points) return bad("n_points is null");
+  if (const char *what = dmi::radius_refusal(radius, min_neighbors)) return bad(what);
+  if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + ": the set holds no points: dmi_views_build_points comes first");
+  if (s->n_points > dmi::radius_rules::kMaxPoints) return bad("the cloud must hold fewer than 2^32 points");
+
+  VS_HIP(s, hipSetDevice(s->device));
+  dmi::RadiusOutcome outcome;
+  if (s->n_points) {
+    dmi::thin_rules::Layout in;
+    (void)dmi::thin_rules::layout_of(s->n_points, &in);  // (it fitted when the points were made; the first five arrays are the build's)
+    const unsigned char *const base = s->points.as<unsigned char>();
+    dmi::RadiusCloud cloud{};
+    cloud.xyz = reinterpret_cast<const double *>(base + in.xyz);
+    cloud.normal = reinterpret_cast<const float *>(base + in.normal);
+    cloud.view = reinterpret_cast<const int32_t *>(base + in.view);
+    cloud.pixel = reinterpret_cast<const int32_t *>(base + in.pixel);
+    cloud.count = reinterpret_cast<const int32_t *>(base + in.count);
+    cloud.members = s->points_thinned ? reinterpret_cast<const uint32_t *>(base + in.members) : nullptr;
+    cloud.n = s->n_points;
+    std::string message;
+    const int rc = dmi::run_radius_points(entry, cloud, radius, min_neighbors, s->radius_group_points, s->points_thinned ? 52 : 48,
+                                          s->stream, s->device_bytes, &outcome, &message);
+    if (rc != DMI_OK) return fail(s, rc, message);  // (nothing of the call is left; the cloud is as it was)
+  }
+  dmi::free_buffers({&s->points}, s->device_bytes);
+  s->points = outcome.result;
+  s->n_points = outcome.n_kept;
+  s->points_filtered = true;
+  s->steps += 1;
+  for (int e = 0; e < 7; ++e) s->radius_pass_ms[e] = outcome.pass_ms[e];
+  *n_points = outcome.n_kept;
+  if (r) *r = outcome.report;
+  return DMI_OK;
+}
+
+int download_point_neighbors(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out) {
+  const std::string entry = "dmi_views_download_point_neighbors: ";
+  if (const int rc = require_set(s, entry)) return rc;
+  if (!s->points_current || !s->points_filtered)
+    return fail(s, DMI_ERR_STATE, entry + "the current cloud did not come out of dmi_views_filter_points_radius");
+  if (first > s->n_points || count > s->n_points - first)
+    return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "first + count must not exceed the number of points");
+  if (count == 0) return DMI_OK;
+  if (!out) return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "out is null");
+  uint64_t neighbors_offset = 0, bytes = 0;
+  (void)dmi::radius_rules::filtered_bytes(s->n_points, s->points_thinned ? 52 : 48, &neighbors_offset, &bytes);
+  VS_HIP(s, hipSetDevice(s->device));
+  VS_HIP(s, hipMemcpyAsync(out, s->points.as<unsigned char>() + neighbors_offset + first * 4, (size_t)(count * 4), hipMemcpyDeviceToHost,
                             s->stream));
   VS_HIP(s, hipStreamSynchronize(s->stream));
   return DMI_OK;
@@ -857,6 +918,35 @@ int dmi_views_set_thin_wave_cell_points(dmi_view_set *s, int32_t k) {
     if (const int rc = require_set(s, "dmi_views_set_thin_wave_cell_points: ")) return rc;
     if (k < 1) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_thin_wave_cell_points: k >= 1 required");
     s->thin_wave_cell_points = (uint32_t)k;
+    return DMI_OK;
+  });
+}
+
+int dmi_views_filter_points_radius(dmi_view_set *s, double radius, int32_t min_neighbors, uint64_t *n_points, dmi_points_radius_report *r) {
+  return guarded(s, "dmi_views_filter_points_radius", [&]() -> int { return filter_points_radius(s, radius, min_neighbors, n_points, r); });
+}
+
+int dmi_views_download_point_neighbors(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out) {
+  return guarded(s, "dmi_views_download_point_neighbors", [&]() -> int { return download_point_neighbors(s, first, count, out); });
+}
+
+int dmi_views_get_radius_pass_ms(dmi_view_set *s, double out_ms[7]) {
+  return guarded(s, "dmi_views_get_radius_pass_ms", [&]() -> int {
+    if (const int rc = require_set(s, "dmi_views_get_radius_pass_ms: ")) return rc;
+    if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_radius_pass_ms: out_ms is null");
+    if (!s->points_current || !s->points_filtered)
+      return fail(s, DMI_ERR_STATE, "dmi_views_get_radius_pass_ms: the current cloud did not come out of the radius filter");
+    for (int e = 0; e < 7; ++e) out_ms[e] = s->radius_pass_ms[e];
+    return DMI_OK;
+  });
+}
+
+int dmi_views_set_radius_group_points(dmi_view_set *s, int32_t k) {
+  return guarded(s, "dmi_views_set_radius_group_points", [&]() -> int {
+    if (const int rc = require_set(s, "dmi_views_set_radius_group_points: ")) return rc;
+    if (k < 1 || k > (int32_t)dmi::radius_rules::kMaxGroupPoints)
+      return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_set_radius_group_points: k must lie in [1, 64]");
+    s->radius_group_points = (uint32_t)k;
     return DMI_OK;
   });
 }

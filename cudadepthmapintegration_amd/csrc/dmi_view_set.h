@@ -8,6 +8,7 @@
 #include "depth_consistency.h"
 #include "depth_holes.h"
 #include "depth_points.h"
+#include "depth_points_radius.h"
 #include "depth_points_thin.h"
 #include "depth_smooth.h"
 #include "depth_speckle.h"
@@ -44,6 +45,11 @@ struct dmi_view_set {
   bool points_thinned = false;
   double thin_pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last thinning's bounds, keys, sort, ranks with their scans, representatives
   uint32_t thin_wave_cell_points = dmi::thin_rules::kDefaultWaveCellPoints;  // dmi_views_set_thin_wave_cell_points
+  // dmi_views_filter_points_radius has replaced the cloud by its kept points: the arrays it had (48 or 52 bytes per point) and a u32
+  // `neighbors` array behind them; a thinning or whatever drops the points drops it
+  bool points_filtered = false;
+  double radius_pass_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // the last filter's bounds, keys, sort, ranks, permute, count, compaction
+  uint32_t radius_group_points = dmi::radius_rules::kDefaultGroupPoints;  // dmi_views_set_radius_group_points
   double points_pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last build's flip, count, flags, block counts + scan, scatter
   dmi::DeviceBuffer counters;  // dmi::kVsCounters u64 (view_set_kernels.h); a build's dmi::kPtCounters stand in the same array
   hipStream_t stream = nullptr;
@@ -75,6 +81,21 @@ struct ThinOutcome {
 };
 int run_thin_points(const std::string &entry, const ThinCloud &cloud, double cell_size, int32_t min_points, uint32_t wave_cell_points,
                     hipStream_t stream, uint64_t &held, ThinOutcome *outcome, std::string *message);
+// dmi_capi_points_radius.hip: the neighbour counts of a cloud that is on the device (n in [1, 2^32), radius and min_neighbors
+// checked with radius_refusal by the caller) and, with bytes_per_point != 0 (the bytes of the cloud's own arrays: 48, or 52 with
+// members), its kept points in a buffer of their own; with 0 the counts themselves, in input order, are the outcome.  Everything
+// else is freed before it returns, `held` following every allocation.  DMI_OK, or a code with *message saying why: then nothing is
+// left allocated and the cloud is as it was.
+struct RadiusOutcome {
+  DeviceBuffer result;     // the cloud's layout for n_kept points, neighbors u32[n_kept] behind it; empty when there are none
+  DeviceBuffer neighbors;  // u32[n] (bytes_per_point == 0 only).  Both are the caller's to free.
+  uint64_t n_kept = 0;
+  dmi_points_radius_report report{};
+  double pass_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+};
+const char *radius_refusal(double radius, int32_t min_neighbors);  // what is wrong with the first of them that is, or null
+int run_radius_points(const std::string &entry, const RadiusCloud &cloud, double radius, int32_t min_neighbors, uint32_t group_points,
+                      uint64_t bytes_per_point, hipStream_t stream, uint64_t &held, RadiusOutcome *outcome, std::string *message);
 // dmi_capi_speckle.hip: the four passes on a piece, an event before the first and one behind each
 hipError_t run_speckle_piece(const SpecklePiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
                              int64_t min_pixels, const SpeckleTuning &tuning, hipStream_t stream, hipEvent_t events[5]);

@@ -401,6 +401,8 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->depth_staged_filters = o.depthStagedFilters ? 1 : 0;
   out->point_cloud_cell_size = o.pointCloudCellSizeGiven ? o.pointCloudCellSize : 0.0;
   out->point_cloud_min_cell_points = o.pointCloudMinCellPoints;
+  out->point_cloud_outlier_radius = o.pointCloudOutlierRadiusGiven ? o.pointCloudOutlierRadius : 0.0;
+  out->point_cloud_min_neighbors = o.pointCloudMinNeighbors;
   return 1;
   });
 }

@@ -362,6 +362,21 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                        return into_count(&o->pointCloudMinCellPoints)(values) && o->pointCloudMinCellPoints >= 1 &&
                                               o->pointCloudMinCellPoints <= 0x7fffffffLL;
                                      }}},
+      {"--pointCloudOutlierRadius", {Kind::kValue, "with --outputPointCloudFilename: drop, on the GPU behind the build and before "
+                                                   "--pointCloudCellSize, every point that has fewer than --pointCloudMinNeighbors other "
+                                                   "points within this distance (world units, finite, > 0); without a thinning behind "
+                                                   "it the file gets the point array NbNeighbors (not in the reference)",
+                                     into_checked_double(&o->pointCloudOutlierRadius, &o->pointCloudOutlierRadiusGiven, [](double x) {
+                                       const double r2 = x * x;  // a normal number: dmi_views_filter_points_radius asks for it
+                                       return x > 0.0 && r2 >= 2.2250738585072014e-308 && r2 <= 1.7976931348623157e308;
+                                     })}},
+      {"--pointCloudMinNeighbors", {Kind::kValue, "with --pointCloudOutlierRadius: the points a point needs within the radius to stay (a "
+                                                  "non-negative integer, default 1; 0 drops nothing and only counts; not in the reference)",
+                                    [o](const std::vector<std::string> &values) {
+                                      o->pointCloudMinNeighborsGiven = true;
+                                      return into_count(&o->pointCloudMinNeighbors)(values) && o->pointCloudMinNeighbors >= 0 &&
+                                             o->pointCloudMinNeighbors <= 0x7fffffffLL;
+                                    }}},
       {"--pointCloudColors", {Kind::kFlag, "with --outputPointCloudFilename: the point array Color (UInt8 RGB), each point's pixel of its "
                                            "view's Color array; every depth map file must carry one (not in the reference)",
                               into_flag(&o->pointCloudColors)}},
@@ -596,13 +611,18 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
                            std::make_pair("--pointCloudPixelStep", o->pointCloudPixelStepGiven),
                            std::make_pair("--pointCloudKeepDuplicates", o->pointCloudKeepDuplicates),
                            std::make_pair("--pointCloudColors", o->pointCloudColors),
-                           std::make_pair("--pointCloudCellSize", o->pointCloudCellSizeGiven)})
+                           std::make_pair("--pointCloudCellSize", o->pointCloudCellSizeGiven),
+                           std::make_pair("--pointCloudOutlierRadius", o->pointCloudOutlierRadiusGiven)})
     if (flag.second && !pointCloud) {
       err << "Error : " << flag.first << " needs --outputPointCloudFilename.\n" << HelpText();
       return false;
     }
   if (o->pointCloudMinCellPointsGiven && !o->pointCloudCellSizeGiven) {
     err << "Error : --pointCloudMinCellPoints needs --pointCloudCellSize.\n" << HelpText();
+    return false;
+  }
+  if (o->pointCloudMinNeighborsGiven && !o->pointCloudOutlierRadiusGiven) {
+    err << "Error : --pointCloudMinNeighbors needs --pointCloudOutlierRadius.\n" << HelpText();
     return false;
   }
   if (pointCloud) {
@@ -842,7 +862,7 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 }
 
 bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
-                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged) {
+                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged, const uint32_t *neighbors) {
   if (nPoints < 0) {
     *error = "WritePointCloud: negative count";
     return false;
@@ -855,12 +875,13 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
   const uint64_t n = (uint64_t)nPoints, header = sizeof(uint64_t);
   const uint64_t point_bytes = n * 3 * sizeof(double), cell_bytes = n * sizeof(int64_t), normal_bytes = n * 3 * sizeof(float),
                  int_bytes = n * sizeof(int32_t), rgb_bytes = n * 3;
-  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, NbMergedPoints, Color -- [UInt64 byte count]
-  // bytes each
+  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, NbMergedPoints, NbNeighbors, Color -- [UInt64
+  // byte count] bytes each
   const uint64_t conn_offset = header + point_bytes, offsets_offset = conn_offset + header + cell_bytes;
   const uint64_t normal_offset = offsets_offset + header + cell_bytes, view_offset = normal_offset + header + normal_bytes;
   const uint64_t agreeing_offset = view_offset + header + int_bytes, merged_offset = agreeing_offset + header + int_bytes;
-  const uint64_t color_offset = merged ? merged_offset + header + int_bytes : merged_offset;
+  const uint64_t neighbors_offset = merged ? merged_offset + header + int_bytes : merged_offset;
+  const uint64_t color_offset = neighbors ? neighbors_offset + header + int_bytes : neighbors_offset;
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
       << nPoints << "\" NumberOfVerts=\"" << nPoints << "\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"0\">\n"
@@ -870,6 +891,8 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
       << "\"/>\n        <DataArray type=\"Int32\" Name=\"NbAgreeingViews\" format=\"appended\" offset=\"" << agreeing_offset << "\"/>\n";
   if (merged)
     out << "        <DataArray type=\"UInt32\" Name=\"NbMergedPoints\" format=\"appended\" offset=\"" << merged_offset << "\"/>\n";
+  if (neighbors)
+    out << "        <DataArray type=\"UInt32\" Name=\"NbNeighbors\" format=\"appended\" offset=\"" << neighbors_offset << "\"/>\n";
   if (color)
     out << "        <DataArray type=\"UInt8\" Name=\"Color\" NumberOfComponents=\"3\" format=\"appended\" offset=\"" << color_offset
         << "\"/>\n";
@@ -897,6 +920,7 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
   write(view, int_bytes);
   write(agreeing, int_bytes);
   if (merged) write(merged, int_bytes);
+  if (neighbors) write(neighbors, int_bytes);
   if (color) write(color, rgb_bytes);
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
@@ -1246,9 +1270,12 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     }
     DepthPointsReport report;
     DepthThinReport thinned;
+    DepthRadiusReport sifted;
     DepthPoints points;
     if (!resident.BuildPoints(o.pointCloudTolerance, o.pointCloudRelTolerance, o.pointCloudNormalTolerance, o.pointCloudNormalRelTolerance,
                               (int)o.pointCloudMinViews, (int)o.pointCloudPixelStep, !o.pointCloudKeepDuplicates, &report) ||
+        (o.pointCloudOutlierRadiusGiven &&
+         !resident.FilterPointsRadius(o.pointCloudOutlierRadius, (int)o.pointCloudMinNeighbors, &sifted)) ||  // strays never become cells
         (o.pointCloudCellSizeGiven && !resident.ThinPoints(o.pointCloudCellSize, (int)o.pointCloudMinCellPoints, &thinned)) ||
         !resident.DownloadPoints(&points)) {
       result->error = flag + ": " + resident.LastError();
@@ -1272,7 +1299,8 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     std::string error;
     if (!WritePointCloud(o.outputPointCloudFilename, points.xyz.data(), (int64_t)points.view.size(), points.normal.data(), points.view.data(),
                          points.count.data(), o.pointCloudColors ? color.data() : nullptr, &error,
-                         o.pointCloudCellSizeGiven ? points.members.data() : nullptr)) {
+                         o.pointCloudCellSizeGiven ? points.members.data() : nullptr,
+                         o.pointCloudOutlierRadiusGiven && !o.pointCloudCellSizeGiven ? points.neighbors.data() : nullptr)) {
       result->error = error;
       return false;
     }
@@ -1291,6 +1319,21 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
          << " held by a lower view, " << report.points << " points, " << report.withNormal << " with a normal; " << report.kernelMs
          << " ms of GPU kernels";
     say(line.str());
+    if (o.pointCloudOutlierRadiusGiven) {
+      result->pointCloudRadiusPointsIn = sifted.pointsIn;
+      result->pointCloudRadiusPointsKept = sifted.pointsKept;
+      result->pointCloudRadiusIsolated = sifted.isolated;
+      result->pointCloudRadiusMaxNeighbors = sifted.maxNeighbors;
+      result->pointCloudRadiusNeighborSum = sifted.neighborSum;
+      result->pointCloudRadiusDistanceTests = sifted.distanceTests;
+      result->pointCloudRadiusKernelMs = sifted.kernelMs;
+      std::ostringstream sift;
+      sift << "point cloud outliers: radius " << o.pointCloudOutlierRadius << ", at least " << o.pointCloudMinNeighbors << " neighbours; "
+           << sifted.pointsIn << " points, " << sifted.pointsKept << " kept, " << sifted.isolated << " without a neighbour, at most "
+           << sifted.maxNeighbors << " neighbours, " << sifted.neighborSum << " in all from " << sifted.distanceTests
+           << " distance tests; " << sifted.kernelMs << " ms of GPU kernels";
+      say(sift.str());
+    }
     if (o.pointCloudCellSizeGiven) {
       result->pointCloudCells = thinned.cells;
       result->pointCloudCellsKept = thinned.cellsKept;
@@ -1705,6 +1748,13 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << "\n  pixels with a depth  " << result->pointCloudValidPixels << "\n  candidates  " << result->pointCloudCandidates
           << "\n  held by a lower view  " << result->pointCloudOwned << "\n  points  " << result->pointCloudPoints
           << "\n  points with a normal  " << result->pointCloudWithNormal << "\n  GPU kernels  " << result->pointCloudKernelMs << " ms\n";
+    if (!o.outputPointCloudFilename.empty() && o.pointCloudOutlierRadiusGiven)
+      out << "point cloud outliers\n  radius  " << o.pointCloudOutlierRadius << "\n  minimum neighbours  " << o.pointCloudMinNeighbors
+          << "\n  points in  " << result->pointCloudRadiusPointsIn << "\n  points kept  " << result->pointCloudRadiusPointsKept
+          << "\n  points without a neighbour  " << result->pointCloudRadiusIsolated << "\n  most neighbours  "
+          << result->pointCloudRadiusMaxNeighbors << "\n  neighbours in all  " << result->pointCloudRadiusNeighborSum
+          << "\n  distance tests  " << result->pointCloudRadiusDistanceTests << "\n  GPU kernels  " << result->pointCloudRadiusKernelMs
+          << " ms\n";
     if (!o.outputPointCloudFilename.empty() && o.pointCloudCellSizeGiven)
       out << "point cloud thinning\n  cell size  " << o.pointCloudCellSize << "\n  minimum points per cell  " << o.pointCloudMinCellPoints
           << "\n  occupied cells  " << result->pointCloudCells << "\n  cells kept  " << result->pointCloudCellsKept

@@ -162,6 +162,12 @@ struct Options {
   double pointCloudCellSize = 0.0;
   long long pointCloudMinCellPoints = 1;
   bool pointCloudCellSizeGiven = false, pointCloudMinCellPointsGiven = false;
+  // with pointCloudOutlierRadius the cloud loses, on the GPU behind the build and BEFORE the thinning -- strays never become cells
+  // --, every point with fewer than pointCloudMinNeighbors other points within that radius (dmi_views_filter_points_radius,
+  // DESIGN.md 8p); the .vtp gets the point array NbNeighbors when no thinning follows
+  double pointCloudOutlierRadius = 0.0;
+  long long pointCloudMinNeighbors = 1;
+  bool pointCloudOutlierRadiusGiven = false, pointCloudMinNeighborsGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -231,6 +237,10 @@ struct RunResult {
   unsigned long long pointCloudCells = 0, pointCloudCellsKept = 0, pointCloudMultiViewCells = 0, pointCloudLargestCell = 0,
                      pointCloudThinnedWithNormal = 0;
   double pointCloudThinKernelMs = 0.0;
+  // --pointCloudOutlierRadius: the report of the filter (include/dmi.h: dmi_points_radius_report)
+  unsigned long long pointCloudRadiusPointsIn = 0, pointCloudRadiusPointsKept = 0, pointCloudRadiusIsolated = 0,
+                     pointCloudRadiusMaxNeighbors = 0, pointCloudRadiusNeighborSum = 0, pointCloudRadiusDistanceTests = 0;
+  double pointCloudRadiusKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);
@@ -254,8 +264,11 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
 // ... and offsets 1, 2, 3 ...), the point arrays Normals (Float32 x 3, the section's Normals), ViewIndex and NbAgreeingViews (Int32)
 // and, with `color` ([nPoints][3] u8), Color (UInt8 x 3) behind them; with `merged` ([nPoints] u32: the points each point of a thinned
 // cloud was merged from) NbMergedPoints (UInt32) behind NbAgreeingViews.  Without `merged` the file is what it was before the array existed.
+// With `neighbors` ([nPoints] u32: the points within the outlier filter's radius) NbNeighbors (UInt32) behind those and before Color;
+// without it the file is what it was before that array existed.
 bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
-                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged = nullptr);
+                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged = nullptr,
+                     const uint32_t *neighbors = nullptr);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

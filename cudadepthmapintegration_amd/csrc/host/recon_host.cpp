@@ -1007,6 +1007,7 @@ bool DepthViewSet::BuildPoints(double absTolerance, double relTolerance, double 
                                      (int32_t)pixelStep, dedupe ? 1 : 0, &n, &r)) != DMI_OK)
     return Fail("dmi_views_build_points");
   NPoints = n;
+  Filtered = false;
   if (report) {
     *report = DepthPointsReport();
     report->views = NViews;
@@ -1025,6 +1026,7 @@ bool DepthViewSet::ThinPoints(double cellSize, int minPoints, DepthThinReport *r
   uint64_t n = 0;
   if ((Code = dmi_views_thin_points(Set, cellSize, (int32_t)minPoints, &n, &r)) != DMI_OK) return Fail("dmi_views_thin_points");
   NPoints = n;
+  Filtered = false;
   if (report) {
     *report = DepthThinReport();
     report->pointsIn = r.points_in;
@@ -1038,8 +1040,31 @@ bool DepthViewSet::ThinPoints(double cellSize, int minPoints, DepthThinReport *r
   return true;
 }
 
+bool DepthViewSet::FilterPointsRadius(double radius, int minNeighbors, DepthRadiusReport *report) {
+  dmi_points_radius_report r;
+  uint64_t n = 0;
+  if ((Code = dmi_views_filter_points_radius(Set, radius, (int32_t)minNeighbors, &n, &r)) != DMI_OK)
+    return Fail("dmi_views_filter_points_radius");
+  NPoints = n;
+  Filtered = true;
+  if (report) {
+    *report = DepthRadiusReport();
+    report->pointsIn = r.points_in;
+    report->pointsKept = r.points_kept;
+    report->isolated = r.isolated;
+    report->maxNeighbors = r.max_neighbors;
+    report->neighborSum = r.neighbor_sum;
+    report->distanceTests = r.distance_tests;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
 bool DepthViewSet::DownloadPoints(DepthPoints *points) {
   const size_t n = (size_t)NPoints;
+  points->neighbors.resize(Filtered ? n : 0);
+  if (Filtered && (Code = dmi_views_download_point_neighbors(Set, 0, NPoints, points->neighbors.data())) != DMI_OK)
+    return Fail("dmi_views_download_point_neighbors");
   points->members.resize(n);
   if ((Code = dmi_views_download_point_members(Set, 0, NPoints, points->members.data())) != DMI_OK)
     return Fail("dmi_views_download_point_members");

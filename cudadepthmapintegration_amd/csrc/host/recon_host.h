@@ -185,11 +185,18 @@ struct DepthPoints {
   std::vector<float> normal;  // [n][3], zero where a point has none
   std::vector<int32_t> view, pixel, count;  // [n]: the view, py * W + px in image coordinates, the views that agree
   std::vector<uint32_t> members;            // [n]: the points each was merged from (1 unless DepthViewSet::ThinPoints has run)
+  std::vector<uint32_t> neighbors;          // [n] where DepthViewSet::FilterPointsRadius made the cloud, else empty: the points within the radius
 };
 // ... and the report of a thinning of it on a voxel grid (dmi_views_thin_points)
 struct DepthThinReport {
   uint64_t pointsIn = 0, cells = 0, cellsKept = 0, multiViewCells = 0, largestCell = 0, withNormal = 0;
   double kernelMs = 0.0;  // hipEvent time of the thinning's kernels
+};
+
+// ... and of a radius outlier filter of it (dmi_views_filter_points_radius)
+struct DepthRadiusReport {
+  uint64_t pointsIn = 0, pointsKept = 0, isolated = 0, maxNeighbors = 0, neighborSum = 0, distanceTests = 0;
+  double kernelMs = 0.0;  // hipEvent time of the filter's kernels
 };
 
 // Not in the reference: the views' depths resident on one GPU from the first of the steps above to the fusion (dmi_view_set,
@@ -221,6 +228,9 @@ class DepthViewSet {
   // The built cloud replaced, on the device, by one point per occupied cell of cellSize that holds at least minPoints points, at
   // their mean (once per build); DownloadPoints then brings the thinned cloud
   bool ThinPoints(double cellSize, int minPoints, DepthThinReport *report);
+  // The cloud, built or thinned, replaced on the device by its points that have at least minNeighbors other points within radius,
+  // in their order (any number of times); DownloadPoints then brings the kept points with their counts
+  bool FilterPointsRadius(double radius, int minNeighbors, DepthRadiusReport *report);
   bool DownloadPoints(DepthPoints *points);
   int Width() const { return W; }
   int Height() const { return H; }
@@ -238,6 +248,7 @@ class DepthViewSet {
   dmi_view_set *Set = nullptr;
   size_t NViews = 0;
   uint64_t NPoints = 0;  // of the last BuildPoints
+  bool Filtered = false;  // the cloud came out of FilterPointsRadius
   int W = 0, H = 0, Dev = 0;
   std::string Error;
   int Code = 0;

@@ -55,7 +55,7 @@ extern "C" {
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
                            *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles;
-                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms; dmi_thin_point_cloud, dmi_views_thin_points, dmi_views_download_point_members, dmi_views_get_thin_pass_ms, dmi_views_set_thin_wave_cell_points */
+                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms; dmi_thin_point_cloud, dmi_views_thin_points, dmi_views_download_point_members, dmi_views_get_thin_pass_ms, dmi_views_set_thin_wave_cell_points; dmi_count_point_neighbors, dmi_views_filter_points_radius, dmi_views_download_point_neighbors, dmi_views_get_radius_pass_ms, dmi_views_set_radius_group_points */
 
 typedef struct dmi_context dmi_context;
 
@@ -1168,6 +1168,65 @@ int dmi_views_thin_points(dmi_view_set *s, double cell_size, int32_t min_points,
 int dmi_views_download_point_members(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out);
 int dmi_views_get_thin_pass_ms(dmi_view_set *s, double out_ms[5]);
 int dmi_views_set_thin_wave_cell_points(dmi_view_set *s, int32_t k);
+
+/* ---- Point-cloud outliers dropped by radius neighbour count (added after round 5, dmi_abi_version() stays 5) ----
+ * Every point's number of other points within a radius, and the cloud without the points that have too few: what PCL's
+ * RadiusOutlierRemoval or Open3D's remove_radius_outlier does to a cloud.  A count in a ball depends on no grid -- min_points of the
+ * thinning drops good surface that a cell face cuts off, and keeps a stray next to a full cell -- and, being an integer, is defined
+ * to the bit whatever the schedule.  csrc/depth_points_radius.hip.  Definition, met bit for bit by the device and by
+ * tests/depth_points_radius_np.py, which counts over all pairs.
+ * The input is P points xyz f64[P][3] in a given order.  Parameters: radius, min_neighbors.  All arithmetic is f64, with every
+ * operation rounded on its own and no FMA; comparisons with a NaN are false.
+ *   1. r2 = radius * radius.
+ *   2. For points i != j: d_k = xyz[j][k] - xyz[i][k], d2 = (d_0*d_0 + d_1*d_1) + d_2*d_2.
+ *   3. j is a NEIGHBOUR of i iff d2 <= r2.  The relation is symmetric; coincident points are neighbours of each other; a point is
+ *      never its own neighbour, by index, not by position.
+ *   4. neighbors[i] (uint32) is the number of neighbours of i.
+ *   5. KEPT iff neighbors[i] >= min_neighbors.
+ *   6. The output is the kept points in input order, every array of a kept point carried bit for bit -- xyz, normal, view, pixel,
+ *      count, and members when the cloud is a thinned one --, with its neighbors[i], counted in the input cloud.
+ *   7. REPORT (dmi_points_radius_report).  points_in: P.  points_kept.  isolated: points with neighbors == 0.  max_neighbors.
+ *      neighbor_sum: the sum of the counts (always even).  distance_tests: the d2 the implementation evaluated for its queries; not
+ *      part of the definition, only >= neighbor_sum, there so that the search's overhead can be computed.  kernel_ms: the hipEvent
+ *      time of the call's kernels.
+ * The search grid is an implementation detail: cells of h = max(radius * (1 + 2^-10), the smallest h with at most 2^21 bins on every
+ * axis), so a far-away stray makes the cells larger -- which costs time -- instead of refusing the call; the radius is never refused
+ * for being small against the cloud's extent.  DMI_ERR_INVALID_ARGUMENT, before the device is touched: a radius that is NaN,
+ * infinite or <= 0, or whose square is not a normal positive number; min_neighbors < 0; P >= 2^32; null pointers; a device out of
+ * range.  A non-finite coordinate, found by the bounds pass, is refused with the same code.  Nothing else is refused.
+ *
+ * dmi_count_point_neighbors is context-free: the coordinates go up in pieces, out_neighbors[P] and (nullable) out_keep[P], 1 where
+ * kept, come back, *n_kept is the number kept; compacting host arrays is the caller's one line.  P == 0 is a success that touches no
+ * device.  A call that is refused or fails leaves the outputs untouched.  dmi_last_error(NULL) has the text.
+ *
+ * dmi_views_filter_points_radius runs the same implementation on the set's current cloud, built or thinned, and replaces it by the
+ * kept points: a buffer of its own at exactly the size needed, swapped in last, so a call that is refused or fails leaves the old
+ * cloud.  DMI_ERR_STATE without a current build.  It may be called repeatedly (each call counts in the cloud it finds);
+ * min_neighbors = 0 drops nothing and only annotates; zero kept points is DMI_OK.  A success counts as a step in
+ * dmi_views_info::steps; device_bytes follows every allocation, and after the call holds 48 + 4 bytes per kept point (52 + 4 for a
+ * thinned cloud) in place of the old cloud.  dmi_views_download_points and dmi_views_download_point_members serve the filtered cloud
+ * unchanged; dmi_views_thin_points on a filtered cloud that was not thinned before gives what dmi_thin_point_cloud gives for the
+ * downloaded filtered arrays, and drops the counts with the old cloud; whatever drops the built cloud drops this one.  During the
+ * call the set holds 56 bytes per input point besides the two clouds, freed when it ends.
+ *   dmi_views_download_point_neighbors   neighbors of the points [first, first + count).  DMI_ERR_STATE unless the current cloud
+ *              came out of the filter.
+ *   dmi_views_get_radius_pass_ms   the last filter's kernel time by pass: bounds, keys, sort, ranks, permute, count, compaction.
+ *              DMI_ERR_STATE unless the current cloud came out of the filter.
+ *   dmi_views_set_radius_group_points   a wave of the count kernel takes at most k points of one grid row as its queries
+ *              (1 <= k <= 64).  No value changes a bit of the result; it lets a test drive every path at small shapes.
+ *              dmi_count_point_neighbors uses the default, 64. */
+typedef struct dmi_points_radius_report {
+  uint64_t points_in, points_kept, isolated, max_neighbors, neighbor_sum, distance_tests;
+  double kernel_ms;
+} dmi_points_radius_report;
+int dmi_count_point_neighbors(const double *xyz, uint64_t n_points, double radius, int32_t min_neighbors, int32_t device,
+                              uint32_t *out_neighbors /* [n_points] */, uint8_t *out_keep /* [n_points], nullable */, uint64_t *n_kept,
+                              dmi_points_radius_report *r /* nullable */);
+int dmi_views_filter_points_radius(dmi_view_set *s, double radius, int32_t min_neighbors, uint64_t *n_points,
+                                   dmi_points_radius_report *r /* nullable */);
+int dmi_views_download_point_neighbors(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out);
+int dmi_views_get_radius_pass_ms(dmi_view_set *s, double out_ms[7]);
+int dmi_views_set_radius_group_points(dmi_view_set *s, int32_t k);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

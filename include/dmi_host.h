@@ -145,6 +145,9 @@ typedef struct dmi_cli_options {
   /* not in the reference, only with --outputPointCloudFilename (dmi_views_thin_points, dmi.h); appended to the struct: */
   double point_cloud_cell_size;          /* --pointCloudCellSize v: thin the point cloud on a voxel grid before it is written; 0: not given */
   int64_t point_cloud_min_cell_points;   /* --pointCloudMinCellPoints N (default 1) */
+  /* not in the reference, only with --outputPointCloudFilename (dmi_views_filter_points_radius, dmi.h); appended to the struct: */
+  double point_cloud_outlier_radius;     /* --pointCloudOutlierRadius r: drop the points with too few neighbours within r, before the thinning; 0: not given */
+  int64_t point_cloud_min_neighbors;     /* --pointCloudMinNeighbors N (default 1) */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
