@@ -59,7 +59,9 @@ def main():
     p.add_argument("--sweep", type=int, nargs="*", default=None, help="values of the knob (no value: 1 2 4 8 16 32 64)")
     p.add_argument("--quality", action="store_true")
     p.add_argument("--inject", type=float, default=0.01)
-    p.add_argument("--check", action="store_true")
+    p.add_argument("--check", action="store_true",
+                   help="first compare a small scene (a few thousand points) with the numpy restatements; the comparison at "
+                        "the sizes timed here, above 2^20 points, is tests/test_depth_points_scale.py")
     a = p.parse_args()
     n, W, H = a.views, a.width, a.height
     voxel = 2.0 / a.cells
