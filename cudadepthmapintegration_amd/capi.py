@@ -631,9 +631,7 @@ class FusionContext:
     def point_smoothing_kernel_ms(self) -> float:
         """hipEvent milliseconds of the smoothing kernels of the last computation of the point data; 0 while the setting is off
         (dmi_get_point_smoothing_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_point_smoothing_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_point_smoothing_kernel_ms")
 
     def iso_active_cells(self, iso: float, ids: bool = True):
         """(count, ids): the cells whose corner point values straddle `iso` (dmi_iso_active_cells); ids ascending int64, or
@@ -657,7 +655,7 @@ class FusionContext:
         self._check(self._lib.dmi_extract_isosurface(self._h, float(iso), ctypes.byref(nv), ctypes.byref(nt)))
         verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
         tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
-        self._mesh_counts = (int(nv.value), int(nt.value), 0)
+        self._mesh_is(nv.value, nt.value)
         self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return verts[:int(nv.value)], tris[:int(nt.value)]
 
@@ -670,7 +668,7 @@ class FusionContext:
         verts = np.empty((max(int(nv.value), 1), 3), dtype=np.float64)    # never a null pointer, even for an empty mesh
         tris = np.empty((max(int(nt.value), 1), 3), dtype=np.int64)
         normals = np.empty((max(int(nv.value), 1), 3), dtype=np.float32)
-        self._mesh_counts = (int(nv.value), int(nt.value), 0)
+        self._mesh_is(nv.value, nt.value)
         self._check(self._lib.dmi_download_isosurface(self._h, _dp(verts), tris.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         self._check(self._lib.dmi_download_isosurface_normals(self._h, normals.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
         return verts[:int(nv.value)], tris[:int(nt.value)], normals[:int(nv.value)]
@@ -683,8 +681,28 @@ class FusionContext:
         m = {"min_triangles": DMI_COMPONENTS_MIN_TRIANGLES, "largest": DMI_COMPONENTS_LARGEST}[mode]
         out = [ctypes.c_uint64(0) for _ in range(4)]
         self._check(self._lib.dmi_filter_isosurface_components(self._h, m, int(min_triangles), *[ctypes.byref(x) for x in out]))
-        self._mesh_counts = (int(out[0].value), int(out[1].value), int(out[3].value))
+        self._mesh_is(out[0].value, out[1].value, regions=out[3].value)
         return tuple(int(x.value) for x in out)
+
+    def _get_ms(self, symbol: str) -> float:
+        a = ctypes.c_double(0)
+        self._check(getattr(self._lib, symbol)(self._h, ctypes.byref(a)))
+        return float(a.value)
+
+    def _get_pass_ms(self, symbol: str, names) -> dict:
+        a = (ctypes.c_double * len(names))()
+        self._check(getattr(self._lib, symbol)(self._h, a))
+        return dict(zip(names, (float(x) for x in a)))
+
+    def _get_u64(self, symbol: str) -> int:
+        a = ctypes.c_uint64(0)
+        self._check(getattr(self._lib, symbol)(self._h, ctypes.byref(a)))
+        return int(a.value)
+
+    def _mesh_is(self, nv, nt, regions=0):
+        """The sizes of the C side's mesh after a call that changed it (the downloads size their arrays by them): an extraction's, a
+        decimation's, a fill's and a trim's counts with no regions, the component filter's with the components it kept."""
+        self._mesh_counts = (int(nv), int(nt), int(regions))
 
     def _current_mesh_counts(self):
         c = self._mesh_counts      # a refused filter changes neither the C side's mesh nor these
@@ -720,21 +738,15 @@ class FusionContext:
 
     def isosurface_filter_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last filter_isosurface_components (dmi_get_isosurface_filter_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_filter_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_filter_kernel_ms")
 
     def isosurface_filter_cas_retries(self) -> int:
         """Compare-and-swaps of the last filter's hooking pass that lost a race (dmi_get_isosurface_filter_cas_retries)."""
-        a = ctypes.c_uint64(0)
-        self._check(self._lib.dmi_get_isosurface_filter_cas_retries(self._h, ctypes.byref(a)))
-        return int(a.value)
+        return self._get_u64("dmi_get_isosurface_filter_cas_retries")
 
     def isosurface_filter_pass_ms(self) -> dict:
         """The same pass by pass (dmi_get_isosurface_filter_pass_ms)."""
-        a = (ctypes.c_double * 4)()
-        self._check(self._lib.dmi_get_isosurface_filter_pass_ms(self._h, a))
-        return dict(zip(("labels", "sizes", "scans", "compaction"), (float(x) for x in a)))
+        return self._get_pass_ms("dmi_get_isosurface_filter_pass_ms", ("labels", "sizes", "scans", "compaction"))
 
     def smooth_isosurface(self, iterations: int, lam: float = 0.5, mu: float = -0.53) -> None:
         """Taubin lambda|mu smoothing of the context's mesh on the device, `iterations` times a step with `lam` and (mu != 0) one
@@ -744,15 +756,11 @@ class FusionContext:
 
     def isosurface_smooth_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last smooth_isosurface (dmi_get_isosurface_smooth_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_smooth_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_smooth_kernel_ms")
 
     def isosurface_smooth_pass_ms(self) -> dict:
         """The same pass by pass (dmi_get_isosurface_smooth_pass_ms)."""
-        a = (ctypes.c_double * 3)()
-        self._check(self._lib.dmi_get_isosurface_smooth_pass_ms(self._h, a))
-        return dict(zip(("adjacency", "steps", "normals"), (float(x) for x in a)))
+        return self._get_pass_ms("dmi_get_isosurface_smooth_pass_ms", ("adjacency", "steps", "normals"))
 
     def decimate_isosurface(self, cell_size: float, placement: str = "mean"):
         """(vertices, triangles) left after vertex clustering of the context's mesh on the device with cubic cells of `cell_size`
@@ -769,20 +777,16 @@ class FusionContext:
         else:
             self._check(self._lib.dmi_decimate_isosurface_placed(self._h, float(cell_size), DECIMATE_PLACEMENTS[placement],
                                                                  ctypes.byref(nv), ctypes.byref(nt)))
-        self._mesh_counts = (int(nv.value), int(nt.value), 0)
+        self._mesh_is(nv.value, nt.value)
         return int(nv.value), int(nt.value)
 
     def isosurface_decimate_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last decimate_isosurface (dmi_get_isosurface_decimate_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_decimate_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_decimate_kernel_ms")
 
     def isosurface_decimate_pass_ms(self) -> dict:
         """The same pass by pass (dmi_get_isosurface_decimate_pass_ms)."""
-        a = (ctypes.c_double * 4)()
-        self._check(self._lib.dmi_get_isosurface_decimate_pass_ms(self._h, a))
-        return dict(zip(("clustering", "representatives", "triangles", "normals"), (float(x) for x in a)))
+        return self._get_pass_ms("dmi_get_isosurface_decimate_pass_ms", ("clustering", "representatives", "triangles", "normals"))
 
     def fill_isosurface_holes(self, max_edges: int):
         """(vertices, triangles, holes filled, boundary edges left) after the small holes of the context's mesh are closed on the
@@ -793,21 +797,17 @@ class FusionContext:
         8f).  download_isosurface* return the filled mesh afterwards."""
         out = [ctypes.c_uint64(0) for _ in range(4)]
         self._check(self._lib.dmi_fill_isosurface_holes(self._h, int(max_edges), *[ctypes.byref(x) for x in out]))
-        if int(out[2].value):
-            self._mesh_counts = (int(out[0].value), int(out[1].value), 0)
+        if out[2].value:   # something was filled
+            self._mesh_is(out[0].value, out[1].value)
         return tuple(int(x.value) for x in out)
 
     def isosurface_holes_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last fill_isosurface_holes (dmi_get_isosurface_holes_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_holes_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_holes_kernel_ms")
 
     def isosurface_holes_pass_ms(self) -> dict:
         """The same pass by pass (dmi_get_isosurface_holes_pass_ms)."""
-        a = (ctypes.c_double * 3)()
-        self._check(self._lib.dmi_get_isosurface_holes_pass_ms(self._h, a))
-        return dict(zip(("boundary", "loops", "fill"), (float(x) for x in a)))
+        return self._get_pass_ms("dmi_get_isosurface_holes_pass_ms", ("boundary", "loops", "fill"))
 
     def filter_isosurface_support(self, min_views: int, tolerance: float, facing: bool = True):
         """(vertices, triangles) left after the trim of the context's mesh by view support on the device: every vertex is given the
@@ -820,7 +820,7 @@ class FusionContext:
                                                             ctypes.byref(nv), ctypes.byref(nt)))
         old = self._mesh_counts
         if old is None or (int(nv.value), int(nt.value)) != old[:2]:   # something went: the regions of an earlier filter too
-            self._mesh_counts = (int(nv.value), int(nt.value), 0)
+            self._mesh_is(nv.value, nt.value)
         return int(nv.value), int(nt.value)
 
     def download_isosurface_support(self):
@@ -833,15 +833,11 @@ class FusionContext:
 
     def isosurface_support_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last filter_isosurface_support (dmi_get_isosurface_support_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_support_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_support_kernel_ms")
 
     def isosurface_support_pass_ms(self) -> dict:
         """The same pass by pass (dmi_get_isosurface_support_pass_ms)."""
-        a = (ctypes.c_double * 3)()
-        self._check(self._lib.dmi_get_isosurface_support_pass_ms(self._h, a))
-        return dict(zip(("counts", "scans", "compaction"), (float(x) for x in a)))
+        return self._get_pass_ms("dmi_get_isosurface_support_pass_ms", ("counts", "scans", "compaction"))
 
     def color_isosurface(self, color_ctx: "ColorContext", fused_depth_tolerance: float | None = None) -> int:
         """Colour the context's mesh where it is, with the views resident in `color_ctx`; returns the number of vertices.  The
@@ -873,16 +869,12 @@ class FusionContext:
 
     def isosurface_color_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last color_isosurface (dmi_get_isosurface_color_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_color_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_color_kernel_ms")
 
     def isosurface_kernel_ms(self) -> float:
         """hipEvent milliseconds of the kernels of the last extract_isosurface or extract_isosurface_with_normals
         (dmi_get_isosurface_kernel_ms)."""
-        a = ctypes.c_double(0)
-        self._check(self._lib.dmi_get_isosurface_kernel_ms(self._h, ctypes.byref(a)))
-        return float(a.value)
+        return self._get_ms("dmi_get_isosurface_kernel_ms")
 
     def brick_class_histogram(self) -> dict:
         """(brick, view) pairs of the last fuse by proven class (diagnostic)."""

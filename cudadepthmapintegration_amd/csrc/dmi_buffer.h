@@ -31,6 +31,15 @@ inline hipError_t grow_buffer(DeviceBuffer &buffer, uint64_t bytes) {
   return e;
 }
 
+// ... and the same for a group's events
+template <size_t N>
+void destroy_events(hipEvent_t (&events)[N]) {
+  for (hipEvent_t &e : events) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+}
+
 // what every group's release() is made of (the caller has selected the device)
 inline void free_buffers(std::initializer_list<DeviceBuffer *> buffers) {
   for (DeviceBuffer *b : buffers) {

@@ -1,6 +1,9 @@
 // dmi_capi_mesh.hip -- the post-processing entry points of the C ABI declared in include/dmi.h: the grid's point data
 // (vtkCellDataToPointData), the active cells of an iso-value, and the iso-surface mesh -- extraction, downloads, the component
-// filter, the smoother, the decimation, the support trim, the coloration and their getters.  All of it works on the grouped state of dmi_context.h; dmi_capi.hip, dmi_capi_views.hip and dmi_capi_fuse.hip have the rest.
+// filter, the smoother, the decimation, the hole fill, the support trim, the coloration and their getters.  All of it works on the
+// grouped state of dmi_context.h; what the mesh stages share -- the mesh's state and its commit, the events and times, the sizes
+// refused, the scratch carving -- is dmi_mesh_stage.h's, and the helpers below (require_mesh, the getters, download) are the rest
+// of their scaffold.  dmi_capi.hip, dmi_capi_views.hip and dmi_capi_fuse.hip have the rest of the C ABI.
 #include "dmi_context.h"
 
 #include <algorithm>
@@ -23,22 +26,64 @@ constexpr uint64_t kVertexBytes = 3 * sizeof(double), kTriangleBytes = 3 * sizeo
 int64_t n_points(const dmi_context *c) {
   return (int64_t)(c->grid.cell_dims[0] + 1) * (c->grid.cell_dims[1] + 1) * (c->grid.cell_dims[2] + 1);
 }
+
+// every entry point that works on the mesh: `since` is what the message says has not happened
+int require_mesh(dmi_context *ctx, const std::string &entry, const char *since = "no extraction has succeeded") {
+  if (ctx->mesh.valid) return DMI_OK;
+  return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (" + since + ")");
+}
+
+// a size the stage cannot hold (dmi_mesh_stage.h: the text, empty when accepted)
+int refuse_size(dmi_context *ctx, const std::string &entry, const std::string &refusal) {
+  return refusal.empty() ? DMI_OK : fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": " + refusal);
+}
+
+// The getters: behind the null check and, for the stages whose events are read late, the drain, one number of the context (a
+// time, a counter; `field` picks it) or a stage's passes
+using Drain = int (*)(dmi_context *);
+template <typename T, typename Read>
+int get(dmi_context *ctx, const char *entry, T *out, Drain drain, Read read) {
+  return guarded(ctx, entry, [&]() -> int {
+    if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, std::string(entry) + ": null argument");
+    const int rc = drain ? drain(ctx) : DMI_OK;
+    if (rc == DMI_OK) read();
+    return rc;
+  });
+}
+template <typename T, typename Field>
+int get_value(dmi_context *ctx, const char *entry, T *out, Field field, Drain drain = nullptr) {
+  return get(ctx, entry, out, drain, [&] { *out = field(*ctx); });
+}
+template <typename Stage>
+int get_passes(dmi_context *ctx, const char *entry, double *out, Stage dmi_context::*stage, Drain drain = nullptr) {
+  return get(ctx, entry, out, drain, [&] { std::copy((ctx->*stage).last_pass_ms.begin(), (ctx->*stage).last_pass_ms.end(), out); });
+}
+
+// The downloads, behind their checks of the state: the copies whose destination is not null and that have bytes, one wait
+struct Download {
+  void *to;
+  const dmi::DeviceBuffer &from;
+  uint64_t bytes;
+};
+int download(dmi_context *ctx, std::initializer_list<Download> copies) {
+  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+  for (const Download &c : copies)
+    if (c.to && c.bytes) DMI_HIP(ctx, hipMemcpyAsync(c.to, c.from.ptr, (size_t)c.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return DMI_OK;
+}
 }  // namespace
 
 int dmi::drain_c2p(dmi_context *ctx) {
   if (ctx->c2p.pending) {
     DMI_HIP(ctx, hipEventSynchronize(ctx->c2p.events[1]));
-    float ms = 0.f;
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, ctx->c2p.events[0], ctx->c2p.events[1]));
-    ctx->timings.last_cell_to_point_ms = ms;
+    DMI_HIP(ctx, ctx->c2p.elapsed(0, 1, &ctx->timings.last_cell_to_point_ms));
     ctx->c2p.pending = false;
   }
   dmi_context::PointSmoothing &ps = ctx->point_smoothing;
   if (ps.pending) {  // the smoothing passes that followed it (dmi_set_point_smoothing)
     DMI_HIP(ctx, hipEventSynchronize(ps.events[1]));
-    float ms = 0.f;
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, ps.events[0], ps.events[1]));
-    ps.last_kernel_ms = ms;
+    DMI_HIP(ctx, ps.elapsed(0, 1, &ps.last_kernel_ms));
     ps.pending = false;
   }
   return DMI_OK;
@@ -65,13 +110,11 @@ int dmi_cell_to_point(dmi_context *ctx) {
   if (ps.on) {
     rc = ensure_buffer(ctx, ps.scratch, (uint64_t)n_points(ctx) * 8);
     if (rc != DMI_OK) return rc;
-    if (!ps.events[0])
-      for (hipEvent_t &e : ps.events) DMI_HIP(ctx, hipEventCreate(&e));
+    DMI_HIP(ctx, ps.create());
   }
   double *first = passes % 2 ? ps.scratch.as<double>() : ctx->c2p.points.as<double>();
   double *second = passes % 2 ? ctx->c2p.points.as<double>() : ps.scratch.as<double>();
-  if (!ctx->c2p.events[0])
-    for (hipEvent_t &e : ctx->c2p.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, ctx->c2p.create());
   DMI_HIP(ctx, hipEventRecord(ctx->c2p.events[0], ctx->stream));
   DMI_HIP(ctx, dmi::launch_cell_to_point(ctx->volume.d_grid, ctx->opt.grid_dtype == DMI_F64 ? 1 : 0, first,
                                          ctx->grid.cell_dims[0], ctx->grid.cell_dims[1], ctx->grid.cell_dims[2], ctx->stream));
@@ -164,14 +207,12 @@ int dmi_get_point_smoothing(dmi_context *ctx, double sigma[3], double *truncate)
 }
 
 int dmi_get_point_smoothing_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_point_smoothing_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_point_smoothing_kernel_ms: null argument");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  const int rc = drain_c2p(ctx);
-  if (rc != DMI_OK) return rc;
-  *last = ctx->point_smoothing.on ? ctx->point_smoothing.last_kernel_ms : 0.0;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_point_smoothing_kernel_ms", last,
+                   [](dmi_context &c) { return c.point_smoothing.on ? c.point_smoothing.last_kernel_ms : 0.0; },
+                   [](dmi_context *ctx) -> int {
+                     DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
+                     return drain_c2p(ctx);
+                   });
 }
 
 int dmi_iso_active_cells(dmi_context *ctx, double iso, uint64_t *count, int64_t *cell_ids, uint64_t capacity) {
@@ -247,7 +288,7 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
   mesh.valid = false;
   mesh.has_normals = false;
   mesh.filtered = false;
-  ctx->support.valid = false;  // the counts of an earlier mesh are not this one's
+  mesh.support_counted = false;  // the counts of an earlier mesh are not this one's
   const int nx = ctx->grid.cell_dims[0], ny = ctx->grid.cell_dims[1], nz = ctx->grid.cell_dims[2];
   const size_t n_seg = dmi::isosurface_segment_count(nx, ny, nz);
   if (n_seg >= (size_t(1) << 31)) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": grid too large for one launch");
@@ -275,8 +316,7 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
   temp_bytes = std::max<size_t>(temp_bytes, 16);
   rc = ensure_buffer(ctx, ex.scan_temp, temp_bytes);
   if (rc != DMI_OK) return rc;
-  if (!ex.events[0])
-    for (hipEvent_t &e : ex.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, ex.create());
   // the trailing zeros behind each count array: bases[n_seg] and bases[2 n_seg + 1] become the totals
   DMI_HIP(ctx, hipMemsetAsync(counts + n_seg, 0, sizeof(uint32_t), ctx->stream));
   DMI_HIP(ctx, hipMemsetAsync(counts + 2 * n_seg + 1, 0, sizeof(uint32_t), ctx->stream));
@@ -287,14 +327,12 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
   DMI_HIP(ctx, hipMemcpyAsync(&totals[0], bases + n_seg, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipMemcpyAsync(&totals[1], bases + 2 * n_seg + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  // vertex and triangle ids are int64 (vtkIdType) and the buffers' byte sizes must fit a size_t: refused, never wrapped
-  const uint64_t id_limit = (uint64_t)std::numeric_limits<int64_t>::max() / kVertexBytes;
-  if (totals[0] > id_limit || totals[1] > id_limit)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for int64 ids");
+  rc = refuse_size(ctx, entry, dmi::extraction_refusal(totals[0], totals[1]));
+  if (rc != DMI_OK) return rc;
   g.n_vertices = totals[0];
   g.n_triangles = totals[1];
-  float ms_count = 0.f, ms_write = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms_count, ex.events[0], ex.events[1]));
+  double ms_count = 0.0, ms_write = 0.0;
+  DMI_HIP(ctx, ex.elapsed(0, 1, &ms_count));
   if (totals[0] > 0) {
     rc = ensure_buffers(ctx, {{&mesh.vertices, totals[0] * kVertexBytes}, {&mesh.triangles, totals[1] * kTriangleBytes},
                               {&mesh.normals, normals ? totals[0] * kNormalBytes : 0}});
@@ -309,9 +347,9 @@ int extract_isosurface(dmi_context *ctx, const std::string &entry, double iso, u
                                               normals ? &nrm : nullptr, ctx->stream));
     DMI_HIP(ctx, hipEventRecord(ex.events[3], ctx->stream));
     DMI_HIP(ctx, hipEventSynchronize(ex.events[3]));
-    DMI_HIP(ctx, hipEventElapsedTime(&ms_write, ex.events[2], ex.events[3]));
+    DMI_HIP(ctx, ex.elapsed(2, 3, &ms_write));
   }
-  ex.last_kernel_ms = (double)ms_count + (double)ms_write;
+  ex.last_kernel_ms = ms_count + ms_write;
   mesh.n_vertices = totals[0];
   mesh.n_triangles = totals[1];
   mesh.valid = true;
@@ -341,15 +379,8 @@ int dmi_download_isosurface(dmi_context *ctx, double *vertices, int64_t *triangl
   return guarded(ctx, "dmi_download_isosurface", [&]() -> int {
   if (!ctx || !vertices || !triangles) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: null argument");
   const dmi_context::Mesh &mesh = ctx->mesh;
-  if (!mesh.valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface: no mesh (dmi_extract_isosurface has not succeeded)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (mesh.n_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(vertices, mesh.vertices.ptr, (size_t)(mesh.n_vertices * kVertexBytes), hipMemcpyDeviceToHost, ctx->stream));
-  if (mesh.n_triangles)
-    DMI_HIP(ctx, hipMemcpyAsync(triangles, mesh.triangles.ptr, (size_t)(mesh.n_triangles * kTriangleBytes), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
+  if (int rc = require_mesh(ctx, "dmi_download_isosurface", "dmi_extract_isosurface has not succeeded")) return rc;
+  return download(ctx, {{vertices, mesh.vertices, mesh.n_vertices * kVertexBytes}, {triangles, mesh.triangles, mesh.n_triangles * kTriangleBytes}});
   });
 }
 
@@ -357,25 +388,16 @@ int dmi_download_isosurface_normals(dmi_context *ctx, float *normals) {
   return guarded(ctx, "dmi_download_isosurface_normals", [&]() -> int {
   if (!ctx || !normals) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: null argument");
   const dmi_context::Mesh &mesh = ctx->mesh;
-  if (!mesh.valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_normals: no mesh (no extraction has succeeded)");
+  if (int rc = require_mesh(ctx, "dmi_download_isosurface_normals")) return rc;
   if (!mesh.has_normals)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
                 "dmi_download_isosurface_normals: the last mesh has no normals (dmi_extract_isosurface, not dmi_extract_isosurface_normals)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (mesh.n_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(normals, mesh.normals.ptr, (size_t)(mesh.n_vertices * kNormalBytes), hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
+  return download(ctx, {{normals, mesh.normals, mesh.n_vertices * kNormalBytes}});
   });
 }
 
 int dmi_get_isosurface_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_kernel_ms: null argument");
-  *last = ctx->extraction.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_kernel_ms", last, [](dmi_context &c) { return c.extraction.last_kernel_ms; });
 }
 
 int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_triangles, uint64_t *n_vertices, uint64_t *n_triangles,
@@ -388,20 +410,18 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": unknown mode " + std::to_string(mode));
   dmi_context::Mesh &mesh = ctx->mesh;
   dmi_context::Components &comp = ctx->components;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  int rc = require_mesh(ctx, entry);
+  if (rc != DMI_OK) return rc;
   *n_vertices = *n_triangles = *n_components = *n_components_kept = 0;
   const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
-  // labels and sizes are u32: refused, never wrapped (as the extraction refuses what its int64 ids cannot hold)
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit component labels");
+  rc = refuse_size(ctx, entry, dmi::ids_refusal(nv, nt, "32-bit component labels"));  // labels and sizes are u32
+  if (rc != DMI_OK) return rc;
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
   if (nv == 0) {  // an empty mesh stays empty
+    mesh.drop(dmi::drops::kComponents);
     mesh.filtered = true;
-    mesh.colored = false;
-    ctx->support.valid = false;
     mesh.regions = 0;
-    comp.last_kernel_ms = 0.0;
-    for (double &p : comp.last_pass_ms) p = 0.0;
+    comp.zero();
     comp.last_cas_retries = 0;
     return DMI_OK;
   }
@@ -409,14 +429,14 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   size_t temp_bytes = 0;
   DMI_HIP(ctx, dmi::components_scan_temp_bytes(nv, nt, &temp_bytes));
   temp_bytes = std::max<size_t>(temp_bytes, 16);
-  // the compaction's output, the region arrays, the union-find's scratch (vertex_scratch: 4 u32 arrays of nv + 1) and the scans'
-  int rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&mesh.alt_triangles, std::max<uint64_t>(nt, 1) * kTriangleBytes},
-                                {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&mesh.region_id, nv * 8}, {&mesh.region_size, nv * 8},
-                                {&comp.vertex_scratch, (nv + 1) * 16}, {&comp.triangle_scratch, (nt + 1) * 4}, {&comp.counters, 24},
-                                {&comp.scan_temp, temp_bytes}});
+  // the compaction's output, the region arrays, the union-find's scratch and the scans'
+  dmi::U32Lanes vs{nullptr, nv + 1};
+  rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&mesh.alt_triangles, std::max<uint64_t>(nt, 1) * kTriangleBytes},
+                            {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&mesh.region_id, nv * 8}, {&mesh.region_size, nv * 8},
+                            {&comp.vertex_scratch, vs.bytes(dmi::kComponentsLanes)}, {&comp.triangle_scratch, (nt + 1) * 4},
+                            {&comp.counters, 24}, {&comp.scan_temp, temp_bytes}});
   if (rc != DMI_OK) return rc;
-  if (!comp.events[0])
-    for (hipEvent_t &e : comp.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, comp.create());
   dmi::ComponentsMesh m{};
   m.n_vertices = nv;
   m.n_triangles = nt;
@@ -429,11 +449,11 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   m.region_id = mesh.region_id.as<int64_t>();
   m.region_size = mesh.region_size.as<int64_t>();
   dmi::ComponentsScratch s{};
-  uint32_t *vs = comp.vertex_scratch.as<uint32_t>();
-  s.parent = vs;
-  s.size = vs + (nv + 1);
-  s.vmap = vs + 2 * (nv + 1);
-  s.rmap = vs + 3 * (nv + 1);
+  vs.base = comp.vertex_scratch.as<uint32_t>();
+  s.parent = vs.lane(0);
+  s.size = vs.lane(1);
+  s.vmap = vs.lane(2);
+  s.rmap = vs.lane(3);
   s.tmap = comp.triangle_scratch.as<uint32_t>();
   s.counters = comp.counters.as<unsigned long long>();
   s.scan_temp = comp.scan_temp.ptr;
@@ -447,23 +467,10 @@ int dmi_filter_isosurface_components(dmi_context *ctx, int mode, uint64_t min_tr
   DMI_HIP(ctx, hipMemcpyAsync(&kept[2], s.rmap + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipMemcpyAsync(counters, s.counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, comp.events[0], comp.events[4]));
-  comp.last_kernel_ms = (double)ms;
-  for (int p = 0; p < 4; ++p) {
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, comp.events[p], comp.events[p + 1]));
-    comp.last_pass_ms[p] = (double)ms;
-  }
-  // the compacted mesh becomes the context's mesh; the buffers it came from are the next filter's output
-  std::swap(mesh.vertices, mesh.alt_vertices);
-  std::swap(mesh.triangles, mesh.alt_triangles);
-  if (normals) std::swap(mesh.normals, mesh.alt_normals);
-  mesh.n_vertices = kept[0];
-  mesh.n_triangles = kept[1];
-  mesh.regions = kept[2];
+  DMI_HIP(ctx, comp.read(0, 4));
+  mesh.commit_alternates(kept[0], kept[1], dmi::drops::kComponents);  // the colours and support counts were the unfiltered mesh's
   mesh.filtered = true;
-  mesh.colored = false;  // the colours were the unfiltered mesh's
-  ctx->support.valid = false;  // ... and so were the support counts
+  mesh.regions = kept[2];
   comp.last_cas_retries = counters[2];
   *n_vertices = kept[0];
   *n_triangles = kept[1];
@@ -477,43 +484,24 @@ int dmi_download_isosurface_regions(dmi_context *ctx, int64_t *region_id, int64_
   return guarded(ctx, "dmi_download_isosurface_regions", [&]() -> int {
   if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: null argument");
   const dmi_context::Mesh &mesh = ctx->mesh;
-  if (!mesh.valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_regions: no mesh (no extraction has succeeded)");
+  if (int rc = require_mesh(ctx, "dmi_download_isosurface_regions")) return rc;
   if (!mesh.filtered)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
                 "dmi_download_isosurface_regions: no regions (dmi_filter_isosurface_components has not run since the last extraction)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (region_id && mesh.n_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(region_id, mesh.region_id.ptr, (size_t)mesh.n_vertices * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (region_size && mesh.regions)
-    DMI_HIP(ctx, hipMemcpyAsync(region_size, mesh.region_size.ptr, (size_t)mesh.regions * 8, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
+  return download(ctx, {{region_id, mesh.region_id, mesh.n_vertices * 8}, {region_size, mesh.region_size, mesh.regions * 8}});
   });
 }
 
 int dmi_get_isosurface_filter_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_filter_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_kernel_ms: null argument");
-  *last = ctx->components.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_filter_kernel_ms", last, [](dmi_context &c) { return c.components.last_kernel_ms; });
 }
 
 int dmi_get_isosurface_filter_pass_ms(dmi_context *ctx, double out[4]) {
-  return guarded(ctx, "dmi_get_isosurface_filter_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_pass_ms: null argument");
-  for (int p = 0; p < 4; ++p) out[p] = ctx->components.last_pass_ms[p];
-  return DMI_OK;
-  });
+  return get_passes(ctx, "dmi_get_isosurface_filter_pass_ms", out, &dmi_context::components);
 }
 
 int dmi_get_isosurface_filter_cas_retries(dmi_context *ctx, uint64_t *last) {
-  return guarded(ctx, "dmi_get_isosurface_filter_cas_retries", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_filter_cas_retries: null argument");
-  *last = ctx->components.last_cas_retries;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_filter_cas_retries", last, [](dmi_context &c) { return c.components.last_cas_retries; });
 }
 
 int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, double mu) {
@@ -526,18 +514,15 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   if (!(mu <= 0.0) || mu - mu != 0.0) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mu is not a finite number <= 0");
   dmi_context::Mesh &mesh = ctx->mesh;
   dmi_context::Smoothing &sm = ctx->smoothing;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
   const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
-  // ids are u32 on the device, and so are the offsets into the 6 T directed edges: refused, never wrapped
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
-  if (6 * nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit adjacency offsets (6 x triangles >= 2^32)");
+  int rc = require_mesh(ctx, entry);
+  // ids are u32 on the device, and so are the offsets into the 6 T directed edges
+  if (rc == DMI_OK) rc = refuse_size(ctx, entry, dmi::ids_refusal(nv, nt, "32-bit vertex ids"));
+  if (rc == DMI_OK) rc = refuse_size(ctx, entry, dmi::product_refusal(6, nt, "32-bit adjacency offsets (6 x triangles >= 2^32)"));
+  if (rc != DMI_OK) return rc;
   if (iterations == 0 || nv == 0) {  // nothing to do: the mesh, its normals included, stays as it is
-    sm.last_kernel_ms = 0.0;
-    for (double &p : sm.last_pass_ms) p = 0.0;
-    if (iterations > 0) mesh.colored = false;
-    if (iterations > 0) ctx->support.valid = false;
+    sm.zero();
+    if (iterations > 0) mesh.drop(dmi::drops::kSmoothing);
     return DMI_OK;
   }
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
@@ -546,14 +531,14 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   size_t temp_bytes = 0;
   DMI_HIP(ctx, dmi::smooth_temp_bytes(nv, nt, &temp_bytes));
   temp_bytes = std::max<size_t>(temp_bytes, 16);
-  // the two position buffers of the steps, the new normals, two key arrays, the per-vertex scratch (fixed bits, then 3 u32 arrays
-  // of nv + 1) and the sort's and scans' own storage
-  int rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&sm.vertices, nv * kVertexBytes},
-                                {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&sm.keys, 2 * n_keys * 8},
-                                {&sm.vertex_scratch, fixed_words * 8 + 3 * (nv + 1) * 4}, {&sm.temp, temp_bytes}});
+  // the two position buffers of the steps, the new normals, two key arrays, the per-vertex scratch (fixed bits, then the u32
+  // arrays) and the sort's and scans' own storage
+  dmi::U32Lanes vs{nullptr, nv + 1};
+  rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&sm.vertices, nv * kVertexBytes},
+                            {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&sm.keys, 2 * n_keys * 8},
+                            {&sm.vertex_scratch, fixed_words * 8 + vs.bytes(dmi::kSmoothingLanes)}, {&sm.temp, temp_bytes}});
   if (rc != DMI_OK) return rc;
-  if (!sm.events[0])
-    for (hipEvent_t &e : sm.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, sm.create());
   dmi::SmoothMesh m{};
   m.n_vertices = nv;
   m.n_triangles = nt;
@@ -564,9 +549,10 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   s.keys[0] = sm.keys.as<uint64_t>();
   s.keys[1] = s.keys[0] + n_keys;
   s.fixed = sm.vertex_scratch.as<unsigned long long>();
-  s.row_start = (uint32_t *)(s.fixed + fixed_words);
-  s.valence = s.row_start + (nv + 1);
-  s.offsets = s.valence + (nv + 1);
+  vs.base = (uint32_t *)(s.fixed + fixed_words);
+  s.row_start = vs.lane(0);
+  s.valence = vs.lane(1);
+  s.offsets = vs.lane(2);
   s.positions[0] = mesh.alt_vertices.as<double>();
   s.positions[1] = sm.vertices.as<double>();
   s.temp = sm.temp.ptr;
@@ -575,36 +561,19 @@ int dmi_smooth_isosurface(dmi_context *ctx, int32_t iterations, double lambda, d
   double *result = nullptr;
   DMI_HIP(ctx, dmi::launch_isosurface_smooth(m, s, iterations, lambda, mu, &result, sm.events, ctx->stream));
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, sm.events[0], sm.events[3]));
-  sm.last_kernel_ms = (double)ms;
-  for (int p = 0; p < 3; ++p) {
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, sm.events[p], sm.events[p + 1]));
-    sm.last_pass_ms[p] = (double)ms;
-  }
+  DMI_HIP(ctx, sm.read(0, 3));
   // the smoothed positions become the context's; the buffer they replace is the next call's scratch
-  std::swap(mesh.vertices, result == mesh.alt_vertices.ptr ? mesh.alt_vertices : sm.vertices);
-  if (normals) std::swap(mesh.normals, mesh.alt_normals);
-  mesh.colored = false;  // the colours were those of the positions before
-  ctx->support.valid = false;  // ... and so were the support counts
+  mesh.commit_positions(result == mesh.alt_vertices.ptr ? mesh.alt_vertices : sm.vertices, dmi::drops::kSmoothing);
   return DMI_OK;
   });
 }
 
 int dmi_get_isosurface_smooth_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_smooth_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_kernel_ms: null argument");
-  *last = ctx->smoothing.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_smooth_kernel_ms", last, [](dmi_context &c) { return c.smoothing.last_kernel_ms; });
 }
 
 int dmi_get_isosurface_smooth_pass_ms(dmi_context *ctx, double out[3]) {
-  return guarded(ctx, "dmi_get_isosurface_smooth_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_smooth_pass_ms: null argument");
-  for (int p = 0; p < 3; ++p) out[p] = ctx->smoothing.last_pass_ms[p];
-  return DMI_OK;
-  });
+  return get_passes(ctx, "dmi_get_isosurface_smooth_pass_ms", out, &dmi_context::smoothing);
 }
 
 namespace {
@@ -613,18 +582,12 @@ int drain_decimation(dmi_context *ctx) {
   dmi_context::Decimation &dc = ctx->decimation;
   if (!dc.pending) return DMI_OK;
   DMI_HIP(ctx, hipEventSynchronize(dc.events[dc.pending_normals ? 7 : 5]));
-  auto elapsed = [&](int a, int b, double *out) -> hipError_t {
-    float ms = 0.f;
-    const hipError_t e = hipEventElapsedTime(&ms, dc.events[a], dc.events[b]);
-    *out = (double)ms;
-    return e;
-  };
   double bounds = 0.0, ranks = 0.0, triangles = 0.0, representatives = 0.0, normals = 0.0;
-  DMI_HIP(ctx, elapsed(0, 1, &bounds));
-  DMI_HIP(ctx, elapsed(2, 3, &ranks));
-  DMI_HIP(ctx, elapsed(3, 4, &triangles));
-  DMI_HIP(ctx, elapsed(4, 5, &representatives));
-  if (dc.pending_normals) DMI_HIP(ctx, elapsed(6, 7, &normals));
+  DMI_HIP(ctx, dc.elapsed(0, 1, &bounds));
+  DMI_HIP(ctx, dc.elapsed(2, 3, &ranks));
+  DMI_HIP(ctx, dc.elapsed(3, 4, &triangles));
+  DMI_HIP(ctx, dc.elapsed(4, 5, &representatives));
+  if (dc.pending_normals) DMI_HIP(ctx, dc.elapsed(6, 7, &normals));
   dc.last_pass_ms[0] = bounds + ranks;
   dc.last_pass_ms[1] = representatives;
   dc.last_pass_ms[2] = triangles;
@@ -655,23 +618,19 @@ int decimate_isosurface(dmi_context *ctx, const char *name, double cell_size, in
   dmi_context::Mesh &mesh = ctx->mesh;
   dmi_context::Decimation &dc = ctx->decimation;
   dmi_context::Smoothing &sm = ctx->smoothing;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
   const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
-  // ids are u32 on the device: refused, never wrapped
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
-  if (quadric && 3 * nt >= (uint64_t(1) << 32))  // ... nor are the corner indices 3t + e
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit corner indices (3 T >= 2^32)");
+  int rc = require_mesh(ctx, entry);
+  // ids are u32 on the device, and so are the quadric placement's corner indices 3t + e
+  if (rc == DMI_OK) rc = refuse_size(ctx, entry, dmi::ids_refusal(nv, nt, "32-bit vertex ids"));
+  if (rc == DMI_OK && quadric) rc = refuse_size(ctx, entry, dmi::product_refusal(3, nt, "32-bit corner indices (3 T >= 2^32)"));
+  if (rc != DMI_OK) return rc;
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  int rc = drain_decimation(ctx);  // (the events are about to be recorded again)
+  rc = drain_decimation(ctx);  // (the events are about to be recorded again)
   if (rc != DMI_OK) return rc;
   *n_vertices = *n_triangles = 0;
   if (nv == 0) {  // an empty mesh stays empty (it has no triangles either)
-    mesh.filtered = false;
-    mesh.colored = false;
-    ctx->support.valid = false;
-    dc.last_kernel_ms = 0.0;
-    for (double &p : dc.last_pass_ms) p = 0.0;
+    mesh.drop(dmi::drops::kDecimation);
+    dc.zero();
     return DMI_OK;
   }
   const bool normals = mesh.has_normals;
@@ -683,13 +642,13 @@ int decimate_isosurface(dmi_context *ctx, const char *name, double cell_size, in
   // incidence of the normals (the smoother's key arrays), the per-vertex and per-triangle u32 arrays, rocPRIM's own storage; the
   // quadric placement's corner pairs and their sort's other halves are 3T u64 in each key array too
   const uint64_t n_keys = std::max<uint64_t>(std::max(nv, 2 * nt), normals || quadric ? 3 * nt : 0);
+  dmi::U32Lanes vs{nullptr, nv + 1}, ts{nullptr, nt + 1};
   rc = ensure_buffers(ctx, {{&mesh.alt_vertices, nv * kVertexBytes}, {&mesh.alt_triangles, std::max<uint64_t>(nt, 1) * kTriangleBytes},
                             {&mesh.alt_normals, normals ? nv * kNormalBytes : 0}, {&sm.keys, 2 * n_keys * 8},
-                            {&dc.vertex_scratch, 8 * (nv + 1) * 4}, {&dc.triangle_scratch, 2 * (nt + 1) * 4}, {&dc.bounds, 64},
-                            {&sm.temp, temp_bytes}});
+                            {&dc.vertex_scratch, vs.bytes(dmi::kDecimationLanes)},
+                            {&dc.triangle_scratch, ts.bytes(dmi::kDecimationTriangleLanes)}, {&dc.bounds, 64}, {&sm.temp, temp_bytes}});
   if (rc != DMI_OK) return rc;
-  if (!dc.events[0])
-    for (hipEvent_t &e : dc.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, dc.create());
   dmi::DecimateMesh m{};
   m.n_vertices = nv;
   m.n_triangles = nt;
@@ -701,17 +660,18 @@ int decimate_isosurface(dmi_context *ctx, const char *name, double cell_size, in
   s.bounds = dc.bounds.as<unsigned long long>();
   s.keys[0] = sm.keys.as<uint64_t>();
   s.keys[1] = s.keys[0] + n_keys;
-  uint32_t *vs = dc.vertex_scratch.as<uint32_t>();
-  s.ids[0] = vs;
-  s.ids[1] = vs + (nv + 1);
-  s.head = vs + 2 * (nv + 1);
-  s.rank = vs + 3 * (nv + 1);
-  s.cluster_of = vs + 4 * (nv + 1);
-  s.start = vs + 5 * (nv + 1);
-  s.mark = vs + 6 * (nv + 1);
-  s.cmap = vs + 7 * (nv + 1);
-  s.keep = dc.triangle_scratch.as<uint32_t>();
-  s.tmap = s.keep + (nt + 1);
+  vs.base = dc.vertex_scratch.as<uint32_t>();
+  s.ids[0] = vs.lane(0);
+  s.ids[1] = vs.lane(1);
+  s.head = vs.lane(2);
+  s.rank = vs.lane(3);
+  s.cluster_of = vs.lane(4);
+  s.start = vs.lane(5);
+  s.mark = vs.lane(6);
+  s.cmap = vs.lane(7);
+  ts.base = dc.triangle_scratch.as<uint32_t>();
+  s.keep = ts.lane(0);
+  s.tmap = ts.lane(1);
   s.temp = sm.temp.ptr;
   s.temp_bytes = temp_bytes;
   // (a failure from here on leaves the context's mesh, its normals and its regions as they were: no kernel writes them, and the
@@ -756,16 +716,7 @@ int decimate_isosurface(dmi_context *ctx, const char *name, double cell_size, in
   }
   dc.pending = true;
   dc.pending_normals = new_normals;
-  // the decimated mesh becomes the context's; the buffers it came from are the next call's output
-  std::swap(mesh.vertices, mesh.alt_vertices);
-  std::swap(mesh.triangles, mesh.alt_triangles);
-  if (normals) std::swap(mesh.normals, mesh.alt_normals);
-  mesh.n_vertices = kept[0];
-  mesh.n_triangles = kept[1];
-  mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
-  mesh.regions = 0;
-  mesh.colored = false;   // ... nor are the colours
-  ctx->support.valid = false;  // ... nor the support counts
+  mesh.commit_alternates(kept[0], kept[1], dmi::drops::kDecimation);
   *n_vertices = kept[0];
   *n_triangles = kept[1];
   return DMI_OK;
@@ -783,23 +734,12 @@ int dmi_decimate_isosurface_placed(dmi_context *ctx, double cell_size, int32_t p
 }
 
 int dmi_get_isosurface_decimate_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_decimate_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_decimate_kernel_ms: null argument");
-  const int rc = drain_decimation(ctx);
-  if (rc != DMI_OK) return rc;
-  *last = ctx->decimation.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_decimate_kernel_ms", last, [](dmi_context &c) { return c.decimation.last_kernel_ms; },
+                   drain_decimation);
 }
 
 int dmi_get_isosurface_decimate_pass_ms(dmi_context *ctx, double out[4]) {
-  return guarded(ctx, "dmi_get_isosurface_decimate_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_decimate_pass_ms: null argument");
-  const int rc = drain_decimation(ctx);
-  if (rc != DMI_OK) return rc;
-  for (int p = 0; p < 4; ++p) out[p] = ctx->decimation.last_pass_ms[p];
-  return DMI_OK;
-  });
+  return get_passes(ctx, "dmi_get_isosurface_decimate_pass_ms", out, &dmi_context::decimation, drain_decimation);
 }
 
 int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_vertices, uint64_t *n_triangles, uint64_t *n_filled,
@@ -812,18 +752,15 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
   dmi_context::Mesh &mesh = ctx->mesh;
   dmi_context::Holes &ho = ctx->holes;
   dmi_context::Smoothing &sm = ctx->smoothing;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
   const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
-  // ids are u32 on the device, and so are the positions among the sorted edge keys: refused, never wrapped
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
-  if (6 * nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit edge positions (6 x triangles >= 2^32)");
-  if (nv >= (uint64_t(1) << 31))  // an edge key is two ids and the direction bit in 64 bits
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for the edge keys' direction bit (vertices >= 2^31)");
+  int rc = require_mesh(ctx, entry);
+  // ids are u32 on the device, and so are the positions among the sorted edge keys
+  if (rc == DMI_OK) rc = refuse_size(ctx, entry, dmi::ids_refusal(nv, nt, "32-bit vertex ids"));
+  if (rc == DMI_OK) rc = refuse_size(ctx, entry, dmi::product_refusal(6, nt, "32-bit edge positions (6 x triangles >= 2^32)"));
+  if (rc == DMI_OK) rc = refuse_size(ctx, entry, dmi::direction_bit_refusal(nv));
+  if (rc != DMI_OK) return rc;
   auto nothing = [&](uint64_t left) {  // the mesh, its regions, its support counts and its colours stay as they are
-    ho.last_kernel_ms = 0.0;
-    for (double &p : ho.last_pass_ms) p = 0.0;
+    ho.zero();
     *n_vertices = nv;
     *n_triangles = nt;
     if (n_filled) *n_filled = 0;
@@ -837,10 +774,10 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
   DMI_HIP(ctx, dmi::holes_temp_bytes(nv, nt, &temp_bytes));
   temp_bytes = std::max<size_t>(temp_bytes, 16);
   const uint64_t n_keys = std::max<uint64_t>(3 * nt, 2);
-  int rc = ensure_buffers(ctx, {{&sm.keys, 2 * n_keys * 8}, {&ho.vertex_scratch, 5 * (nv + 1) * 4}, {&ho.counters, 32}, {&sm.temp, temp_bytes}});
+  dmi::U32Lanes vp{nullptr, nv + 1};
+  rc = ensure_buffers(ctx, {{&sm.keys, 2 * n_keys * 8}, {&ho.vertex_scratch, vp.bytes(dmi::kHolesLanes)}, {&ho.counters, 32}, {&sm.temp, temp_bytes}});
   if (rc != DMI_OK) return rc;
-  if (!ho.events[0])
-    for (hipEvent_t &e : ho.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, ho.create());
   dmi::HolesMesh m{};
   m.n_vertices = nv;
   m.n_triangles = nt;
@@ -848,12 +785,12 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
   m.triangles = mesh.triangles.as<int64_t>();
   m.normals = normals ? mesh.normals.as<float>() : nullptr;
   dmi::HolesVertexScratch vs{};
-  uint32_t *vp = ho.vertex_scratch.as<uint32_t>();
-  vs.out_deg = vp;
-  vs.in_deg = vp + (nv + 1);
-  vs.succ = vp + 2 * (nv + 1);
-  vs.flag = vp + 3 * (nv + 1);
-  vs.rank = vp + 4 * (nv + 1);
+  vp.base = ho.vertex_scratch.as<uint32_t>();
+  vs.out_deg = vp.lane(0);
+  vs.in_deg = vp.lane(1);
+  vs.succ = vp.lane(2);
+  vs.flag = vp.lane(3);
+  vs.rank = vp.lane(4);
   uint64_t *const keys[2] = {sm.keys.as<uint64_t>(), sm.keys.as<uint64_t>() + n_keys};
   unsigned long long *counters = ho.counters.as<unsigned long long>();
   // (a failure from here on leaves the context's mesh as it was: no kernel writes it, and the buffers are swapped only at the end)
@@ -865,22 +802,22 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the first of three: the boundary vertices
   const uint64_t boundary_edges = counts[0];
   if (max_edges < 3 || n_slots == 0) return nothing(boundary_edges);
-  rc = ensure_buffer(ctx, ho.loop_scratch, 11 * ((uint64_t)n_slots + 1) * 4);
+  dmi::U32Lanes lp{nullptr, (uint64_t)n_slots + 1};
+  rc = ensure_buffer(ctx, ho.loop_scratch, lp.bytes(dmi::kHolesLoopLanes));
   if (rc != DMI_OK) return rc;
   dmi::HolesLoopScratch ls{};
-  uint32_t *lp = ho.loop_scratch.as<uint32_t>();
-  const uint64_t pitch = (uint64_t)n_slots + 1;
-  ls.id = lp;
-  ls.next = lp + pitch;
-  ls.ptr[0] = lp + 2 * pitch;
-  ls.ptr[1] = lp + 3 * pitch;
-  ls.label[0] = lp + 4 * pitch;
-  ls.label[1] = lp + 5 * pitch;
-  ls.count = lp + 6 * pitch;
-  ls.new_vertices = lp + 7 * pitch;
-  ls.new_triangles = lp + 8 * pitch;
-  ls.vertex_offset = lp + 9 * pitch;
-  ls.triangle_offset = lp + 10 * pitch;
+  lp.base = ho.loop_scratch.as<uint32_t>();
+  ls.id = lp.lane(0);
+  ls.next = lp.lane(1);
+  ls.ptr[0] = lp.lane(2);
+  ls.ptr[1] = lp.lane(3);
+  ls.label[0] = lp.lane(4);
+  ls.label[1] = lp.lane(5);
+  ls.count = lp.lane(6);
+  ls.new_vertices = lp.lane(7);
+  ls.new_triangles = lp.lane(8);
+  ls.vertex_offset = lp.lane(9);
+  ls.triangle_offset = lp.lane(10);
   DMI_HIP(ctx, dmi::launch_holes_loops(m, vs, ls, n_slots, max_edges, sm.temp.ptr, temp_bytes, counters, ho.events[2], ctx->stream));
   uint32_t added[2] = {0, 0};
   DMI_HIP(ctx, hipMemcpyAsync(&added[0], ls.vertex_offset + n_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -889,8 +826,8 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the second: what the fill adds
   if (counts[1] == 0) return nothing(boundary_edges);
   const uint64_t out_nv = nv + added[0], out_nt = nt + added[1];
-  if (out_nv >= (uint64_t(1) << 32) || out_nt >= (uint64_t(1) << 32) || 6 * out_nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the filled mesh would be too large for 32-bit ids (vertices or 6 x triangles >= 2^32)");
+  rc = refuse_size(ctx, entry, dmi::filled_refusal(out_nv, out_nt));
+  if (rc != DMI_OK) return rc;
   rc = ensure_buffers(ctx, {{&mesh.alt_vertices, out_nv * kVertexBytes}, {&mesh.alt_triangles, out_nt * kTriangleBytes},
                             {&mesh.alt_normals, normals ? out_nv * kNormalBytes : 0}});
   if (rc != DMI_OK) return rc;
@@ -902,23 +839,8 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
   DMI_HIP(ctx, hipMemcpyAsync(counts, counters, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the third: the filled mesh
   if (counts[3]) return fail(ctx, DMI_ERR_STATE, entry + ": a loop's walk did not close (the mesh is left as it was)");
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, ho.events[0], ho.events[3]));
-  ho.last_kernel_ms = (double)ms;
-  for (int p = 0; p < 3; ++p) {
-    DMI_HIP(ctx, hipEventElapsedTime(&ms, ho.events[p], ho.events[p + 1]));
-    ho.last_pass_ms[p] = (double)ms;
-  }
-  // the filled mesh becomes the context's; the buffers it came from are the next call's output
-  std::swap(mesh.vertices, mesh.alt_vertices);
-  std::swap(mesh.triangles, mesh.alt_triangles);
-  if (normals) std::swap(mesh.normals, mesh.alt_normals);
-  mesh.n_vertices = out_nv;
-  mesh.n_triangles = out_nt;
-  mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
-  mesh.regions = 0;
-  mesh.colored = false;   // ... nor are the colours
-  ctx->support.valid = false;  // ... nor the support counts
+  DMI_HIP(ctx, ho.read(0, 3));
+  mesh.commit_alternates(out_nv, out_nt, dmi::drops::kFill);
   *n_vertices = out_nv;
   *n_triangles = out_nt;
   if (n_filled) *n_filled = counts[1];
@@ -928,19 +850,11 @@ int dmi_fill_isosurface_holes(dmi_context *ctx, uint64_t max_edges, uint64_t *n_
 }
 
 int dmi_get_isosurface_holes_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_holes_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_holes_kernel_ms: null argument");
-  *last = ctx->holes.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_holes_kernel_ms", last, [](dmi_context &c) { return c.holes.last_kernel_ms; });
 }
 
 int dmi_get_isosurface_holes_pass_ms(dmi_context *ctx, double out[3]) {
-  return guarded(ctx, "dmi_get_isosurface_holes_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_holes_pass_ms: null argument");
-  for (int p = 0; p < 3; ++p) out[p] = ctx->holes.last_pass_ms[p];
-  return DMI_OK;
-  });
+  return get_passes(ctx, "dmi_get_isosurface_holes_pass_ms", out, &dmi_context::holes);
 }
 
 int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double tolerance, int32_t require_facing, uint64_t *n_vertices,
@@ -953,21 +867,20 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the tolerance must be finite and >= 0");
   dmi_context::Mesh &mesh = ctx->mesh;
   dmi_context::Support &sup = ctx->support;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  int rc = require_mesh(ctx, entry);
+  if (rc != DMI_OK) return rc;
   const bool facing = require_facing != 0;
   if (facing && !mesh.has_normals)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": require_facing needs the mesh's normals (dmi_extract_isosurface_normals)");
   const uint64_t nv = mesh.n_vertices, nt = mesh.n_triangles;
-  // the maps of the compaction are u32: refused, never wrapped
-  if (nv >= (uint64_t(1) << 32) || nt >= (uint64_t(1) << 32))
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": mesh too large for 32-bit vertex ids");
+  rc = refuse_size(ctx, entry, dmi::ids_refusal(nv, nt, "32-bit vertex ids"));  // the maps of the compaction are u32
+  if (rc != DMI_OK) return rc;
   const size_t n_views = ctx->views.h_maps.size();
   if (n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident (call dmi_add_views first)");
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
   if (nv == 0) {  // an empty mesh stays empty, and its counts are empty
-    sup.valid = true;
-    sup.last_kernel_ms = 0.0;
-    for (double &p : sup.last_pass_ms) p = 0.0;
+    mesh.support_counted = true;
+    sup.zero();
     *n_vertices = 0;
     *n_triangles = nt;
     return DMI_OK;
@@ -981,15 +894,15 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   }
   // the counts and the views' records; for a trim also the result's buffers (the component filter's alternates), the compacted
   // counts, the per-vertex and per-triangle u32 arrays and the scans' own storage
-  int rc = ensure_buffers(ctx, {{&sup.work, nv * 4}, {&sup.maps, (uint64_t)n_views * sizeof(dmi::MapRec)},
-                                {&mesh.alt_vertices, trim ? nv * kVertexBytes : 0},
-                                {&mesh.alt_triangles, trim ? std::max<uint64_t>(nt, 1) * kTriangleBytes : 0},
-                                {&mesh.alt_normals, trim && normals ? nv * kNormalBytes : 0}, {&sup.compacted, trim ? nv * 4 : 0},
-                                {&sup.vertex_scratch, trim ? 2 * (nv + 1) * 4 : 0}, {&sup.triangle_scratch, trim ? (nt + 1) * 4 : 0},
-                                {&sup.scan_temp, trim ? temp_bytes : 0}});
+  dmi::U32Lanes vs{nullptr, nv + 1};
+  rc = ensure_buffers(ctx, {{&sup.work, nv * 4}, {&sup.maps, (uint64_t)n_views * sizeof(dmi::MapRec)},
+                            {&mesh.alt_vertices, trim ? nv * kVertexBytes : 0},
+                            {&mesh.alt_triangles, trim ? std::max<uint64_t>(nt, 1) * kTriangleBytes : 0},
+                            {&mesh.alt_normals, trim && normals ? nv * kNormalBytes : 0}, {&sup.compacted, trim ? nv * 4 : 0},
+                            {&sup.vertex_scratch, trim ? vs.bytes(dmi::kSupportLanes) : 0}, {&sup.triangle_scratch, trim ? (nt + 1) * 4 : 0},
+                            {&sup.scan_temp, trim ? temp_bytes : 0}});
   if (rc != DMI_OK) return rc;
-  if (!sup.events[0])
-    for (hipEvent_t &e : sup.events) DMI_HIP(ctx, hipEventCreate(&e));
+  DMI_HIP(ctx, sup.create());
   dmi::SupportMesh m{};
   m.n_vertices = nv;
   m.n_triangles = nt;
@@ -1008,8 +921,9 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   dmi::SupportScratch s{};
   s.support = sup.work.as<int32_t>();
   s.out_support = sup.compacted.as<int32_t>();
-  s.mark = sup.vertex_scratch.as<uint32_t>();
-  s.vmap = trim ? s.mark + (nv + 1) : nullptr;
+  vs.base = sup.vertex_scratch.as<uint32_t>();
+  s.mark = vs.lane(0);
+  s.vmap = trim ? vs.lane(1) : nullptr;
   s.tmap = sup.triangle_scratch.as<uint32_t>();
   s.scan_temp = sup.scan_temp.ptr;
   s.scan_temp_bytes = temp_bytes;
@@ -1029,29 +943,14 @@ int dmi_filter_isosurface_support(dmi_context *ctx, int32_t min_views, double to
   }
   DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int n_passes = trim ? 3 : 1;
-  float ms = 0.f;
-  DMI_HIP(ctx, hipEventElapsedTime(&ms, sup.events[0], sup.events[n_passes]));
-  sup.last_kernel_ms = (double)ms;
-  for (int p = 0; p < 3; ++p) {
-    ms = 0.f;
-    if (p < n_passes) DMI_HIP(ctx, hipEventElapsedTime(&ms, sup.events[p], sup.events[p + 1]));
-    sup.last_pass_ms[p] = (double)ms;
-  }
-  if (kept[0] != nv || kept[1] != nt) {
-    // the compacted mesh becomes the context's; the buffers it came from are the next call's output
-    std::swap(mesh.vertices, mesh.alt_vertices);
-    std::swap(mesh.triangles, mesh.alt_triangles);
-    if (normals) std::swap(mesh.normals, mesh.alt_normals);
+  DMI_HIP(ctx, sup.read(0, n_passes, n_passes));
+  if (kept[0] != nv || kept[1] != nt) {  // the compacted mesh becomes the context's, and its counts with it
+    mesh.commit_alternates(kept[0], kept[1], dmi::drops::kSupportTrim);
     std::swap(sup.counts, sup.compacted);
-    mesh.n_vertices = kept[0];
-    mesh.n_triangles = kept[1];
-    mesh.filtered = false;  // the regions of an earlier filter are not this mesh's
-    mesh.regions = 0;
-    mesh.colored = false;   // ... nor are the colours
-  } else {
-    std::swap(sup.counts, sup.work);  // nothing went: the mesh, its regions and its colours stay
+  } else {  // nothing went: the mesh, its regions and its colours stay
+    std::swap(sup.counts, sup.work);
   }
-  sup.valid = true;
+  mesh.support_counted = true;
   *n_vertices = kept[0];
   *n_triangles = kept[1];
   return DMI_OK;
@@ -1062,33 +961,20 @@ int dmi_download_isosurface_support(dmi_context *ctx, int32_t *support) {
   return guarded(ctx, "dmi_download_isosurface_support", [&]() -> int {
   if (!ctx || !support) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_support: null argument");
   const dmi_context::Mesh &mesh = ctx->mesh;
-  if (!mesh.valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_support: no mesh (no extraction has succeeded)");
-  if (!ctx->support.valid)
+  if (int rc = require_mesh(ctx, "dmi_download_isosurface_support")) return rc;
+  if (!mesh.support_counted)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
                 "dmi_download_isosurface_support: no counts (dmi_filter_isosurface_support has not run since the mesh last changed)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (mesh.n_vertices)
-    DMI_HIP(ctx, hipMemcpyAsync(support, ctx->support.counts.ptr, (size_t)mesh.n_vertices * 4, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
+  return download(ctx, {{support, ctx->support.counts, mesh.n_vertices * 4}});
   });
 }
 
 int dmi_get_isosurface_support_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_support_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_support_kernel_ms: null argument");
-  *last = ctx->support.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_support_kernel_ms", last, [](dmi_context &c) { return c.support.last_kernel_ms; });
 }
 
 int dmi_get_isosurface_support_pass_ms(dmi_context *ctx, double out[3]) {
-  return guarded(ctx, "dmi_get_isosurface_support_pass_ms", [&]() -> int {
-  if (!ctx || !out) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_support_pass_ms: null argument");
-  for (int p = 0; p < 3; ++p) out[p] = ctx->support.last_pass_ms[p];
-  return DMI_OK;
-  });
+  return get_passes(ctx, "dmi_get_isosurface_support_pass_ms", out, &dmi_context::support);
 }
 
 int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t fused_depth_test, double tolerance, uint64_t *n_vertices) {
@@ -1096,8 +982,8 @@ int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t
   const std::string entry = "dmi_color_process_isosurface";
   if (!c || !ctx || !n_vertices) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
   dmi_context::Mesh &mesh = ctx->mesh;
-  dmi_context::Coloration &col = ctx->coloration;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  dmi::StageTimes<1> &col = ctx->coloration;
+  if (int rc = require_mesh(ctx, entry)) return rc;
   const dmi::ColorContextShape views = dmi::color_context_shape(c);
   if (views.device != ctx->opt.device)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the colour context is on device " + std::to_string(views.device) + ", the mesh on device " +
@@ -1121,8 +1007,7 @@ int dmi_color_process_isosurface(dmi_color_context *c, dmi_context *ctx, int32_t
     // the results are built in the alternates and swapped in last: a call that fails leaves the previous colours in place
     int rc = ensure_buffers(ctx, {{&mesh.alt_color_mean, nv * 3}, {&mesh.alt_color_median, nv * 3}, {&mesh.alt_color_count, nv * 4}});
     if (rc != DMI_OK) return rc;
-    if (!col.events[0])
-      for (hipEvent_t &e : col.events) DMI_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    DMI_HIP(ctx, col.create(hipEventDisableTiming));
     // whatever is still queued on this context's stream (a decimation's normals) comes first
     DMI_HIP(ctx, hipEventRecord(col.events[0], ctx->stream));
     std::vector<const void *> tables;
@@ -1159,16 +1044,15 @@ int dmi_color_render_isosurface_depths(dmi_color_context *c, dmi_context *ctx) {
   const std::string entry = "dmi_color_render_isosurface_depths";
   if (!c || !ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": null argument");
   dmi_context::Mesh &mesh = ctx->mesh;
-  dmi_context::Coloration &col = ctx->coloration;
-  if (!mesh.valid) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": no mesh (no extraction has succeeded)");
+  dmi::StageTimes<1> &col = ctx->coloration;
+  if (int rc = require_mesh(ctx, entry)) return rc;
   const dmi::ColorContextShape views = dmi::color_context_shape(c);
   if (views.device != ctx->opt.device)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT, entry + ": the colour context is on device " + std::to_string(views.device) + ", the mesh on device " +
                                                    std::to_string(ctx->opt.device));
   if (views.n_views == 0) return fail(ctx, DMI_ERR_STATE, entry + ": no views resident in the colour context");
   DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  if (!col.events[0])
-    for (hipEvent_t &e : col.events) DMI_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  DMI_HIP(ctx, col.create(hipEventDisableTiming));
   // whatever is still queued on this context's stream (a decimation's normals) comes first
   DMI_HIP(ctx, hipEventRecord(col.events[0], ctx->stream));
   const int rc = dmi::color_render_device_mesh(c, mesh.vertices.as<double>(), (int64_t)mesh.n_vertices, mesh.triangles.as<int64_t>(),
@@ -1182,27 +1066,17 @@ int dmi_download_isosurface_colors(dmi_context *ctx, uint8_t *mean, uint8_t *med
   return guarded(ctx, "dmi_download_isosurface_colors", [&]() -> int {
   if (!ctx) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_colors: null argument");
   const dmi_context::Mesh &mesh = ctx->mesh;
-  if (!mesh.valid)
-    return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_download_isosurface_colors: no mesh (no extraction has succeeded)");
+  if (int rc = require_mesh(ctx, "dmi_download_isosurface_colors")) return rc;
   if (!mesh.colored)
     return fail(ctx, DMI_ERR_INVALID_ARGUMENT,
                 "dmi_download_isosurface_colors: no colours (dmi_color_process_isosurface has not run since the mesh last changed)");
-  DMI_HIP(ctx, hipSetDevice(ctx->opt.device));
-  const size_t nv = (size_t)mesh.n_vertices;
-  if (mean && nv) DMI_HIP(ctx, hipMemcpyAsync(mean, mesh.color_mean.ptr, nv * 3, hipMemcpyDeviceToHost, ctx->stream));
-  if (median && nv) DMI_HIP(ctx, hipMemcpyAsync(median, mesh.color_median.ptr, nv * 3, hipMemcpyDeviceToHost, ctx->stream));
-  if (count && nv) DMI_HIP(ctx, hipMemcpyAsync(count, mesh.color_count.ptr, nv * 4, hipMemcpyDeviceToHost, ctx->stream));
-  DMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return DMI_OK;
+  const uint64_t nv = mesh.n_vertices;
+  return download(ctx, {{mean, mesh.color_mean, nv * 3}, {median, mesh.color_median, nv * 3}, {count, mesh.color_count, nv * 4}});
   });
 }
 
 int dmi_get_isosurface_color_kernel_ms(dmi_context *ctx, double *last) {
-  return guarded(ctx, "dmi_get_isosurface_color_kernel_ms", [&]() -> int {
-  if (!ctx || !last) return fail(ctx, DMI_ERR_INVALID_ARGUMENT, "dmi_get_isosurface_color_kernel_ms: null argument");
-  *last = ctx->coloration.last_kernel_ms;
-  return DMI_OK;
-  });
+  return get_value(ctx, "dmi_get_isosurface_color_kernel_ms", last, [](dmi_context &c) { return c.coloration.last_kernel_ms; });
 }
 
 }  // extern "C"

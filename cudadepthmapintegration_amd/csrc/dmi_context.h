@@ -1,11 +1,13 @@
 // dmi_context.h -- the context behind the C ABI of include/dmi.h, in groups, and the helpers its translation units share
 // (dmi_capi.hip: creation, destruction, grid transfer, info, timings, probes; dmi_capi_views.hip: the resident views;
 // dmi_capi_fuse.hip: the fusion launch and the diagnostics that read it; dmi_capi_mesh.hip: point data and the iso-surface).  Every device allocation is a dmi::DeviceBuffer
-// (dmi_buffer.h, capacity in bytes) grown by one of two rules, every group has a release().  The colour context
+// (dmi_buffer.h, capacity in bytes) grown by one of two rules, every group has a release().  The mesh's state, the stages' events
+// and times and what else the mesh stages share are dmi_mesh_stage.h's.  The colour context
 // (dmi_color_context.h, dmi_capi_color.hip) is built from the same parts and exception guard.  Private: never installed.
 #pragma once
 #include "../../include/dmi.h"
 #include "dmi_buffer.h"
+#include "dmi_mesh_stage.h"
 #include "fusion_kernels.h"
 
 #include <exception>
@@ -32,14 +34,6 @@ struct EventPair {
   hipEvent_t mid = nullptr;  // recorded just before the fusion kernel proper (after cz table, classification, ordering)
   bool has_mid = false;
 };
-
-template <size_t N>
-void destroy_events(hipEvent_t (&events)[N]) {
-  for (hipEvent_t &e : events) {
-    if (e) (void)hipEventDestroy(e);
-    e = nullptr;
-  }
-}
 }  // namespace dmi
 
 struct dmi_context {
@@ -148,115 +142,79 @@ struct dmi_context {
   } last;
 
   // ---- post-processing (dmi_capi_mesh.hip): every buffer is kept while large enough, every capacity is in bytes ----
-  struct CellToPoint {
+  // Every group with events derives from dmi::StageTimes<events, passes> (dmi_mesh_stage.h): the events, created at the first
+  // call that needs them, last_kernel_ms and, where the stage has passes, last_pass_ms
+  struct CellToPoint : dmi::StageTimes<2> {  // start, stop; the time is timings.last_cell_to_point_ms
     dmi::DeviceBuffer points;  // vtkCellDataToPointData of the grid, (nx+1)(ny+1)(nz+1) f64 (grid_post.hip)
     bool valid = false;        // points matches the grid's current contents
-    hipEvent_t events[2] = {nullptr, nullptr};  // start, stop
     bool pending = false;
-    void release() { dmi::free_buffers({&points}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&points}); StageTimes::release(); }
   } c2p;
   // dmi_set_point_smoothing (point_smooth.hip): while `on`, every computation of c2p.points is followed by the smoothing passes
   // and c2p.points holds their result
-  struct PointSmoothing {
+  struct PointSmoothing : dmi::StageTimes<2> {  // start, stop around the smoothing kernels of the last recomputation; 0 when off
     double sigma[3] = {0.0, 0.0, 0.0}, truncate = 3.0;
     bool on = false;             // some sigma is not 0
     dmi::PointSmoothArgs args{}; // the radii and weights of the setting
     dmi::DeviceBuffer scratch;   // the passes' second buffer, of the point data's size; held only while on
-    hipEvent_t events[2] = {nullptr, nullptr};  // start, stop around the smoothing kernels
     bool pending = false;
-    double last_kernel_ms = 0.0;  // of the last recomputation; 0 when off
-    void release() { dmi::free_buffers({&scratch}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&scratch}); StageTimes::release(); }
   } point_smoothing;
-  // The mesh of the last extraction, as the support trim, the filter, the smoother and the decimation have left it.  The filter and the decimation
-  // write into the alternates and the smoother steps through alt_vertices and smoothing.vertices (normals into alt_normals);
-  // whichever holds the result is then swapped with the mesh's own buffer.
-  struct Mesh {
-    dmi::DeviceBuffer vertices, triangles, normals;  // [n][3] f64, [n][3] int64, [n][3] f32
-    dmi::DeviceBuffer alt_vertices, alt_triangles, alt_normals;
-    dmi::DeviceBuffer region_id, region_size;  // int64 per vertex / per kept component, of the last filter
-    uint64_t n_vertices = 0, n_triangles = 0;
-    uint64_t regions = 0;      // kept components of that filter
-    bool valid = false;
-    bool has_normals = false;  // the last successful extraction wrote them
-    bool filtered = false;     // a filter has run since the last extraction or decimation: the region arrays are the mesh's
-    // dmi_color_process_isosurface's results, [n][3] u8, [n][3] u8, [n] int32; written into the alternates and swapped in last
-    dmi::DeviceBuffer color_mean, color_median, color_count;
-    dmi::DeviceBuffer alt_color_mean, alt_color_median, alt_color_count;
-    bool colored = false;      // the colour arrays describe this mesh (dropped by whatever changes it)
-    void release() {
-      dmi::free_buffers({&vertices, &triangles, &normals, &alt_vertices, &alt_triangles, &alt_normals, &region_id, &region_size,
-                         &color_mean, &color_median, &color_count, &alt_color_mean, &alt_color_median, &alt_color_count});
-    }
-  } mesh;
-  struct Extraction {  // dmi_extract_isosurface (isosurface.hip)
+  using Mesh = dmi::MeshState;  // dmi_mesh_stage.h: the mesh, and the one operation that makes a stage's result the mesh
+  Mesh mesh;
+  struct Extraction : dmi::StageTimes<4> {  // dmi_extract_isosurface (isosurface.hip): around the count pass + scans, and the write pass
     dmi::DeviceBuffer counts, bases, scan_temp;  // per-segment counts (u32) and bases (u64), two arrays of (segments + 1) each
-    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};  // around the count pass + scans, and the write pass
-    double last_kernel_ms = 0.0;
-    void release() { dmi::free_buffers({&counts, &bases, &scan_temp}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&counts, &bases, &scan_temp}); StageTimes::release(); }
   } extraction;
-  struct Components {  // dmi_filter_isosurface_components (isosurface_components.hip)
-    dmi::DeviceBuffer vertex_scratch;  // parent, size, vmap, rmap: 4 u32 arrays of (vertices + 1)
+  // dmi_filter_isosurface_components (isosurface_components.hip); passes: labels (init, hook, flatten), sizes (and largest), scans, compaction
+  struct Components : dmi::StageTimes<5, 4> {
+    dmi::DeviceBuffer vertex_scratch;  // dmi::kComponentsLanes u32 arrays of (vertices + 1)
     dmi::DeviceBuffer triangle_scratch, counters, scan_temp;
-    hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double last_kernel_ms = 0.0;
     uint64_t last_cas_retries = 0;  // compare-and-swaps of the last filter's hooking pass that lost a race
-    double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // labels (init, hook, flatten), sizes (and largest), scans, compaction
-    void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &counters, &scan_temp}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &counters, &scan_temp}); StageTimes::release(); }
   } components;
-  struct Smoothing {  // dmi_smooth_isosurface (isosurface_smooth.hip)
+  struct Smoothing : dmi::StageTimes<4, 3> {  // dmi_smooth_isosurface (isosurface_smooth.hip); passes: adjacency (and incidence), steps, normals
     dmi::DeviceBuffer vertices;        // the second position buffer of the steps
     dmi::DeviceBuffer keys;            // two u64 arrays of 6 triangles' keys
-    dmi::DeviceBuffer vertex_scratch;  // the fixed bits, then row starts, valences and offsets: 3 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer vertex_scratch;  // the fixed bits, then dmi::kSmoothingLanes u32 arrays of (vertices + 1)
     dmi::DeviceBuffer temp;
-    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
-    double last_kernel_ms = 0.0;
-    double last_pass_ms[3] = {0.0, 0.0, 0.0};  // adjacency (and incidence), steps, normals
-    void release() { dmi::free_buffers({&vertices, &keys, &vertex_scratch, &temp}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&vertices, &keys, &vertex_scratch, &temp}); StageTimes::release(); }
   } smoothing;
-  struct Decimation {  // dmi_decimate_isosurface (isosurface_decimate.hip); it also uses smoothing.keys and smoothing.temp
-    dmi::DeviceBuffer vertex_scratch;    // sorted ids (2), head, rank, cluster, start, mark, map: 8 u32 arrays of (vertices + 1)
-    dmi::DeviceBuffer triangle_scratch;  // keep, map: 2 u32 arrays of (triangles + 1)
+  // dmi_decimate_isosurface (isosurface_decimate.hip); it also uses smoothing.keys and smoothing.temp.  Events: around the bounds
+  // pass; before the keys, after the ranks, the triangles, the representatives; around the normals.  Passes: clustering,
+  // representatives, triangles, normals
+  struct Decimation : dmi::StageTimes<8, 4> {
+    dmi::DeviceBuffer vertex_scratch;    // dmi::kDecimationLanes u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer triangle_scratch;  // dmi::kDecimationTriangleLanes u32 arrays of (triangles + 1)
     dmi::DeviceBuffer bounds;            // 8 u64
-    // around the bounds pass; before the keys, after the ranks, the triangles, the representatives; around the normals
-    hipEvent_t events[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool pending = false;         // the events of the last call have not been read yet (its normals may still run)
     bool pending_normals = false;
-    double last_kernel_ms = 0.0;
-    double last_pass_ms[4] = {0.0, 0.0, 0.0, 0.0};  // clustering, representatives, triangles, normals
-    void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&vertex_scratch, &triangle_scratch, &bounds}); StageTimes::release(); }
   } decimation;
-  struct Holes {  // dmi_fill_isosurface_holes (isosurface_holes.hip); it also uses smoothing.keys and smoothing.temp
-    dmi::DeviceBuffer vertex_scratch;  // out-degree, in-degree, successor, flag, rank: 5 u32 arrays of (vertices + 1)
-    dmi::DeviceBuffer loop_scratch;    // id, next, 2 pointers, 2 labels, count, 2 additions, 2 offsets: 11 u32 arrays of (slots + 1)
+  // dmi_fill_isosurface_holes (isosurface_holes.hip); it also uses smoothing.keys and smoothing.temp; passes: boundary, loops, fill
+  struct Holes : dmi::StageTimes<4, 3> {
+    dmi::DeviceBuffer vertex_scratch;  // dmi::kHolesLanes u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer loop_scratch;    // dmi::kHolesLoopLanes u32 arrays of (slots + 1)
     dmi::DeviceBuffer counters;        // 4 u64
-    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
-    double last_kernel_ms = 0.0;
-    double last_pass_ms[3] = {0.0, 0.0, 0.0};  // boundary, loops, fill
-    void release() { dmi::free_buffers({&vertex_scratch, &loop_scratch, &counters}); dmi::destroy_events(events); }
+    void release() { dmi::free_buffers({&vertex_scratch, &loop_scratch, &counters}); StageTimes::release(); }
   } holes;
-
-  struct Support {  // dmi_filter_isosurface_support (isosurface_support.hip)
+  // dmi_filter_isosurface_support (isosurface_support.hip); passes: counts, marks and scans, compaction
+  struct Support : dmi::StageTimes<4, 3> {
     dmi::DeviceBuffer counts;          // [n] int32: the supporting views of every vertex of the mesh, as the last call left it
+                                       // (mesh.support_counted: they describe this mesh)
     dmi::DeviceBuffer work, compacted; // the call's own counts, and those of its compacted mesh: whichever holds the result is
                                        // swapped with `counts` last
     dmi::DeviceBuffer maps;            // the resident views' MapRecs as the call found them
-    dmi::DeviceBuffer vertex_scratch;  // mark, vmap: 2 u32 arrays of (vertices + 1)
+    dmi::DeviceBuffer vertex_scratch;  // dmi::kSupportLanes u32 arrays of (vertices + 1)
     dmi::DeviceBuffer triangle_scratch, scan_temp;
-    bool valid = false;                // `counts` describes this mesh (dropped by whatever changes it)
-    hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
-    double last_kernel_ms = 0.0;
-    double last_pass_ms[3] = {0.0, 0.0, 0.0};  // counts, marks and scans, compaction
     void release() {
       dmi::free_buffers({&counts, &work, &compacted, &maps, &vertex_scratch, &triangle_scratch, &scan_temp});
-      dmi::destroy_events(events);
+      StageTimes::release();
     }
   } support;
-
-  struct Coloration {  // dmi_color_process_isosurface (dmi_capi_color.hip through dmi::color_device_vertices)
-    hipEvent_t events[1] = {nullptr};  // what the colour context's stream waits for: the end of this context's queued work
-    double last_kernel_ms = 0.0;
-    void release() { dmi::destroy_events(events); }
-  } coloration;
+  // dmi_color_process_isosurface (dmi_capi_color.hip through dmi::color_device_vertices).  The one event, without timing, is what
+  // the colour context's stream waits for: the end of this context's queued work
+  dmi::StageTimes<1> coloration;
 
   std::vector<dmi::EventPair> pending, pool;
   dmi_timings timings{};

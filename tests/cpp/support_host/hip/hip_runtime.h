@@ -5,7 +5,9 @@
 // hipMalloc and hipFree are malloc and free -- so that AddressSanitizer sees a buffer freed twice or never -- with an allocator
 // that fails on the call a test names (tests/cpp/buffer_growth_host.cpp, for csrc/dmi_buffer.h).  Streams and events are allocations
 // too, counted as they are created and destroyed; the number of devices is the test's to set; a copy is a memcpy, a span between two
-// events one millisecond (tests/cpp/depth_call_host.cpp, for csrc/dmi_depth_call.h).
+// events one millisecond (tests/cpp/depth_call_host.cpp, for csrc/dmi_depth_call.h).  An event holds the clock's value when it was
+// recorded -- the clock goes on by a millisecond with every record, or to what the test sets --, and the creation of events fails on
+// the call a test names, as the allocator does (tests/cpp/mesh_stage_host.cpp, for csrc/dmi_mesh_stage.h).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -37,6 +39,7 @@ constexpr hipError_t hipErrorOutOfMemory = 2;
 constexpr hipError_t hipErrorNoDevice = 100;
 constexpr hipError_t hipErrorInvalidDevice = 101;
 constexpr unsigned hipStreamNonBlocking = 1;
+constexpr unsigned hipEventDisableTiming = 2;
 enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount };
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
 struct hip_host_state {
@@ -46,6 +49,10 @@ struct hip_host_state {
   int compute_units = 256;
   long device_counts = 0, set_devices = 0, attributes = 0, copies = 0, elapsed_times = 0;
   long streams_created = 0, streams_destroyed = 0, events_created = 0, events_destroyed = 0;
+  long event_creations = 0;       // calls, the failed one included
+  long fail_event_create_at = 0;  // the creation of an event (counted from 1) that fails; 0: none
+  long events_without_timing = 0;
+  float clock = 0.f;              // milliseconds: what the next hipEventRecord stamps
 };
 inline hip_host_state hip_host;
 inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -75,19 +82,22 @@ inline hipError_t hipStreamDestroy(hipStream_t s) {
   free(s);
   return hipSuccess;
 }
-inline hipError_t hipEventCreate(hipEvent_t *e) {
+inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags) {
+  if (++hip_host.event_creations == hip_host.fail_event_create_at) return hipErrorOutOfMemory;
   ++hip_host.events_created;
-  *e = malloc(1);
+  if (flags & hipEventDisableTiming) ++hip_host.events_without_timing;
+  *e = calloc(1, sizeof(float));
   return hipSuccess;
 }
+inline hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
 inline hipError_t hipEventDestroy(hipEvent_t e) {
   ++hip_host.events_destroyed;
   free(e);
   return hipSuccess;
 }
-inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) {
+inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t start, hipEvent_t stop) {
   ++hip_host.elapsed_times;
-  *ms = 1.f;
+  *ms = start && stop ? *static_cast<float *>(stop) - *static_cast<float *>(start) : 1.f;  // (no events: a span all the same)
   return hipSuccess;
 }
 inline hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t) {
@@ -109,7 +119,12 @@ inline hipError_t hipStreamSynchronize(hipStream_t) {
   ++hip_host.synchronizes;
   return hipSuccess;
 }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
+  if (!e) return hipSuccess;  // (the kernels' harness has no events)
+  *static_cast<float *>(e) = hip_host.clock;
+  hip_host.clock += 1.f;
+  return hipSuccess;
+}
 inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) {
   memset(p, v, n);
   return hipSuccess;

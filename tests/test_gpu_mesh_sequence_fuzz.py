@@ -1,7 +1,7 @@
 """Sequences of mesh calls on ONE capi.FusionContext (and the capi.ColorContext that goes with it) against a replay by the numpy
 restatements (tests/mesh_sequence_model.py).  Every mesh stage has a test file of its own that checks it bit for bit on a freshly
 extracted mesh; none checks what a context carries from one stage to the next: the flags Mesh::{valid, has_normals, filtered,
-colored}, Support::valid, CellToPoint::valid and PointSmoothing::on; six mesh buffers with an alternate each, swapped in by the
+colored, support_counted}, CellToPoint::valid and PointSmoothing::on; six mesh buffers with an alternate each, swapped in by the
 filter, the smoother, the decimations, the fill and the trim, so that after any stage the two have different capacities and hold
 different stale meshes; scratch the smoother, the decimations and the fill share and keep "while large enough", so that a stage
 behind one on a larger mesh finds another stage's leftovers behind its own n + 1 entries; work ordered across streams by events
