@@ -19,8 +19,8 @@ CSRC = os.path.join(_HERE, "csrc")
 OBJ_DIR = os.path.join(ROOT, "build", "obj")
 LIB_PATH = os.path.join(CSRC, "libdmi_hip.so")
 
-SOURCES = ["fusion_kernels.hip", "fusion_tile.hip", "fusion_classify.hip", "coloration_kernels.hip", "mesh_depth_render.hip", "grid_post.hip", "point_smooth.hip", "isosurface.hip", "isosurface_components.hip", "isosurface_smooth.hip", "isosurface_decimate.hip", "isosurface_holes.hip", "isosurface_support.hip", "depth_consistency.hip", "depth_speckle.hip", "depth_holes.hip", "depth_smooth.hip", "scene_bounds.hip", "depth_points.hip", "depth_points_thin.hip", "depth_points_radius.hip", "dmi_capi.hip", "dmi_capi_views.hip", "dmi_capi_fuse.hip", "dmi_capi_mesh.hip", "dmi_capi_color.hip", "dmi_capi_consistency.hip", "dmi_capi_speckle.hip", "dmi_capi_holes.hip", "dmi_capi_smooth.hip", "dmi_capi_bounds.hip", "dmi_capi_points_thin.hip", "dmi_capi_points_radius.hip", "view_set_kernels.hip", "dmi_capi_viewset.hip", "dmi_multi.hip", "host/recon_host.cpp", "host/vti_reader.cpp", "host/vtp_reader.cpp", "host/recon_cli.cpp", "host/color_cli.cpp", "host/dmi_host_capi.cpp"]
-HEADERS = ["fusion_kernels.h", "view_records.h", "fusion_launch_rules.h", "fusion_device.h", "dmi_buffer.h", "dmi_depth_call.h", "dmi_mesh_stage.h", "dmi_context.h", "dmi_color_context.h", "coloration_kernels.h", "mesh_depth_render.h", "depth_consistency.h", "depth_speckle.h", "depth_speckle_rules.h", "depth_holes.h", "depth_holes_rules.h", "depth_smooth.h", "depth_smooth_rules.h", "union_find_device.h", "scene_bounds.h", "scene_bounds_rules.h", "depth_points.h", "depth_points_rules.h", "depth_points_thin.h", "depth_points_thin_rules.h", "depth_points_radius.h", "depth_points_radius_rules.h", "dmi_view_set.h", "view_set_kernels.h", "view_set_rules.h", "point_smooth_rules.h", "rounded_quotient.h", "fusion_tile_acc.inc", "isosurface_table.inc", os.path.join("host", "recon_host.h"),
+SOURCES = ["fusion_kernels.hip", "fusion_tile.hip", "fusion_classify.hip", "coloration_kernels.hip", "mesh_depth_render.hip", "grid_post.hip", "point_smooth.hip", "isosurface.hip", "isosurface_components.hip", "isosurface_smooth.hip", "isosurface_decimate.hip", "isosurface_holes.hip", "isosurface_support.hip", "depth_consistency.hip", "depth_speckle.hip", "depth_holes.hip", "depth_smooth.hip", "scene_bounds.hip", "depth_points.hip", "depth_points_thin.hip", "depth_points_radius.hip", "depth_points_planes.hip", "dmi_capi.hip", "dmi_capi_views.hip", "dmi_capi_fuse.hip", "dmi_capi_mesh.hip", "dmi_capi_color.hip", "dmi_capi_consistency.hip", "dmi_capi_speckle.hip", "dmi_capi_holes.hip", "dmi_capi_smooth.hip", "dmi_capi_bounds.hip", "dmi_capi_points_thin.hip", "dmi_capi_points_radius.hip", "dmi_capi_points_planes.hip", "view_set_kernels.hip", "dmi_capi_viewset.hip", "dmi_multi.hip", "host/recon_host.cpp", "host/vti_reader.cpp", "host/vtp_reader.cpp", "host/recon_cli.cpp", "host/color_cli.cpp", "host/dmi_host_capi.cpp"]
+HEADERS = ["fusion_kernels.h", "view_records.h", "fusion_launch_rules.h", "fusion_device.h", "dmi_buffer.h", "dmi_depth_call.h", "dmi_mesh_stage.h", "dmi_context.h", "dmi_color_context.h", "coloration_kernels.h", "mesh_depth_render.h", "depth_consistency.h", "depth_speckle.h", "depth_speckle_rules.h", "depth_holes.h", "depth_holes_rules.h", "depth_smooth.h", "depth_smooth_rules.h", "union_find_device.h", "scene_bounds.h", "scene_bounds_rules.h", "depth_points.h", "depth_points_rules.h", "depth_points_thin.h", "depth_points_thin_rules.h", "depth_points_radius.h", "depth_points_radius_rules.h", "depth_points_search_device.h", "depth_points_planes.h", "depth_points_planes_rules.h", "dmi_view_set.h", "view_set_kernels.h", "view_set_rules.h", "point_smooth_rules.h", "rounded_quotient.h", "fusion_tile_acc.inc", "isosurface_table.inc", os.path.join("host", "recon_host.h"),
            os.path.join("host", "vtk_xml_data.h"), os.path.join("host", "vti_reader.h"), os.path.join("host", "vtp_reader.h"),
            os.path.join("host", "recon_cli.h"), os.path.join("host", "color_cli.h"), os.path.join("host", "fan_triangulate.h"),
            os.path.join("..", "..", "include", "dmi.h"), os.path.join("..", "..", "include", "dmi_host.h")]

@@ -102,6 +102,15 @@ class PointsRadiusReportC(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class PointsPlanesReportC(ctypes.Structure):
+    _fields_ = [("points_in", ctypes.c_uint64), ("fitted", ctypes.c_uint64), ("unsupported", ctypes.c_uint64),
+                ("crowded", ctypes.c_uint64), ("max_neighbors", ctypes.c_uint64), ("neighbor_sum", ctypes.c_uint64),
+                ("distance_tests", ctypes.c_uint64), ("max_shift", ctypes.c_double), ("kernel_ms", ctypes.c_double)]
+
+
+PLANE_FIT_MOVE, PLANE_FIT_NORMALS = 1, 2   # DMI_PLANE_FIT_MOVE, DMI_PLANE_FIT_NORMALS
+
+
 class MultiOptionsC(ctypes.Structure):
     _fields_ = [("grid_dtype", ctypes.c_int32), ("depth_storage", ctypes.c_int32), ("kernel_variant", ctypes.c_int32),
                 ("partition", ctypes.c_int32), ("exchange", ctypes.c_int32), ("n_slabs", ctypes.c_int32)]
@@ -162,6 +171,7 @@ ABI_SYMBOLS = [
     "dmi_views_set_thin_wave_cell_points",
     "dmi_count_point_neighbors", "dmi_views_filter_points_radius", "dmi_views_download_point_neighbors", "dmi_views_get_radius_pass_ms",
     "dmi_views_set_radius_group_points",
+    "dmi_fit_point_planes", "dmi_views_fit_point_planes", "dmi_views_download_point_plane_rms", "dmi_views_get_plane_fit_pass_ms",
     "dmi_point_smoothing_weights", "dmi_set_point_smoothing", "dmi_get_point_smoothing", "dmi_get_point_smoothing_kernel_ms",
     "dmi_multi_default_options", "dmi_multi_view_shard", "dmi_multi_z_slab", "dmi_multi_slab_ranges", "dmi_multi_peer_chunk", "dmi_multi_create",
     "dmi_multi_get_unique_id", "dmi_multi_create_rank", "dmi_multi_destroy", "dmi_multi_last_error", "dmi_multi_add_views",
@@ -375,6 +385,12 @@ def load() -> ctypes.CDLL:
         L.dmi_views_download_point_neighbors.argtypes = [vp, u64, u64, u32p]
         L.dmi_views_get_radius_pass_ms.argtypes = [vp, dp]
         L.dmi_views_set_radius_group_points.argtypes = [vp, i32]
+    if hasattr(L, "dmi_fit_point_planes"):
+        u32p, fp, pp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(PointsPlanesReportC)
+        L.dmi_fit_point_planes.argtypes = [dp, fp, u64, dbl, i32, i32, i32, dp, fp, fp, u32p, pp]
+        L.dmi_views_fit_point_planes.argtypes = [vp, dbl, i32, i32, pp]
+        L.dmi_views_download_point_plane_rms.argtypes = [vp, u64, u64, fp]
+        L.dmi_views_get_plane_fit_pass_ms.argtypes = [vp, dp]
     L.dmi_multi_default_options.argtypes = [ctypes.POINTER(MultiOptionsC)]
     L.dmi_multi_default_options.restype = None
     L.dmi_multi_view_shard.argtypes = [i64, i32, i32, i64p, i64p]
@@ -1406,6 +1422,36 @@ def count_point_neighbors(xyz, *, radius: float, min_neighbors: int = 1, device:
     return neighbors, keep.astype(bool), {name: getattr(r, name) for name, _ in PointsRadiusReportC._fields_}
 
 
+def fit_point_planes(xyz, normal=None, *, radius: float, min_neighbors: int = 5, move: bool = True, normals: bool = True,
+                     device: int = 0):
+    """A plane fitted to the points within `radius` of every point that has at least min_neighbors of them; the point moved onto it
+    (move) and its normal replaced by the plane's, on the side of the old one (normals) (include/dmi.h: dmi_fit_point_planes).
+    xyz [P, 3] f64, normal [P, 3] f32 or None.  Returns (arrays, report): arrays has xyz, normal, plane_rms f32 [P] (-1: no fit) and
+    neighbors uint32 [P]; an array whose flag is not set is the input's (zeros for absent normals).  report has points_in, fitted,
+    unsupported, crowded, max_neighbors, neighbor_sum, distance_tests, max_shift, kernel_ms."""
+    L = load()
+    a = np.ascontiguousarray(xyz, dtype=np.float64)
+    if a.size % 3:
+        raise ValueError("xyz must hold 3 values per point")
+    p = a.size // 3
+    old = None if normal is None else np.ascontiguousarray(normal, dtype=np.float32)
+    if old is not None and old.size != 3 * p:
+        raise ValueError("normal must hold 3 values per point")
+    flags = (PLANE_FIT_MOVE if move else 0) | (PLANE_FIT_NORMALS if normals else 0)
+    fp = ctypes.POINTER(ctypes.c_float)
+    out_xyz = a.reshape(p, 3).copy()
+    out_normal = np.zeros((p, 3), dtype=np.float32) if old is None else old.reshape(p, 3).copy()
+    rms, neighbors = np.empty(p, dtype=np.float32), np.empty(p, dtype=np.uint32)
+    r = PointsPlanesReportC()
+    rc = L.dmi_fit_point_planes(_dp(a), None if old is None else old.ctypes.data_as(fp), p, float(radius), int(min_neighbors), flags,
+                                int(device), _dp(out_xyz) if move else None, out_normal.ctypes.data_as(fp) if normals else None,
+                                rms.ctypes.data_as(fp), neighbors.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(r))
+    if rc != DMI_OK:
+        raise DmiError(rc, L.dmi_last_error(None).decode())
+    return (dict(xyz=out_xyz, normal=out_normal, plane_rms=rms, neighbors=neighbors),
+            {name: getattr(r, name) for name, _ in PointsPlanesReportC._fields_})
+
+
 class ViewSet:
     """Depth maps resident on the device from the first filter to the fusion (dmi_views_create ... dmi_views_destroy;
     include/dmi.h states the definition).  add() uploads once; every step replaces the set's depths by exactly what the
@@ -1621,6 +1667,34 @@ class ViewSet:
     def set_radius_group_points(self, k: int):
         """A wave of the neighbour count takes at most k points of one grid row as its queries (1..64).  No result depends on it."""
         self._check(self._lib.dmi_views_set_radius_group_points(self._h, int(k)))
+
+    def fit_point_planes(self, radius: float, min_neighbors: int = 5, *, move: bool = True, normals: bool = True) -> dict:
+        """The set's cloud -- built, thinned or filtered -- with every point that has at least min_neighbors others within `radius`
+        moved onto the plane fitted to them (move) and carrying that plane's normal (normals) (include/dmi.h:
+        dmi_views_fit_point_planes).  Order, layout and every other array stay.  Returns the report: points_in, fitted, unsupported,
+        crowded, max_neighbors, neighbor_sum, distance_tests, max_shift, kernel_ms; download_point_plane_rms serves the residuals."""
+        r = PointsPlanesReportC()
+        flags = (PLANE_FIT_MOVE if move else 0) | (PLANE_FIT_NORMALS if normals else 0)
+        self._check(self._lib.dmi_views_fit_point_planes(self._h, float(radius), int(min_neighbors), flags, ctypes.byref(r)))
+        return {name: getattr(r, name) for name, _ in PointsPlanesReportC._fields_}
+
+    def download_point_plane_rms(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """The RMS distance of each of the points' [first, first + count) balls from their planes, f32; -1 where none was fitted."""
+        first = int(first)
+        if count is None:
+            count = max(getattr(self, "_n_points", 0) - first, 0)
+        count = int(count)
+        if first < 0 or count < 0:
+            raise ValueError("first and count must not be negative")
+        out = np.empty(count, dtype=np.float32)
+        self._check(self._lib.dmi_views_download_point_plane_rms(self._h, first, count, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
+        return out
+
+    def plane_fit_pass_ms(self) -> dict:
+        """The last fit_point_planes' kernel time by pass (ms): bounds, keys, sort, ranks, permute, fit."""
+        out = np.zeros(6, dtype=np.float64)
+        self._check(self._lib.dmi_views_get_plane_fit_pass_ms(self._h, _dp(out)))
+        return dict(zip(("bounds", "keys", "sort", "ranks", "permute", "fit"), out.tolist()))
 
 
 class ColorContext:
@@ -1989,7 +2063,10 @@ class CliOptionsC(ctypes.Structure):
                 ("depth_smooth_tolerance", ctypes.c_double), ("depth_smooth_rel_tolerance", ctypes.c_double),
                 ("depth_smooth_iterations", ctypes.c_int64), ("depth_staged_filters", ctypes.c_int32),
                 ("point_cloud_cell_size", ctypes.c_double), ("point_cloud_min_cell_points", ctypes.c_int64),
-                ("point_cloud_outlier_radius", ctypes.c_double), ("point_cloud_min_neighbors", ctypes.c_int64)]
+                ("point_cloud_outlier_radius", ctypes.c_double), ("point_cloud_min_neighbors", ctypes.c_int64),
+                ("point_cloud_plane_fit_radius", ctypes.c_double), ("point_cloud_plane_fit_min_neighbors", ctypes.c_int64),
+                ("point_cloud_plane_fit_iterations", ctypes.c_int64), ("point_cloud_plane_fit_keep_positions", ctypes.c_int32),
+                ("point_cloud_plane_fit_keep_normals", ctypes.c_int32)]
 
 
 def cli_read_arguments(args):

@@ -55,6 +55,18 @@ struct RadiusCloud {
   uint64_t n;
 };
 
+// what the front passes leave for the kernel that searches: pointers into the scratch
+struct RadiusSorted {
+  const uint64_t *keys;  // n, ascending
+  const uint32_t *ids;   // n: the input index of every sorted position
+  uint32_t *free_words;  // 2 (n + 1) u32 in the key array the sort did not end in: the head flags and ranks, read for the last time
+};
+
+// The front passes both searching kernels share (the count below, the plane fit of depth_points_planes.hip): keys, sort, units
+// (heads, ranks, starts) and the permutation into sorted planes.  events[0..5) stand in front of keys, sort, ranks, permute and
+// behind the permutation.  Leaves scratch.start, scratch.sorted_xyz, counters[kRadiusUnits] and *sorted.
+hipError_t launch_radius_front(const double *xyz, uint64_t n, const RadiusGrid &grid, uint32_t group_points, const RadiusScratch &scratch,
+                               hipEvent_t events[5], RadiusSorted *sorted, hipStream_t stream);
 // keys, sort, units, permutation, count and flags in stream order: events[0..7) stand in front of keys, sort, ranks, permute,
 // count, flags and behind the flags' scan.  Leaves neighbors (input order), counters[kRadiusUnits ..] and *kept.
 hipError_t launch_radius_counts(const double *xyz, uint64_t n, const RadiusGrid &grid, double r2, uint32_t min_neighbors,

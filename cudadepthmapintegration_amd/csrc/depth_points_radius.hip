@@ -29,45 +29,12 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "depth_points_radius.h"
+#include "depth_points_search_device.h"
 
 namespace dmi {
 namespace {
 
 using namespace radius_rules;
-
-constexpr unsigned kStrideBlocks = 4096;  // at most, where a pass ends in one atomic per workgroup: it strides over its entries
-constexpr unsigned kCountBlocks = 8192;   // at most: the waves of the count kernel stride over the units
-
-__device__ __forceinline__ unsigned long long shuffle_xor(unsigned long long x, int mask) {
-  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)x, mask, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(x >> 32), mask, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// the sum of `x` over the workgroup, in every thread (LDS `part`: kBlock / 64 entries; every thread calls it)
-__device__ __forceinline__ unsigned long long block_sum(unsigned long long x, unsigned long long *part) {
-  for (int mask = 32; mask >= 1; mask >>= 1) x += shuffle_xor(x, mask);
-  __syncthreads();  // (part may still be read from an earlier call)
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
-  __syncthreads();
-  unsigned long long sum = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) sum += part[w];
-  return sum;
-}
-
-__device__ __forceinline__ unsigned long long block_max(unsigned long long x, unsigned long long *part) {
-  for (int mask = 32; mask >= 1; mask >>= 1) {
-    const unsigned long long y = shuffle_xor(x, mask);
-    x = y > x ? y : x;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
-  __syncthreads();
-  unsigned long long most = 0;
-#pragma unroll
-  for (int w = 0; w < kBlock / 64; ++w) most = part[w] > most ? part[w] : most;
-  return most;
-}
 
 __global__ __launch_bounds__(kBlock) void radius_keys_kernel(const double *__restrict__ p, uint64_t n, RadiusGrid g,
                                                              uint64_t *__restrict__ keys, uint32_t *__restrict__ ids) {
@@ -110,23 +77,6 @@ __global__ __launch_bounds__(kBlock) void radius_permute_kernel(const double *__
   const uint64_t u = ids[i];
 #pragma unroll
   for (int d = 0; d < 3; ++d) sorted_xyz[(uint64_t)d * n + i] = xyz[3 * u + d];
-}
-
-// orders the LDS accesses of one wave among themselves: nothing crosses it, at compile time or at run time
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// the first sorted position whose key is not below `target` (n when there is none)
-__device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ keys, uint64_t n, uint64_t target) {
-  uint64_t a = 0, b = n;
-  while (a < b) {
-    const uint64_t m = a + ((b - a) >> 1);  // a <= m < b <= n
-    if (keys[m] < target) a = m + 1;
-    else b = m;
-  }
-  return (uint32_t)a;
 }
 
 // A wave per unit, a lane per query.  Every lane tests every candidate of the unit's nine runs, which hold every point of the 27
@@ -244,8 +194,8 @@ unsigned blocks(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
 
-hipError_t launch_radius_counts(const double *xyz, uint64_t n, const RadiusGrid &g, double r2, uint32_t min_neighbors, uint32_t group_points,
-                                const RadiusScratch &s, hipEvent_t events[7], RadiusKept *out, hipStream_t stream) {
+hipError_t launch_radius_front(const double *xyz, uint64_t n, const RadiusGrid &g, uint32_t group_points, const RadiusScratch &s,
+                               hipEvent_t events[5], RadiusSorted *out, hipStream_t stream) {
   const int bits = thin_rules::key_bits(g.n[0], g.n[1], g.n[2]);
   hipError_t e = hipEventRecord(events[0], stream);
   if (e != hipSuccess) return e;
@@ -270,7 +220,20 @@ hipError_t launch_radius_counts(const double *xyz, uint64_t n, const RadiusGrid 
   if ((e = hipEventRecord(events[3], stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(radius_permute_kernel, dim3(blocks(n)), dim3(kBlock), 0, stream, xyz, sorted_ids, n, s.sorted_xyz);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = hipEventRecord(events[4], stream)) != hipSuccess) return e;
+  out->keys = sorted_keys;
+  out->ids = sorted_ids;
+  out->free_words = head;
+  return hipEventRecord(events[4], stream);
+}
+
+hipError_t launch_radius_counts(const double *xyz, uint64_t n, const RadiusGrid &g, double r2, uint32_t min_neighbors, uint32_t group_points,
+                                const RadiusScratch &s, hipEvent_t events[7], RadiusKept *out, hipStream_t stream) {
+  RadiusSorted sorted{};
+  hipError_t e = launch_radius_front(xyz, n, g, group_points, s, events, &sorted, stream);
+  if (e != hipSuccess) return e;
+  const uint64_t *const sorted_keys = sorted.keys;
+  const uint32_t *const sorted_ids = sorted.ids;
+  uint32_t *const head = sorted.free_words, *const rank = head + (n + 1);
   const unsigned count_blocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 31) / 32, 1), kCountBlocks);
   hipLaunchKernelGGL(radius_count_kernel, dim3(count_blocks), dim3(kBlock), 0, stream, sorted_keys, sorted_ids, s.start, s.sorted_xyz, n,
                      g.n[0], g.n[1], g.n[2], r2, s.neighbors, s.counters);
@@ -281,7 +244,7 @@ hipError_t launch_radius_counts(const double *xyz, uint64_t n, const RadiusGrid 
   hipLaunchKernelGGL(radius_flags_kernel, dim3(std::min<unsigned>(blocks(n + 1), kStrideBlocks)), dim3(kBlock), 0, stream, s.neighbors, n,
                      min_neighbors, kept, s.counters);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  bytes = s.temp_bytes;
+  size_t bytes = s.temp_bytes;
   if ((e = rocprim::exclusive_scan(s.temp, bytes, kept, out_index, (uint32_t)0, (size_t)(n + 1), rocprim::plus<uint32_t>(), stream)) !=
       hipSuccess)
     return e;

@@ -77,10 +77,11 @@ struct WholeSetScratch {
 
 // D changes, or the views do: the points of the last build describe neither any longer
 void drop_points(dmi_view_set *s) {
-  if (s->points.ptr) {
+  if (s->points.ptr || s->plane_rms.ptr) {
     (void)hipSetDevice(s->device);
-    dmi::free_buffers({&s->points}, s->device_bytes);
+    dmi::free_buffers({&s->points, &s->plane_rms}, s->device_bytes);
   }
+  s->points_fitted = false;
   s->n_points = 0;
   s->points_current = false;
   s->points_thinned = false;
@@ -675,7 +676,8 @@ int thin_points(dmi_view_set *s, double cell_size, int32_t min_points, uint64_t 
                                         &outcome, &message);
     if (rc != DMI_OK) return fail(s, rc, message);  // (nothing of the call is left; the cloud is as it was)
   }
-  dmi::free_buffers({&s->points}, s->device_bytes);
+  dmi::free_buffers({&s->points, &s->plane_rms}, s->device_bytes);  // (a fit's plane_rms went with the old cloud)
+  s->points_fitted = false;
   s->points = outcome.result;
   s->n_points = outcome.n_out;
   s->points_thinned = true;
@@ -738,7 +740,8 @@ int filter_points_radius(dmi_view_set *s, double radius, int32_t min_neighbors, 
                                           s->stream, s->device_bytes, &outcome, &message);
     if (rc != DMI_OK) return fail(s, rc, message);  // (nothing of the call is left; the cloud is as it was)
   }
-  dmi::free_buffers({&s->points}, s->device_bytes);
+  dmi::free_buffers({&s->points, &s->plane_rms}, s->device_bytes);  // (a fit's plane_rms went with the old cloud)
+  s->points_fitted = false;
   s->points = outcome.result;
   s->n_points = outcome.n_kept;
   s->points_filtered = true;
@@ -767,6 +770,67 @@ int download_point_neighbors(dmi_view_set *s, uint64_t first, uint64_t count, ui
   return DMI_OK;
 }
 
+// the set's cloud -- built, thinned or filtered -- replaced by one of the same layout whose points lie on the planes fitted to their
+// balls and carry those planes' normals: dmi::run_plane_fit_points (dmi_capi_points_planes.hip) from the arrays of s->points into
+// a copy of them
+int fit_point_planes(dmi_view_set *s, double radius, int32_t min_neighbors, int32_t flags, dmi_points_planes_report *r) {
+  const std::string entry = "dmi_views_fit_point_planes";
+  if (const int rc = require_set(s, entry + ": ")) return rc;
+  auto bad = [&](const std::string &what) { return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + ": " + what); };
+  if (const char *what = dmi::plane_fit_refusal(radius, min_neighbors, flags)) return bad(what);
+  if (!s->points_current) return fail(s, DMI_ERR_STATE, entry + ": the set holds no points: dmi_views_build_points comes first");
+  if (s->n_points > dmi::radius_rules::kMaxPoints) return bad("the cloud must hold fewer than 2^32 points");
+
+  VS_HIP(s, hipSetDevice(s->device));
+  dmi::PlaneFitOutcome outcome;
+  dmi::DeviceBuffer fresh;
+  struct Guard {
+    dmi_view_set *s;
+    dmi::DeviceBuffer *b;
+    ~Guard() { dmi::free_buffers({b}, s->device_bytes); }  // (empty once the buffer has become the set's)
+  } guard{s, &fresh};
+  if (s->n_points) {
+    dmi::thin_rules::Layout in;
+    (void)dmi::thin_rules::layout_of(s->n_points, &in);  // (it fitted when the points were made; the first five arrays are the build's)
+    uint64_t neighbors_offset = 0, bytes = (s->points_thinned ? 52 : 48) * s->n_points;
+    if (s->points_filtered) (void)dmi::radius_rules::filtered_bytes(s->n_points, s->points_thinned ? 52 : 48, &neighbors_offset, &bytes);
+    const unsigned char *const base = s->points.as<unsigned char>();
+    VS_HIP(s, grow(s, fresh, bytes));
+    VS_HIP(s, hipMemcpyAsync(fresh.ptr, base, (size_t)bytes, hipMemcpyDeviceToDevice, s->stream));  // every array keeps its bits ...
+    unsigned char *const out = fresh.as<unsigned char>();
+    std::string message;
+    const int rc = dmi::run_plane_fit_points(entry, reinterpret_cast<const double *>(base + in.xyz),
+                                             reinterpret_cast<const float *>(base + in.normal), s->n_points, radius, min_neighbors, flags,
+                                             s->radius_group_points, reinterpret_cast<double *>(out + in.xyz),  // ... but the fitted points'
+                                             reinterpret_cast<float *>(out + in.normal), s->stream, s->device_bytes, &outcome, &message);
+    if (rc != DMI_OK) return fail(s, rc, message);  // (nothing of the call is left; the cloud is as it was)
+    dmi::free_buffers({&outcome.neighbors}, s->device_bytes);  // (the report has their sums; a filtered cloud keeps the filter's counts)
+    std::swap(s->points, fresh);  // (the guard frees the old cloud)
+  }
+  dmi::free_buffers({&s->plane_rms}, s->device_bytes);
+  s->plane_rms = outcome.plane_rms;
+  s->points_fitted = true;
+  s->steps += 1;
+  for (int e = 0; e < 6; ++e) s->plane_fit_pass_ms[e] = outcome.pass_ms[e];
+  if (r) *r = outcome.report;
+  return DMI_OK;
+}
+
+int download_point_plane_rms(dmi_view_set *s, uint64_t first, uint64_t count, float *out) {
+  const std::string entry = "dmi_views_download_point_plane_rms: ";
+  if (const int rc = require_set(s, entry)) return rc;
+  if (!s->points_current || !s->points_fitted)
+    return fail(s, DMI_ERR_STATE, entry + "the current cloud did not come out of dmi_views_fit_point_planes");
+  if (first > s->n_points || count > s->n_points - first)
+    return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "first + count must not exceed the number of points");
+  if (count == 0) return DMI_OK;
+  if (!out) return fail(s, DMI_ERR_INVALID_ARGUMENT, entry + "out is null");
+  VS_HIP(s, hipSetDevice(s->device));
+  VS_HIP(s, hipMemcpyAsync(out, s->plane_rms.as<float>() + first, (size_t)(count * 4), hipMemcpyDeviceToHost, s->stream));
+  VS_HIP(s, hipStreamSynchronize(s->stream));
+  return DMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -781,7 +845,7 @@ void dmi_views_destroy(dmi_view_set *s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   dmi::free_buffers({&s->plane[0], &s->plane[1], &s->stage_depth, &s->stage_cost, &s->label, &s->record, &s->rim_lo, &s->rim_hi,
                      &s->border_down, &s->border_right, &s->second, &s->aux, &s->flipped, &s->counts, &s->cameras, &s->state, &s->hist,
-                     &s->flags, &s->block_counts, &s->block_offsets, &s->points, &s->counters});
+                     &s->flags, &s->block_counts, &s->block_offsets, &s->points, &s->plane_rms, &s->counters});
   dmi::destroy_events(s->events);
   dmi::destroy_events(s->report_events);
   if (s->handed_over) (void)hipEventDestroy(s->handed_over);
@@ -937,6 +1001,25 @@ int dmi_views_get_radius_pass_ms(dmi_view_set *s, double out_ms[7]) {
     if (!s->points_current || !s->points_filtered)
       return fail(s, DMI_ERR_STATE, "dmi_views_get_radius_pass_ms: the current cloud did not come out of the radius filter");
     for (int e = 0; e < 7; ++e) out_ms[e] = s->radius_pass_ms[e];
+    return DMI_OK;
+  });
+}
+
+int dmi_views_fit_point_planes(dmi_view_set *s, double radius, int32_t min_neighbors, int32_t flags, dmi_points_planes_report *r) {
+  return guarded(s, "dmi_views_fit_point_planes", [&]() -> int { return fit_point_planes(s, radius, min_neighbors, flags, r); });
+}
+
+int dmi_views_download_point_plane_rms(dmi_view_set *s, uint64_t first, uint64_t count, float *out) {
+  return guarded(s, "dmi_views_download_point_plane_rms", [&]() -> int { return download_point_plane_rms(s, first, count, out); });
+}
+
+int dmi_views_get_plane_fit_pass_ms(dmi_view_set *s, double out_ms[6]) {
+  return guarded(s, "dmi_views_get_plane_fit_pass_ms", [&]() -> int {
+    if (const int rc = require_set(s, "dmi_views_get_plane_fit_pass_ms: ")) return rc;
+    if (!out_ms) return fail(s, DMI_ERR_INVALID_ARGUMENT, "dmi_views_get_plane_fit_pass_ms: out_ms is null");
+    if (!s->points_current || !s->points_fitted)
+      return fail(s, DMI_ERR_STATE, "dmi_views_get_plane_fit_pass_ms: the current cloud did not come out of the plane fit");
+    for (int e = 0; e < 6; ++e) out_ms[e] = s->plane_fit_pass_ms[e];
     return DMI_OK;
   });
 }

@@ -8,6 +8,7 @@
 #include "depth_consistency.h"
 #include "depth_holes.h"
 #include "depth_points.h"
+#include "depth_points_planes.h"
 #include "depth_points_radius.h"
 #include "depth_points_thin.h"
 #include "depth_smooth.h"
@@ -50,6 +51,11 @@ struct dmi_view_set {
   bool points_filtered = false;
   double radius_pass_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // the last filter's bounds, keys, sort, ranks, permute, count, compaction
   uint32_t radius_group_points = dmi::radius_rules::kDefaultGroupPoints;  // dmi_views_set_radius_group_points
+  // dmi_views_fit_point_planes was the cloud's last step: plane_rms f32[n_points] in a buffer of its own, dropped by whatever
+  // replaces or drops the cloud (a build, a thinning, the radius filter, a change of D)
+  dmi::DeviceBuffer plane_rms;
+  bool points_fitted = false;
+  double plane_fit_pass_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // the last fit's bounds, keys, sort, ranks, permute, fit
   double points_pass_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last build's flip, count, flags, block counts + scan, scatter
   dmi::DeviceBuffer counters;  // dmi::kVsCounters u64 (view_set_kernels.h); a build's dmi::kPtCounters stand in the same array
   hipStream_t stream = nullptr;
@@ -96,6 +102,21 @@ struct RadiusOutcome {
 const char *radius_refusal(double radius, int32_t min_neighbors);  // what is wrong with the first of them that is, or null
 int run_radius_points(const std::string &entry, const RadiusCloud &cloud, double radius, int32_t min_neighbors, uint32_t group_points,
                       uint64_t bytes_per_point, hipStream_t stream, uint64_t &held, RadiusOutcome *outcome, std::string *message);
+// dmi_capi_points_planes.hip: the plane fit of a cloud that is on the device (n in [1, 2^32), the parameters checked with
+// plane_fit_refusal by the caller).  out_xyz and out_normal, each asked for by its flag and null without it, hold copies of the
+// input (zeros for absent normals) when the call begins and are never the arrays being read: the kernel writes the fitted points
+// into them.  plane_rms f32[n] and neighbors u32[n] come back in buffers of their own, the caller's to free; everything else is
+// freed before it returns, `held` following every allocation.  DMI_OK, or a code with *message saying why: then nothing is left
+// allocated.
+struct PlaneFitOutcome {
+  DeviceBuffer plane_rms, neighbors;
+  dmi_points_planes_report report{};
+  double pass_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+};
+const char *plane_fit_refusal(double radius, int32_t min_neighbors, int32_t flags);  // what is wrong with the first that is, or null
+int run_plane_fit_points(const std::string &entry, const double *xyz, const float *normal, uint64_t n, double radius, int32_t min_neighbors,
+                         int32_t flags, uint32_t group_points, double *out_xyz, float *out_normal, hipStream_t stream, uint64_t &held,
+                         PlaneFitOutcome *outcome, std::string *message);
 // dmi_capi_speckle.hip: the four passes on a piece, an event before the first and one behind each
 hipError_t run_speckle_piece(const SpecklePiece &piece, double threshold, int32_t W, int32_t H, double abs_tolerance, double rel_tolerance,
                              int64_t min_pixels, const SpeckleTuning &tuning, hipStream_t stream, hipEvent_t events[5]);

@@ -403,6 +403,11 @@ int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_option
   out->point_cloud_min_cell_points = o.pointCloudMinCellPoints;
   out->point_cloud_outlier_radius = o.pointCloudOutlierRadiusGiven ? o.pointCloudOutlierRadius : 0.0;
   out->point_cloud_min_neighbors = o.pointCloudMinNeighbors;
+  out->point_cloud_plane_fit_radius = o.pointCloudPlaneFitRadiusGiven ? o.pointCloudPlaneFitRadius : 0.0;
+  out->point_cloud_plane_fit_min_neighbors = o.pointCloudPlaneFitMinNeighbors;
+  out->point_cloud_plane_fit_iterations = o.pointCloudPlaneFitIterations;
+  out->point_cloud_plane_fit_keep_positions = o.pointCloudPlaneFitKeepPositions ? 1 : 0;
+  out->point_cloud_plane_fit_keep_normals = o.pointCloudPlaneFitKeepNormals ? 1 : 0;
   return 1;
   });
 }

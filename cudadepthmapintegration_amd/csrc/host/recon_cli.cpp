@@ -377,6 +377,35 @@ std::vector<std::pair<std::string, Spec>> flag_table(Options *o, bool *help) {
                                       return into_count(&o->pointCloudMinNeighbors)(values) && o->pointCloudMinNeighbors >= 0 &&
                                              o->pointCloudMinNeighbors <= 0x7fffffffLL;
                                     }}},
+      {"--pointCloudPlaneFitRadius", {Kind::kValue, "with --outputPointCloudFilename: fit, on the GPU behind --pointCloudOutlierRadius and "
+                                                    "before --pointCloudCellSize, a plane to the points within this distance of every "
+                                                    "point (world units, finite, > 0), move the point onto it and give it the plane's "
+                                                    "normal; without a thinning behind it the file gets the point array PlaneRms, -1 "
+                                                    "where a point had too few neighbours (not in the reference)",
+                                      into_checked_double(&o->pointCloudPlaneFitRadius, &o->pointCloudPlaneFitRadiusGiven, [](double x) {
+                                        const double r2 = x * x;  // a normal number: dmi_views_fit_point_planes asks for it
+                                        return x > 0.0 && r2 >= 2.2250738585072014e-308 && r2 <= 1.7976931348623157e308;
+                                      })}},
+      {"--pointCloudPlaneFitMinNeighbors", {Kind::kValue, "with --pointCloudPlaneFitRadius: the other points a point needs within the "
+                                                          "radius for a fit (an integer >= 2, default 5; not in the reference)",
+                                            [o](const std::vector<std::string> &values) {
+                                              o->pointCloudPlaneFitMinNeighborsGiven = true;
+                                              return into_count(&o->pointCloudPlaneFitMinNeighbors)(values) &&
+                                                     o->pointCloudPlaneFitMinNeighbors >= 2 && o->pointCloudPlaneFitMinNeighbors <= 0x7fffffffLL;
+                                            }}},
+      {"--pointCloudPlaneFitIterations", {Kind::kValue, "with --pointCloudPlaneFitRadius: the passes, each on the result of the one "
+                                                        "before (an integer in [1, 100], default 1; not in the reference)",
+                                          [o](const std::vector<std::string> &values) {
+                                            o->pointCloudPlaneFitIterationsGiven = true;
+                                            return into_count(&o->pointCloudPlaneFitIterations)(values) &&
+                                                   o->pointCloudPlaneFitIterations >= 1 && o->pointCloudPlaneFitIterations <= 100;
+                                          }}},
+      {"--pointCloudPlaneFitKeepPositions", {Kind::kFlag, "with --pointCloudPlaneFitRadius: leave the points where they are, only "
+                                                          "replace the normals (not in the reference)",
+                                             into_flag(&o->pointCloudPlaneFitKeepPositions)}},
+      {"--pointCloudPlaneFitKeepNormals", {Kind::kFlag, "with --pointCloudPlaneFitRadius: leave the normals as they are, only move the "
+                                                        "points (not in the reference)",
+                                           into_flag(&o->pointCloudPlaneFitKeepNormals)}},
       {"--pointCloudColors", {Kind::kFlag, "with --outputPointCloudFilename: the point array Color (UInt8 RGB), each point's pixel of its "
                                            "view's Color array; every depth map file must carry one (not in the reference)",
                               into_flag(&o->pointCloudColors)}},
@@ -612,7 +641,8 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
                            std::make_pair("--pointCloudKeepDuplicates", o->pointCloudKeepDuplicates),
                            std::make_pair("--pointCloudColors", o->pointCloudColors),
                            std::make_pair("--pointCloudCellSize", o->pointCloudCellSizeGiven),
-                           std::make_pair("--pointCloudOutlierRadius", o->pointCloudOutlierRadiusGiven)})
+                           std::make_pair("--pointCloudOutlierRadius", o->pointCloudOutlierRadiusGiven),
+                           std::make_pair("--pointCloudPlaneFitRadius", o->pointCloudPlaneFitRadiusGiven)})
     if (flag.second && !pointCloud) {
       err << "Error : " << flag.first << " needs --outputPointCloudFilename.\n" << HelpText();
       return false;
@@ -623,6 +653,18 @@ bool ReadArguments(int argc, const char *const *argv, Options *o, std::ostream &
   }
   if (o->pointCloudMinNeighborsGiven && !o->pointCloudOutlierRadiusGiven) {
     err << "Error : --pointCloudMinNeighbors needs --pointCloudOutlierRadius.\n" << HelpText();
+    return false;
+  }
+  for (const auto &flag : {std::make_pair("--pointCloudPlaneFitMinNeighbors", o->pointCloudPlaneFitMinNeighborsGiven),
+                           std::make_pair("--pointCloudPlaneFitIterations", o->pointCloudPlaneFitIterationsGiven),
+                           std::make_pair("--pointCloudPlaneFitKeepPositions", o->pointCloudPlaneFitKeepPositions),
+                           std::make_pair("--pointCloudPlaneFitKeepNormals", o->pointCloudPlaneFitKeepNormals)})
+    if (flag.second && !o->pointCloudPlaneFitRadiusGiven) {
+      err << "Error : " << flag.first << " needs --pointCloudPlaneFitRadius.\n" << HelpText();
+      return false;
+    }
+  if (o->pointCloudPlaneFitKeepPositions && o->pointCloudPlaneFitKeepNormals) {
+    err << "Error : --pointCloudPlaneFitKeepPositions and --pointCloudPlaneFitKeepNormals together leave the fit nothing to do.\n" << HelpText();
     return false;
   }
   if (pointCloud) {
@@ -862,7 +904,8 @@ bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const 
 }
 
 bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
-                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged, const uint32_t *neighbors) {
+                     const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged, const uint32_t *neighbors,
+                     const float *planeRms) {
   if (nPoints < 0) {
     *error = "WritePointCloud: negative count";
     return false;
@@ -875,13 +918,14 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
   const uint64_t n = (uint64_t)nPoints, header = sizeof(uint64_t);
   const uint64_t point_bytes = n * 3 * sizeof(double), cell_bytes = n * sizeof(int64_t), normal_bytes = n * 3 * sizeof(float),
                  int_bytes = n * sizeof(int32_t), rgb_bytes = n * 3;
-  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, NbMergedPoints, NbNeighbors, Color -- [UInt64
+  // the raw block: Points, connectivity, offsets, Normals, ViewIndex, NbAgreeingViews, NbMergedPoints, NbNeighbors, PlaneRms, Color -- [UInt64
   // byte count] bytes each
   const uint64_t conn_offset = header + point_bytes, offsets_offset = conn_offset + header + cell_bytes;
   const uint64_t normal_offset = offsets_offset + header + cell_bytes, view_offset = normal_offset + header + normal_bytes;
   const uint64_t agreeing_offset = view_offset + header + int_bytes, merged_offset = agreeing_offset + header + int_bytes;
   const uint64_t neighbors_offset = merged ? merged_offset + header + int_bytes : merged_offset;
-  const uint64_t color_offset = neighbors ? neighbors_offset + header + int_bytes : neighbors_offset;
+  const uint64_t rms_offset = neighbors ? neighbors_offset + header + int_bytes : neighbors_offset;
+  const uint64_t color_offset = planeRms ? rms_offset + header + int_bytes : rms_offset;
   out << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PolyData\" version=\"1.0\" byte_order=\"LittleEndian\" "
          "header_type=\"UInt64\">\n  <PolyData>\n    <Piece NumberOfPoints=\""
       << nPoints << "\" NumberOfVerts=\"" << nPoints << "\" NumberOfLines=\"0\" NumberOfStrips=\"0\" NumberOfPolys=\"0\">\n"
@@ -893,6 +937,8 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
     out << "        <DataArray type=\"UInt32\" Name=\"NbMergedPoints\" format=\"appended\" offset=\"" << merged_offset << "\"/>\n";
   if (neighbors)
     out << "        <DataArray type=\"UInt32\" Name=\"NbNeighbors\" format=\"appended\" offset=\"" << neighbors_offset << "\"/>\n";
+  if (planeRms)
+    out << "        <DataArray type=\"Float32\" Name=\"PlaneRms\" format=\"appended\" offset=\"" << rms_offset << "\"/>\n";
   if (color)
     out << "        <DataArray type=\"UInt8\" Name=\"Color\" NumberOfComponents=\"3\" format=\"appended\" offset=\"" << color_offset
         << "\"/>\n";
@@ -921,6 +967,7 @@ bool WritePointCloud(const std::string &path, const double *points, int64_t nPoi
   write(agreeing, int_bytes);
   if (merged) write(merged, int_bytes);
   if (neighbors) write(neighbors, int_bytes);
+  if (planeRms) write(planeRms, int_bytes);
   if (color) write(color, rgb_bytes);
   out << "\n  </AppendedData>\n</VTKFile>\n";
   if (!out) {
@@ -1271,11 +1318,23 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     DepthPointsReport report;
     DepthThinReport thinned;
     DepthRadiusReport sifted;
+    DepthPlaneFitReport fitted;
+    double fit_ms = 0.0;
+    auto fit_planes = [&]() {  // each pass on the result of the one before; the report is the last one's
+      for (long long pass = 0; pass < o.pointCloudPlaneFitIterations; ++pass) {
+        if (!resident.FitPointPlanes(o.pointCloudPlaneFitRadius, (int)o.pointCloudPlaneFitMinNeighbors, !o.pointCloudPlaneFitKeepPositions,
+                                     !o.pointCloudPlaneFitKeepNormals, &fitted))
+          return false;
+        fit_ms += fitted.kernelMs;
+      }
+      return true;
+    };
     DepthPoints points;
     if (!resident.BuildPoints(o.pointCloudTolerance, o.pointCloudRelTolerance, o.pointCloudNormalTolerance, o.pointCloudNormalRelTolerance,
                               (int)o.pointCloudMinViews, (int)o.pointCloudPixelStep, !o.pointCloudKeepDuplicates, &report) ||
         (o.pointCloudOutlierRadiusGiven &&
          !resident.FilterPointsRadius(o.pointCloudOutlierRadius, (int)o.pointCloudMinNeighbors, &sifted)) ||  // strays never become cells
+        (o.pointCloudPlaneFitRadiusGiven && !fit_planes()) ||  // ... nor pull a plane; the cells then average denoised points
         (o.pointCloudCellSizeGiven && !resident.ThinPoints(o.pointCloudCellSize, (int)o.pointCloudMinCellPoints, &thinned)) ||
         !resident.DownloadPoints(&points)) {
       result->error = flag + ": " + resident.LastError();
@@ -1300,7 +1359,8 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
     if (!WritePointCloud(o.outputPointCloudFilename, points.xyz.data(), (int64_t)points.view.size(), points.normal.data(), points.view.data(),
                          points.count.data(), o.pointCloudColors ? color.data() : nullptr, &error,
                          o.pointCloudCellSizeGiven ? points.members.data() : nullptr,
-                         o.pointCloudOutlierRadiusGiven && !o.pointCloudCellSizeGiven ? points.neighbors.data() : nullptr)) {
+                         o.pointCloudOutlierRadiusGiven && !o.pointCloudCellSizeGiven ? points.neighbors.data() : nullptr,
+                         o.pointCloudPlaneFitRadiusGiven && !o.pointCloudCellSizeGiven ? points.plane_rms.data() : nullptr)) {
       result->error = error;
       return false;
     }
@@ -1333,6 +1393,25 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
            << sifted.maxNeighbors << " neighbours, " << sifted.neighborSum << " in all from " << sifted.distanceTests
            << " distance tests; " << sifted.kernelMs << " ms of GPU kernels";
       say(sift.str());
+    }
+    if (o.pointCloudPlaneFitRadiusGiven) {
+      result->pointCloudPlaneFitPointsIn = fitted.pointsIn;
+      result->pointCloudPlaneFitFitted = fitted.fitted;
+      result->pointCloudPlaneFitUnsupported = fitted.unsupported;
+      result->pointCloudPlaneFitCrowded = fitted.crowded;
+      result->pointCloudPlaneFitMaxNeighbors = fitted.maxNeighbors;
+      result->pointCloudPlaneFitNeighborSum = fitted.neighborSum;
+      result->pointCloudPlaneFitDistanceTests = fitted.distanceTests;
+      result->pointCloudPlaneFitMaxShift = fitted.maxShift;
+      result->pointCloudPlaneFitKernelMs = fit_ms;
+      std::ostringstream fit;
+      fit << "point cloud plane fit: radius " << o.pointCloudPlaneFitRadius << ", at least " << o.pointCloudPlaneFitMinNeighbors
+          << " neighbours, " << o.pointCloudPlaneFitIterations << " passes"
+          << (o.pointCloudPlaneFitKeepPositions ? ", positions kept" : o.pointCloudPlaneFitKeepNormals ? ", normals kept" : "") << "; "
+          << fitted.pointsIn << " points, " << fitted.fitted << " fitted, " << fitted.unsupported << " with too few neighbours, "
+          << fitted.crowded << " crowded, at most " << fitted.maxNeighbors << " neighbours, " << fitted.neighborSum << " in all from "
+          << fitted.distanceTests << " distance tests, the largest shift " << fitted.maxShift << "; " << fit_ms << " ms of GPU kernels";
+      say(fit.str());
     }
     if (o.pointCloudCellSizeGiven) {
       result->pointCloudCells = thinned.cells;
@@ -1755,6 +1834,16 @@ int Run(const Options &given, int argc, const char *const *argv, std::ostream &l
           << result->pointCloudRadiusMaxNeighbors << "\n  neighbours in all  " << result->pointCloudRadiusNeighborSum
           << "\n  distance tests  " << result->pointCloudRadiusDistanceTests << "\n  GPU kernels  " << result->pointCloudRadiusKernelMs
           << " ms\n";
+    if (!o.outputPointCloudFilename.empty() && o.pointCloudPlaneFitRadiusGiven)
+      out << "point cloud plane fit\n  radius  " << o.pointCloudPlaneFitRadius << "\n  minimum neighbours  " << o.pointCloudPlaneFitMinNeighbors
+          << "\n  passes  " << o.pointCloudPlaneFitIterations << "\n  positions  " << (o.pointCloudPlaneFitKeepPositions ? "kept" : "moved")
+          << "\n  normals  " << (o.pointCloudPlaneFitKeepNormals ? "kept" : "replaced") << "\n  points in  "
+          << result->pointCloudPlaneFitPointsIn << "\n  points fitted  " << result->pointCloudPlaneFitFitted
+          << "\n  points with too few neighbours  " << result->pointCloudPlaneFitUnsupported << "\n  crowded points  "
+          << result->pointCloudPlaneFitCrowded << "\n  most neighbours  " << result->pointCloudPlaneFitMaxNeighbors
+          << "\n  neighbours in all  " << result->pointCloudPlaneFitNeighborSum << "\n  distance tests  "
+          << result->pointCloudPlaneFitDistanceTests << "\n  largest shift  " << result->pointCloudPlaneFitMaxShift << "\n  GPU kernels  "
+          << result->pointCloudPlaneFitKernelMs << " ms\n";
     if (!o.outputPointCloudFilename.empty() && o.pointCloudCellSizeGiven)
       out << "point cloud thinning\n  cell size  " << o.pointCloudCellSize << "\n  minimum points per cell  " << o.pointCloudMinCellPoints
           << "\n  occupied cells  " << result->pointCloudCells << "\n  cells kept  " << result->pointCloudCellsKept

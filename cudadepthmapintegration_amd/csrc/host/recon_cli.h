@@ -168,6 +168,14 @@ struct Options {
   double pointCloudOutlierRadius = 0.0;
   long long pointCloudMinNeighbors = 1;
   bool pointCloudOutlierRadiusGiven = false, pointCloudMinNeighborsGiven = false;
+  // with pointCloudPlaneFitRadius every point that has at least pointCloudPlaneFitMinNeighbors others within that radius is moved,
+  // on the GPU behind the outlier filter and BEFORE the thinning, onto the plane fitted to them and takes that plane's normal
+  // (dmi_views_fit_point_planes), pointCloudPlaneFitIterations times, each pass on the result of the one before;
+  // KeepPositions and KeepNormals leave one of the two as it is; the .vtp gets the point array PlaneRms when no thinning follows
+  double pointCloudPlaneFitRadius = 0.0;
+  long long pointCloudPlaneFitMinNeighbors = 5, pointCloudPlaneFitIterations = 1;
+  bool pointCloudPlaneFitKeepPositions = false, pointCloudPlaneFitKeepNormals = false;
+  bool pointCloudPlaneFitRadiusGiven = false, pointCloudPlaneFitMinNeighborsGiven = false, pointCloudPlaneFitIterationsGiven = false;
 };
 
 // rmain:216-343.  false: do not run (an error or --help; the text went to `err`).
@@ -241,6 +249,11 @@ struct RunResult {
   unsigned long long pointCloudRadiusPointsIn = 0, pointCloudRadiusPointsKept = 0, pointCloudRadiusIsolated = 0,
                      pointCloudRadiusMaxNeighbors = 0, pointCloudRadiusNeighborSum = 0, pointCloudRadiusDistanceTests = 0;
   double pointCloudRadiusKernelMs = 0.0;
+  // --pointCloudPlaneFitRadius: the report of the last pass (include/dmi.h: dmi_points_planes_report); the kernel time of all passes
+  unsigned long long pointCloudPlaneFitPointsIn = 0, pointCloudPlaneFitFitted = 0, pointCloudPlaneFitUnsupported = 0,
+                     pointCloudPlaneFitCrowded = 0, pointCloudPlaneFitMaxNeighbors = 0, pointCloudPlaneFitNeighborSum = 0,
+                     pointCloudPlaneFitDistanceTests = 0;
+  double pointCloudPlaneFitMaxShift = 0.0, pointCloudPlaneFitKernelMs = 0.0;
 };
 // rmain:97-213, the contour with --extractMesh only: 0 on success.  `log` receives what --verbose prints.
 int Run(const Options &o, int argc, const char *const *argv, std::ostream &log, RunResult *result);
@@ -265,10 +278,11 @@ bool WritePolyData(const std::string &path, const double *points, int64_t nPoint
 // and, with `color` ([nPoints][3] u8), Color (UInt8 x 3) behind them; with `merged` ([nPoints] u32: the points each point of a thinned
 // cloud was merged from) NbMergedPoints (UInt32) behind NbAgreeingViews.  Without `merged` the file is what it was before the array existed.
 // With `neighbors` ([nPoints] u32: the points within the outlier filter's radius) NbNeighbors (UInt32) behind those and before Color;
-// without it the file is what it was before that array existed.
+// without it the file is what it was before that array existed.  With `planeRms` ([nPoints] f32: the RMS distance of each point's
+// ball from its fitted plane, -1 without a fit) PlaneRms (Float32) behind those and before Color; without it likewise.
 bool WritePointCloud(const std::string &path, const double *points, int64_t nPoints, const float *normals, const int32_t *view,
                      const int32_t *agreeing, const uint8_t *color, std::string *error, const uint32_t *merged = nullptr,
-                     const uint32_t *neighbors = nullptr);
+                     const uint32_t *neighbors = nullptr, const float *planeRms = nullptr);
 bool WriteStructuredGrid(const std::string &path, const int pointDims[3], const double origin[3], const double spacing[3],
                          const double gridMatrix[16], const double *cellScalars, const char *arrayName, std::string *error);
 

@@ -1008,6 +1008,7 @@ bool DepthViewSet::BuildPoints(double absTolerance, double relTolerance, double 
     return Fail("dmi_views_build_points");
   NPoints = n;
   Filtered = false;
+  Fitted = false;
   if (report) {
     *report = DepthPointsReport();
     report->views = NViews;
@@ -1027,6 +1028,7 @@ bool DepthViewSet::ThinPoints(double cellSize, int minPoints, DepthThinReport *r
   if ((Code = dmi_views_thin_points(Set, cellSize, (int32_t)minPoints, &n, &r)) != DMI_OK) return Fail("dmi_views_thin_points");
   NPoints = n;
   Filtered = false;
+  Fitted = false;
   if (report) {
     *report = DepthThinReport();
     report->pointsIn = r.points_in;
@@ -1047,6 +1049,7 @@ bool DepthViewSet::FilterPointsRadius(double radius, int minNeighbors, DepthRadi
     return Fail("dmi_views_filter_points_radius");
   NPoints = n;
   Filtered = true;
+  Fitted = false;
   if (report) {
     *report = DepthRadiusReport();
     report->pointsIn = r.points_in;
@@ -1060,8 +1063,32 @@ bool DepthViewSet::FilterPointsRadius(double radius, int minNeighbors, DepthRadi
   return true;
 }
 
+bool DepthViewSet::FitPointPlanes(double radius, int minNeighbors, bool move, bool normals, DepthPlaneFitReport *report) {
+  dmi_points_planes_report r;
+  const int32_t flags = (move ? DMI_PLANE_FIT_MOVE : 0) | (normals ? DMI_PLANE_FIT_NORMALS : 0);
+  if ((Code = dmi_views_fit_point_planes(Set, radius, (int32_t)minNeighbors, flags, &r)) != DMI_OK)
+    return Fail("dmi_views_fit_point_planes");
+  Fitted = true;
+  if (report) {
+    *report = DepthPlaneFitReport();
+    report->pointsIn = r.points_in;
+    report->fitted = r.fitted;
+    report->unsupported = r.unsupported;
+    report->crowded = r.crowded;
+    report->maxNeighbors = r.max_neighbors;
+    report->neighborSum = r.neighbor_sum;
+    report->distanceTests = r.distance_tests;
+    report->maxShift = r.max_shift;
+    report->kernelMs = r.kernel_ms;
+  }
+  return true;
+}
+
 bool DepthViewSet::DownloadPoints(DepthPoints *points) {
   const size_t n = (size_t)NPoints;
+  points->plane_rms.resize(Fitted ? n : 0);
+  if (Fitted && (Code = dmi_views_download_point_plane_rms(Set, 0, NPoints, points->plane_rms.data())) != DMI_OK)
+    return Fail("dmi_views_download_point_plane_rms");
   points->neighbors.resize(Filtered ? n : 0);
   if (Filtered && (Code = dmi_views_download_point_neighbors(Set, 0, NPoints, points->neighbors.data())) != DMI_OK)
     return Fail("dmi_views_download_point_neighbors");

@@ -186,6 +186,7 @@ struct DepthPoints {
   std::vector<int32_t> view, pixel, count;  // [n]: the view, py * W + px in image coordinates, the views that agree
   std::vector<uint32_t> members;            // [n]: the points each was merged from (1 unless DepthViewSet::ThinPoints has run)
   std::vector<uint32_t> neighbors;          // [n] where DepthViewSet::FilterPointsRadius made the cloud, else empty: the points within the radius
+  std::vector<float> plane_rms;             // [n] where DepthViewSet::FitPointPlanes was the cloud's last step, else empty: -1 without a fit
 };
 // ... and the report of a thinning of it on a voxel grid (dmi_views_thin_points)
 struct DepthThinReport {
@@ -197,6 +198,13 @@ struct DepthThinReport {
 struct DepthRadiusReport {
   uint64_t pointsIn = 0, pointsKept = 0, isolated = 0, maxNeighbors = 0, neighborSum = 0, distanceTests = 0;
   double kernelMs = 0.0;  // hipEvent time of the filter's kernels
+};
+
+// ... and of a plane fit of it (dmi_views_fit_point_planes)
+struct DepthPlaneFitReport {
+  uint64_t pointsIn = 0, fitted = 0, unsupported = 0, crowded = 0, maxNeighbors = 0, neighborSum = 0, distanceTests = 0;
+  double maxShift = 0.0;
+  double kernelMs = 0.0;  // hipEvent time of the fit's kernels
 };
 
 // Not in the reference: the views' depths resident on one GPU from the first of the steps above to the fusion (dmi_view_set,
@@ -231,6 +239,10 @@ class DepthViewSet {
   // The cloud, built or thinned, replaced on the device by its points that have at least minNeighbors other points within radius,
   // in their order (any number of times); DownloadPoints then brings the kept points with their counts
   bool FilterPointsRadius(double radius, int minNeighbors, DepthRadiusReport *report);
+  // The cloud, built, thinned or filtered, with every point that has at least minNeighbors others within radius moved onto the
+  // plane fitted to them (move) and carrying that plane's normal (normals), in its order and layout (any number of times: each call
+  // is a pass); DownloadPoints then brings plane_rms too
+  bool FitPointPlanes(double radius, int minNeighbors, bool move, bool normals, DepthPlaneFitReport *report);
   bool DownloadPoints(DepthPoints *points);
   int Width() const { return W; }
   int Height() const { return H; }
@@ -249,6 +261,7 @@ class DepthViewSet {
   size_t NViews = 0;
   uint64_t NPoints = 0;  // of the last BuildPoints
   bool Filtered = false;  // the cloud came out of FilterPointsRadius
+  bool Fitted = false;    // FitPointPlanes was the cloud's last step
   int W = 0, H = 0, Dev = 0;
   std::string Error;
   int Code = 0;

@@ -55,7 +55,7 @@ extern "C" {
                            *    dmi_estimate_scene_bounds; dmi_fill_isosurface_holes, dmi_get_isosurface_holes_kernel_ms,
                            *    dmi_get_isosurface_holes_pass_ms; dmi_point_smoothing_weights, dmi_set_point_smoothing,
                            *    dmi_get_point_smoothing, dmi_get_point_smoothing_kernel_ms; dmi_filter_depth_speckles;
-                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms; dmi_thin_point_cloud, dmi_views_thin_points, dmi_views_download_point_members, dmi_views_get_thin_pass_ms, dmi_views_set_thin_wave_cell_points; dmi_count_point_neighbors, dmi_views_filter_points_radius, dmi_views_download_point_neighbors, dmi_views_get_radius_pass_ms, dmi_views_set_radius_group_points */
+                           *    dmi_fill_depth_holes; dmi_depth_smoothing_weights, dmi_smooth_depths; dmi_views_build_points, dmi_views_download_points, dmi_views_get_points_pass_ms; dmi_thin_point_cloud, dmi_views_thin_points, dmi_views_download_point_members, dmi_views_get_thin_pass_ms, dmi_views_set_thin_wave_cell_points; dmi_count_point_neighbors, dmi_views_filter_points_radius, dmi_views_download_point_neighbors, dmi_views_get_radius_pass_ms, dmi_views_set_radius_group_points; dmi_fit_point_planes, dmi_views_fit_point_planes, dmi_views_download_point_plane_rms, dmi_views_get_plane_fit_pass_ms */
 
 typedef struct dmi_context dmi_context;
 
@@ -1227,6 +1227,84 @@ int dmi_views_filter_points_radius(dmi_view_set *s, double radius, int32_t min_n
 int dmi_views_download_point_neighbors(dmi_view_set *s, uint64_t first, uint64_t count, uint32_t *out);
 int dmi_views_get_radius_pass_ms(dmi_view_set *s, double out_ms[7]);
 int dmi_views_set_radius_group_points(dmi_view_set *s, int32_t k);
+
+/* ---- Local planes fitted to the point cloud: denoised positions, new normals (added after round 5,
+ * dmi_abi_version() stays 5) ----
+ * A plane fitted to the points within a radius of every point, the point moved onto it along the plane's normal and its normal
+ * replaced by the plane's: what PCL's MovingLeastSquares (a plane, unweighted) and NormalEstimation, or Open3D's estimate_normals,
+ * do to a cloud (only the intent is shared, not the numbers).  A floating-point sum over neighbours depends on its order; here the
+ * sums are sums of integers -- the offsets are rounded to a power-of-two lattice of 2^-15 to 2^-16 of the radius --, and the fit
+ * from them is written down operation for operation, so the result is defined to the bit whatever the schedule.
+ * csrc/depth_points_planes.hip, csrc/depth_points_planes_rules.h.  Definition, met bit for bit by the device and by
+ * tests/depth_points_planes_np.py, which goes over all pairs.
+ * The input is P points xyz f64[P][3] in a given order and, optionally, normal f32[P][3] (absent: zeros).  Parameters: radius,
+ * min_neighbors >= 2, flags (DMI_PLANE_FIT_MOVE, DMI_PLANE_FIT_NORMALS or both; 0 is refused).  All arithmetic is f64, with every
+ * operation rounded on its own and no FMA; comparisons with a NaN are false; divisions and the square root are correctly rounded.
+ *   1. MEMBERS.  r2 = radius * radius.  For every j, j = i included: d_k = xyz[j][k] - xyz[i][k], d2 = (d_0*d_0 + d_1*d_1) + d_2*d_2;
+ *      j is a MEMBER of i's ball iff d2 <= r2.  m is the number of members and neighbors[i] = m - 1: exactly
+ *      dmi_count_point_neighbors' count.
+ *   2. LATTICE.  radius = f * 2^e with f in [0.5, 1) (frexp).  s = 2^(15 - e), inv_s = 2^(e - 15).  q_k = rint(d_k * s), ties to
+ *      even, an integer.  For a member |d_k| <= radius (1 + 2^-51), so |q_k| <= 2^15.
+ *   3. MOMENTS over the members: S_k = sum q_k, T_ab = sum q_a q_b for ab in 00, 01, 02, 11, 12, 22.  Sums of integers: any order
+ *      gives the same value, and with m <= 2^22 every partial sum is below 2^52, exact in an f64.  A point with m > 2^22 is CROWDED:
+ *      it is left as it is and counted.
+ *   4. FIT, only if m - 1 >= min_neighbors; otherwise the point is UNSUPPORTED and left as it is.  c_k = S_k / m.
+ *      C_ab = T_ab / m - c_a*c_b (the quotient, the product, then the difference).  A = C, V = the identity.  Six sweeps of cyclic
+ *      Jacobi over the pairs (p, q) = (0,1), (0,2), (1,2), r the third index, a = A_pq; the pair is skipped if a == 0, otherwise:
+ *        theta = (A_qq - A_pp) / (2*a);  t = sgn(theta) / (fabs(theta) + sqrt(theta*theta + 1)), sgn(x) = -1 iff x < 0, else +1 (an
+ *        infinite theta*theta gives t = +-0);  c = 1 / sqrt(t*t + 1);  sigma = t*c;
+ *        A_pp = A_pp - t*a;  A_qq = A_qq + t*a;  A_pq = 0;
+ *        (A_rp, A_rq) = (c*A_rp - sigma*A_rq, sigma*A_rp + c*A_rq), from the old values;
+ *        (V_kp, V_kq) = (c*V_kp - sigma*V_kq, sigma*V_kp + c*V_kq) for k = 0, 1, 2.
+ *      lambda_k = A_kk.  The normal n is column k of V for the smallest lambda_k (the lowest index at ties: 1 replaces 0 iff
+ *      lambda_1 < lambda_0, 2 replaces that iff lambda_2 is smaller still), divided by sqrt((n_0*n_0 + n_1*n_1) + n_2*n_2).
+ *   5. ORIENTATION.  o = the point's old normal widened to f64.  g = (n_0*o_0 + n_1*o_1) + n_2*o_2.  g < 0 negates n.  If g == 0 (a
+ *      zero old normal, or no normals given) the component of largest magnitude is made positive (the lowest index at ties).
+ *   6. RESULTS.  plane_rms[i] = (float)(sqrt(max(lambda_min, 0)) * inv_s): the RMS distance of the ball's lattice points from the
+ *      plane.  With MOVE: t = ((c_0*n_0 + c_1*n_1) + c_2*n_2) * inv_s and xyz'[i][k] = xyz[i][k] + t*n_k (the product, then the sum).
+ *      With NORMALS: normal'[i][k] = (float)n_k.  An array whose flag is not set keeps its bits.  Unsupported and crowded points keep
+ *      the bits of both arrays and get plane_rms = -1.  Everything is computed from the input cloud; nothing is iterated: a second
+ *      call is a second pass.  The order and every other array of the cloud keep their bits.
+ *   7. REPORT (dmi_points_planes_report).  points_in: P.  fitted, unsupported, crowded: they add up to P.  max_neighbors,
+ *      neighbor_sum, distance_tests: as in dmi_points_radius_report (distance_tests counts a point's test against itself).
+ *      max_shift: the largest fabs(t) of step 6 (0 without MOVE).  kernel_ms: the hipEvent time of the call's kernels.
+ * The lattice's cost: on a noisy sphere cap (sigma 0.004, radii 0.05 and 0.1) the moved positions differ from those of the same fit
+ * on a 2^20 lattice by at most 1.2e-5 of the radius, 3 to 4 thousand times below the noise.
+ * DMI_ERR_INVALID_ARGUMENT, before the device is touched: what dmi_count_point_neighbors refuses in a radius, and a radius for which
+ * s or inv_s is not a normal finite number; min_neighbors < 2; flags outside {1, 2, 3}; P >= 2^32; a null xyz, or a null output
+ * whose flag is set; a device out of range.  A non-finite coordinate, found by the bounds pass, is refused with the same code.
+ *
+ * dmi_fit_point_planes is context-free: the coordinates go up in pieces; out_xyz[P][3] (with MOVE), out_normal[P][3] (with NORMALS),
+ * out_plane_rms[P] and out_neighbors[P] come back, each nullable where not asked for (an output whose flag is not set is not
+ * written).  P == 0 is a success that touches no device.  A call that is refused or fails leaves the outputs untouched.
+ * dmi_last_error(NULL) has the text.
+ *
+ * dmi_views_fit_point_planes runs the same implementation on the set's current cloud -- built, thinned or filtered -- and replaces it
+ * by a cloud of the same layout (members and the filter's neighbors stay where they are) with the new positions and normals: a
+ * buffer of its own, swapped in last, so a call that is refused or fails leaves the old cloud.  DMI_ERR_STATE without a current
+ * cloud.  It may be called repeatedly: each call is a pass over the cloud it finds.  A success counts as a step in
+ * dmi_views_info::steps; device_bytes follows every allocation, and after the call holds the cloud's bytes and 4 bytes per point of
+ * plane_rms, in a buffer of its own that whatever replaces or drops the cloud drops: a build, dmi_views_thin_points,
+ * dmi_views_filter_points_radius, a change of the depths.  dmi_views_thin_points after a fit gives what dmi_thin_point_cloud gives
+ * for the downloaded arrays.  dmi_views_set_radius_group_points applies to the fit kernel as to the count kernel.  During the call
+ * the set holds 60 bytes per point besides the two clouds, freed when it ends.
+ *   dmi_views_download_point_plane_rms   plane_rms of the points [first, first + count).  DMI_ERR_STATE unless the fit was the
+ *              cloud's last step.
+ *   dmi_views_get_plane_fit_pass_ms   the last fit's kernel time by pass: bounds, keys, sort, ranks, permute, fit.  DMI_ERR_STATE
+ *              unless the fit was the cloud's last step. */
+#define DMI_PLANE_FIT_MOVE 1
+#define DMI_PLANE_FIT_NORMALS 2
+typedef struct dmi_points_planes_report {
+  uint64_t points_in, fitted, unsupported, crowded, max_neighbors, neighbor_sum, distance_tests;
+  double max_shift, kernel_ms;
+} dmi_points_planes_report;
+int dmi_fit_point_planes(const double *xyz, const float *normal /* nullable */, uint64_t n_points, double radius, int32_t min_neighbors,
+                         int32_t flags, int32_t device, double *out_xyz, float *out_normal, float *out_plane_rms,
+                         uint32_t *out_neighbors /* each nullable where not asked for */, dmi_points_planes_report *r /* nullable */);
+int dmi_views_fit_point_planes(dmi_view_set *s, double radius, int32_t min_neighbors, int32_t flags,
+                               dmi_points_planes_report *r /* nullable */);
+int dmi_views_download_point_plane_rms(dmi_view_set *s, uint64_t first, uint64_t count, float *out);
+int dmi_views_get_plane_fit_pass_ms(dmi_view_set *s, double out_ms[6]);
 
 /* ---- One fusion over several MI355X of a node (north star: "depth maps shard across the 8 GPUs of one node with a
  * single RCCL all-reduce of the float TSDF grid over xGMI").  The reference has nothing of the kind (one GPU, default

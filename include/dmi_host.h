@@ -148,6 +148,12 @@ typedef struct dmi_cli_options {
   /* not in the reference, only with --outputPointCloudFilename (dmi_views_filter_points_radius, dmi.h); appended to the struct: */
   double point_cloud_outlier_radius;     /* --pointCloudOutlierRadius r: drop the points with too few neighbours within r, before the thinning; 0: not given */
   int64_t point_cloud_min_neighbors;     /* --pointCloudMinNeighbors N (default 1) */
+  /* not in the reference, only with --outputPointCloudFilename (dmi_views_fit_point_planes, dmi.h); appended to the struct: */
+  double point_cloud_plane_fit_radius;            /* --pointCloudPlaneFitRadius r: fit planes within r, behind the outlier filter and before the thinning; 0: not given */
+  int64_t point_cloud_plane_fit_min_neighbors;    /* --pointCloudPlaneFitMinNeighbors N (default 5) */
+  int64_t point_cloud_plane_fit_iterations;       /* --pointCloudPlaneFitIterations k (default 1) */
+  int32_t point_cloud_plane_fit_keep_positions;   /* --pointCloudPlaneFitKeepPositions */
+  int32_t point_cloud_plane_fit_keep_normals;     /* --pointCloudPlaneFitKeepNormals */
 } dmi_cli_options;
 /* 1: the run may proceed, *out filled.  0: an error or --help; the text (what the tool would print) in err. */
 int dmi_cli_read_arguments(int32_t argc, const char *const *argv, dmi_cli_options *out, char *err, size_t errlen);
